@@ -23,6 +23,12 @@ correlation stage is a fixed-size job that the ranks share.  `--workload weak5n`
 correlation work fixed instead (5 N sections; round-1's variant).  `--workload prestitch --gpus N` is the
 cross-CCD path (BASELINE config 5; `--fp16-accumulate` for its resampling variant).
 
+A plain run sets up, warms up, times exactly `--steps` steps and prints the headline figure.  Everything else the bench
+measures or checks -- the per-kernel table and the roofline (an instrumented step), the CPU baselines, the PCIe-inclusive
+pass, the timed runs of the `oip` executable, the other BASELINE configurations, the N-GPU stage times and the verbose
+record -- runs with `--full` only.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy
+(float32 / float64; a fixed, seeded sample of the large rasters), so two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -39,6 +45,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_SAMPLE = 1 << 22          # --dump-outputs: values kept of a large output raster, over all ranks (16 MB as float32)
 
 
 def parse():
@@ -66,11 +73,21 @@ def parse():
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the PCIe-inclusive pass from pageable host buffers")
     ap.add_argument("--no-cli", action="store_true", help="skip the timed run of the `oip` executable on files in tmpfs (the `cli` object)")
     ap.add_argument("--full-record", default=None,
-                    help="where the verbose record goes (default gpurun_out/bench_full.json); stdout carries the compact line")
+                    help="where the verbose record of a --full run goes (giving it implies --full); stdout carries the compact line")
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the short legs for the other single-GPU BASELINE configs (2, 3, 5 at N=1, 12288-wide) that "
                          "the default one-GPU run attaches as `configs`")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: per-kernel table and roofline, CPU baseline, PCIe-inclusive pass, timed `oip` "
+                         "runs, the other BASELINE configurations, N-GPU stage times and the verbose record (the --no-* switches "
+                         "above leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, about "
+                         "%d MB in all: a fixed, seeded sample of each large raster)" % (2 * DUMP_SAMPLE * 4 >> 20))
+    a = ap.parse_args()
+    if a.full_record:
+        a.full = True
+    return a
 
 
 # algorithmic HBM bytes per launch of each kernel, keyed by the name the
@@ -632,7 +649,7 @@ def build_workload(env, p):
 
         def step():
             ctx.rrc_u16(raw_pan, dst, W, pb, d_kb_pan)
-        d.__dict__.update(step=step, pix_per_rank=W * pb, base_rows=1, base_cols=1, M=1, N=1, out_local=0,
+        d.__dict__.update(step=step, pix_per_rank=W * pb, base_rows=1, base_cols=1, M=1, N=1, out_local=0, dst=dst,
                           workload="RRC kernel only, %dx%d u16 per GPU (BASELINE config 2)" % (W, pb))
     else:
         # default: the reference's sections for the WHOLE strip, whatever its length (BASELINE config 4);
@@ -675,7 +692,7 @@ def measure(env, d, steps, warmup):
     step when --warmup 0), recorded by the library on the stream the kernels run on.  The events cost about 2 % of a
     step, so the timed region times only the dominant kernel found there -- which is the kernel the roofline object is
     about."""
-    ctx, torch, dist = env.ctx, env.torch, env.dist
+    ctx = env.ctx
     for _ in range(max(warmup - 1, 0)):
         d.step()
     ctx.profile_filter(None)
@@ -699,15 +716,86 @@ def measure(env, d, steps, warmup):
     ctx.profile_enable(False)
     ctx.profile_filter(None)
     prof = ctx.profile()                     # the dominant kernel, over the timed region
-    t = torch.tensor([elapsed], dtype=torch.float64, device=env.dev if env.dist_backend == "nccl" else "cpu")
+    return max_over_ranks(env, elapsed), prof_all, prof, dom
+
+
+def max_over_ranks(env, seconds):
+    t = env.torch.tensor([seconds], dtype=env.torch.float64, device=env.dev if env.dist_backend == "nccl" else "cpu")
     if env.world > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    return float(t.item()), prof_all, prof, dom
+        env.dist.all_reduce(t, op=env.dist.ReduceOp.MAX)
+    return float(t.item())
+
+
+def time_steps(env, d, steps, warmup):
+    """The plain run's measurement: W untimed warm-up steps, then exactly K timed steps between barriers, no kernel
+    carrying events; max over ranks."""
+    for _ in range(warmup):
+        d.step()
+    env.barrier()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        d.step()
+    env.ctx.sync()
+    env.barrier()
+    return max_over_ranks(env, time.perf_counter() - t0)
+
+
+def rate(env, d, elapsed, steps):
+    """(ms_per_step, Mpix/s over all ranks) of `steps` steps that took `elapsed` seconds"""
+    return elapsed / steps * 1e3, d.pix_per_rank * env.world * steps / elapsed / 1e6
+
+
+def step_outputs(d, p):
+    """What a caller of the timed path receives from a step, by name: device rasters, or host arrays for the small results."""
+    if p.workload == "rrc":
+        return {"rrc_pan": d.dst}
+    if p.workload == "prestitch":
+        out = {"stitched": d.stitched, "shift": np.array([d.info["dx"], d.info["dy"]], np.float64)}
+        if not getattr(p, "fused", False):           # the fused passes never write the resampled CCD-2 raster
+            out["prestt"] = d.prestt
+        return out
+    return {"aligned_mss": d.out, "rrc_pan": d.bufs.pan, "fit_cx": np.asarray(d.info["cx"], np.float64),
+            "fit_cy": np.asarray(d.info["cy"], np.float64)}
+
+
+def dump_outputs(env, d, p, path):
+    """--dump-outputs: every output of the last step as path/<name>.npy (rank suffix when N > 1).  Rasters up to
+    DUMP_SAMPLE / N values are written whole as float32 (u16 values are exact); larger ones as the values at a fixed
+    set of flat positions (seeded, sorted, drawn with replacement), the same for every run with the same arguments."""
+    torch = env.torch
+    env.ctx.sync()
+    os.makedirs(path, exist_ok=True)
+    keep = DUMP_SAMPLE // env.world
+    suffix = "_rank%d" % env.rank if env.world > 1 else ""
+    for i, (name, x) in enumerate(sorted(step_outputs(d, p).items())):
+        if torch.is_tensor(x):
+            flat = x.reshape(-1)
+            u16 = flat.dtype == torch.uint16
+            if u16:
+                flat = flat.view(torch.int16)        # gathers on uint16 tensors are not implemented everywhere
+            if flat.numel() > keep:
+                pos = np.sort(np.random.default_rng(1000 + i).integers(0, flat.numel(), keep))
+                flat = flat[torch.from_numpy(pos).to(flat.device)]
+            v = flat.cpu().numpy()
+            x = (v.view(np.uint16) if u16 else v).astype(np.float32)
+        np.save(os.path.join(path, name + suffix + ".npy"), x)
+
+
+def headline(env, d, p, args, ms_per_step, value):
+    """The keys every line carries (the bench contract's and the workload's description)"""
+    return {
+        "metric": "Mpix/s end-to-end RRC+stitch on 30000x100000x4 strip; % HBM roofline",
+        "value": value, "unit": "Mpix/s", "n_gpus": env.world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u16 rasters; fp64 RRC/maps, f32 bicubic and FFT", "data": "synthetic",
+        "config": {"workload": d.workload, "width": d.W, "pan_lines_per_gpu": d.pb, "parallelism": "rowblock%d" % env.world,
+                   "backend": "rccl" if env.dist_backend == "nccl" else env.dist_backend + " (rehearsal, host-staged)",
+                   "ibc_threshold": p.threshold, "inputs": "resident in HBM"},
+    }
 
 
 def summarise(env, d, p, elapsed, steps, prof_all, prof, dom):
-    ms_per_step = elapsed / steps * 1e3
-    value = d.pix_per_rank * env.world * steps / elapsed / 1e6
+    ms_per_step, value = rate(env, d, elapsed, steps)
     ab = algorithmic_bytes(d.W, d.pb, d.M, d.N, d.base_rows, d.base_cols, d.out_local, d.rows_arrays)
     kernels = {}
     for name, (ms, n) in prof_all.items():
@@ -1012,27 +1100,38 @@ def main():
     p = Params(workload=args.workload, width=args.width, lines=args.lines, slices=args.slices, sections=args.sections,
                threshold=args.ibc_threshold, fp16=args.fp16_accumulate, fused=args.fused)
     d = build_workload(env, p)
+    if not args.full:
+        elapsed = time_steps(env, d, args.steps, args.warmup)
+        if args.dump_outputs:
+            dump_outputs(env, d, p, args.dump_outputs)
+        if rank == 0:
+            line = headline(env, d, p, args, *rate(env, d, elapsed, args.steps))
+            if args.workload == "prestitch":
+                line["shift"] = {"dx": d.info.get("dx"), "dy": d.info.get("dy"), "truth_px": list(synth.CCD_SHIFT)}
+            line["value_note"] = ("`value`: rasters resident in HBM when the timed region starts; per-kernel times, roofline, CPU "
+                                  "baseline, PCIe- and file-inclusive figures and the other configurations: --full")
+            print(json.dumps(line))
+        if world > 1:
+            dist.destroy_process_group()
+        ctx.close()
+        return
     elapsed, prof_all, prof, dom = measure(env, d, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(env, d, p, args.dump_outputs)
     multi_gpu = multi_gpu_stage_times(env, d) if world > 1 and args.workload != "rrc" else None
 
     if rank == 0:
         W, pb = d.W, d.pb
         ms_per_step, value, kernels, roof = summarise(env, d, p, elapsed, args.steps, prof_all, prof, dom)
-        line = {
-            "metric": "Mpix/s end-to-end RRC+stitch on 30000x100000x4 strip; % HBM roofline",
-            "value": value, "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u16 rasters; fp64 RRC/maps, f32 bicubic and FFT", "data": "synthetic",
-            "config": {"workload": d.workload, "width": W, "pan_lines_per_gpu": pb, "parallelism": "rowblock%d" % world,
-                       "backend": "rccl" if dist_backend == "nccl" else dist_backend + " (rehearsal, host-staged)",
-                       "ibc_threshold": p.threshold, "inputs": "resident in HBM"},
+        line = headline(env, d, p, args, ms_per_step, value)
+        line.update({
             "value_note": ("`value` is the whole step with the rasters already resident in HBM when the timed region starts (the bench "
                            "contract); the PCIe-inclusive rate of the same step -- pageable host rasters in, aligned image out, file "
                            "I/O excluded -- is the `end_to_end` object of this line and is never `value`"),
             "roofline": roof,
             "kernels": kernels,
             "kernels_note": "per-kernel HIP-event times of one untimed step, except the dominant kernel: timed over the timed region (where only it carries events)",
-        }
+        })
         r = rrc_line(kernels)
         if r:
             line["rrc_kernel"] = r

@@ -1,5 +1,6 @@
 import os, sys, numpy as np, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+_R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, _R); sys.path.insert(0, os.path.join(_R, "tests"))
 import opticalimageprocessor_amd as oip
 import _synth
 ctx = oip.Context(0)
