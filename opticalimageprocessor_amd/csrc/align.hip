@@ -491,8 +491,7 @@ extern "C" int oip_align_mss_bicubic_u16x4(oip_ctx *ctx, const uint16_t *d_plane
     }
     // fast path: 8 pixels of one band per lane; needs even widths (dword-aligned sample pairs) and 16-byte aligned
     // output lines
-    static const char *envf = getenv("OIP_ALIGN_GENERAL");              // test knob: force the general kernel
-    const bool fast = !(envf && atoi(envf)) && Wb % 2 == 0 && Wb >= 16 && (((uintptr_t)d_dst) & 15) == 0 &&
+    const bool fast = Wb % 2 == 0 && Wb >= 16 && (((uintptr_t)d_dst) & 15) == 0 &&
                       (((uintptr_t)d_planes) & 3) == 0 && (plane_stride % 2) == 0 && src_rows * (long)Wb >= 16;
     const int groups = (Wb + 7) / 8;
     int gx = (groups + 63) / 64;                                  // 4 waves x 16 groups per workgroup

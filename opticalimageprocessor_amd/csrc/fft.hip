@@ -621,12 +621,7 @@ __global__ __launch_bounds__(NT) void fft_pass_ct_kernel(float2 *__restrict__ da
             }
         }
     };
-    if (IOK == 1 && (p.dbg & 1)) {
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) zz[i] = make_float2(1.f, 0.f);
-    } else {
-        issue_loads(t);
-    }
+    issue_loads(t);
     for (int i = threadIdx.x; i < TWN; i += kFftBlock) tw[i] = twF[i];
 
     {
@@ -654,7 +649,7 @@ __global__ __launch_bounds__(NT) void fft_pass_ct_kernel(float2 *__restrict__ da
         }
         __syncthreads();
 
-        if (!(IOK == 1 && (p.dbg & 2))) Stages<F, VS, Vp, NT, 1, Rs...>::run(buf, tw);
+        Stages<F, VS, Vp, NT, 1, Rs...>::run(buf, tw);
 
         if ((IOK == 2 && io.store_kind == 1)) {
             // the scan of the tile ends (barrier inside store_peak) before the scratch is written
@@ -669,7 +664,7 @@ __global__ __launch_bounds__(NT) void fft_pass_ct_kernel(float2 *__restrict__ da
             for (int e = threadIdx.x; e < TOTAL; e += kFftBlock) {
                 const int v = MODE == 0 ? (e & (V - 1)) : e / F;
                 const int n = MODE == 0 ? (e >> VS) : e - v * F;
-                if (v >= t.nv || (IOK == 1 && (p.dbg & 4))) continue;
+                if (v >= t.nv) continue;
                 float2 z = buf[n * Vp + v];
                 if (p.inverse) z.y = -z.y;
                 else if (tile_tw) z = cmul(z, twj[n]);
@@ -691,13 +686,13 @@ __global__ __launch_bounds__(NT) void fft_pass_ct_kernel(float2 *__restrict__ da
 // trips and four barriers instead of five and nine.  The tile maximum is folded into the arg-max slots per
 // WAVE (a value reduction on the DPP path, then an atomicMax by the lanes that hold the maximum -- one lane
 // unless values tie, and atomicMax orders ties by key itself): no LDS hand-off between the waves.
-// Round 2: 0.128 -> 0.104 ms per launch.  Round 3 took the pass apart (profiles/experiments/peak_dbg.sh,
+// Round 2: 0.128 -> 0.104 ms per launch.  Round 3 took the pass apart (profiles/experiments/r03_peak_dbg_result.txt,
 // strided_rows_read.hip): its loads alone take 0.064 ms (the bare pattern reads at 6 TB/s), its arithmetic alone 0.069,
 // loads + first stage 0.0955 -- and 19 % of the bare pattern's time came back when the tile's 128 inter-pass twiddles
 // were GATHERED from table T at a stride of 8 o bytes: 128 more cache lines per tile, requested behind the data and
 // requested behind the data.  They are now one contiguous 1 KiB row per tile row (get_pass_table): 0.104 -> 0.088 ms.
-// Walking several tile rows per workgroup with the next tile's loads in flight (OIP_PEAK_TILES), or fetching two or three
-// tiles up front, changes nothing.
+// Walking several tile rows per workgroup with the next tile's loads in flight, or fetching two or three tiles up front,
+// changes nothing.
 //
 // maximum over the 64 lanes of a wave on the DPP path (no LDS traffic): quad swaps, the two row mirrors, then the row
 // broadcasts of gfx9 bring the maximum of everything to lane 63.  fmaxf semantics per step (a NaN loses against a number);
@@ -1007,7 +1002,7 @@ __global__ __launch_bounds__(NT) void fft_first_pass_up_kernel(float2 *__restric
         const int o1n = o1 + gridDim.y;
         const bool more = o1n < p.O1;
         const long base = (long)o2 * p.o2_stride + (long)o1 * p.o1_stride + lane0;
-        if (F == 128 && NT == 256 && !(p.dbg & 8)) {
+        if (F == 128 && NT == 256) {
             // The element a thread has just built, zz[i], is point (tid >> 4) + 16 i of lane v: the eight inputs of ITS
             // radix-8 butterfly of the first stage.  So the first stage runs on the registers and only its result goes
             // to LDS; the third stage's outputs are multiplied by the inter-pass twiddles and stored from registers
@@ -1096,8 +1091,6 @@ const FastKernel kFast[] = {
     // segments, 17 KiB of LDS per workgroup -> 8 workgroups per CU (measured faster than 32 lanes)
     {125, 4, 0, 256, {fft_pass_ct_kernel<125, 4, 0, 256, 0, 5, 5, 5>, fft_pass_ct_kernel<125, 4, 0, 256, 1, 5, 5, 5>, fft_pass_ct_kernel<125, 4, 0, 256, 2, 5, 5, 5>}},
     {128, 4, 0, 256, {fft_pass_ct_kernel<128, 4, 0, 256, 0, 8, 4, 4>, fft_pass_ct_kernel<128, 4, 0, 256, 1, 8, 4, 4>, fft_pass_ct_kernel<128, 4, 0, 256, 2, 8, 4, 4>}},
-    {125, 5, 0, 256, {fft_pass_ct_kernel<125, 5, 0, 256, 0, 5, 5, 5>, fft_pass_ct_kernel<125, 5, 0, 256, 1, 5, 5, 5>, fft_pass_ct_kernel<125, 5, 0, 256, 2, 5, 5, 5>}},
-    {128, 5, 0, 256, {fft_pass_ct_kernel<128, 5, 0, 256, 0, 8, 4, 4>, fft_pass_ct_kernel<128, 5, 0, 256, 1, 8, 4, 4>, fft_pass_ct_kernel<128, 5, 0, 256, 2, 8, 4, 4>}},
     {100, 4, 0, 256, {fft_pass_ct_kernel<100, 4, 0, 256, 0, 4, 5, 5>, fft_pass_ct_kernel<100, 4, 0, 256, 1, 4, 5, 5>, fft_pass_ct_kernel<100, 4, 0, 256, 2, 4, 5, 5>}},
     {160, 4, 0, 256, {fft_pass_ct_kernel<160, 4, 0, 256, 0, 4, 8, 5>, fft_pass_ct_kernel<160, 4, 0, 256, 1, 4, 8, 5>, fft_pass_ct_kernel<160, 4, 0, 256, 2, 4, 8, 5>}},
     {64, 5, 0, 256, {fft_pass_ct_kernel<64, 5, 0, 256, 0, 4, 4, 4>, fft_pass_ct_kernel<64, 5, 0, 256, 1, 4, 4, 4>, fft_pass_ct_kernel<64, 5, 0, 256, 2, 4, 4, 4>}},
@@ -1105,8 +1098,6 @@ const FastKernel kFast[] = {
     {32, 5, 0, 256, {fft_pass_ct_kernel<32, 5, 0, 256, 0, 8, 4>, fft_pass_ct_kernel<32, 5, 0, 256, 1, 8, 4>, fft_pass_ct_kernel<32, 5, 0, 256, 2, 8, 4>}},
     // row passes: 30000/10, 12288/10 -> 1250, the 200-column stitch overlap
     {3000, 1, 1, 512, {fft_pass_ct_kernel<3000, 1, 1, 512, 0, 3, 8, 5, 5, 5>, fft_pass_ct_kernel<3000, 1, 1, 512, 1, 3, 8, 5, 5, 5>, fft_pass_ct_kernel<3000, 1, 1, 512, 2, 3, 8, 5, 5, 5>}},
-    {3000, 0, 1, 512, {fft_pass_ct_kernel<3000, 0, 1, 512, 0, 3, 8, 5, 5, 5>, fft_pass_ct_kernel<3000, 0, 1, 512, 1, 3, 8, 5, 5, 5>, fft_pass_ct_kernel<3000, 0, 1, 512, 2, 3, 8, 5, 5, 5>}},
-    {3000, 0, 1, 256, {fft_pass_ct_kernel<3000, 0, 1, 256, 0, 3, 8, 5, 5, 5>, fft_pass_ct_kernel<3000, 0, 1, 256, 1, 3, 8, 5, 5, 5>, fft_pass_ct_kernel<3000, 0, 1, 256, 2, 3, 8, 5, 5, 5>}},
     {1250, 1, 1, 256, {fft_pass_ct_kernel<1250, 1, 1, 256, 0, 2, 5, 5, 5, 5>, fft_pass_ct_kernel<1250, 1, 1, 256, 1, 2, 5, 5, 5, 5>, fft_pass_ct_kernel<1250, 1, 1, 256, 2, 2, 5, 5, 5, 5>}},
     {200, 4, 1, 256, {fft_pass_ct_kernel<200, 4, 1, 256, 0, 8, 5, 5>, fft_pass_ct_kernel<200, 4, 1, 256, 1, 8, 5, 5>, fft_pass_ct_kernel<200, 4, 1, 256, 2, 8, 5, 5>}},
 };
@@ -1176,18 +1167,8 @@ int pick_vshift(int F, int want)
 void choose_kernel(OipFftPass *p, int want_v)
 {
     p->fast = -1;
-    // experiment knobs (first match in the table is the default): lanes per column tile,
-    // threads per row-pass workgroup
-    static const char *env = getenv("OIP_FFT_LANES");
-    static const char *envt = getenv("OIP_FFT_ROW_THREADS");
-    const int want_vs = env ? (atoi(env) == 16 ? 4 : 5) : -1;
-    const int want_nt = envt ? atoi(envt) : -1;
-    static const char *envr = getenv("OIP_FFT_ROW_VS");
-    const int want_rvs = envr ? atoi(envr) : -1;
     for (int i = 0; i < kNumFast; ++i)
-        if (kFast[i].F == p->F && kFast[i].mode == p->mode && (p->mode == 1 || want_vs < 0 || kFast[i].vshift == want_vs) &&
-            (p->mode == 0 || want_nt < 0 || kFast[i].threads == want_nt) &&
-            (p->mode == 0 || want_rvs < 0 || kFast[i].vshift == want_rvs)) {
+        if (kFast[i].F == p->F && kFast[i].mode == p->mode) {
             p->fast = i;
             p->vshift = kFast[i].vshift;
             p->Vp = p->vshift > 1 ? (1 << p->vshift) + 1 : (1 << p->vshift);
@@ -1286,8 +1267,7 @@ int oip_fft2d_plan(oip_ctx *ctx, int M, int N, const OipFft2dPlan **out)
     // 16000 = 128 * 125 with the 128-point pass first: its points are 125 rows apart, an odd multiple of
     // 512 B for the padded pitches, so a tile spreads over the HBM channels (125 * 128 would put all
     // points of a tile 47 * 2^16 B apart -- same channel -- and ran at half the bandwidth)
-    static const char *envo = getenv("OIP_FFT_Y_ORDER");
-    if (M == 16000) pl.yf = (envo && atoi(envo) == 125) ? std::vector<int>{125, 128} : std::vector<int>{128, 125};
+    if (M == 16000) pl.yf = std::vector<int>{128, 125};
     else if (M == 4000) pl.yf = std::vector<int>{32, 125};          // the band windows of 16000 correlation lines
     else if (!split_axis(M, 256, 256, &pl.yf)) return oip_fail(ctx, OIP_E_UNSUPPORTED, "fft2d: cannot factor column length %d", M);
     // column (y) passes first: always mode A with lanes = x
@@ -1409,7 +1389,6 @@ static int launch_pass(oip_ctx *ctx, float2 *data, OipFftPass p, int inverse, co
     snprintf(pname, sizeof pname, blocks_override > 0 ? "fft_window_F%d" : (p.fast >= 0 ? "fft_pass_ct_kernel_F%d%s%s" : "fft_pass_kernel_F%d%s%s"), p.F,
              io.load_kind == 1 ? "_pack" : (io.store_kind == 1 ? "_peak" : ""), blocks_override > 0 || !ctx->prof_tag ? "" : ctx->prof_tag);
     OipProfScope prof(ctx, pname);
-    { const char *e = getenv("OIP_PACK_DBG"); p.dbg = e ? atoi(e) : 0; }
     dim3 grid3((unsigned)blocks);
     p.grid3 = 0;
     if (p.mode == 0 && (p.O1 > 65535 || p.O2 > 65535)) return oip_fail(ctx, OIP_E_UNSUPPORTED, "fft pass: more than 65535 rows or blocks");
@@ -1429,10 +1408,9 @@ static int launch_pass(oip_ctx *ctx, float2 *data, OipFftPass p, int inverse, co
     if (blocks_override <= 0 && !inverse && io.load_kind == 1 && p.mode == 0 && p.axis == 1 && p.vshift == 4 && p.tw_mode == 2 &&
         (up_v || pure16) && !io.re && !io.im && io.cols >= 8 && io.rows >= 1 &&
         (!io.re16 || ((io.cols & 7) == 0 && (io.pitch_re16 & 7) == 0 && ((size_t)io.re16 & 15) == 0))) {
-        static const char *envu = getenv("OIP_FIRST_UP");                 // experiment knob: 0 disables, N = tile rows per workgroup
-        const int tiles = envu ? atoi(envu) : 3;
+        const int tiles = 3;                                              // tile rows per workgroup
         for (const FirstUpKernel &k : kFirstUp)
-            if (k.F == p.F && tiles > 0) {
+            if (k.F == p.F) {
                 const int ltn = p.ltn > 0 ? p.ltn : p.lane_tiles;
                 p.xcd_chunk = (ltn + 7) / 8;
                 const int gy = (p.O1 + tiles - 1) / tiles;
@@ -1444,29 +1422,13 @@ static int launch_pass(oip_ctx *ctx, float2 *data, OipFftPass p, int inverse, co
             }
     }
     // the register-staged peak pass for the 128-point inverse column pass (see the kernel)
-    if (blocks_override <= 0 && inverse && io.store_kind == 1 && p.mode == 0 && p.axis == 1 && p.F == 128 && (p.vshift == 4 || p.vshift == 5) &&
+    if (blocks_override <= 0 && inverse && io.store_kind == 1 && p.mode == 0 && p.axis == 1 && p.F == 128 && p.vshift == 4 &&
         p.tw_mode == 2 && p.grid3 && (16 * p.nstride + p.lanes) * 8 < (1L << 31)) {       // 32-bit byte offsets inside a tile row block
-        static const char *envk = getenv("OIP_PEAK_V2");                  // experiment knob: 0 = generic pass kernel
-        if (!(envk && atoi(envk) == 0)) {
-            static const char *envt = getenv("OIP_PEAK_TILES");             // experiment knob: tile rows per workgroup
-            const int tiles = envt && atoi(envt) > 0 ? atoi(envt) : 1;      // measured: 0.104 / 0.106 / 0.106 / 0.110 ms for 1 / 2 / 3 / 5
-            if (p.O2 != 1) return oip_fail(ctx, OIP_E_RUNTIME, "peak pass: the last inverse pass spans the whole axis");
-            // experiment knob: 32-lane tiles (256-byte row segments, 512 threads) for this pass alone, whatever the plan chose
-            static const char *envl = getenv("OIP_PEAK_LANES");
-            if (envl && atoi(envl) == 32 && p.vshift == 4 && p.ltn <= 0) {
-                p.vshift = 5;
-                p.Vp = 33;
-                p.lane_tiles = (int)((p.lanes + 31) >> 5);
-                p.xcd_chunk = (p.lane_tiles + 7) / 8;
-                grid3.x = (unsigned)(8 * p.xcd_chunk);
-            }
-            grid3.y = (unsigned)((p.O1 + tiles - 1) / tiles);
-            p.tw_rows = rows_ok;
-            if (p.vshift == 4) hipLaunchKernelGGL(fft_col128_peak_kernel<4>, grid3, dim3(256), 0, ctx->stream, data, p, io, twF, twR);
-            else hipLaunchKernelGGL(fft_col128_peak_kernel<5>, grid3, dim3(512), 0, ctx->stream, data, p, io, twF, twR);
-            OIP_HIP(ctx, hipGetLastError());
-            return OIP_OK;
-        }
+        if (p.O2 != 1) return oip_fail(ctx, OIP_E_RUNTIME, "peak pass: the last inverse pass spans the whole axis");
+        p.tw_rows = rows_ok;
+        hipLaunchKernelGGL(fft_col128_peak_kernel<4>, grid3, dim3(256), 0, ctx->stream, data, p, io, twF, twR);
+        OIP_HIP(ctx, hipGetLastError());
+        return OIP_OK;
     }
     if (p.fast >= 0 && kFast[p.fast].fn[io.load_kind ? 1 : (io.store_kind ? 2 : 0)]) {
         p.ntiles = blocks;

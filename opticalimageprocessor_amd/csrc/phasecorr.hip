@@ -302,7 +302,6 @@ struct FusedJob {
     int narr, nout;
     int ncorr[2];
     int ia[4], ib[4], pa[4], pb[4];     // correlation 2*o + c of output o
-    int dbg;                            // experiment mask (OIP_ROWS_DBG): skip phases to time the rest; results are wrong
 };
 
 // Cross-power + inverse row pass (OIP_FUSED_ROWS=1: the forward row pass stays a separate launch; kept as
@@ -407,7 +406,6 @@ __global__ __launch_bounds__(NT) void corr_rows_kernel(FusedJob fj, int M, int P
     constexpr int NIT = (N + NT - 1) / NT;
     __shared__ __align__(16) float2 buf[NARR * 2 * F];   // [spectrum][point][line]: line 0 = ky, line 1 = -ky
     __shared__ float2 tw[TWN];
-    const int dbg = fj.dbg;
     const int half = M / 2;
     int ky = blockIdx.x;
     if (ky > half) return;
@@ -468,17 +466,17 @@ __global__ __launch_bounds__(NT) void corr_rows_kernel(FusedJob fj, int M, int P
         // destinations and copied right after the loads -- waiting for them at the point of issue.)
         const int kn = ky + gridDim.x;
         const bool more = kn <= half;
-        if (more && !(dbg & 8)) {
+        if (more) {
             n1 = (long)ypos[kn] * P;
             n2 = (long)ypos[M - kn] * P;
             fetch(tid);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (!(dbg & 1)) oipfft::StagesPipe<F, NT, NARR, 1, Rs...>::run(buf, tw, tid);
+        oipfft::StagesPipe<F, NT, NARR, 1, Rs...>::run(buf, tw, tid);
 #pragma unroll 1
         for (int it = 0; it < NIT; ++it) {
             const int kx = tid + it * NT;
-            if (kx >= N || (dbg & 2)) continue;
+            if (kx >= N) continue;
             const int nkx = kx ? N - kx : 0;
             const bool edge_col = (kx == 0) || (2 * kx == N);
             const bool real_bin = edge_col && (ky == 0 || 2 * ky == M);
@@ -516,7 +514,7 @@ __global__ __launch_bounds__(NT) void corr_rows_kernel(FusedJob fj, int M, int P
         }
         __syncthreads();
         asm volatile("" : "+v"(tid));
-        if (!(dbg & 4)) oipfft::StagesPipe<F, NT, NOUT, 1, Rs...>::run(buf, tw, tid);
+        oipfft::StagesPipe<F, NT, NOUT, 1, Rs...>::run(buf, tw, tid);
         if (NOUT == 1) __syncthreads();
         // Results leave LDS through registers so that the next pair can be committed before the stores
         // are issued.
@@ -538,17 +536,15 @@ __global__ __launch_bounds__(NT) void corr_rows_kernel(FusedJob fj, int M, int P
         __builtin_amdgcn_sched_barrier(0);
         const long o1 = s1, o2 = s2;
         s1 = n1; s2 = n2;
-        if (!(dbg & 16)) {
 #pragma unroll
-            for (int o = 0; o < NOUT; ++o) {
-                float2 *out = fj.out[o];
+        for (int o = 0; o < NOUT; ++o) {
+            float2 *out = fj.out[o];
 #pragma unroll
-                for (int it = 0; it < NIT2; ++it) {
-                    const int q = tid + it * NT;
-                    if (q < N / 2) {
-                        *reinterpret_cast<float4 *>(out + o1 + 2 * q) = ya[o][it];
-                        if (pair) *reinterpret_cast<float4 *>(out + o2 + 2 * q) = yb[o][it];
-                    }
+            for (int it = 0; it < NIT2; ++it) {
+                const int q = tid + it * NT;
+                if (q < N / 2) {
+                    *reinterpret_cast<float4 *>(out + o1 + 2 * q) = ya[o][it];
+                    if (pair) *reinterpret_cast<float4 *>(out + o2 + 2 * q) = yb[o][it];
                 }
             }
         }
@@ -571,7 +567,6 @@ __global__ __launch_bounds__(NT) void corr_rows3_kernel(FusedJob fj, int M, int 
     constexpr int NIT = (N + NT - 1) / NT;
     __shared__ __align__(16) float2 buf[NARR * 2 * F];   // [spectrum][point][line]: line 0 = ky, line 1 = -ky
     __shared__ float2 tw[TWN];
-    const int dbg = fj.dbg;
     const int half = M / 2;
     int ky = blockIdx.x;
     if (ky > half) return;
@@ -632,17 +627,17 @@ __global__ __launch_bounds__(NT) void corr_rows3_kernel(FusedJob fj, int M, int 
         // destinations and copied right after the loads -- waiting for them at the point of issue.)
         const int kn = ky + gridDim.x;
         const bool more = kn <= half;
-        if (more && !(dbg & 8)) {
+        if (more) {
             n1 = (long)ypos[kn] * P;
             n2 = (long)ypos[M - kn] * P;
             fetch(tid);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (!(dbg & 1)) oipfft::StagesAll<F, NT, NARR, 1, Rs...>::run(buf, tw, tid);
+        oipfft::StagesAll<F, NT, NARR, 1, Rs...>::run(buf, tw, tid);
 #pragma unroll 1
         for (int it = 0; it < NIT; ++it) {
             const int kx = tid + it * NT;
-            if (kx >= N || (dbg & 2)) continue;
+            if (kx >= N) continue;
             const int nkx = kx ? N - kx : 0;
             const bool edge_col = (kx == 0) || (2 * kx == N);
             const bool real_bin = edge_col && (ky == 0 || 2 * ky == M);
@@ -680,7 +675,7 @@ __global__ __launch_bounds__(NT) void corr_rows3_kernel(FusedJob fj, int M, int 
         }
         __syncthreads();
         asm volatile("" : "+v"(tid));
-        if (!(dbg & 4)) oipfft::StagesAll<F, NT, NOUT, 1, Rs...>::run(buf, tw, tid);
+        oipfft::StagesAll<F, NT, NOUT, 1, Rs...>::run(buf, tw, tid);
         // Results leave LDS through registers so that the next pair can be committed before the stores
         // are issued.
         float4 ya[NOUT][NIT2], yb[NOUT][NIT2];      // line ky / line -ky, two points each
@@ -701,17 +696,15 @@ __global__ __launch_bounds__(NT) void corr_rows3_kernel(FusedJob fj, int M, int 
         __builtin_amdgcn_sched_barrier(0);
         const long o1 = s1, o2 = s2;
         s1 = n1; s2 = n2;
-        if (!(dbg & 16)) {
 #pragma unroll
-            for (int o = 0; o < NOUT; ++o) {
-                float2 *out = fj.out[o];
+        for (int o = 0; o < NOUT; ++o) {
+            float2 *out = fj.out[o];
 #pragma unroll
-                for (int it = 0; it < NIT2; ++it) {
-                    const int q = tid + it * NT;
-                    if (q < N / 2) {
-                        *reinterpret_cast<float4 *>(out + o1 + 2 * q) = ya[o][it];
-                        if (pair) *reinterpret_cast<float4 *>(out + o2 + 2 * q) = yb[o][it];
-                    }
+            for (int it = 0; it < NIT2; ++it) {
+                const int q = tid + it * NT;
+                if (q < N / 2) {
+                    *reinterpret_cast<float4 *>(out + o1 + 2 * q) = ya[o][it];
+                    if (pair) *reinterpret_cast<float4 *>(out + o2 + 2 * q) = yb[o][it];
                 }
             }
         }
@@ -749,7 +742,6 @@ struct UpRowsJob {
     float2 *out[4];
     const float2 *xtab;     // [5][N]: H, G_0 .. G_3
     int nout;               // 4, or 2 for a single unit (arrays 2 and 3 are not read)
-    int dbg;                // experiment mask like FusedJob::dbg; 32: skip the vertical expansion (results are wrong)
     // VEXP: the vertical up-sampling is applied to the spectra as well.  zn then holds the column transforms of the
     // band windows themselves (m = M / 4 rows): line ky of the up-sampled band is
     //     Hv[ky] zn[ky mod m] + sum_i Gv_i[ky] raw[i],      raw = band rows {0, 1, m-2, m-1}
@@ -812,7 +804,6 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
     __shared__ float2 edgeT[2][5];                                 // H, G_0..3 at kx = 0 and N/2
     float2 *bufN = buf + 4 * F;
     float4 *buf4 = reinterpret_cast<float4 *>(buf), *buf4N = reinterpret_cast<float4 *>(bufN);
-    const int dbg = fj.dbg;
     const int half = M / 2;
     int ky = blockIdx.x;
     if (ky > half) return;
@@ -896,7 +887,7 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
             const int q = tid + it * NT;
             if (q < NQ) {
                 const int a = q / (S / 2), i = q - a * (S / 2);
-                if (VEXP && !(dbg & 32)) {
+                if (VEXP) {
                     // line ky of the vertically up-sampled band pair from line ky mod m of its transform; Hv and Gv of
                     // line -ky are the conjugates.  The raw band rows of this thread's points are kernel-long
                     // constants (two u16 pairs per row and piece).
@@ -938,9 +929,7 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
         if (first) load_tables(tid);            // later iterations: requested before the previous iteration's last stores
         first = false;
         __builtin_amdgcn_sched_barrier(0);
-        if (!(dbg & 1)) {
-            oipfft::StagesDual3<F, 1, S, 4, NT, 25, 15, 8, 2>::run(buf, tw, bufN, tws, tid);
-        }
+        oipfft::StagesDual3<F, 1, S, 4, NT, 25, 15, 8, 2>::run(buf, tw, bufN, tws, tid);
         // PAN spectra of this thread's bins (unit A in the real slot, unit B in the imaginary one); those of the two
         // edge columns (kx = 0, N/2: divSpectrums' double-precision and real-only formulas) also go to edgeA
         float2 Aa[2 * NB], Ab[2 * NB];                  // [2 r]: bin kx, [2 r + 1]: bin N - kx
@@ -959,7 +948,6 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
         }
         // outputs o0, o0 + 1 (narrow arrays of the same index) into the two full-width buffers
         auto xround = [&](int o0, const float2 (&A)[2 * NB]) {
-            if (dbg & 2) return;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const float2 *zn = bufN + (o0 + h) * 2 * S;
@@ -1032,7 +1020,7 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
         auto finish = [&]() {           // inverse row transform of the two buffers; results to registers
             __syncthreads();
             asm volatile("" : "+v"(tid));
-            if (!(dbg & 4)) oipfft::StagesAll<F, NT, 2, 1, 25, 15, 8>::run(buf, tw, tid);
+            oipfft::StagesAll<F, NT, 2, 1, 25, 15, 8>::run(buf, tw, tid);
 #pragma unroll
             for (int o = 0; o < 2; ++o) {
 #pragma unroll
@@ -1048,7 +1036,6 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
             __syncthreads();
         };
         auto store = [&](int o0) {
-            if (dbg & 16) return;
 #pragma unroll
             for (int o = 0; o < 2; ++o) {
                 float2 *out = fj.out[o0 + o];
@@ -1072,7 +1059,7 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
         // The lines of the NEXT pair are requested here -- after the last consumer of anything the compiler may have
         // spilled (a reload is a vector-memory load: younger than the prefetch, it would wait for it) -- and committed at
         // the bottom of this same iteration: three quarters of the iteration run without their registers.
-        if (more && !(dbg & 8)) {
+        if (more) {
             // (scalar loads: as vector loads these look-ups put an s_waitcnt vmcnt(0) -- the stores of store(0) and the table
             // loads -- in front of the prefetch.  ABAB on one box: 1.1677 / 1.1696 -> 1.1509 / 1.1427 ms per launch)
             n1 = oip_sload_i32(ypos, kn);
@@ -1118,7 +1105,6 @@ struct VRowsJob {
     int Pn;
     float2 *out[4];
     int nout;               // 4, or 2 for a single unit (arrays 2 and 3 are neither read nor written)
-    int dbg;
     const float2 *vtab;     // [5][M]: Hv, Gv_0 .. Gv_3
     const float2 *raw;      // [4 rows][4 arrays][zn_stride]: (bX, bY) of the horizontally up-sampled band rows {0, 1, m-2, m-1}
     const int *ypos_s;      // row position of frequency line k in zn, k in [0, m)
@@ -1143,7 +1129,6 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void corr_rows_v_kernel(VRowsJob 
     __shared__ __align__(16) float2 buf[NARR * 2 * F];   // [PAN | array a0 | array a0 + 1][point][line]: line 0 = ky, line 1 = -ky
     __shared__ float2 tw[TWN];
     float4 *buf4 = reinterpret_cast<float4 *>(buf);
-    const int dbg = fj.dbg;
     const int half = M / 2;
     int ky = blockIdx.x;
     if (ky > half) return;
@@ -1194,15 +1179,13 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void corr_rows_v_kernel(VRowsJob 
             const float2 hv = vt[0];
             float2 x0 = oipfft::cmul(hv, make_float2(na[it].x, na[it].y)), x1 = oipfft::cmul(hv, make_float2(na[it].z, na[it].w));
             float2 y0 = cmulj(hv, make_float2(nb[it].x, nb[it].y)), y1 = cmulj(hv, make_float2(nb[it].z, nb[it].w));
-            if (!(dbg & 32)) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float4 rw = *reinterpret_cast<const float4 *>(raw + ((long)r * 4 + a) * fj.zn_stride + 2 * i);
-                    const float2 gv = vt[1 + r];
-                    const float2 w0 = make_float2(rw.x, rw.y), w1 = make_float2(rw.z, rw.w);
-                    x0 = cfma(gv, w0, x0); x1 = cfma(gv, w1, x1);
-                    y0 = cfmaj(gv, w0, y0); y1 = cfmaj(gv, w1, y1);
-                }
+            for (int r = 0; r < 4; ++r) {
+                const float4 rw = *reinterpret_cast<const float4 *>(raw + ((long)r * 4 + a) * fj.zn_stride + 2 * i);
+                const float2 gv = vt[1 + r];
+                const float2 w0 = make_float2(rw.x, rw.y), w1 = make_float2(rw.z, rw.w);
+                x0 = cfma(gv, w0, x0); x1 = cfma(gv, w1, x1);
+                y0 = cfmaj(gv, w0, y0); y1 = cfmaj(gv, w1, y1);
             }
             buf4[(1 + a) * F + 2 * i] = make_float4(x0.x, x0.y, y0.x, y0.y);
             buf4[(1 + a) * F + 2 * i + 1] = make_float4(x1.x, x1.y, y1.x, y1.y);
@@ -1218,7 +1201,7 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void corr_rows_v_kernel(VRowsJob 
         const bool pair = s1 != s2;
         const int kn = ky + gridDim.x;
         const bool more = kn <= half;
-        if (more && !(dbg & 8)) {
+        if (more) {
             // (plain loads here: this kernel requests its next lines at the TOP of the iteration, nothing of its own is in
             // flight yet, and the explicit scalar loads of corr_rows_up_kernel cost it 4.5 % -- 0.740 against 0.708 ms)
             n1 = ypos[kn];
@@ -1229,11 +1212,11 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void corr_rows_v_kernel(VRowsJob 
             fetch(tid);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (!(dbg & 1)) oipfft::StagesPipe<F, NT, NARR, 1, Rs...>::run(buf, tw, tid);
+        oipfft::StagesPipe<F, NT, NARR, 1, Rs...>::run(buf, tw, tid);
 #pragma unroll 1
         for (int it = 0; it < NIT; ++it) {
             const int kx = tid + it * NT;
-            if (kx >= N || (dbg & 2)) continue;
+            if (kx >= N) continue;
             const int nkx = kx ? N - kx : 0;
             const bool edge_col = (kx == 0) || (2 * kx == N);
             const bool real_bin = edge_col && (ky == 0 || 2 * ky == M);
@@ -1251,7 +1234,7 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void corr_rows_v_kernel(VRowsJob 
         }
         __syncthreads();
         asm volatile("" : "+v"(tid));
-        if (!(dbg & 4)) oipfft::StagesPipe<F, NT, NB, 1, Rs...>::run(buf + 2 * F, tw, tid);
+        oipfft::StagesPipe<F, NT, NB, 1, Rs...>::run(buf + 2 * F, tw, tid);
         float4 ya[NB][NIT2], yb[NB][NIT2];          // line ky / line -ky, two points each
 #pragma unroll
         for (int o = 0; o < NB; ++o) {
@@ -1268,17 +1251,15 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void corr_rows_v_kernel(VRowsJob 
         __syncthreads();
         if (more) commit(tid);
         __builtin_amdgcn_sched_barrier(0);
-        if (!(dbg & 16)) {
 #pragma unroll
-            for (int o = 0; o < NB; ++o) {
-                float2 *out = fj.out[a0 + o];
+        for (int o = 0; o < NB; ++o) {
+            float2 *out = fj.out[a0 + o];
 #pragma unroll
-                for (int it = 0; it < NIT2; ++it) {
-                    const int q = tid + it * NT;
-                    if (q < N / 2) {
-                        *reinterpret_cast<float4 *>(out + s1 * P + 2 * q) = ya[o][it];
-                        if (pair) *reinterpret_cast<float4 *>(out + s2 * P + 2 * q) = yb[o][it];
-                    }
+            for (int it = 0; it < NIT2; ++it) {
+                const int q = tid + it * NT;
+                if (q < N / 2) {
+                    *reinterpret_cast<float4 *>(out + s1 * P + 2 * q) = ya[o][it];
+                    if (pair) *reinterpret_cast<float4 *>(out + s2 * P + 2 * q) = yb[o][it];
                 }
             }
         }
@@ -1336,13 +1317,13 @@ __global__ __launch_bounds__(128) void hpack_bands_kernel(HPackJob job, int m, i
 struct FusedRow {
     int F, threads, fwd_threads;
     void (*fwd1)(FusedJob, int, int, const int *, const float2 *);        // one spectrum -> one output
-    void (*fwd3)(FusedJob, int, int, const int *, const float2 *);        // three spectra -> two outputs
+    void (*fwd3)(FusedJob, int, int, const int *, const float2 *);        // three spectra -> two outputs (3000: corr_rows3_kernel)
     void (*inv)(FusedJob, int, int, OipAxisDigits, const float2 *);
 };
 // power-of-two radices last: their stores are then contiguous in LDS (a leading radix-8 stage
 // stores at a 128-byte stride, an 8-way bank conflict for ds_write_b64)
 const FusedRow kFusedRow[] = {
-    {3000, 512, 768, corr_rows_kernel<3000, 768, 1, 1, 3, 5, 5, 5, 8>, corr_rows_kernel<3000, 768, 3, 2, 3, 5, 5, 5, 8>,
+    {3000, 512, 768, corr_rows_kernel<3000, 768, 1, 1, 3, 5, 5, 5, 8>, nullptr,
      xpower_rows_kernel<3000, 512, 2, 3, 8, 5, 5, 5>},
     {1250, 256, 512, corr_rows_kernel<1250, 512, 1, 1, 5, 5, 5, 5, 2>, corr_rows_kernel<1250, 512, 3, 2, 5, 5, 5, 5, 2>,
      xpower_rows_kernel<1250, 256, 2, 2, 5, 5, 5, 5>},
@@ -1820,7 +1801,6 @@ int xpower_stage(oip_ctx *ctx, const OipFft2dPlan *pl, const RowStage &rs, const
         fj.ncorr[c / 2]++;
     }
     for (int o = 0; o < nout; ++o) fj.out[o] = y[o];
-    { const char *e = getenv("OIP_ROWS_DBG"); fj.dbg = e ? atoi(e) : 0; }
     if (rs.level == 2) {
         // persistent: as many workgroups as fit the CUs at once (LDS- or thread-limited)
         // the kernel hard-wires which spectrum and slot feeds which correlation
@@ -1837,8 +1817,7 @@ int xpower_stage(oip_ctx *ctx, const OipFft2dPlan *pl, const RowStage &rs, const
         long grid = (long)ctx->cu_count * per_cu;
         if (grid > pl->M / 2 + 1) grid = pl->M / 2 + 1;
         OipProfScope prof(ctx, "corr_rows_kernel");
-        const char *env3 = getenv("OIP_ROWS3");                         // experiment knob: 0 = the five-stage kernel
-        if (three && rs.k->F == 3000 && !(env3 && atoi(env3) == 0)) {
+        if (three && rs.k->F == 3000) {
             long g3 = ctx->cu_count;
             if (g3 > pl->M / 2 + 1) g3 = pl->M / 2 + 1;
             hipLaunchKernelGGL((corr_rows3_kernel<3000, 768, 3, 2, 25, 15, 8>), dim3((unsigned)g3), dim3(768), 0, ctx->stream, fj, pl->M, pl->P,
@@ -2090,19 +2069,13 @@ int correlate_units_up(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, c
     fj.raw16 = reinterpret_cast<const uint2 *>(raw);
     fj.ypos_s = ypos_s;
     fj.m = band_rows;
-    { const char *e = getenv("OIP_ROWS_DBG"); fj.dbg = e ? atoi(e) : 0; }
     {
         OipProfScope prof(ctx, "corr_rows_up_kernel");
         long grid = ctx->cu_count;
         if (grid > pl->M / 2 + 1) grid = pl->M / 2 + 1;
-        const char *et = getenv("OIP_UP_THREADS");                      // experiment knob: 512 | 768 threads
         const dim3 g((unsigned)grid);
-        if (up.vtab && et && atoi(et) == 768)
-            hipLaunchKernelGGL((corr_rows_up_kernel<768, true>), g, dim3(768), 0, ctx->stream, fj, pl->M, pl->P, pl->d_ypos, twF, twS);
-        else if (up.vtab)       // measured in bench.py: 1.275 ms with 512 threads (244 VGPRs, no scratch), 1.36 with 768 (168, 28 spilled)
+        if (up.vtab)       // measured in bench.py: 1.275 ms with 512 threads (244 VGPRs, no scratch), 1.36 with 768 (168, 28 spilled)
             hipLaunchKernelGGL((corr_rows_up_kernel<512, true>), g, dim3(512), 0, ctx->stream, fj, pl->M, pl->P, pl->d_ypos, twF, twS);
-        else if (et && atoi(et) == 768)
-            hipLaunchKernelGGL((corr_rows_up_kernel<768, false>), g, dim3(768), 0, ctx->stream, fj, pl->M, pl->P, pl->d_ypos, twF, twS);
         else
             hipLaunchKernelGGL((corr_rows_up_kernel<512, false>), g, dim3(512), 0, ctx->stream, fj, pl->M, pl->P, pl->d_ypos, twF, twS);
         OIP_HIP(ctx, hipGetLastError());
@@ -2165,11 +2138,9 @@ int correlate_units_vup(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, 
     fj.raw = raw;
     fj.ypos_s = up.small->d_ypos;
     fj.m = band_rows;
-    { const char *e = getenv("OIP_ROWS_DBG"); fj.dbg = e ? atoi(e) : 0; }
     {
         OipProfScope prof(ctx, "corr_rows_v_kernel");
-        const char *eg = getenv("OIP_VROWS_WG_PER_CU");        // experiment knob: 1 = one workgroup per CU (what co-residency buys)
-        long grid = (eg && atoi(eg) == 1 ? 1L : 2L) * ctx->cu_count;   // two workgroups per CU (60 KB of LDS, <= 128 VGPRs each)
+        long grid = 2L * ctx->cu_count;     // two workgroups per CU (60 KB of LDS, <= 128 VGPRs each)
         if (grid > pl->M / 2 + 1) grid = pl->M / 2 + 1;
         if (N != 1250) return oip_fail(ctx, OIP_E_RUNTIME, "correlate_units_vup: no row stage for %d-point rows", N);
         for (int u = 0; u < nunits; ++u)

@@ -475,11 +475,10 @@ extern "C" int oip_mss_split_rrc_u16(oip_ctx *ctx, const uint16_t *d_bil, uint16
     const double2 *kb = reinterpret_cast<const double2 *>(d_kb4);
     const bool fast = (w % 8 == 0) && (bw % 4 == 0) && (w == bw * 4) && (((uintptr_t)d_bil & 15) == 0) &&
                       (((uintptr_t)d_planes & 7) == 0) && (plane_stride % 4 == 0);
-    // the flat form (16-byte stores, aligned KiB per wave) wherever its index arithmetic holds; OIP_MSS_SPLIT_FLAT=0: the line-owned kernel
-    const char *ef = getenv("OIP_MSS_SPLIT_FLAT");
+    // the flat form (16-byte stores, aligned KiB per wave) wherever its index arithmetic holds
     const int upl = bw / 4;
     long sr = 0;
-    if (fast && !(ef && atoi(ef) == 0)) {
+    if (fast) {
         long g = upl % 2 == 0 ? upl / 2 : upl, t = 64, base = g;
         while (t) { long r = g % t; g = t; t = r; }
         sr = base / g * 64;                                          // lcm(upl / gcd(upl, 2), 64): 2 sr units = whole lines

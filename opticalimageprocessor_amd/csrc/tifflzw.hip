@@ -358,11 +358,10 @@ extern "C" int oip_tiff_lzw_strips_u16(oip_ctx *ctx, const uint16_t *d_img, long
     size_t pos = 0;
     for (long s0 = 0; s0 < nstrips; s0 += per) {
         const long ns = nstrips - s0 < per ? nstrips - s0 : per;
-        static const char *env_active = getenv("OIP_LZW_LANES");
         // Lanes of a wave that take a strip.  A wave steps at the pace of its slowest lane -- the longest probe chain, a code to
         // flush -- so 64 coders in lockstep are slower than 4 (116 -> 86 ms at 25000 strips, 76 -> 45 ms at 2000: the vector ALU
         // idles either way, and more, emptier waves give the memory system more independent chains to overlap).
-        const int active = env_active && atoi(env_active) > 0 && atoi(env_active) <= 64 ? atoi(env_active) : 4;
+        const int active = 4;
         LzwJob j{d_img, rows, width, spp, rows_per_strip, nstrips, s0, d_slots, slot_bytes, d_tab, d_len, active};
         // No slot is read before the lane's occupancy bit says it was written in the current generation, so the tables need no
         // initial VALUE -- but memory fresh from hipMalloc is first touched far cheaper by a linear fill than by the kernel's
@@ -431,8 +430,7 @@ extern "C" int oip_tiff_lzw_decode_u16(oip_ctx *ctx, const uint8_t *d_file, size
     for (long s0 = 0; s0 < nstrips; s0 += per) {
         const long ns = nstrips - s0 < per ? nstrips - s0 : per;
         // (the decoder does not gain from emptier waves as the encoder does: 64 / 16 / 8 / 4 lanes 98 / 102 / 115 / 120 ms)
-        static const char *env_active = getenv("OIP_LZW_DECODE_LANES");
-        const int active = env_active && atoi(env_active) > 0 && atoi(env_active) <= 64 ? atoi(env_active) : 64;
+        const int active = 64;
         LzwDecJob j{d_file, d_off, d_len, rows, width, spp, rows_per_strip, nstrips, s0, predictor, d_img, d_tab, d_got, d_status, active};
         OipProfScope prof(ctx, "lzw_decode_kernel");
         hipLaunchKernelGGL(lzw_decode_kernel, dim3((unsigned)((ns + active - 1) / active)), dim3(64), 0, ctx->stream, j);
