@@ -24,7 +24,8 @@
 //   * fusions: the first forward pass reads the two real f32 images directly (zero padding
 //     included) instead of a packed complex array; the last inverse pass does not store the
 //     correlation surface at all -- it reduces it to per-tile maxima (the arg-max of the
-//     fftShift-ed surface), and the 5x5 window around the winner is recomputed from 25 tiles.
+//     fftShift-ed surface), and the 5x5 window around the winner is evaluated directly from
+//     the pass's input (peak_window_kernel, phasecorr.hip).
 //   * the shapes of the reference geometry run compile-time specialised kernels (radices,
 //     tile and strides are constants: no integer division in the butterfly loops, one LDS
 //     buffer with register staging, 4-5 workgroups per CU); everything else runs the generic
@@ -53,7 +54,7 @@ struct Tile {
     int o1;         // mode 0: outer index 1
     int o2;         // mode 0: outer index 2
     long vec0;      // mode 1: first vector
-    long gtile;     // tile index over the whole pass (peak partial slot), independent of panelling
+    long gtile;     // tile index over the whole pass (peak partial slot)
 };
 
 __device__ __forceinline__ Tile decode_tile(const OipFftPass &p, long bid)
@@ -72,22 +73,20 @@ __device__ __forceinline__ Tile decode_tile(const OipFftPass &p, long bid)
             // is given the contiguous lane tiles [j * chunk, (j + 1) * chunk) instead of every eighth
             // one: the sharing becomes L2 hits instead of 2-4x over-fetch from the fabric.  The grid's
             // x extent is padded to 8 * chunk; surplus workgroups leave before any barrier.
-            const int rel = (int)(blockIdx.x & 7) * p.xcd_chunk + (int)(blockIdx.x >> 3);
-            lt = p.lt0 + rel;
+            lt = (int)(blockIdx.x & 7) * p.xcd_chunk + (int)(blockIdx.x >> 3);
             t.o1 = blockIdx.y;
             t.o2 = blockIdx.z;
             rest = (long)(t.o2 * p.O1 + t.o1);
         } else {
-            const int ltn = p.ltn > 0 ? p.ltn : p.lane_tiles;      // lane-tile window of this launch (column panel)
-            lt = p.lt0 + (int)(bid % ltn);
-            rest = bid / ltn;
+            lt = (int)(bid % p.lane_tiles);
+            rest = bid / p.lane_tiles;
             t.o1 = (int)(rest % p.O1);
             t.o2 = (int)(rest / p.O1);
         }
         t.gtile = rest * p.lane_tiles + lt;
         t.lane0 = lt << p.vshift;
         t.nv = p.lanes - t.lane0 < V ? (int)(p.lanes - t.lane0) : V;
-        if (p.grid3 && lt - p.lt0 >= (p.ltn > 0 ? p.ltn : p.lane_tiles)) t.nv = 0;      // padding workgroup
+        if (p.grid3 && lt >= p.lane_tiles) t.nv = 0;      // padding workgroup
         t.base = (long)t.o2 * p.o2_stride + (long)t.o1 * p.o1_stride + t.lane0;
         t.vec0 = 0;
     } else {
@@ -169,7 +168,7 @@ __device__ __forceinline__ bool peak_better(float v, long k, float bv, long bk) 
 // Reduce the tile to its maximum (first occurrence in the fftShift-ed scan order) for the
 // real and the imaginary part; one partial per workgroup and part.
 __device__ void store_peak(const float2 *buf, int Vp, const OipFftPass &p, const OipFftIo &io,
-                           const Tile &t, float *sval, long *skey, long tile, long ntiles, const int kFftBlock = 256)
+                           const Tile &t, float *sval, long *skey, long tile, const int kFftBlock = 256)
 {
     const int V = 1 << p.vshift;
     const int total = p.F << p.vshift;
@@ -233,57 +232,6 @@ __device__ void store_peak(const float2 *buf, int Vp, const OipFftPass &p, const
     }
 }
 
-// store_kind 2: the peak of part `part` from the slots (block-wide: every thread gets the key); the first
-// window block of a part publishes it for the centroid kernel.  scratch: >= 8 * 16 bytes of LDS.
-__device__ long window_peak_key(const OipFftPass &p, const OipFftIo &io, int blk, unsigned long long *scratch)
-{
-    const int part = blk / 25;
-    unsigned long long best = 0ull;
-    for (int i = threadIdx.x; i < kPeakSlots; i += blockDim.x) {
-        const unsigned long long s = io.slots[part * kPeakSlots + i];
-        best = s > best ? s : best;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off, 64);
-        best = o > best ? o : best;
-    }
-    const int wave = threadIdx.x >> 6, nwaves = (blockDim.x + 63) >> 6;
-    if ((threadIdx.x & 63) == 0) scratch[wave] = best;
-    __syncthreads();
-    best = scratch[0];
-    for (int w = 1; w < nwaves; ++w) best = scratch[w] > best ? scratch[w] : best;
-    __syncthreads();                          // scratch is the tile buffer
-    // an all-NaN surface has no entry: minMaxLoc leaves (0, 0)
-    const long key = oip_peak_key(best, 0);
-    if (blk % 25 == 0 && threadIdx.x == 0) io.peak_key[part] = key;
-    return key;
-}
-
-// store_kind 2: which tile holds window element w of the 5x5 window around the peak
-__device__ __forceinline__ bool window_tile(const OipFftPass &p, const OipFftIo &io, int blk, long key, Tile *t, int *n0, int *v0)
-{
-    // block = 25 * part + w: the windows of all parts of one array go in a single launch
-    const int w = blk % 25;
-    const int py = (int)(key / p.N), px = (int)(key - (long)py * p.N);
-    const int ys = py - 2 + w / 5, xs = px - 2 + w % 5;
-    if (ys < 0 || ys >= p.M || xs < 0 || xs >= p.N) return false;     // weightedCentroid clamps the window
-    int yo = ys - (p.M >> 1); if (yo < 0) yo += p.M;
-    int xo = xs - (p.N >> 1); if (xo < 0) xo += p.N;
-    // the last inverse pass is a column pass over the whole axis: T == M, O2 == 1
-    const int V = 1 << p.vshift;
-    t->o2 = 0;
-    t->o1 = yo % p.S;
-    *n0 = yo / p.S;
-    t->lane0 = (xo >> p.vshift) << p.vshift;
-    *v0 = xo - t->lane0;
-    t->nv = p.lanes - t->lane0 < V ? (int)(p.lanes - t->lane0) : V;
-    t->base = (long)t->o1 * p.o1_stride + t->lane0;
-    t->vec0 = 0;
-    t->gtile = 0;
-    return true;
-}
-
 // ---- generic kernel: run-time radices, ping-pong LDS buffers --------------------------------------
 template <int R>
 __device__ __forceinline__ void stockham_stage(const float2 *__restrict__ in, float2 *__restrict__ out,
@@ -325,18 +273,8 @@ __global__ __launch_bounds__(kFftBlock) void fft_pass_kernel(float2 *__restrict_
     float2 *bufB = smem + F * Vp;
     float2 *tw = smem + 2 * F * Vp;
 
-    Tile t;
-    int wn0 = 0, wv0 = 0;
-    if (io.store_kind == 2) {
-        const long key = window_peak_key(p, io, blockIdx.x, reinterpret_cast<unsigned long long *>(smem));
-        if (!window_tile(p, io, blockIdx.x, key, &t, &wn0, &wv0)) {
-            if (threadIdx.x == 0) io.window[(blockIdx.x / 25) * 32 + blockIdx.x % 25] = NAN;
-            return;
-        }
-    } else {
-        t = decode_tile(p, blockIdx.x);
-        if (p.grid3 && t.nv <= 0) return;       // padding workgroup of the XCD-chunked grid
-    }
+    const Tile t = decode_tile(p, blockIdx.x);
+    if (p.grid3 && t.nv <= 0) return;       // padding workgroup of the XCD-chunked grid
     for (int i = threadIdx.x; i < F; i += kFftBlock) tw[i] = twF[i];
 
     const int total = F << p.vshift;
@@ -369,14 +307,7 @@ __global__ __launch_bounds__(kFftBlock) void fft_pass_kernel(float2 *__restrict_
         Ns *= r;
     }
 
-    if (io.store_kind == 1) { store_peak(bufA, Vp, p, io, t, sval, skey, t.gtile, p.total_tiles); return; }
-    if (io.store_kind == 2) {
-        if (threadIdx.x == 0) {
-            float2 z = bufA[wn0 * Vp + wv0];
-            io.window[(blockIdx.x / 25) * 32 + blockIdx.x % 25] = (blockIdx.x / 25) ? -z.y : z.x;
-        }
-        return;
-    }
+    if (io.store_kind == 1) { store_peak(bufA, Vp, p, io, t, sval, skey, t.gtile); return; }
     for (int e = threadIdx.x; e < total; e += kFftBlock) {
         const int v = p.mode == 0 ? (e & (V - 1)) : e / F;
         const int n = p.mode == 0 ? (e >> p.vshift) : e - v * F;
@@ -412,7 +343,7 @@ __device__ __forceinline__ float2 load_elem_raw(const float2 *__restrict__ data,
 }
 
 // IOK 0: plain pass (complex array in, complex array out); 1: fused loader (io.load_kind 1), plain
-// store; 2: plain load, fused store (io.store_kind 1 or 2).  Separate instantiations because the
+// store; 2: plain load, fused store (io.store_kind 1).  Separate instantiations because the
 // kernel arguments of the fusions cost scalar registers -- past 100 a wave of occupancy goes, and
 // these passes are latency-bound enough to lose 15-20 % with it.
 template <int F, int VS, int MODE, int NT, int IOK, int... Rs>
@@ -431,18 +362,10 @@ __global__ __launch_bounds__(NT) void fft_pass_ct_kernel(float2 *__restrict__ da
     __shared__ float2 twj[MODE == 0 ? F : 1];       // inter-pass twiddles of this tile (column passes)
     static_assert(sizeof(float2) * F * Vp >= kFftBlock * 12 + 16, "tile too small to host the reduction scratch");
 
-    const long ntiles = (IOK == 2 && io.store_kind == 2) ? gridDim.x : p.ntiles;
     long tile = blockIdx.x;
-    if (MODE != 0 && tile >= ntiles) return;
+    if (MODE != 0 && tile >= p.ntiles) return;
     Tile t;
-    int wn0 = 0, wv0 = 0;
-    if ((IOK == 2 && io.store_kind == 2)) {
-        const long key = window_peak_key(p, io, blockIdx.x, reinterpret_cast<unsigned long long *>(buf));
-        if (!window_tile(p, io, blockIdx.x, key, &t, &wn0, &wv0)) {
-            if (threadIdx.x == 0) io.window[(blockIdx.x / 25) * 32 + blockIdx.x % 25] = NAN;
-            return;
-        }
-    } else if (MODE == 0) {
+    if (MODE == 0) {
         OipFftPass pg = p;
         pg.grid3 = 1;                  // launch_pass always gives mode-0 passes the 3-D grid
         t = decode_tile(pg, 0);
@@ -626,7 +549,7 @@ __global__ __launch_bounds__(NT) void fft_pass_ct_kernel(float2 *__restrict__ da
 
     {
         if (tile_tw) {
-            for (int i = threadIdx.x; i < F; i += kFftBlock) twj[i] = p.tw_rows ? twT[(long)t.o1 * F + i] : twT[(long)t.o1 * i];
+            for (int i = threadIdx.x; i < F; i += kFftBlock) twj[i] = twT[(long)t.o1 * i];
             if (p.inverse) __syncthreads();
         }
         // commit the prefetched tile to LDS
@@ -651,15 +574,9 @@ __global__ __launch_bounds__(NT) void fft_pass_ct_kernel(float2 *__restrict__ da
 
         Stages<F, VS, Vp, NT, 1, Rs...>::run(buf, tw);
 
-        if ((IOK == 2 && io.store_kind == 1)) {
+        if (IOK == 2) {
             // the scan of the tile ends (barrier inside store_peak) before the scratch is written
-            store_peak(buf, Vp, p, io, t, reinterpret_cast<float *>(buf + kFftBlock), reinterpret_cast<long *>(buf), t.gtile,
-                       p.total_tiles, NT);
-        } else if ((IOK == 2 && io.store_kind == 2)) {
-            if (threadIdx.x == 0) {
-                float2 z = buf[wn0 * Vp + wv0];
-                io.window[(blockIdx.x / 25) * 32 + blockIdx.x % 25] = (blockIdx.x / 25) ? -z.y : z.x;
-            }
+            store_peak(buf, Vp, p, io, t, reinterpret_cast<float *>(buf + kFftBlock), reinterpret_cast<long *>(buf), t.gtile, NT);
         } else {
             for (int e = threadIdx.x; e < TOTAL; e += kFftBlock) {
                 const int v = MODE == 0 ? (e & (V - 1)) : e / F;
@@ -724,10 +641,8 @@ __global__ __launch_bounds__(16 << VS) void fft_col128_peak_kernel(const float2 
     __shared__ float2 twj[F];
     // lane tile: contiguous chunks per XCD (see decode_tile); the workgroup keeps it and walks the row offsets
     // o1 = blockIdx.y, + gridDim.y, ...: the loads of the next tile are issued before the later stages of the current one
-    const int ltn = p.ltn > 0 ? p.ltn : p.lane_tiles;
-    const int rel = (int)(blockIdx.x & 7) * p.xcd_chunk + (int)(blockIdx.x >> 3);
-    if (rel >= ltn) return;
-    const int lt = p.lt0 + rel;
+    const int lt = (int)(blockIdx.x & 7) * p.xcd_chunk + (int)(blockIdx.x >> 3);
+    if (lt >= p.lane_tiles) return;
     const int lane0 = lt << VS;
     const int nv = p.lanes - lane0 < V ? (int)(p.lanes - lane0) : V;
     const int v = threadIdx.x & (V - 1);
@@ -752,7 +667,7 @@ __global__ __launch_bounds__(16 << VS) void fft_col128_peak_kernel(const float2 
         const char *tb = reinterpret_cast<const char *>(data) + (long)o * p.o1_stride * 8;
 #pragma unroll
         for (int m = 0; m < 8; ++m) x[m] = *reinterpret_cast<const float2 *>(tb + (long)m * 16 * p.nstride * 8 + voff);
-        if (tid < F) rtw = *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(twT) + (unsigned)(p.tw_rows ? o * F + tid : o * tid) * 8u);
+        if (tid < F) rtw = *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(twT) + (unsigned)(o * F + tid) * 8u);
     };
     // inverse = conj(forward(conj(.))); the inter-pass twiddle of point n multiplies the conjugated input
     auto stage1 = [&](int tid) {
@@ -882,10 +797,9 @@ __global__ __launch_bounds__(NT) void fft_first_pass_up_kernel(float2 *__restric
     unsigned short *seg16b = seg16 + F * V;                                               // [F][V] a second PAN window (imaginary slot)
 
     // lane tile: contiguous chunks per XCD (see decode_tile)
-    const int ltn = p.ltn > 0 ? p.ltn : p.lane_tiles;
-    const int rel = (int)(blockIdx.x & 7) * p.xcd_chunk + (int)(blockIdx.x >> 3);
-    if (rel >= ltn) return;
-    const int lane0 = (p.lt0 + rel) << VS;
+    const int lt = (int)(blockIdx.x & 7) * p.xcd_chunk + (int)(blockIdx.x >> 3);
+    if (lt >= p.lane_tiles) return;
+    const int lane0 = lt << VS;
     const int nv = p.lanes - lane0 < V ? (int)(p.lanes - lane0) : V;
     const int o2 = blockIdx.z;
     const int v = threadIdx.x & (V - 1);
@@ -942,7 +856,7 @@ __global__ __launch_bounds__(NT) void fft_first_pass_up_kernel(float2 *__restric
                 rv[sl][i] = *reinterpret_cast<const float2 *>(Vs + (size_t)y * io.v_cols + c);
             }
         }
-        if (tid < F) rtw = p.tw_rows ? twT[(long)o1 * F + tid] : twT[(long)o1 * tid];
+        if (tid < F) rtw = twT[(long)o1 * F + tid];
     };
     float2 zz[NLD];
     auto expand = [&](int o1, int tid) {
@@ -1354,48 +1268,40 @@ int oip_fft2d_plan(oip_ctx *ctx, int M, int N, const OipFft2dPlan **out)
 
 static long pass_blocks(const OipFftPass &p)
 {
-    if (p.mode == 0) return (long)(p.ltn > 0 ? p.ltn : p.lane_tiles) * p.O1 * p.O2;
+    if (p.mode == 0) return (long)p.lane_tiles * p.O1 * p.O2;
     return (p.lanes + (1 << p.vshift) - 1) >> p.vshift;
 }
 
 
-static int launch_pass(oip_ctx *ctx, float2 *data, OipFftPass p, int inverse, const OipFftIo &io, long blocks_override)
+static int launch_pass(oip_ctx *ctx, float2 *data, OipFftPass p, int inverse, const OipFftIo &io)
 {
     p.inverse = inverse;
     const float2 *twF = nullptr, *twT = nullptr;
     int rc = get_table(ctx, p.F, &twF);
     if (rc) return rc;
     if (p.tw_mode) { rc = get_table(ctx, p.T, &twT); if (rc) return rc; }
-    // the specialised kernels of a tw_mode 2 pass read their F inter-pass twiddles as one contiguous row (get_pass_table)
-    const float2 *twR = twT;
-    bool rows_ok = false;
-    p.tw_rows = 0;
-    if (p.tw_mode == 2 && p.F > 0 && p.T % p.F == 0 && p.O1 == p.T / p.F && (long)p.T * 8 <= (16L << 20)) {
-        const char *envr = getenv("OIP_TW_ROWS");                        // read per call (a test compares the forms): 0 = gather from table T
-        if (!(envr && atoi(envr) == 0)) {
-            rc = get_pass_table(ctx, p.T, p.F, &twR);
-            if (rc) return rc;
-            rows_ok = true;
-        }
+    // the register-staged kernels of a tw_mode 2 pass read their F inter-pass twiddles as one contiguous row (get_pass_table).
+    // The LDS-staged kernels keep the gather from table T: with rows the 125-point passes were 1.4 % SLOWER (0.1328 -> 0.1347 ms,
+    // A/B twice on one box).  A tw_mode 2 pass is a column pass with T = F S and O1 = S, and T <= M <= 65535 for every caller.
+    const float2 *twR = nullptr;
+    if (p.tw_mode == 2) {
+        if (p.T % p.F != 0 || p.O1 != p.T / p.F || (long)p.T * 8 > (16L << 20))
+            return oip_fail(ctx, OIP_E_RUNTIME, "fft pass: no inter-pass twiddle rows for T = %d, F = %d", p.T, p.F);
+        rc = get_pass_table(ctx, p.T, p.F, &twR);
+        if (rc) return rc;
     }
-    {
-        OipFftPass whole = p;
-        whole.ltn = 0;
-        p.total_tiles = pass_blocks(whole);
-    }
-    long blocks = blocks_override > 0 ? blocks_override : pass_blocks(p);
+    const long blocks = pass_blocks(p);
     if (blocks <= 0 || blocks > 0x7fffffffL) return oip_fail(ctx, OIP_E_UNSUPPORTED, "fft pass grid too large");
     char pname[64];
-    snprintf(pname, sizeof pname, blocks_override > 0 ? "fft_window_F%d" : (p.fast >= 0 ? "fft_pass_ct_kernel_F%d%s%s" : "fft_pass_kernel_F%d%s%s"), p.F,
-             io.load_kind == 1 ? "_pack" : (io.store_kind == 1 ? "_peak" : ""), blocks_override > 0 || !ctx->prof_tag ? "" : ctx->prof_tag);
+    snprintf(pname, sizeof pname, p.fast >= 0 ? "fft_pass_ct_kernel_F%d%s%s" : "fft_pass_kernel_F%d%s%s", p.F,
+             io.load_kind == 1 ? "_pack" : (io.store_kind == 1 ? "_peak" : ""), ctx->prof_tag ? ctx->prof_tag : "");
     OipProfScope prof(ctx, pname);
     dim3 grid3((unsigned)blocks);
     p.grid3 = 0;
     if (p.mode == 0 && (p.O1 > 65535 || p.O2 > 65535)) return oip_fail(ctx, OIP_E_UNSUPPORTED, "fft pass: more than 65535 rows or blocks");
-    if (p.mode == 0 && blocks_override <= 0) {
+    if (p.mode == 0) {
         p.grid3 = 1;
-        const int ltn = p.ltn > 0 ? p.ltn : p.lane_tiles;
-        p.xcd_chunk = (ltn + 7) / 8;
+        p.xcd_chunk = (p.lane_tiles + 7) / 8;
         grid3 = dim3((unsigned)(8 * p.xcd_chunk), (unsigned)p.O1, (unsigned)p.O2);
     }
     // the persistent first pass with fused up-sampling, when the geometry allows (see the kernel)
@@ -1405,16 +1311,13 @@ static int launch_pass(oip_ctx *ctx, float2 *data, OipFftPass p, int inverse, co
                       ((size_t)io.re_v & 7) == 0 && ((size_t)io.im_v & 7) == 0;
     const bool pure16 = io.re16 && !io.re_v && !io.im_v &&
                         (!io.im16 || ((io.pitch_im16 & 7) == 0 && ((size_t)io.im16 & 15) == 0));
-    if (blocks_override <= 0 && !inverse && io.load_kind == 1 && p.mode == 0 && p.axis == 1 && p.vshift == 4 && p.tw_mode == 2 &&
+    if (!inverse && io.load_kind == 1 && p.mode == 0 && p.axis == 1 && p.vshift == 4 && p.tw_mode == 2 &&
         (up_v || pure16) && !io.re && !io.im && io.cols >= 8 && io.rows >= 1 &&
         (!io.re16 || ((io.cols & 7) == 0 && (io.pitch_re16 & 7) == 0 && ((size_t)io.re16 & 15) == 0))) {
         const int tiles = 3;                                              // tile rows per workgroup
         for (const FirstUpKernel &k : kFirstUp)
             if (k.F == p.F) {
-                const int ltn = p.ltn > 0 ? p.ltn : p.lane_tiles;
-                p.xcd_chunk = (ltn + 7) / 8;
                 const int gy = (p.O1 + tiles - 1) / tiles;
-                p.tw_rows = rows_ok;
                 hipLaunchKernelGGL(k.fn, dim3((unsigned)(8 * p.xcd_chunk), (unsigned)gy, (unsigned)p.O2), dim3(k.threads), 0, ctx->stream,
                                    data, p, io, twF, twR);
                 OIP_HIP(ctx, hipGetLastError());
@@ -1422,22 +1325,16 @@ static int launch_pass(oip_ctx *ctx, float2 *data, OipFftPass p, int inverse, co
             }
     }
     // the register-staged peak pass for the 128-point inverse column pass (see the kernel)
-    if (blocks_override <= 0 && inverse && io.store_kind == 1 && p.mode == 0 && p.axis == 1 && p.F == 128 && p.vshift == 4 &&
+    if (inverse && io.store_kind == 1 && p.mode == 0 && p.axis == 1 && p.F == 128 && p.vshift == 4 &&
         p.tw_mode == 2 && p.grid3 && (16 * p.nstride + p.lanes) * 8 < (1L << 31)) {       // 32-bit byte offsets inside a tile row block
         if (p.O2 != 1) return oip_fail(ctx, OIP_E_RUNTIME, "peak pass: the last inverse pass spans the whole axis");
-        p.tw_rows = rows_ok;
         hipLaunchKernelGGL(fft_col128_peak_kernel<4>, grid3, dim3(256), 0, ctx->stream, data, p, io, twF, twR);
         OIP_HIP(ctx, hipGetLastError());
         return OIP_OK;
     }
     if (p.fast >= 0 && kFast[p.fast].fn[io.load_kind ? 1 : (io.store_kind ? 2 : 0)]) {
         p.ntiles = blocks;
-        long grid = blocks;
-        // the LDS-staged pass kernels keep the gather: with rows the 125-point passes were 1.4 % SLOWER (0.1328 -> 0.1347 ms, A/B twice on
-        // one box), OIP_TW_ROWS=2 turns the rows on for them too
-        const char *envr2 = getenv("OIP_TW_ROWS");
-        p.tw_rows = rows_ok && p.mode == 0 && envr2 && atoi(envr2) == 2;
-        hipLaunchKernelGGL(kFast[p.fast].fn[io.load_kind ? 1 : (io.store_kind ? 2 : 0)], p.grid3 ? grid3 : dim3((unsigned)grid), dim3(kFast[p.fast].threads), 0, ctx->stream, data, p, io, twF, p.tw_rows ? twR : twT);
+        hipLaunchKernelGGL(kFast[p.fast].fn[io.load_kind ? 1 : (io.store_kind ? 2 : 0)], p.grid3 ? grid3 : dim3((unsigned)blocks), dim3(kFast[p.fast].threads), 0, ctx->stream, data, p, io, twF, twT);
     } else {
         size_t lds = sizeof(float2) * ((size_t)2 * p.F * p.Vp + p.F);
         hipLaunchKernelGGL(fft_pass_kernel, p.grid3 ? grid3 : dim3((unsigned)blocks), dim3(kFftBlock), lds, ctx->stream, data, p, io, twF, twT);
@@ -1457,71 +1354,15 @@ int oip_fft2d_exec(oip_ctx *ctx, const OipFft2dPlan *pl, float2 *data, int inver
     const int np = rows_done ? pl->n_y : (int)pl->passes.size();
     OipFftIo plain;
     memset(&plain, 0, sizeof plain);
-    // Column passes are independent per column, so they can run panel by panel (a fraction of
-    // the columns through all column passes, then the next fraction): the later pass then re-reads
-    // what the earlier one just wrote while it is still in the 256 MiB Infinity Cache.
-    static const char *envp = getenv("OIP_FFT_PANELS");
-    int panels = envp ? atoi(envp) : 1;
-    const int lane_tiles = pl->n_y > 0 ? pl->passes[0].lane_tiles : 1;
-    if (panels < 1) panels = 1;
-    if (panels > lane_tiles) panels = lane_tiles;
-    auto column_passes = [&](bool inv) -> int {
-        for (int pn = 0; pn < panels; ++pn) {
-            for (int k = 0; k < pl->n_y; ++k) {
-                const int i = inv ? pl->n_y - 1 - k : k;
-                OipFftPass p = pl->passes[i];
-                // the panel in THIS pass' lane tiles (the passes of one axis may use different tile widths); a panel
-                // boundary must fall on a boundary of every pass, so panels are cut in units of the widest tile
-                int vmax = 0;
-                for (int q = 0; q < pl->n_y; ++q) vmax = pl->passes[q].vshift > vmax ? pl->passes[q].vshift : vmax;
-                const int wide = (int)((p.lanes + (1L << vmax) - 1) >> vmax);              // tiles of the widest pass
-                const int w0 = (int)((long)wide * pn / panels), w1 = (int)((long)wide * (pn + 1) / panels);
-                const int lt0 = w0 << (vmax - p.vshift);
-                int lt1 = w1 << (vmax - p.vshift);
-                if (lt1 > p.lane_tiles || pn == panels - 1) lt1 = p.lane_tiles;
-                p.lt0 = lt0;
-                p.ltn = lt1 - lt0;
-                OipFftIo use = plain;
-                if (!inv && i == 0 && io) { use = *io; use.store_kind = 0; }
-                if (inv && i == 0 && io) { use.store_kind = io->store_kind; use.slots = io->slots; }
-                int rc = launch_pass(ctx, data, p, inv ? 1 : 0, use, 0);
-                if (rc) return rc;
-            }
-        }
-        return OIP_OK;
-    };
-    if (!inverse) {
-        int rc = column_passes(false);
-        if (rc) return rc;
-        for (int i = pl->n_y; i < np; ++i) {
-            OipFftIo use = plain;
-            if (i == 0 && io) { use = *io; use.store_kind = 0; }
-            rc = launch_pass(ctx, data, pl->passes[i], 0, use, 0);
-            if (rc) return rc;
-        }
-    } else {
-        for (int i = np - 1; i >= pl->n_y; --i) {
-            OipFftIo use = plain;
-            if (i == 0 && io) { use.store_kind = io->store_kind; use.slots = io->slots; }
-            int rc = launch_pass(ctx, data, pl->passes[i], 1, use, 0);
-            if (rc) return rc;
-        }
-        int rc = column_passes(true);
+    OipFftIo first = plain;          // what pass 0 reads (forward) or stores (inverse)
+    if (io && !inverse) { first = *io; first.store_kind = 0; }
+    if (io && inverse) { first.store_kind = io->store_kind; first.slots = io->slots; }
+    for (int k = 0; k < np; ++k) {
+        const int i = inverse ? np - 1 - k : k;
+        int rc = launch_pass(ctx, data, pl->passes[i], inverse ? 1 : 0, i == 0 ? first : plain);
         if (rc) return rc;
     }
     return OIP_OK;
 }
 
 int oip_fft_table(oip_ctx *ctx, int T, const float2 **out) { return get_table(ctx, T, out); }
-
-int oip_fft2d_window(oip_ctx *ctx, const OipFft2dPlan *pl, float2 *data, const OipFftIo *io)
-{
-    OipFftIo use;
-    memset(&use, 0, sizeof use);
-    use.store_kind = 2;
-    use.peak_key = io->peak_key;
-    use.slots = io->slots;
-    use.window = io->window;
-    use.part = io->part;
-    return launch_pass(ctx, data, pl->passes[0], 1, use, 25L * (io->part > 0 ? io->part : 1));
-}

@@ -13,8 +13,8 @@ struct oip_ctx;
 // folds its tile maximum into one of kPeakSlots 64-bit slots per surface with atomicMax.  A slot packs
 // (order-preserving bits of the f32 value) << 32 | (0xFFFFFFFF - key), key = row-major index in the
 // fftShift-ed image (< 2^32), so the largest value wins and, among equal values, the smallest key -- the
-// first maximum in minMaxLoc's scan order.  0 = empty (NaN never enters).  The window kernel reduces the
-// slots itself; the centroid kernel zeroes them for the next surface.
+// first maximum in minMaxLoc's scan order.  0 = empty (NaN never enters).  peak_window_kernel (phasecorr.hip)
+// reduces the slots and zeroes them for the next surface.
 constexpr int kPeakSlots = 256;
 __host__ __device__ inline unsigned long long oip_peak_pack(float v, long key)
 {
@@ -48,12 +48,8 @@ struct OipFftIo {
     const float *alpha; // [cols][4]
     int x4;             // exact x4 geometry (host-verified): xofs[x] == (x - 2) >> 2, no table look-up needed
     int rows, cols;     // extent of the real images
-    int store_kind;     // 0: the complex array; 1: peak partials only (nothing stored);
-                        // 2: 5x5 window around a known peak (25 workgroups, nothing else stored)
-    unsigned long long *slots;  // store_kind 1 and 2: [2][kPeakSlots] arg-max slots (real part, imaginary part)
-    long *peak_key;             // store_kind 2: out, shifted key of the peak per part (for the centroid kernel)
-    float *window;              // store_kind 2: [25] values, row-major dy,dx (NaN = outside image)
-    int part;                   // store_kind 2: number of parts (1: real surface only, 2: real and imaginary), 25 tiles each
+    int store_kind;     // 0: the complex array; 1: peak partials only (nothing stored)
+    unsigned long long *slots;  // store_kind 1: [2][kPeakSlots] arg-max slots (real part, imaginary part)
 };
 
 struct OipFftPass {
@@ -79,12 +75,9 @@ struct OipFftPass {
     int P;              // row pitch in elements (N rounded up to whole 128-byte lines)
     int inverse;
     long ntiles;        // tiles of this launch (persistent specialised kernels walk them)
-    long total_tiles;   // tiles of the whole pass (peak partial slots)
-    int lt0, ltn;       // lane-tile window of this launch (column panel); ltn == 0: all
     int fast;           // index of a compile-time specialised kernel, -1: generic
     int grid3;          // mode 0 launched as a (lane tile, o1, o2) grid: the tile needs no divisions to decode
     int xcd_chunk;      // grid3: lane tiles per XCD (grid x = 8 * xcd_chunk >= lane tiles); see decode_tile
-    int tw_rows;        // tw_mode 2, specialised kernels: the inter-pass table is [O1][F] (row o1 contiguous) instead of table T gathered at o1 * n
 };
 
 struct OipFft2dPlan {
@@ -100,8 +93,6 @@ int oip_fft2d_plan(oip_ctx *ctx, int M, int N, const OipFft2dPlan **out);
 // forward: io (optional) applies to the FIRST pass' load; inverse: to the LAST pass' store
 int oip_fft2d_exec(oip_ctx *ctx, const OipFft2dPlan *plan, float2 *data, int inverse, const OipFftIo *io, int rows_done = 0);
 int oip_fft_table(oip_ctx *ctx, int T, const float2 **out);     // exp(-2 pi i t / T), t in [0, T)
-// re-run the last inverse pass for the 25 tiles holding the 5x5 window around *peak_key
-int oip_fft2d_window(oip_ctx *ctx, const OipFft2dPlan *plan, float2 *data, const OipFftIo *io);
 
 // position <-> frequency of one axis after the forward transform.  With factors
 // (F1, F2, ..) position p = k1*(F2*F3..) + k2*(F3..) + .. holds frequency

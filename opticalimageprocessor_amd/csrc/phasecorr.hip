@@ -304,85 +304,6 @@ struct FusedJob {
     int ia[4], ib[4], pa[4], pb[4];     // correlation 2*o + c of output o
 };
 
-// Cross-power + inverse row pass (OIP_FUSED_ROWS=1: the forward row pass stays a separate launch; kept as
-// the measured intermediate step towards corr_rows_kernel below).  The workgroup of frequency line ky owns
-// the lines ky and -ky of every spectrum of the job:
-// the cross-power lines Y(ky,.) and Y(-ky,.) of each output are formed in LDS straight from the
-// registers, inverse row-transformed and stored -- Y never exists in the spectral domain.
-template <int F, int NT, int WPE, int... Rs>
-__global__ __launch_bounds__(NT, WPE) void xpower_rows_kernel(FusedJob fj, int M, int P, OipAxisDigits yd,
-                                                         const float2 *__restrict__ twF)
-{
-    constexpr int TWN = oipfft::TwTable<F, Rs...>::value();
-    constexpr int N = F;
-    constexpr int NIT = (N + NT - 1) / NT;
-    __shared__ float2 buf[2 * F];          // [point][line]: line 0 = ky, line 1 = -ky, interleaved
-    __shared__ float2 tw[TWN];
-    const int ky = blockIdx.x;
-    const int nky = ky ? M - ky : 0;
-    const long r1 = (long)oip_freq_to_pos(yd, ky) * P, r2 = (long)oip_freq_to_pos(yd, nky) * P;
-    const bool pair = r1 != r2;
-    for (int i = threadIdx.x; i < TWN; i += NT) tw[i] = twF[i];
-    const int narr = fj.narr;
-    // one register array per spectrum and line: static indices only (no scratch)
-    float2 zk0[NIT], zk1[NIT], zk2[NIT], zm0[NIT], zm1[NIT], zm2[NIT];
-    const float2 zero = make_float2(0.f, 0.f);
-    const float2 *z0 = fj.z[0], *z1 = fj.z[1], *z2 = fj.z[2];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int kx = threadIdx.x + it * NT;
-        const int nkx = kx ? N - kx : 0;
-        const bool ok = kx < N;
-        zk0[it] = ok ? z0[r1 + kx] : zero;
-        zm0[it] = ok ? z0[r2 + nkx] : zero;
-        zk1[it] = ok && narr > 1 ? z1[r1 + kx] : zero;
-        zm1[it] = ok && narr > 1 ? z1[r2 + nkx] : zero;
-        zk2[it] = ok && narr > 2 ? z2[r1 + kx] : zero;
-        zm2[it] = ok && narr > 2 ? z2[r2 + nkx] : zero;
-    }
-#pragma unroll
-    for (int o = 0; o < 2; ++o) {
-        if (o >= fj.nout) break;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int kx = threadIdx.x + it * NT;
-            if (kx >= N) continue;
-            const int nkx = kx ? N - kx : 0;
-            const bool edge_col = (kx == 0) || (2 * kx == N);
-            const bool real_bin = edge_col && (ky == 0 || 2 * ky == M);
-            float2 y = zero, ym = zero;
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                if (c >= fj.ncorr[o]) break;
-                const int ia = fj.ia[2 * o + c], ib = fj.ib[2 * o + c];
-                const int pa = fj.pa[2 * o + c], pb = fj.pb[2 * o + c];
-                float2 zka = ia == 0 ? zk0[it] : (ia == 1 ? zk1[it] : zk2[it]);
-                float2 zma = ia == 0 ? zm0[it] : (ia == 1 ? zm1[it] : zm2[it]);
-                float2 zkb = ib == 0 ? zk0[it] : (ib == 1 ? zk1[it] : zk2[it]);
-                float2 zmb = ib == 0 ? zm0[it] : (ib == 1 ? zm1[it] : zm2[it]);
-                float2 A = spec_of(pa, zka, zma);
-                float2 B = spec_of(pb, zkb, zmb);
-                float2 C = cross_power_bin(A, B, real_bin, edge_col);
-                if (c == 0) { y.x += C.x; y.y += C.y; ym.x += C.x; ym.y -= C.y; }        // Y = C1 + i C2
-                else { y.x -= C.y; y.y += C.x; ym.x += C.y; ym.y += C.x; }               // i*conj(C2) = (C2.y, C2.x)
-            }
-            // inverse = conj(forward(conj(.)))
-            buf[2 * kx] = make_float2(y.x, -y.y);
-            buf[2 * nkx + 1] = pair ? make_float2(ym.x, -ym.y) : zero;
-        }
-        __syncthreads();
-        oipfft::Stages<F, 1, 2, NT, 1, Rs...>::run(buf, tw);        // both lines in one Stockham network
-        float2 *out = fj.out[o];
-        for (int e = threadIdx.x; e < 2 * N; e += NT) {
-            const int line = e >= N, x = e - line * N;
-            if (line && !pair) break;
-            float2 a = buf[2 * x + line];
-            out[(line ? r2 : r1) + x] = make_float2(a.x, -a.y);
-        }
-        __syncthreads();
-    }
-}
-
 // Row stage of the whole correlation in one persistent kernel, for shapes whose row axis is a single
 // factor (natural order along x).  The spectra arrive with only their column passes done.  A
 // workgroup owns the lines ky and -ky of every spectrum of the job, each spectrum in its own
@@ -1315,59 +1236,21 @@ __global__ __launch_bounds__(128) void hpack_bands_kernel(HPackJob job, int m, i
 }
 
 struct FusedRow {
-    int F, threads, fwd_threads;
+    int F, fwd_threads;
     void (*fwd1)(FusedJob, int, int, const int *, const float2 *);        // one spectrum -> one output
     void (*fwd3)(FusedJob, int, int, const int *, const float2 *);        // three spectra -> two outputs (3000: corr_rows3_kernel)
-    void (*inv)(FusedJob, int, int, OipAxisDigits, const float2 *);
 };
 // power-of-two radices last: their stores are then contiguous in LDS (a leading radix-8 stage
 // stores at a 128-byte stride, an 8-way bank conflict for ds_write_b64)
 const FusedRow kFusedRow[] = {
-    {3000, 512, 768, corr_rows_kernel<3000, 768, 1, 1, 3, 5, 5, 5, 8>, nullptr,
-     xpower_rows_kernel<3000, 512, 2, 3, 8, 5, 5, 5>},
-    {1250, 256, 512, corr_rows_kernel<1250, 512, 1, 1, 5, 5, 5, 5, 2>, corr_rows_kernel<1250, 512, 3, 2, 5, 5, 5, 5, 2>,
-     xpower_rows_kernel<1250, 256, 2, 2, 5, 5, 5, 5>},
-    {200, 256, 256, corr_rows_kernel<200, 256, 1, 1, 5, 5, 8>, corr_rows_kernel<200, 256, 3, 2, 5, 5, 8>,
-     xpower_rows_kernel<200, 256, 2, 8, 5, 5>},
+    {3000, 768, corr_rows_kernel<3000, 768, 1, 1, 3, 5, 5, 5, 8>, nullptr},
+    {1250, 512, corr_rows_kernel<1250, 512, 1, 1, 5, 5, 5, 5, 2>, corr_rows_kernel<1250, 512, 3, 2, 5, 5, 5, 5, 2>},
+    {200, 256, corr_rows_kernel<200, 256, 1, 1, 5, 5, 8>, corr_rows_kernel<200, 256, 3, 2, 5, 5, 8>},
 };
 
 // ---- peak: first maximum of the fftShift-ed surface + 5x5 weighted centroid ----------------------
 
-// weightedCentroid(C, peak, Size(5,5), &response) (phasecorr.cpp) on the recomputed window;
-// NaN marks window cells outside the image (the reference clamps the window to the image).
-__global__ void centroid_kernel(const float *__restrict__ window, const long *__restrict__ key, int M, int N,
-                                double *__restrict__ result, unsigned long long *__restrict__ slots)
-{
-    // last consumer of this surface's arg-max slots: leave them empty for the next surface
-    // (both surfaces: the pass fills the imaginary one's slots even when only the real one is wanted)
-    if (blockIdx.x == 0)
-        for (int i = threadIdx.x; i < 2 * kPeakSlots; i += blockDim.x) slots[i] = 0ull;
-    if (threadIdx.x != 0) return;
-    window += 32 * blockIdx.x;                       // one block per part
-    key += blockIdx.x;
-    result += 3 * blockIdx.x;
-    const int py = (int)(*key / N), px = (int)(*key - (long)py * N);
-    double cxs = 0.0, cys = 0.0, si = 0.0;
-    for (int dy = 0; dy < 5; ++dy)
-        for (int dx = 0; dx < 5; ++dx) {
-            const float f = window[dy * 5 + dx];
-            const int y = py - 2 + dy, x = px - 2 + dx;
-            if (y < 0 || y >= M || x < 0 || x >= N) continue;
-            const double v = (double)f;
-            cxs = __dadd_rn(cxs, __dmul_rn((double)x, v));
-            cys = __dadd_rn(cys, __dmul_rn((double)y, v));
-            si = __dadd_rn(si, v);
-        }
-    double response = si;
-    si = __dadd_rn(si, DBL_EPSILON);
-    const double cx = cxs / si, cy = cys / si;
-    response = response / (double)((long)M * N);
-    result[0] = (double)N / 2.0 - cx;
-    result[1] = (double)M / 2.0 - cy;
-    result[2] = response;
-}
-
-// The same in one launch, without re-running the last inverse pass on 25 tiles per part: block `part` reduces the
+// weightedCentroid(C, peak, Size(5,5), &response) (phasecorr.cpp) in one launch: block `part` reduces the
 // arg-max slots of its surface, evaluates the 25 window cells directly -- the last inverse column pass is
 //     c(y, x) = sum_{n < F1} data[(y mod S) + S n][x] exp(+2 pi i n y / M)        (S = M / F1; nothing was stored by it)
 // so a cell is a 128-term sum for the 16000-line geometry -- and runs weightedCentroid on them.  The cell values differ
@@ -1484,8 +1367,6 @@ struct PcWork {
     float *fb[8];       // second images, f32 (up-sampled bands; two units' worth)
     float *fsmall;      // MSS window before resize
     unsigned long long *slots;  // [4 arrays][2][kPeakSlots] arg-max slots, empty between surfaces
-    long *keys;         // peak key scratch
-    float *window;      // 25 floats
 };
 
 int carve(oip_ctx *ctx, const OipFft2dPlan *pl, int rows, int cols, int small_elems, int nz, int ny, int nfb, PcWork *w)
@@ -1495,7 +1376,7 @@ int carve(oip_ctx *ctx, const OipFft2dPlan *pl, int rows, int cols, int small_el
     const size_t fbytes = align_up(sizeof(float) * (size_t)rows * cols, 256);
     const size_t sbytes = align_up(sizeof(float) * (size_t)(small_elems > 0 ? small_elems : 1), 256);
     const size_t pbytes = align_up(sizeof(unsigned long long) * 4 * 2 * kPeakSlots, 256);
-    size_t total = zbytes * (nz + ny) + fbytes * (1 + nfb) + sbytes + pbytes + 512;
+    size_t total = zbytes * (nz + ny) + fbytes * (1 + nfb) + sbytes + pbytes;
     void *ws;
     int rc = oip_workspace(ctx, total, &ws);
     if (rc) return rc;
@@ -1505,10 +1386,8 @@ int carve(oip_ctx *ctx, const OipFft2dPlan *pl, int rows, int cols, int small_el
     w->fa = (float *)p; p += fbytes;
     for (int i = 0; i < 8; ++i) { w->fb[i] = i < nfb ? (float *)p : nullptr; if (i < nfb) p += fbytes; }
     w->fsmall = (float *)p; p += sbytes;
-    w->slots = (unsigned long long *)p; p += pbytes;
-    w->keys = (long *)p; p += 256;
-    w->window = (float *)p;
-    // the slots must start empty (later surfaces are cleaned by the centroid kernel)
+    w->slots = (unsigned long long *)p;
+    // the slots must start empty (later surfaces are cleaned by peak_window_kernel)
     ctx->prof_chain = nullptr;
     OIP_HIP(ctx, hipMemsetAsync(w->slots, 0, sizeof(unsigned long long) * 4 * 2 * kPeakSlots, ctx->stream));
     return OIP_OK;
@@ -1746,32 +1625,25 @@ int launch_xpower(oip_ctx *ctx, float2 *out, const XpowerJob &job, const OipFft2
     return OIP_OK;
 }
 
-// How the row stage runs for this plan: 2 = forward rows + cross-power + inverse rows in one kernel,
-// 1 = cross-power + inverse rows fused (forward rows as a separate pass), 0 = nothing fused.
-// OIP_FUSED_ROWS=0|1|2 is an experiment knob.
-struct RowStage {
-    const FusedRow *k;
-    int level;
-};
-RowStage row_stage(const OipFft2dPlan *pl)
+// The fused row-stage kernel of this plan (forward rows + cross-power + inverse rows in one kernel), or null:
+// forward row passes, cross_power_kernel and inverse row passes.  OIP_FUSED_ROWS=0 forces the latter.
+const FusedRow *row_stage(const OipFft2dPlan *pl)
 {
     const char *env = getenv("OIP_FUSED_ROWS");          // read per call: a test switches it between two correlations
-    int level = env ? atoi(env) : 2;
-    RowStage rs{nullptr, 0};
-    if (level <= 0 || pl->xf.size() != 1) return rs;
+    if ((env && atoi(env) <= 0) || pl->xf.size() != 1) return nullptr;
     for (const FusedRow &k : kFusedRow)
-        if (k.F == pl->N) { rs.k = &k; rs.level = level > 1 ? 2 : 1; }
-    return rs;
+        if (k.F == pl->N) return &k;
+    return nullptr;
 }
 
 // Cross-power of ncorr (A, B) spectrum pairs into nout = ceil(ncorr / 2) arrays y[o] =
-// C(2o) + i C(2o+1), with whatever row-stage fusion the plan allows.  At most three distinct
+// C(2o) + i C(2o+1), through the fused row-stage kernel `rk` if there is one.  At most three distinct
 // spectra per call.
-int xpower_stage(oip_ctx *ctx, const OipFft2dPlan *pl, const RowStage &rs, const SpecRef *a, const SpecRef *b, int ncorr,
+int xpower_stage(oip_ctx *ctx, const OipFft2dPlan *pl, const FusedRow *rk, const SpecRef *a, const SpecRef *b, int ncorr,
                  float2 *const y[2])
 {
     const int nout = (ncorr + 1) / 2;
-    if (!rs.k) {
+    if (!rk) {
         for (int o = 0; o < nout; ++o) {
             XpowerJob job;
             memset(&job, 0, sizeof job);
@@ -1783,7 +1655,7 @@ int xpower_stage(oip_ctx *ctx, const OipFft2dPlan *pl, const RowStage &rs, const
         return OIP_OK;
     }
     const float2 *twF;
-    int rc = oip_fft_table(ctx, rs.k->F, &twF);
+    int rc = oip_fft_table(ctx, rk->F, &twF);
     if (rc) return rc;
     FusedJob fj;
     memset(&fj, 0, sizeof fj);
@@ -1801,35 +1673,29 @@ int xpower_stage(oip_ctx *ctx, const OipFft2dPlan *pl, const RowStage &rs, const
         fj.ncorr[c / 2]++;
     }
     for (int o = 0; o < nout; ++o) fj.out[o] = y[o];
-    if (rs.level == 2) {
-        // persistent: as many workgroups as fit the CUs at once (LDS- or thread-limited)
-        // the kernel hard-wires which spectrum and slot feeds which correlation
-        const bool one = fj.narr == 1 && fj.nout == 1 && ncorr == 1 && fj.ia[0] == 0 && fj.pa[0] == 0 && fj.ib[0] == 0 && fj.pb[0] == 1;
-        bool three = fj.narr == 3 && fj.nout == 2 && ncorr == 4;
-        const int want_ib[4] = {0, 1, 1, 2}, want_pb[3] = {1, 0, 1};
-        for (int c = 0; c < 4 && three; ++c)
-            three = fj.ia[c] == 0 && fj.pa[c] == 0 && fj.ib[c] == want_ib[c] && (c == 3 || fj.pb[c] == want_pb[c]);
-        if (!one && !three) return oip_fail(ctx, OIP_E_RUNTIME, "xpower_stage: unsupported job shape");
-        const size_t lds = sizeof(float2) * ((size_t)fj.narr * 2 * rs.k->F + rs.k->F / 2);
-        long per_cu = (long)(160 * 1024 / lds);
-        if (per_cu > 2048 / rs.k->fwd_threads) per_cu = 2048 / rs.k->fwd_threads;
-        if (per_cu < 1) per_cu = 1;
-        long grid = (long)ctx->cu_count * per_cu;
-        if (grid > pl->M / 2 + 1) grid = pl->M / 2 + 1;
-        OipProfScope prof(ctx, "corr_rows_kernel");
-        if (three && rs.k->F == 3000) {
-            long g3 = ctx->cu_count;
-            if (g3 > pl->M / 2 + 1) g3 = pl->M / 2 + 1;
-            hipLaunchKernelGGL((corr_rows3_kernel<3000, 768, 3, 2, 25, 15, 8>), dim3((unsigned)g3), dim3(768), 0, ctx->stream, fj, pl->M, pl->P,
-                               pl->d_ypos, twF);
-        } else
-        hipLaunchKernelGGL(one ? rs.k->fwd1 : rs.k->fwd3, dim3((unsigned)grid), dim3(rs.k->fwd_threads), 0, ctx->stream, fj, pl->M,
+    // persistent: as many workgroups as fit the CUs at once (LDS- or thread-limited)
+    // the kernel hard-wires which spectrum and slot feeds which correlation
+    const bool one = fj.narr == 1 && fj.nout == 1 && ncorr == 1 && fj.ia[0] == 0 && fj.pa[0] == 0 && fj.ib[0] == 0 && fj.pb[0] == 1;
+    bool three = fj.narr == 3 && fj.nout == 2 && ncorr == 4;
+    const int want_ib[4] = {0, 1, 1, 2}, want_pb[3] = {1, 0, 1};
+    for (int c = 0; c < 4 && three; ++c)
+        three = fj.ia[c] == 0 && fj.pa[c] == 0 && fj.ib[c] == want_ib[c] && (c == 3 || fj.pb[c] == want_pb[c]);
+    if (!one && !three) return oip_fail(ctx, OIP_E_RUNTIME, "xpower_stage: unsupported job shape");
+    const size_t lds = sizeof(float2) * ((size_t)fj.narr * 2 * rk->F + rk->F / 2);
+    long per_cu = (long)(160 * 1024 / lds);
+    if (per_cu > 2048 / rk->fwd_threads) per_cu = 2048 / rk->fwd_threads;
+    if (per_cu < 1) per_cu = 1;
+    long grid = (long)ctx->cu_count * per_cu;
+    if (grid > pl->M / 2 + 1) grid = pl->M / 2 + 1;
+    OipProfScope prof(ctx, "corr_rows_kernel");
+    if (three && rk->F == 3000) {
+        long g3 = ctx->cu_count;
+        if (g3 > pl->M / 2 + 1) g3 = pl->M / 2 + 1;
+        hipLaunchKernelGGL((corr_rows3_kernel<3000, 768, 3, 2, 25, 15, 8>), dim3((unsigned)g3), dim3(768), 0, ctx->stream, fj, pl->M, pl->P,
+                           pl->d_ypos, twF);
+    } else
+        hipLaunchKernelGGL(one ? rk->fwd1 : rk->fwd3, dim3((unsigned)grid), dim3(rk->fwd_threads), 0, ctx->stream, fj, pl->M,
                            pl->P, pl->d_ypos, twF);
-    } else {
-        OipProfScope prof(ctx, "xpower_rows_kernel");
-        hipLaunchKernelGGL(rs.k->inv, dim3(pl->M / 2 + 1), dim3(rs.k->threads), 0, ctx->stream, fj, pl->M, pl->P,
-                           digits_of(pl->yf, pl->M), twF);
-    }
     OIP_HIP(ctx, hipGetLastError());
     return OIP_OK;
 }
@@ -1851,71 +1717,43 @@ int peak_windows(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, float2 *
     return OIP_OK;
 }
 
-// inverse transform of y whose last pass only leaves per-tile maxima (in slot set `slot_set`), then -- unless `defer`:
-// the caller batches the arrays of a launch through peak_windows -- for each wanted part:
-// arg-max -> recompute the 5x5 window -> centroid -> result slot
-int inverse_and_peaks(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, float2 *y, int nparts, double *d_results,
-                      bool rows_done, int slot_set = 0, bool defer = false)
+// inverse transform of y whose last pass only leaves per-tile maxima, in slot set `slot_set`; peak_windows turns them
+// into results
+int inverse_to_slots(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, float2 *y, bool rows_done, int slot_set)
 {
     OipFftIo io;
     memset(&io, 0, sizeof io);
     io.store_kind = 1;
     io.slots = w.slots + (long)slot_set * 2 * kPeakSlots;
-    int rc = oip_fft2d_exec(ctx, pl, y, 1, &io, rows_done ? 1 : 0);
-    if (rc) return rc;
-    // arg-max -> 5x5 window -> centroid of all parts (the real and imaginary surface of y) in one launch
-    // (OIP_WINDOW_FFT=1: the earlier form -- re-run the last pass on the 25 tiles of the window, then a centroid launch)
-    static const char *envw = getenv("OIP_WINDOW_FFT");
-    if (!(envw && atoi(envw))) {
-        if (defer) return OIP_OK;
-        float2 *const ys[1] = {y};
-        double *const rs[1] = {d_results};
-        PcWork w1 = w;
-        w1.slots = io.slots;
-        return peak_windows(ctx, pl, w1, ys, rs, 1, nparts);
-    }
-    OipFftIo wio;
-    memset(&wio, 0, sizeof wio);
-    wio.peak_key = w.keys;
-    wio.slots = io.slots;
-    wio.window = w.window;
-    wio.part = nparts;
-    if ((rc = oip_fft2d_window(ctx, pl, y, &wio))) return rc;
-    {
-        OipProfScope prof(ctx, "centroid_kernel");
-        hipLaunchKernelGGL(centroid_kernel, dim3(nparts), dim3(64), 0, ctx->stream, w.window, w.keys, pl->M, pl->N, d_results, io.slots);
-    }
-    OIP_HIP(ctx, hipGetLastError());
-    return OIP_OK;
+    return oip_fft2d_exec(ctx, pl, y, 1, &io, rows_done ? 1 : 0);
 }
 
 // one pair (a, b) -> result slot
 int correlate_pair(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, RealSrc a, RealSrc b, int rows,
                    int cols, double *d_result)
 {
-    const RowStage rs = row_stage(pl);
-    int rc = forward_packed(ctx, pl, w.z[0], a, b, rows, cols, rs.level == 2);
+    const FusedRow *rk = row_stage(pl);
+    int rc = forward_packed(ctx, pl, w.z[0], a, b, rows, cols, rk != nullptr);
     if (rc) return rc;
     const SpecRef sa[1] = {{w.z[0], 0}}, sb[1] = {{w.z[0], 1}};
     float2 *const y[2] = {w.y[0], nullptr};
-    if ((rc = xpower_stage(ctx, pl, rs, sa, sb, 1, y))) return rc;
-    return inverse_and_peaks(ctx, pl, w, w.y[0], 1, d_result, rs.k != nullptr);
+    if ((rc = xpower_stage(ctx, pl, rk, sa, sb, 1, y))) return rc;
+    if ((rc = inverse_to_slots(ctx, pl, w, w.y[0], rk != nullptr, 0))) return rc;
+    double *const res[1] = {d_result};
+    return peak_windows(ctx, pl, w, y, res, 1, 1);
 }
 
 // base image (real slot of zp) against (imag slot of zp, both slots of zq, slot `last_part` of zl)
-int correlate_four(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, const RowStage &rs, float2 *zp, float2 *zq,
+int correlate_four(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, const FusedRow *rk, float2 *zp, float2 *zq,
                    float2 *zl, int last_part, double *d_results /* 4 x 3 */)
 {
     const SpecRef sa[4] = {{zp, 0}, {zp, 0}, {zp, 0}, {zp, 0}};
     const SpecRef sb[4] = {{zp, 1}, {zq, 0}, {zq, 1}, {zl, last_part}};
     float2 *const y[2] = {w.y[0], w.y[1]};
     int rc;
-    if ((rc = xpower_stage(ctx, pl, rs, sa, sb, 4, y))) return rc;
-    static const char *envw = getenv("OIP_WINDOW_FFT");
-    const bool batched = !(envw && atoi(envw));
-    if ((rc = inverse_and_peaks(ctx, pl, w, w.y[0], 2, d_results, rs.k != nullptr, 0, batched))) return rc;
-    if ((rc = inverse_and_peaks(ctx, pl, w, w.y[1], 2, d_results + 6, rs.k != nullptr, batched ? 1 : 0, batched))) return rc;
-    if (!batched) return OIP_OK;
+    if ((rc = xpower_stage(ctx, pl, rk, sa, sb, 4, y))) return rc;
+    if ((rc = inverse_to_slots(ctx, pl, w, w.y[0], rk != nullptr, 0))) return rc;
+    if ((rc = inverse_to_slots(ctx, pl, w, w.y[1], rk != nullptr, 1))) return rc;
     double *const res[2] = {d_results, d_results + 6};
     return peak_windows(ctx, pl, w, y, res, 2, 2);
 }
@@ -1924,13 +1762,13 @@ int correlate_four(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, const 
 int correlate_one_to_four(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, RealSrc a, const RealSrc b[4],
                           int rows, int cols, double *d_results /* 4 x 3 */, const HTaps *vt)
 {
-    const RowStage rs = row_stage(pl);
-    const bool skip = rs.level == 2;
+    const FusedRow *rk = row_stage(pl);
+    const bool skip = rk != nullptr;
     int rc;
     if ((rc = forward_packed(ctx, pl, w.z[0], a, b[0], rows, cols, skip, vt))) return rc;
     if ((rc = forward_packed(ctx, pl, w.z[1], b[1], b[2], rows, cols, skip, vt))) return rc;
     if ((rc = forward_packed(ctx, pl, w.z[2], b[3], src_none(), rows, cols, skip, vt))) return rc;
-    return correlate_four(ctx, pl, w, rs, w.z[0], w.z[1], w.z[2], 0, d_results);
+    return correlate_four(ctx, pl, w, rk, w.z[0], w.z[1], w.z[2], 0, d_results);
 }
 
 // Two units (base image + four bands each) at once: the fourth bands of the two units share one
@@ -1939,16 +1777,16 @@ int correlate_one_to_four(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w,
 int correlate_two_units(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, RealSrc aA, const RealSrc bA[4], RealSrc aB,
                         const RealSrc bB[4], int rows, int cols, double *d_resA /* 4 x 3 */, double *d_resB, const HTaps *vt)
 {
-    const RowStage rs = row_stage(pl);
-    const bool skip = rs.level == 2;
+    const FusedRow *rk = row_stage(pl);
+    const bool skip = rk != nullptr;
     int rc;
     if ((rc = forward_packed(ctx, pl, w.z[0], aA, bA[0], rows, cols, skip, vt))) return rc;
     if ((rc = forward_packed(ctx, pl, w.z[1], bA[1], bA[2], rows, cols, skip, vt))) return rc;
     if ((rc = forward_packed(ctx, pl, w.z[2], aB, bB[0], rows, cols, skip, vt))) return rc;
     if ((rc = forward_packed(ctx, pl, w.z[3], bB[1], bB[2], rows, cols, skip, vt))) return rc;
     if ((rc = forward_packed(ctx, pl, w.z[4], bA[3], bB[3], rows, cols, skip, vt))) return rc;
-    if ((rc = correlate_four(ctx, pl, w, rs, w.z[0], w.z[1], w.z[4], 0, d_resA))) return rc;
-    return correlate_four(ctx, pl, w, rs, w.z[2], w.z[3], w.z[4], 1, d_resB);
+    if ((rc = correlate_four(ctx, pl, w, rk, w.z[0], w.z[1], w.z[4], 0, d_resA))) return rc;
+    return correlate_four(ctx, pl, w, rk, w.z[2], w.z[3], w.z[4], 1, d_resB);
 }
 
 // The same pair of units with the horizontal up-sampling applied to the band spectra (corr_rows_up_kernel): one
@@ -2081,16 +1919,12 @@ int correlate_units_up(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, c
         OIP_HIP(ctx, hipGetLastError());
     }
     // the inverse column passes of the outputs, each into its own slot set; one window launch for all of them
-    // (with OIP_WINDOW_FFT=1 every output still runs its own window passes: slot set 0 each time)
-    static const char *envw = getenv("OIP_WINDOW_FFT");
-    const bool batched = !(envw && atoi(envw));
     double *res[4];
     for (int o = 0; o < narr; ++o) {
         res[o] = (o < 2 ? d_resA : d_resB) + 6 * (o & 1);
-        if ((rc = inverse_and_peaks(ctx, pl, w, w.y[o], 2, res[o], true, batched ? o : 0, batched))) return rc;
+        if ((rc = inverse_to_slots(ctx, pl, w, w.y[o], true, o))) return rc;
     }
-    if (batched) return peak_windows(ctx, pl, w, w.y, res, narr, 2);
-    return OIP_OK;
+    return peak_windows(ctx, pl, w, w.y, res, narr, 2);
 }
 
 // A pair of units (or one) of a padded geometry -- the reference's 12288-wide strips: 1228-column slices, 1250-point
@@ -2151,7 +1985,7 @@ int correlate_units_vup(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, 
     double *res[4];
     for (int o = 0; o < narr; ++o) {
         res[o] = (o < 2 ? d_resA : d_resB) + 6 * (o & 1);
-        if ((rc = inverse_and_peaks(ctx, pl, w, w.y[o], 2, res[o], true, o, true))) return rc;
+        if ((rc = inverse_to_slots(ctx, pl, w, w.y[o], true, o))) return rc;
     }
     return peak_windows(ctx, pl, w, w.y, res, narr, 2);
 }
@@ -2297,7 +2131,7 @@ static int interband_units(oip_ctx *ctx, const IbUnit *units, int n, int rows, i
         // OIP_SPECTRAL_UP: 0 = image domain, 1 = horizontal axis on the spectra, 2 (default) = both axes
         const char *e = getenv("OIP_SPECTRAL_UP");
         const int want = e ? atoi(e) : 2;
-        if (want > 0 && rows == 4 * band_rows && cols == 4 * band_cols && M == rows && N == cols && N == 3000 && row_stage(pl).level == 2) {
+        if (want > 0 && rows == 4 * band_rows && cols == 4 * band_cols && M == rows && N == cols && N == 3000 && row_stage(pl)) {
             if ((rc = upsample_spectrum_tables(ctx, tab, 0, &up.xtab))) return rc;
             if (up.xtab) {
                 if ((rc = oip_fft2d_plan(ctx, M, band_cols, &up.narrow))) return rc;
@@ -2313,7 +2147,7 @@ static int interband_units(oip_ctx *ctx, const IbUnit *units, int n, int rows, i
         // (corr_rows_v_kernel).  OIP_SPECTRAL_V=0 keeps the image-domain route.
         const char *ev = getenv("OIP_SPECTRAL_V");
         if (!up.xtab && !(ev && atoi(ev) == 0) && want > 0 && rows == 4 * band_rows && cols == 4 * band_cols && M == rows && N == 1250 &&
-            (cols & 1) == 0 && row_stage(pl).level == 2 && optimal_dft_size(band_rows) == band_rows && band_rows >= 8 && smooth_len(4 * N)) {
+            (cols & 1) == 0 && row_stage(pl) && optimal_dft_size(band_rows) == band_rows && band_rows >= 8 && smooth_len(4 * N)) {
             if ((rc = upsample_spectrum_tables(ctx, tab, 1, &up.vtab))) return rc;
             if (up.vtab) {
                 if ((rc = oip_fft2d_plan(ctx, band_rows, 4 * N, &up.small))) return rc;

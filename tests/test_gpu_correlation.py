@@ -64,33 +64,6 @@ PC_SHAPES = [
 ]
 
 
-def test_column_pass_panels_with_mixed_tile_widths(ctx, tmp_path):
-    """4000 = 32 * 125: the two column passes use 32- and 16-lane tiles.  Cutting the columns into panels
-    (OIP_FFT_PANELS, an experiment knob read once per process -- hence the child process) must cut each pass in its own
-    tile units: a shared lane-tile window once skipped half the columns of the narrower pass.  Same bits as unpanelled."""
-    import subprocess, sys, json, os
-    rows, cols = 4000, 1250
-    sc = _synth.scene(rows + 32, cols + 32, seed=11)
-    a = np.ascontiguousarray(sc[16:16 + rows, 16:16 + cols], dtype=np.float32)
-    b = np.ascontiguousarray(sc[16 - 5:16 - 5 + rows, 16 + 6:16 + 6 + cols], dtype=np.float32)
-    want = ctx.phase_correlate_f32(_cuda(a), _cuda(b), rows, cols)
-    np.save(tmp_path / "a.npy", a); np.save(tmp_path / "b.npy", b)
-    code = ("import sys, json, numpy as np, torch; sys.path.insert(0, %r); import opticalimageprocessor_amd as oip; "
-            "c = oip.Context(0); a = torch.from_numpy(np.load(%r)).cuda(); b = torch.from_numpy(np.load(%r)).cuda(); "
-            "print(json.dumps(c.phase_correlate_f32(a, b, %d, %d)))" %
-            (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), str(tmp_path / "a.npy"), str(tmp_path / "b.npy"), rows, cols))
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, OIP_FFT_PANELS="3"), capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    (gdx, gdy), gr = json.loads(r.stdout.strip().splitlines()[-1])
-    assert (gdx, gdy, gr) == (want[0][0], want[0][1], want[1])
-    # the 5x5 window around the peak: evaluated directly (one launch with the arg-max and the centroid) or, as in round 1,
-    # by re-running the last pass on its 25 tiles (OIP_WINDOW_FFT=1) -- two summation orders of the same 128-term sums
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, OIP_WINDOW_FFT="1"), capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    (odx, ody), orr = json.loads(r.stdout.strip().splitlines()[-1])
-    assert abs(odx - want[0][0]) < 1e-5 and abs(ody - want[0][1]) < 1e-5 and abs(orr - want[1]) < 1e-6, ((odx, ody, orr), want)
-
-
 @pytest.mark.parametrize("rows,cols,shift", PC_SHAPES)
 def test_phase_correlate_matches_oracle(ctx, oracle_mod, parity_log, rows, cols, shift):
     from oracle import phasecorr as pc
@@ -234,28 +207,6 @@ def test_interband_reference_unit_shape_matches_oracle(ctx, oracle_mod, parity_l
             assert gcx == u * bc + bc // 2
     parity_log(shift_px=worst_s, response=worst_r, units=12, masked_out=masked, shift_bar=SHIFT_TOL, response_bar=RESP_TOL)
     assert masked <= MASKED["reference_unit_shape"]
-
-
-def test_twiddle_rows_equal_the_gather(ctx):
-    """The column passes of a 16000-line unit read their inter-pass twiddles either gathered from table T (OIP_TW_ROWS=0) or as
-    one contiguous row per tile row of a [T/F][F] table (1, default: the two register-staged passes; 2: the LDS-staged passes
-    too).  Same values, same arithmetic: the results must be the same bits."""
-    import os
-    rows, W = 16000, 6000
-    pan, bands = _synth.pan_mss(rows, W, [(2, -1), (1, 1), (-1, -2), (-2, 1)], seed=11)
-    dpan, dplanes = _cuda(pan), [_cuda(b) for b in bands]
-    pp = [dpan[:, 3000 * u:] for u in range(2)]
-    bp = [[dplanes[b][:, 750 * u:] for b in range(4)] for u in range(2)]
-    res = {}
-    try:
-        for mode in ("0", "1", "2"):
-            os.environ["OIP_TW_ROWS"] = mode
-            res[mode] = ctx.interband_correlate_units(pp, [W] * 2, bp, [W // 4] * 2, rows, 3000)
-    finally:
-        os.environ.pop("OIP_TW_ROWS", None)
-    assert np.isfinite(res["0"]).all()
-    assert np.array_equal(res["0"], res["1"]) and np.array_equal(res["0"], res["2"])
-    assert np.array_equal(res["1"], ctx.interband_correlate_units(pp, [W] * 2, bp, [W // 4] * 2, rows, 3000))
 
 
 def test_spectral_upsampling_route_equals_the_image_route(ctx, oracle_mod, parity_log):
@@ -470,17 +421,18 @@ def test_valid_set_straddling_the_reference_threshold(ctx, oracle_mod, scene):
     assert worst < 1.0 / 64
 
 
-def test_fast_cross_power_is_bounded_against_the_exact_bin(ctx):
+def test_fast_cross_power_is_bounded_against_the_unfused_route(ctx):
     """The fused row stage forms interior cross-power bins with the hardware reciprocal and square root
-    (cross_power_bin_fast); OIP_FUSED_ROWS=1 runs the same correlations through cross_power_bin (correctly rounded
-    double divisions, the reference's operation order).  Same spectra, same inverse transforms: the difference in
-    shift and response is what the approximation costs."""
+    (cross_power_bin_fast); OIP_FUSED_ROWS=0 runs the same correlations through cross_power_kernel and cross_power_bin
+    (correctly rounded double divisions, the reference's operation order), with separate row passes.  Same column
+    transforms; the forward and inverse row transforms differ too (fused kernel against pass kernels): the difference in
+    shift and response is what the approximation and the other row transforms cost."""
     import os
     pan, bands, (Lp, W, slices, sections, corr) = _straddling_scene(22, W=1600)      # 200-point rows: a fused row-stage shape
     planes = _cuda(np.stack(bands, 0))
     dpan = _cuda(pan)
     fast = ctx.interband_correlate(dpan, Lp, 0, Lp, planes, bands[0].size, 0, Lp // 4, W, slices, sections, corr)
-    os.environ["OIP_FUSED_ROWS"] = "1"
+    os.environ["OIP_FUSED_ROWS"] = "0"
     try:
         exact = ctx.interband_correlate(dpan, Lp, 0, Lp, planes, bands[0].size, 0, Lp // 4, W, slices, sections, corr)
     finally:
