@@ -103,6 +103,42 @@ int oip_rrc_u16_window(oip_ctx *ctx, const uint16_t *d_src, long src_pitch, uint
  * place through pinned, double-buffered line blocks (H2D || kernel || D2H). */
 int oip_rrc_u16_host(oip_ctx *ctx, uint16_t *buff, int w, long h, const double *kb);
 
+/* ---- RRC calibration: producing the files the loader above reads -------------------- */
+/* Per-column count, sum and sum of squares of a u16 raster window, ADDED into d_acc: the one pass over a strip from
+ * which the coefficients that IMO::LoadRRCParamFile (imageop.h:140-192) reads are derived.
+ * d_img: first pixel of the window; rows lines of w columns, `pitch` pixels apart (every line `pitch` pixels long in
+ * memory, as a window of a raster is).  Only samples v with valid_min <= v <= valid_max count (0 and 65535: every sample).
+ * d_acc: 3*w uint64 in HBM, planes [n | S1 | S2] of w entries each:
+ *   n[x] += #valid,  S1[x] += sum v,  S2[x] += sum v*v.
+ * The caller zeroes d_acc (oip_memset) before the first call; several calls over consecutive line blocks of a strip give
+ * the strip's totals.  rows < 2^31 per call.  Asynchronous on the context's stream.  Sums are exact integers: the result
+ * does not depend on the launch geometry or on the order of the calls.  A BIL MSS raster (preproc.h:62-75) needs no call
+ * of its own: column x of its W-wide line is column x % (W/4) of band x / (W/4). */
+int oip_colstats_u16(oip_ctx *ctx, const uint16_t *d_img, long pitch, int w, long rows,
+                     int valid_min, int valid_max, uint64_t *d_acc);
+
+/* Moment matching on those totals, host: one (k, b) per column such that IMO::InplaceRRC (imageop.h:129-138) with the
+ * file written below -- read back by IMO::LoadRRCParamFile, imageop.h:140-192 -- brings every column's statistics to
+ * its group's.  acc: the 3*w totals of oip_colstats_u16 (host copy).  The w columns form `groups` equal groups (1: PAN,
+ * 4: the bands of a BIL MSS line; w % groups == 0), each fitted against its own reference.  In this order:
+ *   usable(x): n >= max(min_count, 2) and D = n*S2 - S1*S1 > 0 (exact, 128-bit);  gain mode: n >= max(min_count, 1), S1 > 0
+ *   mu_x = (double)S1 / (double)n,  sigma_x = sqrt((double)D) / (double)n
+ *   mu_ref, sigma_ref: plain fp64 sums over the group's usable columns in ascending order, divided by their count
+ *   OIP_RRCFIT_MOMENTS: k = sigma_ref / sigma_x, b = mu_ref - k * mu_x (two roundings);  OIP_RRCFIT_GAIN: k = mu_ref / mu_x, b = 0
+ * kb_out: w (k,b) pairs; a column that is not usable gets (1, 0).  dead_out[g] (may be NULL): such columns of group g.
+ * ref_out (may be NULL): groups x (mu_ref, sigma_ref); sigma_ref is 0 in gain mode.
+ * OIP_E_RUNTIME if a group has no usable column (the message names it).  No context needed. */
+#define OIP_RRCFIT_MOMENTS 0
+#define OIP_RRCFIT_GAIN    1
+int oip_rrc_fit_columns(const uint64_t *acc, int w, int groups, int mode, uint64_t min_count,
+                        double *kb_out, int *dead_out, double *ref_out, char *err, int errlen);
+
+/* Writes RRCParam[n] in the format IMO::LoadRRCParamFile reads (imageop.h:148-188): "1\n", "<n>\n", "0\n", then n rows
+ * "k , b" in %.17g (the doubles load back bit for bit), every row ended by one '\n' and nothing after the last (the
+ * reader fails on a trailing blank line); a row is far shorter than the reader's 1024-byte buffer.  An existing file is
+ * replaced: refusing to do so is the caller's policy (`oip rrc-calib` without --force). */
+int oip_write_rrc_param_file(const char *path, const double *kb, int n, char *err, int errlen);
+
 /* ---- raster I/O staging (imageop.h:43-127, stitcher.h:103-120) ---------------------------------------
  * IMO::ReadFileContent + LoadRawImage / WriteBufferToFile move a raster through one pageable heap buffer,
  * serially with the arithmetic (8 MiB fread / fwrite units on the calling thread, imageop.h:69-79, :88-95).

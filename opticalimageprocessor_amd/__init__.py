@@ -21,8 +21,10 @@ from .capi import (  # noqa: F401
     load_rrc_param_file,
     polyfit,
     remap_shift_src_range,
+    rrc_fit_columns,
     stt_mean,
     upsample_operator,
+    write_rrc_param_file,
     align_mss_src_range,
 )
 

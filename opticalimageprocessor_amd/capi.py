@@ -63,6 +63,9 @@ _SIGS = {
     "oip_rrc_u16": ([_vp, _vp, _vp, _i, _l, _vp], _i),
     "oip_rrc_u16_window": ([_vp, _vp, _l, _vp, _l, _i, _l, _vp], _i),
     "oip_rrc_u16_host": ([_vp, _vp, _i, _l, _dp], _i),
+    "oip_colstats_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _vp], _i),
+    "oip_rrc_fit_columns": ([C.POINTER(C.c_uint64), _i, _i, _i, C.c_uint64, _dp, C.POINTER(_i), _dp, _cp, _i], _i),
+    "oip_write_rrc_param_file": ([_cp, _dp, _i, _cp, _i], _i),
     "oip_read_file_to_device": ([_vp, _cp, _sz, _sz, _vp, C.POINTER(_sz), _lp], _i),
     "oip_write_device_to_file": ([_vp, _vp, _sz, _cp, _i], _i),
     "oip_write_device_to_file_at": ([_vp, _vp, _sz, _cp, _sz, _l], _i),
@@ -165,6 +168,35 @@ def load_rrc_param_file(path: str, expected: int) -> np.ndarray:
     if rc:
         raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
     return out
+
+
+RRCFIT_MODES = {"moments": 0, "gain": 1}
+
+
+def rrc_fit_columns(acc, groups: int = 1, mode="moments", min_count: int = 0):
+    """(k, b) per column from the (3, w) uint64 totals of Context.colstats_u16 (include/oip_c.h: oip_rrc_fit_columns).
+    Returns (kb (w, 2), dead columns per group (groups,), (mu_ref, sigma_ref) per group (groups, 2))."""
+    lib = load_library()
+    a = np.ascontiguousarray(acc, dtype=np.uint64)
+    assert a.ndim == 2 and a.shape[0] == 3, a.shape
+    w = a.shape[1]
+    kb, dead, ref = np.zeros((w, 2)), np.zeros(max(groups, 1), np.int32), np.zeros((max(groups, 1), 2))
+    err = C.create_string_buffer(1024)
+    rc = lib.oip_rrc_fit_columns(a.ctypes.data_as(C.POINTER(C.c_uint64)), w, groups, RRCFIT_MODES.get(mode, mode), min_count,
+                                 kb.ctypes.data_as(_dp), dead.ctypes.data_as(C.POINTER(_i)), ref.ctypes.data_as(_dp), err, 1024)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    return kb, dead, ref
+
+
+def write_rrc_param_file(path: str, kb) -> None:
+    """RRCParam[n] in the format load_rrc_param_file (IMO::LoadRRCParamFile) reads; the doubles load back bit for bit"""
+    lib = load_library()
+    kb = _dbl(kb).reshape(-1, 2)
+    err = C.create_string_buffer(2048)
+    rc = lib.oip_write_rrc_param_file(os.fsencode(path), kb.ctypes.data_as(_dp), kb.shape[0], err, 2048)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
 
 
 FIT_MODES = {"reference": 0, "lstsq": 1}
@@ -296,6 +328,11 @@ class Context:
     def rrc_u16_window(self, src, src_pitch, dst, dst_pitch, w, h, d_kb):
         """RRC of columns [0, w) of h lines (pitches in pixels): e.g. straight into the left half of a stitched raster"""
         self._ck(self.lib.oip_rrc_u16_window(self.h, _ptr(src), src_pitch, _ptr(dst), dst_pitch, w, h, _ptr(d_kb)))
+
+    def colstats_u16(self, img, pitch, w, rows, acc, valid_min=0, valid_max=65535):
+        """per-column count / sum / sum of squares of rows x w u16 (lines `pitch` pixels apart) ADDED into acc: (3, w) uint64
+        on the device, zeroed by the caller before the first call"""
+        self._ck(self.lib.oip_colstats_u16(self.h, _ptr(img), pitch, w, rows, valid_min, valid_max, _ptr(acc)))
 
     def rrc_u16_host(self, buff: np.ndarray, kb):
         assert buff.dtype == np.uint16 and buff.flags.c_contiguous and buff.ndim == 2

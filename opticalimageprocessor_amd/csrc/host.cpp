@@ -1,5 +1,6 @@
 // host.cpp -- host-side pieces of the path that carry no raster arithmetic:
-// the RRC parameter file loader and the shift filtering / polynomial fit.
+// the RRC parameter file loader, its counterpart (column fit + writer) and the shift filtering / polynomial fit.
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -47,6 +48,85 @@ extern "C" int oip_load_rrc_param_file(const char *path, int expected_lines, dou
     fclose(f);
     if (index != expected_lines)
         return fail(OIP_E_RUNTIME, "RRC Param file [%s] invalid: %d lines of param expected, %d lines parsed.", path, expected_lines, index);
+    return OIP_OK;
+}
+
+// Moment matching on the per-column totals of oip_colstats_u16 (include/oip_c.h states the operation order; a Python
+// restatement in tests/_colstats_ref.py follows it step by step).  Every step is one correctly rounded fp64
+// operation: the 128-bit D converts to the nearest double, S1 < 2^47 and n < 2^53 convert exactly.
+extern "C" int oip_rrc_fit_columns(const uint64_t *acc, int w, int groups, int mode, uint64_t min_count, double *kb_out, int *dead_out,
+                                   double *ref_out, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *fmt, auto... a) {
+        if (err && errlen > 0) snprintf(err, errlen, fmt, a...);
+        return code;
+    };
+    if (!acc || !kb_out || w <= 0 || groups <= 0 || w % groups != 0 || (mode != OIP_RRCFIT_MOMENTS && mode != OIP_RRCFIT_GAIN))
+        return fail(OIP_E_INVALID, "%s", "oip_rrc_fit_columns: bad argument");
+    const bool moments = mode == OIP_RRCFIT_MOMENTS;
+    const uint64_t need = min_count > (moments ? 2u : 1u) ? min_count : (moments ? 2u : 1u);
+    const int gw = w / groups;
+    const uint64_t *N = acc, *S1 = acc + w, *S2 = acc + 2 * (size_t)w;
+    std::vector<double> mu(gw), sigma(gw);
+    std::vector<char> usable(gw);
+    for (int g = 0; g < groups; ++g) {
+        double muSum = 0.0, sigmaSum = 0.0;
+        int count = 0;
+        for (int i = 0; i < gw; ++i) {
+            const int x = g * gw + i;
+            usable[i] = 0;
+            if (N[x] < need) continue;
+            if (moments) {
+                const unsigned __int128 a = (unsigned __int128)N[x] * S2[x], b = (unsigned __int128)S1[x] * S1[x];
+                if (a <= b) continue;                                  // D == 0: a constant column (a < b cannot come from real totals)
+                const unsigned __int128 D = a - b;
+                mu[i] = (double)S1[x] / (double)N[x];
+                sigma[i] = std::sqrt((double)D) / (double)N[x];
+                sigmaSum += sigma[i];
+            } else {
+                if (S1[x] == 0) continue;
+                mu[i] = (double)S1[x] / (double)N[x];
+            }
+            usable[i] = 1;
+            muSum += mu[i];
+            ++count;
+        }
+        if (count == 0) return fail(OIP_E_RUNTIME, "oip_rrc_fit_columns: group %d has no usable column", g);
+        const double muRef = muSum / (double)count, sigmaRef = moments ? sigmaSum / (double)count : 0.0;
+        for (int i = 0; i < gw; ++i) {
+            double k = 1.0, b = 0.0;
+            if (usable[i]) {
+                if (moments) {
+                    k = sigmaRef / sigma[i];
+                    const double km = k * mu[i];
+                    b = muRef - km;
+                } else {
+                    k = muRef / mu[i];
+                }
+            }
+            kb_out[2 * (size_t)(g * gw + i)] = k;
+            kb_out[2 * (size_t)(g * gw + i) + 1] = b;
+        }
+        if (dead_out) dead_out[g] = gw - count;
+        if (ref_out) { ref_out[2 * g] = muRef; ref_out[2 * g + 1] = sigmaRef; }
+    }
+    return OIP_OK;
+}
+
+// The writer for IMO::LoadRRCParamFile's format (imageop.h:148-188; oip_load_rrc_param_file above reads it back).
+extern "C" int oip_write_rrc_param_file(const char *path, const double *kb, int n, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *fmt, auto... a) {
+        if (err && errlen > 0) snprintf(err, errlen, fmt, a...);
+        return code;
+    };
+    if (!path || !kb || n <= 0) return fail(OIP_E_INVALID, "%s", "oip_write_rrc_param_file: bad argument");
+    FILE *f = fopen(path, "wb");
+    if (!f) return fail(OIP_E_IO, "open RRC Param file [%s] for writing failed: %s", path, strerror(errno));
+    bool ok = fprintf(f, "1\n%d\n0\n", n) > 0;
+    for (int i = 0; i < n && ok; ++i) ok = fprintf(f, "%.17g , %.17g\n", kb[2 * (size_t)i], kb[2 * (size_t)i + 1]) > 0;
+    if (fclose(f) != 0) ok = false;
+    if (!ok) return fail(OIP_E_IO, "write of RRC Param file [%s] failed: %s", path, strerror(errno));
     return OIP_OK;
 }
 

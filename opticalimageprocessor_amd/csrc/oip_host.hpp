@@ -1498,4 +1498,126 @@ inline void RunFusedTask(const std::string &pan1, const std::string &pan2, const
     OLOG("Fused task done in %.3f seconds.", total.tick());
 }
 
+// ---- oip rrc-calib: the coefficient files every other action consumes --------------------------------
+// One read-only pass over a strip accumulates every column's count, sum and sum of squares (oip_colstats_u16); moment
+// matching on those totals (oip_rrc_fit_columns) gives each column the (k, b) that brings its statistics to the sensor-wide
+// ones, written in the format IMO::LoadRRCParamFile reads (imageop.h:140-192).  Not in the reference, which only consumes
+// such files.
+struct RrcCalibOptions {
+    int width = OIP_PIXELS_PER_LINE;
+    int mode = OIP_RRCFIT_MOMENTS;
+    int validMin = 0, validMax = 65535;
+    long minCount = 0;
+    long lineOffset = 0, lines = 0;         // lines == 0: to the end of the file
+    bool force = false;
+};
+
+// the lines [first, first + count) of `file` that a calibration uses; CheckFilesAttributes' size rule (preproc.h:552-572)
+inline void RrcCalibLineRange(const std::string &file, const char *what, const RrcCalibOptions &o, long *first, long *count)
+{
+    const size_t size = IMO::FileSize(file), lineBytes = (size_t)o.width * BYTES_PER_PIXEL;
+    if (size == 0 || size % lineBytes != 0)
+        throw std::invalid_argument(std::string(what) + " file size invalid: should be multiplies of " + std::to_string(lineBytes));
+    const long total = (long)(size / lineBytes);
+    if (o.lineOffset >= total) throw std::invalid_argument(std::string(what) + " file has " + std::to_string(total) + " lines: --line-offset is beyond them");
+    *first = o.lineOffset;
+    *count = o.lines > 0 ? std::min(o.lines, total - o.lineOffset) : total - o.lineOffset;
+}
+
+// The strip is never resident: line blocks go file -> pinned ring -> one of two device blocks, the statistics kernel of a
+// block runs behind its upload (ticket) while the host reads the next block from the file into the pinned ring.  `groups`
+// equal column groups.  Returns the fitted W (k, b) pairs; nothing is written here.
+inline std::vector<double> RrcCalibImage(const std::string &file, const char *what, int groups, const RrcCalibOptions &o)
+{
+    const int W = o.width, gw = W / groups;
+    long first = 0, nLines = 0;
+    RrcCalibLineRange(file, what, o, &first, &nLines);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    const size_t lineBytes = (size_t)W * BYTES_PER_PIXEL;
+    const long blockLines = std::max<long>(1, (long)(((size_t)64 << 20) / lineBytes));       // two slots of the pinned ring
+    DevBuf<uint16_t> buf[2];
+    for (int i = 0; i < 2 && (long)i * blockLines < nLines; ++i) buf[i].alloc((size_t)std::min(blockLines, nLines) * W);
+    DevBuf<uint64_t> acc((size_t)3 * W);
+    ck(oip_memset(ctx, acc.p, 0, (size_t)3 * W * sizeof(uint64_t)));
+    OLOG("Reading raw image from file `%s' ...", file.c_str());
+    stop_watch sw;
+    long block = 0;
+    for (long r = 0; r < nLines; r += blockLines, ++block) {
+        const long m = std::min(blockLines, nLines - r);
+        uint16_t *d = buf[block & 1].p;
+        // uploads do not wait for the compute stream: the kernel that read this buffer two blocks ago goes first (the call orders
+        // the upload behind the previous block's kernel as well -- a kernel is ~1 % of a block's transfer time)
+        if (block >= 2) ck(oip_stage_order_after_compute(ctx));
+        size_t got = 0;
+        long ticket = 0;
+        ck(oip_read_file_to_device(ctx, file.c_str(), (size_t)(first + r) * lineBytes, (size_t)m * lineBytes, d, &got, &ticket));
+        if (got != (size_t)m * lineBytes)
+            throw std::runtime_error("file size(" + std::to_string((size_t)(first + r + m) * lineBytes) + ") doesn't match with read byte count(" +
+                                     std::to_string((size_t)(first + r) * lineBytes + got) + ")");
+        ck(oip_stage_wait(ctx, ticket));
+        ck(oip_colstats_u16(ctx, d, W, W, m, o.validMin, o.validMax, acc.p));
+    }
+    std::vector<uint64_t> totals((size_t)3 * W);
+    acc.download(totals.data(), totals.size());
+    const double es = sw.tick();
+    const size_t bytes = (size_t)nLines * lineBytes;
+    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+
+    std::vector<double> kb((size_t)2 * W), ref((size_t)2 * groups);
+    std::vector<int> dead(groups);
+    char err[1024] = "";
+    const int rc = oip_rrc_fit_columns(totals.data(), W, groups, o.mode, (uint64_t)o.minCount, kb.data(), dead.data(), ref.data(), err, sizeof err);
+    if (rc == OIP_E_INVALID) throw std::invalid_argument(err);
+    if (rc != OIP_OK) throw std::runtime_error(err);
+    for (int g = 0; g < groups; ++g) {
+        double kmin = INFINITY, kmax = -INFINITY, bmin = INFINITY, bmax = -INFINITY;
+        for (int i = 0; i < gw; ++i) {
+            const double k = kb[2 * ((size_t)g * gw + i)], b = kb[2 * ((size_t)g * gw + i) + 1];
+            kmin = std::min(kmin, k); kmax = std::max(kmax, k); bmin = std::min(bmin, b); bmax = std::max(bmax, b);
+        }
+        OLOG("%s%s: %ld lines, %d usable / %d dead columns, mu_ref %.6f, sigma_ref %.6f, k in [%.9f, %.9f], b in [%.6f, %.6f]", what,
+             groups > 1 ? (" band " + std::to_string(g + 1)).c_str() : "", nLines, gw - dead[g], dead[g], ref[2 * g], ref[2 * g + 1], kmin, kmax, bmin,
+             bmax);
+    }
+    return kb;
+}
+
+// everything that can be refused without a device: sizes, line range, outputs named twice, outputs that exist
+inline void RrcCalibCheck(const std::string &pan, const std::string &mss, const std::string &outPan, const std::string *outMss, const RrcCalibOptions &o)
+{
+    long a = 0, b = 0;
+    if (o.width <= 0 || (!mss.empty() && o.width % MSS_BANDS != 0)) throw std::invalid_argument("--width: a positive line width (a multiple of 4 for MSS) expected");
+    if (!pan.empty()) RrcCalibLineRange(pan, "PAN", o, &a, &b);
+    if (!mss.empty()) RrcCalibLineRange(mss, "MSS", o, &a, &b);
+    std::vector<std::string> outs;
+    if (!pan.empty()) outs.push_back(outPan);
+    for (int i = 0; i < MSS_BANDS && !mss.empty(); ++i) outs.push_back(outMss[i]);
+    for (size_t i = 0; i < outs.size(); ++i)
+        for (size_t j = i + 1; j < outs.size(); ++j)
+            if (outs[i] == outs[j] || (std::filesystem::exists(outs[i]) && std::filesystem::exists(outs[j]) && std::filesystem::equivalent(outs[i], outs[j])))
+                throw std::invalid_argument("output file [" + outs[i] + "] is named for two outputs");
+    struct stat st;
+    for (const auto &f : outs)
+        if (!o.force && stat(f.c_str(), &st) == 0)
+            throw std::runtime_error("output file [" + f + "] exists: calibration does not replace a coefficient file without --force");
+}
+
+inline void RunRrcCalib(const std::string &pan, const std::string &mss, const std::string &outPan, const std::string *outMss, const RrcCalibOptions &o)
+{
+    RrcCalibCheck(pan, mss, outPan, outMss, o);
+    // every image and group is fitted before the first file is written: a band without a usable column leaves no partial set
+    std::vector<double> kbPan, kbMss;
+    if (!pan.empty()) kbPan = RrcCalibImage(pan, "PAN", 1, o);
+    if (!mss.empty()) kbMss = RrcCalibImage(mss, "MSS", MSS_BANDS, o);
+    auto write = [](const std::string &path, const double *kb, int n) {
+        char err[1024] = "";
+        if (oip_write_rrc_param_file(path.c_str(), kb, n, err, sizeof err) != OIP_OK) throw errno_error(err, 0);
+        OLOG("RRC parameters written to file [%s].", path.c_str());
+    };
+    if (!pan.empty()) write(outPan, kbPan.data(), o.width);
+    const int bw = o.width / MSS_BANDS;
+    for (int b = 0; b < MSS_BANDS && !mss.empty(); ++b) write(outMss[b], &kbMss[2 * (size_t)b * bw], bw);
+}
+
 }  // namespace OIPGPU

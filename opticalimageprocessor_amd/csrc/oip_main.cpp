@@ -6,10 +6,13 @@
 //   oip --pan P.RAW --mss M.RAW [--do-rrc4pan --rrc-pan F --no-rrc4mss --rrc-msb1..4 F --slices
 //       --ibc-sections --ibc-threshold --line-offset --lines-section --overlap-lines -k]   (:193-252)
 //   oip task ...                fused flow of DOC/sample-task.sh, see run_task()
+//   oip rrc-calib [--pan P.RAW --rrc-pan OUT] [--mss M.RAW --rrc-msb1..4 OUT]   derives the RRC coefficient files the
+//                               actions above read from a strip's per-column statistics, see run_rrc_calib()
 //   oip -v | --version          prints 1.1
 // plus --width N (pixels per PAN line; the reference hard-codes 12288, oipshared.h:28).
 // `auxsep` is outside this build.  TIFF input and output go through oip_tiff.hpp (uncompressed and LZW, with
-// or without the horizontal predictor).  Two options are not the reference's: --fit and --fp16-accumulate.
+// or without the horizontal predictor).  Two options are not the reference's: --fit and --fp16-accumulate; nor is the
+// rrc-calib sub-command.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -129,7 +132,12 @@ void usage()
          "  task       prestitch + stitch + default action x2 + stitch in one process (intermediates stay on the GPU;\n"
          "             --pan-only: the stitched PAN product alone, RRC and resampling written straight into it):\n"
          "             --pan1 --pan2 --rrc1 --rrc2 --mss1 --mss2 --rrc-mss{1,2}-b{1..4} FILE --fold-cols-pan N --fold-cols-mss N\n"
-         "             --out-pan FILE.TIFF --out-mss FILE.TIFF [prestitch, default-action and stitch options]");
+         "             --out-pan FILE.TIFF --out-mss FILE.TIFF [prestitch, default-action and stitch options]\n"
+         "  rrc-calib  derive RRC coefficient files from a strip (moment matching of the per-column statistics); the --rrc-* files\n"
+         "             are OUTPUTS here, and the same arguments given to the default action apply them:\n"
+         "             [--pan FILE --rrc-pan OUT] [--mss FILE --rrc-msb1 OUT --rrc-msb2 OUT --rrc-msb3 OUT --rrc-msb4 OUT]\n"
+         "             [--mode moments|gain] [--valid-min N] [--valid-max N] [--min-count N]\n"
+         "             [--line-offset N] [--lines N] (of each image's own lines) [--force] (replace existing OUT files)");
 }
 
 int run_prestitch(const std::vector<std::string> &args, int width)
@@ -362,6 +370,44 @@ int run_task(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip rrc-calib: the "k , b" files that prestitch (--rrc1/--rrc2), the default action (--rrc-pan, --rrc-msb1..4) and task
+// read, derived from a strip.  The option names are the default action's on purpose -- here the --rrc-* values are outputs.
+int run_rrc_calib(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--pan", "--mss", "--rrc-pan", "--rrc-msb1", "--rrc-msb2", "--rrc-msb3", "--rrc-msb4", "--width", "--mode", "--valid-min",
+                 "--valid-max", "--min-count", "--line-offset", "--lines"};
+    sp.flags = {"--force"};
+    Parsed p = parse(sp, args);
+    const char *msbKeys[MSS_BANDS] = {"--rrc-msb1", "--rrc-msb2", "--rrc-msb3", "--rrc-msb4"};
+    bool anyMsb = false;
+    for (auto k : msbKeys) anyMsb = anyMsb || p.has(k);
+    if (!p.has("--pan") && !p.has("--mss") && !p.has("--rrc-pan") && !anyMsb) throw cli_error(106, "--pan or --mss is required");
+    if (p.has("--pan") || p.has("--rrc-pan")) { require(p, "--pan"); require(p, "--rrc-pan"); }    // an image and its outputs come together
+    if (p.has("--mss") || anyMsb) {
+        require(p, "--mss");
+        for (auto k : msbKeys) require(p, k);
+    }
+    for (auto k : {"--pan", "--mss"}) existing_file(p, k);
+    RrcCalibOptions o;
+    o.width = p.integer("--width", width);
+    const std::string mode = p.str("--mode", "moments");
+    if (mode == "moments") o.mode = OIP_RRCFIT_MOMENTS;
+    else if (mode == "gain") o.mode = OIP_RRCFIT_GAIN;
+    else throw cli_error(105, "--mode: moments or gain expected");
+    o.validMin = p.integer("--valid-min", 0);
+    o.validMax = p.integer("--valid-max", 65535);
+    if (o.validMin < 0 || o.validMax > 65535 || o.validMin > o.validMax) throw cli_error(105, "--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
+    o.minCount = p.integer("--min-count", 0);
+    o.lineOffset = p.integer("--line-offset", 0);
+    o.lines = p.integer("--lines", 0);
+    if (o.minCount < 0 || o.lineOffset < 0 || o.lines < 0) throw cli_error(105, "--min-count, --line-offset, --lines: non-negative values expected");
+    o.force = p.flag.count("--force") != 0;
+    const std::string msb[MSS_BANDS] = {p.str(msbKeys[0]), p.str(msbKeys[1]), p.str(msbKeys[2]), p.str(msbKeys[3])};
+    RunRrcCalib(p.str("--pan"), p.str("--mss"), p.str("--rrc-pan"), msb, o);
+    return 0;
+}
+
 }  // namespace
 
 static int oip_main(int argc, const char *argv[]);
@@ -408,6 +454,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "stitch") return run_stitch({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "task") return run_task({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "plan") return run_plan({args.begin() + 1, args.end()});
+            if (!args.empty() && args[0] == "rrc-calib") return run_rrc_calib({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "auxsep")
                 throw std::invalid_argument("auxsep (down-link de-framing) is outside this build: run the reference's auxsep, then this tool");
             if (args.empty()) { usage(); return 0; }
