@@ -293,15 +293,68 @@ __global__ __launch_bounds__(kBlock) void cross_power_kernel(float2 *__restrict_
     if (r1 != r2) out[r2 + px2] = ym;
 }
 
-// Cross-power jobs flattened on the host: up to three distinct packed spectra, up to two output
-// arrays, each output Y = C(a0,b0) + i C(a1,b1); per correlation which spectrum and which slot
-// (real/imaginary) hold A and B
+// ---- line-pair helpers of the row-stage kernels -------------------------------------------------------------------
+//
+// A row-stage workgroup moves the spectrum lines ky and -ky of an N-point array together: NT lanes, 16 bytes (two
+// points) per lane and line -- half the vector-memory and LDS instructions of 8-byte accesses, whose operand traffic
+// shares the SIMD-to-LDS path with the stages' ds_writes.  Piece q = tid + it * NT holds the points 2q and 2q + 1; the
+// loop over `it` stays with the caller, and b0 is the index of the buffer's first 16-byte element in buf4.
+// A kernel uses a helper only where it compiles to the instructions of the text it replaces (compare the assembly
+// before adopting one elsewhere): these kernels sit at their register limits, and the same statements reached through
+// another inlining order have come out with other register assignments, and with spills.
+
+// piece q of the lines at element offsets e1 and e2 of z into registers (a prefetch: nothing here waits for the loads)
+template <int N>
+__device__ __forceinline__ void line_pair_fetch(float4 &la, float4 &lb, const float2 *z, long e1, long e2, int q)
+{
+    // lanes past the end of the line re-read its last pair (never committed): a select on
+    // the loaded value would need the load to have completed -- a wait inside the prefetch
+    q = q < N / 2 ? q : N / 2 - 1;
+    la = *reinterpret_cast<const float4 *>(z + e1 + 2 * q);
+    lb = *reinterpret_cast<const float4 *>(z + e2 + 2 * q);
+}
+
+// the fetched piece q into a two-line LDS buffer
+template <int N>
+__device__ __forceinline__ void line_pair_commit(float4 *buf4, int b0, float4 la, float4 lb, int q)
+{
+    if (q < N / 2) {
+        // [point][line] interleave: (2q, line 0), (2q, line 1), (2q+1, line 0), (2q+1, line 1):
+        // two 16-byte writes 32 bytes apart per lane (2-way bank conflict; four 8-byte writes
+        // would be 4-way).  The repacking moves sit here, after the loads have landed.
+        buf4[b0 + 2 * q] = make_float4(la.x, la.y, lb.x, lb.y);
+        buf4[b0 + 2 * q + 1] = make_float4(la.z, la.w, lb.z, lb.w);
+    }
+}
+
+// piece q of a two-line LDS buffer holding forward(conj(Y)) into registers as Y: ya = line ky, yb = line -ky
+template <int N>
+__device__ __forceinline__ void line_pair_read_conj(float4 &ya, float4 &yb, const float4 *buf4, int b0, int q)
+{
+    if (q < N / 2) {
+        const float4 u = buf4[b0 + 2 * q], v = buf4[b0 + 2 * q + 1];
+        ya = make_float4(u.x, -u.y, v.x, -v.y);
+        yb = make_float4(u.z, -u.w, v.z, -v.w);
+    }
+}
+
+// piece q of the result lines to element offsets e1 and e2 of out; line -ky only where it is another line (pair)
+template <int N>
+__device__ __forceinline__ void line_pair_store(float2 *out, long e1, long e2, bool pair, float4 ya, float4 yb, int q)
+{
+    if (q < N / 2) {
+        *reinterpret_cast<float4 *>(out + e1 + 2 * q) = ya;
+        if (pair) *reinterpret_cast<float4 *>(out + e2 + 2 * q) = yb;
+    }
+}
+
+// What the fused row stage reads of a cross-power job: the packed spectra (one, or three), the outputs (one, or two),
+// and for the three-spectra shape which slot of z[2] the last correlation takes (xpower_stage checks the rest of the
+// shape on the host)
 struct FusedJob {
     const float2 *z[3];
     float2 *out[2];
-    int narr, nout;
-    int ncorr[2];
-    int ia[4], ib[4], pa[4], pb[4];     // correlation 2*o + c of output o
+    int last_part;                      // 0: real slot, 1: imaginary slot
 };
 
 // Row stage of the whole correlation in one persistent kernel, for shapes whose row axis is a single
@@ -318,7 +371,15 @@ struct FusedJob {
 // read of every Y (cross-power) and the re-read of spectra shared by two outputs; one workgroup
 // per CU (3 x 48 KB of LDS at F = 3000) hides HBM latency by the register prefetch instead of
 // occupancy.
-template <int F, int NT, int NARR, int NOUT, int... Rs>
+// ALL chooses the stage scheduler: false = oipfft::StagesPipe (one buffer after the other, a barrier pair per stage and
+// buffer, pipelined), true = oipfft::StagesAll (every stage dealt over all buffers at once; see kFusedRow).
+template <bool ALL, int F, int NT, int NA, int... Rs>
+__device__ __forceinline__ void row_stages(float2 *buf, const float2 *tw, int tid)
+{
+    if constexpr (ALL) oipfft::StagesAll<F, NT, NA, 1, Rs...>::run(buf, tw, tid);
+    else oipfft::StagesPipe<F, NT, NA, 1, Rs...>::run(buf, tw, tid);
+}
+template <int F, int NT, int NARR, int NOUT, bool ALL, int... Rs>
 __global__ __launch_bounds__(NT) void corr_rows_kernel(FusedJob fj, int M, int P, const int *__restrict__ ypos,
                                                        const float2 *__restrict__ twF)
 {
@@ -331,9 +392,6 @@ __global__ __launch_bounds__(NT) void corr_rows_kernel(FusedJob fj, int M, int P
     int ky = blockIdx.x;
     if (ky > half) return;
     for (int i = threadIdx.x; i < TWN; i += NT) tw[i] = twF[i];
-    // Lines move 16 bytes (two points) per lane: half the vector-memory and LDS instructions of 8-byte
-    // accesses -- their operand traffic shares the SIMD-to-LDS path with the stages' ds_writes.
-    static_assert(N % 2 == 0, "two points per lane");
     constexpr int NIT2 = (N / 2 + NT - 1) / NT;
     float4 la[NARR][NIT2], lb[NARR][NIT2];
     float4 *buf4 = reinterpret_cast<float4 *>(buf);
@@ -345,30 +403,14 @@ __global__ __launch_bounds__(NT) void corr_rows_kernel(FusedJob fj, int M, int P
 #pragma unroll
         for (int a = 0; a < NARR; ++a) {
 #pragma unroll
-            for (int it = 0; it < NIT2; ++it) {
-                // lanes past the end of the line re-read its last pair (never committed): a select on
-                // the loaded value would need the load to have completed -- a wait inside the prefetch
-                int q = tid + it * NT;
-                q = q < N / 2 ? q : N / 2 - 1;
-                la[a][it] = *reinterpret_cast<const float4 *>(fj.z[a] + n1 + 2 * q);
-                lb[a][it] = *reinterpret_cast<const float4 *>(fj.z[a] + n2 + 2 * q);
-            }
+            for (int it = 0; it < NIT2; ++it) line_pair_fetch<N>(la[a][it], lb[a][it], fj.z[a], n1, n2, tid + it * NT);
         }
     };
     auto commit = [&](int tid) {
 #pragma unroll
         for (int a = 0; a < NARR; ++a) {
 #pragma unroll
-            for (int it = 0; it < NIT2; ++it) {
-                const int q = tid + it * NT;
-                if (q < N / 2) {
-                    // [point][line] interleave: (2q, line 0), (2q, line 1), (2q+1, line 0), (2q+1, line 1):
-                    // two 16-byte writes 32 bytes apart per lane (2-way bank conflict; four 8-byte writes
-                    // would be 4-way).  The repacking moves sit here, after the loads have landed.
-                    buf4[a * F + 2 * q] = make_float4(la[a][it].x, la[a][it].y, lb[a][it].x, lb[a][it].y);
-                    buf4[a * F + 2 * q + 1] = make_float4(la[a][it].z, la[a][it].w, lb[a][it].z, lb[a][it].w);
-                }
-            }
+            for (int it = 0; it < NIT2; ++it) line_pair_commit<N>(buf4, a * F, la[a][it], lb[a][it], tid + it * NT);
         }
     };
     fetch(threadIdx.x);
@@ -393,7 +435,7 @@ __global__ __launch_bounds__(NT) void corr_rows_kernel(FusedJob fj, int M, int P
             fetch(tid);
         }
         __builtin_amdgcn_sched_barrier(0);
-        oipfft::StagesPipe<F, NT, NARR, 1, Rs...>::run(buf, tw, tid);
+        row_stages<ALL, F, NT, NARR, Rs...>(buf, tw, tid);
 #pragma unroll 1
         for (int it = 0; it < NIT; ++it) {
             const int kx = tid + it * NT;
@@ -404,7 +446,7 @@ __global__ __launch_bounds__(NT) void corr_rows_kernel(FusedJob fj, int M, int P
             // The two job shapes are fixed (xpower_stage checks them on the host), so which spectrum and
             // slot feeds which correlation is known here -- no run-time selects:
             //   1 spectrum : Y0 = C(z0.re, z0.im)
-            //   3 spectra  : A = z0.re against z0.im, z1.re | z1.im, z2.(re or im: fj.pb[3])
+            //   3 spectra  : A = z0.re against z0.im, z1.re | z1.im, z2.(re or im: fj.last_part)
             const float2 zk0 = buf[2 * kx], zm0 = buf[2 * nkx + 1];
             const float2 A = spec_of(0, zk0, zm0);
             float2 y0, y0m, y1 = make_float2(0.f, 0.f), y1m = make_float2(0.f, 0.f);
@@ -421,7 +463,7 @@ __global__ __launch_bounds__(NT) void corr_rows_kernel(FusedJob fj, int M, int P
                 C = cross_power_bin_fast(A, spec_of(1, zk1, zm1), real_bin, edge_col);
                 y1 = C;
                 y1m = make_float2(C.x, -C.y);
-                const float2 B3 = fj.pb[3] ? spec_of(1, zk2, zm2) : spec_of(0, zk2, zm2);
+                const float2 B3 = fj.last_part ? spec_of(1, zk2, zm2) : spec_of(0, zk2, zm2);
                 C = cross_power_bin_fast(A, B3, real_bin, edge_col);
                 y1.x -= C.y; y1.y += C.x; y1m.x += C.y; y1m.y += C.x;
             }
@@ -435,170 +477,14 @@ __global__ __launch_bounds__(NT) void corr_rows_kernel(FusedJob fj, int M, int P
         }
         __syncthreads();
         asm volatile("" : "+v"(tid));
-        oipfft::StagesPipe<F, NT, NOUT, 1, Rs...>::run(buf, tw, tid);
-        if (NOUT == 1) __syncthreads();
+        row_stages<ALL, F, NT, NOUT, Rs...>(buf, tw, tid);
+        // (Looks redundant: StagesPipe<..., NA = 1> already ends on a barrier.  Kept where it has always been -- the
+        // pipelined scheduler with one output -- until dropping it has been measured on its own.)
+        if (!ALL && NOUT == 1) __syncthreads();
         // Results leave LDS through registers so that the next pair can be committed before the stores
         // are issued.
-        float4 ya[NOUT][NIT2], yb[NOUT][NIT2];      // line ky / line -ky, two points each
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) {
-#pragma unroll
-            for (int it = 0; it < NIT2; ++it) {
-                const int q = tid + it * NT;
-                if (q < N / 2) {
-                    const float4 u = buf4[o * F + 2 * q], v = buf4[o * F + 2 * q + 1];
-                    ya[o][it] = make_float4(u.x, -u.y, v.x, -v.y);
-                    yb[o][it] = make_float4(u.z, -u.w, v.z, -v.w);
-                }
-            }
-        }
-        __syncthreads();
-        if (more) commit(tid);
-        __builtin_amdgcn_sched_barrier(0);
-        const long o1 = s1, o2 = s2;
-        s1 = n1; s2 = n2;
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o) {
-            float2 *out = fj.out[o];
-#pragma unroll
-            for (int it = 0; it < NIT2; ++it) {
-                const int q = tid + it * NT;
-                if (q < N / 2) {
-                    *reinterpret_cast<float4 *>(out + o1 + 2 * q) = ya[o][it];
-                    if (pair) *reinterpret_cast<float4 *>(out + o2 + 2 * q) = yb[o][it];
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// The same row stage with a three-stage factorisation (3000 = 25 * 15 * 8: composite butterflies in registers,
-// oip_fft_dev.h) and every stage dealt over all buffers at once: a point crosses LDS three times per transform instead
-// of five, a stage costs two barriers for all buffers instead of one per buffer.  Single-line items keep LDS accesses
-// 8 bytes wide and conflict-free (the first stage stores at a 25-point stride: 100 dwords, odd multiple of 4).
-// Measured per launch: 0.80 -> 0.76 ms at 3000 points.  The 1250-point geometry (25 * 25 * 2) was measured too and is
-// slower this way (0.46 vs 0.33 ms: eight rounds of radix-2 items), so it keeps the five-stage kernel.
-template <int F, int NT, int NARR, int NOUT, int... Rs>
-__global__ __launch_bounds__(NT) void corr_rows3_kernel(FusedJob fj, int M, int P, const int *__restrict__ ypos,
-                                                       const float2 *__restrict__ twF)
-{
-    constexpr int TWN = oipfft::TwTable<F, Rs...>::value();
-    constexpr int N = F;
-    constexpr int NIT = (N + NT - 1) / NT;
-    __shared__ __align__(16) float2 buf[NARR * 2 * F];   // [spectrum][point][line]: line 0 = ky, line 1 = -ky
-    __shared__ float2 tw[TWN];
-    const int half = M / 2;
-    int ky = blockIdx.x;
-    if (ky > half) return;
-    for (int i = threadIdx.x; i < TWN; i += NT) tw[i] = twF[i];
-    // Lines move 16 bytes (two points) per lane: half the vector-memory and LDS instructions of 8-byte
-    // accesses -- their operand traffic shares the SIMD-to-LDS path with the stages' ds_writes.
-    static_assert(N % 2 == 0, "two points per lane");
-    constexpr int NIT2 = (N / 2 + NT - 1) / NT;
-    float4 la[NARR][NIT2], lb[NARR][NIT2];
-    float4 *buf4 = reinterpret_cast<float4 *>(buf);
-    // rows of the line pair whose loads are in la/lb (n1, n2) and of the pair in LDS (s1, s2)
-    // (row positions come from a per-plan table: decoding them with the digit loop cost ~300 scalar
-    // instructions and four dependent scalar loads per iteration, on every wave at the same time)
-    long n1 = (long)ypos[ky] * P, n2 = (long)ypos[ky ? M - ky : 0] * P;
-    auto fetch = [&](int tid) {
-#pragma unroll
-        for (int a = 0; a < NARR; ++a) {
-#pragma unroll
-            for (int it = 0; it < NIT2; ++it) {
-                // lanes past the end of the line re-read its last pair (never committed): a select on
-                // the loaded value would need the load to have completed -- a wait inside the prefetch
-                int q = tid + it * NT;
-                q = q < N / 2 ? q : N / 2 - 1;
-                la[a][it] = *reinterpret_cast<const float4 *>(fj.z[a] + n1 + 2 * q);
-                lb[a][it] = *reinterpret_cast<const float4 *>(fj.z[a] + n2 + 2 * q);
-            }
-        }
-    };
-    auto commit = [&](int tid) {
-#pragma unroll
-        for (int a = 0; a < NARR; ++a) {
-#pragma unroll
-            for (int it = 0; it < NIT2; ++it) {
-                const int q = tid + it * NT;
-                if (q < N / 2) {
-                    // [point][line] interleave: (2q, line 0), (2q, line 1), (2q+1, line 0), (2q+1, line 1):
-                    // two 16-byte writes 32 bytes apart per lane (2-way bank conflict; four 8-byte writes
-                    // would be 4-way).  The repacking moves sit here, after the loads have landed.
-                    buf4[a * F + 2 * q] = make_float4(la[a][it].x, la[a][it].y, lb[a][it].x, lb[a][it].y);
-                    buf4[a * F + 2 * q + 1] = make_float4(la[a][it].z, la[a][it].w, lb[a][it].z, lb[a][it].w);
-                }
-            }
-        }
-    };
-    fetch(threadIdx.x);
-    commit(threadIdx.x);
-    long s1 = n1, s2 = n2;
-    __syncthreads();
-    for (; ky <= half; ky += gridDim.x) {
-        // opaque per iteration: keeps the stage address arithmetic from being hoisted out of this
-        // loop, where it would occupy registers for the whole kernel
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        const bool pair = s1 != s2;
-        // The lines of the NEXT pair are requested first and committed at the bottom of this same
-        // iteration: the registers holding them then never cross the loop's back edge.  (Carried across
-        // it, the register allocator gave the loop-header values other registers than the loads'
-        // destinations and copied right after the loads -- waiting for them at the point of issue.)
-        const int kn = ky + gridDim.x;
-        const bool more = kn <= half;
-        if (more) {
-            n1 = (long)ypos[kn] * P;
-            n2 = (long)ypos[M - kn] * P;
-            fetch(tid);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        oipfft::StagesAll<F, NT, NARR, 1, Rs...>::run(buf, tw, tid);
-#pragma unroll 1
-        for (int it = 0; it < NIT; ++it) {
-            const int kx = tid + it * NT;
-            if (kx >= N) continue;
-            const int nkx = kx ? N - kx : 0;
-            const bool edge_col = (kx == 0) || (2 * kx == N);
-            const bool real_bin = edge_col && (ky == 0 || 2 * ky == M);
-            // The two job shapes are fixed (xpower_stage checks them on the host), so which spectrum and
-            // slot feeds which correlation is known here -- no run-time selects:
-            //   1 spectrum : Y0 = C(z0.re, z0.im)
-            //   3 spectra  : A = z0.re against z0.im, z1.re | z1.im, z2.(re or im: fj.pb[3])
-            const float2 zk0 = buf[2 * kx], zm0 = buf[2 * nkx + 1];
-            const float2 A = spec_of(0, zk0, zm0);
-            float2 y0, y0m, y1 = make_float2(0.f, 0.f), y1m = make_float2(0.f, 0.f);
-            {
-                const float2 C = cross_power_bin_fast(A, spec_of(1, zk0, zm0), real_bin, edge_col);
-                y0 = C;
-                y0m = make_float2(C.x, -C.y);
-            }
-            if (NARR == 3) {
-                const float2 zk1 = buf[2 * F + 2 * kx], zm1 = buf[2 * F + 2 * nkx + 1];
-                const float2 zk2 = buf[4 * F + 2 * kx], zm2 = buf[4 * F + 2 * nkx + 1];
-                float2 C = cross_power_bin_fast(A, spec_of(0, zk1, zm1), real_bin, edge_col);
-                y0.x -= C.y; y0.y += C.x; y0m.x += C.y; y0m.y += C.x;                        // + i C, + i conj(C)
-                C = cross_power_bin_fast(A, spec_of(1, zk1, zm1), real_bin, edge_col);
-                y1 = C;
-                y1m = make_float2(C.x, -C.y);
-                const float2 B3 = fj.pb[3] ? spec_of(1, zk2, zm2) : spec_of(0, zk2, zm2);
-                C = cross_power_bin_fast(A, B3, real_bin, edge_col);
-                y1.x -= C.y; y1.y += C.x; y1m.x += C.y; y1m.y += C.x;
-            }
-            // inverse = conj(forward(conj(.)))
-            buf[2 * kx] = make_float2(y0.x, -y0.y);
-            buf[2 * nkx + 1] = pair ? make_float2(y0m.x, -y0m.y) : make_float2(0.f, 0.f);
-            if (NOUT == 2) {
-                buf[2 * F + 2 * kx] = make_float2(y1.x, -y1.y);
-                buf[2 * F + 2 * nkx + 1] = pair ? make_float2(y1m.x, -y1m.y) : make_float2(0.f, 0.f);
-            }
-        }
-        __syncthreads();
-        asm volatile("" : "+v"(tid));
-        oipfft::StagesAll<F, NT, NOUT, 1, Rs...>::run(buf, tw, tid);
-        // Results leave LDS through registers so that the next pair can be committed before the stores
-        // are issued.
+        // (line_pair_read_conj and line_pair_store written out: through the helpers the three-spectra forms compile to
+        // another register assignment in the cross-power loop)
         float4 ya[NOUT][NIT2], yb[NOUT][NIT2];      // line ky / line -ky, two points each
 #pragma unroll
         for (int o = 0; o < NOUT; ++o) {
@@ -784,6 +670,7 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
         }
     };
     auto fetch = [&](int tid) {
+        // (line_pair_fetch written out: with the helper the loads are scheduled differently in this kernel)
 #pragma unroll
         for (int it = 0; it < NIT2; ++it) {
             int q = tid + it * NT;
@@ -796,13 +683,7 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
     auto commit = [&](int tid) {
         if (VEXP) fetch_narrow(tid);
 #pragma unroll
-        for (int it = 0; it < NIT2; ++it) {
-            const int q = tid + it * NT;
-            if (q < F / 2) {
-                buf4[2 * q] = make_float4(la[it].x, la[it].y, lb[it].x, lb[it].y);
-                buf4[2 * q + 1] = make_float4(la[it].z, la[it].w, lb[it].z, lb[it].w);
-            }
-        }
+        for (int it = 0; it < NIT2; ++it) line_pair_commit<F>(buf4, 0, la[it], lb[it], tid + it * NT);
 #pragma unroll
         for (int it = 0; it < NITN; ++it) {
             const int q = tid + it * NT;
@@ -945,14 +826,7 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
 #pragma unroll
             for (int o = 0; o < 2; ++o) {
 #pragma unroll
-                for (int it = 0; it < NIT2; ++it) {
-                    const int q = tid + it * NT;
-                    if (q < F / 2) {
-                        const float4 u = buf4[o * F + 2 * q], v = buf4[o * F + 2 * q + 1];
-                        ya[o][it] = make_float4(u.x, -u.y, v.x, -v.y);
-                        yb[o][it] = make_float4(u.z, -u.w, v.z, -v.w);
-                    }
-                }
+                for (int it = 0; it < NIT2; ++it) line_pair_read_conj<F>(ya[o][it], yb[o][it], buf4, o * F, tid + it * NT);
             }
             __syncthreads();
         };
@@ -961,13 +835,7 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
             for (int o = 0; o < 2; ++o) {
                 float2 *out = fj.out[o0 + o];
 #pragma unroll
-                for (int it = 0; it < NIT2; ++it) {
-                    const int q = tid + it * NT;
-                    if (q < F / 2) {
-                        *reinterpret_cast<float4 *>(out + s1 * P + 2 * q) = ya[o][it];
-                        if (pair) *reinterpret_cast<float4 *>(out + s2 * P + 2 * q) = yb[o][it];
-                    }
-                }
+                for (int it = 0; it < NIT2; ++it) line_pair_store<F>(out, s1 * P, s2 * P, pair, ya[o][it], yb[o][it], tid + it * NT);
             }
         };
         xround(0, Aa);
@@ -1062,6 +930,7 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void corr_rows_v_kernel(VRowsJob 
     const float2 *zn = fj.zn + (long)a0 * fj.zn_stride;
     const float2 *raw = fj.raw + (long)a0 * fj.zn_stride;
     auto fetch = [&](int tid) {                     // the PAN line pair, the band lines and their coefficients: one iteration ahead
+        // (line_pair_fetch written out: with the helper the loads are scheduled differently in this kernel)
 #pragma unroll
         for (int it = 0; it < NIT2; ++it) {
             int q = tid + it * NT;
@@ -1083,15 +952,11 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void corr_rows_v_kernel(VRowsJob 
     };
     auto commit = [&](int tid) {
 #pragma unroll
-        for (int it = 0; it < NIT2; ++it) {
-            const int q = tid + it * NT;
-            if (q < N / 2) {
-                buf4[2 * q] = make_float4(la[it].x, la[it].y, lb[it].x, lb[it].y);
-                buf4[2 * q + 1] = make_float4(la[it].z, la[it].w, lb[it].z, lb[it].w);
-            }
-        }
+        for (int it = 0; it < NIT2; ++it) line_pair_commit<N>(buf4, 0, la[it], lb[it], tid + it * NT);
         // line ky of the vertically up-sampled band pair: Hv[ky] zn[ky mod m] + sum_i Gv_i[ky] raw_i; Hv and Gv of line
         // -ky are the conjugates.  The raw rows (160 KB for a pair of units: L2 hits) are read here, not held.
+        // (The same sum as in corr_rows_up_kernel's commit.  One function for both, fed the four raw rows as float2,
+        // was tried: it gathers the raw loads ahead of the multiply-adds and this kernel then spills 16 VGPRs.)
 #pragma unroll
         for (int it = 0; it < NITN; ++it) {
             const int q = tid + it * NT;
@@ -1160,14 +1025,7 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void corr_rows_v_kernel(VRowsJob 
 #pragma unroll
         for (int o = 0; o < NB; ++o) {
 #pragma unroll
-            for (int it = 0; it < NIT2; ++it) {
-                const int q = tid + it * NT;
-                if (q < N / 2) {
-                    const float4 u = buf4[(1 + o) * F + 2 * q], v = buf4[(1 + o) * F + 2 * q + 1];
-                    ya[o][it] = make_float4(u.x, -u.y, v.x, -v.y);
-                    yb[o][it] = make_float4(u.z, -u.w, v.z, -v.w);
-                }
-            }
+            for (int it = 0; it < NIT2; ++it) line_pair_read_conj<N>(ya[o][it], yb[o][it], buf4, (1 + o) * F, tid + it * NT);
         }
         __syncthreads();
         if (more) commit(tid);
@@ -1176,13 +1034,7 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void corr_rows_v_kernel(VRowsJob 
         for (int o = 0; o < NB; ++o) {
             float2 *out = fj.out[a0 + o];
 #pragma unroll
-            for (int it = 0; it < NIT2; ++it) {
-                const int q = tid + it * NT;
-                if (q < N / 2) {
-                    *reinterpret_cast<float4 *>(out + s1 * P + 2 * q) = ya[o][it];
-                    if (pair) *reinterpret_cast<float4 *>(out + s2 * P + 2 * q) = yb[o][it];
-                }
-            }
+            for (int it = 0; it < NIT2; ++it) line_pair_store<N>(out, s1 * P, s2 * P, pair, ya[o][it], yb[o][it], tid + it * NT);
         }
         s1 = n1; s2 = n2;
         __syncthreads();
@@ -1238,14 +1090,23 @@ __global__ __launch_bounds__(128) void hpack_bands_kernel(HPackJob job, int m, i
 struct FusedRow {
     int F, fwd_threads;
     void (*fwd1)(FusedJob, int, int, const int *, const float2 *);        // one spectrum -> one output
-    void (*fwd3)(FusedJob, int, int, const int *, const float2 *);        // three spectra -> two outputs (3000: corr_rows3_kernel)
+    void (*fwd3)(FusedJob, int, int, const int *, const float2 *);        // three spectra -> two outputs
 };
 // power-of-two radices last: their stores are then contiguous in LDS (a leading radix-8 stage
 // stores at a 128-byte stride, an 8-way bank conflict for ds_write_b64)
+//
+// 3000 points, three spectra: a three-stage factorisation (3000 = 25 * 15 * 8: composite butterflies in registers,
+// oip_fft_dev.h) and every stage dealt over all buffers at once (StagesAll): a point crosses LDS three times per transform
+// instead of five, a stage costs two barriers for all buffers instead of one per buffer.  Single-line items keep LDS
+// accesses 8 bytes wide and conflict-free (the first stage stores at a 25-point stride: 100 dwords, odd multiple of 4).
+// Measured per launch: 0.80 -> 0.76 ms at 3000 points.  The 1250-point geometry (25 * 25 * 2) was measured too and is
+// slower this way (0.46 vs 0.33 ms: eight rounds of radix-2 items), so it keeps the five-stage kernel.
+// xpower_stage's grid rule gives this entry one workgroup per CU, the grid it was tuned at: its LDS estimate is
+// 8 * (3 * 2 * 3000 + 1500) = 156000 B, so per_cu = min(163840 / 156000, 2048 / 768) = min(1, 2) = 1.
 const FusedRow kFusedRow[] = {
-    {3000, 768, corr_rows_kernel<3000, 768, 1, 1, 3, 5, 5, 5, 8>, nullptr},
-    {1250, 512, corr_rows_kernel<1250, 512, 1, 1, 5, 5, 5, 5, 2>, corr_rows_kernel<1250, 512, 3, 2, 5, 5, 5, 5, 2>},
-    {200, 256, corr_rows_kernel<200, 256, 1, 1, 5, 5, 8>, corr_rows_kernel<200, 256, 3, 2, 5, 5, 8>},
+    {3000, 768, corr_rows_kernel<3000, 768, 1, 1, false, 3, 5, 5, 5, 8>, corr_rows_kernel<3000, 768, 3, 2, /*all*/ true, 25, 15, 8>},
+    {1250, 512, corr_rows_kernel<1250, 512, 1, 1, false, 5, 5, 5, 5, 2>, corr_rows_kernel<1250, 512, 3, 2, false, 5, 5, 5, 5, 2>},
+    {200, 256, corr_rows_kernel<200, 256, 1, 1, false, 5, 5, 8>, corr_rows_kernel<200, 256, 3, 2, false, 5, 5, 8>},
 };
 
 // ---- peak: first maximum of the fftShift-ed surface + 5x5 weighted centroid ----------------------
@@ -1657,45 +1518,40 @@ int xpower_stage(oip_ctx *ctx, const OipFft2dPlan *pl, const FusedRow *rk, const
     const float2 *twF;
     int rc = oip_fft_table(ctx, rk->F, &twF);
     if (rc) return rc;
+    // the distinct spectra of the job, and per correlation which spectrum and slot hold A and B
     FusedJob fj;
     memset(&fj, 0, sizeof fj);
-    fj.nout = nout;
+    int narr = 0, ia[4], ib[4], pa[4], pb[4];
     auto slot = [&](const float2 *z) {
-        for (int i = 0; i < fj.narr; ++i) if (fj.z[i] == z) return i;
-        if (fj.narr == 3) return -1;
-        fj.z[fj.narr] = z;
-        return fj.narr++;
+        for (int i = 0; i < narr; ++i) if (fj.z[i] == z) return i;
+        if (narr == 3) return -1;
+        fj.z[narr] = z;
+        return narr++;
     };
     for (int c = 0; c < ncorr; ++c) {
-        fj.ia[c] = slot(a[c].z); fj.pa[c] = a[c].part;
-        fj.ib[c] = slot(b[c].z); fj.pb[c] = b[c].part;
-        if (fj.ia[c] < 0 || fj.ib[c] < 0) return oip_fail(ctx, OIP_E_RUNTIME, "xpower_stage: more than three spectra");
-        fj.ncorr[c / 2]++;
+        ia[c] = slot(a[c].z); pa[c] = a[c].part;
+        ib[c] = slot(b[c].z); pb[c] = b[c].part;
+        if (ia[c] < 0 || ib[c] < 0) return oip_fail(ctx, OIP_E_RUNTIME, "xpower_stage: more than three spectra");
     }
     for (int o = 0; o < nout; ++o) fj.out[o] = y[o];
-    // persistent: as many workgroups as fit the CUs at once (LDS- or thread-limited)
     // the kernel hard-wires which spectrum and slot feeds which correlation
-    const bool one = fj.narr == 1 && fj.nout == 1 && ncorr == 1 && fj.ia[0] == 0 && fj.pa[0] == 0 && fj.ib[0] == 0 && fj.pb[0] == 1;
-    bool three = fj.narr == 3 && fj.nout == 2 && ncorr == 4;
+    const bool one = narr == 1 && ncorr == 1 && ia[0] == 0 && pa[0] == 0 && ib[0] == 0 && pb[0] == 1;
+    bool three = narr == 3 && ncorr == 4;
     const int want_ib[4] = {0, 1, 1, 2}, want_pb[3] = {1, 0, 1};
     for (int c = 0; c < 4 && three; ++c)
-        three = fj.ia[c] == 0 && fj.pa[c] == 0 && fj.ib[c] == want_ib[c] && (c == 3 || fj.pb[c] == want_pb[c]);
+        three = ia[c] == 0 && pa[c] == 0 && ib[c] == want_ib[c] && (c == 3 || pb[c] == want_pb[c]);
     if (!one && !three) return oip_fail(ctx, OIP_E_RUNTIME, "xpower_stage: unsupported job shape");
-    const size_t lds = sizeof(float2) * ((size_t)fj.narr * 2 * rk->F + rk->F / 2);
+    if (three) fj.last_part = pb[3];
+    // persistent: as many workgroups as fit the CUs at once (LDS- or thread-limited)
+    const size_t lds = sizeof(float2) * ((size_t)narr * 2 * rk->F + rk->F / 2);
     long per_cu = (long)(160 * 1024 / lds);
     if (per_cu > 2048 / rk->fwd_threads) per_cu = 2048 / rk->fwd_threads;
     if (per_cu < 1) per_cu = 1;
     long grid = (long)ctx->cu_count * per_cu;
     if (grid > pl->M / 2 + 1) grid = pl->M / 2 + 1;
     OipProfScope prof(ctx, "corr_rows_kernel");
-    if (three && rk->F == 3000) {
-        long g3 = ctx->cu_count;
-        if (g3 > pl->M / 2 + 1) g3 = pl->M / 2 + 1;
-        hipLaunchKernelGGL((corr_rows3_kernel<3000, 768, 3, 2, 25, 15, 8>), dim3((unsigned)g3), dim3(768), 0, ctx->stream, fj, pl->M, pl->P,
-                           pl->d_ypos, twF);
-    } else
-        hipLaunchKernelGGL(one ? rk->fwd1 : rk->fwd3, dim3((unsigned)grid), dim3(rk->fwd_threads), 0, ctx->stream, fj, pl->M,
-                           pl->P, pl->d_ypos, twF);
+    hipLaunchKernelGGL(one ? rk->fwd1 : rk->fwd3, dim3((unsigned)grid), dim3(rk->fwd_threads), 0, ctx->stream, fj, pl->M, pl->P,
+                       pl->d_ypos, twF);
     OIP_HIP(ctx, hipGetLastError());
     return OIP_OK;
 }

@@ -61,6 +61,7 @@ PC_SHAPES = [
     (4000, 1250, (-6, 5)),     # 1250 = 2*5^4 rows
     (3000, 100, (0, 0)),       # identical images: peak at the centre
     (243, 125, (2, 1)),        # odd sizes both ways (3^5 x 5^3)
+    (1600, 3000, (3, -1)),     # 3000-point rows, one spectrum; 801 line pairs: some workgroups take a second pair
 ]
 
 
