@@ -139,6 +139,54 @@ int oip_rrc_fit_columns(const uint64_t *acc, int w, int groups, int mode, uint64
  * replaced: refusing to do so is the caller's policy (`oip rrc-calib` without --force). */
 int oip_write_rrc_param_file(const char *path, const double *kb, int n, char *err, int errlen);
 
+/* ---- quick look: an 8-bit browse image of a strip or product (`oip quicklook`; not in the reference) ------------- */
+#define OIP_QUICKLOOK_SUFFIX       ".QL"   /* <stem>.QL.TIFF, built like the reference's other product names (imageop.h:99-108) */
+#define OIP_QUICKLOOK_DEF_FACTOR   16
+#define OIP_QUICKLOOK_DEF_CLIPLOW  2.0
+#define OIP_QUICKLOOK_DEF_CLIPHIGH 98.0
+
+/* F x F box decimation of a u16 raster window, the one pass over the full-size image.  d_src: first sample of the window;
+ * rows lines of w pixels of spp samples (1, or 4 pixel-interleaved), lines `pitch` SAMPLES apart, the window inside the
+ * lines of its raster (start + w * spp <= pitch).  factor F in {2, 4, 8, 16, 32, 64}.  Output: one plane per channel
+ * (spp = 4 de-interleaves), ceil(w / F) x ceil(rows / F) samples, lines dst_pitch samples apart, plane c at
+ * d_dst + c * dst_plane_stride (samples; ignored at spp = 1).  For each output sample, with S the exact integer sum of
+ * the source samples of its channel that lie inside the image within its F x F block and n their count:
+ *   q = (S + n / 2) / n          (integer division; n / 2 floored; edge blocks use their own n)
+ * A strip larger than the device is cut into calls by the caller: as long as every call starts on a line that is a
+ * multiple of F (and writes from output line first / F on) the result is that of one call.  Asynchronous on the context's
+ * stream.  A pitch that is not a multiple of 8 samples, or a window that does not start on a 16-byte boundary, takes a
+ * slower kernel with the same result. */
+int oip_decimate_box_u16(oip_ctx *ctx, const uint16_t *d_src, long pitch, int w, long rows, int spp, int factor,
+                         uint16_t *d_dst, long dst_pitch, size_t dst_plane_stride);
+
+/* Histogram of a u16 raster window (rows lines of w samples, `pitch` samples apart), ADDED into d_hist: 65536 uint64 in
+ * HBM, zeroed by the caller (oip_memset) before the first call.  Exact counts, additive over calls.  Asynchronous. */
+int oip_histogram_u16(oip_ctx *ctx, const uint16_t *d_img, long pitch, int w, long rows, uint64_t *d_hist);
+
+/* out[(r * w + x) * nch + c] = luts[c * 65536 + planes[c][r * pitch + x]]: nch (1 or 3) u16 planes through one 65536-entry
+ * table each into an interleaved 8-bit image.  d_planes: nch device pointers -- the array itself is host memory and is read
+ * during the call; d_luts (nch * 65536 bytes) and d_out (rows * w * nch bytes) are in HBM.  Asynchronous. */
+int oip_apply_lut_u8(oip_ctx *ctx, const uint16_t *const *d_planes, long pitch, int w, long rows, int nch,
+                     const uint8_t *d_luts, uint8_t *d_out);
+
+/* Percentile limits of a histogram, host.  hist: 65536 counts.  N = number of samples with valid_min <= v <= valid_max;
+ * for p in (p_lo, p_hi):  r = min(N - 1, (uint64_t)floor((double)N * p / 100.0))  and the limit is the value at sorted
+ * index r among the valid samples, i.e. the smallest v whose cumulative count (from valid_min) exceeds r.
+ * N == 0: *lo = *hi = 0.  *n_valid (may be NULL) = N.  OIP_E_INVALID unless 0 <= p_lo <= p_hi <= 100 and
+ * 0 <= valid_min <= valid_max <= 65535.  No context needed. */
+int oip_stretch_limits(const uint64_t *hist, int valid_min, int valid_max, double p_lo, double p_hi,
+                       int *lo, int *hi, uint64_t *n_valid);
+
+/* The linear stretch lo..hi -> 0..255 as a table, host: with span = hi - lo > 0
+ *   lut[v] = ((clamp(v, lo, hi) - lo) * 510 + span) / (2 * span)      (integers: round half up of 255 (v - lo) / span)
+ * and with span == 0: lut[v] = v < lo ? 0 : 255.  lut: 65536 bytes.  OIP_E_INVALID unless 0 <= lo <= hi <= 65535. */
+int oip_stretch_lut_u8(int lo, int hi, uint8_t *lut);
+
+/* An 8-bit baseline TIFF (classic, little-endian, uncompressed strips, chunky): spp 1 (BlackIsZero) or 3 (RGB), data =
+ * height x width x spp bytes.  An existing file is replaced.  OIP_E_INVALID for geometry it cannot hold (4 GiB),
+ * OIP_E_IO when the file cannot be written. */
+int oip_write_tiff_u8(const char *path, const uint8_t *data, int width, long height, int spp, char *err, int errlen);
+
 /* ---- raster I/O staging (imageop.h:43-127, stitcher.h:103-120) ---------------------------------------
  * IMO::ReadFileContent + LoadRawImage / WriteBufferToFile move a raster through one pageable heap buffer,
  * serially with the arithmetic (8 MiB fread / fwrite units on the calling thread, imageop.h:69-79, :88-95).

@@ -22,9 +22,12 @@ from .capi import (  # noqa: F401
     polyfit,
     remap_shift_src_range,
     rrc_fit_columns,
+    stretch_limits,
+    stretch_lut_u8,
     stt_mean,
     upsample_operator,
     write_rrc_param_file,
+    write_tiff_u8,
     align_mss_src_range,
 )
 

@@ -66,6 +66,12 @@ _SIGS = {
     "oip_colstats_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _vp], _i),
     "oip_rrc_fit_columns": ([C.POINTER(C.c_uint64), _i, _i, _i, C.c_uint64, _dp, C.POINTER(_i), _dp, _cp, _i], _i),
     "oip_write_rrc_param_file": ([_cp, _dp, _i, _cp, _i], _i),
+    "oip_decimate_box_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _vp, _l, _sz], _i),
+    "oip_histogram_u16": ([_vp, _vp, _l, _i, _l, _vp], _i),
+    "oip_apply_lut_u8": ([_vp, C.POINTER(_vp), _l, _i, _l, _i, _vp, _vp], _i),
+    "oip_stretch_limits": ([C.POINTER(C.c_uint64), _i, _i, _d, _d, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_uint64)], _i),
+    "oip_stretch_lut_u8": ([_i, _i, C.POINTER(C.c_uint8)], _i),
+    "oip_write_tiff_u8": ([_cp, _vp, _i, _l, _i, _cp, _i], _i),
     "oip_read_file_to_device": ([_vp, _cp, _sz, _sz, _vp, C.POINTER(_sz), _lp], _i),
     "oip_write_device_to_file": ([_vp, _vp, _sz, _cp, _i], _i),
     "oip_write_device_to_file_at": ([_vp, _vp, _sz, _cp, _sz, _l], _i),
@@ -195,6 +201,40 @@ def write_rrc_param_file(path: str, kb) -> None:
     kb = _dbl(kb).reshape(-1, 2)
     err = C.create_string_buffer(2048)
     rc = lib.oip_write_rrc_param_file(os.fsencode(path), kb.ctypes.data_as(_dp), kb.shape[0], err, 2048)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+
+
+def stretch_limits(hist, valid_min=1, valid_max=65535, p_lo=2.0, p_hi=98.0):
+    """(lo, hi, n_valid) of a 65536-bin histogram: the values at the p_lo / p_hi percentile ranks among the samples with
+    valid_min <= v <= valid_max (include/oip_c.h: oip_stretch_limits)"""
+    lib = load_library()
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    assert h.shape == (65536,), h.shape
+    lo, hi, n = _i(), _i(), C.c_uint64()
+    rc = lib.oip_stretch_limits(h.ctypes.data_as(C.POINTER(C.c_uint64)), valid_min, valid_max, p_lo, p_hi, C.byref(lo), C.byref(hi), C.byref(n))
+    if rc:
+        raise ValueError("oip_stretch_limits: bad argument")
+    return lo.value, hi.value, n.value
+
+
+def stretch_lut_u8(lo: int, hi: int) -> np.ndarray:
+    """the 65536-entry table of the linear stretch lo..hi -> 0..255 (include/oip_c.h: oip_stretch_lut_u8)"""
+    lib = load_library()
+    lut = np.zeros(65536, np.uint8)
+    rc = lib.oip_stretch_lut_u8(lo, hi, lut.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc:
+        raise ValueError("oip_stretch_lut_u8: bad argument")
+    return lut
+
+
+def write_tiff_u8(path: str, img) -> None:
+    """(rows, w) or (rows, w, 3) uint8 as an uncompressed baseline TIFF (include/oip_c.h: oip_write_tiff_u8)"""
+    lib = load_library()
+    a = np.ascontiguousarray(img, dtype=np.uint8)
+    assert a.ndim in (2, 3), a.shape
+    err = C.create_string_buffer(1024)
+    rc = lib.oip_write_tiff_u8(os.fsencode(path), a.ctypes.data, a.shape[1], a.shape[0], 1 if a.ndim == 2 else a.shape[2], err, 1024)
     if rc:
         raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
 
@@ -333,6 +373,22 @@ class Context:
         """per-column count / sum / sum of squares of rows x w u16 (lines `pitch` pixels apart) ADDED into acc: (3, w) uint64
         on the device, zeroed by the caller before the first call"""
         self._ck(self.lib.oip_colstats_u16(self.h, _ptr(img), pitch, w, rows, valid_min, valid_max, _ptr(acc)))
+
+    # -- quick look
+    def decimate_box_u16(self, src, pitch, w, rows, spp, factor, dst, dst_pitch, dst_plane_stride=0):
+        """factor x factor box means of rows x w pixels of spp samples (lines `pitch` samples apart) into one plane per channel,
+        ceil(w / factor) x ceil(rows / factor) each (include/oip_c.h: oip_decimate_box_u16)"""
+        self._ck(self.lib.oip_decimate_box_u16(self.h, _ptr(src), pitch, w, rows, spp, factor, _ptr(dst), dst_pitch, dst_plane_stride))
+
+    def histogram_u16(self, img, pitch, w, rows, hist):
+        """counts of rows x w u16 (lines `pitch` samples apart) ADDED into hist: 65536 uint64 on the device, zeroed by the caller"""
+        self._ck(self.lib.oip_histogram_u16(self.h, _ptr(img), pitch, w, rows, _ptr(hist)))
+
+    def apply_lut_u8(self, planes, pitch, w, rows, luts, out):
+        """1 or 3 u16 planes through luts (nch x 65536 uint8 on the device) into out: rows x w x nch uint8, interleaved"""
+        n = len(planes)
+        pp = (C.c_void_p * n)(*[_ptr(p) for p in planes])
+        self._ck(self.lib.oip_apply_lut_u8(self.h, pp, pitch, w, rows, n, _ptr(luts), _ptr(out)))
 
     def rrc_u16_host(self, buff: np.ndarray, kb):
         assert buff.dtype == np.uint16 and buff.flags.c_contiguous and buff.ndim == 2

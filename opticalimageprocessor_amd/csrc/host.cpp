@@ -1,5 +1,6 @@
 // host.cpp -- host-side pieces of the path that carry no raster arithmetic:
-// the RRC parameter file loader, its counterpart (column fit + writer) and the shift filtering / polynomial fit.
+// the RRC parameter file loader, its counterpart (column fit + writer), the shift filtering / polynomial fit and the
+// contrast stretch of `oip quicklook` (percentile limits, 8-bit table, 8-bit TIFF).
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "oip_c.h"
+#include "oip_tiff.hpp"
 
 // IMO::LoadRRCParamFile (imageop.h:140-192): three header lines (only the second -- the
 // column count -- is checked outside DEBUG builds), then one "k , b" row per column parsed
@@ -388,5 +390,62 @@ extern "C" int oip_upsample_operator(int n, float *out)
     };
     dft(h, out);
     for (int j = 0; j < 4; ++j) dft(g[j], out + (size_t)(1 + j) * N * 2);
+    return OIP_OK;
+}
+
+// ---- oip quicklook, host side: the contrast stretch between the histogram and the look-up kernel (include/oip_c.h states
+// the arithmetic; tests/_quicklook_ref.py restates it) ------------------------------------------------------------------
+extern "C" int oip_stretch_limits(const uint64_t *hist, int valid_min, int valid_max, double p_lo, double p_hi, int *lo, int *hi,
+                                  uint64_t *n_valid)
+{
+    if (!hist || !lo || !hi || valid_min < 0 || valid_max > 65535 || valid_min > valid_max || !(p_lo >= 0.0) || !(p_hi <= 100.0) || !(p_lo <= p_hi))
+        return OIP_E_INVALID;
+    uint64_t N = 0;
+    for (int v = valid_min; v <= valid_max; ++v) N += hist[v];
+    if (n_valid) *n_valid = N;
+    *lo = *hi = 0;
+    if (N == 0) return OIP_OK;
+    auto at = [&](double p) {
+        const double f = std::floor((double)N * p / 100.0);
+        uint64_t r = f >= 18446744073709551616.0 ? N - 1 : (uint64_t)f;
+        if (r > N - 1) r = N - 1;
+        uint64_t cum = 0;
+        for (int v = valid_min; v <= valid_max; ++v) {
+            cum += hist[v];
+            if (cum > r) return v;
+        }
+        return valid_max;                                    // not reached: cum ends at N > r
+    };
+    *lo = at(p_lo);
+    *hi = at(p_hi);
+    return OIP_OK;
+}
+
+extern "C" int oip_stretch_lut_u8(int lo, int hi, uint8_t *lut)
+{
+    if (!lut || lo < 0 || hi > 65535 || lo > hi) return OIP_E_INVALID;
+    const uint32_t span = (uint32_t)(hi - lo);
+    for (int v = 0; v < 65536; ++v) {
+        if (span == 0) { lut[v] = v < lo ? 0 : 255; continue; }
+        const uint32_t c = (uint32_t)((v < lo ? lo : (v > hi ? hi : v)) - lo);
+        lut[v] = (uint8_t)((c * 510u + span) / (2u * span));           // 65535 * 510 + 65535 < 2^32
+    }
+    return OIP_OK;
+}
+
+extern "C" int oip_write_tiff_u8(const char *path, const uint8_t *data, int width, long height, int spp, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *msg) {
+        if (err && errlen > 0) snprintf(err, errlen, "%s", msg);
+        return code;
+    };
+    if (!path) return fail(OIP_E_INVALID, "oip_write_tiff_u8: bad argument");
+    try {
+        OIPGPU::write_tiff_u8(path, data, width, height, spp);
+    } catch (const std::invalid_argument &e) {
+        return fail(OIP_E_INVALID, e.what());
+    } catch (const std::exception &e) {
+        return fail(OIP_E_IO, e.what());
+    }
     return OIP_OK;
 }

@@ -1620,4 +1620,152 @@ inline void RunRrcCalib(const std::string &pan, const std::string &mss, const st
     for (int b = 0; b < MSS_BANDS && !mss.empty(); ++b) write(outMss[b], &kbMss[2 * (size_t)b * bw], bw);
 }
 
+// ---- oip quicklook: an 8-bit browse image of a strip or product ---------------------------------------------
+// The products are too large to look at (a stitched PAN strip is ~4.8 GB of 12-bit values in 16-bit samples): one read-only
+// pass box-decimates the image by F x F (oip_decimate_box_u16), and everything behind it works on planes F^2 times smaller --
+// per band a histogram (oip_histogram_u16), percentile limits and an 8-bit table on the host (oip_stretch_limits,
+// oip_stretch_lut_u8), one look-up kernel (oip_apply_lut_u8) and an uncompressed 8-bit TIFF.  Not in the reference.
+struct QuicklookOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    bool bil = false;                       // RAW input: the MSS line layout, 4 bands of width / 4 next to each other
+    int factor = OIP_QUICKLOOK_DEF_FACTOR;
+    double clipLow = OIP_QUICKLOOK_DEF_CLIPLOW, clipHigh = OIP_QUICKLOOK_DEF_CLIPHIGH;
+    int validMin = 1, validMax = 65535;     // 0 is the border value of prestitch and the aligner (BORDER_CONSTANT)
+    std::vector<int> bands;                 // 1-based; empty: 1 for one band, 1,2,3 for four
+    long lineOffset = 0, lines = 0;         // lines == 0: to the end of the image
+    bool force = false;
+};
+
+// everything that can be refused without a device; returns the output path and whether the input is a TIFF
+inline std::string QuicklookCheck(const std::string &file, const std::string &out, const QuicklookOptions &o, bool *isTiff)
+{
+    const std::string ext = to_lower(std::filesystem::path(file).extension().string());
+    if (ext != ".tiff" && ext != ".raw") throw std::invalid_argument("quicklook: only RAW and TIFF image supported");
+    *isTiff = ext == ".tiff";
+    const int F = o.factor;
+    if (F != 2 && F != 4 && F != 8 && F != 16 && F != 32 && F != 64) throw usage_error("--factor: one of 2, 4, 8, 16, 32, 64 expected");
+    if (o.bands.size() > 3 || o.bands.size() == 2) throw usage_error("--bands: one band (grey) or three (RGB) expected");
+    if (!*isTiff) {
+        const int nb = o.bil ? MSS_BANDS : 1;
+        for (int b : o.bands)
+            if (b < 1 || b > nb) throw usage_error("--bands: band index out of range (1.." + std::to_string(nb) + ")");
+        if (o.width <= 0 || (o.bil && o.width % MSS_BANDS != 0)) throw std::invalid_argument("--width: a positive line width (a multiple of 4 with --bil) expected");
+    } else {
+        for (int b : o.bands)
+            if (b < 1 || b > MSS_BANDS) throw usage_error("--bands: band index out of range (1.." + std::to_string(MSS_BANDS) + ")");
+    }
+    const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_QUICKLOOK_SUFFIX, ".TIFF") : out;
+    struct stat st;
+    if (!o.force && stat(path.c_str(), &st) == 0)
+        throw std::runtime_error("output file [" + path + "] exists: quicklook does not replace a file without --force");
+    return path;
+}
+
+inline void RunQuicklook(const std::string &file, const std::string &out, const QuicklookOptions &o)
+{
+    bool isTiff = false;
+    const std::string outPath = QuicklookCheck(file, out, o, &isTiff);
+    const int F = o.factor;
+    long first = 0, nLines = 0;
+    int bw = 0, nb = 0;                     // band width in pixels, bands of the image
+    if (!isTiff) {
+        RrcCalibOptions range;
+        range.width = o.width; range.lineOffset = o.lineOffset; range.lines = o.lines;
+        RrcCalibLineRange(file, "image", range, &first, &nLines);
+        nb = o.bil ? MSS_BANDS : 1;
+        bw = o.width / nb;
+    }
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    size_t inBytes = 0;
+    DevBuf<uint16_t> planes;
+    int ow = 0;
+    long oh = 0;
+    size_t plane = 0;
+    auto alloc_planes = [&]() {
+        ow = (bw + F - 1) / F;
+        oh = (nLines + F - 1) / F;
+        plane = (size_t)ow * oh;
+        planes.alloc(plane * nb);
+    };
+    if (isTiff) {
+        int w = 0, spp = 0;
+        long h = 0;
+        DevBuf<uint16_t> img;
+        OLOG("Reading image from file `%s' ...", file.c_str());
+        read_tiff_to_device(file, &w, &h, &spp, img);
+        if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument("quicklook: a TIFF of 1 or 4 samples per pixel expected");
+        if (o.lineOffset >= h) throw std::invalid_argument("image has " + std::to_string(h) + " lines: --line-offset is beyond them");
+        first = o.lineOffset;
+        nLines = o.lines > 0 ? std::min(o.lines, h - first) : h - first;
+        nb = spp;
+        bw = w;
+        for (int b : o.bands)
+            if (b > nb) throw usage_error("--bands: band index out of range (1.." + std::to_string(nb) + ")");
+        alloc_planes();
+        ck(oip_decimate_box_u16(ctx, img.p + (size_t)first * w * spp, (long)w * spp, w, nLines, spp, F, planes.p, ow, plane));
+        ck(oip_sync(ctx));                  // img is released at the end of this block
+        inBytes = (size_t)nLines * w * spp * BYTES_PER_PIXEL;
+    } else {
+        // The strip is never resident: line blocks (a multiple of F lines) go file -> pinned ring -> one of two device blocks, the
+        // decimation of a block runs behind its upload (ticket) while the host reads the next block, as RrcCalibImage does.
+        const int W = o.width;
+        const size_t lineBytes = (size_t)W * BYTES_PER_PIXEL;
+        const long blockLines = std::max<long>(F, (long)(((size_t)64 << 20) / lineBytes) / F * F);
+        alloc_planes();
+        DevBuf<uint16_t> buf[2];
+        for (int i = 0; i < 2 && (long)i * blockLines < nLines; ++i) buf[i].alloc((size_t)std::min(blockLines, nLines) * W);
+        OLOG("Reading raw image from file `%s' ...", file.c_str());
+        long block = 0;
+        for (long r = 0; r < nLines; r += blockLines, ++block) {
+            const long m = std::min(blockLines, nLines - r);
+            uint16_t *d = buf[block & 1].p;
+            if (block >= 2) ck(oip_stage_order_after_compute(ctx));     // the kernels that read this buffer two blocks ago go first
+            size_t got = 0;
+            long ticket = 0;
+            ck(oip_read_file_to_device(ctx, file.c_str(), (size_t)(first + r) * lineBytes, (size_t)m * lineBytes, d, &got, &ticket));
+            if (got != (size_t)m * lineBytes)
+                throw std::runtime_error("file size(" + std::to_string((size_t)(first + r + m) * lineBytes) + ") doesn't match with read byte count(" +
+                                         std::to_string((size_t)(first + r) * lineBytes + got) + ")");
+            ck(oip_stage_wait(ctx, ticket));
+            for (int b = 0; b < nb; ++b)    // a BIL band is a window of the line
+                ck(oip_decimate_box_u16(ctx, d + (size_t)b * bw, W, bw, m, 1, F, planes.p + (size_t)b * plane + (size_t)(r / F) * ow, ow, 0));
+        }
+        ck(oip_sync(ctx));
+        inBytes = (size_t)nLines * lineBytes;
+    }
+    std::vector<int> bands = o.bands;
+    if (bands.empty()) bands = nb == 1 ? std::vector<int>{1} : std::vector<int>{1, 2, 3};
+    const int nch = (int)bands.size();
+
+    // per band: histogram of the decimated plane -> limits -> table
+    DevBuf<uint64_t> hist(65536);
+    DevBuf<uint8_t> luts((size_t)nch * 65536);
+    std::vector<uint64_t> h(65536);
+    std::vector<uint8_t> lut((size_t)nch * 65536);
+    const uint16_t *chan[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < nch; ++i) {
+        chan[i] = planes.p + (size_t)(bands[i] - 1) * plane;
+        ck(oip_memset(ctx, hist.p, 0, 65536 * sizeof(uint64_t)));
+        ck(oip_histogram_u16(ctx, chan[i], ow, ow, oh, hist.p));
+        hist.download(h.data(), h.size());
+        int lo = 0, hi = 0;
+        uint64_t nValid = 0;
+        if (oip_stretch_limits(h.data(), o.validMin, o.validMax, o.clipLow, o.clipHigh, &lo, &hi, &nValid) != OIP_OK ||
+            oip_stretch_lut_u8(lo, hi, &lut[(size_t)i * 65536]) != OIP_OK)
+            throw std::invalid_argument("quicklook: invalid stretch arguments");
+        OLOG("band %d: %ld lines, %llu valid samples, stretch %d..%d", bands[i], nLines, (unsigned long long)nValid, lo, hi);
+    }
+    luts.upload(lut.data(), lut.size());
+    DevBuf<uint8_t> img8(plane * nch);
+    ck(oip_apply_lut_u8(ctx, chan, ow, ow, oh, nch, luts.p, img8.p));
+    std::vector<uint8_t> host(plane * nch);
+    img8.download(host.data(), host.size());
+    OLOG("Write quick look (%d x %ld, %s) to file '%s' ...", ow, oh, nch == 1 ? "grey" : "RGB", outPath.c_str());
+    write_tiff_u8(outPath, host.data(), ow, oh, nch);
+    const double es = total.tick();
+    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", inBytes, es, inBytes / es / 1024.0 / 1024.0);
+}
+
 }  // namespace OIPGPU

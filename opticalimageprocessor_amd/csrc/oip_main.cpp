@@ -8,11 +8,12 @@
 //   oip task ...                fused flow of DOC/sample-task.sh, see run_task()
 //   oip rrc-calib [--pan P.RAW --rrc-pan OUT] [--mss M.RAW --rrc-msb1..4 OUT]   derives the RRC coefficient files the
 //                               actions above read from a strip's per-column statistics, see run_rrc_calib()
+//   oip quicklook IMAGE [-o OUT.TIFF] [--factor 16 ...]   8-bit browse image of a strip or product, see run_quicklook()
 //   oip -v | --version          prints 1.1
 // plus --width N (pixels per PAN line; the reference hard-codes 12288, oipshared.h:28).
 // `auxsep` is outside this build.  TIFF input and output go through oip_tiff.hpp (uncompressed and LZW, with
-// or without the horizontal predictor).  Two options are not the reference's: --fit and --fp16-accumulate; nor is the
-// rrc-calib sub-command.
+// or without the horizontal predictor).  Two options are not the reference's: --fit and --fp16-accumulate; nor are the
+// rrc-calib and quicklook sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -137,7 +138,11 @@ void usage()
          "             are OUTPUTS here, and the same arguments given to the default action apply them:\n"
          "             [--pan FILE --rrc-pan OUT] [--mss FILE --rrc-msb1 OUT --rrc-msb2 OUT --rrc-msb3 OUT --rrc-msb4 OUT]\n"
          "             [--mode moments|gain] [--valid-min N] [--valid-max N] [--min-count N]\n"
-         "             [--line-offset N] [--lines N] (of each image's own lines) [--force] (replace existing OUT files)");
+         "             [--line-offset N] [--lines N] (of each image's own lines) [--force] (replace existing OUT files)\n"
+         "  quicklook  IMAGE.RAW|IMAGE.TIFF: an 8-bit browse image, box-decimated by --factor and contrast-stretched per band\n"
+         "             between two percentiles of its valid samples; written to <stem>.QL.TIFF in the working directory:\n"
+         "             [-o,--out FILE] [--factor 2|4|8|16|32|64] [--clip-low P] [--clip-high P] [--valid-min N] [--valid-max N]\n"
+         "             [--bands A | A,B,C] [--bil] (RAW: the MSS line layout) [--width N] [--line-offset N] [--lines N] [--force]");
 }
 
 int run_prestitch(const std::vector<std::string> &args, int width)
@@ -408,6 +413,54 @@ int run_rrc_calib(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip quicklook IMAGE: the browse image of a strip (.RAW, with --bil the MSS line layout) or a product (.TIFF of 1 or 4
+// samples).  IMAGE is the one positional argument of the tool.
+int run_quicklook(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--out", "--factor", "--clip-low", "--clip-high", "--valid-min", "--valid-max", "--bands", "--width", "--line-offset", "--lines"};
+    sp.flags = {"--bil", "--force"};
+    sp.alias = {{"-o", "--out"}};
+    std::string image;
+    std::vector<std::string> rest;
+    for (size_t i = 0; i < args.size(); ++i) {
+        const std::string &a = args[i];
+        if (!a.empty() && a[0] != '-' && image.empty()) { image = a; continue; }
+        rest.push_back(a);
+        auto al = sp.alias.find(a);
+        if (sp.valued.count(al != sp.alias.end() ? al->second : a) && i + 1 < args.size()) rest.push_back(args[++i]);
+    }
+    Parsed p = parse(sp, rest);
+    if (image.empty()) throw cli_error(106, "IMAGE is required");
+    struct stat st;
+    if (stat(image.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) throw cli_error(105, "IMAGE: File does not exist: " + image);
+    QuicklookOptions o;
+    o.width = p.integer("--width", width);
+    o.bil = p.flag.count("--bil") != 0;
+    o.factor = p.integer("--factor", OIP_QUICKLOOK_DEF_FACTOR);
+    o.clipLow = p.real("--clip-low", OIP_QUICKLOOK_DEF_CLIPLOW);
+    o.clipHigh = p.real("--clip-high", OIP_QUICKLOOK_DEF_CLIPHIGH);
+    if (!(o.clipLow >= 0.0 && o.clipLow <= o.clipHigh && o.clipHigh <= 100.0)) throw cli_error(105, "--clip-low/--clip-high: 0 <= low <= high <= 100 expected");
+    o.validMin = p.integer("--valid-min", 1);
+    o.validMax = p.integer("--valid-max", 65535);
+    if (o.validMin < 0 || o.validMax > 65535 || o.validMin > o.validMax) throw cli_error(105, "--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
+    o.lineOffset = p.integer("--line-offset", 0);
+    o.lines = p.integer("--lines", 0);
+    if (o.lineOffset < 0 || o.lines < 0) throw cli_error(105, "--line-offset, --lines: non-negative values expected");
+    o.force = p.flag.count("--force") != 0;
+    if (p.has("--bands")) {
+        const std::string b = p.str("--bands");
+        int v[4] = {0, 0, 0, 0};
+        char junk = 0;
+        const int n = sscanf(b.c_str(), "%d,%d,%d%c", v, v + 1, v + 2, &junk);
+        const bool one = n == 1 && b.find(',') == std::string::npos;
+        if (!one && n != 3) throw usage_error("--bands: one band index (grey) or three (RGB) expected");
+        o.bands.assign(v, v + (one ? 1 : 3));
+    }
+    RunQuicklook(image, p.str("--out"), o);
+    return 0;
+}
+
 }  // namespace
 
 static int oip_main(int argc, const char *argv[]);
@@ -455,6 +508,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "task") return run_task({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "plan") return run_plan({args.begin() + 1, args.end()});
             if (!args.empty() && args[0] == "rrc-calib") return run_rrc_calib({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "quicklook") return run_quicklook({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "auxsep")
                 throw std::invalid_argument("auxsep (down-link de-framing) is outside this build: run the reference's auxsep, then this tool");
             if (args.empty()) { usage(); return 0; }

@@ -733,4 +733,51 @@ inline void write_tiff_u16(const std::string &path, const uint16_t *data, int wi
     w.close();
 }
 
+// The 8-bit sibling for the browse image of `oip quicklook`: classic little-endian TIFF, uncompressed strips of about 8 MiB,
+// chunky, spp 1 (BlackIsZero) or 3 (RGB).  Tens of MB at most: no BigTIFF, no LZW, one buffered write.
+inline void write_tiff_u8(const std::string &path, const uint8_t *data, int width, long height, int spp)
+{
+    if (width <= 0 || height <= 0 || (spp != 1 && spp != 3) || !data) throw std::invalid_argument("write_tiff_u8: bad geometry");
+    const uint64_t rowBytes = (uint64_t)width * spp, total = rowBytes * (uint64_t)height;
+    long rps = (long)(((uint64_t)8 << 20) / rowBytes);
+    rps = rps < 1 ? 1 : (rps > height ? height : rps);
+    const uint64_t nstrips = ((uint64_t)height + rps - 1) / rps;
+    if (total + nstrips * 8 + 4096 > 0xFFFFF000ull) throw std::invalid_argument("write_tiff_u8: image too large for a classic TIFF");
+    std::vector<unsigned char> tail;                                     // everything behind the pixels
+    auto putv = [&](uint64_t v, int n) { for (int i = 0; i < n; ++i) tail.push_back((unsigned char)(v >> (8 * i))); };
+    uint64_t pos = 8 + total;
+    if (pos & 1) { putv(0, 1); ++pos; }
+    uint64_t offStripOff = 0, offStripLen = 0, offBits = 0;
+    if (nstrips > 1) {
+        offStripOff = pos; for (uint64_t k = 0; k < nstrips; ++k) putv(8 + k * rps * rowBytes, 4);
+        offStripLen = offStripOff + nstrips * 4;
+        for (uint64_t k = 0; k < nstrips; ++k) putv(std::min<uint64_t>((uint64_t)rps, (uint64_t)height - k * rps) * rowBytes, 4);
+        pos += nstrips * 8;
+    }
+    if (spp == 3) { offBits = pos; for (int i = 0; i < 3; ++i) putv(8, 2); pos += 6; }
+    const uint64_t ifd = pos;
+    const uint16_t SHORT = 3, LONG = 4;
+    struct Tag { uint16_t id, type; uint32_t count, value; };
+    const Tag tags[] = {{256, LONG, 1, (uint32_t)width},
+                        {257, LONG, 1, (uint32_t)height},
+                        {258, SHORT, (uint32_t)spp, spp == 3 ? (uint32_t)offBits : 8u},
+                        {259, SHORT, 1, 1},
+                        {262, SHORT, 1, spp == 3 ? 2u : 1u},                 // RGB / BlackIsZero
+                        {273, LONG, (uint32_t)nstrips, nstrips > 1 ? (uint32_t)offStripOff : 8u},
+                        {277, SHORT, 1, (uint32_t)spp},
+                        {278, LONG, 1, (uint32_t)rps},
+                        {279, LONG, (uint32_t)nstrips, nstrips > 1 ? (uint32_t)offStripLen : (uint32_t)total},
+                        {284, SHORT, 1, 1}};                                 // chunky
+    putv(sizeof tags / sizeof tags[0], 2);
+    for (const Tag &t : tags) { putv(t.id, 2); putv(t.type, 2); putv(t.count, 4); putv(t.value, 4); }
+    putv(0, 4);
+    unsigned char head[8] = {'I', 'I', 42, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 4; ++i) head[4 + i] = (unsigned char)(ifd >> (8 * i));
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) throw std::runtime_error("open file [" + path + "] failed");
+    const bool ok = fwrite(head, 1, 8, f) == 8 && fwrite(data, 1, (size_t)total, f) == (size_t)total &&
+                    fwrite(tail.data(), 1, tail.size(), f) == tail.size();
+    if (fclose(f) != 0 || !ok) throw std::runtime_error("write file [" + path + "] failed");
+}
+
 }  // namespace OIPGPU
