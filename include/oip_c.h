@@ -411,6 +411,63 @@ int oip_stitch_rows_u16(oip_ctx *ctx, const uint16_t *d_left, const uint16_t *d_
  * device, its lines go from HBM into the TIFF's pixel payload without a host pass.  d_img 16-byte aligned. */
 int oip_permute_u16x4(oip_ctx *ctx, uint16_t *d_img, size_t npixels, const int *order);
 
+/* ---- seam balancing and feathering of the stitch (`oip stitch --balance / --feather`; not in the reference) --------
+ * IMO::StitchBigRaw cuts hard at the seam, and the two CCDs are calibrated apart (oip_rrc_fit_columns matches a strip to
+ * itself), so a level difference between them is a step through every product.  After prestitch the last 2*fold columns
+ * of image 1 and the first 2*fold columns of image 2 see the same ground: that overlap gives image 2's gain and offset
+ * relative to image 1, and room to blend the two.
+ * Lines are in SAMPLE units, as for the 4-sample TIFF stitch: spp samples per pixel (1 or 4, pixel-interleaved),
+ * Ws = W * spp samples per input line, fs = fold * spp (fold: the halved --fold-cols); the channel of sample j is j % spp.
+ * An overlap pair of line r is  a = left[r * Ws + Ws - 2 fs + j],  b = right[r * Ws + j],  j in [0, 2 fs). */
+
+/* Per channel c the totals over the pairs of L lines whose TWO samples lie in [valid_min, valid_max], ADDED into d_acc:
+ * (6, spp) uint64 in HBM, planes  n | Sa = sum a | Sb = sum b | Saa = sum a*a | Sbb = sum b*b | Sab = sum a*b,  entry
+ * [k * spp + c].  The caller zeroes d_acc (oip_memset) before the first call; calls over consecutive line blocks add up to
+ * the strip's totals.  Sums are exact integers: they do not depend on the launch geometry or the order of the calls, as
+ * long as one channel sees at most 2^32 pairs in all (2 * fold * L <= 2^32: then Sab <= 2^32 * 65535^2 < 2^64; a single
+ * call beyond that is OIP_E_INVALID).  2 fs <= Ws, L < 2^31.  The windows may start on any 2-byte boundary.  Asynchronous. */
+int oip_seam_moments_u16(oip_ctx *ctx, const uint16_t *d_left, const uint16_t *d_right, int Ws, long L, int fs, int spp,
+                         int valid_min, int valid_max, uint64_t *d_acc);
+
+/* Gain and offset of image 2 relative to image 1 from those totals, host.  acc: the 6 * spp totals (host copy).  Per
+ * channel, in this order, every step one correctly rounded fp64 operation (integers below 2^53 convert exactly, the
+ * 128-bit ones to the nearest double):
+ *   Da = n * Saa - Sa * Sa,  Db = n * Sbb - Sb * Sb,  Dab = n * Sab - Sa * Sb              exact 128-bit integers
+ *   mean_a = (double)Sa / (double)n,  mean_b = (double)Sb / (double)n
+ *   ra = sqrt((double)Da),  rb = sqrt((double)Db),  sigma_a = ra / (double)n,  sigma_b = rb / (double)n
+ *   r = (double)Dab / (ra * rb)                                   (0 when Da or Db is 0; everything is 0 when n is 0)
+ *   OIP_SEAM_MOMENTS: g = sqrt((double)Da / (double)Db);  OIP_SEAM_GAIN: g = (double)Sa / (double)Sb;  OIP_SEAM_OFFSET: g = 1
+ *   G = rint(g * 65536)
+ *   O = rint((mean_a - (G / 65536) * mean_b) * 65536)             from the QUANTISED gain, so that the means still meet
+ *                                                                 after quantisation; OIP_SEAM_GAIN: O = 0
+ * A channel gets the identity (G = 65536, O = 0) and identity[c] = 1 -- not an error, like a dead column of the RRC fit --
+ * when n < max(min_count, 2), when Da or Db is 0 in moments mode, or when Sb is 0 in gain mode.
+ * gain_q16 / offset_q16 / identity: spp entries each.  report (may be NULL): spp x (n, mean_a, mean_b, sigma_a, sigma_b, r);
+ * r is the number that tells whether fold matches the real overlap.
+ * OIP_E_INVALID, with the channel and the value in err, for a G outside [16384, 262144] (a quarter to four: the images
+ * do not show the same ground, usually a wrong --fold-cols) or an O that does not fit 32 bits.  No context needed. */
+#define OIP_SEAM_MOMENTS 0
+#define OIP_SEAM_GAIN    1
+#define OIP_SEAM_OFFSET  2
+int oip_seam_fit(const uint64_t *acc, int spp, int mode, uint64_t min_count, int32_t *gain_q16, int32_t *offset_q16,
+                 double *report, int *identity, char *err, int errlen);
+
+/* oip_stitch_rows_u16 with image 2 balanced, a blend zone around the seam and "no data" inside it: the one pass over the
+ * full-size product.  d_out: L lines of 2 (Ws - fs) samples.  d_gain_q16 / d_offset_q16: spp int32 each in HBM (G_c, O_c).
+ * In integers, for output pixel column p of line r, channel c, with s = W - fold (the seam) and h = feather (half-width of
+ * the blend zone in pixels, 0 <= h <= fold; above 16384: OIP_E_UNSUPPORTED):
+ *   a  = left[r][p],  b = right[r][p - (W - 2 fold)]
+ *   b' = clamp((G_c * b + O_c + 32768) >> 16, 0, 65535)           64-bit, arithmetic shift
+ *   p <  s - h: a          p >= s + h: b'
+ *   otherwise, with t = p - (s - h), wr = 2 t + 1, wl = 4 h - wr:   (wl * a + wr * b' + 2 h) / (4 h), floored;
+ *              b' instead if a < valid_min, else a instead if b < valid_min
+ * With G = 65536, O = 0, h = 0 the output is oip_stitch_rows_u16's, byte for byte.  An output line that is not a multiple
+ * of 8 samples, or bases that are not 16-byte (out) / 4-byte (in) aligned, take a slower kernel with the same result.
+ * Asynchronous on the context's stream. */
+int oip_stitch_balanced_u16(oip_ctx *ctx, const uint16_t *d_left, const uint16_t *d_right, uint16_t *d_out, int Ws, long L,
+                            int fs, int spp, const int32_t *d_gain_q16, const int32_t *d_offset_q16, int feather,
+                            int valid_min);
+
 /* The strips of an LZW TIFF product, encoded on the device (cv::imwrite's TIFF encoder behind preproc.h:167-185 and GDAL's
  * COMPRESS=LZW PREDICTOR=2 behind imageop.h:460-567 do this on the host, strip by strip).  d_img: rows x width x spp u16,
  * interleaved, in file sample order (oip_permute_u16x4 first where cv::imwrite / a band map reorder); spp 1 or 4; strip k

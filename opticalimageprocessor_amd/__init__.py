@@ -22,6 +22,7 @@ from .capi import (  # noqa: F401
     polyfit,
     remap_shift_src_range,
     rrc_fit_columns,
+    seam_fit,
     stretch_limits,
     stretch_lut_u8,
     stt_mean,

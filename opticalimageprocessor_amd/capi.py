@@ -116,6 +116,9 @@ _SIGS = {
     "oip_align_mss_bicubic_u16x4": ([_vp, _vp, _sz, _l, _l, _vp, _l, _l, _i, _l, _dp, _dp, _i, _i, _i, _i, _i, _lp], _i),
     "oip_align_mss_src_range": ([_l, _l, _l, _dp, _i, _i, _i, _i, _i, _i, _lp, _lp], _i),
     "oip_stitch_rows_u16": ([_vp, _vp, _vp, _vp, _i, _l, _i], _i),
+    "oip_seam_moments_u16": ([_vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _vp], _i),
+    "oip_seam_fit": ([C.POINTER(C.c_uint64), _i, _i, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.POINTER(_i), _cp, _i], _i),
+    "oip_stitch_balanced_u16": ([_vp, _vp, _vp, _vp, _i, _l, _i, _i, _vp, _vp, _i, _i], _i),
     "oip_merge_subimages_be16": ([_vp, _vp, _vp, _i, _i, _i, _i], _i),
     "oip_profile_enable": ([_vp, _i], _i),
     "oip_profile_reset": ([_vp], _i),
@@ -203,6 +206,30 @@ def write_rrc_param_file(path: str, kb) -> None:
     rc = lib.oip_write_rrc_param_file(os.fsencode(path), kb.ctypes.data_as(_dp), kb.shape[0], err, 2048)
     if rc:
         raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+
+
+SEAM_MODES = {"moments": 0, "gain": 1, "offset": 2}
+
+
+def seam_fit(acc, mode="moments", min_count: int = 0):
+    """gain and offset (Q16) of image 2 relative to image 1 from the (6, spp) uint64 totals of Context.seam_moments_u16
+    (include/oip_c.h: oip_seam_fit).  Returns (gain_q16 (spp,) int32, offset_q16 (spp,) int32, identity (spp,) int32,
+    report (spp, 6): n, mean_a, mean_b, sigma_a, sigma_b, r)."""
+    lib = load_library()
+    m = SEAM_MODES.get(mode, mode)
+    if not isinstance(m, int):
+        raise ValueError("seam_fit: moments, gain or offset expected")
+    a = np.ascontiguousarray(acc, dtype=np.uint64)
+    assert a.ndim == 2 and a.shape[0] == 6, a.shape
+    spp = a.shape[1]
+    gain, offset, ident, report = np.zeros(spp, np.int32), np.zeros(spp, np.int32), np.zeros(spp, np.int32), np.zeros((spp, 6))
+    err = C.create_string_buffer(1024)
+    rc = lib.oip_seam_fit(a.ctypes.data_as(C.POINTER(C.c_uint64)), spp, m, min_count,
+                          gain.ctypes.data_as(C.POINTER(C.c_int32)), offset.ctypes.data_as(C.POINTER(C.c_int32)), report.ctypes.data_as(_dp),
+                          ident.ctypes.data_as(C.POINTER(_i)), err, 1024)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    return gain, offset, ident, report
 
 
 def stretch_limits(hist, valid_min=1, valid_max=65535, p_lo=2.0, p_hi=98.0):
@@ -590,6 +617,18 @@ class Context:
 
     def stitch_rows_u16(self, left, right, out, W, L, fold):
         self._ck(self.lib.oip_stitch_rows_u16(self.h, _ptr(left), _ptr(right), _ptr(out), W, L, fold))
+
+    # -- seam balancing and feathering
+    def seam_moments_u16(self, left, right, Ws, L, fs, spp, acc, valid_min=0, valid_max=65535):
+        """overlap totals n, Sa, Sb, Saa, Sbb, Sab per channel ADDED into acc: (6, spp) uint64 on the device, zeroed by the
+        caller before the first call (include/oip_c.h: oip_seam_moments_u16; Ws, fs in samples)"""
+        self._ck(self.lib.oip_seam_moments_u16(self.h, _ptr(left), _ptr(right), Ws, L, fs, spp, valid_min, valid_max, _ptr(acc)))
+
+    def stitch_balanced_u16(self, left, right, out, Ws, L, fs, spp, gain_q16, offset_q16, feather=0, valid_min=1):
+        """the stitch with image 2 balanced by gain_q16 / offset_q16 (spp int32 each, on the device) and blended over
+        `feather` pixels either side of the seam (include/oip_c.h: oip_stitch_balanced_u16)"""
+        self._ck(self.lib.oip_stitch_balanced_u16(self.h, _ptr(left), _ptr(right), _ptr(out), Ws, L, fs, spp, _ptr(gain_q16), _ptr(offset_q16),
+                                                  feather, valid_min))
 
     # -- instrumentation
     def merge_subimages_be16(self, tiles, out, vparts, hparts, sub_lines, sub_cols):

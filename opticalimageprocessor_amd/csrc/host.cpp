@@ -1,6 +1,6 @@
 // host.cpp -- host-side pieces of the path that carry no raster arithmetic:
-// the RRC parameter file loader, its counterpart (column fit + writer), the shift filtering / polynomial fit and the
-// contrast stretch of `oip quicklook` (percentile limits, 8-bit table, 8-bit TIFF).
+// the RRC parameter file loader, its counterpart (column fit + writer), the seam fit of `oip stitch --balance`, the shift
+// filtering / polynomial fit and the contrast stretch of `oip quicklook` (percentile limits, 8-bit table, 8-bit TIFF).
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -111,6 +111,75 @@ extern "C" int oip_rrc_fit_columns(const uint64_t *acc, int w, int groups, int m
         }
         if (dead_out) dead_out[g] = gw - count;
         if (ref_out) { ref_out[2 * g] = muRef; ref_out[2 * g + 1] = sigmaRef; }
+    }
+    return OIP_OK;
+}
+
+// Gain and offset of image 2 relative to image 1 from the overlap totals of oip_seam_moments_u16 (include/oip_c.h states
+// the operation order; tests/_seam_ref.py restates it).  n <= 2^32 and Sa, Sb < 2^48 convert exactly; Saa, Sbb, Sab < 2^64
+// enter only through the exact 128-bit D's, which convert to the nearest double.
+extern "C" int oip_seam_fit(const uint64_t *acc, int spp, int mode, uint64_t min_count, int32_t *gain_q16, int32_t *offset_q16, double *report,
+                            int *identity, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *fmt, auto... a) {
+        if (err && errlen > 0) snprintf(err, errlen, fmt, a...);
+        return code;
+    };
+    if (!acc || !gain_q16 || !offset_q16 || !identity || spp <= 0 || (mode != OIP_SEAM_MOMENTS && mode != OIP_SEAM_GAIN && mode != OIP_SEAM_OFFSET))
+        return fail(OIP_E_INVALID, "%s", "oip_seam_fit: bad argument");
+    const uint64_t need = min_count > 2u ? min_count : 2u;
+    for (int c = 0; c < spp; ++c) {
+        const uint64_t n = acc[c], Sa = acc[spp + c], Sb = acc[2 * spp + c], Saa = acc[3 * spp + c], Sbb = acc[4 * spp + c], Sab = acc[5 * spp + c];
+        // (a D below zero cannot come from real totals; it is treated as 0)
+        const unsigned __int128 na = (unsigned __int128)n * Saa, sa2 = (unsigned __int128)Sa * Sa;
+        const unsigned __int128 nb = (unsigned __int128)n * Sbb, sb2 = (unsigned __int128)Sb * Sb;
+        const unsigned __int128 Da = na > sa2 ? na - sa2 : 0, Db = nb > sb2 ? nb - sb2 : 0;
+        const __int128 Dab = (__int128)((unsigned __int128)n * Sab) - (__int128)((unsigned __int128)Sa * Sb);
+        double meanA = 0.0, meanB = 0.0, sigmaA = 0.0, sigmaB = 0.0, r = 0.0;
+        if (n > 0) {
+            const double nd = (double)n;
+            meanA = (double)Sa / nd;
+            meanB = (double)Sb / nd;
+            const double ra = std::sqrt((double)Da), rb = std::sqrt((double)Db);
+            sigmaA = ra / nd;
+            sigmaB = rb / nd;
+            if (Da != 0 && Db != 0) {
+                const double den = ra * rb;
+                r = (double)Dab / den;
+            }
+        }
+        if (report) {
+            double *o = report + 6 * (size_t)c;
+            o[0] = (double)n; o[1] = meanA; o[2] = meanB; o[3] = sigmaA; o[4] = sigmaB; o[5] = r;
+        }
+        gain_q16[c] = 65536;
+        offset_q16[c] = 0;
+        identity[c] = 1;
+        if (n < need) continue;
+        double g = 1.0;
+        if (mode == OIP_SEAM_MOMENTS) {
+            if (Da == 0 || Db == 0) continue;
+            const double q = (double)Da / (double)Db;
+            g = std::sqrt(q);
+        } else if (mode == OIP_SEAM_GAIN) {
+            if (Sb == 0) continue;
+            g = (double)Sa / (double)Sb;
+        }
+        const double G = std::rint(g * 65536.0);
+        if (!(G >= 16384.0 && G <= 262144.0))
+            return fail(OIP_E_INVALID, "oip_seam_fit: channel %d: gain_q16 %.0f outside [16384, 262144] -- the overlaps do not show the same ground (--fold-cols?)", c, G);
+        double O = 0.0;
+        if (mode != OIP_SEAM_GAIN) {
+            const double gq = G / 65536.0;
+            const double t = gq * meanB;
+            const double d = meanA - t;
+            O = std::rint(d * 65536.0);
+            if (!(O >= -2147483648.0 && O <= 2147483647.0))
+                return fail(OIP_E_INVALID, "oip_seam_fit: channel %d: offset_q16 %.0f does not fit 32 bits", c, O);
+        }
+        gain_q16[c] = (int32_t)G;
+        offset_q16[c] = (int32_t)O;
+        identity[c] = 0;
     }
     return OIP_OK;
 }

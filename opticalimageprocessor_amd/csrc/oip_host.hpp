@@ -443,6 +443,49 @@ inline void read_tiff_to_device(const std::string &path, int *width, long *heigh
 // ---- ImageOperations (imageop.h:33-568, hot-path subset) -----------------------------------------
 struct RRCParam { double k; double b; };     // imageop.h:26-29
 
+// ---- oip stitch --balance / --feather: seam balancing and feathering (not in the reference) ------------------
+// The two CCDs are calibrated apart, so the hard cut of StitchBigRaw shows any level difference as a step.  The overlap that
+// the cut discards gives image 2's gain and offset relative to image 1 (oip_seam_moments_u16 + oip_seam_fit) and room to
+// blend (oip_stitch_balanced_u16).  Inactive by default: the stitch is then oip_stitch_rows_u16's, as before.
+struct SeamOptions {
+    int balance = -1;                       // -1: none, else OIP_SEAM_MOMENTS / OIP_SEAM_GAIN / OIP_SEAM_OFFSET
+    int feather = 0;                        // half-width of the blend zone in pixels (the halved --feather)
+    int validMin = 1, validMax = 65535;     // 0 is the border value of prestitch and the aligner (BORDER_CONSTANT)
+    long minCount = 0;
+    bool active() const { return balance >= 0 || feather > 0; }
+};
+
+// the stitch of two resident images through the seam path; Ws, fs in samples (include/oip_c.h)
+inline void StitchSeam(const uint16_t *dl, const uint16_t *dr, uint16_t *dout, int Ws, long L, int fs, int spp, const SeamOptions &o)
+{
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    std::vector<int32_t> G(spp, 65536), O(spp, 0);
+    if (o.balance >= 0) {
+        DevBuf<uint64_t> acc((size_t)6 * spp);
+        ck(oip_memset(ctx, acc.p, 0, (size_t)6 * spp * sizeof(uint64_t)));
+        ck(oip_seam_moments_u16(ctx, dl, dr, Ws, L, fs, spp, o.validMin, o.validMax, acc.p));
+        std::vector<uint64_t> totals((size_t)6 * spp);
+        acc.download(totals.data(), totals.size());
+        std::vector<double> rep((size_t)6 * spp);
+        std::vector<int> ident(spp);
+        char err[1024] = "";
+        const int rc = oip_seam_fit(totals.data(), spp, o.balance, (uint64_t)o.minCount, G.data(), O.data(), rep.data(), ident.data(), err, sizeof err);
+        if (rc == OIP_E_INVALID) throw std::invalid_argument(err);
+        if (rc != OIP_OK) throw std::runtime_error(err);
+        for (int c = 0; c < spp; ++c)
+            OLOG("seam channel %d: n %llu, mean %.3f / %.3f, sigma %.3f / %.3f, r %.6f, gain_q16 %d, offset_q16 %d%s", c + 1,
+                 (unsigned long long)totals[c], rep[6 * c + 1], rep[6 * c + 2], rep[6 * c + 3], rep[6 * c + 4], rep[6 * c + 5], G[c], O[c],
+                 ident[c] ? " (identity substituted)" : "");
+    }
+    DevBuf<int32_t> go((size_t)2 * spp);
+    std::vector<int32_t> h(G);
+    h.insert(h.end(), O.begin(), O.end());
+    go.upload(h.data(), h.size());
+    ck(oip_stitch_balanced_u16(ctx, dl, dr, dout, Ws, L, fs, spp, go.p, go.p + spp, o.feather, o.validMin));
+    ck(oip_sync(ctx));                      // `go` leaves scope
+}
+
 class ImageOperations {
 public:
     static size_t FileSize(const std::string &filePath)            // imageop.h:43-47
@@ -574,7 +617,8 @@ public:
 
     // imageop.h:277-363, RAW output only (the GTiff writer is "next")
     static std::string StitchBigRaw(const std::string &leftImagePath, const std::string &rightImagePath,
-                                    const std::string &stitchedFilePath, int pixelPerLine, int foldColPixels)
+                                    const std::string &stitchedFilePath, int pixelPerLine, int foldColPixels,
+                                    const SeamOptions *seam = nullptr)
     {
         size_t szl = FileSize(leftImagePath), szr = FileSize(rightImagePath);
         if (szl != szr)
@@ -597,7 +641,8 @@ public:
         dr.load_file(rightImagePath, npx);
         OLOG("Begin stitching two images ...");
         stop_watch sw;
-        Device::get().check(oip_stitch_rows_u16(Device::get().ctx(), dl.p, dr.p, dout.p, pixelPerLine, imageLines, foldColPixels));
+        if (seam && seam->active()) StitchSeam(dl.p, dr.p, dout.p, pixelPerLine, imageLines, foldColPixels, 1, *seam);
+        else Device::get().check(oip_stitch_rows_u16(Device::get().ctx(), dl.p, dr.p, dout.p, pixelPerLine, imageLines, foldColPixels));
         if (outputIsTiff) {                                            // 1-band GTiff (imageop.h:316-328), straight from the device
             write_tiff_from_device(outputFilePath, dout.p, outputFullLinePixels, imageLines, 1, tiff_compression(TIFF_NONE), false);
         } else {
@@ -614,7 +659,7 @@ public:
     // GDAL writes band b from channel bandMap[b]-1 (imageop.h:529).
     static std::string StitchTiff(const std::string &leftImagePath, const std::string &rightImagePath,
                                   const std::string &stitchedFilePath, int foldColPixels, bool useGDAL = false,
-                                  const int *bandMap = nullptr)
+                                  const int *bandMap = nullptr, const SeamOptions *seam = nullptr)
     {
         std::string outputFilePath = stitchedFilePath;
         if (stitchedFilePath.empty()) outputFilePath = (std::filesystem::current_path() / "stitched.TIFF").string();
@@ -635,7 +680,9 @@ public:
         const size_t nin = (size_t)W4 * hl, nout = (size_t)2 * (W4 - fold4) * hl;
         (void)nin;
         DevBuf<uint16_t> dout(nout);
-        Device::get().check(oip_stitch_rows_u16(Device::get().ctx(), dl.p, dr.p, dout.p, W4, hl, fold4));
+        // (balancing acts on the samples in file order, before any --GDAL / --band-map permutation below)
+        if (seam && seam->active()) StitchSeam(dl.p, dr.p, dout.p, W4, hl, fold4, MSS_BANDS, *seam);
+        else Device::get().check(oip_stitch_rows_u16(Device::get().ctx(), dl.p, dr.p, dout.p, W4, hl, fold4));
         const int ow = 2 * (wl - foldColPixels);
         OLOG("Write stitched image to file '%s' ...", outputFilePath.c_str());
         // file order is RGBA = (c2, c1, c0, c3) of the reference's Mat.  The stitched image stays on the device: its samples are
@@ -660,14 +707,14 @@ public:
     // stitcher.h:21-46; foldCols is the already-halved value (main.cpp:189)
     static std::string Stitch(const std::string &leftImagePath, const std::string &rightImagePath,
                               const std::string &outputPath = "", int foldCols = 0, int pixelsPerLine = OIP_PIXELS_PER_LINE,
-                              bool useGDAL = false, const int *bandMap = nullptr)
+                              bool useGDAL = false, const int *bandMap = nullptr, const SeamOptions *seam = nullptr)
     {
         std::string leftExt = to_lower(std::filesystem::path(leftImagePath).extension().string());
         std::string rightExt = to_lower(std::filesystem::path(rightImagePath).extension().string());
         if (leftExt != rightExt) throw std::invalid_argument("Stitch(): two images should be same type");
         if (leftExt != ".tiff" && leftExt != ".raw") throw std::invalid_argument("Stitch(): only RAW and TIFF image supported");
-        if (leftExt == ".raw") return IMO::StitchBigRaw(leftImagePath, rightImagePath, outputPath, pixelsPerLine, foldCols);
-        return IMO::StitchTiff(leftImagePath, rightImagePath, outputPath, foldCols, useGDAL, bandMap);
+        if (leftExt == ".raw") return IMO::StitchBigRaw(leftImagePath, rightImagePath, outputPath, pixelsPerLine, foldCols, seam);
+        return IMO::StitchTiff(leftImagePath, rightImagePath, outputPath, foldCols, useGDAL, bandMap, seam);
     }
 
     Stitcher(const std::string &pan1, const std::string &pan2, const std::string &rrc1, const std::string &rrc2,

@@ -3,6 +3,7 @@
 //   oip prestitch --pan1 A.RAW --pan2 B.RAW [--rrc1 --rrc2 -s -l --stitch-overlap --stt-threshold
 //                 --stt-maxdeltay -e -r/--rrc/--no-rrc -c]                     (main.cpp:112-150)
 //   oip stitch --image1 L.RAW --image2 R.RAW -c/--fold-cols N [-o OUT.RAW]       (main.cpp:159-190)
+//              [--balance none|offset|gain|moments --feather N --valid-min N --valid-max N --min-count N]   see run_stitch()
 //   oip --pan P.RAW --mss M.RAW [--do-rrc4pan --rrc-pan F --no-rrc4mss --rrc-msb1..4 F --slices
 //       --ibc-sections --ibc-threshold --line-offset --lines-section --overlap-lines -k]   (:193-252)
 //   oip task ...                fused flow of DOC/sample-task.sh, see run_task()
@@ -12,8 +13,8 @@
 //   oip -v | --version          prints 1.1
 // plus --width N (pixels per PAN line; the reference hard-codes 12288, oipshared.h:28).
 // `auxsep` is outside this build.  TIFF input and output go through oip_tiff.hpp (uncompressed and LZW, with
-// or without the horizontal predictor).  Two options are not the reference's: --fit and --fp16-accumulate; nor are the
-// rrc-calib and quicklook sub-commands.
+// or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
+// (--balance, --feather and their --valid-min / --valid-max / --min-count) and the rrc-calib and quicklook sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -128,6 +129,9 @@ void usage()
          "  prestitch  --pan1 FILE --pan2 FILE [--rrc1 FILE --rrc2 FILE -s N -l N --stitch-overlap N\n"
          "             --stt-threshold X --stt-maxdeltay X -e N -r,--rrc/--no-rrc -c,--only-calculate --fp16-accumulate]\n"
          "  stitch     --image1 FILE --image2 FILE -c,--fold-cols N [-o,--out FILE] [-g,--GDAL -m,--band-map a,b,c,d]\n"
+         "             [--balance none|offset|gain|moments] image 2's gain / offset relative to image 1, fitted on the overlap\n"
+         "             [--feather N] blend the images over N columns around the seam (even, 0 <= N <= fold-cols)\n"
+         "             [--valid-min N] [--valid-max N] (samples outside are no data; default 1, 65535) [--min-count N]\n"
          "  --gpus N   (default action and prestitch) scan-line blocks over the N GPUs of the node, RCCL exchanges\n"
          "  plan       strip|ccd --width W --lines L --gpus N ...: print the multi-GPU row plan as JSON\n"
          "  task       prestitch + stitch + default action x2 + stitch in one process (intermediates stay on the GPU;\n"
@@ -189,7 +193,8 @@ int run_prestitch(const std::vector<std::string> &args, int width)
 int run_stitch(const std::vector<std::string> &args, int width)
 {
     Spec sp;
-    sp.valued = {"--image1", "--image2", "--out", "--fold-cols", "--band-map", "--width"};
+    sp.valued = {"--image1", "--image2", "--out", "--fold-cols", "--band-map", "--width", "--balance", "--feather", "--valid-min", "--valid-max",
+                 "--min-count"};
     sp.flags = {"--GDAL"};
     sp.alias = {{"-o", "--out"}, {"-c", "--fold-cols"}, {"-g", "--GDAL"}, {"-m", "--band-map"}};
     Parsed p = parse(sp, args);
@@ -207,8 +212,23 @@ int run_stitch(const std::vector<std::string> &args, int width)
         for (int i = 0; i < MSS_BANDS; ++i)
             if (map[i] <= 0 || map[i] > MSS_BANDS) throw cli_error(105, "-m: invalid band index");
     }
+    // seam balancing and feathering (not in the reference).  Without these options the stitch is the reference's hard cut.
+    SeamOptions seam;
+    const std::string balance = p.str("--balance", "none");
+    if (balance == "moments") seam.balance = OIP_SEAM_MOMENTS;
+    else if (balance == "gain") seam.balance = OIP_SEAM_GAIN;
+    else if (balance == "offset") seam.balance = OIP_SEAM_OFFSET;
+    else if (balance != "none") throw cli_error(105, "--balance: none, offset, gain or moments expected");
+    const int feather = p.integer("--feather", 0);
+    if (feather < 0 || feather % 2 != 0 || feather > foldCols) throw cli_error(105, "--feather: an even value, 0 <= N <= fold-cols, expected");
+    seam.feather = feather / 2;                                                                                  // halved like --fold-cols
+    seam.validMin = p.integer("--valid-min", 1);
+    seam.validMax = p.integer("--valid-max", 65535);
+    if (seam.validMin < 0 || seam.validMax > 65535 || seam.validMin > seam.validMax) throw cli_error(105, "--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
+    seam.minCount = p.integer("--min-count", 0);
+    if (seam.minCount < 0) throw cli_error(105, "--min-count: a non-negative value expected");
     Stitcher::Stitch(p.str("--image1"), p.str("--image2"), p.str("--out"), foldCols / 2, width, p.has("--GDAL"),
-                     bandMap.empty() ? nullptr : map);                                                           // main.cpp:189
+                     bandMap.empty() ? nullptr : map, &seam);                                                    // main.cpp:189
     return 0;
 }
 
