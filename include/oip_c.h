@@ -468,6 +468,52 @@ int oip_stitch_balanced_u16(oip_ctx *ctx, const uint16_t *d_left, const uint16_t
                             int fs, int spp, const int32_t *d_gain_q16, const int32_t *d_offset_q16, int feather,
                             int valid_min);
 
+/* ---- MTF compensation: a fixed-point restoration filter (`oip mtfc`; not in the reference) -------------------------
+ * CCD 2 goes through a bicubic resampling in prestitch and every MSS band through one in the aligner; CCD 1 goes through
+ * none, so the halves of a stitched product differ in sharpness.  MTFC is the small convolution that level-1 chains apply
+ * behind the radiometric correction.  Specified in exact integers: any evaluation order gives the same bytes. */
+#define OIP_MTFC_SUFFIX        ".MTFC"  /* <stem>.MTFC.<ext>, built like the reference's other product names (imageop.h:99-108) */
+#define OIP_MTFC_DEF_MAXGAIN   2.0
+#define OIP_CONVOLVE_MAX_K     9
+
+/* The raster is W pixels x L lines of spp samples (1, or 4 pixel-interleaved); lines are W * spp samples apart and the
+ * channel of sample j is j % spp.  d_src holds global lines [src_row0, src_row0 + src_rows) and d_dst receives output lines
+ * [out_row0, out_row0 + out_rows), the first at d_dst (oip_remap_shift_bicubic_u16's convention: a strip cut into calls
+ * gives the bytes of one call).  taps: HOST array of ky * kx Q12 integers, row-major; ky, kx odd in 1..9; ry = ky / 2,
+ * rx = kx / 2.  For output line y, pixel x, channel c, all in integers:
+ *   s(v, u) = src[clamp(v, 0, L-1)][clamp(u, 0, W-1)][c]                replicate at the image border
+ *   ctr = s(y, x)
+ *   ctr < valid_min:  out = ctr                                         no data passes through
+ *   otherwise:        n(j, i) = s(y + j - ry, x + i - rx),  n'(j, i) = n(j, i) < valid_min ? ctr : n(j, i)
+ *                     acc = sum_{j,i} taps[j * kx + i] * n'(j, i)       correlation form, as cv::filter2D
+ *                     out = clamp((acc + 2048) >> 12, valid_min, 65535) arithmetic shift (floor)
+ * Clamping at valid_min keeps data from becoming no data; replacing no-data neighbours by the centre keeps the black
+ * borders of prestitch and the aligner from ringing into the image.
+ * OIP_E_INVALID: sum |taps| > 32767 -- the bound that makes acc + 2048 fit int32: 32767 * 65535 + 2048 = 2 147 387 393
+ * < 2^31 --, valid_min outside 0..65535, spp other than 1 or 4, W < 1, L < 1, ky or kx even or above 9, output lines
+ * outside [0, L), a needed source line clamp(out_row0 - ry, 0, L-1) .. clamp(out_row0 + out_rows - 1 + ry, 0, L-1) that is
+ * not resident, d_dst == d_src (the call is not in place).  out_rows == 0 is a no-op.  A line that is not a multiple of 8
+ * samples, or bases that are not 16-byte aligned, take a slower kernel with the same result.  Asynchronous on the
+ * context's stream (the taps are copied during the call). */
+int oip_convolve_u16(oip_ctx *ctx, const uint16_t *d_src, long src_row0, long src_rows, uint16_t *d_dst, long out_row0,
+                     long out_rows, int W, long L, int spp, const int32_t *taps, int ky, int kx, int valid_min);
+
+/* The taps, host, no context needed.  fp64, every step one correctly rounded operation in the stated order.
+ * oip_mtfc_quantise: c (ky * kx coefficients, row-major) -> Q12 taps:
+ *   1. t = rint(c * 4096) per tap, ties to even
+ *   2. OIP_E_INVALID unless |sum c - 1| <= 1e-6, the plain ascending row-major sum
+ *   3. 4096 - sum t is added to the centre tap: the DC gain is exactly 1 and flat areas are unchanged
+ *   4. OIP_E_INVALID if sum |t| > 32767 (err names the sum)
+ * oip_mtfc_design3: the separable 3 x 3 filter that brings the MTF at Nyquist of either axis to 1, limited by max_gain.
+ *   Per axis  g = min(1 / m, max_gain),  a = (g - 1) / 4,  f = [-a, 1 + 2 * a, -a]  (response at Nyquist 1 + 4 a = g);
+ *   c9[j * 3 + i] = fy[j] * fx[i].  OIP_E_INVALID unless 0 < m <= 1 and max_gain >= 1.
+ * oip_mtfc_load_kernel: a text file, first line `ky kx`, then ky rows of kx numbers, white-space separated, read with
+ *   strtod.  c: room for 81 doubles.  OIP_E_IO when the file cannot be read, OIP_E_INVALID for a malformed file, an even
+ *   size or a size above 9. */
+int oip_mtfc_quantise(const double *c, int ky, int kx, int32_t *taps, char *err, int errlen);
+int oip_mtfc_design3(double mtf_x, double mtf_y, double max_gain, double *c9);
+int oip_mtfc_load_kernel(const char *path, double *c, int *ky, int *kx, char *err, int errlen);
+
 /* The strips of an LZW TIFF product, encoded on the device (cv::imwrite's TIFF encoder behind preproc.h:167-185 and GDAL's
  * COMPRESS=LZW PREDICTOR=2 behind imageop.h:460-567 do this on the host, strip by strip).  d_img: rows x width x spp u16,
  * interleaved, in file sample order (oip_permute_u16x4 first where cv::imwrite / a band map reorder); spp 1 or 4; strip k

@@ -19,6 +19,9 @@ from .capi import (  # noqa: F401
     library_path,
     load_library,
     load_rrc_param_file,
+    mtfc_design3,
+    mtfc_load_kernel,
+    mtfc_quantise,
     polyfit,
     remap_shift_src_range,
     rrc_fit_columns,

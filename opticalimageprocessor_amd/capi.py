@@ -119,6 +119,10 @@ _SIGS = {
     "oip_seam_moments_u16": ([_vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _vp], _i),
     "oip_seam_fit": ([C.POINTER(C.c_uint64), _i, _i, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.POINTER(_i), _cp, _i], _i),
     "oip_stitch_balanced_u16": ([_vp, _vp, _vp, _vp, _i, _l, _i, _i, _vp, _vp, _i, _i], _i),
+    "oip_convolve_u16": ([_vp, _vp, _l, _l, _vp, _l, _l, _i, _l, _i, C.POINTER(C.c_int32), _i, _i, _i], _i),
+    "oip_mtfc_quantise": ([_dp, _i, _i, C.POINTER(C.c_int32), _cp, _i], _i),
+    "oip_mtfc_design3": ([_d, _d, _d, _dp], _i),
+    "oip_mtfc_load_kernel": ([_cp, _dp, C.POINTER(_i), C.POINTER(_i), _cp, _i], _i),
     "oip_merge_subimages_be16": ([_vp, _vp, _vp, _i, _i, _i, _i], _i),
     "oip_profile_enable": ([_vp, _i], _i),
     "oip_profile_reset": ([_vp], _i),
@@ -230,6 +234,43 @@ def seam_fit(acc, mode="moments", min_count: int = 0):
     if rc:
         raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
     return gain, offset, ident, report
+
+
+def mtfc_quantise(c) -> np.ndarray:
+    """(ky, kx) coefficients summing to 1 -> Q12 int32 taps with DC gain exactly 1 (include/oip_c.h: oip_mtfc_quantise);
+    ValueError for a sum away from 1, an even or too large size, or sum |taps| above 32767"""
+    lib = load_library()
+    a = _dbl(c)
+    if a.ndim != 2:
+        raise ValueError("mtfc_quantise: a (ky, kx) array expected")
+    taps = np.zeros(a.shape, np.int32)
+    err = C.create_string_buffer(1024)
+    rc = lib.oip_mtfc_quantise(a.ctypes.data_as(_dp), a.shape[0], a.shape[1], taps.ctypes.data_as(C.POINTER(C.c_int32)), err, 1024)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    return taps
+
+
+def mtfc_design3(mtf_x: float, mtf_y: float, max_gain: float = 2.0) -> np.ndarray:
+    """the separable 3 x 3 MTF-compensation coefficients (fp64) for the MTF at Nyquist of either axis
+    (include/oip_c.h: oip_mtfc_design3)"""
+    lib = load_library()
+    c = np.zeros((3, 3))
+    if lib.oip_mtfc_design3(mtf_x, mtf_y, max_gain, c.ctypes.data_as(_dp)):
+        raise ValueError("oip_mtfc_design3: 0 < mtf <= 1 and max_gain >= 1 expected")
+    return c
+
+
+def mtfc_load_kernel(path: str) -> np.ndarray:
+    """the (ky, kx) coefficients of a kernel text file (include/oip_c.h: oip_mtfc_load_kernel)"""
+    lib = load_library()
+    c = np.zeros(81)
+    ky, kx = _i(), _i()
+    err = C.create_string_buffer(2048)
+    rc = lib.oip_mtfc_load_kernel(os.fsencode(path), c.ctypes.data_as(_dp), C.byref(ky), C.byref(kx), err, 2048)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    return c[:ky.value * kx.value].reshape(ky.value, kx.value).copy()
 
 
 def stretch_limits(hist, valid_min=1, valid_max=65535, p_lo=2.0, p_hi=98.0):
@@ -629,6 +670,18 @@ class Context:
         `feather` pixels either side of the seam (include/oip_c.h: oip_stitch_balanced_u16)"""
         self._ck(self.lib.oip_stitch_balanced_u16(self.h, _ptr(left), _ptr(right), _ptr(out), Ws, L, fs, spp, _ptr(gain_q16), _ptr(offset_q16),
                                                   feather, valid_min))
+
+    # -- MTF compensation
+    def convolve_u16(self, src, dst, W, L, spp, taps, valid_min=1, src_row0=0, src_rows=None, out_row0=0, out_rows=None):
+        """the (ky, kx) Q12 integer taps (host) applied to lines [out_row0, out_row0 + out_rows) of the W x L x spp raster
+        whose lines [src_row0, src_row0 + src_rows) are at src; not in place (include/oip_c.h: oip_convolve_u16)"""
+        t = np.ascontiguousarray(taps, dtype=np.int32)
+        if t.ndim != 2:
+            raise ValueError("convolve_u16: a (ky, kx) tap array expected")
+        src_rows = L if src_rows is None else src_rows
+        out_rows = L if out_rows is None else out_rows
+        self._ck(self.lib.oip_convolve_u16(self.h, _ptr(src), src_row0, src_rows, _ptr(dst), out_row0, out_rows, W, L, spp,
+                                           t.ctypes.data_as(C.POINTER(C.c_int32)), t.shape[0], t.shape[1], valid_min))
 
     # -- instrumentation
     def merge_subimages_be16(self, tiles, out, vparts, hparts, sub_lines, sub_cols):

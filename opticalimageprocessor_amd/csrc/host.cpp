@@ -1,11 +1,13 @@
 // host.cpp -- host-side pieces of the path that carry no raster arithmetic:
 // the RRC parameter file loader, its counterpart (column fit + writer), the seam fit of `oip stitch --balance`, the shift
-// filtering / polynomial fit and the contrast stretch of `oip quicklook` (percentile limits, 8-bit table, 8-bit TIFF).
+// filtering / polynomial fit, the contrast stretch of `oip quicklook` (percentile limits, 8-bit table, 8-bit TIFF) and the
+// taps of `oip mtfc` (design, quantisation, kernel file).
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "oip_c.h"
@@ -516,5 +518,100 @@ extern "C" int oip_write_tiff_u8(const char *path, const uint8_t *data, int widt
     } catch (const std::exception &e) {
         return fail(OIP_E_IO, e.what());
     }
+    return OIP_OK;
+}
+
+// ---- oip mtfc, host side: the taps of oip_convolve_u16 (include/oip_c.h states the operation order; tests/_mtfc_ref.py
+// restates it).  fp64 throughout, one rounded operation per step (-ffp-contract=off) ------------------------------------
+static bool mtfc_size_ok(int ky, int kx) { return ky >= 1 && kx >= 1 && ky <= OIP_CONVOLVE_MAX_K && kx <= OIP_CONVOLVE_MAX_K && ky % 2 == 1 && kx % 2 == 1; }
+
+extern "C" int oip_mtfc_quantise(const double *c, int ky, int kx, int32_t *taps, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *fmt, auto... a) {
+        if (err && errlen > 0) snprintf(err, errlen, fmt, a...);
+        return code;
+    };
+    if (!c || !taps || !mtfc_size_ok(ky, kx)) return fail(OIP_E_INVALID, "%s", "oip_mtfc_quantise: bad argument (odd sizes 1..9 expected)");
+    const int n = ky * kx;
+    double t[OIP_CONVOLVE_MAX_K * OIP_CONVOLVE_MAX_K];
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const double s = c[i] * 4096.0;
+        t[i] = std::rint(s);                                  // ties to even (default rounding mode)
+        sum += c[i];
+    }
+    const double dev = std::fabs(sum - 1.0);
+    if (!(dev <= 1e-6)) return fail(OIP_E_INVALID, "oip_mtfc_quantise: the coefficients sum to %.9g, not to 1 (within 1e-6)", sum);
+    long tsum = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!(std::fabs(t[i]) <= 1073741824.0)) return fail(OIP_E_INVALID, "oip_mtfc_quantise: coefficient %d (%g) is out of range", i, c[i]);
+        taps[i] = (int32_t)t[i];
+        tsum += taps[i];
+    }
+    taps[(ky / 2) * kx + kx / 2] += (int32_t)(4096 - tsum);   // DC gain exactly 1: flat areas stay as they are
+    long abssum = 0;
+    for (int i = 0; i < n; ++i) abssum += taps[i] < 0 ? -(long)taps[i] : (long)taps[i];
+    if (abssum > 32767)
+        return fail(OIP_E_INVALID, "oip_mtfc_quantise: sum |taps| = %ld above 32767 (the int32 accumulator of oip_convolve_u16): lower the gain", abssum);
+    return OIP_OK;
+}
+
+extern "C" int oip_mtfc_design3(double mtf_x, double mtf_y, double max_gain, double *c9)
+{
+    if (!c9 || !(mtf_x > 0.0 && mtf_x <= 1.0) || !(mtf_y > 0.0 && mtf_y <= 1.0) || !(max_gain >= 1.0)) return OIP_E_INVALID;
+    double f[2][3];
+    const double m[2] = {mtf_x, mtf_y};
+    for (int k = 0; k < 2; ++k) {
+        const double inv = 1.0 / m[k];
+        const double g = inv < max_gain ? inv : max_gain;
+        const double d = g - 1.0;
+        const double a = d / 4.0;
+        const double a2 = 2.0 * a;
+        f[k][0] = -a;
+        f[k][1] = 1.0 + a2;
+        f[k][2] = -a;
+    }
+    for (int j = 0; j < 3; ++j)
+        for (int i = 0; i < 3; ++i) c9[j * 3 + i] = f[1][j] * f[0][i];
+    return OIP_OK;
+}
+
+extern "C" int oip_mtfc_load_kernel(const char *path, double *c, int *ky, int *kx, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *fmt, auto... a) {
+        if (err && errlen > 0) snprintf(err, errlen, fmt, a...);
+        return code;
+    };
+    if (!path || !c || !ky || !kx) return fail(OIP_E_INVALID, "%s", "oip_mtfc_load_kernel: bad argument");
+    FILE *f = fopen(path, "rb");
+    if (!f) return fail(OIP_E_IO, "open kernel file [%s] failed: %s", path, strerror(errno));
+    std::string text;
+    char buff[4096];
+    size_t got = 0;
+    while (text.size() <= 65536 && (got = fread(buff, 1, sizeof buff, f)) > 0) text.append(buff, got);
+    const bool bad = ferror(f) != 0;
+    fclose(f);
+    if (bad) return fail(OIP_E_IO, "read of kernel file [%s] failed", path);
+    if (text.size() > 65536 || text.find('\0') != std::string::npos) return fail(OIP_E_INVALID, "kernel file [%s] invalid: not a small text file", path);
+    const char *p = text.c_str();
+    char *e = nullptr;
+    long dims[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+        dims[k] = strtol(p, &e, 10);
+        if (e == p) return fail(OIP_E_INVALID, "kernel file [%s] invalid: first line `ky kx' expected", path);
+        p = e;
+    }
+    if (dims[0] < 1 || dims[1] < 1 || dims[0] > OIP_CONVOLVE_MAX_K || dims[1] > OIP_CONVOLVE_MAX_K || dims[0] % 2 == 0 || dims[1] % 2 == 0)
+        return fail(OIP_E_INVALID, "kernel file [%s] invalid: size %ld x %ld, odd sizes 1..%d expected", path, dims[0], dims[1], OIP_CONVOLVE_MAX_K);
+    const int n = (int)(dims[0] * dims[1]);
+    for (int i = 0; i < n; ++i) {
+        c[i] = strtod(p, &e);
+        if (e == p) return fail(OIP_E_INVALID, "kernel file [%s] invalid: %d numbers expected, %d found", path, n, i);
+        p = e;
+    }
+    while (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r' || *p == '\f' || *p == '\v') ++p;
+    if (*p) return fail(OIP_E_INVALID, "kernel file [%s] invalid: text behind the %d numbers", path, n);
+    *ky = (int)dims[0];
+    *kx = (int)dims[1];
     return OIP_OK;
 }

@@ -1815,4 +1815,146 @@ inline void RunQuicklook(const std::string &file, const std::string &out, const 
     OLOG("%zu bytes in %.3f seconds (%.1f MBps).", inBytes, es, inBytes / es / 1024.0 / 1024.0);
 }
 
+// ---- oip mtfc: MTF compensation of a strip or product ---------------------------------------------------------------
+// A small fixed-point restoration filter (oip_convolve_u16) behind the radiometric correction: the taps come from a kernel
+// file or from the MTF at Nyquist of the two axes (oip_mtfc_load_kernel / oip_mtfc_design3, then oip_mtfc_quantise).  The
+// output has the container of the input.  Not in the reference.
+struct MtfcOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    std::string kernelFile;                 // --kernel, or
+    double mtfX = 0.0, mtfY = 0.0;          // --mtf-x / --mtf-y: the MTF at Nyquist across and along the lines
+    double maxGain = OIP_MTFC_DEF_MAXGAIN;
+    int validMin = 1;                       // 0 is the border value of prestitch and the aligner (BORDER_CONSTANT)
+    bool force = false;
+};
+
+struct MtfcTaps {
+    int ky = 0, kx = 0;
+    int32_t t[OIP_CONVOLVE_MAX_K * OIP_CONVOLVE_MAX_K];
+};
+
+// everything that can be refused without a device: the container, the taps, the output; returns the output path
+inline std::string MtfcCheck(const std::string &file, const std::string &out, const MtfcOptions &o, bool *isTiff, MtfcTaps *taps)
+{
+    const std::string ext = to_lower(std::filesystem::path(file).extension().string());
+    if (ext != ".tiff" && ext != ".raw") throw std::invalid_argument("mtfc: only RAW and TIFF image supported");
+    *isTiff = ext == ".tiff";
+    if (!*isTiff) {
+        if (o.width <= 0) throw std::invalid_argument("--width: a positive line width expected");
+        const size_t size = IMO::FileSize(file), lineBytes = (size_t)o.width * BYTES_PER_PIXEL;
+        if (size == 0 || size % lineBytes != 0)
+            throw std::invalid_argument("image file size invalid: should be multiplies of " + std::to_string(lineBytes));
+    }
+    double c[OIP_CONVOLVE_MAX_K * OIP_CONVOLVE_MAX_K];
+    char err[1024] = "";
+    if (!o.kernelFile.empty()) {
+        const int rc = oip_mtfc_load_kernel(o.kernelFile.c_str(), c, &taps->ky, &taps->kx, err, sizeof err);
+        if (rc == OIP_E_IO) throw errno_error(err, 0);
+        if (rc != OIP_OK) throw std::invalid_argument(err);
+    } else {
+        taps->ky = taps->kx = 3;
+        if (oip_mtfc_design3(o.mtfX, o.mtfY, o.maxGain, c) != OIP_OK) throw std::invalid_argument("--mtf-x/--mtf-y/--max-gain: 0 < M <= 1 and G >= 1 expected");
+    }
+    if (oip_mtfc_quantise(c, taps->ky, taps->kx, taps->t, err, sizeof err) != OIP_OK) throw std::invalid_argument(err);
+    const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_MTFC_SUFFIX) : out;
+    if (to_lower(std::filesystem::path(path).extension().string()) != ext) throw std::invalid_argument("mtfc: the output has the container of the input (" + ext + ")");
+    struct stat st;
+    if (stat(path.c_str(), &st) == 0) {
+        if (std::filesystem::equivalent(path, file)) throw std::invalid_argument("output file [" + path + "] is the input image");
+        if (!o.force) throw std::runtime_error("output file [" + path + "] exists: mtfc does not replace a file without --force");
+    }
+    return path;
+}
+
+inline void RunMtfc(const std::string &file, const std::string &out, const MtfcOptions &o)
+{
+    bool isTiff = false;
+    MtfcTaps taps;
+    const std::string outPath = MtfcCheck(file, out, o, &isTiff, &taps);
+    const int ky = taps.ky, kx = taps.kx, ry = ky / 2;
+    long absSum = 0;
+    OLOG("MTFC taps (Q12, %d x %d):", ky, kx);
+    for (int j = 0; j < ky; ++j) {
+        std::string row;
+        for (int i = 0; i < kx; ++i) {
+            row += (i ? " " : "") + std::to_string(taps.t[j * kx + i]);
+            absSum += std::abs((long)taps.t[j * kx + i]);
+        }
+        RLOG("    %s", row.c_str());
+    }
+    OLOG("sum |t| = %ld (gain at most %.3f), valid-min %d", absSum, absSum / 4096.0, o.validMin);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    size_t bytes = 0;
+    if (isTiff) {
+        // a product is filtered resident and leaves through the product writer of `oip stitch`
+        int w = 0, spp = 0;
+        long h = 0;
+        DevBuf<uint16_t> img;
+        OLOG("Reading image from file `%s' ...", file.c_str());
+        read_tiff_to_device(file, &w, &h, &spp, img);
+        if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument("mtfc: a TIFF of 1 or 4 samples per pixel expected");
+        DevBuf<uint16_t> res((size_t)w * h * spp);
+        ck(oip_convolve_u16(ctx, img.p, 0, h, res.p, 0, h, w, h, spp, taps.t, ky, kx, o.validMin));
+        OLOG("Write filtered image to file '%s' ...", outPath.c_str());
+        write_tiff_from_device(outPath, res.p, w, h, spp, tiff_compression(spp == 1 ? TIFF_NONE : TIFF_LZW), false);
+        bytes = (size_t)w * h * spp * BYTES_PER_PIXEL;
+    } else {
+        // The strip is never resident: line blocks with ry halo lines either side go file -> pinned ring -> one of two device
+        // blocks (as RunQuicklook does it), the filter of a block runs behind its upload (ticket), and its output goes from one of
+        // two device blocks to its byte offset in the product on a writer thread behind a compute mark: read || filter || write.
+        const int W = o.width;
+        const size_t lineBytes = (size_t)W * BYTES_PER_PIXEL;
+        const long L = (long)(IMO::FileSize(file) / lineBytes);
+        long blockLines = std::max<long>(1, (long)(((size_t)64 << 20) / lineBytes));
+        if (const char *e = getenv("OIP_MTFC_BLOCK_LINES")) {             // test hook: several blocks on a small image
+            const long v = atol(e);
+            if (v > 0) blockLines = v;
+        }
+        const long cap = std::min(blockLines, L);
+        DevBuf<uint16_t> in[2], res[2];
+        for (int i = 0; i < 2 && (long)i * blockLines < L; ++i) {
+            in[i].alloc((size_t)std::min(cap + 2 * ry, L) * W);
+            res[i].alloc((size_t)cap * W);
+        }
+        { FILE *f = fopen(outPath.c_str(), "wb"); if (!f) throw std::runtime_error("open file [" + outPath + "] failed: " + std::to_string(errno)); fclose(f); }
+        OLOG("Reading raw image from file `%s' ...", file.c_str());
+        std::future<void> written[2];
+        JobThread writer;                                               // (declared after the buffers: joined before they are released)
+        long block = 0;
+        for (long r = 0; r < L; r += blockLines, ++block) {
+            const long m = std::min(blockLines, L - r);
+            const long s0 = std::max<long>(0, r - ry), s1 = std::min(L, r + m + ry);
+            uint16_t *d = in[block & 1].p, *q = res[block & 1].p;
+            if (block >= 2) ck(oip_stage_order_after_compute(ctx));     // the kernel that read this buffer two blocks ago goes first
+            size_t got = 0;
+            long ticket = 0;
+            ck(oip_read_file_to_device(ctx, file.c_str(), (size_t)s0 * lineBytes, (size_t)(s1 - s0) * lineBytes, d, &got, &ticket));
+            if (got != (size_t)(s1 - s0) * lineBytes)
+                throw std::runtime_error("file size(" + std::to_string((size_t)s1 * lineBytes) + ") doesn't match with read byte count(" +
+                                         std::to_string((size_t)s0 * lineBytes + got) + ")");
+            ck(oip_stage_wait(ctx, ticket));
+            if (written[block & 1].valid()) {                           // the output block of two blocks ago is in the file
+                try { written[block & 1].get(); } catch (const std::future_error &) { writer.finish(); throw; }      // (a failed writer drops its jobs)
+            }
+            ck(oip_convolve_u16(ctx, d, s0, s1 - s0, q, r, m, W, L, 1, taps.t, ky, kx, o.validMin));
+            long mark = 0;
+            ck(oip_compute_mark(ctx, &mark));
+            auto done = std::make_shared<std::promise<void>>();
+            written[block & 1] = done->get_future();
+            const size_t nb = (size_t)m * lineBytes, off = (size_t)r * lineBytes;
+            writer.post([=] {
+                const int rc = oip_write_device_to_file_at(ctx, q, nb, outPath.c_str(), off, mark);
+                done->set_value();                                      // the buffer is free either way; finish() reports a failure
+                Device::get().check(rc);
+            });
+        }
+        writer.finish();
+        bytes = (size_t)L * lineBytes;
+    }
+    const double es = total.tick();
+    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+}
+
 }  // namespace OIPGPU

@@ -10,11 +10,12 @@
 //   oip rrc-calib [--pan P.RAW --rrc-pan OUT] [--mss M.RAW --rrc-msb1..4 OUT]   derives the RRC coefficient files the
 //                               actions above read from a strip's per-column statistics, see run_rrc_calib()
 //   oip quicklook IMAGE [-o OUT.TIFF] [--factor 16 ...]   8-bit browse image of a strip or product, see run_quicklook()
+//   oip mtfc IMAGE [-o OUT] (--kernel FILE | --mtf-x M --mtf-y M)   MTF-compensation filter of a strip or product, see run_mtfc()
 //   oip -v | --version          prints 1.1
 // plus --width N (pixels per PAN line; the reference hard-codes 12288, oipshared.h:28).
 // `auxsep` is outside this build.  TIFF input and output go through oip_tiff.hpp (uncompressed and LZW, with
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
-// (--balance, --feather and their --valid-min / --valid-max / --min-count) and the rrc-calib and quicklook sub-commands.
+// (--balance, --feather and their --valid-min / --valid-max / --min-count) and the rrc-calib, quicklook and mtfc sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -146,7 +147,12 @@ void usage()
          "  quicklook  IMAGE.RAW|IMAGE.TIFF: an 8-bit browse image, box-decimated by --factor and contrast-stretched per band\n"
          "             between two percentiles of its valid samples; written to <stem>.QL.TIFF in the working directory:\n"
          "             [-o,--out FILE] [--factor 2|4|8|16|32|64] [--clip-low P] [--clip-high P] [--valid-min N] [--valid-max N]\n"
-         "             [--bands A | A,B,C] [--bil] (RAW: the MSS line layout) [--width N] [--line-offset N] [--lines N] [--force]");
+         "             [--bands A | A,B,C] [--bil] (RAW: the MSS line layout) [--width N] [--line-offset N] [--lines N] [--force]\n"
+         "  mtfc       IMAGE.RAW|IMAGE.TIFF: MTF compensation, a fixed-point restoration filter of up to 9 x 9 taps; the output has\n"
+         "             the container of the input and is written to <stem>.MTFC.<ext> in the working directory:\n"
+         "             [-o,--out FILE] --kernel FILE (text: `ky kx', then ky rows of kx coefficients summing to 1)\n"
+         "             | --mtf-x M --mtf-y M (the MTF at Nyquist across / along the lines, 0 < M <= 1) [--max-gain G] (default 2.0)\n"
+         "             [--valid-min N] (samples below are no data and pass through; default 1) [--width N] [--force]");
 }
 
 int run_prestitch(const std::vector<std::string> &args, int width)
@@ -481,6 +487,51 @@ int run_quicklook(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip mtfc IMAGE: the MTF-compensation filter of a strip (.RAW, --width samples per line) or a product (.TIFF of 1 or 4
+// samples).  IMAGE is the one positional argument, as for quicklook.
+int run_mtfc(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--out", "--kernel", "--mtf-x", "--mtf-y", "--max-gain", "--valid-min", "--width"};
+    sp.flags = {"--force"};
+    sp.alias = {{"-o", "--out"}};
+    std::string image;
+    std::vector<std::string> rest;
+    for (size_t i = 0; i < args.size(); ++i) {
+        const std::string &a = args[i];
+        if (!a.empty() && a[0] != '-' && image.empty()) { image = a; continue; }
+        rest.push_back(a);
+        auto al = sp.alias.find(a);
+        if (sp.valued.count(al != sp.alias.end() ? al->second : a) && i + 1 < args.size()) rest.push_back(args[++i]);
+    }
+    Parsed p = parse(sp, rest);
+    if (image.empty()) throw cli_error(106, "IMAGE is required");
+    struct stat st;
+    if (stat(image.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) throw cli_error(105, "IMAGE: File does not exist: " + image);
+    const bool design = p.has("--mtf-x") || p.has("--mtf-y") || p.has("--max-gain");
+    if (p.has("--kernel") && design) throw usage_error("--kernel and --mtf-x/--mtf-y/--max-gain exclude each other");
+    if (!p.has("--kernel") && !design) throw usage_error("--kernel FILE or --mtf-x M --mtf-y M expected");
+    MtfcOptions o;
+    o.width = p.integer("--width", width);
+    if (design) {
+        require(p, "--mtf-x");
+        require(p, "--mtf-y");
+        o.mtfX = p.real("--mtf-x", 0.0);
+        o.mtfY = p.real("--mtf-y", 0.0);
+        o.maxGain = p.real("--max-gain", OIP_MTFC_DEF_MAXGAIN);
+        if (!(o.mtfX > 0.0 && o.mtfX <= 1.0) || !(o.mtfY > 0.0 && o.mtfY <= 1.0)) throw cli_error(105, "--mtf-x/--mtf-y: 0 < M <= 1 expected");
+        if (!(o.maxGain >= 1.0)) throw cli_error(105, "--max-gain: G >= 1 expected");
+    } else {
+        existing_file(p, "--kernel");
+        o.kernelFile = p.str("--kernel");
+    }
+    o.validMin = p.integer("--valid-min", 1);
+    if (o.validMin < 0 || o.validMin > 65535) throw cli_error(105, "--valid-min: 0 <= N <= 65535 expected");
+    o.force = p.flag.count("--force") != 0;
+    RunMtfc(image, p.str("--out"), o);
+    return 0;
+}
+
 }  // namespace
 
 static int oip_main(int argc, const char *argv[]);
@@ -529,6 +580,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "plan") return run_plan({args.begin() + 1, args.end()});
             if (!args.empty() && args[0] == "rrc-calib") return run_rrc_calib({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "quicklook") return run_quicklook({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "mtfc") return run_mtfc({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "auxsep")
                 throw std::invalid_argument("auxsep (down-link de-framing) is outside this build: run the reference's auxsep, then this tool");
             if (args.empty()) { usage(); return 0; }
