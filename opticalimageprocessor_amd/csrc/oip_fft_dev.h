@@ -87,15 +87,22 @@ __device__ __forceinline__ void bf4(float2 *x)
 __device__ __forceinline__ void bf5(float2 *x)
 {
     OIP_FFT_FMA
-    const float c1 = 0.30901699437494742410f, c2 = -0.80901699437494742410f;
+    // cos(2 pi / 5) = -1/4 + q, cos(4 pi / 5) = -1/4 - q, q = sqrt(5) / 4: the real parts as x0 - (t1 + t2) / 4 +- q (t1 - t2).
+    // Five equal inputs then give exact zeros in x[1..4] (t1 == t2, x0 - 4 x0 / 4 == 0), as bf2, bf3, bf4 and bf8 do: the
+    // transform of a constant image is DC alone.  With x0 + c1 t1 + c2 t2 (c1 + c2 rounded: not -1/2) those outputs were
+    // rounding noise of the size of an ulp of the sum, which the cross-power division whitens into unit-magnitude bins -- a
+    // constant 10000 x 48 pair came out with a response of 1.5e-4 (tests/test_gpu_fft_routes.py).  Same operation count.
+    const float q = 0.55901699437494742410f;
     const float s1 = 0.95105651629515357212f, s2 = 0.58778525229247312917f;
     float2 t1 = cadd(x[1], x[4]), t2 = cadd(x[2], x[3]);
     float2 t3 = csub(x[1], x[4]), t4 = csub(x[2], x[3]);
-    float2 m1 = make_float2(x[0].x + c1 * t1.x + c2 * t2.x, x[0].y + c1 * t1.y + c2 * t2.y);
-    float2 m2 = make_float2(x[0].x + c2 * t1.x + c1 * t2.x, x[0].y + c2 * t1.y + c1 * t2.y);
+    float2 ts = cadd(t1, t2), td = csub(t1, t2);
+    float2 mb = make_float2(x[0].x - 0.25f * ts.x, x[0].y - 0.25f * ts.y);
+    float2 m1 = make_float2(mb.x + q * td.x, mb.y + q * td.y);
+    float2 m2 = make_float2(mb.x - q * td.x, mb.y - q * td.y);
     float2 u1 = make_float2(s1 * t3.x + s2 * t4.x, s1 * t3.y + s2 * t4.y);
     float2 u2 = make_float2(s2 * t3.x - s1 * t4.x, s2 * t3.y - s1 * t4.y);
-    x[0] = cadd(x[0], cadd(t1, t2));
+    x[0] = cadd(x[0], ts);
     x[1] = cadd_rot(m1, u1);
     x[4] = csub_rot(m1, u1);
     x[2] = cadd_rot(m2, u2);

@@ -80,13 +80,9 @@ def _cross_power_ccs(F1: np.ndarray, F2: np.ndarray, M: int, N: int) -> np.ndarr
     return C
 
 
-def phase_correlate(a: np.ndarray, b: np.ndarray, fft: str = "f64"):
-    """cv::phaseCorrelate(src1, src2, noArray(), &response) -> ((dx, dy), response).
-
-    fft="f64": the transforms run in float64 (numpy) and are rounded to float32 storage -- the tightest statement of
-    the algorithm.  fft="f32": scipy.fft on float32 arrays, single precision throughout like OpenCV's own dft() -- a
-    second, independent float32 implementation next to the GPU's: the spread between the two float32 results and the
-    float64 one is what "any correct float32 FFT" costs, and the tests report GPU-vs-f32 and f32-vs-f64 side by side."""
+def correlation_surface(a: np.ndarray, b: np.ndarray, fft: str = "f64") -> np.ndarray:
+    """The fftShift-ed float32 correlation surface (M x N, the padded size) that phase_correlate takes its peak and
+    its 5x5 centroid from.  `fft` as in phase_correlate."""
     a = np.asarray(a, np.float32)
     b = np.asarray(b, np.float32)
     assert a.shape == b.shape and a.ndim == 2
@@ -111,9 +107,28 @@ def phase_correlate(a: np.ndarray, b: np.ndarray, fft: str = "f64"):
         F2 = np.fft.rfft2(pb.astype(np.float64))
         C = _cross_power_ccs(F1, F2, M, N)
         c = (np.fft.irfft2(C.astype(np.complex128), s=(M, N)) * (M * N)).astype(np.float32)
-    c = np.roll(c, (M >> 1, N >> 1), axis=(0, 1))            # fftShift
-    peak = int(np.argmax(c))                                 # minMaxLoc: first maximum
-    py, px = divmod(peak, N)
+    return np.roll(c, (M >> 1, N >> 1), axis=(0, 1))         # fftShift
+
+
+def surface_peak(c: np.ndarray):
+    """minMaxLoc on the shifted surface: (py, px) of the first maximum in scan order"""
+    return divmod(int(np.argmax(c)), c.shape[1])
+
+
+def phase_correlate(a: np.ndarray, b: np.ndarray, fft: str = "f64"):
+    """cv::phaseCorrelate(src1, src2, noArray(), &response) -> ((dx, dy), response).
+
+    fft="f64": the transforms run in float64 (numpy) and are rounded to float32 storage -- the tightest statement of
+    the algorithm.  fft="f32": scipy.fft on float32 arrays, single precision throughout like OpenCV's own dft() -- a
+    second, independent float32 implementation next to the GPU's: the spread between the two float32 results and the
+    float64 one is what "any correct float32 FFT" costs, and the tests report GPU-vs-f32 and f32-vs-f64 side by side."""
+    return centroid_of_surface(correlation_surface(a, b, fft))
+
+
+def centroid_of_surface(c: np.ndarray):
+    """peak + weightedCentroid + response of a shifted surface -> ((dx, dy), response)"""
+    M, N = c.shape
+    py, px = surface_peak(c)
     # weightedCentroid(C, peak, Size(5,5))
     minr, maxr = max(py - 2, 0), min(py + 2, M - 1)
     minc, maxc = max(px - 2, 0), min(px + 2, N - 1)

@@ -239,3 +239,19 @@ def test_upsample_operator_reproduces_the_transform_of_the_resized_image(oracle_
         assert np.abs(got - ref).max() < 2e-6 * np.abs(ref).max(), (m, n, np.abs(got - ref).max() / np.abs(ref).max())
     with pytest.raises(ValueError):
         oip.upsample_operator(4)
+
+
+def test_fft_index_helpers_under_sanitizers(tmp_path):
+    """csrc/oip_fft.h on the CPU (tests/cpp/fft_index_test.cpp; ASan + UBSan): oip_pos_to_freq / oip_freq_to_pos are mutual
+    inverses, permutations of [0, L) and the header's definition recomputed independently, for every factor list the planner
+    emits for the tested shapes; oip_peak_pack / oip_peak_key keep the value order (negative, denormal, zero, positive, inf),
+    -0 == +0, NaN = the empty slot, ties to the smallest key (0 and 2^32 - 2 included), and the key round-trips."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = os.path.join(root, "tests", "cpp", "fft_index_test.cpp")
+    inc = os.path.join(root, "opticalimageprocessor_amd", "csrc")
+    rocm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")          # oip_fft.h takes float2 from the HIP headers
+    exe = tmp_path / "fft_index"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-D__HIP_PLATFORM_AMD__", "-I" + rocm, "-I" + inc, src, "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and " checks, 0 bad" in r.stdout and "FAILED" not in r.stdout, r.stdout + r.stderr
