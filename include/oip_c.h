@@ -133,6 +133,10 @@ int oip_colstats_u16(oip_ctx *ctx, const uint16_t *d_img, long pitch, int w, lon
 int oip_rrc_fit_columns(const uint64_t *acc, int w, int groups, int mode, uint64_t min_count,
                         double *kb_out, int *dead_out, double *ref_out, char *err, int errlen);
 
+/* The columns that oip_rrc_fit_columns treats as not usable (the same predicate, stated once), ascending: cols has room for
+ * w entries, *n receives their number.  The list `oip despike --bad-columns` consumes.  OIP_E_INVALID for a bad argument. */
+int oip_rrc_dead_columns(const uint64_t *acc, int w, int mode, uint64_t min_count, int *cols, int *n);
+
 /* Writes RRCParam[n] in the format IMO::LoadRRCParamFile reads (imageop.h:148-188): "1\n", "<n>\n", "0\n", then n rows
  * "k , b" in %.17g (the doubles load back bit for bit), every row ended by one '\n' and nothing after the last (the
  * reader fails on a trailing blank line); a row is far shorter than the reader's 1024-byte buffer.  An existing file is
@@ -513,6 +517,62 @@ int oip_convolve_u16(oip_ctx *ctx, const uint16_t *d_src, long src_row0, long sr
 int oip_mtfc_quantise(const double *c, int ky, int kx, int32_t *taps, char *err, int errlen);
 int oip_mtfc_design3(double mtf_x, double mtf_y, double max_gain, double *c9);
 int oip_mtfc_load_kernel(const char *path, double *c, int *ky, int *kx, char *err, int errlen);
+
+/* ---- despike: repair of a raw strip ahead of RRC (`oip despike`; not in the reference) ------------------------------
+ * oip_rrc_fit_columns finds dead detectors and gives them (1, 0); a hot or flickering pixel goes through RRC multiplied by its
+ * k; the first resampling then spreads each such sample over a 4 x 4 bicubic footprint.  This is the step before all that:
+ * listed bad columns are interpolated from their good neighbours and isolated impulse pixels are replaced by a conditional
+ * 3 x 3 median.  Specified in exact integers: any evaluation order gives the same bytes.  The zero-filled line blocks that
+ * the de-framer writes for missing frames (aux_separator.h:280-310) are no data: they pass through and stay out of their
+ * neighbours' medians. */
+#define OIP_DESPIKE_SUFFIX     ".DSPK"  /* <stem>.DSPK.<ext>, built like the reference's other product names (imageop.h:99-108) */
+
+/* Raster and window conventions are oip_convolve_u16's: W pixels x L lines of spp samples (1, or 4 pixel-interleaved); d_src
+ * holds global lines [src_row0, src_row0 + src_rows), d_dst receives [out_row0, out_row0 + out_rows), the first at d_dst; a
+ * strip cut into calls gives the bytes of one call.  groups: 1, or 4 for a BIL MSS line (preproc.h:62-75; needs spp 1 and
+ * W % 4 == 0): four bands of gw = W / groups columns next to each other that never mix.  d_coltab: NULL, or 2 * W int32 in HBM,
+ * (Lx, Rx) per column as oip_despike_column_table builds them (spp 1 only, else OIP_E_UNSUPPORTED; the table is trusted: an
+ * entry that is not Lx <= x <= Rx inside the line copies a sample of the line).  d_count: NULL, or W * spp uint64 in HBM that
+ * are ADDED into; the caller zeroes them (oip_memset).  For output line y, pixel x, channel ch, all in integers:
+ *   1. column repair, with a = src[v][Lx], b = src[v][Rx], D = Rx - Lx:
+ *        D == 0 (every good column has Lx = Rx = x):   c(v, x) = a
+ *        a < valid_min or b < valid_min:               c = a >= valid_min ? a : b
+ *        otherwise:                                    c = (a * (Rx - x) + b * (x - Lx) + D / 2) / D     D / 2 and the division floored
+ *      without a table c = src.
+ *   2. s(v, u) = c(clamp(v, 0, L-1), clamp(u, g0, g0 + gw - 1)),  g0 = (x / gw) * gw: replicate at the image border and at
+ *      band borders; with spp 4 the pixel index is clamped and the channel kept.
+ *   3. ctr = s(y, x).  ctr < valid_min: out = ctr, no count.  Otherwise
+ *        n'(j, i) = s(y + j - 1, x + i - 1), replaced by ctr where it is < valid_min
+ *        med = the 5th smallest of the nine n' (the centre is one of them)
+ *        T = thr_abs + ((med * thr_rel_q8) >> 8)
+ *        |ctr - med| > T:  out = med and d_count[x * spp + ch] += 1;  otherwise out = ctr
+ *      med >= valid_min always: data never becomes no data.
+ * thr_abs = thr_rel_q8 = 0 is the plain 3 x 3 median with a replicate border; thr_abs = 65535 switches the despike off (the
+ * output is the column-repaired input).  The counts are exact and do not depend on the launch geometry or on how the strip
+ * is cut.  OIP_E_INVALID: thr_abs outside 0..65535, thr_rel_q8 outside 0..256, valid_min outside 0..65535, spp or groups other
+ * than stated, W < 1, L < 1, output lines outside [0, L), a needed source line clamp(out_row0 - 1, 0, L-1) ..
+ * clamp(out_row0 + out_rows, 0, L-1) that is not resident, d_dst == d_src (the call is not in place).  out_rows == 0 is a
+ * no-op.  A line or a group that is not a multiple of 8 samples, or bases that are not 16-byte aligned, take a slower kernel
+ * with the same result.  Asynchronous on the context's stream. */
+int oip_despike_u16(oip_ctx *ctx, const uint16_t *d_src, long src_row0, long src_rows, uint16_t *d_dst, long out_row0,
+                    long out_rows, int W, long L, int spp, int groups, const int32_t *d_coltab, int thr_abs,
+                    int thr_rel_q8, int valid_min, uint64_t *d_count);
+
+/* The column list and the table, host, no context needed.
+ * oip_load_column_list: a text file; `#` starts a comment that runs to the end of the line; otherwise white-space separated
+ *   decimal integers, each a 0-based column of the w-sample line (BIL MSS: band b column i is b * w / 4 + i), in any order,
+ *   duplicates tolerated.  cols (room for cap) receives them sorted and unique, *n their number; an empty list is valid.
+ *   OIP_E_IO when the file cannot be read; OIP_E_INVALID for a token that is not a number, a value outside [0, w), more than
+ *   cap columns.
+ * oip_write_column_list: `# comment` (one line), then one index per line.  An existing file is replaced: refusing to do so is
+ *   the caller's policy.
+ * oip_despike_column_table: tab (2 * w int32) receives (Lx, Rx) per column: (x, x) for a good one, for a listed one the nearest
+ *   good column on either side INSIDE ITS GROUP (groups 1 or 4, w % groups == 0); a missing side is set to the other (a copy).
+ *   OIP_E_INVALID for a column outside [0, w) or a group without a good column (err names the group).  longest_run (may be
+ *   NULL): the longest run of adjacent listed columns inside a group. */
+int oip_load_column_list(const char *path, int w, int *cols, int cap, int *n, char *err, int errlen);
+int oip_write_column_list(const char *path, const int *cols, int n, const char *comment, char *err, int errlen);
+int oip_despike_column_table(const int *bad, int nbad, int w, int groups, int32_t *tab, int *longest_run, char *err, int errlen);
 
 /* The strips of an LZW TIFF product, encoded on the device (cv::imwrite's TIFF encoder behind preproc.h:167-185 and GDAL's
  * COMPRESS=LZW PREDICTOR=2 behind imageop.h:460-567 do this on the host, strip by strip).  d_img: rows x width x spp u16,

@@ -15,8 +15,10 @@ from .capi import (  # noqa: F401
     STATUS_NAMES,
     build,
     declared_symbols,
+    despike_column_table,
     filter_and_fit,
     library_path,
+    load_column_list,
     load_library,
     load_rrc_param_file,
     mtfc_design3,
@@ -24,12 +26,14 @@ from .capi import (  # noqa: F401
     mtfc_quantise,
     polyfit,
     remap_shift_src_range,
+    rrc_dead_columns,
     rrc_fit_columns,
     seam_fit,
     stretch_limits,
     stretch_lut_u8,
     stt_mean,
     upsample_operator,
+    write_column_list,
     write_rrc_param_file,
     write_tiff_u8,
     align_mss_src_range,

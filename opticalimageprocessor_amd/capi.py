@@ -66,6 +66,7 @@ _SIGS = {
     "oip_colstats_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _vp], _i),
     "oip_rrc_fit_columns": ([C.POINTER(C.c_uint64), _i, _i, _i, C.c_uint64, _dp, C.POINTER(_i), _dp, _cp, _i], _i),
     "oip_write_rrc_param_file": ([_cp, _dp, _i, _cp, _i], _i),
+    "oip_rrc_dead_columns": ([C.POINTER(C.c_uint64), _i, _i, C.c_uint64, C.POINTER(_i), C.POINTER(_i)], _i),
     "oip_decimate_box_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _vp, _l, _sz], _i),
     "oip_histogram_u16": ([_vp, _vp, _l, _i, _l, _vp], _i),
     "oip_apply_lut_u8": ([_vp, C.POINTER(_vp), _l, _i, _l, _i, _vp, _vp], _i),
@@ -123,6 +124,10 @@ _SIGS = {
     "oip_mtfc_quantise": ([_dp, _i, _i, C.POINTER(C.c_int32), _cp, _i], _i),
     "oip_mtfc_design3": ([_d, _d, _d, _dp], _i),
     "oip_mtfc_load_kernel": ([_cp, _dp, C.POINTER(_i), C.POINTER(_i), _cp, _i], _i),
+    "oip_despike_u16": ([_vp, _vp, _l, _l, _vp, _l, _l, _i, _l, _i, _i, _vp, _i, _i, _i, _vp], _i),
+    "oip_load_column_list": ([_cp, _i, C.POINTER(_i), _i, C.POINTER(_i), _cp, _i], _i),
+    "oip_write_column_list": ([_cp, C.POINTER(_i), _i, _cp, _cp, _i], _i),
+    "oip_despike_column_table": ([C.POINTER(_i), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(_i), _cp, _i], _i),
     "oip_merge_subimages_be16": ([_vp, _vp, _vp, _i, _i, _i, _i], _i),
     "oip_profile_enable": ([_vp, _i], _i),
     "oip_profile_reset": ([_vp], _i),
@@ -210,6 +215,57 @@ def write_rrc_param_file(path: str, kb) -> None:
     rc = lib.oip_write_rrc_param_file(os.fsencode(path), kb.ctypes.data_as(_dp), kb.shape[0], err, 2048)
     if rc:
         raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+
+
+def rrc_dead_columns(acc, mode="moments", min_count: int = 0) -> np.ndarray:
+    """the columns of the (3, w) uint64 totals that rrc_fit_columns treats as not usable, ascending
+    (include/oip_c.h: oip_rrc_dead_columns)"""
+    lib = load_library()
+    a = np.ascontiguousarray(acc, dtype=np.uint64)
+    assert a.ndim == 2 and a.shape[0] == 3, a.shape
+    w = a.shape[1]
+    cols, n = np.zeros(w, np.int32), _i()
+    rc = lib.oip_rrc_dead_columns(a.ctypes.data_as(C.POINTER(C.c_uint64)), w, RRCFIT_MODES.get(mode, mode), min_count,
+                                  cols.ctypes.data_as(C.POINTER(_i)), C.byref(n))
+    if rc:
+        raise ValueError("oip_rrc_dead_columns: bad argument")
+    return cols[:n.value].copy()
+
+
+def load_column_list(path: str, w: int, cap: int = None) -> np.ndarray:
+    """the sorted, unique 0-based columns of a bad-column text file for a w-sample line (include/oip_c.h: oip_load_column_list)"""
+    lib = load_library()
+    cap = w if cap is None else cap
+    cols, n = np.zeros(max(cap, 1), np.int32), _i()
+    err = C.create_string_buffer(2048)
+    rc = lib.oip_load_column_list(os.fsencode(path), w, cols.ctypes.data_as(C.POINTER(_i)), cap, C.byref(n), err, 2048)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    return cols[:n.value].copy()
+
+
+def write_column_list(path: str, cols, comment: str = "") -> None:
+    """`# comment`, then one column index per line (include/oip_c.h: oip_write_column_list)"""
+    lib = load_library()
+    c = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+    err = C.create_string_buffer(2048)
+    rc = lib.oip_write_column_list(os.fsencode(path), c.ctypes.data_as(C.POINTER(_i)), c.size, comment.encode(), err, 2048)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+
+
+def despike_column_table(bad, w: int, groups: int = 1):
+    """((w, 2) int32 table of (Lx, Rx) per column, longest run of adjacent listed columns) for Context.despike_u16
+    (include/oip_c.h: oip_despike_column_table)"""
+    lib = load_library()
+    b = np.ascontiguousarray(bad, dtype=np.int32).reshape(-1)
+    tab, run = np.zeros((max(w, 1), 2), np.int32), _i()
+    err = C.create_string_buffer(1024)
+    rc = lib.oip_despike_column_table(b.ctypes.data_as(C.POINTER(_i)), b.size, w, groups, tab.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      C.byref(run), err, 1024)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    return tab, run.value
 
 
 SEAM_MODES = {"moments": 0, "gain": 1, "offset": 2}
@@ -682,6 +738,18 @@ class Context:
         out_rows = L if out_rows is None else out_rows
         self._ck(self.lib.oip_convolve_u16(self.h, _ptr(src), src_row0, src_rows, _ptr(dst), out_row0, out_rows, W, L, spp,
                                            t.ctypes.data_as(C.POINTER(C.c_int32)), t.shape[0], t.shape[1], valid_min))
+
+    # -- despike
+    def despike_u16(self, src, dst, W, L, spp, thr_abs, thr_rel_q8=0, valid_min=1, groups=1, coltab=None, count=None,
+                    src_row0=0, src_rows=None, out_row0=0, out_rows=None):
+        """column repair (coltab: (W, 2) int32 on the device, or None) and the conditional 3 x 3 median of lines
+        [out_row0, out_row0 + out_rows) of the W x L x spp raster whose lines [src_row0, src_row0 + src_rows) are at src; the
+        replacements per sample column are ADDED into count ((W * spp,) uint64 on the device, or None); not in place
+        (include/oip_c.h: oip_despike_u16)"""
+        src_rows = L if src_rows is None else src_rows
+        out_rows = L if out_rows is None else out_rows
+        self._ck(self.lib.oip_despike_u16(self.h, _ptr(src), src_row0, src_rows, _ptr(dst), out_row0, out_rows, W, L, spp, groups,
+                                          _ptr(coltab), thr_abs, thr_rel_q8, valid_min, _ptr(count)))
 
     # -- instrumentation
     def merge_subimages_be16(self, tiles, out, vparts, hparts, sub_lines, sub_cols):

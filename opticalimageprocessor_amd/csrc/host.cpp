@@ -1,7 +1,8 @@
 // host.cpp -- host-side pieces of the path that carry no raster arithmetic:
 // the RRC parameter file loader, its counterpart (column fit + writer), the seam fit of `oip stitch --balance`, the shift
 // filtering / polynomial fit, the contrast stretch of `oip quicklook` (percentile limits, 8-bit table, 8-bit TIFF) and the
-// taps of `oip mtfc` (design, quantisation, kernel file).
+// taps of `oip mtfc` (design, quantisation, kernel file) and the column lists and column table of `oip despike`.
+#include <algorithm>
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -55,6 +56,21 @@ extern "C" int oip_load_rrc_param_file(const char *path, int expected_lines, dou
     return OIP_OK;
 }
 
+// Is column x of the totals usable for the fit?  The ONE statement of the rule: oip_rrc_fit_columns fits the columns it
+// accepts, oip_rrc_dead_columns lists the ones it refuses.  D (may be NULL) receives n*S2 - S1*S1 of a usable column in
+// moments mode.
+static bool rrc_column_usable(const uint64_t *acc, int w, int x, bool moments, uint64_t min_count, unsigned __int128 *D)
+{
+    const uint64_t need = min_count > (moments ? 2u : 1u) ? min_count : (moments ? 2u : 1u);
+    const uint64_t n = acc[x], S1 = acc[(size_t)w + x], S2 = acc[2 * (size_t)w + x];
+    if (n < need) return false;
+    if (!moments) return S1 != 0;
+    const unsigned __int128 a = (unsigned __int128)n * S2, b = (unsigned __int128)S1 * S1;
+    if (a <= b) return false;                                      // D == 0: a constant column (a < b cannot come from real totals)
+    if (D) *D = a - b;
+    return true;
+}
+
 // Moment matching on the per-column totals of oip_colstats_u16 (include/oip_c.h states the operation order; a Python
 // restatement in tests/_colstats_ref.py follows it step by step).  Every step is one correctly rounded fp64
 // operation: the 128-bit D converts to the nearest double, S1 < 2^47 and n < 2^53 convert exactly.
@@ -68,9 +84,8 @@ extern "C" int oip_rrc_fit_columns(const uint64_t *acc, int w, int groups, int m
     if (!acc || !kb_out || w <= 0 || groups <= 0 || w % groups != 0 || (mode != OIP_RRCFIT_MOMENTS && mode != OIP_RRCFIT_GAIN))
         return fail(OIP_E_INVALID, "%s", "oip_rrc_fit_columns: bad argument");
     const bool moments = mode == OIP_RRCFIT_MOMENTS;
-    const uint64_t need = min_count > (moments ? 2u : 1u) ? min_count : (moments ? 2u : 1u);
     const int gw = w / groups;
-    const uint64_t *N = acc, *S1 = acc + w, *S2 = acc + 2 * (size_t)w;
+    const uint64_t *N = acc, *S1 = acc + w;
     std::vector<double> mu(gw), sigma(gw);
     std::vector<char> usable(gw);
     for (int g = 0; g < groups; ++g) {
@@ -78,20 +93,14 @@ extern "C" int oip_rrc_fit_columns(const uint64_t *acc, int w, int groups, int m
         int count = 0;
         for (int i = 0; i < gw; ++i) {
             const int x = g * gw + i;
-            usable[i] = 0;
-            if (N[x] < need) continue;
+            unsigned __int128 D = 0;
+            usable[i] = rrc_column_usable(acc, w, x, moments, min_count, &D);
+            if (!usable[i]) continue;
+            mu[i] = (double)S1[x] / (double)N[x];
             if (moments) {
-                const unsigned __int128 a = (unsigned __int128)N[x] * S2[x], b = (unsigned __int128)S1[x] * S1[x];
-                if (a <= b) continue;                                  // D == 0: a constant column (a < b cannot come from real totals)
-                const unsigned __int128 D = a - b;
-                mu[i] = (double)S1[x] / (double)N[x];
                 sigma[i] = std::sqrt((double)D) / (double)N[x];
                 sigmaSum += sigma[i];
-            } else {
-                if (S1[x] == 0) continue;
-                mu[i] = (double)S1[x] / (double)N[x];
             }
-            usable[i] = 1;
             muSum += mu[i];
             ++count;
         }
@@ -114,6 +123,16 @@ extern "C" int oip_rrc_fit_columns(const uint64_t *acc, int w, int groups, int m
         if (dead_out) dead_out[g] = gw - count;
         if (ref_out) { ref_out[2 * g] = muRef; ref_out[2 * g + 1] = sigmaRef; }
     }
+    return OIP_OK;
+}
+
+extern "C" int oip_rrc_dead_columns(const uint64_t *acc, int w, int mode, uint64_t min_count, int *cols, int *n)
+{
+    if (!acc || !cols || !n || w <= 0 || (mode != OIP_RRCFIT_MOMENTS && mode != OIP_RRCFIT_GAIN)) return OIP_E_INVALID;
+    int k = 0;
+    for (int x = 0; x < w; ++x)
+        if (!rrc_column_usable(acc, w, x, mode == OIP_RRCFIT_MOMENTS, min_count, nullptr)) cols[k++] = x;
+    *n = k;
     return OIP_OK;
 }
 
@@ -613,5 +632,107 @@ extern "C" int oip_mtfc_load_kernel(const char *path, double *c, int *ky, int *k
     if (*p) return fail(OIP_E_INVALID, "kernel file [%s] invalid: text behind the %d numbers", path, n);
     *ky = (int)dims[0];
     *kx = (int)dims[1];
+    return OIP_OK;
+}
+
+// ---- oip despike, host side: the list of bad columns (a text file) and the (Lx, Rx) table oip_despike_u16 reads
+// (include/oip_c.h states both; tests/_despike_ref.py restates them) ---------------------------------------------------------
+extern "C" int oip_load_column_list(const char *path, int w, int *cols, int cap, int *n, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *fmt, auto... a) {
+        if (err && errlen > 0) snprintf(err, errlen, fmt, a...);
+        return code;
+    };
+    if (!path || w <= 0 || cap < 0 || (!cols && cap > 0) || !n) return fail(OIP_E_INVALID, "%s", "oip_load_column_list: bad argument");
+    FILE *f = fopen(path, "rb");
+    if (!f) return fail(OIP_E_IO, "open column list [%s] failed: %s", path, strerror(errno));
+    const size_t limit = (size_t)16 << 20;                        // twelve bytes a column of the widest line is far below
+    std::string text;
+    char buff[4096];
+    size_t got = 0;
+    while (text.size() <= limit && (got = fread(buff, 1, sizeof buff, f)) > 0) text.append(buff, got);
+    const bool bad = ferror(f) != 0;
+    fclose(f);
+    if (bad) return fail(OIP_E_IO, "read of column list [%s] failed", path);
+    if (text.size() > limit || text.find('\0') != std::string::npos) return fail(OIP_E_INVALID, "column list [%s] invalid: not a text file of that kind", path);
+    std::vector<int> list;
+    const char *p = text.c_str();
+    for (;;) {
+        while (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r' || *p == '\f' || *p == '\v') ++p;
+        if (*p == '#') {                                           // a comment runs to the end of the line
+            while (*p && *p != '\n') ++p;
+            continue;
+        }
+        if (!*p) break;
+        const char *t = p;
+        while (*p && *p != '#' && *p != ' ' && *p != '\t' && *p != '\n' && *p != '\r' && *p != '\f' && *p != '\v') ++p;
+        const std::string tok(t, p);
+        const char *d = tok.c_str();
+        if (*d == '+' || *d == '-') ++d;
+        if (!*d || strspn(d, "0123456789") != strlen(d)) return fail(OIP_E_INVALID, "column list [%s] invalid: `%.32s' is not a number", path, tok.c_str());
+        errno = 0;
+        const long v = strtol(tok.c_str(), nullptr, 10);
+        if (errno == ERANGE || v < 0 || v >= w) return fail(OIP_E_INVALID, "column list [%s] invalid: column %.32s outside [0, %d)", path, tok.c_str(), w);
+        list.push_back((int)v);
+    }
+    std::sort(list.begin(), list.end());
+    list.erase(std::unique(list.begin(), list.end()), list.end());
+    if (list.size() > (size_t)cap) return fail(OIP_E_INVALID, "column list [%s] invalid: %zu columns, room for %d", path, list.size(), cap);
+    for (size_t i = 0; i < list.size(); ++i) cols[i] = list[i];
+    *n = (int)list.size();
+    return OIP_OK;
+}
+
+extern "C" int oip_write_column_list(const char *path, const int *cols, int n, const char *comment, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *fmt, auto... a) {
+        if (err && errlen > 0) snprintf(err, errlen, fmt, a...);
+        return code;
+    };
+    if (!path || n < 0 || (!cols && n > 0)) return fail(OIP_E_INVALID, "%s", "oip_write_column_list: bad argument");
+    FILE *f = fopen(path, "wb");
+    if (!f) return fail(OIP_E_IO, "open column list [%s] for writing failed: %s", path, strerror(errno));
+    std::string head = comment ? comment : "";
+    for (char &c : head)
+        if (c == '\n' || c == '\r') c = ' ';                        // the comment stays one line
+    bool ok = fprintf(f, "# %s\n", head.c_str()) > 0;
+    for (int i = 0; i < n && ok; ++i) ok = fprintf(f, "%d\n", cols[i]) > 0;
+    ok = fclose(f) == 0 && ok;
+    if (!ok) return fail(OIP_E_IO, "write of column list [%s] failed", path);
+    return OIP_OK;
+}
+
+extern "C" int oip_despike_column_table(const int *bad, int nbad, int w, int groups, int32_t *tab, int *longest_run, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *fmt, auto... a) {
+        if (err && errlen > 0) snprintf(err, errlen, fmt, a...);
+        return code;
+    };
+    if (!tab || nbad < 0 || (!bad && nbad > 0) || w <= 0 || (groups != 1 && groups != 4) || w % groups != 0)
+        return fail(OIP_E_INVALID, "%s", "oip_despike_column_table: bad argument");
+    std::vector<char> isBad((size_t)w, 0);
+    for (int i = 0; i < nbad; ++i) {
+        if (bad[i] < 0 || bad[i] >= w) return fail(OIP_E_INVALID, "oip_despike_column_table: column %d outside [0, %d)", bad[i], w);
+        isBad[bad[i]] = 1;
+    }
+    const int gw = w / groups;
+    int longest = 0;
+    for (int g = 0; g < groups; ++g) {
+        const int g0 = g * gw, g1 = g0 + gw;
+        int good = -1, run = 0;                                     // the nearest good column on the left, inside the group
+        for (int x = g0; x < g1; ++x) {
+            if (!isBad[x]) { good = x; run = 0; }
+            else if (++run > longest) longest = run;
+            tab[2 * (size_t)x] = good;
+        }
+        if (good < 0) return fail(OIP_E_INVALID, "oip_despike_column_table: group %d has no good column", g);
+        good = -1;
+        for (int x = g1 - 1; x >= g0; --x) {                        // ... and on the right; a missing side copies the other
+            if (!isBad[x]) good = x;
+            tab[2 * (size_t)x + 1] = good >= 0 ? good : tab[2 * (size_t)x];
+            if (tab[2 * (size_t)x] < 0) tab[2 * (size_t)x] = tab[2 * (size_t)x + 1];
+        }
+    }
+    if (longest_run) *longest_run = longest;
     return OIP_OK;
 }

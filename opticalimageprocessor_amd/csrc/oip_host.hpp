@@ -1557,6 +1557,7 @@ struct RrcCalibOptions {
     long minCount = 0;
     long lineOffset = 0, lines = 0;         // lines == 0: to the end of the file
     bool force = false;
+    std::string badPan, badMss;             // --bad-pan / --bad-mss: the columns the fit refuses, as `oip despike --bad-columns` reads them
 };
 
 // the lines [first, first + count) of `file` that a calibration uses; CheckFilesAttributes' size rule (preproc.h:552-572)
@@ -1573,8 +1574,9 @@ inline void RrcCalibLineRange(const std::string &file, const char *what, const R
 
 // The strip is never resident: line blocks go file -> pinned ring -> one of two device blocks, the statistics kernel of a
 // block runs behind its upload (ticket) while the host reads the next block from the file into the pinned ring.  `groups`
-// equal column groups.  Returns the fitted W (k, b) pairs; nothing is written here.
-inline std::vector<double> RrcCalibImage(const std::string &file, const char *what, int groups, const RrcCalibOptions &o)
+// equal column groups.  Returns the fitted W (k, b) pairs, and in `deadCols` (may be NULL) the columns the fit refused;
+// nothing is written here.
+inline std::vector<double> RrcCalibImage(const std::string &file, const char *what, int groups, const RrcCalibOptions &o, std::vector<int> *deadCols = nullptr)
 {
     const int W = o.width, gw = W / groups;
     long first = 0, nLines = 0;
@@ -1627,6 +1629,12 @@ inline std::vector<double> RrcCalibImage(const std::string &file, const char *wh
              groups > 1 ? (" band " + std::to_string(g + 1)).c_str() : "", nLines, gw - dead[g], dead[g], ref[2 * g], ref[2 * g + 1], kmin, kmax, bmin,
              bmax);
     }
+    if (deadCols) {
+        deadCols->resize(W);
+        int n = 0;
+        if (oip_rrc_dead_columns(totals.data(), W, o.mode, (uint64_t)o.minCount, deadCols->data(), &n) != OIP_OK) throw std::invalid_argument("oip_rrc_dead_columns: bad argument");
+        deadCols->resize(n);
+    }
     return kb;
 }
 
@@ -1640,6 +1648,8 @@ inline void RrcCalibCheck(const std::string &pan, const std::string &mss, const 
     std::vector<std::string> outs;
     if (!pan.empty()) outs.push_back(outPan);
     for (int i = 0; i < MSS_BANDS && !mss.empty(); ++i) outs.push_back(outMss[i]);
+    if (!o.badPan.empty()) outs.push_back(o.badPan);
+    if (!o.badMss.empty()) outs.push_back(o.badMss);
     for (size_t i = 0; i < outs.size(); ++i)
         for (size_t j = i + 1; j < outs.size(); ++j)
             if (outs[i] == outs[j] || (std::filesystem::exists(outs[i]) && std::filesystem::exists(outs[j]) && std::filesystem::equivalent(outs[i], outs[j])))
@@ -1655,8 +1665,9 @@ inline void RunRrcCalib(const std::string &pan, const std::string &mss, const st
     RrcCalibCheck(pan, mss, outPan, outMss, o);
     // every image and group is fitted before the first file is written: a band without a usable column leaves no partial set
     std::vector<double> kbPan, kbMss;
-    if (!pan.empty()) kbPan = RrcCalibImage(pan, "PAN", 1, o);
-    if (!mss.empty()) kbMss = RrcCalibImage(mss, "MSS", MSS_BANDS, o);
+    std::vector<int> deadPan, deadMss;
+    if (!pan.empty()) kbPan = RrcCalibImage(pan, "PAN", 1, o, o.badPan.empty() ? nullptr : &deadPan);
+    if (!mss.empty()) kbMss = RrcCalibImage(mss, "MSS", MSS_BANDS, o, o.badMss.empty() ? nullptr : &deadMss);
     auto write = [](const std::string &path, const double *kb, int n) {
         char err[1024] = "";
         if (oip_write_rrc_param_file(path.c_str(), kb, n, err, sizeof err) != OIP_OK) throw errno_error(err, 0);
@@ -1665,6 +1676,16 @@ inline void RunRrcCalib(const std::string &pan, const std::string &mss, const st
     if (!pan.empty()) write(outPan, kbPan.data(), o.width);
     const int bw = o.width / MSS_BANDS;
     for (int b = 0; b < MSS_BANDS && !mss.empty(); ++b) write(outMss[b], &kbMss[2 * (size_t)b * bw], bw);
+    // the columns the fit refused, behind the coefficient files: the list `oip despike --bad-columns` reads
+    auto writeList = [&](const std::string &path, const std::vector<int> &cols, const std::string &image) {
+        char err[1024] = "";
+        const std::string comment = "columns of " + image + " (" + std::to_string(o.width) + " samples per line) without usable statistics: oip rrc-calib --mode " +
+                                    (o.mode == OIP_RRCFIT_MOMENTS ? "moments" : "gain");
+        if (oip_write_column_list(path.c_str(), cols.data(), (int)cols.size(), comment.c_str(), err, sizeof err) != OIP_OK) throw errno_error(err, 0);
+        OLOG("%zu bad columns written to file [%s].", cols.size(), path.c_str());
+    };
+    if (!o.badPan.empty()) writeList(o.badPan, deadPan, pan);
+    if (!o.badMss.empty()) writeList(o.badMss, deadMss, mss);
 }
 
 // ---- oip quicklook: an 8-bit browse image of a strip or product ---------------------------------------------
@@ -1952,6 +1973,190 @@ inline void RunMtfc(const std::string &file, const std::string &out, const MtfcO
         }
         writer.finish();
         bytes = (size_t)L * lineBytes;
+    }
+    const double es = total.tick();
+    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+}
+
+// ---- oip despike: repair of a raw strip ahead of RRC ------------------------------------------------------------------
+// Listed bad columns are interpolated and isolated impulse pixels replaced by a conditional 3 x 3 median (oip_despike_u16)
+// before RRC multiplies them and a resampling spreads them.  The list comes from `oip rrc-calib --bad-pan / --bad-mss` or
+// from a --report of an earlier run.  The output has the container of the input.  Not in the reference.
+struct DespikeOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    bool bil = false;                       // RAW input: the MSS line layout, 4 bands of width / 4 next to each other
+    bool hasThreshold = false;              // without --threshold: column repair only (thr_abs 65535)
+    int thrAbs = 65535, thrRelQ8 = 0;
+    int validMin = 1;                       // 0 is what the de-framer writes for missing frames
+    std::string badColumns, report;
+    bool force = false;
+};
+
+struct DespikeTable {
+    std::vector<int32_t> tab;               // empty: no list
+    int listed = 0, longestRun = 0;
+};
+
+// everything that can be refused without a device: the container, sizes, the list and its table, the outputs; returns the output path
+inline std::string DespikeCheck(const std::string &file, const std::string &out, const DespikeOptions &o, bool *isTiff, DespikeTable *table)
+{
+    const std::string ext = to_lower(std::filesystem::path(file).extension().string());
+    if (ext != ".tiff" && ext != ".raw") throw std::invalid_argument("despike: only RAW and TIFF image supported");
+    *isTiff = ext == ".tiff";
+    if (*isTiff) {
+        if (!o.badColumns.empty() || o.bil)
+            throw std::invalid_argument("despike: --bad-columns and --bil apply to a RAW strip: the columns of a TIFF product are no longer detector columns");
+    } else {
+        if (o.width <= 0 || (o.bil && o.width % MSS_BANDS != 0)) throw std::invalid_argument("--width: a positive line width (a multiple of 4 with --bil) expected");
+        const size_t size = IMO::FileSize(file), lineBytes = (size_t)o.width * BYTES_PER_PIXEL;
+        if (size == 0 || size % lineBytes != 0)
+            throw std::invalid_argument("image file size invalid: should be multiplies of " + std::to_string(lineBytes));
+    }
+    if (!o.badColumns.empty()) {
+        const int W = o.width;
+        std::vector<int> cols(W);
+        char err[1024] = "";
+        int n = 0;
+        int rc = oip_load_column_list(o.badColumns.c_str(), W, cols.data(), W, &n, err, sizeof err);
+        if (rc == OIP_E_IO) throw errno_error(err, 0);
+        if (rc != OIP_OK) throw std::invalid_argument(err);
+        table->tab.resize((size_t)2 * W);
+        rc = oip_despike_column_table(cols.data(), n, W, o.bil ? MSS_BANDS : 1, table->tab.data(), &table->longestRun, err, sizeof err);
+        if (rc != OIP_OK) throw std::invalid_argument(err);
+        table->listed = n;
+    }
+    const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_DESPIKE_SUFFIX) : out;
+    if (to_lower(std::filesystem::path(path).extension().string()) != ext) throw std::invalid_argument("despike: the output has the container of the input (" + ext + ")");
+    struct stat st;
+    if (stat(path.c_str(), &st) == 0) {
+        if (std::filesystem::equivalent(path, file)) throw std::invalid_argument("output file [" + path + "] is the input image");
+        if (!o.force) throw std::runtime_error("output file [" + path + "] exists: despike does not replace a file without --force");
+    }
+    if (!o.report.empty()) {
+        const bool exists = stat(o.report.c_str(), &st) == 0;
+        const bool same = std::filesystem::absolute(o.report).lexically_normal() == std::filesystem::absolute(path).lexically_normal();
+        if (same || (exists && (std::filesystem::equivalent(o.report, file) || (stat(path.c_str(), &st) == 0 && std::filesystem::equivalent(o.report, path)))))
+            throw std::invalid_argument("report file [" + o.report + "] is the input image or the output");
+        if (exists && !o.force) throw std::runtime_error("report file [" + o.report + "] exists: despike does not replace a file without --force");
+    }
+    return path;
+}
+
+inline void RunDespike(const std::string &file, const std::string &out, const DespikeOptions &o)
+{
+    bool isTiff = false;
+    DespikeTable table;
+    const std::string outPath = DespikeCheck(file, out, o, &isTiff, &table);
+    if (o.hasThreshold) OLOG("despike: threshold %d + %d / 256 of the median, valid-min %d", o.thrAbs, o.thrRelQ8, o.validMin);
+    else OLOG("despike: column repair only (no --threshold), valid-min %d", o.validMin);
+    if (!o.badColumns.empty()) OLOG("%d bad columns listed in [%s], longest run %d", table.listed, o.badColumns.c_str(), table.longestRun);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    size_t bytes = 0;
+    DevBuf<uint64_t> cnt;                                               // replacements per sample column; only a threshold replaces
+    std::vector<uint64_t> counts;
+    auto alloc_counts = [&](size_t n) {
+        if (!o.hasThreshold) return;
+        cnt.alloc(n);
+        ck(oip_memset(ctx, cnt.p, 0, n * sizeof(uint64_t)));
+        counts.resize(n);
+    };
+    if (isTiff) {
+        // a product is processed resident and leaves through the product writer of `oip stitch`
+        int w = 0, spp = 0;
+        long h = 0;
+        DevBuf<uint16_t> img;
+        OLOG("Reading image from file `%s' ...", file.c_str());
+        read_tiff_to_device(file, &w, &h, &spp, img);
+        if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument("despike: a TIFF of 1 or 4 samples per pixel expected");
+        DevBuf<uint16_t> res((size_t)w * h * spp);
+        alloc_counts((size_t)w * spp);
+        ck(oip_despike_u16(ctx, img.p, 0, h, res.p, 0, h, w, h, spp, 1, nullptr, o.thrAbs, o.thrRelQ8, o.validMin, cnt.p));
+        OLOG("Write repaired image to file '%s' ...", outPath.c_str());
+        write_tiff_from_device(outPath, res.p, w, h, spp, tiff_compression(spp == 1 ? TIFF_NONE : TIFF_LZW), false);
+        bytes = (size_t)w * h * spp * BYTES_PER_PIXEL;
+    } else {
+        // The strip is never resident: line blocks with one halo line either side go file -> pinned ring -> one of two device
+        // blocks, the kernel of a block runs behind its upload (ticket), and its output goes from one of two device blocks to its
+        // byte offset in the product on a writer thread behind a compute mark, as RunMtfc does it: read || kernel || write.
+        const int W = o.width;
+        const size_t lineBytes = (size_t)W * BYTES_PER_PIXEL;
+        const long L = (long)(IMO::FileSize(file) / lineBytes);
+        long blockLines = std::max<long>(1, (long)(((size_t)64 << 20) / lineBytes));
+        if (const char *e = getenv("OIP_DESPIKE_BLOCK_LINES")) {          // test hook: several blocks on a small image
+            const long v = atol(e);
+            if (v > 0) blockLines = v;
+        }
+        const long cap = std::min(blockLines, L);
+        DevBuf<uint16_t> in[2], res[2];
+        for (int i = 0; i < 2 && (long)i * blockLines < L; ++i) {
+            in[i].alloc((size_t)std::min(cap + 2, L) * W);
+            res[i].alloc((size_t)cap * W);
+        }
+        DevBuf<int32_t> tab;
+        if (!table.tab.empty()) {
+            tab.alloc(table.tab.size());
+            tab.upload(table.tab.data(), table.tab.size());
+        }
+        alloc_counts((size_t)W);
+        { FILE *f = fopen(outPath.c_str(), "wb"); if (!f) throw std::runtime_error("open file [" + outPath + "] failed: " + std::to_string(errno)); fclose(f); }
+        OLOG("Reading raw image from file `%s' ...", file.c_str());
+        std::future<void> written[2];
+        JobThread writer;                                               // (declared after the buffers: joined before they are released)
+        long block = 0;
+        for (long r = 0; r < L; r += blockLines, ++block) {
+            const long m = std::min(blockLines, L - r);
+            const long s0 = std::max<long>(0, r - 1), s1 = std::min(L, r + m + 1);
+            uint16_t *d = in[block & 1].p, *q = res[block & 1].p;
+            if (block >= 2) ck(oip_stage_order_after_compute(ctx));     // the kernel that read this buffer two blocks ago goes first
+            size_t got = 0;
+            long ticket = 0;
+            ck(oip_read_file_to_device(ctx, file.c_str(), (size_t)s0 * lineBytes, (size_t)(s1 - s0) * lineBytes, d, &got, &ticket));
+            if (got != (size_t)(s1 - s0) * lineBytes)
+                throw std::runtime_error("file size(" + std::to_string((size_t)s1 * lineBytes) + ") doesn't match with read byte count(" +
+                                         std::to_string((size_t)s0 * lineBytes + got) + ")");
+            ck(oip_stage_wait(ctx, ticket));
+            if (written[block & 1].valid()) {                           // the output block of two blocks ago is in the file
+                try { written[block & 1].get(); } catch (const std::future_error &) { writer.finish(); throw; }      // (a failed writer drops its jobs)
+            }
+            ck(oip_despike_u16(ctx, d, s0, s1 - s0, q, r, m, W, L, 1, o.bil ? MSS_BANDS : 1, tab.p, o.thrAbs, o.thrRelQ8, o.validMin, cnt.p));
+            long mark = 0;
+            ck(oip_compute_mark(ctx, &mark));
+            auto done = std::make_shared<std::promise<void>>();
+            written[block & 1] = done->get_future();
+            const size_t nb = (size_t)m * lineBytes, off = (size_t)r * lineBytes;
+            writer.post([=] {
+                const int rc = oip_write_device_to_file_at(ctx, q, nb, outPath.c_str(), off, mark);
+                done->set_value();                                      // the buffer is free either way; finish() reports a failure
+                Device::get().check(rc);
+            });
+        }
+        writer.finish();
+        bytes = (size_t)L * lineBytes;
+    }
+    if (o.hasThreshold) {
+        cnt.download(counts.data(), counts.size());                     // (synchronises: the last kernel has run)
+        uint64_t sum = 0;
+        std::vector<size_t> hit;
+        for (size_t x = 0; x < counts.size(); ++x)
+            if (counts[x]) { sum += counts[x]; hit.push_back(x); }
+        OLOG("%llu samples replaced in %zu of %zu columns", (unsigned long long)sum, hit.size(), counts.size());
+        if (!o.report.empty()) {
+            FILE *f = fopen(o.report.c_str(), "wb");
+            if (!f) throw std::runtime_error("open file [" + o.report + "] failed: " + std::to_string(errno));
+            fprintf(f, "# column count: samples replaced by oip despike --threshold %d in %s\n", o.thrAbs, file.c_str());
+            for (size_t x : hit) fprintf(f, "%zu %llu\n", x, (unsigned long long)counts[x]);
+            if (fclose(f) != 0) throw std::runtime_error("write of file [" + o.report + "] failed");
+            OLOG("Replacement counts written to file [%s].", o.report.c_str());
+        }
+        std::stable_sort(hit.begin(), hit.end(), [&](size_t a, size_t b) { return counts[a] > counts[b]; });
+        for (size_t i = 0; i < hit.size() && i < 10; ++i) RLOG("    column %zu: %llu", hit[i], (unsigned long long)counts[hit[i]]);
+    } else if (!o.report.empty()) {
+        FILE *f = fopen(o.report.c_str(), "wb");
+        if (!f) throw std::runtime_error("open file [" + o.report + "] failed: " + std::to_string(errno));
+        fprintf(f, "# column count: no --threshold, no sample replaced in %s\n", file.c_str());
+        fclose(f);
     }
     const double es = total.tick();
     OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);

@@ -11,11 +11,14 @@
 //                               actions above read from a strip's per-column statistics, see run_rrc_calib()
 //   oip quicklook IMAGE [-o OUT.TIFF] [--factor 16 ...]   8-bit browse image of a strip or product, see run_quicklook()
 //   oip mtfc IMAGE [-o OUT] (--kernel FILE | --mtf-x M --mtf-y M)   MTF-compensation filter of a strip or product, see run_mtfc()
+//   oip despike IMAGE [-o OUT] [--threshold N] [--relative R] [--bad-columns FILE] [--bil]   repair of a raw strip ahead of RRC:
+//                               bad columns interpolated, impulse pixels replaced by a conditional 3 x 3 median, see run_despike()
 //   oip -v | --version          prints 1.1
 // plus --width N (pixels per PAN line; the reference hard-codes 12288, oipshared.h:28).
 // `auxsep` is outside this build.  TIFF input and output go through oip_tiff.hpp (uncompressed and LZW, with
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
-// (--balance, --feather and their --valid-min / --valid-max / --min-count) and the rrc-calib, quicklook and mtfc sub-commands.
+// (--balance, --feather and their --valid-min / --valid-max / --min-count) and the rrc-calib, quicklook, mtfc and despike
+// sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -144,6 +147,7 @@ void usage()
          "             [--pan FILE --rrc-pan OUT] [--mss FILE --rrc-msb1 OUT --rrc-msb2 OUT --rrc-msb3 OUT --rrc-msb4 OUT]\n"
          "             [--mode moments|gain] [--valid-min N] [--valid-max N] [--min-count N]\n"
          "             [--line-offset N] [--lines N] (of each image's own lines) [--force] (replace existing OUT files)\n"
+         "             [--bad-pan OUT] [--bad-mss OUT] the columns without usable statistics (dead detectors), as despike --bad-columns reads them\n"
          "  quicklook  IMAGE.RAW|IMAGE.TIFF: an 8-bit browse image, box-decimated by --factor and contrast-stretched per band\n"
          "             between two percentiles of its valid samples; written to <stem>.QL.TIFF in the working directory:\n"
          "             [-o,--out FILE] [--factor 2|4|8|16|32|64] [--clip-low P] [--clip-high P] [--valid-min N] [--valid-max N]\n"
@@ -152,7 +156,14 @@ void usage()
          "             the container of the input and is written to <stem>.MTFC.<ext> in the working directory:\n"
          "             [-o,--out FILE] --kernel FILE (text: `ky kx', then ky rows of kx coefficients summing to 1)\n"
          "             | --mtf-x M --mtf-y M (the MTF at Nyquist across / along the lines, 0 < M <= 1) [--max-gain G] (default 2.0)\n"
-         "             [--valid-min N] (samples below are no data and pass through; default 1) [--width N] [--force]");
+         "             [--valid-min N] (samples below are no data and pass through; default 1) [--width N] [--force]\n"
+         "  despike    IMAGE.RAW|IMAGE.TIFF: repair of a raw strip ahead of RRC; the output has the container of the input and is\n"
+         "             written to <stem>.DSPK.<ext> in the working directory.  At least one of --threshold and --bad-columns:\n"
+         "             [-o,--out FILE] [--threshold N] a sample further than N (0..65535) + R * median from the median of its 3 x 3\n"
+         "             neighbourhood is replaced by it (there is no default: measure the sensor's noise) [--relative R] (0..1, default 0)\n"
+         "             [--bad-columns FILE] (RAW; text: 0-based columns, # comments) interpolated from their good neighbours\n"
+         "             [--bil] (RAW: the MSS line layout, bands never mix) [--valid-min N] (samples below are no data; default 1)\n"
+         "             [--width N] [--report FILE] (`column count' of the replaced samples) [--force]");
 }
 
 int run_prestitch(const std::vector<std::string> &args, int width)
@@ -407,9 +418,11 @@ int run_rrc_calib(const std::vector<std::string> &args, int width)
 {
     Spec sp;
     sp.valued = {"--pan", "--mss", "--rrc-pan", "--rrc-msb1", "--rrc-msb2", "--rrc-msb3", "--rrc-msb4", "--width", "--mode", "--valid-min",
-                 "--valid-max", "--min-count", "--line-offset", "--lines"};
+                 "--valid-max", "--min-count", "--line-offset", "--lines", "--bad-pan", "--bad-mss"};
     sp.flags = {"--force"};
     Parsed p = parse(sp, args);
+    if (p.has("--bad-pan") && !p.has("--pan")) throw cli_error(107, "--bad-pan requires --pan");             // a list comes with its image
+    if (p.has("--bad-mss") && !p.has("--mss")) throw cli_error(107, "--bad-mss requires --mss");
     const char *msbKeys[MSS_BANDS] = {"--rrc-msb1", "--rrc-msb2", "--rrc-msb3", "--rrc-msb4"};
     bool anyMsb = false;
     for (auto k : msbKeys) anyMsb = anyMsb || p.has(k);
@@ -434,6 +447,9 @@ int run_rrc_calib(const std::vector<std::string> &args, int width)
     o.lines = p.integer("--lines", 0);
     if (o.minCount < 0 || o.lineOffset < 0 || o.lines < 0) throw cli_error(105, "--min-count, --line-offset, --lines: non-negative values expected");
     o.force = p.flag.count("--force") != 0;
+    o.badPan = p.str("--bad-pan");
+    o.badMss = p.str("--bad-mss");
+    if ((p.has("--bad-pan") && o.badPan.empty()) || (p.has("--bad-mss") && o.badMss.empty())) throw cli_error(105, "--bad-pan, --bad-mss: a file name expected");
     const std::string msb[MSS_BANDS] = {p.str(msbKeys[0]), p.str(msbKeys[1]), p.str(msbKeys[2]), p.str(msbKeys[3])};
     RunRrcCalib(p.str("--pan"), p.str("--mss"), p.str("--rrc-pan"), msb, o);
     return 0;
@@ -532,6 +548,50 @@ int run_mtfc(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip despike IMAGE: column repair and the conditional 3 x 3 median of a strip (.RAW, --width samples per line, with --bil the
+// MSS line layout) or a product (.TIFF of 1 or 4 samples).  IMAGE is the one positional argument, as for mtfc.
+int run_despike(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--out", "--threshold", "--relative", "--bad-columns", "--valid-min", "--width", "--report"};
+    sp.flags = {"--bil", "--force"};
+    sp.alias = {{"-o", "--out"}};
+    std::string image;
+    std::vector<std::string> rest;
+    for (size_t i = 0; i < args.size(); ++i) {
+        const std::string &a = args[i];
+        if (!a.empty() && a[0] != '-' && image.empty()) { image = a; continue; }
+        rest.push_back(a);
+        auto al = sp.alias.find(a);
+        if (sp.valued.count(al != sp.alias.end() ? al->second : a) && i + 1 < args.size()) rest.push_back(args[++i]);
+    }
+    Parsed p = parse(sp, rest);
+    if (image.empty()) throw cli_error(106, "IMAGE is required");
+    struct stat st;
+    if (stat(image.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) throw cli_error(105, "IMAGE: File does not exist: " + image);
+    // nobody has measured this sensor's noise: there is no default threshold, and without one only the listed columns are repaired
+    if (!p.has("--threshold") && !p.has("--bad-columns")) throw usage_error("--threshold N or --bad-columns FILE expected");
+    if (p.has("--relative") && !p.has("--threshold")) throw cli_error(107, "--relative requires --threshold");
+    DespikeOptions o;
+    o.width = p.integer("--width", width);
+    o.bil = p.flag.count("--bil") != 0;
+    o.hasThreshold = p.has("--threshold");
+    o.thrAbs = p.integer("--threshold", 65535);
+    if (o.thrAbs < 0 || o.thrAbs > 65535) throw cli_error(105, "--threshold: 0 <= N <= 65535 expected");
+    const double rel = p.real("--relative", 0.0);
+    if (!(rel >= 0.0 && rel <= 1.0)) throw cli_error(105, "--relative: 0 <= R <= 1 expected");
+    o.thrRelQ8 = (int)std::rint(rel * 256.0);
+    o.validMin = p.integer("--valid-min", 1);
+    if (o.validMin < 0 || o.validMin > 65535) throw cli_error(105, "--valid-min: 0 <= N <= 65535 expected");
+    existing_file(p, "--bad-columns");
+    o.badColumns = p.str("--bad-columns");
+    if (p.has("--bad-columns") && o.badColumns.empty()) throw cli_error(105, "--bad-columns: a file name expected");
+    o.report = p.str("--report");
+    o.force = p.flag.count("--force") != 0;
+    RunDespike(image, p.str("--out"), o);
+    return 0;
+}
+
 }  // namespace
 
 static int oip_main(int argc, const char *argv[]);
@@ -581,6 +641,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "rrc-calib") return run_rrc_calib({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "quicklook") return run_quicklook({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "mtfc") return run_mtfc({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "despike") return run_despike({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "auxsep")
                 throw std::invalid_argument("auxsep (down-link de-framing) is outside this build: run the reference's auxsep, then this tool");
             if (args.empty()) { usage(); return 0; }

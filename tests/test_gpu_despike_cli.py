@@ -1,0 +1,160 @@
+"""GPU: `oip despike` end to end -- the product is the restatement's (_despike_ref.py) of the input file's samples, sample
+for sample, in the container of the input; the report holds the restatement's counts; and the bad-column list that
+`oip rrc-calib --bad-pan / --bad-mss` writes is the one `oip despike --bad-columns` fills."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import _despike_ref as ref
+from _tiff import read_tiff_u16, write_tiff_u16
+
+pytestmark = pytest.mark.gpu
+OIP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "opticalimageprocessor_amd", "lib", "oip")
+
+
+def _run(args, cwd, tool="despike", **env):
+    env = dict(os.environ, LOGFILE=os.path.join(cwd, "oip.log"), **env)
+    return subprocess.run([OIP, tool] + args, cwd=cwd, env=env, capture_output=True, text=True)
+
+
+def _strip(W, L, seed, spp=1):
+    """sensor-like data (a smooth scene with noise), 2 % impulse pixels, a few no-data samples and a de-framer gap"""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:L, 0:W * spp]
+    img = 1500 + 200 * np.sin(x / 17.0) + 3 * y + rng.integers(-20, 21, (L, W * spp))
+    hot = rng.random(img.shape) < 0.02
+    img[hot] += rng.choice([-900, 1200, 2500], int(hot.sum()))
+    img = np.clip(img, 1, 65535).astype(np.uint16)
+    img[rng.random(img.shape) < 0.01] = 0
+    img[L // 2:L // 2 + 6] = 0
+    return img
+
+
+def _report(path):
+    rows = [line.split() for line in open(path) if not line.startswith("#")]
+    return {int(c): int(n) for c, n in rows}
+
+
+def _counts(cnt):
+    return {int(x): int(cnt[x]) for x in np.flatnonzero(cnt)}
+
+
+def test_raw_pan_strip_in_several_line_blocks(tmp_path):
+    """96 x 50 with --threshold / --relative.  OIP_DESPIKE_BLOCK_LINES forces line blocks of 7 lines (the tool's own are
+    64 MiB): eight blocks, so both device blocks of either kind are reused, the halo line above and below a block comes from
+    the file, and the last block is a single line.  The default name, the report, then -o, --force and another valid-min."""
+    d = str(tmp_path)
+    W, L = 96, 50
+    img = _strip(W, L, 1)
+    img.tofile(os.path.join(d, "P.RAW"))
+    base = ["P.RAW", "--width", str(W), "--threshold", "150", "--relative", "0.125"]
+    r = _run(base + ["--report", "hits.txt"], d, OIP_DESPIKE_BLOCK_LINES="7")
+    assert r.returncode == 0, r.stdout + r.stderr
+    out = os.path.join(d, "P.DSPK.RAW")
+    want, cnt = ref.despike(img, 150, 32, 1)
+    assert 0.01 * img.size < cnt.sum() < 0.05 * img.size            # the impulses, not the scene
+    assert np.array_equal(np.fromfile(out, np.uint16).reshape(L, W), want)
+    assert not want[L // 2:L // 2 + 6].any()
+    assert _report(os.path.join(d, "hits.txt")) == _counts(cnt)
+    assert "%d samples replaced in %d of %d columns" % (cnt.sum(), np.count_nonzero(cnt), W) in r.stdout
+    top = re.findall(r"^ {4}column (\d+): (\d+)$", r.stdout, re.M)
+    assert len(top) == 10 and [int(n) for _, n in top] == sorted(cnt.astype(int).tolist(), reverse=True)[:10]
+    assert all(cnt[int(c)] == int(n) for c, n in top)
+    # one block gives the same bytes
+    r = _run(base + ["-o", "one.RAW"], d)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert open(os.path.join(d, "one.RAW"), "rb").read() == open(out, "rb").read()
+    # an existing output: refused, then replaced with --force (valid-min 0: another result)
+    r = _run(base + ["-o", "one.RAW", "--valid-min", "0"], d)
+    assert r.returncode == 2 and "--force" in r.stdout
+    assert open(os.path.join(d, "one.RAW"), "rb").read() == want.tobytes()
+    with open(os.path.join(d, "one.RAW"), "ab") as f:
+        f.write(b"longer than the product")
+    r = _run(base + ["-o", "one.RAW", "--valid-min", "0", "--force", "--report", "hits.txt"], d, OIP_DESPIKE_BLOCK_LINES="16")
+    assert r.returncode == 0, r.stdout + r.stderr
+    want0, cnt0 = ref.despike(img, 150, 32, 0)
+    assert open(os.path.join(d, "one.RAW"), "rb").read() == want0.tobytes() and not np.array_equal(want0, want)
+    assert _report(os.path.join(d, "hits.txt")) == _counts(cnt0)
+
+
+def test_raw_bil_strip_with_a_list(tmp_path):
+    """148 samples per line, four bands of 37: listed columns either side of a band border are filled from their own band,
+    the medians never cross it.  With and without --threshold (column repair only), in blocks of 7 lines and in one."""
+    d = str(tmp_path)
+    W, L = 148, 50
+    img = _strip(W, L, 2)
+    bad = [0, 36, 37, 50, 51, 52, 147]
+    img[:, bad] = 777                                               # stuck detectors
+    img.tofile(os.path.join(d, "M.RAW"))
+    open(os.path.join(d, "bad.txt"), "w").write("# stuck\n" + " ".join(str(c) for c in reversed(bad)) + " 36\n")
+    tab, run = ref.column_table(bad, W, 4)
+    base = ["M.RAW", "--width", str(W), "--bil", "--bad-columns", "bad.txt"]
+    r = _run(base + ["--threshold", "150", "--report", "hits.txt", "-o", "blocks.RAW"], d, OIP_DESPIKE_BLOCK_LINES="7")
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "%d bad columns listed" % len(bad) in r.stdout and "longest run %d" % run in r.stdout
+    want, cnt = ref.despike(img, 150, 0, 1, groups=4, coltab=tab)
+    assert open(os.path.join(d, "blocks.RAW"), "rb").read() == want.tobytes()
+    assert not np.array_equal(want, ref.despike(img, 150, 0, 1, groups=1, coltab=ref.column_table(bad, W, 1)[0])[0])
+    assert _report(os.path.join(d, "hits.txt")) == _counts(cnt)
+    r = _run(base + ["--threshold", "150"], d)                      # one block, the default name
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert open(os.path.join(d, "M.DSPK.RAW"), "rb").read() == want.tobytes()
+    # column repair only
+    r = _run(base + ["-o", "cols.RAW"], d, OIP_DESPIKE_BLOCK_LINES="7")
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "column repair only" in r.stdout
+    only, none = ref.despike(img, 65535, 0, 1, groups=4, coltab=tab)
+    got = np.fromfile(os.path.join(d, "cols.RAW"), np.uint16).reshape(L, W)
+    good = np.setdiff1d(np.arange(W), bad)
+    assert np.array_equal(got, only) and not none.any() and np.array_equal(got[:, good], img[:, good])
+    assert (got[:, bad] != 777).mean() > 0.9
+
+
+@pytest.mark.parametrize("spp,compress", [(1, "none"), (4, "none"), (4, "lzw")])
+def test_tiff_products(tmp_path, spp, compress):
+    d = str(tmp_path)
+    w, rows = 131, 60
+    img = _strip(w, rows, 3 + spp, spp)
+    write_tiff_u16(os.path.join(d, "A.TIFF"), img.reshape(rows, w, spp) if spp > 1 else img, lzw=compress == "lzw",
+                   predictor=2 if compress == "lzw" else 1, rows_per_strip=16 if compress == "lzw" else None)
+    r = _run(["A.TIFF", "--threshold", "150", "--report", "hits.txt", "--tiff-compress", compress], d)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = read_tiff_u16(os.path.join(d, "A.DSPK.TIFF"))[0]
+    want, cnt = ref.despike(img, 150, 0, 1, spp=spp)
+    assert cnt.sum() > 0 and np.array_equal(got.reshape(rows, -1), want)
+    assert _report(os.path.join(d, "hits.txt")) == _counts(cnt)
+
+
+@pytest.mark.parametrize("bil", [False, True])
+def test_calibration_lists_the_dead_columns_and_despike_fills_them(tmp_path, bil):
+    """rrc-calib on a strip with two constant columns lists exactly those two; despike fills them from their neighbours; a
+    second rrc-calib on the result finds no dead column"""
+    d = str(tmp_path)
+    W, L = 256, 400
+    rng = np.random.default_rng(9)
+    img = rng.integers(300, 3800, (L, W)).astype(np.uint16)
+    dead = [70, 200]
+    img[:, 70], img[:, 200] = 0, 2047
+    img.tofile(os.path.join(d, "S.RAW"))
+    outs = []
+    for b in range(4):
+        outs += ["--rrc-msb%d" % (b + 1), "m%d.csv" % (b + 1)]
+    calib = ["--width", str(W)] + (["--mss", "S.RAW", "--bad-mss", "bad.txt"] + outs if bil else ["--pan", "S.RAW", "--rrc-pan", "pan.csv", "--bad-pan", "bad.txt"])
+    r = _run(calib, d, "rrc-calib")
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "2 bad columns written" in r.stdout
+    assert ref.parse_column_list(os.path.join(d, "bad.txt"), W) == dead
+    assert open(os.path.join(d, "bad.txt")).readline().startswith("# ")
+    r = _run(["S.RAW", "--width", str(W), "--bad-columns", "bad.txt"] + (["--bil"] if bil else []), d)
+    assert r.returncode == 0, r.stdout + r.stderr
+    want = ref.despike(img, 65535, 0, 1, groups=4 if bil else 1, coltab=ref.column_table(dead, W, 4 if bil else 1)[0])[0]
+    assert open(os.path.join(d, "S.DSPK.RAW"), "rb").read() == want.tobytes()
+    again = ["--width", str(W), "--force"] + (["--mss", "S.DSPK.RAW", "--bad-mss", "bad2.txt"] + outs if bil else
+                                              ["--pan", "S.DSPK.RAW", "--rrc-pan", "pan.csv", "--bad-pan", "bad2.txt"])
+    r = _run(again, d, "rrc-calib")
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert " dead columns" in r.stdout and not re.search(r"/ [1-9]\d* dead columns", r.stdout)
+    assert ref.parse_column_list(os.path.join(d, "bad2.txt"), W) == []
