@@ -472,6 +472,53 @@ int oip_stitch_balanced_u16(oip_ctx *ctx, const uint16_t *d_left, const uint16_t
                             int fs, int spp, const int32_t *d_gain_q16, const int32_t *d_offset_q16, int feather,
                             int valid_min);
 
+/* -- gains that follow the strip (`oip stitch --balance-lines B`).  Over 100 000 lines illumination, stray light and the two
+ * detectors' temperatures drift apart: one (G, O) meets the means of the whole overlap and leaves a step at the ends.  The
+ * strip is cut into nb = max(1, L / B) blocks of B = block_lines >= 1 lines (integer division): block k < nb - 1 covers lines
+ * [k B, (k + 1) B), the last one [(nb - 1) B, L) -- a short tail is merged into it, so it holds B .. 2B - 1 lines, or all L
+ * lines when L < B.  Each block is fitted, the fits are nodes at the blocks' nominal centres, and every line gets the
+ * linear interpolation of its two nodes.  All of it in exact integers or correctly rounded fp64, like the block above. */
+
+/* oip_seam_moments_u16 per block, in ONE launch: d_acc is (nb, 6, spp) uint64, entry [(k * 6 + m) * spp + c], and the six
+ * totals of block k are ADDED into plane k (the caller zeroes the array).  Same arguments, checks and limit (2 * fold * L <=
+ * 2^32 per call) plus block_lines >= 1; the planes summed over k equal what oip_seam_moments_u16 adds for the same lines,
+ * exactly, and no total depends on the launch geometry.  Asynchronous. */
+int oip_seam_moments_blocks_u16(oip_ctx *ctx, const uint16_t *d_left, const uint16_t *d_right, int Ws, long L, int fs, int spp,
+                                int valid_min, int valid_max, long block_lines, uint64_t *d_acc);
+
+/* The fits of those totals, host.  acc: nb * 6 * spp totals (host copy).
+ *   1. (G0_c, O0_c, identity0_c) = oip_seam_fit of the planes' sum.  Its errors (a gain outside [16384, 262144], an offset
+ *      that does not fit 32 bits) are this function's, with the same text and OIP_E_INVALID.
+ *   2. oip_seam_fit's arithmetic on the totals of each block k, channel c.  Where that would give the identity (fewer than
+ *      max(min_count, 2) pairs, Da or Db 0 in moments mode, Sb 0 in gain mode), a gain outside [16384, 262144] or an offset
+ *      that does not fit 32 bits, the block channel takes (G0_c, O0_c) and substituted[k * spp + c] = 1: never an error --
+ *      the zero-filled line blocks of the de-framer, water and cloud are such blocks.
+ * gain_q16 / offset_q16 / substituted: nb * spp entries, [k * spp + c].  gain0_q16 / offset0_q16 / identity0: spp entries.
+ * report (may be NULL): nb * spp * 6 doubles, block k's spp x 6 at report + k * spp * 6 as oip_seam_fit lays out its own
+ * (the block's own statistics, substituted or not).  No context needed. */
+int oip_seam_fit_blocks(const uint64_t *acc, long nb, int spp, int mode, uint64_t min_count, int32_t *gain_q16,
+                        int32_t *offset_q16, int *substituted, int32_t *gain0_q16, int32_t *offset0_q16, int *identity0,
+                        double *report, char *err, int errlen);
+
+/* The nodes as per-line tables, host: line_gain_q16 / line_offset_q16 are L * spp int32, entry [r * spp + c].  Node k sits at
+ * line y_k = k B + floor(B / 2).  For line r and either quantity V:
+ *   u = r - floor(B / 2),  k = clamp(floor(u / B), 0, max(nb - 2, 0)),  t = clamp(u - k B, 0, B),  k' = min(k + 1, nb - 1)
+ *   V(r) = floor((V_k * (B - t) + V_k' * t + floor(B / 2)) / B)       64-bit, the floor toward minus infinity
+ * Constant before the first node and after the last, constant for nb = 1, and never outside the interval of its two
+ * nodes.  nb must be max(1, L / B); L = 0 writes nothing.  OIP_E_INVALID otherwise.  No context needed. */
+int oip_seam_line_tables(const int32_t *gain_q16, const int32_t *offset_q16, long nb, int spp, long L, long block_lines,
+                         int32_t *line_gain_q16, int32_t *line_offset_q16);
+
+/* oip_stitch_balanced_u16 with one change: d_line_gain_q16 / d_line_offset_q16 are the per-line tables, L * spp int32 each
+ * in HBM, and line r, channel c uses G[r * spp + c], O[r * spp + c].  b', the blend, the no-data rule, the h <= 16384 limit
+ * and the slower kernel for lines that are not a multiple of 8 samples or misaligned bases (here also: 4-sample tables that
+ * are not 16-byte aligned) are as stated there.  Output samples left of the blend zone are copies and read no table entry.
+ * Tables that repeat one (G, O) on every line give oip_stitch_balanced_u16's bytes; the identity with h = 0 gives
+ * oip_stitch_rows_u16's.  Asynchronous on the context's stream. */
+int oip_stitch_balanced_lines_u16(oip_ctx *ctx, const uint16_t *d_left, const uint16_t *d_right, uint16_t *d_out, int Ws, long L,
+                                  int fs, int spp, const int32_t *d_line_gain_q16, const int32_t *d_line_offset_q16,
+                                  int feather, int valid_min);
+
 /* ---- MTF compensation: a fixed-point restoration filter (`oip mtfc`; not in the reference) -------------------------
  * CCD 2 goes through a bicubic resampling in prestitch and every MSS band through one in the aligner; CCD 1 goes through
  * none, so the halves of a stitched product differ in sharpness.  MTFC is the small convolution that level-1 chains apply

@@ -29,6 +29,8 @@ from .capi import (  # noqa: F401
     rrc_dead_columns,
     rrc_fit_columns,
     seam_fit,
+    seam_fit_blocks,
+    seam_line_tables,
     stretch_limits,
     stretch_lut_u8,
     stt_mean,

@@ -120,6 +120,11 @@ _SIGS = {
     "oip_seam_moments_u16": ([_vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _vp], _i),
     "oip_seam_fit": ([C.POINTER(C.c_uint64), _i, _i, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, C.POINTER(_i), _cp, _i], _i),
     "oip_stitch_balanced_u16": ([_vp, _vp, _vp, _vp, _i, _l, _i, _i, _vp, _vp, _i, _i], _i),
+    "oip_seam_moments_blocks_u16": ([_vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _l, _vp], _i),
+    "oip_seam_fit_blocks": ([C.POINTER(C.c_uint64), _l, _i, _i, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_i),
+                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_i), _dp, _cp, _i], _i),
+    "oip_seam_line_tables": ([C.POINTER(C.c_int32), C.POINTER(C.c_int32), _l, _i, _l, _l, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], _i),
+    "oip_stitch_balanced_lines_u16": ([_vp, _vp, _vp, _vp, _i, _l, _i, _i, _vp, _vp, _i, _i], _i),
     "oip_convolve_u16": ([_vp, _vp, _l, _l, _vp, _l, _l, _i, _l, _i, C.POINTER(C.c_int32), _i, _i, _i], _i),
     "oip_mtfc_quantise": ([_dp, _i, _i, C.POINTER(C.c_int32), _cp, _i], _i),
     "oip_mtfc_design3": ([_d, _d, _d, _dp], _i),
@@ -290,6 +295,48 @@ def seam_fit(acc, mode="moments", min_count: int = 0):
     if rc:
         raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
     return gain, offset, ident, report
+
+
+def seam_fit_blocks(acc, mode="moments", min_count: int = 0):
+    """a fit per block of lines from the (nb, 6, spp) uint64 totals of Context.seam_moments_blocks_u16, a block channel
+    without a usable fit of its own taking the whole strip's (include/oip_c.h: oip_seam_fit_blocks).  Returns (gain_q16
+    (nb, spp) int32, offset_q16 (nb, spp) int32, substituted (nb, spp) int32, gain0_q16 (spp,), offset0_q16 (spp,), identity0
+    (spp,), report (nb, spp, 6))."""
+    lib = load_library()
+    m = SEAM_MODES.get(mode, mode)
+    if not isinstance(m, int):
+        raise ValueError("seam_fit_blocks: moments, gain or offset expected")
+    a = np.ascontiguousarray(acc, dtype=np.uint64)
+    assert a.ndim == 3 and a.shape[1] == 6, a.shape
+    nb, spp = a.shape[0], a.shape[2]
+    i32 = C.POINTER(C.c_int32)
+    gain, offset, sub = (np.zeros((nb, spp), np.int32) for _ in range(3))
+    gain0, offset0, ident0 = (np.zeros(spp, np.int32) for _ in range(3))
+    report = np.zeros((nb, spp, 6))
+    err = C.create_string_buffer(1024)
+    rc = lib.oip_seam_fit_blocks(a.ctypes.data_as(C.POINTER(C.c_uint64)), nb, spp, m, min_count, gain.ctypes.data_as(i32),
+                                 offset.ctypes.data_as(i32), sub.ctypes.data_as(C.POINTER(_i)), gain0.ctypes.data_as(i32),
+                                 offset0.ctypes.data_as(i32), ident0.ctypes.data_as(C.POINTER(_i)), report.ctypes.data_as(_dp), err, 1024)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    return gain, offset, sub, gain0, offset0, ident0, report
+
+
+def seam_line_tables(gain_q16, offset_q16, L: int, block_lines: int):
+    """the (nb, spp) block values as nodes, interpolated to (L, spp) int32 tables of gain and offset per line
+    (include/oip_c.h: oip_seam_line_tables); nb must be max(1, L // block_lines)"""
+    lib = load_library()
+    g = np.ascontiguousarray(gain_q16, dtype=np.int32)
+    o = np.ascontiguousarray(offset_q16, dtype=np.int32)
+    assert g.ndim == 2 and g.shape == o.shape, (g.shape, o.shape)
+    nb, spp = g.shape
+    i32 = C.POINTER(C.c_int32)
+    lg, lo = np.zeros((max(L, 0), spp), np.int32), np.zeros((max(L, 0), spp), np.int32)
+    rc = lib.oip_seam_line_tables(g.ctypes.data_as(i32), o.ctypes.data_as(i32), nb, spp, L, block_lines, lg.ctypes.data_as(i32),
+                                  lo.ctypes.data_as(i32))
+    if rc:
+        raise ValueError("oip_seam_line_tables: bad argument")
+    return lg, lo
 
 
 def mtfc_quantise(c) -> np.ndarray:
@@ -726,6 +773,19 @@ class Context:
         `feather` pixels either side of the seam (include/oip_c.h: oip_stitch_balanced_u16)"""
         self._ck(self.lib.oip_stitch_balanced_u16(self.h, _ptr(left), _ptr(right), _ptr(out), Ws, L, fs, spp, _ptr(gain_q16), _ptr(offset_q16),
                                                   feather, valid_min))
+
+    def seam_moments_blocks_u16(self, left, right, Ws, L, fs, spp, block_lines, acc, valid_min=0, valid_max=65535):
+        """seam_moments_u16 per block of block_lines lines in one launch: the totals of block k ADDED into plane k of acc,
+        (max(1, L // block_lines), 6, spp) uint64 on the device, zeroed by the caller (include/oip_c.h:
+        oip_seam_moments_blocks_u16)"""
+        self._ck(self.lib.oip_seam_moments_blocks_u16(self.h, _ptr(left), _ptr(right), Ws, L, fs, spp, valid_min, valid_max, block_lines,
+                                                      _ptr(acc)))
+
+    def stitch_balanced_lines_u16(self, left, right, out, Ws, L, fs, spp, line_gain_q16, line_offset_q16, feather=0, valid_min=1):
+        """stitch_balanced_u16 with a gain and an offset per line and channel: (L, spp) int32 tables on the device
+        (include/oip_c.h: oip_stitch_balanced_lines_u16)"""
+        self._ck(self.lib.oip_stitch_balanced_lines_u16(self.h, _ptr(left), _ptr(right), _ptr(out), Ws, L, fs, spp, _ptr(line_gain_q16),
+                                                        _ptr(line_offset_q16), feather, valid_min))
 
     # -- MTF compensation
     def convolve_u16(self, src, dst, W, L, spp, taps, valid_min=1, src_row0=0, src_rows=None, out_row0=0, out_rows=None):

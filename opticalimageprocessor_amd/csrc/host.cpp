@@ -1,5 +1,6 @@
 // host.cpp -- host-side pieces of the path that carry no raster arithmetic:
-// the RRC parameter file loader, its counterpart (column fit + writer), the seam fit of `oip stitch --balance`, the shift
+// the RRC parameter file loader, its counterpart (column fit + writer), the seam fits of `oip stitch --balance` (per strip, per
+// block of lines, and the per-line tables), the shift
 // filtering / polynomial fit, the contrast stretch of `oip quicklook` (percentile limits, 8-bit table, 8-bit TIFF) and the
 // taps of `oip mtfc` (design, quantisation, kernel file) and the column lists and column table of `oip despike`.
 #include <algorithm>
@@ -139,6 +140,61 @@ extern "C" int oip_rrc_dead_columns(const uint64_t *acc, int w, int mode, uint64
 // Gain and offset of image 2 relative to image 1 from the overlap totals of oip_seam_moments_u16 (include/oip_c.h states
 // the operation order; tests/_seam_ref.py restates it).  n <= 2^32 and Sa, Sb < 2^48 convert exactly; Saa, Sbb, Sab < 2^64
 // enter only through the exact 128-bit D's, which convert to the nearest double.
+// The ONE statement of the arithmetic, for one channel: oip_seam_fit runs it on a strip's totals, oip_seam_fit_blocks on the
+// sum of the blocks' and on each block's.  t: n, Sa, Sb, Saa, Sbb, Sab.  rep (may be NULL): 6 doubles.  G, O: the rounded
+// values as doubles, in range or not (the identity when the result is SEAM_FIT_IDENTITY).
+enum SeamFitResult { SEAM_FIT_OK, SEAM_FIT_IDENTITY, SEAM_FIT_GAIN_RANGE, SEAM_FIT_OFFSET_RANGE };
+static SeamFitResult seam_fit_channel(const uint64_t t[6], int mode, uint64_t need, double *rep, double *Gout, double *Oout)
+{
+    const uint64_t n = t[0], Sa = t[1], Sb = t[2], Saa = t[3], Sbb = t[4], Sab = t[5];
+    // (a D below zero cannot come from real totals; it is treated as 0)
+    const unsigned __int128 na = (unsigned __int128)n * Saa, sa2 = (unsigned __int128)Sa * Sa;
+    const unsigned __int128 nb = (unsigned __int128)n * Sbb, sb2 = (unsigned __int128)Sb * Sb;
+    const unsigned __int128 Da = na > sa2 ? na - sa2 : 0, Db = nb > sb2 ? nb - sb2 : 0;
+    const __int128 Dab = (__int128)((unsigned __int128)n * Sab) - (__int128)((unsigned __int128)Sa * Sb);
+    double meanA = 0.0, meanB = 0.0, sigmaA = 0.0, sigmaB = 0.0, r = 0.0;
+    if (n > 0) {
+        const double nd = (double)n;
+        meanA = (double)Sa / nd;
+        meanB = (double)Sb / nd;
+        const double ra = std::sqrt((double)Da), rb = std::sqrt((double)Db);
+        sigmaA = ra / nd;
+        sigmaB = rb / nd;
+        if (Da != 0 && Db != 0) {
+            const double den = ra * rb;
+            r = (double)Dab / den;
+        }
+    }
+    if (rep) { rep[0] = (double)n; rep[1] = meanA; rep[2] = meanB; rep[3] = sigmaA; rep[4] = sigmaB; rep[5] = r; }
+    *Gout = 65536.0;
+    *Oout = 0.0;
+    if (n < need) return SEAM_FIT_IDENTITY;
+    double g = 1.0;
+    if (mode == OIP_SEAM_MOMENTS) {
+        if (Da == 0 || Db == 0) return SEAM_FIT_IDENTITY;
+        const double q = (double)Da / (double)Db;
+        g = std::sqrt(q);
+    } else if (mode == OIP_SEAM_GAIN) {
+        if (Sb == 0) return SEAM_FIT_IDENTITY;
+        g = (double)Sa / (double)Sb;
+    }
+    const double G = std::rint(g * 65536.0);
+    *Gout = G;
+    if (!(G >= 16384.0 && G <= 262144.0)) return SEAM_FIT_GAIN_RANGE;
+    double O = 0.0;
+    if (mode != OIP_SEAM_GAIN) {
+        const double gq = G / 65536.0;
+        const double tt = gq * meanB;
+        const double d = meanA - tt;
+        O = std::rint(d * 65536.0);
+        *Oout = O;
+        if (!(O >= -2147483648.0 && O <= 2147483647.0)) return SEAM_FIT_OFFSET_RANGE;
+    }
+    return SEAM_FIT_OK;
+}
+
+static bool seam_mode_ok(int mode) { return mode == OIP_SEAM_MOMENTS || mode == OIP_SEAM_GAIN || mode == OIP_SEAM_OFFSET; }
+
 extern "C" int oip_seam_fit(const uint64_t *acc, int spp, int mode, uint64_t min_count, int32_t *gain_q16, int32_t *offset_q16, double *report,
                             int *identity, char *err, int errlen)
 {
@@ -146,61 +202,92 @@ extern "C" int oip_seam_fit(const uint64_t *acc, int spp, int mode, uint64_t min
         if (err && errlen > 0) snprintf(err, errlen, fmt, a...);
         return code;
     };
-    if (!acc || !gain_q16 || !offset_q16 || !identity || spp <= 0 || (mode != OIP_SEAM_MOMENTS && mode != OIP_SEAM_GAIN && mode != OIP_SEAM_OFFSET))
+    if (!acc || !gain_q16 || !offset_q16 || !identity || spp <= 0 || !seam_mode_ok(mode))
         return fail(OIP_E_INVALID, "%s", "oip_seam_fit: bad argument");
     const uint64_t need = min_count > 2u ? min_count : 2u;
     for (int c = 0; c < spp; ++c) {
-        const uint64_t n = acc[c], Sa = acc[spp + c], Sb = acc[2 * spp + c], Saa = acc[3 * spp + c], Sbb = acc[4 * spp + c], Sab = acc[5 * spp + c];
-        // (a D below zero cannot come from real totals; it is treated as 0)
-        const unsigned __int128 na = (unsigned __int128)n * Saa, sa2 = (unsigned __int128)Sa * Sa;
-        const unsigned __int128 nb = (unsigned __int128)n * Sbb, sb2 = (unsigned __int128)Sb * Sb;
-        const unsigned __int128 Da = na > sa2 ? na - sa2 : 0, Db = nb > sb2 ? nb - sb2 : 0;
-        const __int128 Dab = (__int128)((unsigned __int128)n * Sab) - (__int128)((unsigned __int128)Sa * Sb);
-        double meanA = 0.0, meanB = 0.0, sigmaA = 0.0, sigmaB = 0.0, r = 0.0;
-        if (n > 0) {
-            const double nd = (double)n;
-            meanA = (double)Sa / nd;
-            meanB = (double)Sb / nd;
-            const double ra = std::sqrt((double)Da), rb = std::sqrt((double)Db);
-            sigmaA = ra / nd;
-            sigmaB = rb / nd;
-            if (Da != 0 && Db != 0) {
-                const double den = ra * rb;
-                r = (double)Dab / den;
-            }
-        }
-        if (report) {
-            double *o = report + 6 * (size_t)c;
-            o[0] = (double)n; o[1] = meanA; o[2] = meanB; o[3] = sigmaA; o[4] = sigmaB; o[5] = r;
-        }
+        const uint64_t t[6] = {acc[c], acc[spp + c], acc[2 * spp + c], acc[3 * spp + c], acc[4 * spp + c], acc[5 * spp + c]};
+        double G = 0.0, O = 0.0;
+        const SeamFitResult res = seam_fit_channel(t, mode, need, report ? report + 6 * (size_t)c : nullptr, &G, &O);
         gain_q16[c] = 65536;
         offset_q16[c] = 0;
         identity[c] = 1;
-        if (n < need) continue;
-        double g = 1.0;
-        if (mode == OIP_SEAM_MOMENTS) {
-            if (Da == 0 || Db == 0) continue;
-            const double q = (double)Da / (double)Db;
-            g = std::sqrt(q);
-        } else if (mode == OIP_SEAM_GAIN) {
-            if (Sb == 0) continue;
-            g = (double)Sa / (double)Sb;
-        }
-        const double G = std::rint(g * 65536.0);
-        if (!(G >= 16384.0 && G <= 262144.0))
+        if (res == SEAM_FIT_IDENTITY) continue;
+        if (res == SEAM_FIT_GAIN_RANGE)
             return fail(OIP_E_INVALID, "oip_seam_fit: channel %d: gain_q16 %.0f outside [16384, 262144] -- the overlaps do not show the same ground (--fold-cols?)", c, G);
-        double O = 0.0;
-        if (mode != OIP_SEAM_GAIN) {
-            const double gq = G / 65536.0;
-            const double t = gq * meanB;
-            const double d = meanA - t;
-            O = std::rint(d * 65536.0);
-            if (!(O >= -2147483648.0 && O <= 2147483647.0))
-                return fail(OIP_E_INVALID, "oip_seam_fit: channel %d: offset_q16 %.0f does not fit 32 bits", c, O);
-        }
+        if (res == SEAM_FIT_OFFSET_RANGE) return fail(OIP_E_INVALID, "oip_seam_fit: channel %d: offset_q16 %.0f does not fit 32 bits", c, O);
         gain_q16[c] = (int32_t)G;
         offset_q16[c] = (int32_t)O;
         identity[c] = 0;
+    }
+    return OIP_OK;
+}
+
+// A fit per block of lines from the (nb, 6, spp) totals of oip_seam_moments_blocks_u16 (include/oip_c.h).  The whole-strip
+// fit on the sum of the planes is oip_seam_fit itself, errors and texts included; a block channel whose own fit is the
+// identity or out of range takes the strip's pair and is flagged -- a block of zero-filled lines, water or cloud is no error.
+extern "C" int oip_seam_fit_blocks(const uint64_t *acc, long nb, int spp, int mode, uint64_t min_count, int32_t *gain_q16, int32_t *offset_q16,
+                                   int *substituted, int32_t *gain0_q16, int32_t *offset0_q16, int *identity0, double *report, char *err,
+                                   int errlen)
+{
+    auto fail = [&](int code, const char *fmt, auto... a) {
+        if (err && errlen > 0) snprintf(err, errlen, fmt, a...);
+        return code;
+    };
+    if (!acc || !gain_q16 || !offset_q16 || !substituted || !gain0_q16 || !offset0_q16 || !identity0 || nb < 1 || spp <= 0 || !seam_mode_ok(mode))
+        return fail(OIP_E_INVALID, "%s", "oip_seam_fit_blocks: bad argument");
+    const size_t plane = 6 * (size_t)spp;
+    std::vector<uint64_t> sum(plane, 0);
+    for (long k = 0; k < nb; ++k)
+        for (size_t i = 0; i < plane; ++i) sum[i] += acc[(size_t)k * plane + i];
+    const int rc = oip_seam_fit(sum.data(), spp, mode, min_count, gain0_q16, offset0_q16, nullptr, identity0, err, errlen);
+    if (rc != OIP_OK) return rc;
+    const uint64_t need = min_count > 2u ? min_count : 2u;
+    for (long k = 0; k < nb; ++k)
+        for (int c = 0; c < spp; ++c) {
+            const uint64_t *a = acc + (size_t)k * plane;
+            const uint64_t t[6] = {a[c], a[spp + c], a[2 * spp + c], a[3 * spp + c], a[4 * spp + c], a[5 * spp + c]};
+            double G = 0.0, O = 0.0;
+            const size_t e = (size_t)k * spp + c;
+            const bool own = seam_fit_channel(t, mode, need, report ? report + 6 * e : nullptr, &G, &O) == SEAM_FIT_OK;
+            gain_q16[e] = own ? (int32_t)G : gain0_q16[c];
+            offset_q16[e] = own ? (int32_t)O : offset0_q16[c];
+            substituted[e] = own ? 0 : 1;
+        }
+    return OIP_OK;
+}
+
+// The block values as nodes at the blocks' nominal centres, interpolated to one value per line and channel in 64-bit
+// integers (include/oip_c.h).  The division floors toward minus infinity: offsets are negative as often as not.
+extern "C" int oip_seam_line_tables(const int32_t *gain_q16, const int32_t *offset_q16, long nb, int spp, long L, long block_lines,
+                                    int32_t *line_gain_q16, int32_t *line_offset_q16)
+{
+    if (!gain_q16 || !offset_q16 || spp <= 0 || L < 0 || L >= (1L << 31) || block_lines < 1 || nb != (L / block_lines > 1 ? L / block_lines : 1) ||
+        (L > 0 && (!line_gain_q16 || !line_offset_q16)))
+        return OIP_E_INVALID;
+    const long B = block_lines, half = B / 2;
+    auto floordiv = [](long long a, long long b) { return a / b - ((a % b != 0 && a < 0) ? 1 : 0); };      // b > 0
+    for (long r = 0; r < L; ++r) {
+        long k = 0, k1 = 0, t = 0;
+        if (nb > 1) {                              // (B <= L < 2^31 here: |V| * B < 2^62)
+            const long u = r - half;
+            k = u < 0 ? 0 : u / B;
+            if (k > nb - 2) k = nb - 2;
+            t = u - k * B;
+            t = t < 0 ? 0 : (t > B ? B : t);
+            k1 = k + 1;
+        }
+        for (int c = 0; c < spp; ++c) {
+            const size_t e = (size_t)r * spp + c;
+            if (nb == 1) {                         // one node: constant (the formula's value, without B in the products)
+                line_gain_q16[e] = gain_q16[c];
+                line_offset_q16[e] = offset_q16[c];
+                continue;
+            }
+            const long long g0 = gain_q16[k * spp + c], g1 = gain_q16[k1 * spp + c], o0 = offset_q16[k * spp + c], o1 = offset_q16[k1 * spp + c];
+            line_gain_q16[e] = (int32_t)floordiv(g0 * (B - t) + g1 * t + half, B);
+            line_offset_q16[e] = (int32_t)floordiv(o0 * (B - t) + o1 * t + half, B);
+        }
     }
     return OIP_OK;
 }

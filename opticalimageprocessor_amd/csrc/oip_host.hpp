@@ -446,12 +446,15 @@ struct RRCParam { double k; double b; };     // imageop.h:26-29
 // ---- oip stitch --balance / --feather: seam balancing and feathering (not in the reference) ------------------
 // The two CCDs are calibrated apart, so the hard cut of StitchBigRaw shows any level difference as a step.  The overlap that
 // the cut discards gives image 2's gain and offset relative to image 1 (oip_seam_moments_u16 + oip_seam_fit) and room to
-// blend (oip_stitch_balanced_u16).  Inactive by default: the stitch is then oip_stitch_rows_u16's, as before.
+// blend (oip_stitch_balanced_u16).  Inactive by default: the stitch is then oip_stitch_rows_u16's, as before.  With blockLines the
+// fit is made per block of lines and interpolated to a (G, O) per line (oip_seam_moments_blocks_u16, oip_seam_fit_blocks,
+// oip_seam_line_tables, oip_stitch_balanced_lines_u16).  `oip stitch` and both stitches of `oip task` come through here.
 struct SeamOptions {
     int balance = -1;                       // -1: none, else OIP_SEAM_MOMENTS / OIP_SEAM_GAIN / OIP_SEAM_OFFSET
     int feather = 0;                        // half-width of the blend zone in pixels (the halved --feather)
     int validMin = 1, validMax = 65535;     // 0 is the border value of prestitch and the aligner (BORDER_CONSTANT)
     long minCount = 0;
+    long blockLines = 0;                    // > 0 (with a balance mode): a fit per block of this many lines, interpolated per line
     bool active() const { return balance >= 0 || feather > 0; }
 };
 
@@ -460,23 +463,60 @@ inline void StitchSeam(const uint16_t *dl, const uint16_t *dr, uint16_t *dout, i
 {
     oip_ctx *ctx = Device::get().ctx();
     auto ck = [](int rc) { Device::get().check(rc); };
-    std::vector<int32_t> G(spp, 65536), O(spp, 0);
-    if (o.balance >= 0) {
-        DevBuf<uint64_t> acc((size_t)6 * spp);
-        ck(oip_memset(ctx, acc.p, 0, (size_t)6 * spp * sizeof(uint64_t)));
-        ck(oip_seam_moments_u16(ctx, dl, dr, Ws, L, fs, spp, o.validMin, o.validMax, acc.p));
-        std::vector<uint64_t> totals((size_t)6 * spp);
-        acc.download(totals.data(), totals.size());
-        std::vector<double> rep((size_t)6 * spp);
-        std::vector<int> ident(spp);
-        char err[1024] = "";
-        const int rc = oip_seam_fit(totals.data(), spp, o.balance, (uint64_t)o.minCount, G.data(), O.data(), rep.data(), ident.data(), err, sizeof err);
+    auto fit_ck = [](int rc, const char *err) {
         if (rc == OIP_E_INVALID) throw std::invalid_argument(err);
         if (rc != OIP_OK) throw std::runtime_error(err);
+    };
+    const bool blocks = o.balance >= 0 && o.blockLines > 0;
+    const long B = blocks ? o.blockLines : 1, nb = blocks ? std::max<long>(1, L / B) : 1;
+    const size_t plane = (size_t)6 * spp;
+    std::vector<int32_t> G(spp, 65536), O(spp, 0);
+    std::vector<uint64_t> planes;                                      // (nb, 6, spp) with --balance-lines
+    char err[1024] = "";
+    if (o.balance >= 0) {
+        DevBuf<uint64_t> acc(plane * nb);
+        ck(oip_memset(ctx, acc.p, 0, plane * nb * sizeof(uint64_t)));
+        if (blocks) ck(oip_seam_moments_blocks_u16(ctx, dl, dr, Ws, L, fs, spp, o.validMin, o.validMax, B, acc.p));
+        else ck(oip_seam_moments_u16(ctx, dl, dr, Ws, L, fs, spp, o.validMin, o.validMax, acc.p));
+        planes.resize(plane * nb);
+        acc.download(planes.data(), planes.size());
+        std::vector<uint64_t> totals(plane, 0);
+        for (long k = 0; k < nb; ++k)
+            for (size_t i = 0; i < plane; ++i) totals[i] += planes[(size_t)k * plane + i];
+        std::vector<double> rep(plane);
+        std::vector<int> ident(spp);
+        fit_ck(oip_seam_fit(totals.data(), spp, o.balance, (uint64_t)o.minCount, G.data(), O.data(), rep.data(), ident.data(), err, sizeof err), err);
         for (int c = 0; c < spp; ++c)
             OLOG("seam channel %d: n %llu, mean %.3f / %.3f, sigma %.3f / %.3f, r %.6f, gain_q16 %d, offset_q16 %d%s", c + 1,
                  (unsigned long long)totals[c], rep[6 * c + 1], rep[6 * c + 2], rep[6 * c + 3], rep[6 * c + 4], rep[6 * c + 5], G[c], O[c],
                  ident[c] ? " (identity substituted)" : "");
+    }
+    if (blocks) {
+        // a (G, O) per block, the strip's where a block has none of its own, then per line: tables of L * spp pairs in HBM
+        const size_t nodes = (size_t)nb * spp, entries = (size_t)L * spp;
+        std::vector<int32_t> bg(nodes), bo(nodes), g0(spp), o0(spp), tab(2 * entries + 1);
+        std::vector<int> sub(nodes), ident0(spp);
+        fit_ck(oip_seam_fit_blocks(planes.data(), nb, spp, o.balance, (uint64_t)o.minCount, bg.data(), bo.data(), sub.data(), g0.data(), o0.data(),
+                                   ident0.data(), nullptr, err, sizeof err), err);
+        for (int c = 0; c < spp; ++c) {
+            long s = 0;
+            int32_t gmin = bg[c], gmax = bg[c], omin = bo[c], omax = bo[c];
+            for (long k = 0; k < nb; ++k) {
+                const size_t e = (size_t)k * spp + c;
+                s += sub[e];
+                gmin = std::min(gmin, bg[e]); gmax = std::max(gmax, bg[e]);
+                omin = std::min(omin, bo[e]); omax = std::max(omax, bo[e]);
+            }
+            OLOG("seam blocks channel %d: %ld blocks of %ld lines, %ld substituted, gain_q16 %d..%d, offset_q16 %d..%d", c + 1, nb, B, s, gmin, gmax,
+                 omin, omax);
+        }
+        if (oip_seam_line_tables(bg.data(), bo.data(), nb, spp, L, B, tab.data(), tab.data() + entries) != OIP_OK)
+            throw std::invalid_argument("oip_seam_line_tables: bad argument");
+        DevBuf<int32_t> dtab(2 * entries + 4);                         // (both tables 16-byte aligned: entries * 4 bytes is, at spp 4)
+        dtab.upload(tab.data(), 2 * entries);
+        ck(oip_stitch_balanced_lines_u16(ctx, dl, dr, dout, Ws, L, fs, spp, dtab.p, dtab.p + entries, o.feather, o.validMin));
+        ck(oip_sync(ctx));                  // `dtab` leaves scope
+        return;
     }
     DevBuf<int32_t> go((size_t)2 * spp);
     std::vector<int32_t> h(G);
@@ -1423,6 +1463,7 @@ struct TaskOptions {
     int fitMode = OIP_FIT_REFERENCE;
     bool fp16acc = false;
     bool panOnly = false;       // stitched PAN product only: fused RRC / resampling straight into the stitched raster
+    SeamOptions seamPAN, seamMSS;   // the two stitches' seam options (inactive: the hard cut of oip_stitch_rows_u16); not with panOnly
 };
 
 inline void RunFusedTask(const std::string &pan1, const std::string &pan2, const std::string &rrc1, const std::string &rrc2,
@@ -1500,7 +1541,8 @@ inline void RunFusedTask(const std::string &pan1, const std::string &pan2, const
         if (fold < 0 || fold >= W) throw std::invalid_argument("fold columns exceed the image width");
         const size_t nout = (size_t)2 * (W - fold) * L;
         auto st = std::make_shared<DevBuf<uint16_t>>(nout);
-        ck(oip_stitch_rows_u16(ctx, p1.p, p2s.p, st->p, W, L, fold));
+        if (o.seamPAN.active()) StitchSeam(p1.p, p2s.p, st->p, W, L, fold, 1, o.seamPAN);
+        else ck(oip_stitch_rows_u16(ctx, p1.p, p2s.p, st->p, W, L, fold));
         long mark = 0;
         ck(oip_compute_mark(ctx, &mark));
         OLOG("Write stitched image to file '%s' ...", outPAN.c_str());
@@ -1530,7 +1572,10 @@ inline void RunFusedTask(const std::string &pan1, const std::string &pan2, const
         const int W4 = Wb * MSS_BANDS, fold4 = fold * MSS_BANDS;
         const size_t nout = (size_t)2 * (W4 - fold4) * arows[0];
         DevBuf<uint16_t> st(nout);
-        ck(oip_stitch_rows_u16(ctx, aligned[0].p, aligned[1].p, st.p, W4, arows[0], fold4));
+        // (the fit is per channel: the order the aligned images hold their samples in, the Mat's here and the file's in `oip stitch`,
+        // does not change what a channel gets)
+        if (o.seamMSS.active()) StitchSeam(aligned[0].p, aligned[1].p, st.p, W4, arows[0], fold4, MSS_BANDS, o.seamMSS);
+        else ck(oip_stitch_rows_u16(ctx, aligned[0].p, aligned[1].p, st.p, W4, arows[0], fold4));
         OLOG("Write stitched image to file '%s' ...", outMSS.c_str());
         const int ow = 2 * (Wb - fold);
         if (!o.useGDAL && nout < 4000000000ull) {

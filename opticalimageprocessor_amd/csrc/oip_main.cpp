@@ -3,7 +3,8 @@
 //   oip prestitch --pan1 A.RAW --pan2 B.RAW [--rrc1 --rrc2 -s -l --stitch-overlap --stt-threshold
 //                 --stt-maxdeltay -e -r/--rrc/--no-rrc -c]                     (main.cpp:112-150)
 //   oip stitch --image1 L.RAW --image2 R.RAW -c/--fold-cols N [-o OUT.RAW]       (main.cpp:159-190)
-//              [--balance none|offset|gain|moments --feather N --valid-min N --valid-max N --min-count N]   see run_stitch()
+//              [--balance none|offset|gain|moments --balance-lines N --feather N --valid-min N --valid-max N --min-count N]
+//                                                                               see seam_options() and run_stitch()
 //   oip --pan P.RAW --mss M.RAW [--do-rrc4pan --rrc-pan F --no-rrc4mss --rrc-msb1..4 F --slices
 //       --ibc-sections --ibc-threshold --line-offset --lines-section --overlap-lines -k]   (:193-252)
 //   oip task ...                fused flow of DOC/sample-task.sh, see run_task()
@@ -17,12 +18,13 @@
 // plus --width N (pixels per PAN line; the reference hard-codes 12288, oipshared.h:28).
 // `auxsep` is outside this build.  TIFF input and output go through oip_tiff.hpp (uncompressed and LZW, with
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
-// (--balance, --feather and their --valid-min / --valid-max / --min-count) and the rrc-calib, quicklook, mtfc and despike
-// sub-commands.
+// (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
+// --feather-pan / --feather-mss for its two stitches) and the rrc-calib, quicklook, mtfc and despike sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
 // codes (RequiredError 106, ValidationError 105, ExtrasError 109, ConversionError 104).
+#include <climits>
 #include <cstdlib>
 #include <unistd.h>
 #include <map>
@@ -134,6 +136,7 @@ void usage()
          "             --stt-threshold X --stt-maxdeltay X -e N -r,--rrc/--no-rrc -c,--only-calculate --fp16-accumulate]\n"
          "  stitch     --image1 FILE --image2 FILE -c,--fold-cols N [-o,--out FILE] [-g,--GDAL -m,--band-map a,b,c,d]\n"
          "             [--balance none|offset|gain|moments] image 2's gain / offset relative to image 1, fitted on the overlap\n"
+         "             [--balance-lines N] with --balance: a fit per block of N lines (N >= 1), interpolated to a gain / offset per line\n"
          "             [--feather N] blend the images over N columns around the seam (even, 0 <= N <= fold-cols)\n"
          "             [--valid-min N] [--valid-max N] (samples outside are no data; default 1, 65535) [--min-count N]\n"
          "  --gpus N   (default action and prestitch) scan-line blocks over the N GPUs of the node, RCCL exchanges\n"
@@ -142,6 +145,8 @@ void usage()
          "             --pan-only: the stitched PAN product alone, RRC and resampling written straight into it):\n"
          "             --pan1 --pan2 --rrc1 --rrc2 --mss1 --mss2 --rrc-mss{1,2}-b{1..4} FILE --fold-cols-pan N --fold-cols-mss N\n"
          "             --out-pan FILE.TIFF --out-mss FILE.TIFF [prestitch, default-action and stitch options]\n"
+         "             [--balance M --balance-lines N --valid-min N --valid-max N --min-count N] as for stitch, applied to both stitches,\n"
+         "             [--feather-pan N] [--feather-mss N] (even, 0 <= N <= the stitch's --fold-cols-*); none of these with --pan-only\n"
          "  rrc-calib  derive RRC coefficient files from a strip (moment matching of the per-column statistics); the --rrc-* files\n"
          "             are OUTPUTS here, and the same arguments given to the default action apply them:\n"
          "             [--pan FILE --rrc-pan OUT] [--mss FILE --rrc-msb1 OUT --rrc-msb2 OUT --rrc-msb3 OUT --rrc-msb4 OUT]\n"
@@ -207,11 +212,44 @@ int run_prestitch(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// The seam options `stitch` and `task` share (not in the reference): --balance, --balance-lines, --valid-min, --valid-max,
+// --min-count.  The blend width is per stitch (seam_feather).  Without any of them a stitch is the reference's hard cut.
+const char *const kSeamValued[] = {"--balance", "--balance-lines", "--valid-min", "--valid-max", "--min-count"};
+
+SeamOptions seam_options(const Parsed &p)
+{
+    SeamOptions seam;
+    const std::string balance = p.str("--balance", "none");
+    if (balance == "moments") seam.balance = OIP_SEAM_MOMENTS;
+    else if (balance == "gain") seam.balance = OIP_SEAM_GAIN;
+    else if (balance == "offset") seam.balance = OIP_SEAM_OFFSET;
+    else if (balance != "none") throw cli_error(105, "--balance: none, offset, gain or moments expected");
+    if (p.has("--balance-lines")) {
+        seam.blockLines = p.integer("--balance-lines", 0);
+        if (seam.blockLines < 1) throw cli_error(105, "--balance-lines: a line count of at least 1 expected");
+        if (seam.balance < 0) throw cli_error(107, "--balance-lines requires --balance");
+    }
+    seam.validMin = p.integer("--valid-min", 1);
+    seam.validMax = p.integer("--valid-max", 65535);
+    if (seam.validMin < 0 || seam.validMax > 65535 || seam.validMin > seam.validMax) throw cli_error(105, "--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
+    seam.minCount = p.integer("--min-count", 0);
+    if (seam.minCount < 0) throw cli_error(105, "--min-count: a non-negative value expected");
+    return seam;
+}
+
+// --feather / --feather-pan / --feather-mss: the blend width in columns, halved like the fold columns it is bounded by
+int seam_feather(const Parsed &p, const std::string &key, int foldCols, const std::string &foldKey)
+{
+    const int feather = p.integer(key, 0);
+    if (feather < 0 || feather % 2 != 0 || feather > foldCols) throw cli_error(105, key + ": an even value, 0 <= N <= " + foldKey + ", expected");
+    return feather / 2;
+}
+
 int run_stitch(const std::vector<std::string> &args, int width)
 {
     Spec sp;
-    sp.valued = {"--image1", "--image2", "--out", "--fold-cols", "--band-map", "--width", "--balance", "--feather", "--valid-min", "--valid-max",
-                 "--min-count"};
+    sp.valued = {"--image1", "--image2", "--out", "--fold-cols", "--band-map", "--width", "--feather"};
+    sp.valued.insert(std::begin(kSeamValued), std::end(kSeamValued));
     sp.flags = {"--GDAL"};
     sp.alias = {{"-o", "--out"}, {"-c", "--fold-cols"}, {"-g", "--GDAL"}, {"-m", "--band-map"}};
     Parsed p = parse(sp, args);
@@ -229,21 +267,8 @@ int run_stitch(const std::vector<std::string> &args, int width)
         for (int i = 0; i < MSS_BANDS; ++i)
             if (map[i] <= 0 || map[i] > MSS_BANDS) throw cli_error(105, "-m: invalid band index");
     }
-    // seam balancing and feathering (not in the reference).  Without these options the stitch is the reference's hard cut.
-    SeamOptions seam;
-    const std::string balance = p.str("--balance", "none");
-    if (balance == "moments") seam.balance = OIP_SEAM_MOMENTS;
-    else if (balance == "gain") seam.balance = OIP_SEAM_GAIN;
-    else if (balance == "offset") seam.balance = OIP_SEAM_OFFSET;
-    else if (balance != "none") throw cli_error(105, "--balance: none, offset, gain or moments expected");
-    const int feather = p.integer("--feather", 0);
-    if (feather < 0 || feather % 2 != 0 || feather > foldCols) throw cli_error(105, "--feather: an even value, 0 <= N <= fold-cols, expected");
-    seam.feather = feather / 2;                                                                                  // halved like --fold-cols
-    seam.validMin = p.integer("--valid-min", 1);
-    seam.validMax = p.integer("--valid-max", 65535);
-    if (seam.validMin < 0 || seam.validMax > 65535 || seam.validMin > seam.validMax) throw cli_error(105, "--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
-    seam.minCount = p.integer("--min-count", 0);
-    if (seam.minCount < 0) throw cli_error(105, "--min-count: a non-negative value expected");
+    SeamOptions seam = seam_options(p);
+    seam.feather = seam_feather(p, "--feather", foldCols, "fold-cols");
     Stitcher::Stitch(p.str("--image1"), p.str("--image2"), p.str("--out"), foldCols / 2, width, p.has("--GDAL"),
                      bandMap.empty() ? nullptr : map, &seam);                                                    // main.cpp:189
     return 0;
@@ -351,7 +376,9 @@ int run_task(const std::vector<std::string> &args, int width)
     Spec sp;
     sp.valued = {"--pan1", "--pan2", "--rrc1", "--rrc2", "--mss1", "--mss2", "--out-pan", "--out-mss", "--fold-cols-pan", "--fold-cols-mss",
                  "--sections", "--section-lines", "--stitch-overlap", "--stt-threshold", "--stt-maxdeltay", "--edge-cols", "--band-map",
-                 "--slices", "--ibc-sections", "--ibc-threshold", "--line-offset", "--lines-section", "--overlap-lines", "--width", "--fit"};
+                 "--slices", "--ibc-sections", "--ibc-threshold", "--line-offset", "--lines-section", "--overlap-lines", "--width", "--fit",
+                 "--feather-pan", "--feather-mss"};
+    sp.valued.insert(std::begin(kSeamValued), std::end(kSeamValued));
     for (int c = 1; c <= 2; ++c)
         for (int b = 1; b <= MSS_BANDS; ++b) sp.valued.insert("--rrc-mss" + std::to_string(c) + "-b" + std::to_string(b));
     sp.flags = {"--GDAL", "--keep-leading", "--fp16-accumulate", "--pan-only"};
@@ -361,6 +388,18 @@ int run_task(const std::vector<std::string> &args, int width)
     // --pan-only: the stitched PAN product alone (steps 1-2 of DOC/sample-task.sh).  No corrected strip is needed afterwards,
     // so RRC of CCD 1 and the resampled CCD-2 lines are written straight into the stitched raster (one pass each).
     const bool panOnly = p.flag.count("--pan-only") != 0;
+    // The seam options of the two stitches.  In the --pan-only flow the resampling kernel writes the right half of the product
+    // itself and has no (G, O) to apply on store, so any of them is refused there -- here, before a file or the device is touched.
+    if (panOnly) {
+        for (auto k : kSeamValued)
+            if (p.has(k)) throw cli_error(107, std::string(k) + " is not available with --pan-only");
+        for (auto k : {"--feather-pan", "--feather-mss"})
+            if (p.has(k)) throw cli_error(107, std::string(k) + " is not available with --pan-only");
+    }
+    const SeamOptions seam = seam_options(p);
+    // (a missing --fold-cols-* is reported below, as before)
+    const int featherPAN = seam_feather(p, "--feather-pan", p.integer("--fold-cols-pan", INT_MAX), "fold-cols-pan");
+    const int featherMSS = seam_feather(p, "--feather-mss", p.integer("--fold-cols-mss", INT_MAX), "fold-cols-mss");
     for (auto k : {"--pan1", "--pan2", "--rrc1", "--rrc2", "--out-pan", "--fold-cols-pan"}) require(p, k);
     if (!panOnly)
         for (auto k : {"--mss1", "--mss2", "--out-mss", "--fold-cols-mss"}) require(p, k);
@@ -405,6 +444,9 @@ int run_task(const std::vector<std::string> &args, int width)
     o.keepLeading = p.flag.count("--keep-leading") != 0;
     o.fitMode = fit_mode(p);
     o.fp16acc = p.flag.count("--fp16-accumulate") != 0;
+    o.seamPAN = o.seamMSS = seam;
+    o.seamPAN.feather = featherPAN;
+    o.seamMSS.feather = featherMSS;
     for (auto k : {"--out-pan", "--out-mss"})
         if (p.has(k) && to_lower(std::filesystem::path(p.str(k)).extension().string()) != ".tiff") throw std::invalid_argument("Output file should be a tiff image");
     RunFusedTask(p.str("--pan1"), p.str("--pan2"), p.str("--rrc1"), p.str("--rrc2"), p.str("--mss1"), p.str("--mss2"), msb[0], msb[1],

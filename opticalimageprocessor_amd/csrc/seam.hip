@@ -9,6 +9,8 @@
 //                            exact integers ADDED into a (6, spp) uint64 array
 //   oip_stitch_balanced_u16  the stitch with image 2 balanced (b' = (G b + O) in Q16), a linear blend of half-width h pixels
 //                            around the seam and "no data" (a sample below valid_min) handled inside it
+//   oip_seam_moments_blocks_u16    the totals per block of B lines, (nb, 6, spp), all blocks in one launch   } `--balance-lines`:
+//   oip_stitch_balanced_lines_u16  the balanced stitch with a (G, O) per line and channel from tables in HBM } see their kernels
 //
 // Moments: layout / mapping.  The overlap is a few hundred samples wide and as tall as the strip, so a lane owns ONE overlap
 // sample j and walks lines: the 64 lanes of a wave read 128 contiguous bytes of a line of either image, the four waves of a
@@ -106,6 +108,69 @@ __global__ __launch_bounds__(kBlock) void seam_moments_kernel(const uint16_t *__
 #pragma unroll
         for (int w = 0; w < kWaves; ++w) t += sh[w][k][c];
         atomicAdd(acc + k * SPP + c, t);
+    }
+}
+
+// The totals of every line block of B lines in ONE launch (`oip stitch --balance-lines`): block k < nb - 1 covers lines
+// [k B, (k + 1) B), the last one [(nb - 1) B, L), and its six totals go to plane k of acc, (nb, 6, SPP).  Lane mapping, line
+// walk and reduction are seam_moments_kernel's.  A line RANGE (at most rows_per_range lines, never across a block boundary)
+// is what a workgroup reduces and adds: full blocks are cut into ranges_per_block ranges each, the last block into whatever
+// it needs, and the workgroups of a column group (blockIdx.y) take the ranges with a grid stride, so the grid does not grow
+// with nb.  The 32-bit partials start again with every range: a lane sees at most 65536 lines between two reductions.
+template <bool MASK, int SPP>
+__global__ __launch_bounds__(kBlock) void seam_moments_blocks_kernel(const uint16_t *__restrict__ left, const uint16_t *__restrict__ right,
+                                                                    long Ws, long L, int fs2, unsigned vmin, unsigned vspan,
+                                                                    unsigned long long *__restrict__ acc, long B, long nb,
+                                                                    long rows_per_range, long ranges_per_block, long nranges)
+{
+    __shared__ unsigned long long sh[kWaves][6][SPP];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = blockIdx.y * 64 + lane;
+    const uint16_t *pa = left + (Ws - fs2) + j, *pb = right + j;      // + r * Ws: inside line r of either raster (j < fs2)
+    const long full = (nb - 1) * ranges_per_block;                    // the ranges of the blocks in front of the last one
+    for (long y = blockIdx.x; y < nranges; y += gridDim.x) {
+        const long k = y < full ? y / ranges_per_block : nb - 1;
+        const long s = y < full ? y - k * ranges_per_block : y - full;
+        const long end = k < nb - 1 ? (k + 1) * B : L;
+        const long r0 = k * B + s * rows_per_range;
+        long r1 = r0 + rows_per_range;
+        if (r1 > end) r1 = end;
+        unsigned n = 0, sa = 0, sb = 0;
+        unsigned long long saa = 0, sbb = 0, sab = 0;
+        if (j < fs2) {
+            long r = r0 + wave;
+            for (; r + (kRowsInFlight - 1) * kWaves < r1; r += kRowsInFlight * kWaves) {
+                unsigned a[kRowsInFlight], b[kRowsInFlight];
+#pragma unroll
+                for (int u = 0; u < kRowsInFlight; ++u) {
+                    a[u] = pa[(r + u * kWaves) * Ws];
+                    b[u] = pb[(r + u * kWaves) * Ws];
+                }
+#pragma unroll
+                for (int u = 0; u < kRowsInFlight; ++u) seam_pair<MASK>(a[u], b[u], vmin, vspan, n, sa, sb, saa, sbb, sab);
+            }
+            for (; r < r1; r += kWaves) seam_pair<MASK>(pa[r * Ws], pb[r * Ws], vmin, vspan, n, sa, sb, saa, sbb, sab);
+            if (!MASK) n = (unsigned)((r1 - r0 - wave + kWaves - 1) / kWaves);      // the lines this wave took (r1 > r0)
+        }
+        unsigned long long v[6] = {n, sa, sb, saa, sbb, sab};
+#pragma unroll
+        for (int off = 32; off >= SPP; off >>= 1) {
+#pragma unroll
+            for (int m = 0; m < 6; ++m) v[m] += __shfl_xor(v[m], off, 64);
+        }
+        if (lane < SPP) {
+#pragma unroll
+            for (int m = 0; m < 6; ++m) sh[wave][m][lane] = v[m];
+        }
+        __syncthreads();
+        if (threadIdx.x < 6 * SPP) {
+            const int m = threadIdx.x / SPP, c = threadIdx.x % SPP;
+            unsigned long long t = 0;
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) t += sh[w][m][c];
+            atomicAdd(acc + (k * 6 + m) * SPP + c, t);
+        }
+        __syncthreads();                                              // sh is written again in the next trip
     }
 }
 
@@ -235,6 +300,95 @@ __global__ __launch_bounds__(kBlock) void stitch_balanced_scalar_kernel(const ui
     }
 }
 
+// ---- balanced stitch, one (G, O) per line and channel --------------------------------------------------------------
+// stitch_balanced_kernel with the pairs of line r read from per-line tables (entry r * SPP + c) instead of kept as loop
+// constants.  Per lane: a chunk left of the blend zone is the same pure copy and reads no table; any other chunk loads the SPP
+// pairs of its own line next to its image samples -- one dword from either table at SPP 1, one 16-byte load from either at
+// SPP 4 -- which the thousands of chunks of a line share through L2.  The arithmetic is balance_px / seam_sample, so equal
+// pairs on every line give stitch_balanced_kernel's bytes.
+// requires: stitch_balanced_kernel's alignments, and at SPP 4 table bases 16-byte aligned.
+template <int SPP>
+__device__ __forceinline__ void seam_line_pairs(const int *__restrict__ gain, const int *__restrict__ offset, long r, int (&G)[4], long long (&orr)[4])
+{
+    if (SPP == 4) {
+        const int4 g4 = reinterpret_cast<const int4 *>(gain)[r], o4 = reinterpret_cast<const int4 *>(offset)[r];
+        G[0] = g4.x; G[1] = g4.y; G[2] = g4.z; G[3] = g4.w;
+        orr[0] = (long long)o4.x + 32768; orr[1] = (long long)o4.y + 32768; orr[2] = (long long)o4.z + 32768; orr[3] = (long long)o4.w + 32768;
+    } else {
+        const int g1 = gain[r];
+        const long long o1 = (long long)offset[r] + 32768;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { G[k] = g1; orr[k] = o1; }
+    }
+}
+
+template <int SPP>
+__global__ __launch_bounds__(kBlock) void stitch_balanced_lines_kernel(const uint16_t *__restrict__ left, const uint16_t *__restrict__ right,
+                                                                       uint16_t *__restrict__ out, SeamGeom g, long L,
+                                                                       const int *__restrict__ gain, const int *__restrict__ offset)
+{
+    const int cpr = (2 * g.half) / 8;             // chunks per output line
+    const long nchunks = (long)cpr * L;
+    const long n_elems = g.Ws * L;
+    constexpr int U = 4;
+    const long stride = (long)gridDim.x * kBlock;
+    for (long f0 = (long)blockIdx.x * kBlock + threadIdx.x; f0 < nchunks; f0 += stride * U) {
+        uint4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long f = f0 + u * stride;
+            if (f >= nchunks) break;
+            const long r = f / cpr;
+            const int x0 = (int)(f - r * cpr) * 8;
+            if (x0 + 8 <= g.z0) {
+                v[u] = seam_load8(left, r * g.Ws + x0, n_elems);
+                continue;
+            }
+            int G[4];
+            long long orr[4];
+            seam_line_pairs<SPP>(gain, offset, r, G, orr);
+            if (x0 >= g.z1) {
+                const uint4 q = seam_load8(right, r * g.Ws + (x0 - g.off_b), n_elems);
+                v[u].x = balance_px(q.x & 0xffffu, G[0], orr[0]) | (balance_px(q.x >> 16, G[1], orr[1]) << 16);
+                v[u].y = balance_px(q.y & 0xffffu, G[2], orr[2]) | (balance_px(q.y >> 16, G[3], orr[3]) << 16);
+                v[u].z = balance_px(q.z & 0xffffu, G[0], orr[0]) | (balance_px(q.z >> 16, G[1], orr[1]) << 16);
+                v[u].w = balance_px(q.w & 0xffffu, G[2], orr[2]) | (balance_px(q.w >> 16, G[3], orr[3]) << 16);
+            } else {
+                unsigned t[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) t[i] = seam_sample(left, right, g, r, x0 + i, G[i & 3], orr[i & 3]);
+                v[u].x = t[0] | (t[1] << 16); v[u].y = t[2] | (t[3] << 16);
+                v[u].z = t[4] | (t[5] << 16); v[u].w = t[6] | (t[7] << 16);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long f = f0 + u * stride;
+            if (f >= nchunks) break;
+            reinterpret_cast<uint4 *>(out)[f] = v[u];
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void stitch_balanced_lines_scalar_kernel(const uint16_t *__restrict__ left, const uint16_t *__restrict__ right,
+                                                                              uint16_t *__restrict__ out, SeamGeom g, long L,
+                                                                              const int *__restrict__ gain, const int *__restrict__ offset, int spp)
+{
+    const long ow = 2L * g.half;
+    const long n = ow * L;
+    const long stride = (long)gridDim.x * kBlock;
+    for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const long r = i / ow;
+        const int x = (int)(i - r * ow);
+        if (x < g.z0) {                                               // a copy: no table entry is read
+            out[i] = left[r * g.Ws + x];
+            continue;
+        }
+        const long e = r * spp + (x & (spp - 1));
+        out[i] = (uint16_t)seam_sample(left, right, g, r, x, gain[e], (long long)offset[e] + 32768);
+    }
+}
+
 }  // namespace
 
 extern "C" int oip_seam_moments_u16(oip_ctx *ctx, const uint16_t *d_left, const uint16_t *d_right, int Ws, long L, int fs, int spp,
@@ -309,6 +463,98 @@ extern "C" int oip_stitch_balanced_u16(oip_ctx *ctx, const uint16_t *d_left, con
         if (blocks > cap) blocks = cap;
         hipLaunchKernelGGL(stitch_balanced_scalar_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, d_left, d_right, d_out, g, L,
                            d_gain_q16, d_offset_q16, spp);
+    }
+    OIP_HIP(ctx, hipGetLastError());
+    return OIP_OK;
+}
+
+extern "C" int oip_seam_moments_blocks_u16(oip_ctx *ctx, const uint16_t *d_left, const uint16_t *d_right, int Ws, long L, int fs, int spp,
+                                           int valid_min, int valid_max, long block_lines, uint64_t *d_acc)
+{
+    OIP_CHECK_CTX(ctx);
+    if (!d_left || !d_right || !d_acc || ((uintptr_t)d_acc & 7) || ((uintptr_t)d_left & 1) || ((uintptr_t)d_right & 1) || (spp != 1 && spp != 4) ||
+        Ws <= 0 || Ws % spp != 0 || fs <= 0 || fs % spp != 0 || 2L * fs > Ws || L < 0 || L >= (1L << 31) || valid_min < 0 || valid_max > 65535 ||
+        valid_min > valid_max || block_lines < 1)
+        return oip_fail(ctx, OIP_E_INVALID, "oip_seam_moments_blocks_u16: bad argument");
+    if ((unsigned long long)(2 * fs / spp) * (unsigned long long)L > (1ull << 32))
+        return oip_fail(ctx, OIP_E_INVALID, "oip_seam_moments_blocks_u16: more than 2^32 pairs per channel");
+    if (L == 0) return OIP_OK;
+    const int fs2 = 2 * fs;
+    const int gx = (fs2 + 63) / 64;
+    if (gx > 65535) return oip_fail(ctx, OIP_E_UNSUPPORTED, "oip_seam_moments_blocks_u16: an overlap of more than 65535 * 64 samples");
+    OipProfScope prof(ctx, "seam_moments_blocks_kernel");
+    const long B = block_lines;
+    const long nb = L / B > 1 ? L / B : 1;
+    const long last = L - (nb - 1) * B;                              // B .. 2B - 1 lines, or all L of them
+    // ranges as oip_seam_moments_u16 sizes them (about 8 blocks per CU over the whole grid, 64 .. kWaves * kMaxLaneRows lines),
+    // then cut at the block boundaries
+    long want = (long)ctx->cu_count * 8 / gx;
+    if (want < 1) want = 1;
+    long rpr = (L + want - 1) / want;
+    if (rpr < 64) rpr = 64;
+    if (rpr > kWaves * kMaxLaneRows) rpr = kWaves * kMaxLaneRows;
+    const long per_block = nb > 1 ? (B - 1) / rpr + 1 : 0;           // (B <= L where it is used)
+    const long nranges = (nb - 1) * per_block + (last - 1) / rpr + 1;
+    const long gy = nranges < want ? nranges : want;                  // one resident set; the rest by grid stride
+    const bool mask = !(valid_min == 0 && valid_max == 65535);
+    const unsigned vmin = (unsigned)valid_min, vspan = (unsigned)(valid_max - valid_min);
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(d_acc);
+    const dim3 grid((unsigned)gy, (unsigned)gx), block(kBlock);
+#define OIP_SEAM_LAUNCH(M, S)                                                                                                                     \
+    hipLaunchKernelGGL((seam_moments_blocks_kernel<M, S>), grid, block, 0, ctx->stream, d_left, d_right, (long)Ws, L, fs2, vmin, vspan, acc, B, nb, \
+                       rpr, per_block, nranges)
+    if (spp == 1) { if (mask) OIP_SEAM_LAUNCH(true, 1); else OIP_SEAM_LAUNCH(false, 1); }
+    else          { if (mask) OIP_SEAM_LAUNCH(true, 4); else OIP_SEAM_LAUNCH(false, 4); }
+#undef OIP_SEAM_LAUNCH
+    OIP_HIP(ctx, hipGetLastError());
+    return OIP_OK;
+}
+
+extern "C" int oip_stitch_balanced_lines_u16(oip_ctx *ctx, const uint16_t *d_left, const uint16_t *d_right, uint16_t *d_out, int Ws, long L, int fs,
+                                             int spp, const int32_t *d_line_gain_q16, const int32_t *d_line_offset_q16, int feather, int valid_min)
+{
+    OIP_CHECK_CTX(ctx);
+    if (!d_left || !d_right || !d_out || !d_line_gain_q16 || !d_line_offset_q16 || ((uintptr_t)d_line_gain_q16 & 3) ||
+        ((uintptr_t)d_line_offset_q16 & 3) || ((uintptr_t)d_left & 1) || ((uintptr_t)d_right & 1) || ((uintptr_t)d_out & 1) ||
+        (spp != 1 && spp != 4) || Ws <= 0 || Ws % spp != 0 || fs < 0 || fs % spp != 0 || fs >= Ws || L < 0 || feather < 0 ||
+        (long)feather * spp > fs || valid_min > 65535)
+        return oip_fail(ctx, OIP_E_INVALID, "oip_stitch_balanced_lines_u16: bad argument");
+    if (feather > 16384)
+        return oip_fail(ctx, OIP_E_UNSUPPORTED, "oip_stitch_balanced_lines_u16: feather above 16384 pixels (the blend's 32-bit numerator)");
+    if (L == 0) return OIP_OK;
+    OipProfScope prof(ctx, "stitch_balanced_lines_kernel");
+    SeamGeom g;
+    g.Ws = Ws;
+    g.half = Ws - fs;
+    g.off_b = Ws - 2 * fs;
+    g.z0 = g.half - feather * spp;
+    g.z1 = g.half + feather * spp;
+    g.spp_shift = spp == 4 ? 2 : 0;
+    g.h2 = 2u * (unsigned)feather;
+    g.h4 = 4u * (unsigned)feather;
+    g.vmin = valid_min < 0 ? 0u : (unsigned)valid_min;
+    const int ow = 2 * g.half;
+    const bool tables16 = spp == 1 || ((((uintptr_t)d_line_gain_q16 | (uintptr_t)d_line_offset_q16) & 15) == 0);
+    const bool fast = (ow % 8 == 0) && (((uintptr_t)d_out & 15) == 0) && (((uintptr_t)d_left & 3) == 0) && (((uintptr_t)d_right & 3) == 0) &&
+                      ((long)Ws * L >= 16 && ((long)Ws * L) % 2 == 0) && tables16;
+    // one resident set of blocks (8 per CU), grid-stride over the rest
+    const long cap = (long)ctx->cu_count * 8;
+    if (fast) {
+        const long nchunks = (long)(ow / 8) * L;
+        long blocks = (nchunks + (long)kBlock * 4 - 1) / ((long)kBlock * 4);
+        if (blocks > cap) blocks = cap;
+        if (spp == 1)
+            hipLaunchKernelGGL(stitch_balanced_lines_kernel<1>, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, d_left, d_right, d_out, g, L,
+                               d_line_gain_q16, d_line_offset_q16);
+        else
+            hipLaunchKernelGGL(stitch_balanced_lines_kernel<4>, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, d_left, d_right, d_out, g, L,
+                               d_line_gain_q16, d_line_offset_q16);
+    } else {
+        const long n = (long)ow * L;
+        long blocks = (n + kBlock - 1) / kBlock;
+        if (blocks > cap) blocks = cap;
+        hipLaunchKernelGGL(stitch_balanced_lines_scalar_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, d_left, d_right, d_out, g, L,
+                           d_line_gain_q16, d_line_offset_q16, spp);
     }
     OIP_HIP(ctx, hipGetLastError());
     return OIP_OK;
