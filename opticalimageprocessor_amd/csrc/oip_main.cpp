@@ -31,6 +31,7 @@
 #include <set>
 
 #include "oip_host.hpp"
+#include "oip_rastertools.hpp"
 #include "oip_multigpu.hpp"
 
 using namespace OIPGPU;
@@ -94,6 +95,25 @@ Parsed parse(const Spec &sp, const std::vector<std::string> &args)
         }
         throw cli_error(109, "The following argument was not expected: " + args[i]);
     }
+    return p;
+}
+
+// The tools with one positional argument (quicklook, mtfc, despike): IMAGE, an existing regular file, is the first argument
+// that is neither an option nor the value of one (an option's value stays with it, alias or not); the rest is parsed as usual.
+Parsed parse_with_image(const Spec &sp, const std::vector<std::string> &args, std::string *image)
+{
+    std::vector<std::string> rest;
+    for (size_t i = 0; i < args.size(); ++i) {
+        const std::string &a = args[i];
+        if (!a.empty() && a[0] != '-' && image->empty()) { *image = a; continue; }
+        rest.push_back(a);
+        auto al = sp.alias.find(a);
+        if (sp.valued.count(al != sp.alias.end() ? al->second : a) && i + 1 < args.size()) rest.push_back(args[++i]);
+    }
+    Parsed p = parse(sp, rest);
+    if (image->empty()) throw cli_error(106, "IMAGE is required");
+    struct stat st;
+    if (stat(image->c_str(), &st) != 0 || !S_ISREG(st.st_mode)) throw cli_error(105, "IMAGE: File does not exist: " + *image);
     return p;
 }
 
@@ -506,18 +526,7 @@ int run_quicklook(const std::vector<std::string> &args, int width)
     sp.flags = {"--bil", "--force"};
     sp.alias = {{"-o", "--out"}};
     std::string image;
-    std::vector<std::string> rest;
-    for (size_t i = 0; i < args.size(); ++i) {
-        const std::string &a = args[i];
-        if (!a.empty() && a[0] != '-' && image.empty()) { image = a; continue; }
-        rest.push_back(a);
-        auto al = sp.alias.find(a);
-        if (sp.valued.count(al != sp.alias.end() ? al->second : a) && i + 1 < args.size()) rest.push_back(args[++i]);
-    }
-    Parsed p = parse(sp, rest);
-    if (image.empty()) throw cli_error(106, "IMAGE is required");
-    struct stat st;
-    if (stat(image.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) throw cli_error(105, "IMAGE: File does not exist: " + image);
+    Parsed p = parse_with_image(sp, args, &image);
     QuicklookOptions o;
     o.width = p.integer("--width", width);
     o.bil = p.flag.count("--bil") != 0;
@@ -554,18 +563,7 @@ int run_mtfc(const std::vector<std::string> &args, int width)
     sp.flags = {"--force"};
     sp.alias = {{"-o", "--out"}};
     std::string image;
-    std::vector<std::string> rest;
-    for (size_t i = 0; i < args.size(); ++i) {
-        const std::string &a = args[i];
-        if (!a.empty() && a[0] != '-' && image.empty()) { image = a; continue; }
-        rest.push_back(a);
-        auto al = sp.alias.find(a);
-        if (sp.valued.count(al != sp.alias.end() ? al->second : a) && i + 1 < args.size()) rest.push_back(args[++i]);
-    }
-    Parsed p = parse(sp, rest);
-    if (image.empty()) throw cli_error(106, "IMAGE is required");
-    struct stat st;
-    if (stat(image.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) throw cli_error(105, "IMAGE: File does not exist: " + image);
+    Parsed p = parse_with_image(sp, args, &image);
     const bool design = p.has("--mtf-x") || p.has("--mtf-y") || p.has("--max-gain");
     if (p.has("--kernel") && design) throw usage_error("--kernel and --mtf-x/--mtf-y/--max-gain exclude each other");
     if (!p.has("--kernel") && !design) throw usage_error("--kernel FILE or --mtf-x M --mtf-y M expected");
@@ -599,18 +597,7 @@ int run_despike(const std::vector<std::string> &args, int width)
     sp.flags = {"--bil", "--force"};
     sp.alias = {{"-o", "--out"}};
     std::string image;
-    std::vector<std::string> rest;
-    for (size_t i = 0; i < args.size(); ++i) {
-        const std::string &a = args[i];
-        if (!a.empty() && a[0] != '-' && image.empty()) { image = a; continue; }
-        rest.push_back(a);
-        auto al = sp.alias.find(a);
-        if (sp.valued.count(al != sp.alias.end() ? al->second : a) && i + 1 < args.size()) rest.push_back(args[++i]);
-    }
-    Parsed p = parse(sp, rest);
-    if (image.empty()) throw cli_error(106, "IMAGE is required");
-    struct stat st;
-    if (stat(image.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) throw cli_error(105, "IMAGE: File does not exist: " + image);
+    Parsed p = parse_with_image(sp, args, &image);
     // nobody has measured this sensor's noise: there is no default threshold, and without one only the listed columns are repaired
     if (!p.has("--threshold") && !p.has("--bad-columns")) throw usage_error("--threshold N or --bad-columns FILE expected");
     if (p.has("--relative") && !p.has("--threshold")) throw cli_error(107, "--relative requires --threshold");

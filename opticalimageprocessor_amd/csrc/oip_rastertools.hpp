@@ -1,0 +1,574 @@
+// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike) above the
+// host layer of oip_host.hpp: what they check before a device is touched, the one driver that streams a RAW strip through
+// the device in line blocks (geometry: oip_stripplan.hpp), the resident filter of a TIFF product, and the four tools.
+#pragma once
+
+#include "oip_host.hpp"
+#include "oip_stripplan.hpp"
+
+namespace OIPGPU {
+
+// ---- what the tools refuse without a device ---------------------------------------------------------------------
+// the container of an image by its extension: ".raw" or ".tiff"
+inline std::string RasterContainer(const std::string &file, const char *tool)
+{
+    const std::string ext = to_lower(std::filesystem::path(file).extension().string());
+    if (ext != ".tiff" && ext != ".raw") throw std::invalid_argument(std::string(tool) + ": only RAW and TIFF image supported");
+    return ext;
+}
+
+// the lines of a RAW file of lineBytes per line; CheckFilesAttributes' size rule (preproc.h:552-572)
+inline long RawLineCount(const std::string &file, const char *what, size_t lineBytes)
+{
+    const size_t size = IMO::FileSize(file);
+    if (size == 0 || size % lineBytes != 0)
+        throw std::invalid_argument(std::string(what) + " file size invalid: should be multiplies of " + std::to_string(lineBytes));
+    return (long)(size / lineBytes);
+}
+
+// the lines [first, first + count) of `file` that --line-offset / --lines (0: to the end) select; returns the file's lines
+inline long RawLineRange(const std::string &file, const char *what, int width, long lineOffset, long lines, long *first, long *count)
+{
+    const long total = RawLineCount(file, what, (size_t)width * BYTES_PER_PIXEL);
+    if (lineOffset >= total) throw std::invalid_argument(std::string(what) + " file has " + std::to_string(total) + " lines: --line-offset is beyond them");
+    *first = lineOffset;
+    *count = lines > 0 ? std::min(lines, total - lineOffset) : total - lineOffset;
+    return total;
+}
+
+// the product of a filter (mtfc, despike): <stem><suffix><ext> unless named, in the container `ext` of the input, never the
+// input itself, and an existing file only with --force
+inline std::string FilterOutputPath(const std::string &file, const std::string &out, const char *suffix, const std::string &ext, const char *tool, bool force)
+{
+    const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, suffix) : out;
+    if (to_lower(std::filesystem::path(path).extension().string()) != ext)
+        throw std::invalid_argument(std::string(tool) + ": the output has the container of the input (" + ext + ")");
+    struct stat st;
+    if (stat(path.c_str(), &st) == 0) {
+        if (std::filesystem::equivalent(path, file)) throw std::invalid_argument("output file [" + path + "] is the input image");
+        if (!force) throw std::runtime_error("output file [" + path + "] exists: " + tool + " does not replace a file without --force");
+    }
+    return path;
+}
+
+// OIP_MTFC_BLOCK_LINES / OIP_DESPIKE_BLOCK_LINES (test hooks: several blocks on a small image); 0 without one
+inline long BlockLinesHook(const char *name) { const char *e = getenv(name); return e ? atol(e) : 0; }
+
+// ---- the strip-streaming driver ---------------------------------------------------------------------------------
+// A RAW strip is never resident.  The line blocks of `plan` go file -> pinned ring -> one of two device blocks; work(src,
+// srcFirst, srcLines, dst, dstFirst, dstLines) of a block runs behind its upload (ticket) while the host reads the next
+// block from the file into the pinned ring.  With an output (outPath != NULL) the block's dstLines lines go from one of two
+// further device blocks to their byte offset in the product on a writer thread behind a compute mark: read || kernel ||
+// write.  Without one, dst is NULL and nothing is written.
+template <class Work> inline void StreamStrip(const std::string &file, const StripPlan &plan, const std::string *outPath, Work work)
+{
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    DevBuf<uint16_t> in[2], res[2];
+    for (int i = 0; i < (plan.secondSlot() ? 2 : 1); ++i) {
+        in[i].alloc((size_t)plan.inLines() * plan.lineBytes / BYTES_PER_PIXEL);
+        if (outPath) res[i].alloc((size_t)plan.outLines() * plan.lineBytes / BYTES_PER_PIXEL);
+    }
+    if (outPath) { FILE *f = fopen(outPath->c_str(), "wb"); if (!f) throw std::runtime_error("open file [" + *outPath + "] failed: " + std::to_string(errno)); fclose(f); }
+    OLOG("Reading raw image from file `%s' ...", file.c_str());
+    std::future<void> written[2];
+    std::unique_ptr<JobThread> writer(outPath ? new JobThread : nullptr);      // (declared after the buffers: joined before they are released)
+    for (long i = 0; i < plan.blocks(); ++i) {
+        const StripBlock b = plan.block(i);
+        uint16_t *d = in[b.slot].p, *q = res[b.slot].p;
+        // uploads do not wait for the compute stream: the kernel that read this buffer two blocks ago goes first (the call orders
+        // the upload behind the previous block's kernel as well -- a kernel is ~1 % of a block's transfer time)
+        if (i >= 2) ck(oip_stage_order_after_compute(ctx));
+        size_t got = 0;
+        long ticket = 0;
+        ck(oip_read_file_to_device(ctx, file.c_str(), b.srcOffset, b.srcBytes, d, &got, &ticket));
+        if (got != b.srcBytes)
+            throw std::runtime_error("file size(" + std::to_string(b.srcOffset + b.srcBytes) + ") doesn't match with read byte count(" +
+                                     std::to_string(b.srcOffset + got) + ")");
+        ck(oip_stage_wait(ctx, ticket));
+        if (written[b.slot].valid()) {                                  // the output block of two blocks ago is in the file
+            try { written[b.slot].get(); } catch (const std::future_error &) { writer->finish(); throw; }      // (a failed writer drops its jobs)
+        }
+        work(d, b.srcFirst, b.srcLines, q, b.dstFirst, b.dstLines);
+        if (!outPath) continue;
+        long mark = 0;
+        ck(oip_compute_mark(ctx, &mark));
+        auto done = std::make_shared<std::promise<void>>();
+        written[b.slot] = done->get_future();
+        writer->post([=] {                                              // (outPath is the caller's: it outlives the writer, joined in here)
+            const int rc = oip_write_device_to_file_at(ctx, q, b.dstBytes, outPath->c_str(), b.dstOffset, mark);
+            done->set_value();                                          // the buffer is free either way; finish() reports a failure
+            Device::get().check(rc);
+        });
+    }
+    if (writer) writer->finish();
+}
+
+// read only: work(src, firstLineInRange, lines)
+template <class Work> inline void ReadStrip(const std::string &file, const StripPlan &plan, Work work)
+{
+    StreamStrip(file, plan, nullptr, [&](const uint16_t *src, long s0, long lines, uint16_t *, long, long) { work(src, s0 - plan.first, lines); });
+}
+
+// A TIFF product is filtered resident, by one work(src, dst, w, h, spp), and leaves through the product writer of `oip
+// stitch`; `word` is the tool's for what it writes.  Returns the bytes of the image.
+template <class Work> inline size_t FilterTiffResident(const std::string &file, const std::string &outPath, const char *tool, const char *word, Work work)
+{
+    int w = 0, spp = 0;
+    long h = 0;
+    DevBuf<uint16_t> img;
+    OLOG("Reading image from file `%s' ...", file.c_str());
+    read_tiff_to_device(file, &w, &h, &spp, img);
+    if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument(std::string(tool) + ": a TIFF of 1 or 4 samples per pixel expected");
+    DevBuf<uint16_t> res((size_t)w * h * spp);
+    work(img.p, res.p, w, h, spp);
+    OLOG("Write %s image to file '%s' ...", word, outPath.c_str());
+    write_tiff_from_device(outPath, res.p, w, h, spp, tiff_compression(spp == 1 ? TIFF_NONE : TIFF_LZW), false);
+    return (size_t)w * h * spp * BYTES_PER_PIXEL;
+}
+
+// ---- oip rrc-calib: the coefficient files every other action consumes --------------------------------
+// One read-only pass over a strip accumulates every column's count, sum and sum of squares (oip_colstats_u16); moment
+// matching on those totals (oip_rrc_fit_columns) gives each column the (k, b) that brings its statistics to the sensor-wide
+// ones, written in the format IMO::LoadRRCParamFile reads (imageop.h:140-192).  Not in the reference, which only consumes
+// such files.
+struct RrcCalibOptions {
+    int width = OIP_PIXELS_PER_LINE;
+    int mode = OIP_RRCFIT_MOMENTS;
+    int validMin = 0, validMax = 65535;
+    long minCount = 0;
+    long lineOffset = 0, lines = 0;         // lines == 0: to the end of the file
+    bool force = false;
+    std::string badPan, badMss;             // --bad-pan / --bad-mss: the columns the fit refuses, as `oip despike --bad-columns` reads them
+};
+
+// The statistics kernel runs per line block of the strip (ReadStrip).  `groups` equal column groups.  Returns the fitted W
+// (k, b) pairs, and in `deadCols` (may be NULL) the columns the fit refused; nothing is written here.
+inline std::vector<double> RrcCalibImage(const std::string &file, const char *what, int groups, const RrcCalibOptions &o, std::vector<int> *deadCols = nullptr)
+{
+    const int W = o.width, gw = W / groups;
+    long first = 0, nLines = 0;
+    const long L = RawLineRange(file, what, W, o.lineOffset, o.lines, &first, &nLines);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    const size_t lineBytes = (size_t)W * BYTES_PER_PIXEL;
+    DevBuf<uint64_t> acc((size_t)3 * W);
+    ck(oip_memset(ctx, acc.p, 0, (size_t)3 * W * sizeof(uint64_t)));
+    stop_watch sw;
+    ReadStrip(file, StripPlan{first, nLines, L, 0, StripBlockLines(lineBytes), lineBytes},
+              [&](const uint16_t *d, long, long m) { ck(oip_colstats_u16(ctx, d, W, W, m, o.validMin, o.validMax, acc.p)); });
+    std::vector<uint64_t> totals((size_t)3 * W);
+    acc.download(totals.data(), totals.size());
+    const double es = sw.tick();
+    const size_t bytes = (size_t)nLines * lineBytes;
+    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+
+    std::vector<double> kb((size_t)2 * W), ref((size_t)2 * groups);
+    std::vector<int> dead(groups);
+    char err[1024] = "";
+    const int rc = oip_rrc_fit_columns(totals.data(), W, groups, o.mode, (uint64_t)o.minCount, kb.data(), dead.data(), ref.data(), err, sizeof err);
+    if (rc == OIP_E_INVALID) throw std::invalid_argument(err);
+    if (rc != OIP_OK) throw std::runtime_error(err);
+    for (int g = 0; g < groups; ++g) {
+        double kmin = INFINITY, kmax = -INFINITY, bmin = INFINITY, bmax = -INFINITY;
+        for (int i = 0; i < gw; ++i) {
+            const double k = kb[2 * ((size_t)g * gw + i)], b = kb[2 * ((size_t)g * gw + i) + 1];
+            kmin = std::min(kmin, k); kmax = std::max(kmax, k); bmin = std::min(bmin, b); bmax = std::max(bmax, b);
+        }
+        OLOG("%s%s: %ld lines, %d usable / %d dead columns, mu_ref %.6f, sigma_ref %.6f, k in [%.9f, %.9f], b in [%.6f, %.6f]", what,
+             groups > 1 ? (" band " + std::to_string(g + 1)).c_str() : "", nLines, gw - dead[g], dead[g], ref[2 * g], ref[2 * g + 1], kmin, kmax, bmin,
+             bmax);
+    }
+    if (deadCols) {
+        deadCols->resize(W);
+        int n = 0;
+        if (oip_rrc_dead_columns(totals.data(), W, o.mode, (uint64_t)o.minCount, deadCols->data(), &n) != OIP_OK) throw std::invalid_argument("oip_rrc_dead_columns: bad argument");
+        deadCols->resize(n);
+    }
+    return kb;
+}
+
+// everything that can be refused without a device: sizes, line range, outputs named twice, outputs that exist
+inline void RrcCalibCheck(const std::string &pan, const std::string &mss, const std::string &outPan, const std::string *outMss, const RrcCalibOptions &o)
+{
+    long a = 0, b = 0;
+    if (o.width <= 0 || (!mss.empty() && o.width % MSS_BANDS != 0)) throw std::invalid_argument("--width: a positive line width (a multiple of 4 for MSS) expected");
+    if (!pan.empty()) RawLineRange(pan, "PAN", o.width, o.lineOffset, o.lines, &a, &b);
+    if (!mss.empty()) RawLineRange(mss, "MSS", o.width, o.lineOffset, o.lines, &a, &b);
+    std::vector<std::string> outs;
+    if (!pan.empty()) outs.push_back(outPan);
+    for (int i = 0; i < MSS_BANDS && !mss.empty(); ++i) outs.push_back(outMss[i]);
+    if (!o.badPan.empty()) outs.push_back(o.badPan);
+    if (!o.badMss.empty()) outs.push_back(o.badMss);
+    for (size_t i = 0; i < outs.size(); ++i)
+        for (size_t j = i + 1; j < outs.size(); ++j)
+            if (outs[i] == outs[j] || (std::filesystem::exists(outs[i]) && std::filesystem::exists(outs[j]) && std::filesystem::equivalent(outs[i], outs[j])))
+                throw std::invalid_argument("output file [" + outs[i] + "] is named for two outputs");
+    struct stat st;
+    for (const auto &f : outs)
+        if (!o.force && stat(f.c_str(), &st) == 0)
+            throw std::runtime_error("output file [" + f + "] exists: calibration does not replace a coefficient file without --force");
+}
+
+inline void RunRrcCalib(const std::string &pan, const std::string &mss, const std::string &outPan, const std::string *outMss, const RrcCalibOptions &o)
+{
+    RrcCalibCheck(pan, mss, outPan, outMss, o);
+    // every image and group is fitted before the first file is written: a band without a usable column leaves no partial set
+    std::vector<double> kbPan, kbMss;
+    std::vector<int> deadPan, deadMss;
+    if (!pan.empty()) kbPan = RrcCalibImage(pan, "PAN", 1, o, o.badPan.empty() ? nullptr : &deadPan);
+    if (!mss.empty()) kbMss = RrcCalibImage(mss, "MSS", MSS_BANDS, o, o.badMss.empty() ? nullptr : &deadMss);
+    auto write = [](const std::string &path, const double *kb, int n) {
+        char err[1024] = "";
+        if (oip_write_rrc_param_file(path.c_str(), kb, n, err, sizeof err) != OIP_OK) throw errno_error(err, 0);
+        OLOG("RRC parameters written to file [%s].", path.c_str());
+    };
+    if (!pan.empty()) write(outPan, kbPan.data(), o.width);
+    const int bw = o.width / MSS_BANDS;
+    for (int b = 0; b < MSS_BANDS && !mss.empty(); ++b) write(outMss[b], &kbMss[2 * (size_t)b * bw], bw);
+    // the columns the fit refused, behind the coefficient files: the list `oip despike --bad-columns` reads
+    auto writeList = [&](const std::string &path, const std::vector<int> &cols, const std::string &image) {
+        char err[1024] = "";
+        const std::string comment = "columns of " + image + " (" + std::to_string(o.width) + " samples per line) without usable statistics: oip rrc-calib --mode " +
+                                    (o.mode == OIP_RRCFIT_MOMENTS ? "moments" : "gain");
+        if (oip_write_column_list(path.c_str(), cols.data(), (int)cols.size(), comment.c_str(), err, sizeof err) != OIP_OK) throw errno_error(err, 0);
+        OLOG("%zu bad columns written to file [%s].", cols.size(), path.c_str());
+    };
+    if (!o.badPan.empty()) writeList(o.badPan, deadPan, pan);
+    if (!o.badMss.empty()) writeList(o.badMss, deadMss, mss);
+}
+
+// ---- oip quicklook: an 8-bit browse image of a strip or product ---------------------------------------------
+// The products are too large to look at (a stitched PAN strip is ~4.8 GB of 12-bit values in 16-bit samples): one read-only
+// pass box-decimates the image by F x F (oip_decimate_box_u16), and everything behind it works on planes F^2 times smaller --
+// per band a histogram (oip_histogram_u16), percentile limits and an 8-bit table on the host (oip_stretch_limits,
+// oip_stretch_lut_u8), one look-up kernel (oip_apply_lut_u8) and an uncompressed 8-bit TIFF.  Not in the reference.
+struct QuicklookOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    bool bil = false;                       // RAW input: the MSS line layout, 4 bands of width / 4 next to each other
+    int factor = OIP_QUICKLOOK_DEF_FACTOR;
+    double clipLow = OIP_QUICKLOOK_DEF_CLIPLOW, clipHigh = OIP_QUICKLOOK_DEF_CLIPHIGH;
+    int validMin = 1, validMax = 65535;     // 0 is the border value of prestitch and the aligner (BORDER_CONSTANT)
+    std::vector<int> bands;                 // 1-based; empty: 1 for one band, 1,2,3 for four
+    long lineOffset = 0, lines = 0;         // lines == 0: to the end of the image
+    bool force = false;
+};
+
+// everything that can be refused without a device; returns the output path and whether the input is a TIFF
+inline std::string QuicklookCheck(const std::string &file, const std::string &out, const QuicklookOptions &o, bool *isTiff)
+{
+    *isTiff = RasterContainer(file, "quicklook") == ".tiff";
+    const int F = o.factor;
+    if (F != 2 && F != 4 && F != 8 && F != 16 && F != 32 && F != 64) throw usage_error("--factor: one of 2, 4, 8, 16, 32, 64 expected");
+    if (o.bands.size() > 3 || o.bands.size() == 2) throw usage_error("--bands: one band (grey) or three (RGB) expected");
+    if (!*isTiff) {
+        const int nb = o.bil ? MSS_BANDS : 1;
+        for (int b : o.bands)
+            if (b < 1 || b > nb) throw usage_error("--bands: band index out of range (1.." + std::to_string(nb) + ")");
+        if (o.width <= 0 || (o.bil && o.width % MSS_BANDS != 0)) throw std::invalid_argument("--width: a positive line width (a multiple of 4 with --bil) expected");
+    } else {
+        for (int b : o.bands)
+            if (b < 1 || b > MSS_BANDS) throw usage_error("--bands: band index out of range (1.." + std::to_string(MSS_BANDS) + ")");
+    }
+    // (not FilterOutputPath: a quick look is a .TIFF whatever the input is, and may be named like anything but an existing file)
+    const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_QUICKLOOK_SUFFIX, ".TIFF") : out;
+    struct stat st;
+    if (!o.force && stat(path.c_str(), &st) == 0)
+        throw std::runtime_error("output file [" + path + "] exists: quicklook does not replace a file without --force");
+    return path;
+}
+
+inline void RunQuicklook(const std::string &file, const std::string &out, const QuicklookOptions &o)
+{
+    bool isTiff = false;
+    const std::string outPath = QuicklookCheck(file, out, o, &isTiff);
+    const int F = o.factor;
+    long first = 0, nLines = 0, fileLines = 0;
+    int bw = 0, nb = 0;                     // band width in pixels, bands of the image
+    if (!isTiff) {
+        fileLines = RawLineRange(file, "image", o.width, o.lineOffset, o.lines, &first, &nLines);
+        nb = o.bil ? MSS_BANDS : 1;
+        bw = o.width / nb;
+    }
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    size_t inBytes = 0;
+    DevBuf<uint16_t> planes;
+    int ow = 0;
+    long oh = 0;
+    size_t plane = 0;
+    auto alloc_planes = [&]() {
+        ow = (bw + F - 1) / F;
+        oh = (nLines + F - 1) / F;
+        plane = (size_t)ow * oh;
+        planes.alloc(plane * nb);
+    };
+    if (isTiff) {
+        int w = 0, spp = 0;
+        long h = 0;
+        DevBuf<uint16_t> img;
+        OLOG("Reading image from file `%s' ...", file.c_str());
+        read_tiff_to_device(file, &w, &h, &spp, img);
+        if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument("quicklook: a TIFF of 1 or 4 samples per pixel expected");
+        if (o.lineOffset >= h) throw std::invalid_argument("image has " + std::to_string(h) + " lines: --line-offset is beyond them");
+        first = o.lineOffset;
+        nLines = o.lines > 0 ? std::min(o.lines, h - first) : h - first;
+        nb = spp;
+        bw = w;
+        for (int b : o.bands)
+            if (b > nb) throw usage_error("--bands: band index out of range (1.." + std::to_string(nb) + ")");
+        alloc_planes();
+        ck(oip_decimate_box_u16(ctx, img.p + (size_t)first * w * spp, (long)w * spp, w, nLines, spp, F, planes.p, ow, plane));
+        ck(oip_sync(ctx));                  // img is released at the end of this block
+        inBytes = (size_t)nLines * w * spp * BYTES_PER_PIXEL;
+    } else {
+        // the decimation runs per line block of the strip (ReadStrip), a block being a multiple of F lines
+        const size_t lineBytes = (size_t)o.width * BYTES_PER_PIXEL;
+        alloc_planes();
+        ReadStrip(file, StripPlan{first, nLines, fileLines, 0, StripBlockLines(lineBytes, F), lineBytes}, [&](const uint16_t *d, long r, long m) {
+            for (int b = 0; b < nb; ++b)    // a BIL band is a window of the line
+                ck(oip_decimate_box_u16(ctx, d + (size_t)b * bw, o.width, bw, m, 1, F, planes.p + (size_t)b * plane + (size_t)(r / F) * ow, ow, 0));
+        });
+        ck(oip_sync(ctx));
+        inBytes = (size_t)nLines * lineBytes;
+    }
+    std::vector<int> bands = o.bands;
+    if (bands.empty()) bands = nb == 1 ? std::vector<int>{1} : std::vector<int>{1, 2, 3};
+    const int nch = (int)bands.size();
+
+    // per band: histogram of the decimated plane -> limits -> table
+    DevBuf<uint64_t> hist(65536);
+    DevBuf<uint8_t> luts((size_t)nch * 65536);
+    std::vector<uint64_t> h(65536);
+    std::vector<uint8_t> lut((size_t)nch * 65536);
+    const uint16_t *chan[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < nch; ++i) {
+        chan[i] = planes.p + (size_t)(bands[i] - 1) * plane;
+        ck(oip_memset(ctx, hist.p, 0, 65536 * sizeof(uint64_t)));
+        ck(oip_histogram_u16(ctx, chan[i], ow, ow, oh, hist.p));
+        hist.download(h.data(), h.size());
+        int lo = 0, hi = 0;
+        uint64_t nValid = 0;
+        if (oip_stretch_limits(h.data(), o.validMin, o.validMax, o.clipLow, o.clipHigh, &lo, &hi, &nValid) != OIP_OK ||
+            oip_stretch_lut_u8(lo, hi, &lut[(size_t)i * 65536]) != OIP_OK)
+            throw std::invalid_argument("quicklook: invalid stretch arguments");
+        OLOG("band %d: %ld lines, %llu valid samples, stretch %d..%d", bands[i], nLines, (unsigned long long)nValid, lo, hi);
+    }
+    luts.upload(lut.data(), lut.size());
+    DevBuf<uint8_t> img8(plane * nch);
+    ck(oip_apply_lut_u8(ctx, chan, ow, ow, oh, nch, luts.p, img8.p));
+    std::vector<uint8_t> host(plane * nch);
+    img8.download(host.data(), host.size());
+    OLOG("Write quick look (%d x %ld, %s) to file '%s' ...", ow, oh, nch == 1 ? "grey" : "RGB", outPath.c_str());
+    write_tiff_u8(outPath, host.data(), ow, oh, nch);
+    const double es = total.tick();
+    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", inBytes, es, inBytes / es / 1024.0 / 1024.0);
+}
+
+// ---- oip mtfc: MTF compensation of a strip or product ---------------------------------------------------------------
+// A small fixed-point restoration filter (oip_convolve_u16) behind the radiometric correction: the taps come from a kernel
+// file or from the MTF at Nyquist of the two axes (oip_mtfc_load_kernel / oip_mtfc_design3, then oip_mtfc_quantise).  The
+// output has the container of the input.  Not in the reference.
+struct MtfcOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    std::string kernelFile;                 // --kernel, or
+    double mtfX = 0.0, mtfY = 0.0;          // --mtf-x / --mtf-y: the MTF at Nyquist across and along the lines
+    double maxGain = OIP_MTFC_DEF_MAXGAIN;
+    int validMin = 1;                       // 0 is the border value of prestitch and the aligner (BORDER_CONSTANT)
+    bool force = false;
+};
+
+struct MtfcTaps {
+    int ky = 0, kx = 0;
+    int32_t t[OIP_CONVOLVE_MAX_K * OIP_CONVOLVE_MAX_K];
+};
+
+// everything that can be refused without a device: the container, the taps, the output; returns the output path
+inline std::string MtfcCheck(const std::string &file, const std::string &out, const MtfcOptions &o, bool *isTiff, MtfcTaps *taps)
+{
+    const std::string ext = RasterContainer(file, "mtfc");
+    *isTiff = ext == ".tiff";
+    if (!*isTiff) {
+        if (o.width <= 0) throw std::invalid_argument("--width: a positive line width expected");
+        RawLineCount(file, "image", (size_t)o.width * BYTES_PER_PIXEL);
+    }
+    double c[OIP_CONVOLVE_MAX_K * OIP_CONVOLVE_MAX_K];
+    char err[1024] = "";
+    if (!o.kernelFile.empty()) {
+        const int rc = oip_mtfc_load_kernel(o.kernelFile.c_str(), c, &taps->ky, &taps->kx, err, sizeof err);
+        if (rc == OIP_E_IO) throw errno_error(err, 0);
+        if (rc != OIP_OK) throw std::invalid_argument(err);
+    } else {
+        taps->ky = taps->kx = 3;
+        if (oip_mtfc_design3(o.mtfX, o.mtfY, o.maxGain, c) != OIP_OK) throw std::invalid_argument("--mtf-x/--mtf-y/--max-gain: 0 < M <= 1 and G >= 1 expected");
+    }
+    if (oip_mtfc_quantise(c, taps->ky, taps->kx, taps->t, err, sizeof err) != OIP_OK) throw std::invalid_argument(err);
+    return FilterOutputPath(file, out, OIP_MTFC_SUFFIX, ext, "mtfc", o.force);
+}
+
+inline void RunMtfc(const std::string &file, const std::string &out, const MtfcOptions &o)
+{
+    bool isTiff = false;
+    MtfcTaps taps;
+    const std::string outPath = MtfcCheck(file, out, o, &isTiff, &taps);
+    const int ky = taps.ky, kx = taps.kx, ry = ky / 2;
+    long absSum = 0;
+    OLOG("MTFC taps (Q12, %d x %d):", ky, kx);
+    for (int j = 0; j < ky; ++j) {
+        std::string row;
+        for (int i = 0; i < kx; ++i) {
+            row += (i ? " " : "") + std::to_string(taps.t[j * kx + i]);
+            absSum += std::abs((long)taps.t[j * kx + i]);
+        }
+        RLOG("    %s", row.c_str());
+    }
+    OLOG("sum |t| = %ld (gain at most %.3f), valid-min %d", absSum, absSum / 4096.0, o.validMin);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    size_t bytes = 0;
+    if (isTiff) {
+        bytes = FilterTiffResident(file, outPath, "mtfc", "filtered", [&](const uint16_t *src, uint16_t *dst, int w, long h, int spp) {
+            ck(oip_convolve_u16(ctx, src, 0, h, dst, 0, h, w, h, spp, taps.t, ky, kx, o.validMin));
+        });
+    } else {
+        // the filter runs per line block of the strip, with ry halo lines either side (StreamStrip)
+        const size_t lineBytes = (size_t)o.width * BYTES_PER_PIXEL;
+        const long L = RawLineCount(file, "image", lineBytes);
+        StreamStrip(file, StripPlan{0, L, L, ry, StripBlockLines(lineBytes, 1, BlockLinesHook("OIP_MTFC_BLOCK_LINES")), lineBytes}, &outPath,
+                   [&](const uint16_t *d, long s0, long sn, uint16_t *q, long r, long m) {
+                       ck(oip_convolve_u16(ctx, d, s0, sn, q, r, m, o.width, L, 1, taps.t, ky, kx, o.validMin));
+                   });
+        bytes = (size_t)L * lineBytes;
+    }
+    const double es = total.tick();
+    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+}
+
+// ---- oip despike: repair of a raw strip ahead of RRC ------------------------------------------------------------------
+// Listed bad columns are interpolated and isolated impulse pixels replaced by a conditional 3 x 3 median (oip_despike_u16)
+// before RRC multiplies them and a resampling spreads them.  The list comes from `oip rrc-calib --bad-pan / --bad-mss` or
+// from a --report of an earlier run.  The output has the container of the input.  Not in the reference.
+struct DespikeOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    bool bil = false;                       // RAW input: the MSS line layout, 4 bands of width / 4 next to each other
+    bool hasThreshold = false;              // without --threshold: column repair only (thr_abs 65535)
+    int thrAbs = 65535, thrRelQ8 = 0;
+    int validMin = 1;                       // 0 is what the de-framer writes for missing frames
+    std::string badColumns, report;
+    bool force = false;
+};
+
+struct DespikeTable {
+    std::vector<int32_t> tab;               // empty: no list
+    int listed = 0, longestRun = 0;
+};
+
+// everything that can be refused without a device: the container, sizes, the list and its table, the outputs; returns the output path
+inline std::string DespikeCheck(const std::string &file, const std::string &out, const DespikeOptions &o, bool *isTiff, DespikeTable *table)
+{
+    const std::string ext = RasterContainer(file, "despike");
+    *isTiff = ext == ".tiff";
+    if (*isTiff) {
+        if (!o.badColumns.empty() || o.bil)
+            throw std::invalid_argument("despike: --bad-columns and --bil apply to a RAW strip: the columns of a TIFF product are no longer detector columns");
+    } else {
+        if (o.width <= 0 || (o.bil && o.width % MSS_BANDS != 0)) throw std::invalid_argument("--width: a positive line width (a multiple of 4 with --bil) expected");
+        RawLineCount(file, "image", (size_t)o.width * BYTES_PER_PIXEL);
+    }
+    if (!o.badColumns.empty()) {
+        const int W = o.width;
+        std::vector<int> cols(W);
+        char err[1024] = "";
+        int n = 0;
+        int rc = oip_load_column_list(o.badColumns.c_str(), W, cols.data(), W, &n, err, sizeof err);
+        if (rc == OIP_E_IO) throw errno_error(err, 0);
+        if (rc != OIP_OK) throw std::invalid_argument(err);
+        table->tab.resize((size_t)2 * W);
+        rc = oip_despike_column_table(cols.data(), n, W, o.bil ? MSS_BANDS : 1, table->tab.data(), &table->longestRun, err, sizeof err);
+        if (rc != OIP_OK) throw std::invalid_argument(err);
+        table->listed = n;
+    }
+    const std::string path = FilterOutputPath(file, out, OIP_DESPIKE_SUFFIX, ext, "despike", o.force);
+    if (!o.report.empty()) {
+        struct stat st;
+        const bool exists = stat(o.report.c_str(), &st) == 0;
+        const bool same = std::filesystem::absolute(o.report).lexically_normal() == std::filesystem::absolute(path).lexically_normal();
+        if (same || (exists && (std::filesystem::equivalent(o.report, file) || (stat(path.c_str(), &st) == 0 && std::filesystem::equivalent(o.report, path)))))
+            throw std::invalid_argument("report file [" + o.report + "] is the input image or the output");
+        if (exists && !o.force) throw std::runtime_error("report file [" + o.report + "] exists: despike does not replace a file without --force");
+    }
+    return path;
+}
+
+inline void RunDespike(const std::string &file, const std::string &out, const DespikeOptions &o)
+{
+    bool isTiff = false;
+    DespikeTable table;
+    const std::string outPath = DespikeCheck(file, out, o, &isTiff, &table);
+    if (o.hasThreshold) OLOG("despike: threshold %d + %d / 256 of the median, valid-min %d", o.thrAbs, o.thrRelQ8, o.validMin);
+    else OLOG("despike: column repair only (no --threshold), valid-min %d", o.validMin);
+    if (!o.badColumns.empty()) OLOG("%d bad columns listed in [%s], longest run %d", table.listed, o.badColumns.c_str(), table.longestRun);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    size_t bytes = 0;
+    DevBuf<uint64_t> cnt;                                               // replacements per sample column; only a threshold replaces
+    std::vector<uint64_t> counts;
+    auto alloc_counts = [&](size_t n) {
+        if (!o.hasThreshold) return;
+        cnt.alloc(n);
+        ck(oip_memset(ctx, cnt.p, 0, n * sizeof(uint64_t)));
+        counts.resize(n);
+    };
+    if (isTiff) {
+        bytes = FilterTiffResident(file, outPath, "despike", "repaired", [&](const uint16_t *src, uint16_t *dst, int w, long h, int spp) {
+            alloc_counts((size_t)w * spp);
+            ck(oip_despike_u16(ctx, src, 0, h, dst, 0, h, w, h, spp, 1, nullptr, o.thrAbs, o.thrRelQ8, o.validMin, cnt.p));
+        });
+    } else {
+        // the kernel runs per line block of the strip, with one halo line either side (StreamStrip)
+        const int W = o.width;
+        const size_t lineBytes = (size_t)W * BYTES_PER_PIXEL;
+        const long L = RawLineCount(file, "image", lineBytes);
+        DevBuf<int32_t> tab;
+        if (!table.tab.empty()) {
+            tab.alloc(table.tab.size());
+            tab.upload(table.tab.data(), table.tab.size());
+        }
+        alloc_counts((size_t)W);
+        StreamStrip(file, StripPlan{0, L, L, 1, StripBlockLines(lineBytes, 1, BlockLinesHook("OIP_DESPIKE_BLOCK_LINES")), lineBytes}, &outPath,
+                   [&](const uint16_t *d, long s0, long sn, uint16_t *q, long r, long m) {
+                       ck(oip_despike_u16(ctx, d, s0, sn, q, r, m, W, L, 1, o.bil ? MSS_BANDS : 1, tab.p, o.thrAbs, o.thrRelQ8, o.validMin, cnt.p));
+                   });
+        bytes = (size_t)L * lineBytes;
+    }
+    if (o.hasThreshold) {
+        cnt.download(counts.data(), counts.size());                     // (synchronises: the last kernel has run)
+        uint64_t sum = 0;
+        std::vector<size_t> hit;
+        for (size_t x = 0; x < counts.size(); ++x)
+            if (counts[x]) { sum += counts[x]; hit.push_back(x); }
+        OLOG("%llu samples replaced in %zu of %zu columns", (unsigned long long)sum, hit.size(), counts.size());
+        if (!o.report.empty()) {
+            FILE *f = fopen(o.report.c_str(), "wb");
+            if (!f) throw std::runtime_error("open file [" + o.report + "] failed: " + std::to_string(errno));
+            fprintf(f, "# column count: samples replaced by oip despike --threshold %d in %s\n", o.thrAbs, file.c_str());
+            for (size_t x : hit) fprintf(f, "%zu %llu\n", x, (unsigned long long)counts[x]);
+            if (fclose(f) != 0) throw std::runtime_error("write of file [" + o.report + "] failed");
+            OLOG("Replacement counts written to file [%s].", o.report.c_str());
+        }
+        std::stable_sort(hit.begin(), hit.end(), [&](size_t a, size_t b) { return counts[a] > counts[b]; });
+        for (size_t i = 0; i < hit.size() && i < 10; ++i) RLOG("    column %zu: %llu", hit[i], (unsigned long long)counts[hit[i]]);
+    } else if (!o.report.empty()) {
+        FILE *f = fopen(o.report.c_str(), "wb");
+        if (!f) throw std::runtime_error("open file [" + o.report + "] failed: " + std::to_string(errno));
+        fprintf(f, "# column count: no --threshold, no sample replaced in %s\n", file.c_str());
+        fclose(f);
+    }
+    const double es = total.tick();
+    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+}
+
+}  // namespace OIPGPU

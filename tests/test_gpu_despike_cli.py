@@ -158,3 +158,29 @@ def test_calibration_lists_the_dead_columns_and_despike_fills_them(tmp_path, bil
     assert r.returncode == 0, r.stdout + r.stderr
     assert " dead columns" in r.stdout and not re.search(r"/ [1-9]\d* dead columns", r.stdout)
     assert ref.parse_column_list(os.path.join(d, "bad2.txt"), W) == []
+
+
+def test_counts_do_not_depend_on_how_the_strip_is_cut(tmp_path):
+    """96 x 23 in the MSS line layout with --threshold and a list.  OIP_DESPIKE_BLOCK_LINES 1 and 2 reuse every device block
+    many times with the halo line clamped at both ends of the strip; 23 is exactly one block; 24 is larger than the strip, so no
+    second block is allocated.  The product, the report and the log's total are the restatement's however the strip is cut."""
+    d = str(tmp_path)
+    W, L = 96, 23
+    img = _strip(W, L, 11)
+    bad = [0, 23, 24, 40, 41, 95]
+    img[:, bad] = 777
+    img.tofile(os.path.join(d, "M.RAW"))
+    open(os.path.join(d, "bad.txt"), "w").write(" ".join(str(c) for c in bad) + "\n")
+    want, cnt = ref.despike(img, 150, 0, 1, groups=4, coltab=ref.column_table(bad, W, 4)[0])
+    assert cnt.sum() > 0
+    total = "%d samples replaced in %d of %d columns" % (cnt.sum(), np.count_nonzero(cnt), W)
+    seen = []
+    for lines in (1, 2, 23, 24):
+        r = _run(["M.RAW", "--width", str(W), "--bil", "--threshold", "150", "--bad-columns", "bad.txt", "-o", "b%d.RAW" % lines, "--report", "r%d.txt" % lines],
+                 d, OIP_DESPIKE_BLOCK_LINES=str(lines))
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert open(os.path.join(d, "b%d.RAW" % lines), "rb").read() == want.tobytes(), "blocks of %d lines" % lines
+        assert _report(os.path.join(d, "r%d.txt" % lines)) == _counts(cnt), "blocks of %d lines" % lines
+        assert total in r.stdout
+        seen.append((_report(os.path.join(d, "r%d.txt" % lines)), re.findall(r"\d+ samples replaced in \d+ of \d+ columns", r.stdout)))
+    assert all(len(s[1]) == 1 and s == seen[0] for s in seen)

@@ -101,3 +101,27 @@ def test_one_sample_tiff_and_identity_kernel(tmp_path):
     r = _run(["S.RAW", "--width", str(w), "--kernel", "id.txt"], d)
     assert r.returncode == 0, r.stdout + r.stderr
     assert open(os.path.join(d, "S.MTFC.RAW"), "rb").read() == img.tobytes()
+
+
+def test_halo_larger_than_the_block_and_every_way_to_cut_a_small_strip(tmp_path):
+    """96 x 23 through a 9 x 9 kernel file: four halo lines either side.  OIP_MTFC_BLOCK_LINES 1 and 2 make the halo larger than
+    the block, reuse every device block many times and clamp the halo at both ends of the strip; 23 is exactly one block; 24 is
+    larger than the strip, so no second block is allocated.  However the strip is cut, the product is the restatement's."""
+    d = str(tmp_path)
+    W, L = 96, 23
+    img = _strip(W, L, 7)
+    img.tofile(os.path.join(d, "P.RAW"))
+    c = np.random.default_rng(8).normal(0, 0.01, (9, 9))
+    c[4, 4] += 1.0 - sum(float(v) for v in c.ravel())
+    c[4, 4] += 1.0 - sum(float(v) for v in c.ravel())
+    ref.write_kernel(os.path.join(d, "k.txt"), c)
+    taps = ref.quantise(ref.load_kernel(os.path.join(d, "k.txt")))
+    assert taps.shape == (9, 9) and np.count_nonzero(taps[0]) and np.count_nonzero(taps[8])
+    want = ref.convolve(img, taps, 1).tobytes()
+    products = []
+    for lines in (1, 2, 23, 24):
+        r = _run(["P.RAW", "--width", str(W), "--kernel", "k.txt", "-o", "b%d.RAW" % lines], d, OIP_MTFC_BLOCK_LINES=str(lines))
+        assert r.returncode == 0, r.stdout + r.stderr
+        products.append(open(os.path.join(d, "b%d.RAW" % lines), "rb").read())
+        assert products[-1] == want, "blocks of %d lines" % lines
+    assert all(p == products[0] for p in products)
