@@ -645,6 +645,30 @@ int oip_tiff_lzw_decode_u16(oip_ctx *ctx, const uint8_t *d_file, size_t file_byt
                             const uint64_t *strip_len, long nstrips, long rows, int width, int spp, long rows_per_strip,
                             int predictor, uint16_t *d_img);
 
+/* ---- overviews: reduced-resolution levels of a strip or product (`oip overviews`; not in the reference) ---- */
+#define OIP_OVERVIEW_SUFFIX ".ovr"   /* appended to the whole file name, GDAL's external-overview convention */
+
+/* One level of the pyramid.  Level 0 is the image: w0 x h0 pixels of spp samples (1, or 4 pixel-interleaved); level k >= 1
+ * has w_k = ceil(w_{k-1} / 2), h_k = ceil(h_{k-1} / 2) and the same spp.  For its sample (y, x, c): of the up-to-four samples
+ * (2y + j, 2x + i, c), j, i in {0, 1}, of level k - 1 that lie inside level k - 1, keep those with v >= valid_min; with n their
+ * number and S their sum the output is
+ *   n == 0 ? 0 : (S + n / 2) / n      (integer division; n / 2 floored)
+ * Exact integers: any evaluation order gives the same bytes.  With valid_min = 0 a full block is (S + 2) >> 2.  Every output
+ * is 0 or >= valid_min, so data never becomes no data, and no data appears only where all inputs were no data.  A level is
+ * defined from the level before it, as gdaladdo -r average does it, not from the image: a direct 2^k box differs by 1 DN on
+ * about a quarter of the samples.
+ * d_src: rows lines of w pixels of spp samples, src_pitch SAMPLES apart (a window inside a wider raster is allowed).  Output:
+ * ceil(rows / 2) lines of ceil(w / 2) pixels, dst_pitch samples apart.  A strip cut into calls at even lines (each call
+ * writing from output line first / 2 on) gives the bytes of one call.  Asynchronous on the context's stream.  OIP_E_INVALID for
+ * spp other than 1 or 4, w < 1, rows < 0 or >= 2^31, valid_min outside 0..65535, a pitch shorter than its line, d_dst ==
+ * d_src; rows == 0 is a no-op.  A source pitch that is not a multiple of 8 samples, or a source that does not start on a
+ * 16-byte boundary, takes a slower kernel (a lane per output sample) with the same result. */
+int oip_halve_u16(oip_ctx *ctx, const uint16_t *d_src, long src_pitch, int w, long rows, int spp, int valid_min,
+                  uint16_t *d_dst, long dst_pitch);
+/* host: the default level count of a w x h image, the smallest n >= 1 with ceil(w / 2^n) <= 256 and ceil(h / 2^n) <= 256,
+ * at most 16.  No context needed. */
+int oip_overview_levels(int w, long h);
+
 /* ---- instrumentation --------------------------------------------------------------- */
 /* name + accumulated device time of the kernels launched through this context since the
  * last reset, measured with HIP events on the context's stream (off by default). */

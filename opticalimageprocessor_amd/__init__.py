@@ -24,6 +24,7 @@ from .capi import (  # noqa: F401
     mtfc_design3,
     mtfc_load_kernel,
     mtfc_quantise,
+    overview_levels,
     polyfit,
     remap_shift_src_range,
     rrc_dead_columns,

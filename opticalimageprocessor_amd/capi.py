@@ -133,6 +133,8 @@ _SIGS = {
     "oip_load_column_list": ([_cp, _i, C.POINTER(_i), _i, C.POINTER(_i), _cp, _i], _i),
     "oip_write_column_list": ([_cp, C.POINTER(_i), _i, _cp, _cp, _i], _i),
     "oip_despike_column_table": ([C.POINTER(_i), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(_i), _cp, _i], _i),
+    "oip_halve_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _vp, _l], _i),
+    "oip_overview_levels": ([_i, _l], _i),
     "oip_merge_subimages_be16": ([_vp, _vp, _vp, _i, _i, _i, _i], _i),
     "oip_profile_enable": ([_vp, _i], _i),
     "oip_profile_reset": ([_vp], _i),
@@ -410,6 +412,11 @@ def write_tiff_u8(path: str, img) -> None:
         raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
 
 
+def overview_levels(w: int, h: int) -> int:
+    """the default level count of the pyramid of a w x h image (include/oip_c.h: oip_overview_levels)"""
+    return load_library().oip_overview_levels(w, h)
+
+
 FIT_MODES = {"reference": 0, "lstsq": 1}
 
 
@@ -550,6 +557,11 @@ class Context:
         """factor x factor box means of rows x w pixels of spp samples (lines `pitch` samples apart) into one plane per channel,
         ceil(w / factor) x ceil(rows / factor) each (include/oip_c.h: oip_decimate_box_u16)"""
         self._ck(self.lib.oip_decimate_box_u16(self.h, _ptr(src), pitch, w, rows, spp, factor, _ptr(dst), dst_pitch, dst_plane_stride))
+
+    def halve_u16(self, src, src_pitch, w, rows, spp, valid_min, dst, dst_pitch):
+        """one pyramid level: 2 x 2 means, skipping samples below valid_min, of rows x w pixels of spp samples (lines src_pitch
+        samples apart) into ceil(rows / 2) lines of ceil(w / 2) pixels, dst_pitch samples apart (include/oip_c.h: oip_halve_u16)"""
+        self._ck(self.lib.oip_halve_u16(self.h, _ptr(src), src_pitch, w, rows, spp, valid_min, _ptr(dst), dst_pitch))
 
     def histogram_u16(self, img, pitch, w, rows, hist):
         """counts of rows x w u16 (lines `pitch` samples apart) ADDED into hist: 65536 uint64 on the device, zeroed by the caller"""

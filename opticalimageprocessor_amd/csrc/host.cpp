@@ -610,6 +610,13 @@ extern "C" int oip_stretch_lut_u8(int lo, int hi, uint8_t *lut)
     return OIP_OK;
 }
 
+extern "C" int oip_overview_levels(int w, long h)
+{
+    int n = 1;
+    while (n < 16 && ((((long)w - 1) >> n) + 1 > 256 || ((h - 1) >> n) + 1 > 256)) ++n;      // ceil(v / 2^n) of v >= 1
+    return n;
+}
+
 extern "C" int oip_write_tiff_u8(const char *path, const uint8_t *data, int width, long height, int spp, char *err, int errlen)
 {
     auto fail = [&](int code, const char *msg) {

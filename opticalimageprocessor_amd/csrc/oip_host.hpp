@@ -376,6 +376,23 @@ inline void tiff_lzw_from_device(TiffWriterU16 &tw, const std::string &path, con
     RLOG("TIMING tiff_lzw strips=%zu alloc=%.4f encode=%.4f write=%.4f bytes=%zu prepared=%d", nstrips, tAlloc, tEncode, tWrite, bytes, prep != &own);
 }
 
+// The pixels of the directory `tw` is writing (width x height x spp u16 in HBM, in file sample order) leave the device:
+// uncompressed as one external payload, LZW strips from the device encoder where gpu_lzw() says so, else through the host's.
+inline void tiff_image_from_device(TiffWriterU16 &tw, const std::string &path, const uint16_t *d_img, int width, long height, int spp,
+                                   int compression, long mark)
+{
+    const size_t rowSamples = (size_t)width * spp;
+    if (compression == TIFF_NONE) {
+        const uint64_t at = tw.begin_external_payload();
+        Device::get().check(oip_write_device_to_file_at(Device::get().ctx(), d_img, (size_t)height * rowSamples * 2, path.c_str(), (size_t)at, mark));
+        tw.end_external_payload();
+    } else if (gpu_lzw()) {
+        tiff_lzw_from_device(tw, path, d_img, width, height, spp);
+    } else {
+        tiff_rows_from_device(tw, d_img, height, rowSamples, mark);
+    }
+}
+
 // A TIFF product whose pixels are in HBM (rows x width x spp u16, interleaved).  Uncompressed: the pixel payload goes from
 // the device into the file behind the header (TiffWriterU16::begin_external_payload + oip_write_device_to_file_at) -- no
 // strip-sized heap copy, as the reference's cv::imwrite / GDAL paths make (imageop.h:316-328, preproc.h:167-185).  LZW: the
@@ -392,17 +409,55 @@ inline void write_tiff_from_device(const std::string &path, uint16_t *d_img, int
         mark = 0;                                                      // (the permutation is younger than the mark)
     }
     TiffWriterU16 tw(path, width, height, spp, false, compression);
-    const size_t rowSamples = (size_t)width * spp;
-    if (compression == TIFF_NONE) {
-        const uint64_t at = tw.begin_external_payload();
-        Device::get().check(oip_write_device_to_file_at(ctx, d_img, (size_t)height * rowSamples * 2, path.c_str(), (size_t)at, mark));
-        tw.end_external_payload();
-    } else if (gpu_lzw()) {
-        tiff_lzw_from_device(tw, path, d_img, width, height, spp);
-    } else {
-        tiff_rows_from_device(tw, d_img, height, rowSamples, mark);
+    tiff_image_from_device(tw, path, d_img, width, height, spp, compression, mark);
+    tw.close();
+}
+
+// ---- overviews: <product>.ovr, the reduced-resolution pyramid of a product or strip (not in the reference) ----------------
+// `oip overviews` and `oip stitch --overviews` come through here.  levels: 0 = oip_overview_levels.
+struct OverviewOptions {
+    int levels = 0;
+    int validMin = 1;                       // 0 is the border value of prestitch and the aligner (BORDER_CONSTANT)
+};
+
+// The pyramid of a w0 x h0 x spp image whose LEVEL 1 is resident (oip_halve_u16 of the image, or of a strip block by block):
+// a TIFF of `levels` chained directories, level 1 first (TiffWriterU16 with overview_levels), every level leaving the device
+// the way a product of its geometry does.  Levels 2 .. n are resident calls that alternate between level1's buffer and a second
+// one a quarter of its size: a level is in the file before the level after the next one replaces it.
+inline void write_overviews_from_device(const std::string &path, DevBuf<uint16_t> &level1, int w0, long h0, int spp, int levels, int validMin)
+{
+    oip_ctx *ctx = Device::get().ctx();
+    const int comp = tiff_compression(spp == 1 ? TIFF_NONE : TIFF_LZW);
+    OLOG("Write %d overview levels to file '%s' ...", levels, path.c_str());
+    TiffWriterU16 tw(path, w0, h0, spp, false, comp, levels);
+    DevBuf<uint16_t> second;
+    uint16_t *cur = level1.p;
+    for (int k = 1; k <= levels; ++k) {
+        const int w = tw.width();
+        const long h = tw.height();
+        RLOG("    level %d: %d x %ld x %d", k, w, h, spp);
+        tiff_image_from_device(tw, path, cur, w, h, spp, comp, 0);
+        if (k == levels) break;
+        const int nw = (w + 1) / 2;
+        const long nh = (h + 1) / 2;
+        if (k == 1) second.alloc((size_t)nw * nh * spp);
+        uint16_t *next = cur == level1.p ? second.p : level1.p;
+        Device::get().check(oip_halve_u16(ctx, cur, (long)w * spp, w, h, spp, validMin, next, (long)nw * spp));
+        tw.next_directory();
+        cur = next;
     }
     tw.close();
+}
+
+// the same of an image that is itself resident (a stitched product, a TIFF read to the device)
+inline void write_overviews_of_device_image(const std::string &path, const uint16_t *d_img, int w, long h, int spp, const OverviewOptions &o)
+{
+    const int levels = o.levels > 0 ? o.levels : oip_overview_levels(w, h);
+    const int w1 = (w + 1) / 2;
+    const long h1 = (h + 1) / 2;
+    DevBuf<uint16_t> level1((size_t)w1 * h1 * spp);
+    Device::get().check(oip_halve_u16(Device::get().ctx(), d_img, (long)w * spp, w, h, spp, o.validMin, level1.p, (long)w1 * spp));
+    write_overviews_from_device(path, level1, w, h, spp, levels, o.validMin);
 }
 
 
@@ -658,7 +713,7 @@ public:
     // imageop.h:277-363, RAW output only (the GTiff writer is "next")
     static std::string StitchBigRaw(const std::string &leftImagePath, const std::string &rightImagePath,
                                     const std::string &stitchedFilePath, int pixelPerLine, int foldColPixels,
-                                    const SeamOptions *seam = nullptr)
+                                    const SeamOptions *seam = nullptr, const OverviewOptions *overviews = nullptr)
     {
         size_t szl = FileSize(leftImagePath), szr = FileSize(rightImagePath);
         if (szl != szr)
@@ -690,6 +745,7 @@ public:
         }
         double es = sw.tick();
         OLOG("%zu bytes written in %.3f seconds (%.1f MBps).", nout * 2, es, nout * 2 / es / (1024.0 * 1024.0));
+        if (overviews) write_overviews_of_device_image(outputFilePath + OIP_OVERVIEW_SUFFIX, dout.p, outputFullLinePixels, imageLines, 1, *overviews);
         return outputFilePath;
     }
 
@@ -699,7 +755,7 @@ public:
     // GDAL writes band b from channel bandMap[b]-1 (imageop.h:529).
     static std::string StitchTiff(const std::string &leftImagePath, const std::string &rightImagePath,
                                   const std::string &stitchedFilePath, int foldColPixels, bool useGDAL = false,
-                                  const int *bandMap = nullptr, const SeamOptions *seam = nullptr)
+                                  const int *bandMap = nullptr, const SeamOptions *seam = nullptr, const OverviewOptions *overviews = nullptr)
     {
         std::string outputFilePath = stitchedFilePath;
         if (stitchedFilePath.empty()) outputFilePath = (std::filesystem::current_path() / "stitched.TIFF").string();
@@ -736,6 +792,8 @@ public:
             for (int b = 0; b < 4; ++b) order[b] = mat2file[bandMap ? bandMap[b] - 1 : b];
             write_tiff_from_device(outputFilePath, dout.p, ow, hl, MSS_BANDS, tiff_compression(TIFF_LZW), false, order);
         }
+        // (dout is in the product's on-disk sample order by now; the average is per channel)
+        if (overviews) write_overviews_of_device_image(outputFilePath + OIP_OVERVIEW_SUFFIX, dout.p, ow, hl, MSS_BANDS, *overviews);
         return outputFilePath;
     }
 };
@@ -747,14 +805,15 @@ public:
     // stitcher.h:21-46; foldCols is the already-halved value (main.cpp:189)
     static std::string Stitch(const std::string &leftImagePath, const std::string &rightImagePath,
                               const std::string &outputPath = "", int foldCols = 0, int pixelsPerLine = OIP_PIXELS_PER_LINE,
-                              bool useGDAL = false, const int *bandMap = nullptr, const SeamOptions *seam = nullptr)
+                              bool useGDAL = false, const int *bandMap = nullptr, const SeamOptions *seam = nullptr,
+                              const OverviewOptions *overviews = nullptr)
     {
         std::string leftExt = to_lower(std::filesystem::path(leftImagePath).extension().string());
         std::string rightExt = to_lower(std::filesystem::path(rightImagePath).extension().string());
         if (leftExt != rightExt) throw std::invalid_argument("Stitch(): two images should be same type");
         if (leftExt != ".tiff" && leftExt != ".raw") throw std::invalid_argument("Stitch(): only RAW and TIFF image supported");
-        if (leftExt == ".raw") return IMO::StitchBigRaw(leftImagePath, rightImagePath, outputPath, pixelsPerLine, foldCols, seam);
-        return IMO::StitchTiff(leftImagePath, rightImagePath, outputPath, foldCols, useGDAL, bandMap, seam);
+        if (leftExt == ".raw") return IMO::StitchBigRaw(leftImagePath, rightImagePath, outputPath, pixelsPerLine, foldCols, seam, overviews);
+        return IMO::StitchTiff(leftImagePath, rightImagePath, outputPath, foldCols, useGDAL, bandMap, seam, overviews);
     }
 
     Stitcher(const std::string &pan1, const std::string &pan2, const std::string &rrc1, const std::string &rrc2,

@@ -121,6 +121,20 @@ struct OipProfScope {
     ~OipProfScope() { oip_prof_end(ctx, id); }
 };
 
+// grid.y of the raster kernels that walk the lines of a column range (quicklook.hip, overview.hip): about `per_cu` workgroups
+// per CU over the whole grid, every workgroup a line range that is a multiple of `range` lines
+inline void oip_row_blocks(const oip_ctx *ctx, int gx, long rows, int per_cu, long range, long *rows_per_block, int *gy)
+{
+    long want = (long)ctx->cu_count * per_cu / (gx > 0 ? gx : 1);
+    if (want < 1) want = 1;
+    long rpb = (rows + want - 1) / want;
+    rpb = (rpb + range - 1) / range * range;
+    if (rpb < range) rpb = range;
+    if ((rows + rpb - 1) / rpb > 65535) rpb = ((rows + 65534) / 65535 + range - 1) / range * range;
+    *rows_per_block = rpb;
+    *gy = (int)((rows + rpb - 1) / rpb);
+}
+
 // ---- device helpers shared by the resampling kernels -----------------------------------
 // A line index that is the same in every lane, told to the compiler: the per-line row tables are then read with scalar loads
 // (s_load, counted by lgkmcnt) instead of one vector load per lane of the same 16-24 bytes -- whose s_waitcnt vmcnt(0) also

@@ -14,12 +14,15 @@
 //   oip mtfc IMAGE [-o OUT] (--kernel FILE | --mtf-x M --mtf-y M)   MTF-compensation filter of a strip or product, see run_mtfc()
 //   oip despike IMAGE [-o OUT] [--threshold N] [--relative R] [--bad-columns FILE] [--bil]   repair of a raw strip ahead of RRC:
 //                               bad columns interpolated, impulse pixels replaced by a conditional 3 x 3 median, see run_despike()
+//   oip overviews IMAGE [-o OUT] [--levels N] [--valid-min N]   the reduced-resolution pyramid of a strip or product as
+//                               <IMAGE>.ovr beside it; `stitch --overviews [--levels N]` writes its product's, see run_overviews()
 //   oip -v | --version          prints 1.1
 // plus --width N (pixels per PAN line; the reference hard-codes 12288, oipshared.h:28).
 // `auxsep` is outside this build.  TIFF input and output go through oip_tiff.hpp (uncompressed and LZW, with
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
-// --feather-pan / --feather-mss for its two stitches) and the rrc-calib, quicklook, mtfc and despike sub-commands.
+// --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
+// despike and overviews sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -98,7 +101,7 @@ Parsed parse(const Spec &sp, const std::vector<std::string> &args)
     return p;
 }
 
-// The tools with one positional argument (quicklook, mtfc, despike): IMAGE, an existing regular file, is the first argument
+// The tools with one positional argument (quicklook, mtfc, despike, overviews): IMAGE, an existing regular file, is the first argument
 // that is neither an option nor the value of one (an option's value stays with it, alias or not); the rest is parsed as usual.
 Parsed parse_with_image(const Spec &sp, const std::vector<std::string> &args, std::string *image)
 {
@@ -159,6 +162,7 @@ void usage()
          "             [--balance-lines N] with --balance: a fit per block of N lines (N >= 1), interpolated to a gain / offset per line\n"
          "             [--feather N] blend the images over N columns around the seam (even, 0 <= N <= fold-cols)\n"
          "             [--valid-min N] [--valid-max N] (samples outside are no data; default 1, 65535) [--min-count N]\n"
+         "             [--overviews] [--levels N] also write the product's pyramid to <output>.ovr, as `overviews` does (--valid-min applies)\n"
          "  --gpus N   (default action and prestitch) scan-line blocks over the N GPUs of the node, RCCL exchanges\n"
          "  plan       strip|ccd --width W --lines L --gpus N ...: print the multi-GPU row plan as JSON\n"
          "  task       prestitch + stitch + default action x2 + stitch in one process (intermediates stay on the GPU;\n"
@@ -188,7 +192,11 @@ void usage()
          "             neighbourhood is replaced by it (there is no default: measure the sensor's noise) [--relative R] (0..1, default 0)\n"
          "             [--bad-columns FILE] (RAW; text: 0-based columns, # comments) interpolated from their good neighbours\n"
          "             [--bil] (RAW: the MSS line layout, bands never mix) [--valid-min N] (samples below are no data; default 1)\n"
-         "             [--width N] [--report FILE] (`column count' of the replaced samples) [--force]");
+         "             [--width N] [--report FILE] (`column count' of the replaced samples) [--force]\n"
+         "  overviews  IMAGE.RAW|IMAGE.TIFF: the reduced-resolution pyramid of a strip or product, every band at 16 bits, each level\n"
+         "             the 2 x 2 average of the one before; written to IMAGE.ovr beside the image, where GDAL-based viewers look for it:\n"
+         "             [-o,--out FILE] [--levels N] (1..16; default: until a level fits 256 x 256) [--valid-min N] (samples below are\n"
+         "             no data and do not enter an average; default 1) [--width N] [--force]");
 }
 
 int run_prestitch(const std::vector<std::string> &args, int width)
@@ -265,12 +273,22 @@ int seam_feather(const Parsed &p, const std::string &key, int foldCols, const st
     return feather / 2;
 }
 
+// --levels N of `overviews` and `stitch --overviews`: 1..16; 0 without one (the default count, oip_overview_levels)
+int overview_levels(const Parsed &p)
+{
+    if (!p.has("--levels")) return 0;
+    const int n = p.integer("--levels", 0);
+    if (n < 1 || n > 16) throw cli_error(105, "--levels: 1 <= N <= 16 expected");
+    return n;
+}
+
 int run_stitch(const std::vector<std::string> &args, int width)
 {
     Spec sp;
     sp.valued = {"--image1", "--image2", "--out", "--fold-cols", "--band-map", "--width", "--feather"};
     sp.valued.insert(std::begin(kSeamValued), std::end(kSeamValued));
-    sp.flags = {"--GDAL"};
+    sp.valued.insert("--levels");
+    sp.flags = {"--GDAL", "--overviews"};
     sp.alias = {{"-o", "--out"}, {"-c", "--fold-cols"}, {"-g", "--GDAL"}, {"-m", "--band-map"}};
     Parsed p = parse(sp, args);
     require(p, "--image1");
@@ -289,8 +307,13 @@ int run_stitch(const std::vector<std::string> &args, int width)
     }
     SeamOptions seam = seam_options(p);
     seam.feather = seam_feather(p, "--feather", foldCols, "fold-cols");
+    // --overviews [--levels N] (not in the reference): the product's pyramid beside it, with the seam options' --valid-min
+    if (p.has("--levels") && !p.has("--overviews")) throw cli_error(107, "--levels requires --overviews");
+    OverviewOptions ovr;
+    ovr.levels = overview_levels(p);
+    ovr.validMin = seam.validMin;
     Stitcher::Stitch(p.str("--image1"), p.str("--image2"), p.str("--out"), foldCols / 2, width, p.has("--GDAL"),
-                     bandMap.empty() ? nullptr : map, &seam);                                                    // main.cpp:189
+                     bandMap.empty() ? nullptr : map, &seam, p.has("--overviews") ? &ovr : nullptr);             // main.cpp:189
     return 0;
 }
 
@@ -621,6 +644,26 @@ int run_despike(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip overviews IMAGE: the pyramid of a strip (.RAW, --width samples per line) or a product (.TIFF of 1 or 4 samples) as
+// IMAGE.ovr.  IMAGE is the one positional argument, as for mtfc.
+int run_overviews(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--out", "--levels", "--valid-min", "--width"};
+    sp.flags = {"--force"};
+    sp.alias = {{"-o", "--out"}};
+    std::string image;
+    Parsed p = parse_with_image(sp, args, &image);
+    OverviewsOptions o;
+    o.width = p.integer("--width", width);
+    o.pyramid.levels = overview_levels(p);
+    o.pyramid.validMin = p.integer("--valid-min", 1);
+    if (o.pyramid.validMin < 0 || o.pyramid.validMin > 65535) throw cli_error(105, "--valid-min: 0 <= N <= 65535 expected");
+    o.force = p.flag.count("--force") != 0;
+    RunOverviews(image, p.str("--out"), o);
+    return 0;
+}
+
 }  // namespace
 
 static int oip_main(int argc, const char *argv[]);
@@ -671,6 +714,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "quicklook") return run_quicklook({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "mtfc") return run_mtfc({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "despike") return run_despike({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "overviews") return run_overviews({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "auxsep")
                 throw std::invalid_argument("auxsep (down-link de-framing) is outside this build: run the reference's auxsep, then this tool");
             if (args.empty()) { usage(); return 0; }

@@ -1,6 +1,6 @@
-// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike) above the
-// host layer of oip_host.hpp: what they check before a device is touched, the one driver that streams a RAW strip through
-// the device in line blocks (geometry: oip_stripplan.hpp), the resident filter of a TIFF product, and the four tools.
+// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, overviews) above
+// the host layer of oip_host.hpp: what they check before a device is touched, the one driver that streams a RAW strip through
+// the device in line blocks (geometry: oip_stripplan.hpp), the resident filter of a TIFF product, and the five tools.
 #pragma once
 
 #include "oip_host.hpp"
@@ -51,7 +51,7 @@ inline std::string FilterOutputPath(const std::string &file, const std::string &
     return path;
 }
 
-// OIP_MTFC_BLOCK_LINES / OIP_DESPIKE_BLOCK_LINES (test hooks: several blocks on a small image); 0 without one
+// OIP_MTFC_BLOCK_LINES / OIP_DESPIKE_BLOCK_LINES / OIP_OVERVIEWS_BLOCK_LINES (test hooks: several blocks on a small image); 0 without one
 inline long BlockLinesHook(const char *name) { const char *e = getenv(name); return e ? atol(e) : 0; }
 
 // ---- the strip-streaming driver ---------------------------------------------------------------------------------
@@ -566,6 +566,74 @@ inline void RunDespike(const std::string &file, const std::string &out, const De
         if (!f) throw std::runtime_error("open file [" + o.report + "] failed: " + std::to_string(errno));
         fprintf(f, "# column count: no --threshold, no sample replaced in %s\n", file.c_str());
         fclose(f);
+    }
+    const double es = total.tick();
+    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+}
+
+// ---- oip overviews: the reduced-resolution pyramid of a strip or product ------------------------------------------------
+// Every band at 16 bits, each level the 2 x 2 average of the one before that skips no data (oip_halve_u16), written where
+// GDAL, QGIS and libtiff programs look for it: <IMAGE>.ovr beside the image, a TIFF of chained reduced-resolution
+// directories (write_overviews_from_device).  A RAW strip is halved block by block into a resident level 1, a quarter of the
+// strip; a TIFF product is resident.  `oip stitch --overviews` writes the same of its product while that is still in HBM.
+// Not in the reference.
+struct OverviewsOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    OverviewOptions pyramid;                // --levels (0: oip_overview_levels), --valid-min
+    bool force = false;
+};
+
+// everything that can be refused without a device: the container, sizes, the ranges, the output; returns the output path
+inline std::string OverviewsCheck(const std::string &file, const std::string &out, const OverviewsOptions &o, bool *isTiff)
+{
+    *isTiff = RasterContainer(file, "overviews") == ".tiff";
+    if (!*isTiff) {
+        if (o.width <= 0) throw std::invalid_argument("--width: a positive line width expected");
+        RawLineCount(file, "image", (size_t)o.width * BYTES_PER_PIXEL);
+    }
+    if (o.pyramid.levels < 0 || o.pyramid.levels > 16) throw std::invalid_argument("--levels: 1 <= N <= 16 expected");
+    if (o.pyramid.validMin < 0 || o.pyramid.validMin > 65535) throw std::invalid_argument("--valid-min: 0 <= N <= 65535 expected");
+    // (not FilterOutputPath: the overview file is a TIFF named after the whole file name of the image, beside it)
+    const std::string path = out.empty() ? file + OIP_OVERVIEW_SUFFIX : out;
+    struct stat st;
+    if (stat(path.c_str(), &st) == 0) {
+        if (std::filesystem::equivalent(path, file)) throw std::invalid_argument("output file [" + path + "] is the input image");
+        if (!o.force) throw std::runtime_error("output file [" + path + "] exists: overviews does not replace a file without --force");
+    }
+    return path;
+}
+
+inline void RunOverviews(const std::string &file, const std::string &out, const OverviewsOptions &o)
+{
+    bool isTiff = false;
+    const std::string outPath = OverviewsCheck(file, out, o, &isTiff);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    size_t bytes = 0;
+    if (isTiff) {
+        int w = 0, spp = 0;
+        long h = 0;
+        DevBuf<uint16_t> img;
+        OLOG("Reading image from file `%s' ...", file.c_str());
+        read_tiff_to_device(file, &w, &h, &spp, img);
+        if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument("overviews: a TIFF of 1 or 4 samples per pixel expected");
+        write_overviews_of_device_image(outPath, img.p, w, h, spp, o.pyramid);
+        bytes = (size_t)w * h * spp * BYTES_PER_PIXEL;
+    } else {
+        // level 1 is built per line block of the strip (ReadStrip), a block being an even number of lines
+        const int W = o.width;
+        const size_t lineBytes = (size_t)W * BYTES_PER_PIXEL;
+        const long L = RawLineCount(file, "image", lineBytes);
+        const int w1 = (W + 1) / 2;
+        DevBuf<uint16_t> level1((size_t)w1 * ((L + 1) / 2));
+        long hook = BlockLinesHook("OIP_OVERVIEWS_BLOCK_LINES");
+        if (hook > 0) hook = std::max<long>(2, hook / 2 * 2);
+        ReadStrip(file, StripPlan{0, L, L, 0, StripBlockLines(lineBytes, 2, hook), lineBytes}, [&](const uint16_t *d, long r, long m) {
+            ck(oip_halve_u16(ctx, d, W, W, m, 1, o.pyramid.validMin, level1.p + (size_t)(r / 2) * w1, w1));
+        });
+        write_overviews_from_device(outPath, level1, W, L, 1, o.pyramid.levels > 0 ? o.pyramid.levels : oip_overview_levels(W, L), o.pyramid.validMin);
+        bytes = (size_t)L * lineBytes;
     }
     const double es = total.tick();
     OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);

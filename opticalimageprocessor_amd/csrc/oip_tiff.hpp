@@ -266,25 +266,26 @@ class TiffWriterU16 {
 public:
     // rows are appended top to bottom with write_rows(); close() writes the directory.
     // compression: TIFF_NONE, or TIFF_LZW (always with predictor 2, what cv::imwrite and the reference's GDAL call use)
-    TiffWriterU16(const std::string &path, int width, long height, int spp, bool opencv_order, int compression = TIFF_NONE)
+    // overview_levels = n > 0: the file is the external overview file (<product>.ovr) of a width x height product instead --
+    // n directories, directory k the pyramid's level k + 1 (each half the one before, rounded up), every one with the tags of a
+    // product of its geometry plus NewSubfileType (254) = 1, chained by their next-directory offsets.  The rows of level 1 come
+    // first; next_directory() goes on to the next level.  n = 0 is the one-image file: no tag 254, the one directory linked from the header.
+    TiffWriterU16(const std::string &path, int width, long height, int spp, bool opencv_order, int compression = TIFF_NONE, int overview_levels = 0)
         : mW(width), mH(height), mSpp(spp), mSwap(opencv_order && spp == 4), mComp(compression)
     {
-        if (width <= 0 || height <= 0 || (spp != 1 && spp != 4)) throw std::invalid_argument("TiffWriterU16: bad geometry");
+        mLevelsLeft = overview_levels;
+        if (width <= 0 || height <= 0 || (spp != 1 && spp != 4) || overview_levels < 0) throw std::invalid_argument("TiffWriterU16: bad geometry");
         if (compression != TIFF_NONE && compression != TIFF_LZW) throw std::invalid_argument("TiffWriterU16: unsupported compression");
-        mRowBytes = (size_t)width * spp * 2;
-        const size_t data = mRowBytes * (size_t)height;
         // classic TIFF offsets are 32 bit.  LZW can also GROW a strip: at worst one 12-bit code per byte (x1.5), so the
         // choice is made on the worst case and a classic file can never overflow half-way (BigTIFF is always valid).
-        const size_t worst = compression == TIFF_LZW ? data + data / 2 : data;
-        // Strips: 8 MiB uncompressed (their offsets are arithmetic); LZW: whole rows up to 64 KiB (cv::imwrite and GDAL write 8
-        // KB strips; libtiff's table restarts every ~5 KB of sensor data, so the strip size does not change the ratio).  An
-        // LZW strip is the unit of parallel work of whoever encodes it: a lane of the device encoder (csrc/tifflzw.hip: 25000
-        // strips for a 7500 x 25000 x 4 product), a thread of the host encoder below -- both write the same strips, so a file
-        // is the same bytes whoever encoded it.
-        mRowsPerStrip = compression == TIFF_LZW ? (long)((64u << 10) / mRowBytes) : (long)((8u << 20) / mRowBytes);
-        if (mRowsPerStrip < 1) mRowsPerStrip = 1;
-        if (mRowsPerStrip > height) mRowsPerStrip = height;
-        const size_t nstrips = ((size_t)height + mRowsPerStrip - 1) / mRowsPerStrip;
+        // (An overview file: on the sum of its levels.)
+        size_t worst = 0, nstrips = 0;
+        if (overview_levels == 0) {
+            set_geometry(width, height, &worst, &nstrips);
+        } else {
+            for (int k = overview_levels; k >= 1; --k)                         // (level 1 last: its geometry is the first directory's)
+                set_geometry((int)(((long)width - 1) >> k) + 1, ((height - 1) >> k) + 1, &worst, &nstrips);
+        }
         mBig = worst + nstrips * 16 + 16384 > 0xFFFFF000ull;                  // header, page-aligned payload, strip tables, directory
         if (const char *e = getenv("OIP_TIFF_FORCE_BIG")) mBig = mBig || atoi(e) != 0;   // test hook: BigTIFF at any size
         mF = fopen(path.c_str(), "wb");
@@ -297,7 +298,13 @@ public:
             put(h, 8);
         }
         mPos = mBig ? 16 : 8;
+        mLink = mBig ? 8 : 4;
     }
+
+    // geometry of the directory being written (an overview file: of the current level)
+    int width() const { return mW; }
+    long height() const { return mH; }
+    int levels_left() const { return mLevelsLeft; }                            // overview file: levels still to come, this one included
 
     void write_rows(const uint16_t *rows, long count)
     {
@@ -346,59 +353,27 @@ public:
         }
     }
 
+    // an overview file: the current level is complete, its directory is written and the rows of the next level follow
+    void next_directory()
+    {
+        if (!mF || mLevelsLeft < 2) throw std::logic_error("TiffWriterU16: no further directory");
+        end_directory();
+        --mLevelsLeft;
+        size_t worst = 0, nstrips = 0;
+        set_geometry((mW + 1) / 2, (mH + 1) / 2, &worst, &nstrips);
+        mRowsDone = 0;
+        mStripOff.clear();
+        mStripLen.clear();
+        mScratch.clear();                                                      // (sized for the previous level's strips)
+        if (fseeko(mF, (off_t)mPos, SEEK_SET) != 0) { fclose(mF); mF = nullptr; throw std::runtime_error("TiffWriterU16: seek failed"); }
+        mPositioned = false;
+    }
+
     void close()
     {
         if (!mF) return;
-        wait_write();
-        if (mRowsDone != mH || !mPending.empty()) { fclose(mF); mF = nullptr; throw std::logic_error("TiffWriterU16: rows missing"); }
-        if (mPositioned && fseeko(mF, (off_t)mPos, SEEK_SET) != 0) { fclose(mF); mF = nullptr; throw std::runtime_error("TiffWriterU16: seek failed"); }
-        if (mPos & 1) { const unsigned char z = 0; put(&z, 1); ++mPos; }
-        // out-of-line arrays first
-        const uint64_t nstrips = mStripOff.size();
-        uint64_t offStripOff = 0, offStripLen = 0, offBits = 0, offFmt = 0;
-        const size_t osz = mBig ? 8 : 4, inl = mBig ? 8 : 4;
-        if (!mBig && mPos + nstrips * 8 + 4096 > 0xFFFFFFFFull) { fclose(mF); mF = nullptr; throw std::runtime_error("TiffWriterU16: classic TIFF overflow"); }
-        if (nstrips * osz > inl) {
-            offStripOff = mPos; for (uint64_t v : mStripOff) putv(v, osz);
-            offStripLen = mPos; for (uint64_t v : mStripLen) putv(v, osz);
-        }
-        if ((size_t)mSpp * 2 > inl) {
-            offBits = mPos; for (int i = 0; i < mSpp; ++i) putv(16, 2);
-            offFmt = mPos; for (int i = 0; i < mSpp; ++i) putv(1, 2);
-        }
-        if (mPos & 1) { const unsigned char z = 0; put(&z, 1); ++mPos; }
-        const uint64_t ifd = mPos;
-        struct Tag { uint16_t id, type; uint64_t count, value; bool is_offset; };
-        const uint16_t SHORT = 3, LONG = 4, LONG8 = 16;
-        const uint16_t otype = mBig ? LONG8 : LONG;
-        std::vector<Tag> tags;
-        auto inline_shorts = [&](int n, uint16_t v) { uint64_t x = 0; for (int i = 0; i < n; ++i) x |= (uint64_t)v << (16 * i); return x; };
-        tags.push_back({256, LONG, 1, (uint64_t)mW, false});
-        tags.push_back({257, LONG, 1, (uint64_t)mH, false});
-        tags.push_back({258, SHORT, (uint64_t)mSpp, offBits ? offBits : inline_shorts(mSpp, 16), offBits != 0});
-        tags.push_back({259, SHORT, 1, (uint64_t)mComp, false});
-        tags.push_back({262, SHORT, 1, (uint64_t)(mSpp == 4 ? 2 : 1), false});            // RGB / BlackIsZero
-        tags.push_back({273, otype, nstrips, offStripOff ? offStripOff : mStripOff[0], offStripOff != 0});
-        tags.push_back({277, SHORT, 1, (uint64_t)mSpp, false});
-        tags.push_back({278, LONG, 1, (uint64_t)mRowsPerStrip, false});
-        tags.push_back({279, otype, nstrips, offStripLen ? offStripLen : mStripLen[0], offStripLen != 0});
-        tags.push_back({284, SHORT, 1, 1, false});                                        // chunky
-        if (mComp == TIFF_LZW) tags.push_back({317, SHORT, 1, 2, false});                 // horizontal predictor
-        if (mSpp == 4) tags.push_back({338, SHORT, 1, 2, false});                         // unassociated alpha
-        tags.push_back({339, SHORT, (uint64_t)mSpp, offFmt ? offFmt : inline_shorts(mSpp, 1), offFmt != 0});
-        if (mBig) {
-            putv(tags.size(), 8);
-            for (auto &t : tags) { putv(t.id, 2); putv(t.type, 2); putv(t.count, 8); putv(t.value, 8); }
-            putv(0, 8);
-            fseeko(mF, 8, SEEK_SET);
-            putv_raw(ifd, 8);
-        } else {
-            putv(tags.size(), 2);
-            for (auto &t : tags) { putv(t.id, 2); putv(t.type, 2); putv(t.count, 4); putv(t.value, 4); }
-            putv(0, 4);
-            fseeko(mF, 4, SEEK_SET);
-            putv_raw(ifd, 4);
-        }
+        if (mLevelsLeft > 1) { fclose(mF); mF = nullptr; throw std::logic_error("TiffWriterU16: levels missing"); }
+        end_directory();
         if (fclose(mF) != 0) { mF = nullptr; throw std::runtime_error("TiffWriterU16: close failed"); }
         mF = nullptr;
     }
@@ -469,6 +444,83 @@ public:
     }
 
 private:
+    // strip geometry of a width x height image; adds what it may take in the file to *worst and its strips to *nstrips
+    void set_geometry(int width, long height, size_t *worst, size_t *nstrips)
+    {
+        mW = width;
+        mH = height;
+        mRowBytes = (size_t)width * mSpp * 2;
+        const size_t data = mRowBytes * (size_t)height;
+        *worst += mComp == TIFF_LZW ? data + data / 2 : data;
+        // Strips: 8 MiB uncompressed (their offsets are arithmetic); LZW: whole rows up to 64 KiB (cv::imwrite and GDAL write 8
+        // KB strips; libtiff's table restarts every ~5 KB of sensor data, so the strip size does not change the ratio).  An
+        // LZW strip is the unit of parallel work of whoever encodes it: a lane of the device encoder (csrc/tifflzw.hip: 25000
+        // strips for a 7500 x 25000 x 4 product), a thread of the host encoder below -- both write the same strips, so a file
+        // is the same bytes whoever encoded it.
+        mRowsPerStrip = mComp == TIFF_LZW ? (long)((64u << 10) / mRowBytes) : (long)((8u << 20) / mRowBytes);
+        if (mRowsPerStrip < 1) mRowsPerStrip = 1;
+        if (mRowsPerStrip > height) mRowsPerStrip = height;
+        *nstrips += ((size_t)height + mRowsPerStrip - 1) / mRowsPerStrip;
+    }
+
+    // the strip tables and the directory of the image whose rows are complete, linked behind the header or the previous directory
+    void end_directory()
+    {
+        wait_write();
+        if (mRowsDone != mH || !mPending.empty()) { fclose(mF); mF = nullptr; throw std::logic_error("TiffWriterU16: rows missing"); }
+        if (mPositioned && fseeko(mF, (off_t)mPos, SEEK_SET) != 0) { fclose(mF); mF = nullptr; throw std::runtime_error("TiffWriterU16: seek failed"); }
+        if (mPos & 1) { const unsigned char z = 0; put(&z, 1); ++mPos; }
+        // out-of-line arrays first
+        const uint64_t nstrips = mStripOff.size();
+        uint64_t offStripOff = 0, offStripLen = 0, offBits = 0, offFmt = 0;
+        const size_t osz = mBig ? 8 : 4, inl = mBig ? 8 : 4;
+        if (!mBig && mPos + nstrips * 8 + 4096 > 0xFFFFFFFFull) { fclose(mF); mF = nullptr; throw std::runtime_error("TiffWriterU16: classic TIFF overflow"); }
+        if (nstrips * osz > inl) {
+            offStripOff = mPos; for (uint64_t v : mStripOff) putv(v, osz);
+            offStripLen = mPos; for (uint64_t v : mStripLen) putv(v, osz);
+        }
+        if ((size_t)mSpp * 2 > inl) {
+            offBits = mPos; for (int i = 0; i < mSpp; ++i) putv(16, 2);
+            offFmt = mPos; for (int i = 0; i < mSpp; ++i) putv(1, 2);
+        }
+        if (mPos & 1) { const unsigned char z = 0; put(&z, 1); ++mPos; }
+        const uint64_t ifd = mPos;
+        struct Tag { uint16_t id, type; uint64_t count, value; bool is_offset; };
+        const uint16_t SHORT = 3, LONG = 4, LONG8 = 16;
+        const uint16_t otype = mBig ? LONG8 : LONG;
+        std::vector<Tag> tags;
+        auto inline_shorts = [&](int n, uint16_t v) { uint64_t x = 0; for (int i = 0; i < n; ++i) x |= (uint64_t)v << (16 * i); return x; };
+        if (mLevelsLeft > 0) tags.push_back({254, LONG, 1, 1, false});                    // NewSubfileType: reduced-resolution image
+        tags.push_back({256, LONG, 1, (uint64_t)mW, false});
+        tags.push_back({257, LONG, 1, (uint64_t)mH, false});
+        tags.push_back({258, SHORT, (uint64_t)mSpp, offBits ? offBits : inline_shorts(mSpp, 16), offBits != 0});
+        tags.push_back({259, SHORT, 1, (uint64_t)mComp, false});
+        tags.push_back({262, SHORT, 1, (uint64_t)(mSpp == 4 ? 2 : 1), false});            // RGB / BlackIsZero
+        tags.push_back({273, otype, nstrips, offStripOff ? offStripOff : mStripOff[0], offStripOff != 0});
+        tags.push_back({277, SHORT, 1, (uint64_t)mSpp, false});
+        tags.push_back({278, LONG, 1, (uint64_t)mRowsPerStrip, false});
+        tags.push_back({279, otype, nstrips, offStripLen ? offStripLen : mStripLen[0], offStripLen != 0});
+        tags.push_back({284, SHORT, 1, 1, false});                                        // chunky
+        if (mComp == TIFF_LZW) tags.push_back({317, SHORT, 1, 2, false});                 // horizontal predictor
+        if (mSpp == 4) tags.push_back({338, SHORT, 1, 2, false});                         // unassociated alpha
+        tags.push_back({339, SHORT, (uint64_t)mSpp, offFmt ? offFmt : inline_shorts(mSpp, 1), offFmt != 0});
+        if (mBig) {
+            putv(tags.size(), 8);
+            for (auto &t : tags) { putv(t.id, 2); putv(t.type, 2); putv(t.count, 8); putv(t.value, 8); }
+            putv(0, 8);
+            fseeko(mF, (off_t)mLink, SEEK_SET);
+            putv_raw(ifd, 8);
+            mLink = mPos - 8;
+        } else {
+            putv(tags.size(), 2);
+            for (auto &t : tags) { putv(t.id, 2); putv(t.type, 2); putv(t.count, 4); putv(t.value, 4); }
+            putv(0, 4);
+            fseeko(mF, (off_t)mLink, SEEK_SET);
+            putv_raw(ifd, 4);
+            mLink = mPos - 4;
+        }
+    }
+
     // encode `nrows` rows (whole strips, the last one possibly short) on a few threads and append them to the file.
     // No allocation per strip: a worker copies + differences a strip in a scratch buffer of its own and encodes it into its
     // region of one of two arenas that alternate between batches (the previous batch is still being written from the other).
@@ -562,6 +614,8 @@ private:
     int mArenaCur = 0;
     std::vector<std::unique_ptr<uint16_t[]>> mScratch;  // one strip of differenced samples per worker
     uint64_t mPos = 0;
+    int mLevelsLeft = 0;                // overview file: directories still to be written (0: a one-image file)
+    uint64_t mLink = 0;                 // where the offset of the next directory goes: in the header, then in the previous directory
     std::vector<uint64_t> mStripOff, mStripLen;
     std::vector<uint16_t> mPending;
     std::future<void> mWrite;           // the batch of encoded strips being written

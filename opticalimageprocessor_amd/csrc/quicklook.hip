@@ -189,19 +189,6 @@ __global__ __launch_bounds__(kBlock) void decimate_box_u16_block_kernel(const ui
     }
 }
 
-// grid.y: about `per_cu` workgroups per CU over the whole grid, line ranges that are multiples of kRangeLines
-inline void decimate_row_blocks(const oip_ctx *ctx, int gx, long rows, int per_cu, long *rows_per_block, int *gy)
-{
-    long want = (long)ctx->cu_count * per_cu / (gx > 0 ? gx : 1);
-    if (want < 1) want = 1;
-    long rpb = (rows + want - 1) / want;
-    rpb = (rpb + kRangeLines - 1) / kRangeLines * kRangeLines;
-    if (rpb < kRangeLines) rpb = kRangeLines;
-    if ((rows + rpb - 1) / rpb > 65535) rpb = ((rows + 65534) / 65535 + kRangeLines - 1) / kRangeLines * kRangeLines;
-    *rows_per_block = rpb;
-    *gy = (int)((rows + rpb - 1) / rpb);
-}
-
 template <int SPP>
 void launch_decimate(oip_ctx *ctx, int F, dim3 grid, const uint16_t *src, long pitch, int w, long rows, uint16_t *dst, long dst_pitch,
                      size_t dst_plane, long rpb)
@@ -300,12 +287,12 @@ extern "C" int oip_decimate_box_u16(oip_ctx *ctx, const uint16_t *d_src, long pi
     int gy;
     if (vec) {
         const int gx = (int)((((long)w * spp + 7) / 8 + kBlock - 1) / kBlock);
-        decimate_row_blocks(ctx, gx, rows, 8, &rpb, &gy);
+        oip_row_blocks(ctx, gx, rows, 8, kRangeLines, &rpb, &gy);
         if (spp == 1) launch_decimate<1>(ctx, factor, dim3(gx, gy), d_src, pitch, w, rows, d_dst, dst_pitch, dst_plane_stride, rpb);
         else launch_decimate<4>(ctx, factor, dim3(gx, gy), d_src, pitch, w, rows, d_dst, dst_pitch, dst_plane_stride, rpb);
     } else {
         const int gx = (ow * spp + kBlock - 1) / kBlock;
-        decimate_row_blocks(ctx, gx, rows, 16, &rpb, &gy);
+        oip_row_blocks(ctx, gx, rows, 16, kRangeLines, &rpb, &gy);
         hipLaunchKernelGGL(decimate_box_u16_block_kernel, dim3(gx, gy), dim3(kBlock), 0, ctx->stream, d_src, pitch, w, rows, spp, factor, d_dst,
                            dst_pitch, dst_plane_stride, rpb);
     }
