@@ -669,6 +669,59 @@ int oip_halve_u16(oip_ctx *ctx, const uint16_t *d_src, long src_pitch, int w, lo
  * at most 16.  No context needed. */
 int oip_overview_levels(int w, long h);
 
+/* ---- regcheck: tile-matching registration check of two rasters (`oip regcheck`; not in the reference) ---- */
+/* Dense template matching by zero-mean normalised cross-correlation in the spatial domain, built from exact integer sums: a
+ * measure of registration that shares no code with the phase correlation it judges.
+ * Planes.  A is the reference image, B the sensed one; both u16, w x rows samples, given as a base pointer, a pitch in
+ * SAMPLES and a sample stride of 1 or 4 (4: one band of a pixel-interleaved 4-sample raster, base + band):
+ *   A(y, x) = d_a[y * pitch_a + x * stride_a].
+ * Tiles.  Tile (j, i), 0 <= j < ny, 0 <= i < nx, has its T x T template at (ty, tx) = (y0 + j * step_y, x0 + i * step_x) in A;
+ * T a multiple of 8, 8 <= T <= 128.  For every offset (dy, dx) in [-S, S]^2, 1 <= S <= 16, B's window at (ty + dy, tx + dx).
+ * Sums over the n = T^2 samples, exact in 64 bits (sum a b < 2^46 at T = 128):
+ *   sa = sum a, saa = sum a^2                    once per tile
+ *   sb = sum b, sbb = sum b^2, sab = sum a b     per offset
+ *   bad_a, bad_b: the samples outside [valid_min, valid_max] in the template and in B's whole (T + 2S)^2 search window
+ *   num = n sab - sa sb,  va = n saa - sa^2,  vb = n sbb - sb^2        (all fit int64)
+ *   score = (double)num / sqrt((double)va * (double)vb);  no score (-2) where va <= 0 or vb <= 0
+ * Peak: the largest score; among equal ones the first offset in row-major order (dy, then dx); the offset (0, 0) where no
+ * offset has a score.  (dx, dy) is where A's template is found in B, relative to its own position.
+ * Record of tile j * nx + i, OIP_MATCH_RECORD_WORDS uint64:
+ *   0 sa   1 saa   2 bad_a   3 bad_b   4 peak index (dy + S) * (2S + 1) + (dx + S)
+ *   5..19 (sb, sbb, sab) at the peak, then at its left (dx - 1), right (dx + 1), upper (dy - 1) and lower (dy + 1) neighbour;
+ *         three zeros for a neighbour outside the range
+ * d_sums, if not NULL, receives (sb, sbb, sab) of every offset of every tile: nx * ny * (2S + 1)^2 * 3 uint64, tile-major,
+ * offsets in row-major order.  Everything else -- scores, sub-pixel offsets, flags -- is computed on the host from the
+ * record's integers (oip_match_peak).  Asynchronous on the context's stream.
+ * OIP_E_INVALID: T or S out of range, a stride other than 1 or 4, w, rows, nx, ny, step_x or step_y < 1, a pitch shorter than
+ * (w - 1) * stride + 1, valid_min > valid_max or outside 0..65535, a NULL or odd plane or record pointer, nx * ny >= 2^31,
+ * or any search window that leaves w x rows: x0 < S, y0 < S, x0 + (nx - 1) step_x + T + S > w or the same in y. */
+#define OIP_MATCH_RECORD_WORDS 20
+#define OIP_MATCH_MIN_T 8
+#define OIP_MATCH_MAX_T 128
+#define OIP_MATCH_MAX_S 16
+#define OIP_MATCH_NO_SCORE (-2.0)
+#define OIP_MATCH_NODATA 1      /* bad_a + bad_b > 0 */
+#define OIP_MATCH_FLAT   2      /* no offset has a score */
+#define OIP_MATCH_EDGE   4      /* |dy| = S or |dx| = S at the peak */
+#define OIP_MATCH_WEAK   8      /* score < min_score */
+#define OIP_REGCHECK_SUFFIX ".REG"
+int oip_match_tiles_u16(oip_ctx *ctx, const uint16_t *d_a, long pitch_a, int stride_a, const uint16_t *d_b, long pitch_b,
+                        int stride_b, int w, long rows, int T, int S, int x0, long y0, int step_x, long step_y, int nx, long ny,
+                        int valid_min, int valid_max, uint64_t *d_records, uint64_t *d_sums);
+/* host: the grid of step `step` whose search windows lie inside w x rows: x0 = y0 = S, nx = (w - 2S - T) / step + 1 and ny
+ * likewise.  OIP_E_INVALID (and nx = ny = 0) for T, S out of range, step < 1, or an image that holds no tile.  No context. */
+int oip_match_grid(int w, long rows, int T, int S, int step, int *x0, long *y0, int *nx, long *ny);
+/* host: shift, score and flags of one record.  The score is the peak's; per axis the shift is the peak's integer offset plus
+ *   f = (l - r) / (2 (l - 2 c + r))     l, c, r: the scores of the left (upper) neighbour, the peak, the right (lower) one
+ * clamped to +-0.5 -- the vertex of the parabola through the three -- only where the peak is off the range's border on that
+ * axis, all three have a score and the denominator is negative; f = 0 otherwise.  flags: the OIP_MATCH_ bits above.
+ * OIP_E_INVALID for T, S out of range or a peak index >= (2S + 1)^2.  No context. */
+int oip_match_peak(const uint64_t *record, int T, int S, double min_score, double *dx, double *dy, double *score, int *flags);
+/* host: over the n_ok of n tiles whose flags are 0, out[8] = n_ok, mean dx, mean dy, their standard deviations (population),
+ * the RMS of the radial error r = sqrt(dx^2 + dy^2), its nearest-rank 90th percentile (CE90: the ceil(0.9 n_ok)-th smallest)
+ * and its maximum; all zero where n_ok = 0.  No context. */
+int oip_match_summary(const double *dx, const double *dy, const int *flags, long n, double *out);
+
 /* ---- instrumentation --------------------------------------------------------------- */
 /* name + accumulated device time of the kernels launched through this context since the
  * last reset, measured with HIP events on the context's stream (off by default). */

@@ -21,6 +21,9 @@ from .capi import (  # noqa: F401
     load_column_list,
     load_library,
     load_rrc_param_file,
+    match_grid,
+    match_peak,
+    match_summary,
     mtfc_design3,
     mtfc_load_kernel,
     mtfc_quantise,

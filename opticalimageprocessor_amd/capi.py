@@ -135,6 +135,10 @@ _SIGS = {
     "oip_despike_column_table": ([C.POINTER(_i), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(_i), _cp, _i], _i),
     "oip_halve_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _vp, _l], _i),
     "oip_overview_levels": ([_i, _l], _i),
+    "oip_match_tiles_u16": ([_vp, _vp, _l, _i, _vp, _l, _i, _i, _l, _i, _i, _i, _l, _i, _l, _i, _l, _i, _i, _vp, _vp], _i),
+    "oip_match_grid": ([_i, _l, _i, _i, _i, C.POINTER(_i), _lp, C.POINTER(_i), _lp], _i),
+    "oip_match_peak": ([C.POINTER(C.c_uint64), _i, _i, _d, _dp, _dp, _dp, C.POINTER(_i)], _i),
+    "oip_match_summary": ([_dp, _dp, C.POINTER(_i), _l, _dp], _i),
     "oip_merge_subimages_be16": ([_vp, _vp, _vp, _i, _i, _i, _i], _i),
     "oip_profile_enable": ([_vp, _i], _i),
     "oip_profile_reset": ([_vp], _i),
@@ -417,6 +421,41 @@ def overview_levels(w: int, h: int) -> int:
     return load_library().oip_overview_levels(w, h)
 
 
+MATCH_RECORD_WORDS = 20
+MATCH_NODATA, MATCH_FLAT, MATCH_EDGE, MATCH_WEAK = 1, 2, 4, 8
+
+
+def match_grid(w: int, rows: int, T: int, S: int, step: int):
+    """(x0, y0, nx, ny) of the regcheck grid of step `step` whose search windows lie inside w x rows (include/oip_c.h:
+    oip_match_grid); ValueError for sizes out of range or an image that holds no tile"""
+    x0, y0, nx, ny = _i(), _l(), _i(), _l()
+    if load_library().oip_match_grid(w, rows, T, S, step, C.byref(x0), C.byref(y0), C.byref(nx), C.byref(ny)):
+        raise ValueError("oip_match_grid: T a multiple of 8 in 8..128, 1 <= S <= 16, step >= 1 and an image of at least T + 2S expected")
+    return x0.value, y0.value, nx.value, ny.value
+
+
+def match_peak(record, T: int, S: int, min_score: float = 0.5):
+    """(dx, dy, score, flags) of one 20-word record of Context.match_tiles_u16 (include/oip_c.h: oip_match_peak)"""
+    r = np.ascontiguousarray(record, dtype=np.uint64).reshape(-1)
+    assert r.size == MATCH_RECORD_WORDS, r.size
+    dx, dy, sc, fl = _d(), _d(), _d(), _i()
+    if load_library().oip_match_peak(r.ctypes.data_as(C.POINTER(C.c_uint64)), T, S, min_score, C.byref(dx), C.byref(dy), C.byref(sc), C.byref(fl)):
+        raise ValueError("oip_match_peak: bad T, S or peak index")
+    return dx.value, dy.value, sc.value, fl.value
+
+
+def match_summary(dx, dy, flags) -> np.ndarray:
+    """(count, mean dx, mean dy, std dx, std dy, rms, ce90, max) over the tiles whose flags are 0 (include/oip_c.h:
+    oip_match_summary)"""
+    x, y = _dbl(dx).reshape(-1), _dbl(dy).reshape(-1)
+    f = np.ascontiguousarray(flags, dtype=np.int32).reshape(-1)
+    assert x.size == y.size == f.size
+    out = np.zeros(8)
+    if load_library().oip_match_summary(x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), f.ctypes.data_as(C.POINTER(_i)), x.size, out.ctypes.data_as(_dp)):
+        raise ValueError("oip_match_summary: bad argument")
+    return out
+
+
 FIT_MODES = {"reference": 0, "lstsq": 1}
 
 
@@ -562,6 +601,13 @@ class Context:
         """one pyramid level: 2 x 2 means, skipping samples below valid_min, of rows x w pixels of spp samples (lines src_pitch
         samples apart) into ceil(rows / 2) lines of ceil(w / 2) pixels, dst_pitch samples apart (include/oip_c.h: oip_halve_u16)"""
         self._ck(self.lib.oip_halve_u16(self.h, _ptr(src), src_pitch, w, rows, spp, valid_min, _ptr(dst), dst_pitch))
+
+    def match_tiles_u16(self, a, pitch_a, stride_a, b, pitch_b, stride_b, w, rows, T, S, x0, y0, step_x, step_y, nx, ny, valid_min, valid_max,
+                        records, sums=None):
+        """regcheck: per tile of the nx x ny grid the 20-word record of the T x T template of plane a matched in plane b over
+        offsets [-S, S]^2, and (sums not None) the three sums of every offset (include/oip_c.h: oip_match_tiles_u16)"""
+        self._ck(self.lib.oip_match_tiles_u16(self.h, _ptr(a), pitch_a, stride_a, _ptr(b), pitch_b, stride_b, w, rows, T, S, x0, y0, step_x, step_y,
+                                              nx, ny, valid_min, valid_max, _ptr(records), _ptr(sums)))
 
     def histogram_u16(self, img, pitch, w, rows, hist):
         """counts of rows x w u16 (lines `pitch` samples apart) ADDED into hist: 65536 uint64 on the device, zeroed by the caller"""

@@ -617,6 +617,100 @@ extern "C" int oip_overview_levels(int w, long h)
     return n;
 }
 
+// ---- regcheck: the host side of oip_match_tiles_u16 (include/oip_c.h) ---------------------------------------------------
+static bool match_sizes_ok(int T, int S)
+{
+    return T >= OIP_MATCH_MIN_T && T <= OIP_MATCH_MAX_T && T % 8 == 0 && S >= 1 && S <= OIP_MATCH_MAX_S;
+}
+
+extern "C" int oip_match_grid(int w, long rows, int T, int S, int step, int *x0, long *y0, int *nx, long *ny)
+{
+    if (!x0 || !y0 || !nx || !ny) return OIP_E_INVALID;
+    *x0 = 0; *y0 = 0; *nx = 0; *ny = 0;
+    if (!match_sizes_ok(T, S) || step < 1 || w < T + 2 * S || rows < T + 2 * S) return OIP_E_INVALID;
+    *x0 = S;
+    *y0 = S;
+    *nx = (w - 2 * S - T) / step + 1;
+    *ny = (rows - 2 * S - T) / step + 1;
+    return OIP_OK;
+}
+
+// the score of one (sb, sbb, sab) against the tile's sa, saa: the ONE statement of it on the host
+static double match_score(int64_t n, int64_t sa, int64_t saa, const uint64_t *q)
+{
+    const int64_t sb = (int64_t)q[0], sbb = (int64_t)q[1], sab = (int64_t)q[2];
+    const int64_t va = n * saa - sa * sa, vb = n * sbb - sb * sb;
+    if (va <= 0 || vb <= 0) return OIP_MATCH_NO_SCORE;
+    return (double)(n * sab - sa * sb) / sqrt((double)va * (double)vb);
+}
+
+static double match_subpixel(double l, double c, double r)
+{
+    if (l <= OIP_MATCH_NO_SCORE || c <= OIP_MATCH_NO_SCORE || r <= OIP_MATCH_NO_SCORE) return 0.0;
+    const double den = l - 2.0 * c + r;
+    if (!(den < 0.0)) return 0.0;
+    const double f = (l - r) / (2.0 * den);
+    return f > 0.5 ? 0.5 : (f < -0.5 ? -0.5 : f);
+}
+
+extern "C" int oip_match_peak(const uint64_t *record, int T, int S, double min_score, double *dx, double *dy, double *score, int *flags)
+{
+    if (!record || !dx || !dy || !score || !flags || !match_sizes_ok(T, S)) return OIP_E_INVALID;
+    const int K = 2 * S + 1;
+    if (record[4] >= (uint64_t)(K * K)) return OIP_E_INVALID;
+    const int j = (int)record[4] / K, i = (int)record[4] % K;
+    const int64_t n = (int64_t)T * T, sa = (int64_t)record[0], saa = (int64_t)record[1];
+    double sc[5];                                                // peak, left, right, upper, lower
+    for (int k = 0; k < 5; ++k) sc[k] = match_score(n, sa, saa, record + 5 + 3 * k);
+    const double fx = i > 0 && i < K - 1 ? match_subpixel(sc[1], sc[0], sc[2]) : 0.0;
+    const double fy = j > 0 && j < K - 1 ? match_subpixel(sc[3], sc[0], sc[4]) : 0.0;
+    int f = 0;
+    if (record[2] + record[3] > 0) f |= OIP_MATCH_NODATA;
+    if (sc[0] <= OIP_MATCH_NO_SCORE) f |= OIP_MATCH_FLAT;
+    if (i == 0 || i == K - 1 || j == 0 || j == K - 1) f |= OIP_MATCH_EDGE;
+    if (sc[0] < min_score) f |= OIP_MATCH_WEAK;
+    *dx = (double)(i - S) + fx;
+    *dy = (double)(j - S) + fy;
+    *score = sc[0];
+    *flags = f;
+    return OIP_OK;
+}
+
+extern "C" int oip_match_summary(const double *dx, const double *dy, const int *flags, long n, double *out)
+{
+    if (!out || n < 0 || (n > 0 && (!dx || !dy || !flags))) return OIP_E_INVALID;
+    for (int k = 0; k < 8; ++k) out[k] = 0.0;
+    std::vector<double> r;
+    double sx = 0.0, sy = 0.0;
+    for (long t = 0; t < n; ++t)
+        if (flags[t] == 0) {
+            sx += dx[t];
+            sy += dy[t];
+            r.push_back(sqrt(dx[t] * dx[t] + dy[t] * dy[t]));
+        }
+    const size_t m = r.size();
+    if (m == 0) return OIP_OK;
+    const double mx = sx / (double)m, my = sy / (double)m;
+    double vx = 0.0, vy = 0.0, rr = 0.0;
+    for (long t = 0; t < n; ++t)
+        if (flags[t] == 0) {
+            vx += (dx[t] - mx) * (dx[t] - mx);
+            vy += (dy[t] - my) * (dy[t] - my);
+            rr += dx[t] * dx[t] + dy[t] * dy[t];
+        }
+    std::sort(r.begin(), r.end());
+    const size_t rank = (9 * m + 9) / 10;                        // ceil(0.9 m), exact in integers
+    out[0] = (double)m;
+    out[1] = mx;
+    out[2] = my;
+    out[3] = sqrt(vx / (double)m);
+    out[4] = sqrt(vy / (double)m);
+    out[5] = sqrt(rr / (double)m);
+    out[6] = r[rank - 1];
+    out[7] = r[m - 1];
+    return OIP_OK;
+}
+
 extern "C" int oip_write_tiff_u8(const char *path, const uint8_t *data, int width, long height, int spp, char *err, int errlen)
 {
     auto fail = [&](int code, const char *msg) {

@@ -16,13 +16,16 @@
 //                               bad columns interpolated, impulse pixels replaced by a conditional 3 x 3 median, see run_despike()
 //   oip overviews IMAGE [-o OUT] [--levels N] [--valid-min N]   the reduced-resolution pyramid of a strip or product as
 //                               <IMAGE>.ovr beside it; `stitch --overviews [--levels N]` writes its product's, see run_overviews()
+//   oip regcheck --image1 A [--image2 B] [--band1 k] [--band2 k] [--scale F] [--shift-x N] [--shift-y N] [--tile T] [--search S]
+//                               how well two rasters are registered: tile matching (ZNCC), a shift and a score per tile and a
+//                               summary in <A>.REG.CSV, see run_regcheck()
 //   oip -v | --version          prints 1.1
 // plus --width N (pixels per PAN line; the reference hard-codes 12288, oipshared.h:28).
 // `auxsep` is outside this build.  TIFF input and output go through oip_tiff.hpp (uncompressed and LZW, with
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
 // --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
-// despike and overviews sub-commands.
+// despike, overviews and regcheck sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -196,7 +199,17 @@ void usage()
          "  overviews  IMAGE.RAW|IMAGE.TIFF: the reduced-resolution pyramid of a strip or product, every band at 16 bits, each level\n"
          "             the 2 x 2 average of the one before; written to IMAGE.ovr beside the image, where GDAL-based viewers look for it:\n"
          "             [-o,--out FILE] [--levels N] (1..16; default: until a level fits 256 x 256) [--valid-min N] (samples below are\n"
-         "             no data and do not enter an average; default 1) [--width N] [--force]");
+         "             no data and do not enter an average; default 1) [--width N] [--force]\n"
+         "  regcheck   --image1 A [--image2 B]: how well B is registered to A (TIFF of 1 or 4 samples, or single-band RAW), measured by\n"
+         "             template matching (zero-mean normalised cross-correlation from exact integer sums) on a grid of tiles; writes\n"
+         "             x,y,dx,dy,score,flags per tile and a summary (count, mean, std, RMS, CE90, max) to <stem of A>.REG.CSV:\n"
+         "             [--band1 k] [--band2 k] (1-based; B defaults to A: band against band of one aligned product)\n"
+         "             [--scale F] (2..64: box-decimate A first; PAN against an MSS band is --scale 4)\n"
+         "             [--shift-x N] [--shift-y N] (B's origin in (decimated) A coordinates; the CCD overlap is --shift-x W-fold)\n"
+         "             [--tile T] (multiple of 8, 8..128; default 64) [--search S] (1..16; default 4) [--step N] (default T)\n"
+         "             [--valid-min N] [--valid-max N] (samples outside are no data; default 1, 65535) [--min-score X] (default 0.5)\n"
+         "             flags: 1 no data in the tile, 2 flat, 4 peak on the border of the search range, 8 score below --min-score\n"
+         "             [--width N] [--width2 N] (RAW: samples per line of A / B) [-o,--out report.csv] [--force]");
 }
 
 int run_prestitch(const std::vector<std::string> &args, int width)
@@ -664,6 +677,56 @@ int run_overviews(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip regcheck --image1 A [--image2 B]: the registration check of two rasters (RunRegcheck).  Bad values end in 105, an
+// option that needs another in 107, before any file is read.
+int run_regcheck(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--image1", "--image2", "--band1", "--band2", "--scale", "--shift-x", "--shift-y", "--tile", "--search", "--step",
+                 "--valid-min", "--valid-max", "--min-score", "--width", "--width2", "--out"};
+    sp.flags = {"--force", "--bil"};
+    sp.alias = {{"-o", "--out"}};
+    Parsed p = parse(sp, args);
+    require(p, "--image1");
+    existing_file(p, "--image1");
+    existing_file(p, "--image2");
+    if (p.has("--width2") && !p.has("--image2")) throw cli_error(107, "--width2 requires --image2");
+    if ((p.has("--shift-x") || p.has("--shift-y")) && !p.has("--image2")) throw cli_error(107, "--shift-x / --shift-y require --image2");
+    RegcheckOptions o;
+    o.image2 = p.str("--image2");
+    o.band1 = p.integer("--band1", 1);
+    o.band2 = p.integer("--band2", 1);
+    if (o.band1 < 1 || o.band1 > MSS_BANDS || o.band2 < 1 || o.band2 > MSS_BANDS) throw cli_error(105, "--band1/--band2: 1 <= k <= 4 expected");
+    o.scale = p.integer("--scale", 1);
+    if (p.has("--scale") && o.scale != 2 && o.scale != 4 && o.scale != 8 && o.scale != 16 && o.scale != 32 && o.scale != 64)
+        throw cli_error(105, "--scale: one of 2, 4, 8, 16, 32, 64 expected");
+    o.shiftX = p.integer("--shift-x", 0);
+    o.shiftY = p.integer("--shift-y", 0);
+    o.tile = p.integer("--tile", 64);
+    if (o.tile < OIP_MATCH_MIN_T || o.tile > OIP_MATCH_MAX_T || o.tile % 8 != 0) throw cli_error(105, "--tile: a multiple of 8, 8 <= T <= 128 expected");
+    o.search = p.integer("--search", 4);
+    if (o.search < 1 || o.search > OIP_MATCH_MAX_S) throw cli_error(105, "--search: 1 <= S <= 16 expected");
+    o.step = p.integer("--step", o.tile);
+    if (o.step < 1) throw cli_error(105, "--step: N >= 1 expected");
+    o.validMin = p.integer("--valid-min", 1);
+    o.validMax = p.integer("--valid-max", 65535);
+    if (o.validMin < 0 || o.validMax > 65535 || o.validMin > o.validMax) throw cli_error(105, "--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
+    o.minScore = p.real("--min-score", 0.5);
+    if (!(o.minScore >= -1.0 && o.minScore <= 1.0)) throw cli_error(105, "--min-score: -1 <= X <= 1 expected");
+    o.width = p.integer("--width", width);
+    o.width2 = p.integer("--width2", 0);
+    if (o.width <= 0 || (p.has("--width2") && o.width2 <= 0)) throw cli_error(105, "--width/--width2: a positive line width expected");
+    o.bil = p.flag.count("--bil") != 0;
+    o.force = p.flag.count("--force") != 0;
+    char buf[256];
+    snprintf(buf, sizeof buf, " band1=%d band2=%d scale=%d shift-x=%ld shift-y=%ld tile=%d search=%d step=%d valid-min=%d valid-max=%d min-score=%g",
+             o.band1, o.band2, o.scale, o.shiftX, o.shiftY, o.tile, o.search, o.step, o.validMin, o.validMax, o.minScore);
+    o.params = "oip regcheck image1=" + p.str("--image1") + " image2=" + (o.image2.empty() ? p.str("--image1") : o.image2) + buf +
+               " columns=x,y,dx,dy,score,flags";
+    RunRegcheck(p.str("--image1"), p.str("--out"), o);
+    return 0;
+}
+
 }  // namespace
 
 static int oip_main(int argc, const char *argv[]);
@@ -715,6 +778,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "mtfc") return run_mtfc({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "despike") return run_despike({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "overviews") return run_overviews({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "regcheck") return run_regcheck({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "auxsep")
                 throw std::invalid_argument("auxsep (down-link de-framing) is outside this build: run the reference's auxsep, then this tool");
             if (args.empty()) { usage(); return 0; }

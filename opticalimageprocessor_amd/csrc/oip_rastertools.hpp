@@ -1,9 +1,11 @@
-// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, overviews) above
-// the host layer of oip_host.hpp: what they check before a device is touched, the one driver that streams a RAW strip through
-// the device in line blocks (geometry: oip_stripplan.hpp), the resident filter of a TIFF product, and the five tools.
+// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, overviews,
+// regcheck) above the host layer of oip_host.hpp: what they check before a device is touched, the one driver that streams a
+// RAW strip through the device in line blocks (geometry: oip_stripplan.hpp), the resident filter of a TIFF product, and the
+// six tools.
 #pragma once
 
 #include "oip_host.hpp"
+#include "oip_regreport.hpp"
 #include "oip_stripplan.hpp"
 
 namespace OIPGPU {
@@ -637,6 +639,138 @@ inline void RunOverviews(const std::string &file, const std::string &out, const 
     }
     const double es = total.tick();
     OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+}
+
+// ---- oip regcheck: how well two rasters are registered ------------------------------------------------------------------
+// Dense template matching (oip_match_tiles_u16: ZNCC from exact integer sums, no code shared with the phase correlation it
+// judges) of image 2 against image 1 on a grid of tiles; shift, score and flags per tile and the summary come from the
+// records on the host (oip_regreport.hpp) and go to <stem of image1>.REG.CSV.  Both images are resident.  Three uses: band
+// against band inside one aligned MSS product (one image, --band1 / --band2), PAN against an MSS band (--scale 4 box-decimates
+// image 1 first), the CCD overlap (--shift-x W - fold).  Not in the reference.
+struct RegcheckOptions {
+    std::string image2;                     // empty: image 1
+    int band1 = 1, band2 = 1;               // 1-based
+    int scale = 1;                          // 1: none; 2 .. 64: box decimation of image 1 (oip_decimate_box_u16)
+    long shiftX = 0, shiftY = 0;            // image 2's origin in (decimated) image-1 coordinates
+    int tile = 64, search = 4, step = 0;    // step 0: the tile size
+    int validMin = 1, validMax = 65535;
+    double minScore = 0.5;
+    int width = OIP_PIXELS_PER_LINE, width2 = 0;      // RAW inputs: samples per line (width2 0: width)
+    bool bil = false;                       // refused: BIL RAW is left out on purpose
+    bool force = false;
+    std::string params;                     // the first line of the report
+};
+
+// everything that can be refused without a device; returns the output path
+inline std::string RegcheckCheck(const std::string &file, const std::string &out, const RegcheckOptions &o, bool *isTiff1, bool *isTiff2)
+{
+    const std::string file2 = o.image2.empty() ? file : o.image2;
+    *isTiff1 = RasterContainer(file, "regcheck") == ".tiff";
+    *isTiff2 = RasterContainer(file2, "regcheck") == ".tiff";
+    if (o.bil) throw std::invalid_argument("regcheck: a BIL RAW strip is not supported: split the bands first (the default action writes them)");
+    const int T = o.tile, S = o.search, F = o.scale;
+    if (T < OIP_MATCH_MIN_T || T > OIP_MATCH_MAX_T || T % 8 != 0) throw usage_error("--tile: a multiple of 8, 8 <= T <= 128 expected");
+    if (S < 1 || S > OIP_MATCH_MAX_S) throw usage_error("--search: 1 <= S <= 16 expected");
+    if (o.step < 0) throw usage_error("--step: N >= 1 expected");
+    if (F != 1 && F != 2 && F != 4 && F != 8 && F != 16 && F != 32 && F != 64) throw usage_error("--scale: one of 2, 4, 8, 16, 32, 64 expected");
+    if (o.validMin < 0 || o.validMax > 65535 || o.validMin > o.validMax) throw usage_error("--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
+    if (!(o.minScore >= -1.0 && o.minScore <= 1.0)) throw usage_error("--min-score: -1 <= X <= 1 expected");
+    const int bands[2] = {o.band1, o.band2};
+    const bool tiff[2] = {*isTiff1, *isTiff2};
+    for (int k = 0; k < 2; ++k) {
+        const int nb = tiff[k] ? MSS_BANDS : 1;
+        if (bands[k] < 1 || bands[k] > nb) throw usage_error(std::string(k ? "--band2" : "--band1") + ": band index out of range (1.." + std::to_string(nb) + ")");
+    }
+    const int W2 = o.width2 > 0 ? o.width2 : o.width;
+    if ((!*isTiff1 && o.width <= 0) || (!*isTiff2 && W2 <= 0)) throw std::invalid_argument("--width / --width2: a positive line width expected");
+    if (!*isTiff1) RawLineCount(file, "image1", (size_t)o.width * BYTES_PER_PIXEL);
+    if (!*isTiff2) RawLineCount(file2, "image2", (size_t)W2 * BYTES_PER_PIXEL);
+    const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_REGCHECK_SUFFIX, ".CSV") : out;
+    struct stat st;
+    if (stat(path.c_str(), &st) == 0) {
+        if (std::filesystem::equivalent(path, file) || std::filesystem::equivalent(path, file2)) throw std::invalid_argument("output file [" + path + "] is an input image");
+        if (!o.force) throw std::runtime_error("output file [" + path + "] exists: regcheck does not replace a file without --force");
+    }
+    return path;
+}
+
+inline void RunRegcheck(const std::string &file, const std::string &out, const RegcheckOptions &o)
+{
+    bool isTiff[2] = {false, false};
+    const std::string outPath = RegcheckCheck(file, out, o, &isTiff[0], &isTiff[1]);
+    const std::string file2 = o.image2.empty() ? file : o.image2;
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    // a resident image: TIFF of 1 or 4 samples, or single-band RAW
+    struct Image {
+        DevBuf<uint16_t> buf;
+        int w = 0, spp = 1;
+        long h = 0;
+    } img[2];
+    auto load = [&](int k, const std::string &path, int rawWidth, int band) {
+        Image &m = img[k];
+        if (isTiff[k]) {
+            OLOG("Reading image from file `%s' ...", path.c_str());
+            read_tiff_to_device(path, &m.w, &m.h, &m.spp, m.buf);
+            if (m.spp != 1 && m.spp != MSS_BANDS) throw std::invalid_argument("regcheck: a TIFF of 1 or 4 samples per pixel expected");
+            if (band > m.spp) throw usage_error(std::string(k ? "--band2" : "--band1") + ": band index out of range (1.." + std::to_string(m.spp) + ")");
+        } else {
+            m.w = rawWidth;
+            m.h = RawLineCount(path, k ? "image2" : "image1", (size_t)rawWidth * BYTES_PER_PIXEL);
+            m.buf.alloc((size_t)m.w * m.h);
+            m.buf.load_file(path, (size_t)m.w * m.h);
+        }
+    };
+    load(0, file, o.width, o.band1);
+    const bool shared = o.image2.empty() || std::filesystem::equivalent(file, file2);          // one file: read once
+    if (!shared) load(1, file2, o.width2 > 0 ? o.width2 : o.width, o.band2);
+    else if (o.band2 > img[0].spp) throw usage_error("--band2: band index out of range (1.." + std::to_string(img[0].spp) + ")");
+    const Image &m2 = shared ? img[0] : img[1];
+
+    // plane A: band1 of image 1, or of its F x F box decimation (one plane per band)
+    const uint16_t *A = img[0].buf.p + (o.band1 - 1);
+    long pitchA = (long)img[0].w * img[0].spp, w1 = img[0].w, h1 = img[0].h;
+    int strideA = img[0].spp;
+    DevBuf<uint16_t> planes;
+    if (o.scale > 1) {
+        const int F = o.scale, ow = (img[0].w + F - 1) / F;
+        const long oh = (img[0].h + F - 1) / F;
+        const size_t plane = (size_t)ow * oh;
+        planes.alloc(plane * img[0].spp);
+        ck(oip_decimate_box_u16(ctx, img[0].buf.p, pitchA, img[0].w, img[0].h, img[0].spp, F, planes.p, ow, plane));
+        A = planes.p + (size_t)(o.band1 - 1) * plane;
+        pitchA = ow; strideA = 1; w1 = ow; h1 = oh;
+    }
+    const uint16_t *B = m2.buf.p + (o.band2 - 1);
+    const long pitchB = (long)m2.w * m2.spp;
+    const int strideB = m2.spp;
+
+    RegOverlap ov;
+    RegGrid g;
+    g.T = o.tile; g.S = o.search; g.step = o.step > 0 ? o.step : o.tile; g.scale = o.scale;
+    if (!RegIntersect(w1, h1, m2.w, m2.h, o.shiftX, o.shiftY, &ov) || ov.w >= (1L << 31) ||
+        oip_match_grid((int)ov.w, ov.h, g.T, g.S, g.step, &g.x0, &g.y0, &g.nx, &g.ny) != OIP_OK)
+        throw std::invalid_argument("regcheck: the images overlap on " + std::to_string(ov.w) + " x " + std::to_string(ov.h) +
+                                    " pixels, which holds no tile of " + std::to_string(g.T + 2 * g.S) + " x " + std::to_string(g.T + 2 * g.S));
+    g.originX = ov.ax; g.originY = ov.ay;
+    const size_t n = (size_t)g.nx * g.ny;
+    OLOG("Matching %d x %ld tiles of %d x %d, search +-%d, on %ld x %ld pixels ...", g.nx, g.ny, g.T, g.T, g.S, ov.w, ov.h);
+    DevBuf<uint64_t> records(n * OIP_MATCH_RECORD_WORDS);
+    stop_watch sw;
+    ck(oip_match_tiles_u16(ctx, A + ov.ay * pitchA + ov.ax * strideA, pitchA, strideA, B + ov.by * pitchB + ov.bx * strideB, pitchB, strideB, (int)ov.w, ov.h,
+                           g.T, g.S, g.x0, g.y0, g.step, g.step, g.nx, g.ny, o.validMin, o.validMax, records.p, nullptr));
+    std::vector<uint64_t> rec(n * OIP_MATCH_RECORD_WORDS);
+    records.download(rec.data(), rec.size());
+    ck(oip_sync(ctx));
+    OLOG("Matched in %.3f seconds.", sw.tick());
+    FILE *f = fopen(outPath.c_str(), "w");
+    if (!f) throw std::runtime_error("open file [" + outPath + "] failed: " + std::to_string(errno));
+    RegSummary sum;
+    const bool ok = WriteRegReport(f, o.params, rec.data(), g, o.minScore, &sum);
+    if (fclose(f) != 0 || !ok) throw std::runtime_error("write file [" + outPath + "] failed");
+    OLOG("regcheck: %s", RegSummaryLine(sum).c_str());
+    OLOG("Report written to '%s' in %.3f seconds.", outPath.c_str(), total.tick());
 }
 
 }  // namespace OIPGPU
