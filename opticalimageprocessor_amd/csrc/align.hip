@@ -193,18 +193,9 @@ struct AlignFix {
     int group, band, ra, rb;
 };
 
-// Six dwords = the 11 samples a lane's 8 pixels tap on one source line (12 with the sample in front of an odd first column).
-// `lane_base` is the lane's plane advanced to the dword of its first column; widths are even, so a line is a whole number of
-// dwords and the address is one 64-bit multiply-add with the six loads at immediate offsets.  A REGULAR group's window ends
-// inside its own line (ix0 + 11 < Wb below), so no dword can leave the buffer and nothing is clamped: the clamped form this
-// replaces made the compiler carry six separate 64-bit addresses through the merge of its two branches (a fifth of the
-// kernel's vector instructions, and the kernel is bound by their issue rate -- DESIGN 4.1).
-__device__ __forceinline__ void align_load_raw6(const uint32_t *__restrict__ lane_base, long row, int half_pitch, uint32_t w[6])
-{
-    const uint32_t *q = lane_base + row * half_pitch;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) w[i] = q[i];
-}
+// Line load (six dwords per lane and source line, unclamped: ix0 + 11 < Wb below), tap window, weights and sums are
+// oip_bicubic.h's oip_load_raw6 and OipTaps8<false>, shared with remap.hip's fast kernels; the map evaluation, the fix-up list
+// and the transposing store are this kernel's own.
 __global__ __launch_bounds__(kBlock, 3) void align_mss8_kernel(const uint16_t *__restrict__ planes, size_t plane_stride,
                                                                long src_rows, uint16_t *__restrict__ dst,
                                                                const AlignRow *__restrict__ rows, int Wb, long out_rows,
@@ -253,15 +244,13 @@ __global__ __launch_bounds__(kBlock, 3) void align_mss8_kernel(const uint16_t *_
         xreg = xreg && mono && ix0 >= 0 && ix0 + 11 < Wb;      // + 11: the sixth dword of an even first column stays in the line
     }
     const int c0 = xreg ? ix0 : 0;
-    const bool odd = c0 & 1;
     const uint32_t *lane_base = reinterpret_cast<const uint32_t *>(pl) + (c0 >> 1);
     const int half_pitch = Wb >> 1;
     float wx[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) wx[j] = tab1d[fx0 * 4 + j];
 
-    oip_f2 win[4][7];
-    float w2d[16];
+    OipTaps8<false> taps;
     uint32_t nraw[6] = {0u, 0u, 0u, 0u, 0u, 0u};
     long nline = -1;                 // global plane line whose raw dwords are in nraw (-1: none)
     int cur_iy = INT_MIN, cur_base = INT_MIN, cur_fy = -1;
@@ -286,29 +275,21 @@ __global__ __launch_bounds__(kBlock, 3) void align_mss8_kernel(const uint16_t *_
                     const bool slide = a.base == cur_base && iy == cur_iy + 1;
                     if (slide) {
                         // rotate: this unrolled step's slot order is (k + t) & 3
-                        if (nline == l0 + 3) oip_expand_pairs(nraw, odd, win[(k + 3) & 3]);
-                        else { uint32_t w[6]; align_load_raw6(lane_base, l0 + 3, half_pitch, w); oip_expand_pairs(w, odd, win[(k + 3) & 3]); }
+                        if (nline == l0 + 3) taps.expand(nraw, c0, (k + 3) & 3);
+                        else { uint32_t w[6]; oip_load_raw6(lane_base, l0 + 3, half_pitch, w); taps.expand(w, c0, (k + 3) & 3); }
                     } else {
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) { uint32_t w[6]; align_load_raw6(lane_base, l0 + t, half_pitch, w); oip_expand_pairs(w, odd, win[(k + t) & 3]); }
+                        for (int t = 0; t < 4; ++t) { uint32_t w[6]; oip_load_raw6(lane_base, l0 + t, half_pitch, w); taps.expand(w, c0, (k + t) & 3); }
                     }
                     cur_base = a.base; cur_iy = iy;
                     // next line's newest source line, in flight under this line's sums
                     nline = l0 + 4;
-                    if (nline < src_rows) align_load_raw6(lane_base, nline, half_pitch, nraw); else nline = -1;
+                    if (nline < src_rows) oip_load_raw6(lane_base, nline, half_pitch, nraw); else nline = -1;
                     if (fy != cur_fy) {
                         cur_fy = fy;
-#pragma unroll
-                        for (int ky = 0; ky < 4; ++ky) {
-                            const float wy = tab1d[fy * 4 + ky];
-#pragma unroll
-                            for (int kx = 0; kx < 4; ++kx) w2d[ky * 4 + kx] = __fmul_rn(wy, wx[kx]);
-                        }
+                        taps.weights(tab1d, fy, wx);
                     }
-                    oip_f2 sum[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) oip_row_taps8(win[(k + t) & 3], w2d + t * 4, t == 0, sum);
-                    px = oip_sat_pack8(sum);
+                    px = taps.sums(k);
                 } else {
                     // the slot rotation of the unrolled loop assumes one slide per step: a skipped line breaks it
                     cur_iy = INT_MIN;

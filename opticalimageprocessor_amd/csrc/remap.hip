@@ -181,6 +181,8 @@ __global__ __launch_bounds__(kBlock) void remap_shift_kernel(const uint16_t *__r
 // inside the 8, image borders) and lines whose window touches a section border are NOT written
 // here: two small fix-up launches of the general per-column code handle them, which keeps this
 // kernel free of calls and within 128 VGPRs.  Arithmetic order per pixel is oip_bicubic_interior.
+// Line load, tap window, weights, sums and store are oip_bicubic.h's (oip_load_raw6, OipTaps8, oip_store8), shared with the
+// RRC-on-load kernel below and with align.hip's fast kernel.
 __host__ __device__ inline bool shift_group_regular(int x0, int W, double dx, int *ix0_out, int *fx0_out)
 {
     int ix0 = 0, fx0 = 0;
@@ -201,201 +203,14 @@ __host__ __device__ inline bool shift_group_regular(int x0, int W, double dx, in
     return regular && ix0 >= 0 && ix0 + 11 < W;
 }
 
-// One source line of a lane = 11 consecutive u16 = 6 dwords from a 4-byte aligned address.  The load is split
-// from its use: the raw dwords of the NEXT output line's new source line are requested before the current
-// line's 16-tap sums, so twice the bytes are in flight per wave (these kernels are bound by memory-level
-// parallelism: 1 KiB per wave and line, 16-24 waves per CU, against ~35 KiB per CU that the latency-bandwidth
-// product of HBM asks for).
-__device__ __forceinline__ void load_raw6(const uint32_t *__restrict__ lane_base, int row, int half_pitch, uint32_t w[6])
-{
-    // lane_base: the dword holding the lane's first tap column on line 0 (W is even: a line is half_pitch dwords).  A regular
-    // group's six dwords stay inside its line (shift_group_regular), so the address is one 64-bit multiply-add with six
-    // immediate offsets and nothing is clamped.  Round 3 had dropped the per-dword clamps for all lines but the buffer's last
-    // (708 -> 530 vector instructions per line and wave); the remaining two-branch form still made the compiler carry six
-    // 64-bit addresses through the merge (84 v_lshl_add_u64 per line).
-    const uint32_t *q = lane_base + (long)row * half_pitch;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) w[i] = q[i];
-}
-
+// The register-window kernel in both accumulate modes (OipTaps8<F16>, oip_bicubic.h: F16 = the fp16-accumulate sums, whose
+// tolerance is stated there).  The raw dwords of the source line the NEXT output line will add are requested one output line
+// ahead (oip_load_raw6), under the current line's sums.
+template <bool F16>
 __global__ __launch_bounds__(kBlock, 4) void remap_shift8_kernel(const uint16_t *__restrict__ src, uint16_t *__restrict__ dst, DstWin dw,
                                                                  const RowInfo *__restrict__ rows, int W, long out_rows,
                                                                  long src_elems, double dx, const float *__restrict__ tab1d,
                                                                  int rows_per_block)
-{
-    const int x0 = (blockIdx.x * kBlock + threadIdx.x) * 8;
-    if (x0 >= W || x0 + 8 <= dw.col0) return;
-    int c0, fx0;
-    if (!shift_group_regular(x0, W, dx, &c0, &fx0)) return;        // fix-up launch A
-    const long r0 = (long)blockIdx.y * rows_per_block;
-    long r1 = r0 + rows_per_block;
-    if (r1 > out_rows) r1 = out_rows;
-    float wx[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) wx[j] = tab1d[fx0 * 4 + j];
-
-    const uint32_t *lane_base = reinterpret_cast<const uint32_t *>(src) + (c0 >> 1);
-    const int half_pitch = W >> 1;
-    const bool odd = c0 & 1;
-    oip_f2 win[4][7];                             // tap line t at unrolled step k lives in win[(k+t)&3], as sample pairs
-    float w2d[16];
-    int cur1 = -2, cur2 = -2, cur3 = -2;
-    int cur_fy = -1;
-    uint32_t nraw[6] = {0u, 0u, 0u, 0u, 0u, 0u};  // raw dwords of source line `nline`, requested one output line ahead
-    int nline = -2;
-    for (long rb = r0; rb < r1; rb += 4) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const long r = rb + k;
-            if (r >= r1) break;
-            const RowInfo ri = rows[r];
-            if (ri.flags != 1) { cur1 = cur2 = cur3 = -2; continue; }      // fix-up launch B
-            const bool slide = cur1 != -2 && ri.src[0] == cur1 && ri.src[1] == cur2 && ri.src[2] == cur3;
-            if (slide) {
-                if (ri.src[3] == nline) oip_expand_pairs(nraw, odd, win[(k + 3) & 3]);
-                else { uint32_t w[6]; load_raw6(lane_base, ri.src[3], half_pitch, w); oip_expand_pairs(w, odd, win[(k + 3) & 3]); }
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) { uint32_t w[6]; load_raw6(lane_base, ri.src[t], half_pitch, w); oip_expand_pairs(w, odd, win[(k + t) & 3]); }
-            }
-            cur1 = ri.src[1]; cur2 = ri.src[2]; cur3 = ri.src[3];
-            // the line the next output line will add in the regular case (its taps one line further down)
-            nline = -2;
-            if (r + 1 < r1 && (long)(ri.src[3] + 1) * W < src_elems) {
-                nline = ri.src[3] + 1;
-                load_raw6(lane_base, nline, half_pitch, nraw);
-            }
-            if (ri.fy != cur_fy) {
-                cur_fy = ri.fy;
-#pragma unroll
-                for (int ky = 0; ky < 4; ++ky) {
-                    const float wy = tab1d[cur_fy * 4 + ky];
-#pragma unroll
-                    for (int kx = 0; kx < 4; ++kx) w2d[ky * 4 + kx] = __fmul_rn(wy, wx[kx]);
-                }
-            }
-            uint4 o;
-            {
-                oip_f2 sum[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) oip_row_taps8(win[(k + t) & 3], w2d + t * 4, t == 0, sum);
-                o = oip_sat_pack8(sum);
-            }
-            uint16_t *drow = dst + r * dw.pitch + x0 + dw.shift;
-            if (x0 >= dw.col0 && dw.vec) {
-                *reinterpret_cast<uint4 *>(drow) = o;
-            } else {
-                // the group that straddles col0, or a destination whose 16-byte stores would be misaligned
-                const unsigned d[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (x0 + j >= dw.col0) drow[j] = (uint16_t)(d[j >> 1] >> (16 * (j & 1)));
-            }
-        }
-    }
-}
-
-// ---- RRC on load: the RAW strip goes through the workgroup's LDS once -------------------------------------
-// The source is CCD 2's RAW strip.  The block's 256 lanes fetch one aligned 16-byte chunk each of every new source line
-// (2048 consecutive columns from cbase = 2032 * blockIdx.x + ixmin8, ixmin8 = 8 * floor((floor(dx) - 2) / 8): the taps of
-// the block's 254 output groups lie inside whatever the rounding of x + dx does; the host checks it), correct its 8 samples
-// with the (k, b) pairs of the lane's own columns held in registers (IMO::InplaceRRC's pixel, exact) and write them to LDS;
-// after one barrier the 254 output lanes read their 11 samples from there.  Every sample is corrected ONCE (the register
-// form would correct 11 per 8 output pixels and needs the pairs of 11 columns per lane: 6.0 ms with the pairs in LDS,
-// profiles/experiments/remap_rrc_on_load.diff.txt), so Stitcher::DoRRC of CCD 2 rides PreStitch's pass and <pan2>.RRC.RAW
-// is never written.  Lines are double-buffered in LDS (a write to buffer p follows the barrier of buffer p ^ 1, which
-// every reader of the previous use of p has passed); chunks are requested two output lines ahead.  Everything that decides
-// a barrier is uniform over the block (the row table and blockIdx); arithmetic per pixel is remap_shift8_kernel's.
-// The same staging WITHOUT the correction is slower than remap_shift8_kernel's register window (3.47 against 3.19 ms on
-// two 30000 x 100000 segments, at 3 or 4 workgroups per CU): the plain call keeps the register form.
-constexpr int kLdsOut = kBlock - 2;
-
-// ---- fp16-accumulate variant (BASELINE config 5: "fp16 accumulate, tolerance stated") ----------------------
-// Same geometry, phases, tap positions and border rules as remap_shift8_kernel; only the 16-tap sum of
-// the regular interior pixels changes: samples and the sixteen 2-D weights are rounded to fp16 and the sum
-// is a chain of packed fp16 FMAs (v_pk_fma_f16: two output pixels per instruction, 16 instructions per
-// pixel pair instead of 62 unfused f32 operations).  NOT the parity mode: fp16 carries 11 significant bits.
-// Samples enter as (sample - 2048) -- exact integers for 12-bit data -- and the running sum of 16 products
-// rounds to 0.5..2 DN steps depending on its magnitude.  Measured against the f32 kernel on the 12-bit
-// synthetic strips: tests/test_gpu_config5.py::test_remap_f16acc_tolerance prints max and mean |delta|
-// (DESIGN.md section 4.2 records them: max 5, mean 0.25 DN); the bound asserted for arbitrary data is
-// |delta| <= 6 + max|sample - 2048| / 64.  The mode is specified for data up to 15 bits (the biased
-// sample must fit int16).  Irregular column groups and section-border lines still go through the f32
-// fix-up kernels.
-typedef _Float16 oip_h2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ oip_h2 h2_from_u16pair(uint32_t w)
-{
-    oip_h2 r;
-    r.x = (_Float16)(unsigned short)(w & 0xffffu);
-    r.y = (_Float16)(unsigned short)(w >> 16);
-    return r;
-}
-// (a.y, b.x): the pair one sample further along the line
-__device__ __forceinline__ oip_h2 h2_shift(oip_h2 a, oip_h2 b)
-{
-    const uint32_t ua = __builtin_bit_cast(uint32_t, a), ub = __builtin_bit_cast(uint32_t, b);
-    return __builtin_bit_cast(oip_h2, __builtin_amdgcn_alignbit(ub, ua, 16));
-}
-
-// one source line as packed fp16 pairs of (sample - kF16Bias): E[i] = (g[2i], g[2i+1]), O[i] = (g[2i+1], g[2i+2]),
-// g[q] = sample c0 + q.  The bias is taken off in 16-bit integer arithmetic (exact), so 12-bit data enters fp16
-// as integers in [-2048, 2047] -- all exactly representable -- and the partial sums stay small; the bicubic
-// weights sum to one, so the bias is added back to the finished sum.
-constexpr int kF16Bias = 2048;
-__device__ __forceinline__ oip_h2 h2_from_biased_pair(uint32_t w)
-{
-    oip_h2 r;
-    r.x = (_Float16)(short)((w & 0xffffu) - kF16Bias);
-    r.y = (_Float16)(short)((w >> 16) - kF16Bias);
-    return r;
-}
-__device__ __forceinline__ void expand_h(const uint32_t w[6], int c0, oip_h2 E[6], oip_h2 O[5])
-{
-    // odd first column: one funnel shift per dword brings the line to the even layout (as oip_expand_pairs does) -- selecting
-    // between the two layouts after the conversion cost ten v_cndmask per line
-    const unsigned sh = (c0 & 1) ? 16u : 0u;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) E[i] = h2_from_biased_pair(__builtin_amdgcn_alignbit(w[i + 1], w[i], sh));
-    E[5] = h2_from_biased_pair(w[5] >> sh);       // only its first half (sample 10) is used, through O[4]
-#pragma unroll
-    for (int i = 0; i < 5; ++i) O[i] = h2_shift(E[i], E[i + 1]);
-}
-// The 8 fp16 sums (acc[p] = pixels 2p, 2p+1) biased back, saturated and packed.  (float)acc + 2048 is exact in f32 for every
-// fp16 value that can round to a different integer than its neighbour (|acc| >= 0.5 has an ulp >= 2^-11; below that the sum
-// stays strictly inside (2047.5, 2048.5)), so adding 2048 + 1.5 * 2^23 in one step rounds exactly as rintf((float)acc + 2048)
-// does and leaves the integer in the low bits (oip_sat_pack8's trick); the integer clamp maps +inf to 65535 and -inf to 0 as
-// the fminf / fmaxf pair it replaces did.  A NaN sum -- not reachable: 16 products of int16 samples with weights whose
-// magnitudes add up to 1.6 stay far below fp16's 65504 -- would saturate by its sign bit.
-__device__ __forceinline__ uint4 h2_sat_pack8(const oip_h2 acc[4])
-{
-    unsigned c[8];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int lo = (int)__float_as_uint((float)acc[p].x + (12582912.0f + (float)kF16Bias));
-        const int hi = (int)__float_as_uint((float)acc[p].y + (12582912.0f + (float)kF16Bias));
-        c[2 * p] = (unsigned)(lo < 0x4B400000 ? 0x4B400000 : (lo > 0x4B40FFFF ? 0x4B40FFFF : lo));
-        c[2 * p + 1] = (unsigned)(hi < 0x4B400000 ? 0x4B400000 : (hi > 0x4B40FFFF ? 0x4B40FFFF : hi));
-    }
-    uint4 o;
-    o.x = __builtin_amdgcn_perm(c[1], c[0], 0x05040100u);
-    o.y = __builtin_amdgcn_perm(c[3], c[2], 0x05040100u);
-    o.z = __builtin_amdgcn_perm(c[5], c[4], 0x05040100u);
-    o.w = __builtin_amdgcn_perm(c[7], c[6], 0x05040100u);
-    return o;
-}
-__device__ __forceinline__ void load_src_line11_h(const uint32_t *__restrict__ lane_base, int row, int half_pitch, int c0,
-                                                  oip_h2 E[6], oip_h2 O[5])
-{
-    uint32_t w[6];
-    load_raw6(lane_base, row, half_pitch, w);
-    expand_h(w, c0, E, O);
-}
-
-__global__ __launch_bounds__(kBlock, 4) void remap_shift8_f16_kernel(const uint16_t *__restrict__ src, uint16_t *__restrict__ dst, DstWin dw,
-                                                                     const RowInfo *__restrict__ rows, int W, long out_rows,
-                                                                     long src_elems, double dx, const float *__restrict__ tab1d,
-                                                                     int rows_per_block)
 {
     const int x0 = (blockIdx.x * kBlock + threadIdx.x) * 8;
     if (x0 >= W || x0 + 8 <= dw.col0) return;
@@ -410,11 +225,10 @@ __global__ __launch_bounds__(kBlock, 4) void remap_shift8_f16_kernel(const uint1
 
     const uint32_t *lane_base = reinterpret_cast<const uint32_t *>(src) + (c0 >> 1);
     const int half_pitch = W >> 1;
-    oip_h2 E[4][6], O[4][5];                      // tap line t at unrolled step k lives in slot (k+t)&3
-    oip_h2 w2d[16];
+    OipTaps8<F16> taps;                           // tap line t at unrolled step k lives in slot (k+t)&3
     int cur1 = -2, cur2 = -2, cur3 = -2;
     int cur_fy = -1;
-    uint32_t nraw[6] = {0u, 0u, 0u, 0u, 0u, 0u};  // one-line lookahead, as in remap_shift8_kernel
+    uint32_t nraw[6] = {0u, 0u, 0u, 0u, 0u, 0u};  // raw dwords of source line `nline`, requested one output line ahead
     int nline = -2;
     for (long rb = r0; rb < r1; rb += 4) {
 #pragma unroll
@@ -425,60 +239,46 @@ __global__ __launch_bounds__(kBlock, 4) void remap_shift8_f16_kernel(const uint1
             if (ri.flags != 1) { cur1 = cur2 = cur3 = -2; continue; }      // fix-up launch B (f32)
             const bool slide = cur1 != -2 && ri.src[0] == cur1 && ri.src[1] == cur2 && ri.src[2] == cur3;
             if (slide) {
-                if (ri.src[3] == nline) expand_h(nraw, c0, E[(k + 3) & 3], O[(k + 3) & 3]);
-                else load_src_line11_h(lane_base, ri.src[3], half_pitch, c0, E[(k + 3) & 3], O[(k + 3) & 3]);
+                if (ri.src[3] == nline) taps.expand(nraw, c0, (k + 3) & 3);
+                else { uint32_t w[6]; oip_load_raw6(lane_base, ri.src[3], half_pitch, w); taps.expand(w, c0, (k + 3) & 3); }
             } else {
 #pragma unroll
-                for (int t = 0; t < 4; ++t) load_src_line11_h(lane_base, ri.src[t], half_pitch, c0, E[(k + t) & 3], O[(k + t) & 3]);
+                for (int t = 0; t < 4; ++t) { uint32_t w[6]; oip_load_raw6(lane_base, ri.src[t], half_pitch, w); taps.expand(w, c0, (k + t) & 3); }
             }
             cur1 = ri.src[1]; cur2 = ri.src[2]; cur3 = ri.src[3];
+            // the line the next output line will add in the regular case (its taps one line further down)
             nline = -2;
             if (r + 1 < r1 && (long)(ri.src[3] + 1) * W < src_elems) {
                 nline = ri.src[3] + 1;
-                load_raw6(lane_base, nline, half_pitch, nraw);
+                oip_load_raw6(lane_base, nline, half_pitch, nraw);
             }
             if (ri.fy != cur_fy) {
                 cur_fy = ri.fy;
-#pragma unroll
-                for (int ky = 0; ky < 4; ++ky) {
-                    const float wy = tab1d[cur_fy * 4 + ky];
-#pragma unroll
-                    for (int kx = 0; kx < 4; ++kx) {
-                        const _Float16 h = (_Float16)__fmul_rn(wy, wx[kx]);
-                        oip_h2 hh = {h, h};
-                        w2d[ky * 4 + kx] = hh;
-                    }
-                }
+                taps.weights(tab1d, cur_fy, wx);
             }
-            oip_h2 acc[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {             // output pixels 2p, 2p+1
-                acc[p] = oip_h2{(_Float16)0.f, (_Float16)0.f};
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const oip_h2 *Et = E[(k + t) & 3], *Ot = O[(k + t) & 3];
-                    acc[p] = __builtin_elementwise_fma(Et[p], w2d[t * 4 + 0], acc[p]);
-                    acc[p] = __builtin_elementwise_fma(Ot[p], w2d[t * 4 + 1], acc[p]);
-                    acc[p] = __builtin_elementwise_fma(Et[p + 1], w2d[t * 4 + 2], acc[p]);
-                    acc[p] = __builtin_elementwise_fma(Ot[p + 1], w2d[t * 4 + 3], acc[p]);
-                }
-            }
-            const uint4 o = h2_sat_pack8(acc);
-            uint16_t *drow = dst + r * dw.pitch + x0 + dw.shift;
-            if (x0 >= dw.col0 && dw.vec) {
-                *reinterpret_cast<uint4 *>(drow) = o;
-            } else {
-                // the group that straddles col0, or a destination whose 16-byte stores would be misaligned
-                const unsigned d[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (x0 + j >= dw.col0) drow[j] = (uint16_t)(d[j >> 1] >> (16 * (j & 1)));
-            }
+            oip_store8(dst + r * dw.pitch + x0 + dw.shift, taps.sums(k), x0, dw.col0, dw.vec);
         }
     }
 }
 
-// RRC on load, both accumulate modes (the block comment "RRC on load" above the fp16 helpers describes the kernel)
+// ---- RRC on load: the RAW strip goes through the workgroup's LDS once -------------------------------------
+// The source is CCD 2's RAW strip.  The block's 256 lanes fetch one aligned 16-byte chunk each of every new source line
+// (2048 consecutive columns from cbase = 2032 * blockIdx.x + ixmin8, ixmin8 = 8 * floor((floor(dx) - 2) / 8): the taps of
+// the block's 254 output groups lie inside whatever the rounding of x + dx does; the host checks it), correct its 8 samples
+// with the (k, b) pairs of the lane's own columns held in registers (IMO::InplaceRRC's pixel, exact) and write them to LDS;
+// after one barrier the 254 output lanes read their 11 samples from there.  Every sample is corrected ONCE (the register
+// form would correct 11 per 8 output pixels and needs the pairs of 11 columns per lane: 6.0 ms with the pairs in LDS,
+// profiles/experiments/remap_rrc_on_load.diff.txt), so Stitcher::DoRRC of CCD 2 rides PreStitch's pass and <pan2>.RRC.RAW
+// is never written.  Lines are double-buffered in LDS (a write to buffer p follows the barrier of buffer p ^ 1, which
+// every reader of the previous use of p has passed); chunks are requested two output lines ahead.  Everything that decides
+// a barrier is uniform over the block (the row table and blockIdx); arithmetic per pixel is remap_shift8_kernel's, in either
+// accumulate mode (OipTaps8<F16>).
+// The same staging WITHOUT the correction is slower than remap_shift8_kernel's register window (3.47 against 3.19 ms on
+// two 30000 x 100000 segments, at 3 or 4 workgroups per CU; measured again with the present loop: 2.70 ms f32 / 2.65 fp16
+// against the register-window kernels' 2.55 / 2.70 -- every form of this pass now sits at 4.5-4.8 TB/s, 85 % of what the plain
+// copy kernels reach): the plain calls keep the register form.
+constexpr int kLdsOut = kBlock - 2;
+
 // IMO::InplaceRRC's pixel with or without the range test of the conversion (SAFE: the caller has proved |k s + b| < 2^31)
 template <bool SAFE> __device__ __forceinline__ unsigned rrc_px_t(double k, double b, unsigned s)
 {
@@ -489,10 +289,6 @@ template <bool SAFE> __device__ __forceinline__ unsigned rrc_px_t(double k, doub
     }
 }
 
-// F16: the fp16-accumulate sums of remap_shift8_f16_kernel on the corrected samples.  (The same staging WITHOUT the correction,
-// for plain calls, was measured again with this loop: 2.70 ms f32 / 2.65 fp16 against the register-window kernels' 2.55 / 2.70 on
-// two 30000 x 100000 segments -- every form of this pass now sits at 4.5-4.8 TB/s, 85 % of what the plain copy kernels reach,
-// and the plain calls keep the register form.)
 template <bool F16>
 __global__ __launch_bounds__(kBlock, 3) void remap_shift8_rrc_kernel(const uint16_t *__restrict__ src, uint16_t *__restrict__ dst, DstWin dw,
                                                                      const RowInfo *__restrict__ rows, int W, long out_rows,
@@ -530,9 +326,7 @@ __global__ __launch_bounds__(kBlock, 3) void remap_shift8_rrc_kernel(const uint1
 
     auto body = [&](auto safe_tag) __attribute__((always_inline)) {
     constexpr bool SAFE = decltype(safe_tag)::value;
-    oip_f2 win[F16 ? 1 : 4][7];                   // tap line t at step k of a quad lives in slot (k+t)&3, as sample pairs
-    oip_h2 E[F16 ? 4 : 1][6], O[F16 ? 4 : 1][5];
-    typename std::conditional<F16, oip_h2, float>::type w2d[16];
+    OipTaps8<F16> taps;                           // tap line t at step k of a quad lives in slot (k+t)&3
     auto fetch = [&](long row) __attribute__((always_inline)) {
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
         if (chunk_ok && row >= 0 && row < src_lines) v = *reinterpret_cast<const uint4 *>(src + row * W + cc);
@@ -551,8 +345,7 @@ __global__ __launch_bounds__(kBlock, 3) void remap_shift8_rrc_kernel(const uint1
             uint32_t w[6];
 #pragma unroll
             for (int i = 0; i < 6; ++i) w[i] = lds[buf][d0 + i];
-            if constexpr (F16) expand_h(w, c0, E[slot], O[slot]);
-            else oip_expand_pairs(w, c0 & 1, win[slot]);
+            taps.expand(w, c0, slot);
         }
     };
     // Everything that steers the loop is wave-uniform and lives in scalar registers: the row table comes in through scalar loads
@@ -590,51 +383,9 @@ __global__ __launch_bounds__(kBlock, 3) void remap_shift8_rrc_kernel(const uint1
         if (active) {
             if (ri.fy != cur_fy) {
                 cur_fy = ri.fy;
-#pragma unroll
-                for (int ky = 0; ky < 4; ++ky) {
-                    const float wy = tab1d[cur_fy * 4 + ky];
-#pragma unroll
-                    for (int kx = 0; kx < 4; ++kx) {
-                        if constexpr (F16) {
-                            const _Float16 h = (_Float16)__fmul_rn(wy, wx[kx]);
-                            w2d[ky * 4 + kx] = oip_h2{h, h};
-                        } else {
-                            w2d[ky * 4 + kx] = __fmul_rn(wy, wx[kx]);
-                        }
-                    }
-                }
+                taps.weights(tab1d, cur_fy, wx);
             }
-            uint4 o;
-            if constexpr (F16) {
-                oip_h2 acc[4];
-#pragma unroll
-                for (int pp = 0; pp < 4; ++pp) {          // output pixels 2pp, 2pp+1 (remap_shift8_f16_kernel's sums)
-                    acc[pp] = oip_h2{(_Float16)0.f, (_Float16)0.f};
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const oip_h2 *Et = E[(k + t) & 3], *Ot = O[(k + t) & 3];
-                        acc[pp] = __builtin_elementwise_fma(Et[pp], w2d[t * 4 + 0], acc[pp]);
-                        acc[pp] = __builtin_elementwise_fma(Ot[pp], w2d[t * 4 + 1], acc[pp]);
-                        acc[pp] = __builtin_elementwise_fma(Et[pp + 1], w2d[t * 4 + 2], acc[pp]);
-                        acc[pp] = __builtin_elementwise_fma(Ot[pp + 1], w2d[t * 4 + 3], acc[pp]);
-                    }
-                }
-                o = h2_sat_pack8(acc);
-            } else {
-                oip_f2 sum[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) oip_row_taps8(win[(k + t) & 3], w2d + t * 4, t == 0, sum);
-                o = oip_sat_pack8(sum);
-            }
-            uint16_t *drow = dst + rr_ * dw.pitch + x0 + dw.shift;
-            if (x0 >= dw.col0 && dw.vec) {
-                *reinterpret_cast<uint4 *>(drow) = o;
-            } else {
-                const unsigned d[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (x0 + j >= dw.col0) drow[j] = (uint16_t)(d[j >> 1] >> (16 * (j & 1)));
-            }
+            oip_store8(dst + rr_ * dw.pitch + x0 + dw.shift, taps.sums(k), x0, dw.col0, dw.vec);
         }
     };
     auto follows = [](const RowInfo &n, const RowInfo &p) __attribute__((always_inline)) {     // n's window = p's, one line down
@@ -844,21 +595,17 @@ static int remap_shift_impl(oip_ctx *ctx, const uint16_t *d_src, long src_row0, 
         rpb = (rpb + 3) / 4 * 4;
         long gy = (out_rows + rpb - 1) / rpb;
         if (gy > 65535) { gy = 65535; rpb = ((out_rows + gy - 1) / gy + 3) / 4 * 4; gy = (out_rows + rpb - 1) / rpb; }
-        {
-            OipProfScope prof(ctx, lds ? (f16acc ? "remap_shift8_rrc_f16_kernel" : "remap_shift8_rrc_kernel") : (f16acc ? "remap_shift8_f16_kernel" : "remap_shift8_kernel"));
-            if (lds && f16acc)
-                hipLaunchKernelGGL(remap_shift8_rrc_kernel<true>, dim3(gx, (unsigned)gy), dim3(kBlock), 0, ctx->stream, d_src, d_dst, dw, rows, W,
+        auto launch8 = [&](auto f16_tag) {                               // the profiler scopes keep the kernels' historical names
+            constexpr bool F16 = decltype(f16_tag)::value;
+            OipProfScope prof(ctx, lds ? (F16 ? "remap_shift8_rrc_f16_kernel" : "remap_shift8_rrc_kernel") : (F16 ? "remap_shift8_f16_kernel" : "remap_shift8_kernel"));
+            if (lds)
+                hipLaunchKernelGGL(remap_shift8_rrc_kernel<F16>, dim3(gx, (unsigned)gy), dim3(kBlock), 0, ctx->stream, d_src, d_dst, dw, rows, W,
                                    out_rows, src_rows * (long)W, dx, ctx->d_tab1d, (int)rpb, kb, ixmin8);
-            else if (lds)
-                hipLaunchKernelGGL(remap_shift8_rrc_kernel<false>, dim3(gx, (unsigned)gy), dim3(kBlock), 0, ctx->stream, d_src, d_dst, dw, rows, W,
-                                   out_rows, src_rows * (long)W, dx, ctx->d_tab1d, (int)rpb, kb, ixmin8);
-            else if (f16acc)
-                hipLaunchKernelGGL(remap_shift8_f16_kernel, dim3(gx, (unsigned)gy), dim3(kBlock), 0, ctx->stream, d_src, d_dst, dw, rows, W, out_rows,
-                                   src_rows * (long)W, dx, ctx->d_tab1d, (int)rpb);
             else
-                hipLaunchKernelGGL(remap_shift8_kernel, dim3(gx, (unsigned)gy), dim3(kBlock), 0, ctx->stream, d_src, d_dst, dw, rows, W, out_rows,
+                hipLaunchKernelGGL(remap_shift8_kernel<F16>, dim3(gx, (unsigned)gy), dim3(kBlock), 0, ctx->stream, d_src, d_dst, dw, rows, W, out_rows,
                                    src_rows * (long)W, dx, ctx->d_tab1d, (int)rpb);
-        }
+        };
+        if (f16acc) launch8(std::true_type{}); else launch8(std::false_type{});
         if (!bad_groups.empty()) {
             OipProfScope prof(ctx, "remap_fix_cols_kernel");
             long rpb2 = 2048;

@@ -48,8 +48,10 @@ def test_config1_rrc_4096x8192_matches_the_reference_loop(ctx, oracle_mod):
 
 @pytest.mark.parametrize("W,L,dx,dy", [(4096, 3000, 3.37, -1.62), (30000, 1500, -2.21, 2.4), (1000, 2100, 0.5, 0.5)])
 def test_remap_f16acc_tolerance(ctx, W, L, dx, dy):
-    """fp16-accumulate variant vs the fp32 (parity) kernel on 12-bit pushbroom data: |delta| <= 4 DN; the measured
-    maximum is printed and recorded in DESIGN.md.  Border lines / irregular columns are computed in fp32 by both."""
+    """fp16-accumulate instance (remap_shift8_kernel<true>: OipTaps8<true> in csrc/oip_bicubic.h, where the tolerance is
+    stated) vs the fp32 (parity) instance on 12-bit pushbroom data: |delta| <= F16_ABS_DN = 6 DN; the measured maximum
+    (5 DN) is printed and recorded in DESIGN.md section 4.2.  Border lines / irregular columns are computed in fp32 by both.
+    tests/test_gpu_bicubic_golden.py pins the bits of both."""
     import torch
     from opticalimageprocessor_amd import synth
     kb = np.stack([np.ones(W), np.zeros(W)], 1)
