@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "oip_c.h"
+#include "oip_corrgeom.h"
 #include "oip_tiff.hpp"
 
 namespace OIPGPU {
@@ -217,6 +218,7 @@ template <typename T> struct DevBuf {              // RAII device buffer
         if (count * sizeof(T) >= ((size_t)8 << 20)) Device::get().check(oip_upload_staged(Device::get().ctx(), p, h, count * sizeof(T), nullptr));
         else Device::get().check(oip_memcpy_h2d(Device::get().ctx(), p, h, count * sizeof(T)));
     }
+    void assign(const std::vector<T> &h) { alloc(h.size()); upload(h.data(), h.size()); }       // a host table, e.g. IMO::LoadLut's
     void download(T *h, size_t count) const
     {
         if (count * sizeof(T) >= ((size_t)8 << 20)) { Device::get().check(oip_download_staged(Device::get().ctx(), h, p, count * sizeof(T))); return; }
@@ -666,16 +668,28 @@ public:
         Device::get().check(oip_rrc_u16_host(Device::get().ctx(), buff, w, h, reinterpret_cast<const double *>(rrcParam)));
     }
 
-    static RRCParam *LoadRRCParamFile(const char *paramFilePath, int expectedLines)      // imageop.h:140-192
+    // LoadRRCParamFile (imageop.h:140-192): the n (k, b) pairs of a parameter file, as the 2n doubles the kernels take
+    static std::vector<double> LoadLut(const std::string &paramFilePath, int n)
     {
-        OLOG("Loading RRC paramter from file `%s' ...", paramFilePath);
-        std::unique_ptr<RRCParam[]> p(new RRCParam[expectedLines]);
+        OLOG("Loading RRC paramter from file `%s' ...", paramFilePath.c_str());
+        std::vector<double> kb((size_t)n * 2);
         char err[1024];
-        int rc = oip_load_rrc_param_file(paramFilePath, expectedLines, reinterpret_cast<double *>(p.get()), err, sizeof err);
+        int rc = oip_load_rrc_param_file(paramFilePath.c_str(), n, kb.data(), err, sizeof err);
         if (rc == OIP_E_IO) throw errno_error(err);
         if (rc != OIP_OK) throw std::runtime_error(err);
         OLOG("LoadRRCParamFile(): loaded.");
-        return p.release();
+        return kb;
+    }
+    // the four band files of an MSS strip W samples wide, one after the other (preproc.h:202-222)
+    static std::vector<double> LoadMssLuts(const std::string files[MSS_BANDS], int W)
+    {
+        const int bw = W / MSS_BANDS;
+        std::vector<double> all((size_t)W * 2);
+        for (int b = 0; b < MSS_BANDS; ++b) {
+            const std::vector<double> kb = LoadLut(files[b], bw);
+            std::copy(kb.begin(), kb.end(), all.begin() + (size_t)b * bw * 2);
+        }
+        return all;
     }
 
     // imageop.h:194-228.  The raster goes file -> HBM -> file through the staging ring (no whole-file heap buffer);
@@ -688,9 +702,9 @@ public:
         DevBuf<uint16_t> image(npx ? npx : 1);
         image.load_file(raw, npx);
         long lines = (long)(size / ((size_t)pixelPerLine * BYTES_PER_PIXEL));
-        std::unique_ptr<RRCParam[]> rrcParam(LoadRRCParamFile(rrc.c_str(), pixelPerLine));
-        DevBuf<double> kb((size_t)pixelPerLine * 2);
-        kb.upload((double *)rrcParam.get(), (size_t)pixelPerLine * 2);
+        const std::vector<double> rrcParam = LoadLut(rrc, pixelPerLine);
+        DevBuf<double> kb;
+        kb.assign(rrcParam);
         OLOG("Do inplace RRC ...");
         stop_watch sw;
         Device::get().check(oip_rrc_u16(Device::get().ctx(), image.p, image.p, pixelPerLine, lines, kb.p));
@@ -855,15 +869,14 @@ public:
         std::vector<double> r(3 * (size_t)mSections);
         Device::get().check(oip_stt_correlate(Device::get().ctx(), mD1.p, mD2.p, mW, mLinesPAN, 0, mLinesPAN, mSections,
                                               mLinePerSection, mOverlapCols, edgeCols, r.data()));
-        const int gapLines = (mLinesPAN - mSections * mLinePerSection) / (mSections + 1);
-        const int stepLines = gapLines + mLinePerSection;
+        const CcdGeom g(mW, mLinesPAN, mSections, mLinePerSection, mOverlapCols, edgeCols);    // (the call above has checked it)
         OLOG("Calculating stitching delta values ...");
         RLOG("| offset |  delta x |  delta y | response | r |");
         RLOG("-----------------------------------------------");
         for (int i = 0; i < mSections; ++i) {
             double dx = r[3 * i], dy = r[3 * i + 1], resp = r[3 * i + 2];
             bool isValid = resp >= threshold && (maxDeltaY <= 0.0 || std::abs(dy) <= maxDeltaY);
-            RLOG("|%7d |%10.4f|%10.4f|%10.4f|%s|", gapLines + i * stepLines, dx, dy, resp, isValid ? " Y " : " N ");
+            RLOG("|%7ld |%10.4f|%10.4f|%10.4f|%s|", g.section_start(i), dx, dy, resp, isValid ? " Y " : " N ");
         }
         int valid = 0;                                                  // stitcher.h:181-198
         if (oip_stt_mean(r.data(), mSections, threshold, maxDeltaY, &mDeltaX, &mDeltaY, &mResponse, &valid) != OIP_OK)
@@ -885,8 +898,8 @@ public:
         DevBuf<double> kb((size_t)mW * 2);
         oip_ctx *ctx = Device::get().ctx();
         for (int c = 0; c < 2; ++c) {                                   // IMO::DoRRC4RAW on the resident strip
-            std::unique_ptr<RRCParam[]> prm(IMO::LoadRRCParamFile((c ? mParamFileRRC2 : mParamFileRRC1).c_str(), mW));
-            kb.upload((double *)prm.get(), (size_t)mW * 2);
+            const std::vector<double> prm = IMO::LoadLut(c ? mParamFileRRC2 : mParamFileRRC1, mW);
+            kb.upload(prm.data(), prm.size());
             DevBuf<uint16_t> &d = c ? mD2 : mD1;
             OLOG("Do inplace RRC ...");
             stop_watch sw;
@@ -960,10 +973,27 @@ private:
 };
 
 // ---- PreProcessor (preproc.h:30-599) ---------------------------------------------------------------
-struct InterBandShift { double dx, dy, rs; int cx; };                   // preproc.h:23-28
+// the fitted polynomials as preproc.h:339-344 logs them
+inline void LogShiftCoeffs(const double cx[MSS_BANDS][2], const double cy[MSS_BANDS][3])
+{
+    for (int b = 0; b < MSS_BANDS; ++b) {
+        OLOG("BAND %d\tdeltaX coeff: [1] %.15f, [0] %.9f", b, cx[b][1], cx[b][0]);
+        OLOG("\tdeltaY coeff: [2] %.15f, [1] %.15f, [0] %.9f", cy[b][2], cy[b][1], cy[b][0]);
+    }
+}
 
 class PreProcessor {
 public:
+    // CheckFilesAttributes' size rules (preproc.h:565-571)
+    static void CheckStripSizes(size_t sizePAN, size_t sizeMSS, size_t lineBytes)
+    {
+        if (sizePAN != MSS_BANDS * sizeMSS)
+            throw std::runtime_error("PAN file size does not match MSS file size: PAN file should be " + std::to_string(MSS_BANDS) +
+                                     "x as large as MSS file");
+        if (sizePAN % lineBytes != 0)
+            throw std::runtime_error("PAN file size invalid: should be multiplies of " + std::to_string(lineBytes));
+    }
+
     PreProcessor(const std::string &panFile, const std::string &mssFile, const std::string &rrcFile4PAN,
                  const std::string rrcFile4MSSBand[MSS_BANDS], int pixelsPerLine = OIP_PIXELS_PER_LINE)
         : mPanFile(panFile), mMssFile(mssFile), mRrcPanFile(rrcFile4PAN), mW(pixelsPerLine)
@@ -1000,9 +1030,9 @@ public:
     void DoRRC4PAN()                                                    // preproc.h:188-200
     {
         if (!mPAN.p) throw std::logic_error("PAN raw image data not loaded, call `LoadPAN()' first");
-        std::unique_ptr<RRCParam[]> prm(IMO::LoadRRCParamFile(mRrcPanFile.c_str(), mW));
-        DevBuf<double> kb((size_t)mW * 2);
-        kb.upload((double *)prm.get(), (size_t)mW * 2);
+        const std::vector<double> prm = IMO::LoadLut(mRrcPanFile, mW);
+        DevBuf<double> kb;
+        kb.assign(prm);
         OLOG("Begin inplace RRC for PAN data ... ");
         stop_watch sw;
         Device::get().check(oip_rrc_u16(Device::get().ctx(), mPAN.p, mPAN.p, mW, (long)mLinesPAN, kb.p));
@@ -1015,17 +1045,8 @@ public:
     void DoRRC4MSS(bool doRRC = true)
     {
         if (!mMssBil.p) throw std::logic_error("MSS raw image data not loaded, call `LoadMSS()' first");
-        const int bw = mW / MSS_BANDS;
         DevBuf<double> kb;
-        if (doRRC) {
-            std::vector<double> all((size_t)mW * 2);
-            for (int i = 0; i < MSS_BANDS; ++i) {
-                std::unique_ptr<RRCParam[]> prm(IMO::LoadRRCParamFile(mRrcMssBndFile[i].c_str(), bw));
-                memcpy(&all[(size_t)i * bw * 2], prm.get(), sizeof(double) * 2 * bw);
-            }
-            kb.alloc((size_t)mW * 2);
-            kb.upload(all.data(), (size_t)mW * 2);
-        }
+        if (doRRC) kb.assign(IMO::LoadMssLuts(mRrcMssBndFile, mW));
         OLOG("Splitting %d bands of MSS image%s ...", MSS_BANDS, doRRC ? " with inplace RRC" : "");
         stop_watch sw;
         Device::get().check(oip_mss_split_rrc_u16(Device::get().ctx(), mMssBil.p, mPlanes.p, mPlaneStride, mW, (long)mLinesMSS,
@@ -1051,23 +1072,7 @@ public:
                                                     mPlaneStride, 0, (long)mLinesMSS, mW, slices, sections,
                                                     OIP_CORRELATION_LINES, t.data()));
         OLOG("Inter-band correlation finished in %.3f seconds, result:", sw.tick());
-        for (int b = 0; b < MSS_BANDS; ++b) {
-            mBandShift[b].resize(n);
-            for (int i = 0; i < n; ++i) {
-                const double *s = &t[((size_t)b * n + i) * 4];
-                mBandShift[b][i] = InterBandShift{s[0], s[1], s[2], (int)s[3]};
-            }
-        }
-        DumpInterBandShiftValues(slices, sections);
-        OLOG("Filter invalid correlation values & try polynomial fitting ...");
-        char err[512];
-        int rc = oip_filter_and_fit_mode(t.data(), n, threshold, OIP_IBCV_MIN_COUNT, mFitMode, &mDeltaXcoeffs[0][0], &mDeltaYcoeffs[0][0], err, sizeof err);
-        if (rc != OIP_OK) { OLOG("%s.", err); throw std::runtime_error(err); }
-        for (int b = 0; b < MSS_BANDS; ++b) {
-            OLOG("BAND %d\tdeltaX coeff: [1] %.15f, [0] %.9f", b, mDeltaXcoeffs[b][1], mDeltaXcoeffs[b][0]);
-            OLOG("\tdeltaY coeff: [2] %.15f, [1] %.15f, [0] %.9f", mDeltaYcoeffs[b][2], mDeltaYcoeffs[b][1], mDeltaYcoeffs[b][0]);
-        }
-        OLOG("CalcInterBandCorrelation(): done.");
+        FitShiftTable(t, slices, sections, threshold);
         if (autoUnloadPAN) mPAN.release();
     }
 
@@ -1089,23 +1094,18 @@ public:
                                                         rows, Wb, (long)mLinesMSS, &mDeltaXcoeffs[0][0], &mDeltaYcoeffs[0][0],
                                                         linePerSection, lineOffset, sectionOverlap, keepLeadingLines ? 1 : 0,
                                                         OIP_IBPA_MIN_PROCESSLINES, &processed));
+        Device::get().check(oip_sync(Device::get().ctx()));
+        OLOG("Alignment done in %.3f seconds (%ld lines valid of %ld).", sw.tick(), processed, rows);
         if (keepOnDevice) {
-            Device::get().check(oip_sync(Device::get().ctx()));
-            OLOG("Alignment done in %.3f seconds (%ld lines valid of %ld).", sw.tick(), processed, rows);
             keepOnDevice->swap(out);
             if (keptRows) *keptRows = rows;
-            if (autoUnloadRawMSS) mPlanes.release();
-            OLOG("DoInterBandAlignment(): done.");
-            return;
+        } else {
+            // preproc.h:167-185 WriteAlignedMSS_TIFF: 4-channel 16-bit TIFF, samples in OpenCV's on-disk order
+            auto save = IMO::BuildOutputFilePath(mMssFile, ".ALIGNED", ".TIFF");
+            OLOG("Outputing aligned TIFF image (%d x %ld x 4) to [%s] ...", Wb, rows, save.c_str());
+            write_tiff_from_device(save, out.p, Wb, rows, MSS_BANDS, tiff_compression(TIFF_LZW), true);
+            OLOG("Output done.");
         }
-        Device::get().check(oip_sync(Device::get().ctx()));
-        double es = sw.tick();
-        OLOG("Alignment done in %.3f seconds (%ld lines valid of %ld).", es, processed, rows);
-        // preproc.h:167-185 WriteAlignedMSS_TIFF: 4-channel 16-bit TIFF, samples in OpenCV's on-disk order
-        auto save = IMO::BuildOutputFilePath(mMssFile, ".ALIGNED", ".TIFF");
-        OLOG("Outputing aligned TIFF image (%d x %ld x 4) to [%s] ...", Wb, rows, save.c_str());
-        write_tiff_from_device(save, out.p, Wb, rows, MSS_BANDS, tiff_compression(TIFF_LZW), true);
-        OLOG("Output done.");
         if (autoUnloadRawMSS) mPlanes.release();
         OLOG("DoInterBandAlignment(): done.");
     }
@@ -1139,174 +1139,225 @@ public:
         int linesSection = OIP_IBPA_DEFAULT_BATCHLINES, lineOffset = 0, overlapLines = OIP_IBPA_DEFAULT_LINEOVERLAP;
     };
 
+    // The locals stand in the order their lifetimes need: what a thread's jobs use is declared before the object that owns the
+    // thread, and the reader -- declared last -- is stopped first, whatever is thrown.
     void RunPipelined(const DefaultActionOptions &o)
     {
         oip_ctx *ctx = Device::get().ctx();
         auto ck = [](int rc) { Device::get().check(rc); };
-        const auto t0 = std::chrono::steady_clock::now();
+        PipelineTimes t;
         const int W = mW, Wb = W / MSS_BANDS;
         const long Lp = (long)mLinesPAN, Lm = (long)mLinesMSS;
         // the argument checks of CalcInterBandCorrelation (preproc.h:228-237) and DoInterBandAlignment, before a byte is read
-        char msg[256];
-        if (o.slices < OIP_IBCV_MIN_SLICES) {
-            snprintf(msg, sizeof msg, "CalcInterBandCorrelation: at lease %d slice needed", OIP_IBCV_MIN_SLICES);
-            throw std::invalid_argument(msg);
-        }
-        if (o.sections <= 0) throw std::invalid_argument("CalcInterBandCorrelation: section count should be a positive integer");
-        if (o.sections > 1 && (long)o.sections * OIP_CORRELATION_LINES > Lp) {
-            snprintf(msg, sizeof msg, "CalcInterBandCorrelation: too many sections (%d lines per section), not enough total PAN data lines", OIP_CORRELATION_LINES);
-            throw std::invalid_argument(msg);
-        }
+        std::string refused = InterBandArgCheck(Lp, o.slices, o.sections, OIP_CORRELATION_LINES);
+        if (!refused.empty()) throw std::invalid_argument(refused);
         const long outRows = Lm - o.lineOffset - (o.keepLeading ? 0 : o.overlapLines);
         if (outRows <= 0) throw std::invalid_argument("Too few image lines left to process");
-        // preproc.h:245-247, :274-276
-        const int baseRows = (int)std::min<long>(Lp, OIP_CORRELATION_LINES), baseCols = W / o.slices;
-        const long baseGap = (Lp - (long)baseRows * o.sections) / (o.sections + 1);
-        const int bandRows = baseRows / MSS_BANDS, bandCols = baseCols / MSS_BANDS;
-        const long bandGap = baseGap / MSS_BANDS;
-        if (bandRows <= 0 || bandCols <= 0) throw std::invalid_argument("oip_interband_correlate: slice too small");
-        std::vector<long> p0(o.sections), m0(o.sections);
-        for (int sec = 0; sec < o.sections; ++sec) {
-            p0[sec] = baseGap + (long)sec * (baseRows + baseGap);                 // preproc.h:257
-            m0[sec] = bandGap + (long)sec * (bandRows + bandGap);                 // preproc.h:284
-            if (p0[sec] + baseRows > Lp || m0[sec] + bandRows > Lm) throw std::invalid_argument("oip_interband_correlate: section outside the strip");
-        }
+        InterBandGeom g;
+        refused = MakeInterBandGeom(W, Lp, o.slices, o.sections, OIP_CORRELATION_LINES, &g);
+        if (!refused.empty()) throw std::invalid_argument(refused);
+        if (g.mss_start(g.sections - 1) + g.band_rows > Lm) throw std::invalid_argument("oip_interband_correlate: section outside the strip");
         mPAN.alloc((size_t)W * Lp);
         mMssBil.alloc((size_t)W * Lm);
         mPlaneStride = (size_t)Wb * Lm;
         mPlanes.alloc(mPlaneStride * MSS_BANDS);
         DevBuf<uint16_t> out((size_t)outRows * Wb * MSS_BANDS);
         DevBuf<double> kbPan, kbMss;
-        const double tSetup = seconds_since(t0);
+        t.setup = seconds_since(t.t0);
+        const std::vector<ArrivalItem> order = ArrivalOrder(g, Lm, std::max<long>(1, (long)(((size_t)256 << 20) / ((size_t)W * BYTES_PER_PIXEL))));
+        const std::string rrcPanPath = IMO::BuildOutputFilePath(mPanFile, ".RRC");
+        AlignedProduct product(IMO::BuildOutputFilePath(mMssFile, ".ALIGNED", ".TIFF"), Wb, outRows);
+        JobThread panWriter;
+        StripReader reader(*this, order, t);
+        product.prepare();
+        PrepareWhileReading(o, g, kbPan, kbMss, rrcPanPath, &t);
 
-        // ---- the order of arrival
-        enum Kind { kMss, kPan, kUnits, kFit };
-        struct Item { Kind kind; long a, b; };
-        std::vector<Item> order;
-        const long blockLines = std::max<long>(1, (long)(((size_t)256 << 20) / ((size_t)W * BYTES_PER_PIXEL)));
-        auto pan_blocks = [&](long a, long b) { for (long r = a; r < b; r += blockLines) order.push_back({kPan, r, std::min(b, r + blockLines)}); };
-        for (int sec = 0; sec < o.sections; ++sec) {
-            order.push_back({kMss, m0[sec], m0[sec] + bandRows});
-            pan_blocks(p0[sec], p0[sec] + baseRows);
-            order.push_back({kUnits, sec, 0});
+        std::vector<double> table((size_t)MSS_BANDS * g.n_units * 4);
+        ShiftTableInit(g, table.data());
+        int unitsDone = 0;
+        for (const ArrivalItem &it : order) {
+            if (it.kind == ArrivalItem::kMss || it.kind == ArrivalItem::kPan) reader.wait_next();
+            if (it.kind == ArrivalItem::kMss)
+                ck(oip_mss_split_rrc_u16(ctx, mMssBil.p + (size_t)it.a * W, mPlanes.p + (size_t)it.a * Wb, mPlaneStride, W, it.b - it.a, kbMss.p));
+            else if (it.kind == ArrivalItem::kPan) CorrectPanBlock(o, it, kbPan.p, panWriter, rrcPanPath);
+            else if (it.kind == ArrivalItem::kUnits) CorrelateUnitsThrough(g, (int)it.a, &unitsDone, table.data(), &t);
+            else FitAlignAndPost(o, table, out.p, outRows, product, &t);       // every section and every MSS line is in
         }
-        {   // the MSS lines between the sections: only the alignment reads them
-            long prev = 0;
-            for (int sec = 0; sec <= o.sections; ++sec) {
-                const long a = sec < o.sections ? m0[sec] : Lm;
-                if (prev < a) order.push_back({kMss, prev, a});
-                prev = sec < o.sections ? m0[sec] + bandRows : Lm;
-            }
-        }
-        order.push_back({kFit, 0, 0});
-        {   // the PAN lines between the sections: no arithmetic of this action reads them (they are read and corrected as
-            // the reference does -- the strip's size is checked, --write-rrcpan wants them)
-            long prev = 0;
-            for (int sec = 0; sec <= o.sections; ++sec) {
-                const long a = sec < o.sections ? p0[sec] : Lp;
-                if (prev < a) pan_blocks(prev, a);
-                prev = sec < o.sections ? p0[sec] + baseRows : Lp;
-            }
-        }
+        reader.finish();
+        ck(oip_sync(ctx));
+        t.computeDone = seconds_since(t.t0);
+        OLOG("%zu bytes read in %.3f seconds (%.1f MBps).", mSizePAN + mSizeMSS, t.readDone, (mSizePAN + mSizeMSS) / t.readDone / 1024.0 / 1024.0);
+        if (o.doRRC4PAN) OLOG("RRC for PAN done in %.4f seconds (%.1f MBps).", t.computeDone, mSizePAN / t.computeDone / 1024.0 / 1024.0);
+        OLOG("RRC done for MSS bands in %.4f seconds (%.1f MBps).", t.computeDone, mSizeMSS / t.computeDone / 1024.0 / 1024.0);
+        panWriter.finish();
+        if (o.writeRrcPan) OLOG("Written to file [%s].", rrcPanPath.c_str());
+        // the strips are done with: their 9 GB go back while the product is still on its way to the file (releasing them is a
+        // good part of what a process of this size pays at exit)
+        mMssBil.release();
+        mPlanes.release();
+        mPAN.release();
+        product.finish();
+        t.all = seconds_since(t.t0);
+        OLOG("DoInterBandAlignment(): done.");
+        t.log(mSizePAN + mSizeMSS, product.bytes() + (o.writeRrcPan ? mSizePAN : 0));
+    }
 
-        // ---- reader thread
-        OLOG("Loading PAN raw image ...");
-        OLOG("Loading MSS raw image ...");
-        OLOG("Reading raw image from file `%s' ...", mPanFile.c_str());
-        OLOG("Reading raw image from file `%s' ...", mMssFile.c_str());
-        BlockingQueue<long> tickets;                       // one per read item, in order; -1: the reader failed
-        std::atomic<bool> cancel{false};
-        std::exception_ptr readerError;
-        double tReadDone = 0.0;
-        const size_t lineBytes = (size_t)W * BYTES_PER_PIXEL;
-        std::thread reader([&] {
-            try {
-                for (const Item &it : order) {
-                    if (it.kind != kMss && it.kind != kPan) continue;
-                    if (cancel.load()) break;
-                    const bool pan = it.kind == kPan;
-                    const size_t off = (size_t)it.a * lineBytes, n = (size_t)(it.b - it.a) * lineBytes;
-                    size_t got = 0;
-                    long t = 0;
-                    const int rc = oip_read_file_to_device(ctx, (pan ? mPanFile : mMssFile).c_str(), off, n,
-                                                           (char *)(pan ? mPAN.p : mMssBil.p) + off, &got, &t);
-                    if (rc != OIP_OK) Device::get().check(rc);
-                    if (got != n)
-                        throw std::runtime_error("file size(" + std::to_string(pan ? mSizePAN : mSizeMSS) + ") doesn't match with read byte count(" +
-                                                 std::to_string(off + got) + ")");
-                    tickets.push(t);
+    const double *deltaXcoeffs() const { return &mDeltaXcoeffs[0][0]; }
+    const double *deltaYcoeffs() const { return &mDeltaYcoeffs[0][0]; }
+
+private:
+    // ---- the parts of RunPipelined ----
+    // seconds since the action started, and the one line harnesses read (bench.py's `cli` object)
+    struct PipelineTimes {
+        const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+        double setup = 0, prepared = 0, readDone = 0, corrDone = 0, alignDone = 0, computeDone = 0, all = 0;
+        std::string corrCalls;                             // start+duration of every correlation call, ms
+        void log(size_t bytesRead, size_t bytesWritten) const
+        {
+            double lane[4] = {0, 0, 0, 0};                   // the reader's own time: in pread (all pool threads), waiting for a ring slot's DMA
+            oip_stage_stats(Device::get().ctx(), lane, 0);
+            RLOG("TIMING default_action pipelined=1 setup=%.4f prepared=%.4f read_done=%.4f correlation_done=%.4f aligned=%.4f compute_done=%.4f products_written=%.4f "
+                 "device_create=%.4f since_process_start=%.4f reader_in_pread=%.4f reader_waiting_for_slot=%.4f bytes_read=%zu bytes_written=%zu "
+                 "correlation_calls_ms=%s",
+                 setup, prepared, readDone, corrDone, alignDone, computeDone, all, Device::get().create_seconds(), seconds_since(process_start()), lane[0], lane[1],
+                 bytesRead, bytesWritten, corrCalls.c_str());
+        }
+    };
+
+    // The reader: the two RAW files go file -> pinned ring -> HBM in the order of arrival, a ticket per read item.  Its thread
+    // is a JobThread's, joined by that member's destructor: nothing can stand between the thread's start and its guard.
+    class StripReader {
+    public:
+        StripReader(PreProcessor &pp, const std::vector<ArrivalItem> &order, PipelineTimes &times)
+        {
+            OLOG("Loading PAN raw image ...");
+            OLOG("Loading MSS raw image ...");
+            OLOG("Reading raw image from file `%s' ...", pp.mPanFile.c_str());
+            OLOG("Reading raw image from file `%s' ...", pp.mMssFile.c_str());
+            mThread.post([this, &pp, &order, &times] {
+                const size_t lineBytes = (size_t)pp.mW * BYTES_PER_PIXEL;
+                try {
+                    for (const ArrivalItem &it : order) {
+                        if (it.kind != ArrivalItem::kMss && it.kind != ArrivalItem::kPan) continue;
+                        if (mCancel.load()) break;
+                        const bool pan = it.kind == ArrivalItem::kPan;
+                        const size_t off = (size_t)it.a * lineBytes, n = (size_t)(it.b - it.a) * lineBytes;
+                        size_t got = 0;
+                        long t = 0;
+                        Device::get().check(oip_read_file_to_device(Device::get().ctx(), (pan ? pp.mPanFile : pp.mMssFile).c_str(), off, n,
+                                                                    (char *)(pan ? pp.mPAN.p : pp.mMssBil.p) + off, &got, &t));
+                        if (got != n)
+                            throw std::runtime_error("file size(" + std::to_string(pan ? pp.mSizePAN : pp.mSizeMSS) + ") doesn't match with read byte count(" +
+                                                     std::to_string(off + got) + ")");
+                        mTickets.push(t);
+                    }
+                    times.readDone = seconds_since(times.t0);
+                } catch (...) {
+                    mTickets.push(-1);
+                    throw;
                 }
-                tReadDone = seconds_since(t0);
-            } catch (...) {
-                readerError = std::current_exception();
-                tickets.push(-1);
-            }
-        });
-        double tCorrDone = 0.0, tAlignDone = 0.0;
-        // the product file exists from the start (its blocks are reserved while the strip is still being read); a run that fails
-        // takes it away again
-        struct ProductGuard {
-            std::string path;
-            bool done = false;
-            oip_file_sink *sink = nullptr;         // the product's prepared file (uncompressed products)
-            uint64_t payloadAt = 0;
-            ~ProductGuard()
-            {
-                if (sink) oip_file_sink_close(nullptr, sink);
-                if (!done && !path.empty()) ::remove(path.c_str());
-            }
-        } productGuard;
-        const std::string alignedPath = IMO::BuildOutputFilePath(mMssFile, ".ALIGNED", ".TIFF");
-        const int comp = tiff_compression(TIFF_LZW);
-        std::unique_ptr<TiffWriterU16> tiff(new TiffWriterU16(alignedPath, Wb, outRows, MSS_BANDS, false, comp));   // (declared before the writers: their jobs use it)
-        productGuard.path = alignedPath;
-        std::unique_ptr<TiffLzwPrep> lzwPrep;              // (declared before the writers too)
-        JobThread panWriter, productWriter;
-        const size_t productBytes = (size_t)outRows * Wb * MSS_BANDS * 2;
-        // (an empty transfer: the writer's download lane pins its two slots now, not when the product is waiting for them)
-        productWriter.post([=] { Device::get().check(oip_download_staged_after(ctx, nullptr, nullptr, 0, 0)); });
-        if (comp == TIFF_LZW && gpu_lzw()) {
-            // likewise for the LZW product: device buffers of the strip encoder, the file reserved at its worst-case size
-            lzwPrep.reset(new TiffLzwPrep());
-            TiffWriterU16 *twp = tiff.get();
-            TiffLzwPrep *lp = lzwPrep.get();
-            productWriter.post([=] { lp->prepare(*twp, alignedPath, Wb, outRows, MSS_BANDS, true); });
-        }
-        if (comp == TIFF_NONE) {
-            // the writer thread has nothing to do until the fit is in: it prepares the product file -- header out, blocks
-            // reserved, pages mapped and populated (oip_file_sink_open) -- so that the pixels, when they exist, are copied
-            // into pages that exist (the allocation is what bounds a buffered write of a new file)
-            TiffWriterU16 *twp = tiff.get();
-            ProductGuard *pg = &productGuard;
-            productWriter.post([=] {
-                pg->payloadAt = twp->begin_external_payload();
-                Device::get().check(oip_file_sink_open(ctx, alignedPath.c_str(), (size_t)pg->payloadAt + productBytes, &pg->sink));
             });
         }
-        struct Joiner {                                    // whatever happens below, the threads are stopped and joined
-            std::thread &reader; std::atomic<bool> &cancel;
-            ~Joiner() { cancel = true; if (reader.joinable()) reader.join(); }
-        } joiner{reader, cancel};
+        ~StripReader() { mCancel = true; }
+        // the next read item: the compute stream waits for it on the device; a failure of the reader is raised here
+        void wait_next()
+        {
+            const long t = mTickets.pop();
+            if (t < 0) finish();
+            Device::get().check(oip_stage_wait(Device::get().ctx(), t));
+        }
+        void finish() { mThread.finish(); }
+    private:
+        BlockingQueue<long> mTickets;                      // one per read item, in order; -1: the reader failed
+        std::atomic<bool> mCancel{false};
+        JobThread mThread;
+    };
 
-        // while the first section is on its way: the LUTs, and everything the first correlation call would otherwise set up behind
-        // the data -- FFT plans and twiddles, the up-sampling operator's tables, the workspace (a call with no units does just that)
-        if (o.doRRC4PAN) {
-            std::unique_ptr<RRCParam[]> prm(IMO::LoadRRCParamFile(mRrcPanFile.c_str(), W));
-            kbPan.alloc((size_t)W * 2);
-            kbPan.upload((double *)prm.get(), (size_t)W * 2);
+    // <mss>.ALIGNED.TIFF of the pipeline.  The file exists from the start -- its blocks are reserved on the writer thread while
+    // the strip is still being read -- and a run that fails takes it away again.  The writer thread is declared (and started,
+    // idle) before the file is created: nothing in the constructor can throw once the file is there, so the destructor, which
+    // lets the writer finish its jobs before what they use goes, always gets to take a failed run's file away.
+    struct AlignedProduct {
+        const std::string path;
+        const int comp, Wb;
+        const long rows;
+        bool done = false;
+        oip_file_sink *sink = nullptr;                     // the product's prepared file (uncompressed products)
+        uint64_t payloadAt = 0;
+        JobThread writer;
+        TiffWriterU16 tiff;
+        std::unique_ptr<TiffLzwPrep> lzwPrep;
+
+        size_t bytes() const { return (size_t)rows * Wb * MSS_BANDS * 2; }
+        AlignedProduct(const std::string &path_, int Wb_, long rows_)
+            : path(path_), comp(tiff_compression(TIFF_LZW)), Wb(Wb_), rows(rows_), tiff(path, Wb, rows, MSS_BANDS, false, comp)
+        {
         }
-        if (o.doRRC4MSS) {
-            std::vector<double> all((size_t)W * 2);
-            for (int i = 0; i < MSS_BANDS; ++i) {
-                std::unique_ptr<RRCParam[]> prm(IMO::LoadRRCParamFile(mRrcMssBndFile[i].c_str(), Wb));
-                memcpy(&all[(size_t)i * Wb * 2], prm.get(), sizeof(double) * 2 * Wb);
+        ~AlignedProduct()
+        {
+            try { writer.finish(); } catch (...) {}
+            if (sink) oip_file_sink_close(nullptr, sink);
+            if (!done) ::remove(path.c_str());
+        }
+        // what the writer thread does while the strip is being read.  Called once the reader has started: the jobs pin memory and
+        // reserve the file's blocks, and the first section's lines should not start behind that
+        void prepare()
+        {
+            oip_ctx *ctx = Device::get().ctx();
+            // (an empty transfer: the writer's download lane pins its two slots now, not when the product is waiting for them)
+            writer.post([=] { Device::get().check(oip_download_staged_after(ctx, nullptr, nullptr, 0, 0)); });
+            if (comp == TIFF_LZW && gpu_lzw()) {
+                // likewise for the LZW product: device buffers of the strip encoder, the file reserved at its worst-case size
+                lzwPrep.reset(new TiffLzwPrep());
+                writer.post([this] { lzwPrep->prepare(tiff, path, Wb, rows, MSS_BANDS, true); });
             }
-            kbMss.alloc((size_t)W * 2);
-            kbMss.upload(all.data(), (size_t)W * 2);
+            if (comp == TIFF_NONE) {
+                // the writer thread has nothing to do until the fit is in: it prepares the product file -- header out, blocks
+                // reserved, pages mapped and populated (oip_file_sink_open) -- so that the pixels, when they exist, are copied
+                // into pages that exist (the allocation is what bounds a buffered write of a new file)
+                writer.post([this, ctx] {
+                    payloadAt = tiff.begin_external_payload();
+                    Device::get().check(oip_file_sink_open(ctx, path.c_str(), (size_t)payloadAt + bytes(), &sink));
+                });
+            }
         }
-        ck(oip_interband_correlate_units(ctx, nullptr, nullptr, nullptr, nullptr, 0, baseRows, baseCols, nullptr));
-        const double tPrepared = seconds_since(t0);
-        const std::string rrcPanPath = IMO::BuildOutputFilePath(mPanFile, ".RRC");
+        // the image (rows x Wb x 4 u16 in file sample order, complete at `mark` of the compute stream) goes to the file
+        void post_write(const uint16_t *img, long mark, long processed, PipelineTimes *times)
+        {
+            oip_ctx *ctx = Device::get().ctx();
+            writer.post([this, ctx, img, mark, processed, times] {
+                Device::get().check(oip_compute_mark_sync(ctx, mark));
+                times->alignDone = seconds_since(times->t0);
+                OLOG("Alignment done in %.3f seconds (%ld lines valid of %ld).", times->alignDone, processed, rows);
+                OLOG("Outputing aligned TIFF image (%d x %ld x 4) to [%s] ...", Wb, rows, path.c_str());
+                if (comp == TIFF_NONE) {
+                    Device::get().check(oip_file_sink_write(ctx, sink, (size_t)payloadAt, img, bytes(), mark));
+                    oip_file_sink *k = sink;
+                    sink = nullptr;
+                    Device::get().check(oip_file_sink_close(ctx, k));
+                    tiff.end_external_payload();
+                } else if (gpu_lzw()) {
+                    tiff_lzw_from_device(tiff, path, img, Wb, rows, MSS_BANDS, lzwPrep.get());
+                } else {
+                    tiff_rows_from_device(tiff, img, rows, (size_t)Wb * MSS_BANDS, mark);     // download || encode || write
+                }
+                tiff.close();
+                OLOG("Output done.");
+            });
+        }
+        // the product is on disk when this returns (a failure of the writer is re-thrown)
+        void finish() { writer.finish(); done = true; }
+    };
+
+    // while the first section is on its way: the LUTs, and everything the first correlation call would otherwise set up behind
+    // the data -- FFT plans and twiddles, the up-sampling operator's tables, the workspace (a call with no units does just that)
+    void PrepareWhileReading(const DefaultActionOptions &o, const InterBandGeom &g, DevBuf<double> &kbPan, DevBuf<double> &kbMss,
+                             const std::string &rrcPanPath, PipelineTimes *t)
+    {
+        if (o.doRRC4PAN) kbPan.assign(IMO::LoadLut(mRrcPanFile, mW));
+        if (o.doRRC4MSS) kbMss.assign(IMO::LoadMssLuts(mRrcMssBndFile, mW));
+        Device::get().check(oip_interband_correlate_units(Device::get().ctx(), nullptr, nullptr, nullptr, nullptr, 0, g.base_rows, g.base_cols, nullptr));
+        t->prepared = seconds_since(t->t0);
         if (o.writeRrcPan) {                               // sized up front: blocks land at their offsets in any order
             FILE *f = fopen(rrcPanPath.c_str(), "wb");
             if (!f) throw std::runtime_error("open file [" + rrcPanPath + "] failed: " + std::to_string(errno));
@@ -1315,157 +1366,82 @@ public:
         if (o.doRRC4PAN) OLOG("Begin inplace RRC for PAN data ... ");
         OLOG("Splitting %d bands of MSS image%s ...", MSS_BANDS, o.doRRC4MSS ? " with inplace RRC" : "");
         OLOG("Calculating inter-band correlation with %d slices in %d section(s) ...", o.slices, o.sections);
-
-        const int n = o.slices * o.sections;
-        std::vector<double> table((size_t)MSS_BANDS * n * 4, NAN);
-        for (int b = 0; b < MSS_BANDS; ++b)
-            for (int u = 0; u < n; ++u) table[((size_t)b * n + u) * 4 + 3] = (double)((u % o.slices) * baseCols + baseCols / 2);   // preproc.h:326
-        int unitsDone = 0;
-        std::string corrCalls;                             // start+duration of every correlation call, ms (TIMING line)
-        for (const Item &it : order) {
-            if (it.kind == kMss || it.kind == kPan) {
-                const long t = tickets.pop();
-                if (t < 0) { reader.join(); std::rethrow_exception(readerError); }
-                ck(oip_stage_wait(ctx, t));
-                if (it.kind == kMss) {
-                    ck(oip_mss_split_rrc_u16(ctx, mMssBil.p + (size_t)it.a * W, mPlanes.p + (size_t)it.a * Wb, mPlaneStride, W, it.b - it.a,
-                                             o.doRRC4MSS ? kbMss.p : nullptr));
-                } else {
-                    uint16_t *blk = mPAN.p + (size_t)it.a * W;
-                    if (o.doRRC4PAN) ck(oip_rrc_u16(ctx, blk, blk, W, it.b - it.a, kbPan.p));
-                    if (o.writeRrcPan) {
-                        long mark = 0;
-                        ck(oip_compute_mark(ctx, &mark));
-                        const size_t off = (size_t)it.a * lineBytes, nb = (size_t)(it.b - it.a) * lineBytes;
-                        panWriter.post([=] { Device::get().check(oip_write_device_to_file_at(ctx, blk, nb, rrcPanPath.c_str(), off, mark)); });
-                    }
-                }
-            } else if (it.kind == kUnits) {
-                // the units of the sections resident so far, in the pairs (2k, 2k+1) of the one-call form (a pair that spans two
-                // sections -- odd slice counts -- waits for the second)
-                const int sec = (int)it.a;
-                int hi = (sec + 1) * o.slices;
-                if (sec != o.sections - 1) hi &= ~1;
-                const int cnt = hi - unitsDone;
-                if (cnt <= 0) continue;
-                std::vector<const uint16_t *> dPan(cnt), dBands((size_t)cnt * MSS_BANDS);
-                std::vector<size_t> panPitch(cnt, (size_t)W), bandPitch(cnt, (size_t)Wb);
-                for (int j = 0; j < cnt; ++j) {
-                    const int u = unitsDone + j, us = u / o.slices, i = u % o.slices;
-                    dPan[j] = mPAN.p + (size_t)p0[us] * W + (size_t)i * baseCols;
-                    for (int b = 0; b < MSS_BANDS; ++b) dBands[(size_t)j * MSS_BANDS + b] = mPlanes.p + (size_t)b * mPlaneStride + (size_t)m0[us] * Wb + (size_t)i * bandCols;
-                }
-                std::vector<double> r((size_t)12 * cnt);
-                const double tc0 = seconds_since(t0);
-                ck(oip_interband_correlate_units(ctx, dPan.data(), panPitch.data(), dBands.data(), bandPitch.data(), cnt, baseRows, baseCols, r.data()));
-                corrCalls += (corrCalls.empty() ? "" : ",") + std::to_string((int)(tc0 * 1e3)) + "+" + std::to_string((int)((seconds_since(t0) - tc0) * 1e3));
-                for (int j = 0; j < cnt; ++j)
-                    for (int b = 0; b < MSS_BANDS; ++b)
-                        for (int k = 0; k < 3; ++k) table[((size_t)b * n + unitsDone + j) * 4 + k] = r[(size_t)12 * j + 3 * b + k];
-                unitsDone = hi;
-                if (sec == o.sections - 1) tCorrDone = seconds_since(t0);
-            } else {
-                // every section and every MSS line is in: filter, fit, align, product
-                OLOG("Inter-band correlation finished in %.3f seconds, result:", tCorrDone);
-                for (int b = 0; b < MSS_BANDS; ++b) {
-                    mBandShift[b].resize(n);
-                    for (int i = 0; i < n; ++i) {
-                        const double *sv = &table[((size_t)b * n + i) * 4];
-                        mBandShift[b][i] = InterBandShift{sv[0], sv[1], sv[2], (int)sv[3]};
-                    }
-                }
-                DumpInterBandShiftValues(o.slices, o.sections);
-                OLOG("Filter invalid correlation values & try polynomial fitting ...");
-                char err[512];
-                const int rc = oip_filter_and_fit_mode(table.data(), n, o.threshold, OIP_IBCV_MIN_COUNT, mFitMode, &mDeltaXcoeffs[0][0], &mDeltaYcoeffs[0][0], err, sizeof err);
-                if (rc != OIP_OK) { OLOG("%s.", err); throw std::runtime_error(err); }
-                for (int b = 0; b < MSS_BANDS; ++b) {
-                    OLOG("BAND %d\tdeltaX coeff: [1] %.15f, [0] %.9f", b, mDeltaXcoeffs[b][1], mDeltaXcoeffs[b][0]);
-                    OLOG("\tdeltaY coeff: [2] %.15f, [1] %.15f, [0] %.9f", mDeltaYcoeffs[b][2], mDeltaYcoeffs[b][1], mDeltaYcoeffs[b][0]);
-                }
-                OLOG("CalcInterBandCorrelation(): done.");
-                OLOG("Doing inter-band alignment ...");
-                long processed = 0;
-                ck(oip_align_mss_bicubic_u16x4(ctx, mPlanes.p, mPlaneStride, 0, Lm, out.p, 0, outRows, Wb, Lm, &mDeltaXcoeffs[0][0], &mDeltaYcoeffs[0][0],
-                                               o.linesSection, o.lineOffset, o.overlapLines, o.keepLeading ? 1 : 0, OIP_IBPA_MIN_PROCESSLINES, &processed));
-                // preproc.h:167-185 WriteAlignedMSS_TIFF: cv::imwrite stores the Mat's channels (c0,c1,c2,c3) as samples (c2,c1,c0,c3);
-                // the image takes that order on the device, so its lines go from HBM into the file as they are
-                const int fileOrder[4] = {2, 1, 0, 3};
-                ck(oip_permute_u16x4(ctx, out.p, (size_t)outRows * Wb, fileOrder));
-                long mark = 0;
-                ck(oip_compute_mark(ctx, &mark));
-                TiffWriterU16 *tw = tiff.get();
-                ProductGuard *pg = &productGuard;
-                TiffLzwPrep *lp = lzwPrep.get();
-                const uint16_t *img = out.p;
-                const size_t rowSamples = (size_t)Wb * MSS_BANDS;
-                const long rows = outRows;
-                productWriter.post([=, &tAlignDone] {
-                    Device::get().check(oip_compute_mark_sync(ctx, mark));
-                    tAlignDone = seconds_since(t0);
-                    OLOG("Alignment done in %.3f seconds (%ld lines valid of %ld).", tAlignDone, processed, rows);
-                    OLOG("Outputing aligned TIFF image (%d x %ld x 4) to [%s] ...", Wb, rows, alignedPath.c_str());
-                    if (comp == TIFF_NONE) {
-                        Device::get().check(oip_file_sink_write(ctx, pg->sink, (size_t)pg->payloadAt, img, (size_t)rows * rowSamples * 2, mark));
-                        oip_file_sink *k = pg->sink;
-                        pg->sink = nullptr;
-                        Device::get().check(oip_file_sink_close(ctx, k));
-                        tw->end_external_payload();
-                    } else if (gpu_lzw()) {
-                        tiff_lzw_from_device(*tw, alignedPath, img, Wb, rows, MSS_BANDS, lp);
-                    } else {
-                        tiff_rows_from_device(*tw, img, rows, rowSamples, mark);     // download || encode || write
-                    }
-                    tw->close();
-                    OLOG("Output done.");
-                });
-            }
-        }
-        reader.join();
-        if (readerError) std::rethrow_exception(readerError);
-        ck(oip_sync(ctx));
-        const double tComputeDone = seconds_since(t0);
-        OLOG("%zu bytes read in %.3f seconds (%.1f MBps).", mSizePAN + mSizeMSS, tReadDone, (mSizePAN + mSizeMSS) / tReadDone / 1024.0 / 1024.0);
-        if (o.doRRC4PAN) OLOG("RRC for PAN done in %.4f seconds (%.1f MBps).", tComputeDone, mSizePAN / tComputeDone / 1024.0 / 1024.0);
-        OLOG("RRC done for MSS bands in %.4f seconds (%.1f MBps).", tComputeDone, mSizeMSS / tComputeDone / 1024.0 / 1024.0);
-        panWriter.finish();
-        if (o.writeRrcPan) OLOG("Written to file [%s].", rrcPanPath.c_str());
-        // the strips are done with: their 9 GB go back while the product is still on its way to the file (releasing them is a
-        // good part of what a process of this size pays at exit)
-        mMssBil.release();
-        mPlanes.release();
-        mPAN.release();
-        productWriter.finish();
-        productGuard.done = true;
-        const double tAll = seconds_since(t0);
-        OLOG("DoInterBandAlignment(): done.");
-        // one line for harnesses (bench.py's `cli` object): seconds since the action started
-        double lane[4] = {0, 0, 0, 0};                       // the reader's own time: in pread (all pool threads), waiting for a ring slot's DMA
-        oip_stage_stats(ctx, lane, 0);
-        RLOG("TIMING default_action pipelined=1 setup=%.4f prepared=%.4f read_done=%.4f correlation_done=%.4f aligned=%.4f compute_done=%.4f products_written=%.4f "
-             "device_create=%.4f since_process_start=%.4f reader_in_pread=%.4f reader_waiting_for_slot=%.4f bytes_read=%zu bytes_written=%zu "
-             "correlation_calls_ms=%s",
-             tSetup, tPrepared, tReadDone, tCorrDone, tAlignDone, tComputeDone, tAll, Device::get().create_seconds(), seconds_since(process_start()), lane[0], lane[1],
-             mSizePAN + mSizeMSS, (size_t)outRows * Wb * MSS_BANDS * 2 + (o.writeRrcPan ? mSizePAN : 0), corrCalls.c_str());
     }
 
-    const double *deltaXcoeffs() const { return &mDeltaXcoeffs[0][0]; }
-    const double *deltaYcoeffs() const { return &mDeltaYcoeffs[0][0]; }
-
-private:
-    void DumpInterBandShiftValues(int slices, int sections)             // preproc.h:470-490
+    // a PAN block is resident: RRC in place; --write-rrcpan: out to its place in the file behind a mark of the RRC kernel
+    void CorrectPanBlock(const DefaultActionOptions &o, const ArrivalItem &it, const double *kbPan, JobThread &panWriter, const std::string &rrcPanPath)
     {
+        oip_ctx *ctx = Device::get().ctx();
+        uint16_t *blk = mPAN.p + (size_t)it.a * mW;
+        if (o.doRRC4PAN) Device::get().check(oip_rrc_u16(ctx, blk, blk, mW, it.b - it.a, kbPan));
+        if (!o.writeRrcPan) return;
+        long mark = 0;
+        Device::get().check(oip_compute_mark(ctx, &mark));
+        const size_t lineBytes = (size_t)mW * BYTES_PER_PIXEL, off = (size_t)it.a * lineBytes, nb = (size_t)(it.b - it.a) * lineBytes;
+        panWriter.post([=] { Device::get().check(oip_write_device_to_file_at(ctx, blk, nb, rrcPanPath.c_str(), off, mark)); });
+    }
+
+    // section `sec` is resident: the units that may run now (InterBandGeom::units_through) in one call, their shifts into the table
+    void CorrelateUnitsThrough(const InterBandGeom &g, int sec, int *unitsDone, double *table, PipelineTimes *t)
+    {
+        const int first = *unitsDone, cnt = g.units_through(sec) - first;
+        if (cnt <= 0) return;
+        std::vector<const uint16_t *> dPan(cnt), dBands((size_t)cnt * MSS_BANDS);
+        std::vector<size_t> panPitch(cnt, (size_t)g.W), bandPitch(cnt, (size_t)g.Wb);
+        for (int j = 0; j < cnt; ++j) {
+            const int u = first + j, us = u / g.slices, i = u % g.slices;
+            dPan[j] = mPAN.p + (size_t)g.pan_start(us) * g.W + (size_t)i * g.base_cols;
+            for (int b = 0; b < MSS_BANDS; ++b)
+                dBands[(size_t)j * MSS_BANDS + b] = mPlanes.p + (size_t)b * mPlaneStride + (size_t)g.mss_start(us) * g.Wb + (size_t)i * g.band_cols;
+        }
+        std::vector<double> r((size_t)12 * cnt);
+        const double tc0 = seconds_since(t->t0);
+        Device::get().check(oip_interband_correlate_units(Device::get().ctx(), dPan.data(), panPitch.data(), dBands.data(), bandPitch.data(), cnt, g.base_rows,
+                                                          g.base_cols, r.data()));
+        t->corrCalls += (t->corrCalls.empty() ? "" : ",") + std::to_string((int)(tc0 * 1e3)) + "+" + std::to_string((int)((seconds_since(t->t0) - tc0) * 1e3));
+        for (int j = 0; j < cnt; ++j) ShiftTablePut(g, table, first + j, &r[(size_t)12 * j]);
+        *unitsDone = first + cnt;
+        if (sec == g.sections - 1) t->corrDone = seconds_since(t->t0);
+    }
+
+    // filter, fit, the alignment kernel, and the image on its way to the product
+    void FitAlignAndPost(const DefaultActionOptions &o, const std::vector<double> &table, uint16_t *out, long outRows, AlignedProduct &product, PipelineTimes *t)
+    {
+        oip_ctx *ctx = Device::get().ctx();
+        const int Wb = mW / MSS_BANDS;
+        OLOG("Inter-band correlation finished in %.3f seconds, result:", t->corrDone);
+        FitShiftTable(table, o.slices, o.sections, o.threshold);
+        OLOG("Doing inter-band alignment ...");
+        long processed = 0, mark = 0;
+        Device::get().check(oip_align_mss_bicubic_u16x4(ctx, mPlanes.p, mPlaneStride, 0, (long)mLinesMSS, out, 0, outRows, Wb, (long)mLinesMSS, &mDeltaXcoeffs[0][0],
+                                                        &mDeltaYcoeffs[0][0], o.linesSection, o.lineOffset, o.overlapLines, o.keepLeading ? 1 : 0,
+                                                        OIP_IBPA_MIN_PROCESSLINES, &processed));
+        // preproc.h:167-185 WriteAlignedMSS_TIFF: cv::imwrite stores the Mat's channels (c0,c1,c2,c3) as samples (c2,c1,c0,c3);
+        // the image takes that order on the device, so its lines go from HBM into the file as they are
+        const int fileOrder[4] = {2, 1, 0, 3};
+        Device::get().check(oip_permute_u16x4(ctx, out, (size_t)outRows * Wb, fileOrder));
+        Device::get().check(oip_compute_mark(ctx, &mark));
+        product.post_write(out, mark, processed, t);
+    }
+
+    // the shift table [band][unit][dx, dy, rs, cx] of all units: dumped (preproc.h:470-490), filtered and fitted (:331-346)
+    void FitShiftTable(const std::vector<double> &table, int slices, int sections, double threshold)
+    {
+        const int n = slices * sections, sliceCols = mW / slices;
         RLOG("|#SLC|Start|Center| End |   B1.x   |   B2.x   |   B3.x   |   B4.x   |   B1.y   |   B2.y   |   B3.y   |   B4.y   "
              "|   B1.r   |   B2.r   |   B3.r   |   B4.r   |");
-        int sliceCols = mW / slices;
-        for (int s = 0; s < sections; ++s)
-            for (int i = 0; i < slices; ++i) {
-                int ii = i + s * slices;
-                RLOG("|%4d|%5d|%6d|%5d|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|", i,
-                     i * sliceCols, mBandShift[0][ii].cx, (i + 1) * sliceCols, mBandShift[0][ii].dx, mBandShift[1][ii].dx,
-                     mBandShift[2][ii].dx, mBandShift[3][ii].dx, mBandShift[0][ii].dy, mBandShift[1][ii].dy, mBandShift[2][ii].dy,
-                     mBandShift[3][ii].dy, mBandShift[0][ii].rs, mBandShift[1][ii].rs, mBandShift[2][ii].rs, mBandShift[3][ii].rs);
-            }
+        for (int u = 0; u < n; ++u) {
+            auto v = [&](int b, int k) { return table[((size_t)b * n + u) * 4 + k]; };
+            const int i = u % slices;
+            RLOG("|%4d|%5d|%6d|%5d|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|%10.4f|", i, i * sliceCols, (int)v(0, 3),
+                 (i + 1) * sliceCols, v(0, 0), v(1, 0), v(2, 0), v(3, 0), v(0, 1), v(1, 1), v(2, 1), v(3, 1), v(0, 2), v(1, 2), v(2, 2), v(3, 2));
+        }
+        OLOG("Filter invalid correlation values & try polynomial fitting ...");
+        char err[512];
+        int rc = oip_filter_and_fit_mode(table.data(), n, threshold, OIP_IBCV_MIN_COUNT, mFitMode, &mDeltaXcoeffs[0][0], &mDeltaYcoeffs[0][0], err, sizeof err);
+        if (rc != OIP_OK) { OLOG("%s.", err); throw std::runtime_error(err); }
+        LogShiftCoeffs(mDeltaXcoeffs, mDeltaYcoeffs);
+        OLOG("CalcInterBandCorrelation(): done.");
     }
 
     void CheckFilesAttributes()                                         // preproc.h:552-572
@@ -1477,11 +1453,7 @@ private:
         OLOG("Checking MSS raw file attributes ...");
         mSizeMSS = IMO::FileSize(mMssFile);
         mLinesMSS = mSizeMSS / lineBytes;
-        if (mSizePAN != MSS_BANDS * mSizeMSS)
-            throw std::runtime_error("PAN file size does not match MSS file size: PAN file should be " + std::to_string(MSS_BANDS) +
-                                     "x as large as MSS file");
-        if (mSizePAN % lineBytes != 0)
-            throw std::runtime_error("PAN file size invalid: should be multiplies of " + std::to_string(lineBytes));
+        CheckStripSizes(mSizePAN, mSizeMSS, lineBytes);
         OLOG("CheckFilesAttributes(): OK.");
     }
 
@@ -1493,7 +1465,6 @@ private:
     const uint16_t *mPanView = nullptr;
     bool mSplitDone = false;
     int mFitMode = OIP_FIT_REFERENCE;
-    std::vector<InterBandShift> mBandShift[MSS_BANDS];
     double mDeltaXcoeffs[MSS_BANDS][2] = {};
     double mDeltaYcoeffs[MSS_BANDS][3] = {};
 };
@@ -1564,13 +1535,13 @@ inline void RunFusedTask(const std::string &pan1, const std::string &pan2, const
         const size_t nout = (size_t)ow * L;
         DevBuf<uint16_t> st(nout);
         DevBuf<double> kb((size_t)W * 2);
-        std::unique_ptr<RRCParam[]> prm(IMO::LoadRRCParamFile(rrc1.c_str(), W));
-        kb.upload((double *)prm.get(), (size_t)W * 2);
+        std::vector<double> prm = IMO::LoadLut(rrc1, W);
+        kb.upload(prm.data(), prm.size());
         ck(oip_rrc_u16_window(ctx, p1.p, W, st.p, ow, W - fold, L, kb.p));
         ck(oip_sync(ctx));
         p1.release();
-        prm.reset(IMO::LoadRRCParamFile(rrc2.c_str(), W));
-        kb.upload((double *)prm.get(), (size_t)W * 2);
+        prm = IMO::LoadLut(rrc2, W);
+        kb.upload(prm.data(), prm.size());
         // the raw CCD-2 samples are corrected on load by the resampling kernel itself (either accumulate mode): one pass over the strip
         ck(oip_remap_shift_rrc_bicubic_u16_window(ctx, p2.p, 0, L, kb.p, st.p, ow, fold, W - fold, 0, L, W, L, dx, dy, OIP_REMAP_SECTION_ROWS,
                                                   OIP_REMAP_ROW_GUARD, o.fp16acc ? 1 : 0));
@@ -1584,8 +1555,8 @@ inline void RunFusedTask(const std::string &pan1, const std::string &pan2, const
     {
         DevBuf<double> kb((size_t)W * 2);
         for (int c = 0; c < 2; ++c) {
-            std::unique_ptr<RRCParam[]> prm(IMO::LoadRRCParamFile((c ? rrc2 : rrc1).c_str(), W));
-            kb.upload((double *)prm.get(), (size_t)W * 2);
+            const std::vector<double> prm = IMO::LoadLut(c ? rrc2 : rrc1, W);
+            kb.upload(prm.data(), prm.size());
             ck(oip_rrc_u16(ctx, c ? p2.p : p1.p, c ? p2.p : p1.p, W, L, kb.p));
             ck(oip_sync(ctx));
         }

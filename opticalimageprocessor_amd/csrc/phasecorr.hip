@@ -18,6 +18,7 @@
 // and two correlation surfaces ride one inverse FFT as Y = C1 + i C2.  The FFT round-off
 // differs from OpenCV's own DFT, so shifts agree to ~1e-4 px, not bitwise (parity unpinned:
 // OpenCV is not in the reference tree).
+#include "oip_corrgeom.h"
 #include "oip_fft.h"
 #include "oip_fft_dev.h"
 #include "oip_internal.h"
@@ -1935,30 +1936,23 @@ extern "C" int oip_stt_correlate(oip_ctx *ctx, const uint16_t *d_pan1, const uin
                                  double *out)
 {
     OIP_CHECK_CTX(ctx);
-    if (!d_pan1 || !d_pan2 || !out || W <= 0 || L <= 0 || sections <= 0 || lines_per_section <= 0 || overlap_cols <= 0 ||
-        overlap_cols > W || edge_cols < 0 || edge_cols >= overlap_cols || sections > 100000)
-        return oip_fail(ctx, OIP_E_INVALID, "oip_stt_correlate: bad argument");
-    // stitcher.h:75-77
-    if (L < (long)sections * lines_per_section)
-        return oip_fail(ctx, OIP_E_INVALID, "PAN line count less than sections times line-per-section, use smaller -s and/or -l value(s)");
-    const int rows = lines_per_section, cols = overlap_cols - edge_cols;
-    // stitcher.h:151-152, :167
-    const long gap = (L - (long)sections * lines_per_section) / (sections + 1);
-    const long step = gap + lines_per_section;
+    if (!d_pan1 || !d_pan2 || !out) return oip_fail(ctx, OIP_E_INVALID, "oip_stt_correlate: bad argument");
+    OIPGPU::CcdGeom g;
+    const std::string refused = OIPGPU::MakeCcdGeom(W, L, sections, lines_per_section, overlap_cols, edge_cols, &g);
+    if (!refused.empty()) return oip_fail(ctx, OIP_E_INVALID, "%s", refused.c_str());
     std::vector<int> which;
     std::vector<const uint16_t *> a, b;
     for (int s = 0; s < sections; ++s) {
-        const long off = gap + (long)s * step;
-        if (off < row0 || off + rows > row0 + nrows) continue;     // another rank's section
+        const long off = g.section_start(s);
+        if (off < row0 || off + g.rows > row0 + nrows) continue;     // another rank's section
         which.push_back(s);
-        // stitcher.h:175-176: PAN1 cols [W-ov, W-edge), PAN2 cols [edge, ov); the u16->f32
-        // conversion happens in the first FFT pass' loader
-        a.push_back(d_pan1 + (size_t)(off - row0) * W + (W - overlap_cols));
-        b.push_back(d_pan2 + (size_t)(off - row0) * W + edge_cols);
+        // the u16->f32 conversion happens in the first FFT pass' loader
+        a.push_back(d_pan1 + (size_t)(off - row0) * W + g.col1);
+        b.push_back(d_pan2 + (size_t)(off - row0) * W + g.col2);
     }
     std::vector<size_t> pitch(which.size(), (size_t)W);
     std::vector<double> r(3 * which.size() + 3);
-    int rc = stt_pairs(ctx, a.data(), pitch.data(), b.data(), pitch.data(), (int)which.size(), rows, cols, r.data());
+    int rc = stt_pairs(ctx, a.data(), pitch.data(), b.data(), pitch.data(), (int)which.size(), g.rows, g.cols, r.data());
     if (rc) return rc;
     for (int s = 0; s < sections; ++s)
         for (int k = 0; k < 3; ++k) out[3 * s + k] = NAN;
@@ -2097,54 +2091,31 @@ extern "C" int oip_interband_correlate(oip_ctx *ctx, const uint16_t *d_pan, long
                                        int slices, int sections, int corr_lines, double *out)
 {
     OIP_CHECK_CTX(ctx);
-    if (!d_pan || !d_planes || !out || W <= 0 || Lp <= 0 || corr_lines <= 0)
-        return oip_fail(ctx, OIP_E_INVALID, "oip_interband_correlate: bad argument");
-    // preproc.h:228-237
-    if (slices < OIP_IBCV_MIN_SLICES)
-        return oip_fail(ctx, OIP_E_INVALID, "CalcInterBandCorrelation: at lease %d slice needed", OIP_IBCV_MIN_SLICES);
-    if (sections <= 0) return oip_fail(ctx, OIP_E_INVALID, "CalcInterBandCorrelation: section count should be a positive integer");
-    if (sections > 1 && (long)sections * corr_lines > Lp)
-        return oip_fail(ctx, OIP_E_INVALID, "CalcInterBandCorrelation: too many sections (%d lines per section), not enough total PAN data lines", corr_lines);
-    // preproc.h:245-247, :274-276
-    const int baseRows = (int)(Lp < corr_lines ? Lp : corr_lines);
-    const long baseRowGap = (Lp - (long)baseRows * sections) / (sections + 1);
-    const int baseSliceCols = W / slices;
-    const int bandRows = baseRows / OIP_MSS_BANDS;
-    const long bandRowGap = baseRowGap / OIP_MSS_BANDS;
-    const int bandSliceCols = baseSliceCols / OIP_MSS_BANDS;
-    const int Wb = W / OIP_MSS_BANDS;
-    if (bandRows <= 0 || bandSliceCols <= 0) return oip_fail(ctx, OIP_E_INVALID, "oip_interband_correlate: slice too small");
-    const int n = slices * sections;
+    if (!d_pan || !d_planes || !out) return oip_fail(ctx, OIP_E_INVALID, "oip_interband_correlate: bad argument");
+    OIPGPU::InterBandGeom g;
+    const std::string refused = OIPGPU::MakeInterBandGeom(W, Lp, slices, sections, corr_lines, &g);
+    if (!refused.empty()) return oip_fail(ctx, OIP_E_INVALID, "%s", refused.c_str());
     std::vector<int> which;
     std::vector<IbUnit> units;
     for (int sec = 0; sec < sections; ++sec) {
-        const long secRowStart = baseRowGap + (long)sec * (baseRows + baseRowGap);        // preproc.h:257
-        const long secBandRowStart = bandRowGap + (long)sec * (bandRows + bandRowGap);    // preproc.h:284
-        if (secRowStart < prow0 || secRowStart + baseRows > prow0 + pn) continue;
-        if (secBandRowStart < mrow0 || secBandRowStart + bandRows > mrow0 + mn) continue;
+        const long p0 = g.pan_start(sec), m0 = g.mss_start(sec);
+        if (p0 < prow0 || p0 + g.base_rows > prow0 + pn) continue;
+        if (m0 < mrow0 || m0 + g.band_rows > mrow0 + mn) continue;
         for (int i = 0; i < slices; ++i) {
             which.push_back(sec * slices + i);
             IbUnit u;
-            u.pan = d_pan + (size_t)(secRowStart - prow0) * W + (size_t)i * baseSliceCols;
+            u.pan = d_pan + (size_t)(p0 - prow0) * W + (size_t)i * g.base_cols;
             u.pan_pitch = W;
             for (int b = 0; b < OIP_MSS_BANDS; ++b)
-                u.band[b] = d_planes + (size_t)b * plane_stride + (size_t)(secBandRowStart - mrow0) * Wb + (size_t)i * bandSliceCols;
-            u.band_pitch = Wb;
+                u.band[b] = d_planes + (size_t)b * plane_stride + (size_t)(m0 - mrow0) * g.Wb + (size_t)i * g.band_cols;
+            u.band_pitch = g.Wb;
             units.push_back(u);
         }
     }
     std::vector<double> r(12 * units.size() + 12);
-    int rc = interband_units(ctx, units.data(), (int)units.size(), baseRows, baseSliceCols, bandRows, bandSliceCols, r.data());
+    int rc = interband_units(ctx, units.data(), (int)units.size(), g.base_rows, g.base_cols, g.band_rows, g.band_cols, r.data());
     if (rc) return rc;
-    for (int b = 0; b < OIP_MSS_BANDS; ++b)
-        for (int u = 0; u < n; ++u) {
-            double *o = out + ((size_t)b * n + u) * 4;
-            const int i = u % slices;
-            o[0] = o[1] = o[2] = NAN;
-            o[3] = (double)(i * baseSliceCols + baseSliceCols / 2);                        // preproc.h:326
-        }
-    for (size_t j = 0; j < which.size(); ++j)
-        for (int b = 0; b < OIP_MSS_BANDS; ++b)
-            for (int k = 0; k < 3; ++k) out[((size_t)b * n + which[j]) * 4 + k] = r[12 * j + 3 * b + k];
+    OIPGPU::ShiftTableInit(g, out);
+    for (size_t j = 0; j < which.size(); ++j) OIPGPU::ShiftTablePut(g, out, which[j], &r[12 * j]);
     return OIP_OK;
 }

@@ -199,6 +199,20 @@ def test_pipelined_default_action_equals_the_step_by_step_one(tmp_path):
     r = subprocess.run([OIP, "--width", str(W), "--pan", "T_PAN.RAW", "--mss", "T_MSS.RAW", "--no-rrc4mss", "--ibc-sections", "3"], cwd=d, env=env,
                        capture_output=True, text=True)
     assert r.returncode == 2 and "too many sections" in r.stdout
+    # ... and a product that cannot be created (a directory stands where <mss>.ALIGNED.TIFF goes: opening that for writing fails
+    # for every user): the pipeline, whose reader thread and product writers are running by then, ends like the steps do -- the
+    # writer's message and exit code 2, not a signal -- and leaves nothing behind
+    sub = os.path.join(d, "unwritable")
+    os.makedirs(os.path.join(sub, "T_MSS.ALIGNED.TIFF"))
+    said = []
+    for pl in ("0", "1"):
+        r = subprocess.run([OIP, "--width", str(W), "--pan", "../T_PAN.RAW", "--mss", "../T_MSS.RAW", "--no-rrc4mss", "--ibc-sections", "1"], cwd=sub,
+                           env=dict(os.environ, LOGFILE=os.path.join(sub, "oip.log"), OIP_PIPELINE=pl), capture_output=True, text=True)
+        assert r.returncode == 2, (pl, r.returncode, r.stdout[-2000:] + r.stderr[-2000:])
+        said.append([ln[ln.index("open file ["):] for ln in r.stdout.splitlines() if "open file [" in ln and "] failed" in ln])
+        assert len(said[-1]) == 1 and "T_MSS.ALIGNED.TIFF" in said[-1][0], (pl, r.stdout[-2000:])
+        assert not os.path.exists(os.path.join(sub, "T_PAN.RRC.RAW")) and os.path.isdir(os.path.join(sub, "T_MSS.ALIGNED.TIFF"))
+    assert said[0] == said[1]
     with open(os.path.join(d, "T_MSS.RAW"), "r+b") as f:
         f.truncate(bil.nbytes - W * 2 * 4)
     r = subprocess.run([OIP, "--width", str(W), "--pan", "T_PAN.RAW", "--mss", "T_MSS.RAW", "--no-rrc4mss", "--ibc-sections", "1"], cwd=d, env=env,
