@@ -317,6 +317,13 @@ int oip_interband_correlate_units(oip_ctx *ctx, const uint16_t *const *d_pan, co
                                   const uint16_t *const *d_bands, const size_t *band_pitch, int n, int rows,
                                   int cols, double *out);
 
+/* The spectral route's peak search transforms only the lane tiles (16 or 32 columns) of a correlation surface whose
+ * column bound admits a maximum; OIP_PEAK_PRUNE=0 in the environment, read per call, searches all of
+ * them through the same kernels.  This returns how many tiles were searched and how many there were, summed over the
+ * output arrays of every correlation since the previous call, and starts the count again (either pointer may be
+ * null).  Waits for the context's stream. */
+int oip_peak_prune_stats(oip_ctx *ctx, long long *tiles_searched, long long *tiles_total);
+
 /* The x4 cubic up-sampling of cv::resize (preproc.h:302-307) along one axis as an operator on spectra -- what
  * oip_interband_correlate applies to the transforms of the band windows instead of transforming the up-sampled
  * image.  Host only.  out: 5 x (4 n) complex floats, rows H, G_0 .. G_3:

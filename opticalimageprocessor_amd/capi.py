@@ -103,6 +103,7 @@ _SIGS = {
     "oip_stt_correlate_windows": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _dp], _i),
     "oip_interband_correlate_units": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _dp], _i),
     "oip_interband_correlate": ([_vp, _vp, _l, _l, _l, _vp, _sz, _l, _l, _i, _i, _i, _i, _dp], _i),
+    "oip_peak_prune_stats": ([_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], _i),
     "oip_filter_and_fit": ([_dp, _i, _d, _i, _dp, _dp, _cp, _i], _i),
     "oip_filter_and_fit_mode": ([_dp, _i, _d, _i, _i, _dp, _dp, _cp, _i], _i),
     "oip_polyfit": ([_dp, _dp, _i, _i, _dp], _i),
@@ -773,6 +774,12 @@ class Context:
         qp = (C.c_size_t * n)(*pan_pitch); qb = (C.c_size_t * n)(*band_pitch)
         self._ck(self.lib.oip_interband_correlate_units(self.h, pp, qp, bp, qb, n, rows, cols, out.ctypes.data_as(_dp)))
         return out
+
+    def peak_prune_stats(self):
+        """(tiles searched, tiles in all) of the spectral route's peak search since the previous call; starts the count again"""
+        s, t = C.c_longlong(0), C.c_longlong(0)
+        self._ck(self.lib.oip_peak_prune_stats(self.h, C.byref(s), C.byref(t)))
+        return s.value, t.value
 
     # -- resampling
     def remap_shift_bicubic_u16(self, src, dst, W, L, dx, dy, section_rows=30000, row_guard=32767,

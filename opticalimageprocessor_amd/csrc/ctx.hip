@@ -82,6 +82,7 @@ extern "C" void oip_destroy(oip_ctx *ctx)
     for (auto &t : ctx->resize_tabs) { hipFree(t.d_xofs); hipFree(t.d_alpha); hipFree(t.d_yofs); hipFree(t.d_beta); if (t.d_xspec) hipFree(t.d_xspec); if (t.d_yspec) hipFree(t.d_yspec); }
     for (auto &p : ctx->prof_pending) { if (p.own_e0) hipEventDestroy(p.e0); hipEventDestroy(p.e1); }
     if (ctx->d_tab1d) hipFree(ctx->d_tab1d);
+    if (ctx->d_prune_stats) hipFree(ctx->d_prune_stats);
     if (ctx->d_small) hipFree(ctx->d_small);
     if (ctx->h_small) hipHostFree(ctx->h_small);
     if (ctx->d_work) hipFree(ctx->d_work);

@@ -769,6 +769,310 @@ __global__ __launch_bounds__(16 << VS) void fft_col128_peak_kernel(const float2 
     }
 }
 
+// ---- inverse column passes over a device-side list of lane tiles ------------------------------------------------
+// The peak search of the spectral correlation route transforms only the columns that can hold a surface's maximum
+// (phasecorr.hip, col_sel_first_kernel): a selection kernel leaves, per array, a list of lane tiles, and these forms of
+// the column passes walk it -- a persistent grid sized by the host, every workgroup taking the work items
+// w = blockIdx.x, + gridDim.x, ... of all (up to four) arrays of the launch.  An item is (list entry, row block r), the
+// entries of one row block being neighbours as the lane tiles of the array-sized grids are; r = o2 * O1 + o1.  The
+// arithmetic of a tile is that of the array-sized kernels, statement for statement: the same tile gives the same bits.
+__device__ __forceinline__ int list_counts(const OipColList &L, int (&c)[4])
+{
+    int E = 0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) { c[a] = a < L.narr ? oip_sload_i32(L.count, a) : 0; E += c[a]; }
+    return E;
+}
+__device__ __forceinline__ void list_item(const OipColList &L, const int (&c)[4], int E, int w, int *a, int *lt, int *r)
+{
+    *r = w / E;
+    int e = w - *r * E, aa = 0;
+    while (aa < 3 && e >= c[aa]) { e -= c[aa]; ++aa; }
+    *a = aa;
+    *lt = oip_sload_i32(L.tiles, (long)aa * L.stride + e);
+}
+__device__ __forceinline__ Tile list_tile(const OipFftPass &p, int lt, int r)
+{
+    Tile t;
+    const int V = 1 << p.vshift;
+    t.o1 = r % p.O1;
+    t.o2 = r / p.O1;
+    t.gtile = (long)r * p.lane_tiles + lt;                  // as decode_tile numbers them
+    t.lane0 = lt << p.vshift;
+    t.nv = p.lanes - t.lane0 < V ? (int)(p.lanes - t.lane0) : V;
+    t.base = (long)t.o2 * p.o2_stride + (long)t.o1 * p.o1_stride + t.lane0;
+    t.vec0 = 0;
+    return t;
+}
+
+// fft_pass_kernel (run-time radices) over a list; peak: the pass leaves per-tile maxima (store_peak) instead of the array
+__global__ __launch_bounds__(kFftBlock) void col_list_pass_kernel(OipColList L, OipFftPass p, int peak, const float2 *__restrict__ twF,
+                                                                  const float2 *__restrict__ twT)
+{
+    extern __shared__ float2 smem[];
+    __shared__ float sval[kFftBlock];
+    __shared__ long skey[kFftBlock];
+    const int F = p.F;
+    const int V = 1 << p.vshift;
+    const int Vp = p.Vp;
+    float2 *tw = smem + 2 * F * Vp;
+    int c[4];
+    const int E = list_counts(L, c);
+    if (E <= 0) return;
+    const int total = E * p.O1 * p.O2;
+    for (int i = threadIdx.x; i < F; i += kFftBlock) tw[i] = twF[i];
+    const int elems = F << p.vshift;
+    for (int w = blockIdx.x; w < total; w += gridDim.x) {
+        int a, lt, r;
+        list_item(L, c, E, w, &a, &lt, &r);
+        const Tile t = list_tile(p, lt, r);
+        float2 *__restrict__ data = L.data[a];
+        float2 *bufA = smem;
+        float2 *bufB = smem + F * Vp;
+        for (int e = threadIdx.x; e < elems; e += kFftBlock) {
+            const int v = e & (V - 1), n = e >> p.vshift;
+            float2 z = make_float2(0.f, 0.f);
+            if (v < t.nv) {
+                z = data[t.base + (long)n * p.nstride + v];
+                z.y = -z.y;
+                if (p.tw_mode) z = cmul(z, twT[(long)(p.tw_mode == 1 ? t.lane0 + v : t.o1) * n]);
+            }
+            bufA[n * Vp + v] = z;
+        }
+        __syncthreads();
+        int Ns = 1;
+        for (int s = 0; s < p.nradix; ++s) {
+            const int rx = p.radix[s];
+            if (rx == 4) stockham_stage<4>(bufA, bufB, tw, F, Ns, p.vshift, Vp);
+            else if (rx == 5) stockham_stage<5>(bufA, bufB, tw, F, Ns, p.vshift, Vp);
+            else if (rx == 2) stockham_stage<2>(bufA, bufB, tw, F, Ns, p.vshift, Vp);
+            else if (rx == 8) stockham_stage<8>(bufA, bufB, tw, F, Ns, p.vshift, Vp);
+            else stockham_stage<3>(bufA, bufB, tw, F, Ns, p.vshift, Vp);
+            __syncthreads();
+            float2 *tmp = bufA; bufA = bufB; bufB = tmp;
+            Ns *= rx;
+        }
+        if (peak) {
+            OipFftIo io;
+            io.slots = L.slots + (long)a * 2 * kPeakSlots;
+            store_peak(bufA, Vp, p, io, t, sval, skey, t.gtile);
+        } else {
+            for (int e = threadIdx.x; e < elems; e += kFftBlock) {
+                const int v = e & (V - 1), n = e >> p.vshift;
+                if (v >= t.nv) continue;
+                float2 z = bufA[n * Vp + v];
+                z.y = -z.y;
+                data[t.base + (long)n * p.nstride + v] = z;
+            }
+        }
+        __syncthreads();                // the next item's commit overwrites the tile and the reduction scratch
+    }
+}
+
+// fft_pass_ct_kernel (mode 0, inverse, IOK 0 or 2) over a list
+template <int F, int VS, int NT, bool PEAK, int... Rs>
+__global__ __launch_bounds__(NT) void col_list_ct_kernel(OipColList L, OipFftPass p, const float2 *__restrict__ twF,
+                                                         const float2 *__restrict__ twT)
+{
+    constexpr int V = 1 << VS;
+    constexpr int Vp = VS > 1 ? V + 1 : V;
+    constexpr int TWN = TwTable<F, Rs...>::value();
+    constexpr int TOTAL = F << VS;
+    constexpr int NLD = (TOTAL + NT - 1) / NT;
+    __shared__ float2 buf[F * Vp];
+    __shared__ float2 tw[TWN];
+    __shared__ float2 twj[F];
+    static_assert(sizeof(float2) * F * Vp >= NT * 12 + 16, "tile too small to host the reduction scratch");
+    int c[4];
+    const int E = list_counts(L, c);
+    if (E <= 0) return;
+    const int total = E * p.O1 * p.O2;
+    const bool tile_tw = p.tw_mode == 2;
+    for (int i = threadIdx.x; i < TWN; i += NT) tw[i] = twF[i];
+    for (int w = blockIdx.x; w < total; w += gridDim.x) {
+        int a, lt, r;
+        list_item(L, c, E, w, &a, &lt, &r);
+        const Tile t = list_tile(p, lt, r);
+        float2 *__restrict__ data = L.data[a];
+        float2 zz[NLD];
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int e = threadIdx.x + i * NT;
+            const int v = e & (V - 1), n = e >> VS;
+            zz[i] = make_float2(0.f, 0.f);
+            if ((TOTAL % NT == 0 || e < TOTAL) && v < t.nv) zz[i] = data[t.base + (long)n * p.nstride + v];
+        }
+        if (tile_tw) {
+            for (int i = threadIdx.x; i < F; i += NT) twj[i] = twT[(long)t.o1 * i];
+            __syncthreads();
+        }
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int e = threadIdx.x + i * NT;
+            const int v = e & (V - 1), n = e >> VS;
+            if (TOTAL % NT == 0 || e < TOTAL) {
+                float2 z = zz[i];
+                if (v < t.nv) {
+                    z.y = -z.y;
+                    if (tile_tw) z = cmul(z, twj[n]);
+                    else if (p.tw_mode == 1) z = cmul(z, twT[(long)(t.lane0 + v) * n]);
+                }
+                buf[n * Vp + v] = z;
+            }
+        }
+        __syncthreads();
+        Stages<F, VS, Vp, NT, 1, Rs...>::run(buf, tw);
+        if (PEAK) {
+            OipFftIo io;
+            io.slots = L.slots + (long)a * 2 * kPeakSlots;
+            store_peak(buf, Vp, p, io, t, reinterpret_cast<float *>(buf + NT), reinterpret_cast<long *>(buf), t.gtile, NT);
+        } else {
+            for (int e = threadIdx.x; e < TOTAL; e += NT) {
+                const int v = e & (V - 1), n = e >> VS;
+                if (v >= t.nv) continue;
+                float2 z = buf[n * Vp + v];
+                z.y = -z.y;
+                data[t.base + (long)n * p.nstride + v] = z;
+            }
+        }
+        __syncthreads();                // the next item's commit overwrites the tile, twj and the reduction scratch
+    }
+}
+
+// fft_col128_peak_kernel over a list: an item is (list entry, tile row o1); the loads of the next item are in flight under
+// the later stages of the current one
+__global__ __launch_bounds__(256) void col_list_peak128_kernel(OipColList L, OipFftPass p, const float2 *__restrict__ twF,
+                                                               const float2 *__restrict__ twT)
+{
+    constexpr int VS = 4, F = 128, V = 1 << VS, Vp = V + 1;
+    __shared__ float2 buf[F * Vp];
+    __shared__ float2 tw[96];
+    __shared__ float2 twj[F];
+    int c[4];
+    const int E = list_counts(L, c);
+    if (E <= 0) return;
+    const int total = E * p.O1;
+    int w = blockIdx.x;
+    if (w >= total) return;
+    const int v = threadIdx.x & (V - 1);
+    const long none = (long)p.M * p.N;
+    const int ym = p.M >> 1, xm = p.N >> 1;
+    int a, lt, o1;
+    list_item(L, c, E, w, &a, &lt, &o1);
+    float2 x[8];
+    float2 rtw = make_float2(1.f, 0.f);
+    auto fetch = [&](int fa, int flt, int o, int tid) {
+        const int lane0 = flt << VS;
+        const int nv = p.lanes - lane0 < V ? (int)(p.lanes - lane0) : V;
+        const int vc = v < nv ? v : nv - 1;
+        const unsigned voff = (unsigned)((tid >> VS) * (int)p.nstride + lane0 + vc) * 8u;
+        const char *tb = reinterpret_cast<const char *>(L.data[fa]) + (long)o * p.o1_stride * 8;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) x[m] = *reinterpret_cast<const float2 *>(tb + (long)m * 16 * p.nstride * 8 + voff);
+        if (tid < F) rtw = *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(twT) + (unsigned)(o * F + tid) * 8u);
+    };
+    auto stage1 = [&](int tid) {
+        const int qq = tid >> VS;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) x[m] = cmul(make_float2(x[m].x, -x[m].y), twj[qq + 16 * m]);
+        bf8(x);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) buf[(qq * 8 + m) * Vp + v] = x[m];
+    };
+    fetch(a, lt, o1, threadIdx.x);
+    if (threadIdx.x < 96) tw[threadIdx.x] = twF[threadIdx.x];
+    if (threadIdx.x < F) twj[threadIdx.x] = rtw;
+    __syncthreads();
+    stage1(threadIdx.x);
+    __syncthreads();
+    for (;;) {
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const int qq = tid >> VS;
+        const int wn = w + gridDim.x;
+        const bool more = wn < total;
+        int an = a, ltn = lt, o1n = o1;
+        if (more) {
+            list_item(L, c, E, wn, &an, &ltn, &o1n);
+            fetch(an, ltn, o1n, tid);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        float2 y[2][4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int b = qq + 16 * i;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) y[i][m] = buf[(b + 32 * m) * Vp + v];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int b = qq + 16 * i, k = b & 7;
+            const float2 w1 = tw[k * 4], w2 = tw[k * 8], w3 = tw[k * 12];
+            y[i][1] = cmul(y[i][1], w1);
+            y[i][2] = cmul(y[i][2], w2);
+            y[i][3] = cmul(y[i][3], w3);
+            bf4(y[i]);
+            const int j0 = (b - k) * 4 + k;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) buf[(j0 + 8 * m) * Vp + v] = y[i][m];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int b = qq + 16 * i;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) y[i][m] = buf[(b + 32 * m) * Vp + v];
+            const float2 w1 = tw[b], w2 = tw[2 * b], w3 = tw[3 * b];
+            y[i][1] = cmul(y[i][1], w1);
+            y[i][2] = cmul(y[i][2], w2);
+            y[i][3] = cmul(y[i][3], w3);
+            bf4(y[i]);
+        }
+        // arg-max in fftShift-ed scan order, as in fft_col128_peak_kernel
+        float bv0 = -INFINITY, bv1 = -INFINITY;
+        int bn0 = -1, bn1 = -1;
+#pragma unroll
+        for (int s2 = 0; s2 < 8; ++s2) {
+            const int i = s2 & 1, m = ((s2 >> 1) + 2) & 3;
+            const int n = qq + 16 * i + 32 * m;
+            const float re = y[i][m].x, im = -y[i][m].y;
+            if (re > bv0) { bv0 = re; bn0 = n; }
+            if (im > bv1) { bv1 = im; bn1 = n; }
+        }
+        const int lane0 = lt << VS;
+        const bool lane_ok = lane0 + v < p.lanes;
+        if (!lane_ok) { bv0 = bv1 = -INFINITY; bn0 = bn1 = -1; }
+        const long gtile = (long)o1 * p.lane_tiles + lt;
+        const int slot = (int)(gtile & (kPeakSlots - 1));
+        unsigned long long *slots = L.slots + (long)a * 2 * kPeakSlots;
+#pragma unroll
+        for (int part = 0; part < 2; ++part) {
+            const float mine = part ? bv1 : bv0;
+            const int bn = part ? bn1 : bn0;
+            const float wmax = wave_max_f32(mine);
+            const bool holder = mine == wmax && (mine > -INFINITY || (tid & 63) == 0);
+            if (holder) {
+                long key = none;
+                if (bn >= 0 && lane_ok) {
+                    int ys = o1 + bn * p.S + ym; if (ys >= p.M) ys -= p.M;
+                    int xs = lane0 + v + xm; if (xs >= p.N) xs -= p.N;
+                    key = (long)ys * p.N + xs;
+                }
+                const unsigned long long packed = oip_peak_pack(mine, key);
+                if (packed) atomicMax(&slots[part * kPeakSlots + slot], packed);
+            }
+        }
+        if (!more) break;
+        __syncthreads();
+        if (tid < F) twj[tid] = rtw;
+        __syncthreads();
+        stage1(tid);
+        __syncthreads();
+        w = wn; a = an; lt = ltn; o1 = o1n;
+    }
+}
+
 // ---- first forward column pass with fused x4 up-sampling: persistent over rows, register prefetch ----
 // The generic fused loader above spends most of its time waiting: a tile's source rows are S rows apart
 // (a DRAM page and a TLB entry each), eight workgroups per CU are all the LDS allows, and each of them
@@ -999,17 +1303,18 @@ const FirstUpKernel kFirstUp[] = {
 struct FastKernel {
     int F, vshift, mode, threads;
     void (*fn[3])(float2 *, OipFftPass, OipFftIo, const float2 *, const float2 *);         // by IOK: plain, fused load, fused store
+    void (*list[2])(OipColList, OipFftPass, const float2 *, const float2 *);               // column passes over a tile list: plain, peak
 };
 const FastKernel kFast[] = {
     // column passes of 16000 = 125 * 128 (and other 5^3 / 2^7 factors): 16 lanes = 128-byte
     // segments, 17 KiB of LDS per workgroup -> 8 workgroups per CU (measured faster than 32 lanes)
-    {125, 4, 0, 256, {fft_pass_ct_kernel<125, 4, 0, 256, 0, 5, 5, 5>, fft_pass_ct_kernel<125, 4, 0, 256, 1, 5, 5, 5>, fft_pass_ct_kernel<125, 4, 0, 256, 2, 5, 5, 5>}},
-    {128, 4, 0, 256, {fft_pass_ct_kernel<128, 4, 0, 256, 0, 8, 4, 4>, fft_pass_ct_kernel<128, 4, 0, 256, 1, 8, 4, 4>, fft_pass_ct_kernel<128, 4, 0, 256, 2, 8, 4, 4>}},
-    {100, 4, 0, 256, {fft_pass_ct_kernel<100, 4, 0, 256, 0, 4, 5, 5>, fft_pass_ct_kernel<100, 4, 0, 256, 1, 4, 5, 5>, fft_pass_ct_kernel<100, 4, 0, 256, 2, 4, 5, 5>}},
-    {160, 4, 0, 256, {fft_pass_ct_kernel<160, 4, 0, 256, 0, 4, 8, 5>, fft_pass_ct_kernel<160, 4, 0, 256, 1, 4, 8, 5>, fft_pass_ct_kernel<160, 4, 0, 256, 2, 4, 8, 5>}},
-    {64, 5, 0, 256, {fft_pass_ct_kernel<64, 5, 0, 256, 0, 4, 4, 4>, fft_pass_ct_kernel<64, 5, 0, 256, 1, 4, 4, 4>, fft_pass_ct_kernel<64, 5, 0, 256, 2, 4, 4, 4>}},
+    {125, 4, 0, 256, {fft_pass_ct_kernel<125, 4, 0, 256, 0, 5, 5, 5>, fft_pass_ct_kernel<125, 4, 0, 256, 1, 5, 5, 5>, fft_pass_ct_kernel<125, 4, 0, 256, 2, 5, 5, 5>}, {col_list_ct_kernel<125, 4, 256, false, 5, 5, 5>, col_list_ct_kernel<125, 4, 256, true, 5, 5, 5>}},
+    {128, 4, 0, 256, {fft_pass_ct_kernel<128, 4, 0, 256, 0, 8, 4, 4>, fft_pass_ct_kernel<128, 4, 0, 256, 1, 8, 4, 4>, fft_pass_ct_kernel<128, 4, 0, 256, 2, 8, 4, 4>}, {col_list_ct_kernel<128, 4, 256, false, 8, 4, 4>, col_list_ct_kernel<128, 4, 256, true, 8, 4, 4>}},
+    {100, 4, 0, 256, {fft_pass_ct_kernel<100, 4, 0, 256, 0, 4, 5, 5>, fft_pass_ct_kernel<100, 4, 0, 256, 1, 4, 5, 5>, fft_pass_ct_kernel<100, 4, 0, 256, 2, 4, 5, 5>}, {col_list_ct_kernel<100, 4, 256, false, 4, 5, 5>, col_list_ct_kernel<100, 4, 256, true, 4, 5, 5>}},
+    {160, 4, 0, 256, {fft_pass_ct_kernel<160, 4, 0, 256, 0, 4, 8, 5>, fft_pass_ct_kernel<160, 4, 0, 256, 1, 4, 8, 5>, fft_pass_ct_kernel<160, 4, 0, 256, 2, 4, 8, 5>}, {col_list_ct_kernel<160, 4, 256, false, 4, 8, 5>, col_list_ct_kernel<160, 4, 256, true, 4, 8, 5>}},
+    {64, 5, 0, 256, {fft_pass_ct_kernel<64, 5, 0, 256, 0, 4, 4, 4>, fft_pass_ct_kernel<64, 5, 0, 256, 1, 4, 4, 4>, fft_pass_ct_kernel<64, 5, 0, 256, 2, 4, 4, 4>}, {col_list_ct_kernel<64, 5, 256, false, 4, 4, 4>, col_list_ct_kernel<64, 5, 256, true, 4, 4, 4>}},
     // 4000 = 32 * 125: the column transform of the band windows themselves (a quarter of the correlation lines)
-    {32, 5, 0, 256, {fft_pass_ct_kernel<32, 5, 0, 256, 0, 8, 4>, fft_pass_ct_kernel<32, 5, 0, 256, 1, 8, 4>, fft_pass_ct_kernel<32, 5, 0, 256, 2, 8, 4>}},
+    {32, 5, 0, 256, {fft_pass_ct_kernel<32, 5, 0, 256, 0, 8, 4>, fft_pass_ct_kernel<32, 5, 0, 256, 1, 8, 4>, fft_pass_ct_kernel<32, 5, 0, 256, 2, 8, 4>}, {col_list_ct_kernel<32, 5, 256, false, 8, 4>, col_list_ct_kernel<32, 5, 256, true, 8, 4>}},
     // row passes: 30000/10, 12288/10 -> 1250, the 200-column stitch overlap
     {3000, 1, 1, 512, {fft_pass_ct_kernel<3000, 1, 1, 512, 0, 3, 8, 5, 5, 5>, fft_pass_ct_kernel<3000, 1, 1, 512, 1, 3, 8, 5, 5, 5>, fft_pass_ct_kernel<3000, 1, 1, 512, 2, 3, 8, 5, 5, 5>}},
     {1250, 1, 1, 256, {fft_pass_ct_kernel<1250, 1, 1, 256, 0, 2, 5, 5, 5, 5>, fft_pass_ct_kernel<1250, 1, 1, 256, 1, 2, 5, 5, 5, 5>, fft_pass_ct_kernel<1250, 1, 1, 256, 2, 2, 5, 5, 5, 5>}},
@@ -1362,6 +1667,50 @@ int oip_fft2d_exec(oip_ctx *ctx, const OipFft2dPlan *pl, float2 *data, int inver
         int rc = launch_pass(ctx, data, pl->passes[i], inverse ? 1 : 0, i == 0 ? first : plain);
         if (rc) return rc;
     }
+    return OIP_OK;
+}
+
+// The list forms take a plan whose column passes all work on lane tiles of one width (the list names tiles of that
+// width) and whose work items fit an int.
+bool oip_fft_col_list_ok(const OipFft2dPlan *pl, int narr)
+{
+    if (pl->n_y < 1) return false;
+    for (int i = 0; i < pl->n_y; ++i) {
+        const OipFftPass &p = pl->passes[i];
+        if (p.mode != 0 || p.axis != 1 || p.vshift != pl->passes[0].vshift || p.tw_mode == 1) return false;
+        if ((long)narr * p.lane_tiles * p.O1 * p.O2 > 0x7fffffffL) return false;
+    }
+    return pl->passes[0].O2 == 1;       // the last inverse pass spans the whole axis
+}
+
+// Inverse column pass `pass` (index in forward order; 0 is the last one of the inverse) of the arrays of `list` over
+// its tile lists; peak: only per-tile maxima are left, in list.slots.  `name` is the profiler's name of the launch.
+int oip_fft_col_list_pass(oip_ctx *ctx, const OipFft2dPlan *pl, int pass, const OipColList &list, bool peak, const char *name)
+{
+    if (pass < 0 || pass >= pl->n_y || (peak && pass != 0) || !oip_fft_col_list_ok(pl, list.narr))
+        return oip_fail(ctx, OIP_E_RUNTIME, "column list pass: unsupported plan or pass");
+    OipFftPass p = pl->passes[pass];
+    p.inverse = 1;
+    const float2 *twF = nullptr, *twT = nullptr, *twR = nullptr;
+    int rc = get_table(ctx, p.F, &twF);
+    if (rc) return rc;
+    if (p.tw_mode) { rc = get_table(ctx, p.T, &twT); if (rc) return rc; }
+    const long items = (long)list.narr * p.lane_tiles * p.O1 * p.O2;        // with full lists
+    long grid = (long)ctx->cu_count * 8;            // 17 KiB of LDS per workgroup: eight per CU
+    if (grid > items) grid = items;
+    if (grid < 1) grid = 1;
+    OipProfScope prof(ctx, name);
+    if (peak && p.F == 128 && p.vshift == 4 && p.tw_mode == 2 && (16 * p.nstride + p.lanes) * 8 < (1L << 31) &&
+        p.T % p.F == 0 && p.O1 == p.T / p.F && (long)p.T * 8 <= (16L << 20)) {
+        if ((rc = get_pass_table(ctx, p.T, p.F, &twR))) return rc;
+        hipLaunchKernelGGL(col_list_peak128_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, list, p, twF, twR);
+    } else if (p.fast >= 0 && kFast[p.fast].list[peak ? 1 : 0]) {
+        hipLaunchKernelGGL(kFast[p.fast].list[peak ? 1 : 0], dim3((unsigned)grid), dim3(kFast[p.fast].threads), 0, ctx->stream, list, p, twF, twT);
+    } else {
+        const size_t lds = sizeof(float2) * ((size_t)2 * p.F * p.Vp + p.F);
+        hipLaunchKernelGGL(col_list_pass_kernel, dim3((unsigned)grid), dim3(kFftBlock), lds, ctx->stream, list, p, peak ? 1 : 0, twF, twT);
+    }
+    OIP_HIP(ctx, hipGetLastError());
     return OIP_OK;
 }
 

@@ -94,6 +94,20 @@ int oip_fft2d_plan(oip_ctx *ctx, int M, int N, const OipFft2dPlan **out);
 int oip_fft2d_exec(oip_ctx *ctx, const OipFft2dPlan *plan, float2 *data, int inverse, const OipFftIo *io, int rows_done = 0);
 int oip_fft_table(oip_ctx *ctx, int T, const float2 **out);     // exp(-2 pi i t / T), t in [0, T)
 
+// Inverse column passes over device-side lists of lane tiles (fft.hip): up to four arrays of one plan per launch, array a
+// with count[a] entries tiles[a * stride + j], each a lane tile of the plan's column passes.  Every listed tile is
+// transformed in place once per call -- the lists of a call must not name a tile twice.
+struct OipColList {
+    float2 *data[4];
+    const int *count;               // device, [4]
+    const int *tiles;               // device, [4][stride]
+    int stride;
+    int narr;
+    unsigned long long *slots;      // peak pass: [4][2][kPeakSlots] arg-max slots, array a at slots + a * 2 * kPeakSlots
+};
+bool oip_fft_col_list_ok(const OipFft2dPlan *plan, int narr);
+int oip_fft_col_list_pass(oip_ctx *ctx, const OipFft2dPlan *plan, int pass, const OipColList &list, bool peak, const char *name);
+
 // position <-> frequency of one axis after the forward transform.  With factors
 // (F1, F2, ..) position p = k1*(F2*F3..) + k2*(F3..) + .. holds frequency
 // k = k1 + F1*(k2 + F2*(k3 ..)).

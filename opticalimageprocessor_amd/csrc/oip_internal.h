@@ -79,6 +79,7 @@ struct oip_ctx {
 
     oip_fft_state *fft = nullptr;
     std::vector<OipResizeTab> resize_tabs;
+    unsigned long long *d_prune_stats = nullptr;   // device: lane tiles searched / in all by the correlation's peak search (oip_peak_prune_stats)
 
     // profiling
     bool prof_on = false;

@@ -557,6 +557,10 @@ struct UpRowsJob {
     const uint2 *raw16;     // [4 rows][4 arrays x n / 2]: (bX | bY << 16) of two neighbouring points
     const int *ypos_s;      // row position of frequency line k in zn, k in [0, m)
     int m;
+    // Column bounds for the peak search (col_sel_first_kernel): workgroup g leaves sum |Re| + |Im| of everything it
+    // stored in column x of output o at bound[(g * 4 + o) * P + x], zero before the launch.  A thread owns its columns for
+    // the whole launch, so an element is the private accumulator of one thread (no sum depends on an order between threads).
+    float *bound;
 };
 
 // conj(a) b, acc + a b, acc + conj(a) b on packed-f32 instructions (two each; operand selection as in oipfft::cmul).
@@ -723,6 +727,7 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
     long s1 = n1, s2 = n2;
     __syncthreads();
     bool first = true;
+    char *const brow = reinterpret_cast<char *>(fj.bound + (long)blockIdx.x * 4 * P);
     for (; ky <= half; ky += gridDim.x) {
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
@@ -839,11 +844,38 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
                 for (int it = 0; it < NIT2; ++it) line_pair_store<F>(out, s1 * P, s2 * P, pair, ya[o][it], yb[o][it], tid + it * NT);
             }
         };
+        // Column bounds: |Re| + |Im| of what store(o0) has just written is added to the workgroup's rows with the
+        // hardware's f32 add (no value comes back: nothing to wait for, no register held).  Every address has one writer,
+        // this thread, so the order of the additions is the order of the line pairs: the sums are the same bits every run.
+        // (Read-add-write through registers was measured: the 12 registers of a round's sums spill three of the prefetched
+        // lines, whose reload waits for the prefetch -- 1.16 -> 1.38 ms per launch; this form runs at 1.19.)
+        auto bound_add = [&](int o0) {
+            int tb = tid;
+            asm volatile("" : "+v"(tb));            // addresses formed here, not carried through the iteration
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+#pragma unroll
+                for (int it = 0; it < NIT2; ++it) {
+                    const int q = tb + it * NT;
+                    if (q < F / 2) {
+                        const float4 a = ya[o][it], b = yb[o][it];
+                        float2 s = make_float2(fabsf(a.x) + fabsf(a.y), fabsf(a.z) + fabsf(a.w));
+                        if (pair) { s.x += fabsf(b.x) + fabsf(b.y); s.y += fabsf(b.z) + fabsf(b.w); }     // an unpaired line counts once
+                        // (uniform base + 32-bit byte offset: no 64-bit address arithmetic per element)
+                        float *bp = reinterpret_cast<float *>(brow + (unsigned)((o0 + o) * P + 2 * q) * 4u);
+                        unsafeAtomicAdd(bp, s.x);
+                        unsafeAtomicAdd(bp + 1, s.y);
+                    }
+                }
+            }
+        };
         xround(0, Aa);
         finish();
         if (fj.nout == 4) load_tables(tid);
         __builtin_amdgcn_sched_barrier(0);
         store(0);
+        __builtin_amdgcn_sched_barrier(0);
+        bound_add(0);
         if (fj.nout == 4) xround(2, Ab);
         __builtin_amdgcn_sched_barrier(0);
         // The lines of the NEXT pair are requested here -- after the last consumer of anything the compiler may have
@@ -865,7 +897,11 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
         __builtin_amdgcn_sched_barrier(0);
         if (more) load_tables(tid);             // ahead of the stores: waiting for them then waits for nothing younger
         __builtin_amdgcn_sched_barrier(0);
-        if (fj.nout == 4) store(2);
+        if (fj.nout == 4) {
+            store(2);
+            __builtin_amdgcn_sched_barrier(0);
+            bound_add(2);
+        }
         s1 = n1; s2 = n2;
         __syncthreads();
     }
@@ -1221,8 +1257,176 @@ OipAxisDigits digits_of(const std::vector<int> &f, int L)
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline bool smooth_len(long n) { for (int p : {2, 3, 5}) while (n % p == 0) n /= p; return n == 1; }
 
+// ---- peak search of the spectral route: which lane tiles can hold a surface's maximum -------------------------------
+// After the inverse row transform an output array Y~(ky, x) holds two real surfaces, y = c1 + i c2, and the inverse
+// column transform is y(n, x) = sum_ky Y~(ky, x) u(ky, n) with |u| = 1 (stage and inter-pass twiddles alike), so
+//     |c1(n, x)|, |c2(n, x)|  <=  |y(n, x)|  <=  B(x) := sum_ky |Re Y~(ky, x)| + |Im Y~(ky, x)|       for every n.
+// A column whose B(x) lies below a surface value already found cannot hold that surface's maximum.  The row stage sums
+// B per workgroup (UpRowsJob::bound); col_sel_first_kernel adds the workgroups' rows in a fixed order, takes the maximum
+// Bt over each lane tile of the column passes and has the tile with the largest Bt searched (its column passes run on
+// it and on its two neighbours, wrapping in x: the 5 x 5 window around a peak reads two columns beyond it).  With the
+// candidates m1, m2 of the two surfaces then in the arg-max slots, col_sel_second_kernel has every other tile searched
+// unless Bt (1 + eps) < min(m1, m2) -- written so that a NaN anywhere means "search".  One round is enough: the true
+// maximum is at least the candidate, so what stays unsearched is strictly below it and cannot even tie.  A unit with a
+// real peak is searched in a handful of tiles (B is of the order M sqrt(N) where the peak is M N times the response);
+// without one B exceeds every surface value and all tiles are searched, as before.
+// eps = 2^-8: the f32 sum of n = 16000 non-negative terms is off by at most (n - 1) 2^-24 = 9.5e-4 of its value, and the
+// f32 transform's own error is about 1e-5 of sum |x|; 2^-8 = 3.9e-3 covers both four times over and costs nothing, the
+// bound sitting 3 to 20 times below a usable peak.
+constexpr float kPruneMargin = 0x1p-8f;
+constexpr int kSelThreads = 1024, kSelCols = 64, kSelParts = kSelThreads / kSelCols, kSelMaxTiles = 1024;
+struct PruneWork {
+    float *bound;       // [row-stage workgroups][4][P]: the row stage's partial column sums
+    int groups;         // workgroups of the row stage
+    float *bt;          // [4][T]
+    int *flags;         // [4][T]: bit 0 column passes done, bit 1 searched
+    int *count;         // [2 phases][2: column passes, peak pass][4]
+    int *tiles;         // [2][2][4][T]; null: the plan has no list form (the exhaustive passes run)
+    int *ticket;        // [4]: workgroups of col_sel_first_kernel that are done with an array; zero between launches
+    int T, vshift;      // lane tiles of the column passes and log2 of their width
+};
+
+// grid (ceil(N / kSelCols), arrays): a workgroup sums kSelCols columns -- thread (x, j) the rows j, j + kSelParts, ... of
+// column x, thread (x, 0) the kSelParts partial sums, both in a fixed order -- and leaves the maxima of their tiles; the
+// workgroup of an array that finishes last (a ticket) picks the tile and writes the first lists.
+__global__ __launch_bounds__(kSelThreads) void col_sel_first_kernel(PruneWork pw, int P, int N, int full)
+{
+    __shared__ float sPart[kSelParts][kSelCols];
+    __shared__ float sBt[kSelMaxTiles];
+    __shared__ int sbest;
+    const int a = blockIdx.y, T = pw.T, V = 1 << pw.vshift;
+    const int xl = threadIdx.x & (kSelCols - 1), j = threadIdx.x / kSelCols, x0 = blockIdx.x * kSelCols;
+    {
+        const int x = x0 + xl < N ? x0 + xl : N - 1;
+        const float *p = pw.bound + (long)a * P + x;
+        float s = 0.f;
+#pragma unroll 8
+        for (int g = j; g < pw.groups; g += kSelParts) s += p[(long)g * 4 * P];
+        sPart[j][xl] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < kSelCols) {
+        float s = sPart[0][xl];
+        for (int k = 1; k < kSelParts; ++k) s += sPart[k][xl];
+        sPart[0][xl] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < kSelCols / V) {
+        const int t = x0 / V + threadIdx.x;
+        if (t < T) {
+            float m = 0.f;
+            bool bad = false;
+            for (int x = t * V; x < (t + 1) * V && x < N; ++x) { const float b = sPart[0][x - x0]; bad = bad || b != b; m = fmaxf(m, b); }
+            pw.bt[a * T + t] = bad ? NAN : m;
+        }
+        __threadfence();
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) sbest = atomicAdd(&pw.ticket[a], 1) == (int)gridDim.x - 1 ? 1 : 0;
+    __syncthreads();
+    if (!sbest) return;
+    __syncthreads();
+    __threadfence();                                    // the other workgroups' maxima, written before their tickets
+    for (int t = threadIdx.x; t < T; t += kSelThreads) sBt[t] = __builtin_nontemporal_load(pw.bt + a * T + t);
+    if (threadIdx.x == 0) pw.ticket[a] = 0;             // for the next launch
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float bv = -1.f;        // Bt >= 0; a NaN never wins
+        int bi = 0;
+        for (int t = threadIdx.x; t < T; t += 64)
+            if (sBt[t] > bv) { bv = sBt[t]; bi = t; }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_xor(bv, off, 64);
+            const int oi = __shfl_xor(bi, off, 64);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if (threadIdx.x == 0) sbest = bi;
+    }
+    __syncthreads();
+    const int tm = sbest, tp = tm ? tm - 1 : T - 1, tn = tm + 1 < T ? tm + 1 : 0;
+    int *listA = pw.tiles + (long)(0 * 4 + a) * T, *listP = pw.tiles + (long)(1 * 4 + a) * T;
+    for (int t = threadIdx.x; t < T; t += kSelThreads) {
+        pw.flags[a * T + t] = full ? 3 : (t == tm ? 3 : (t == tp || t == tn ? 1 : 0));
+        if (full) { listA[t] = t; listP[t] = t; }
+    }
+    if (threadIdx.x == 0) {
+        int nA = T, nP = T;
+        if (!full) {
+            listP[0] = tm;
+            nP = 1;
+            nA = 0;
+            listA[nA++] = tm;
+            if (tp != tm) listA[nA++] = tp;
+            if (tn != tm && tn != tp) listA[nA++] = tn;
+        }
+        pw.count[0 * 4 + a] = nA;
+        pw.count[1 * 4 + a] = nP;
+        pw.count[2 * 4 + a] = 0;
+        pw.count[3 * 4 + a] = 0;
+    }
+}
+
+__device__ __forceinline__ float peak_slot_value(unsigned long long packed)        // oip_peak_pack's value; empty: -inf
+{
+    if (!packed) return -INFINITY;
+    unsigned u = (unsigned)(packed >> 32);
+    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    return __uint_as_float(u);
+}
+
+// stats[0] += tiles searched, stats[1] += tiles (per array): oip_peak_prune_stats
+__global__ __launch_bounds__(kPeakSlots) void col_sel_second_kernel(PruneWork pw, const unsigned long long *__restrict__ slots,
+                                                                   unsigned long long *__restrict__ stats)
+{
+    constexpr int NW = kPeakSlots / 64;
+    __shared__ unsigned long long sb[2][NW];
+    __shared__ int sflag[kSelMaxTiles];
+    __shared__ int nA, nP;
+    const int a = blockIdx.x, T = pw.T;
+    const unsigned long long *s = slots + (long)a * 2 * kPeakSlots;
+    unsigned long long b0 = s[threadIdx.x], b1 = s[kPeakSlots + threadIdx.x];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o0 = __shfl_xor(b0, off, 64), o1 = __shfl_xor(b1, off, 64);
+        b0 = o0 > b0 ? o0 : b0;
+        b1 = o1 > b1 ? o1 : b1;
+    }
+    if ((threadIdx.x & 63) == 0) { sb[0][threadIdx.x >> 6] = b0; sb[1][threadIdx.x >> 6] = b1; }
+    if (threadIdx.x == 0) { nA = 0; nP = 0; }
+    for (int t = threadIdx.x; t < T; t += kPeakSlots) sflag[t] = pw.flags[a * T + t];
+    __syncthreads();
+    b0 = sb[0][0]; b1 = sb[1][0];
+    for (int w = 1; w < NW; ++w) { b0 = sb[0][w] > b0 ? sb[0][w] : b0; b1 = sb[1][w] > b1 ? sb[1][w] : b1; }
+    const float mm = fminf(peak_slot_value(b0), peak_slot_value(b1));         // NaN never enters a slot
+    for (int t = threadIdx.x; t < T; t += kPeakSlots) {
+        if (sflag[t] & 2) continue;
+        const float bt = pw.bt[a * T + t];
+        const bool skip = bt * (1.f + kPruneMargin) < mm && mm < INFINITY;    // false for a NaN and for an infinite candidate
+        if (!skip) sflag[t] |= 4;
+    }
+    __syncthreads();
+    int *listA = pw.tiles + (long)(2 * 4 + a) * T, *listP = pw.tiles + (long)(3 * 4 + a) * T;
+    for (int t = threadIdx.x; t < T; t += kPeakSlots) {
+        if (!(sflag[t] & 4)) continue;
+        listP[atomicAdd(&nP, 1)] = t;
+        const int nb[3] = {t ? t - 1 : T - 1, t, t + 1 < T ? t + 1 : 0};
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+            if (!(atomicOr(&sflag[nb[d]], 1) & 1)) listA[atomicAdd(&nA, 1)] = nb[d];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        pw.count[2 * 4 + a] = nA;
+        pw.count[3 * 4 + a] = nP;
+        atomicAdd(&stats[0], (unsigned long long)(pw.count[1 * 4 + a] + nP));
+        atomicAdd(&stats[1], (unsigned long long)T);
+    }
+}
+
 // Workspace carve-up for one correlation unit
 struct PcWork {
+    PruneWork prune;
     float2 *z[5];
     float2 *y[4];
     float *fa;          // base window, f32
@@ -1231,18 +1435,41 @@ struct PcWork {
     unsigned long long *slots;  // [4 arrays][2][kPeakSlots] arg-max slots, empty between surfaces
 };
 
-int carve(oip_ctx *ctx, const OipFft2dPlan *pl, int rows, int cols, int small_elems, int nz, int ny, int nfb, PcWork *w)
+// prune: the storage of the peak search of the spectral route (PruneWork) as well
+int carve(oip_ctx *ctx, const OipFft2dPlan *pl, int rows, int cols, int small_elems, int nz, int ny, int nfb, PcWork *w, bool prune = false)
 {
     const int M = pl->M;
+    memset(&w->prune, 0, sizeof w->prune);
+    size_t bbytes = 0, tbytes = 0;
+    if (prune) {
+        PruneWork &pw = w->prune;
+        pw.groups = ctx->cu_count < M / 2 + 1 ? ctx->cu_count : M / 2 + 1;       // the row stage's grid
+        pw.T = pl->passes[0].lane_tiles;
+        pw.vshift = pl->passes[0].vshift;
+        bbytes = align_up(sizeof(float) * (size_t)pw.groups * 4 * pl->P, 256);
+        if (oip_fft_col_list_ok(pl, 4) && (1 << pw.vshift) <= kSelCols && pw.T <= kSelMaxTiles)
+            tbytes = align_up(sizeof(int) * ((size_t)(4 + 4 + 16) * pw.T + 16 + 4), 256);
+    }
     const size_t zbytes = align_up(sizeof(float2) * (size_t)M * pl->P, 256);
     const size_t fbytes = align_up(sizeof(float) * (size_t)rows * cols, 256);
     const size_t sbytes = align_up(sizeof(float) * (size_t)(small_elems > 0 ? small_elems : 1), 256);
     const size_t pbytes = align_up(sizeof(unsigned long long) * 4 * 2 * kPeakSlots, 256);
-    size_t total = zbytes * (nz + ny) + fbytes * (1 + nfb) + sbytes + pbytes;
+    size_t total = zbytes * (nz + ny) + fbytes * (1 + nfb) + sbytes + pbytes + bbytes + tbytes;
     void *ws;
     int rc = oip_workspace(ctx, total, &ws);
     if (rc) return rc;
     char *p = (char *)ws;
+    if (bbytes) { w->prune.bound = (float *)p; p += bbytes; }
+    if (tbytes) {
+        // but for the tickets (cleared below) every word of these is written by col_sel_first_kernel before anything reads it
+        PruneWork &pw = w->prune;
+        pw.bt = (float *)p;
+        pw.flags = (int *)p + 4 * pw.T;
+        pw.count = (int *)p + 8 * pw.T;
+        pw.ticket = (int *)p + 8 * pw.T + 16;
+        pw.tiles = (int *)p + 8 * pw.T + 16 + 4;
+        p += tbytes;
+    }
     for (int i = 0; i < 5; ++i) { w->z[i] = i < nz ? (float2 *)p : nullptr; if (i < nz) p += zbytes; }
     for (int i = 0; i < 4; ++i) { w->y[i] = i < ny ? (float2 *)p : nullptr; if (i < ny) p += zbytes; }
     w->fa = (float *)p; p += fbytes;
@@ -1252,6 +1479,7 @@ int carve(oip_ctx *ctx, const OipFft2dPlan *pl, int rows, int cols, int small_el
     // the slots must start empty (later surfaces are cleaned by peak_window_kernel)
     ctx->prof_chain = nullptr;
     OIP_HIP(ctx, hipMemsetAsync(w->slots, 0, sizeof(unsigned long long) * 4 * 2 * kPeakSlots, ctx->stream));
+    if (w->prune.ticket) OIP_HIP(ctx, hipMemsetAsync(w->prune.ticket, 0, sizeof(int) * 4, ctx->stream));
     return OIP_OK;
 }
 
@@ -1764,10 +1992,12 @@ int correlate_units_up(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, c
     fj.raw16 = reinterpret_cast<const uint2 *>(raw);
     fj.ypos_s = ypos_s;
     fj.m = band_rows;
+    fj.bound = w.prune.bound;
+    if (!fj.bound) return oip_fail(ctx, OIP_E_RUNTIME, "correlate_units_up: no storage for the column bounds");
+    OIP_HIP(ctx, hipMemsetAsync(fj.bound, 0, sizeof(float) * (size_t)w.prune.groups * 4 * pl->P, ctx->stream));     // the kernel adds to it
     {
         OipProfScope prof(ctx, "corr_rows_up_kernel");
-        long grid = ctx->cu_count;
-        if (grid > pl->M / 2 + 1) grid = pl->M / 2 + 1;
+        const long grid = w.prune.groups;
         const dim3 g((unsigned)grid);
         if (up.vtab)       // measured in bench.py: 1.275 ms with 512 threads (244 VGPRs, no scratch), 1.36 with 768 (168, 28 spilled)
             hipLaunchKernelGGL((corr_rows_up_kernel<512, true>), g, dim3(512), 0, ctx->stream, fj, pl->M, pl->P, pl->d_ypos, twF, twS);
@@ -1775,11 +2005,56 @@ int correlate_units_up(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, c
             hipLaunchKernelGGL((corr_rows_up_kernel<512, false>), g, dim3(512), 0, ctx->stream, fj, pl->M, pl->P, pl->d_ypos, twF, twS);
         OIP_HIP(ctx, hipGetLastError());
     }
-    // the inverse column passes of the outputs, each into its own slot set; one window launch for all of them
     double *res[4];
-    for (int o = 0; o < narr; ++o) {
-        res[o] = (o < 2 ? d_resA : d_resB) + 6 * (o & 1);
-        if ((rc = inverse_to_slots(ctx, pl, w, w.y[o], true, o))) return rc;
+    for (int o = 0; o < narr; ++o) res[o] = (o < 2 ? d_resA : d_resB) + 6 * (o & 1);
+    const PruneWork &pw = w.prune;
+    if (!pw.tiles) {
+        // a plan without list forms of its column passes: the exhaustive passes, each output into its own slot set
+        for (int o = 0; o < narr; ++o)
+            if ((rc = inverse_to_slots(ctx, pl, w, w.y[o], true, o))) return rc;
+        return peak_windows(ctx, pl, w, w.y, res, narr, 2);
+    }
+    // The inverse column passes of all outputs over the tiles that can hold a maximum (see PruneWork): select, column
+    // passes, peak pass -- twice.  OIP_PEAK_PRUNE=0 (read per call) lists every tile the first time: the exhaustive
+    // search through the same kernels.  A tile that is not searched keeps its untransformed data in y[o]; nothing else
+    // reads it (peak_window_kernel reads the two columns either side of a searched tile at most, and those are done).
+    const char *pe = getenv("OIP_PEAK_PRUNE");
+    const int full = pe && atoi(pe) == 0 ? 1 : 0;
+    if (!ctx->d_prune_stats) {
+        OIP_HIP(ctx, hipMalloc((void **)&ctx->d_prune_stats, 2 * sizeof(unsigned long long)));
+        OIP_HIP(ctx, hipMemsetAsync(ctx->d_prune_stats, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    }
+    {
+        OipProfScope prof(ctx, "col_sel_first_kernel");
+        hipLaunchKernelGGL(col_sel_first_kernel, dim3((pl->N + kSelCols - 1) / kSelCols, narr), dim3(kSelThreads), 0, ctx->stream, pw, pl->P, pl->N, full);
+        OIP_HIP(ctx, hipGetLastError());
+    }
+    OipColList cl;
+    memset(&cl, 0, sizeof cl);
+    for (int o = 0; o < 4; ++o) cl.data[o] = w.y[o < narr ? o : 0];
+    cl.stride = pw.T;
+    cl.narr = narr;
+    cl.slots = w.slots;
+    for (int phase = 0; phase < 2; ++phase) {
+        if (phase == 1) {
+            OipProfScope prof(ctx, "col_sel_second_kernel");
+            hipLaunchKernelGGL(col_sel_second_kernel, dim3(narr), dim3(kPeakSlots), 0, ctx->stream, pw, w.slots, ctx->d_prune_stats);
+            OIP_HIP(ctx, hipGetLastError());
+            if (full) break;            // every tile was listed the first time
+        }
+        for (int kind = 0; kind < 2; ++kind) {
+            cl.count = pw.count + (phase * 2 + kind) * 4;
+            cl.tiles = pw.tiles + (long)(phase * 2 + kind) * 4 * pw.T;
+            if (kind == 1) {
+                if ((rc = oip_fft_col_list_pass(ctx, pl, 0, cl, true, "col_sel_peak"))) return rc;
+                continue;
+            }
+            for (int i = pl->n_y - 1; i >= 1; --i) {
+                char name[32];
+                snprintf(name, sizeof name, "col_sel_F%d", pl->passes[i].F);
+                if ((rc = oip_fft_col_list_pass(ctx, pl, i, cl, false, name))) return rc;
+            }
+        }
     }
     return peak_windows(ctx, pl, w, w.y, res, narr, 2);
 }
@@ -2008,7 +2283,7 @@ static int interband_units(oip_ctx *ctx, const IbUnit *units, int n, int rows, i
     }
     PcWork w;
     const bool spectral = up.xtab || up.vonly;
-    if ((rc = carve(ctx, pl, rows, band_cols, up.vonly ? 32 * N : 0, spectral ? 2 : 5, spectral ? 4 : 2, 8, &w))) return rc;      // f32 scratch: the V images
+    if ((rc = carve(ctx, pl, rows, band_cols, up.vonly ? 32 * N : 0, spectral ? 2 : 5, spectral ? 4 : 2, 8, &w, up.xtab != nullptr))) return rc;      // f32 scratch: the V images
     if ((rc = oip_small(ctx, sizeof(double) * 12 * (size_t)(n > 0 ? n : 1)))) return rc;
     double *d_res = (double *)ctx->d_small;
     // vertical passes of all bands of one or two units in one launch
@@ -2061,6 +2336,23 @@ static int interband_units(oip_ctx *ctx, const IbUnit *units, int n, int rows, i
         }
     }
     if (n > 0 && (rc = fetch_results(ctx, 12 * n, host_out))) return rc;
+    return OIP_OK;
+}
+
+extern "C" int oip_peak_prune_stats(oip_ctx *ctx, long long *tiles_searched, long long *tiles_total)
+{
+    OIP_CHECK_CTX(ctx);
+    unsigned long long *h = nullptr;
+    if (ctx->d_prune_stats) {
+        int rc = oip_small(ctx, 2 * sizeof(unsigned long long));
+        if (rc) return rc;
+        h = (unsigned long long *)ctx->h_small;
+        OIP_HIP(ctx, hipMemcpyAsync(h, ctx->d_prune_stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        OIP_HIP(ctx, hipMemsetAsync(ctx->d_prune_stats, 0, 2 * sizeof(unsigned long long), ctx->stream));
+        OIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (tiles_searched) *tiles_searched = h ? (long long)h[0] : 0;
+    if (tiles_total) *tiles_total = h ? (long long)h[1] : 0;
     return OIP_OK;
 }
 
