@@ -324,6 +324,18 @@ int oip_interband_correlate_units(oip_ctx *ctx, const uint16_t *const *d_pan, co
  * null).  Waits for the context's stream. */
 int oip_peak_prune_stats(oip_ctx *ctx, long long *tiles_searched, long long *tiles_total);
 
+/* The row stage of that route stores only the columns the pruned search reads: the lane tiles 0 .. R and T - R .. T - 1
+ * of the T tiles of the column passes, a circular window around column 0, where the surfaces of inter-band shifts of a
+ * few pixels peak.  R = OIP_ROWS_WINDOW in the environment, read per call (default 8; 0 stores every
+ * column, and so do OIP_PEAK_PRUNE=0 and plans without tile lists).  A pair of units whose search lists a tile outside
+ * the window is detected on the device and run again inside the same call with every column stored: results have
+ * the same bits either way.  OIP_ROWS_WINDOW_POISON=1 (debug) fills the output arrays with NaN before the row stage.
+ * oip_rows_window_stats returns how many pairs (or single units) went through the windowed row stage and how many of
+ * them were run again, since the previous call, and starts the count again; oip_rows_window_geometry returns the tile
+ * width in columns, T and R (-1: every column stored) of the latest correlation call.  Any pointer may be null. */
+int oip_rows_window_stats(oip_ctx *ctx, long long *pairs, long long *pairs_rerun);
+int oip_rows_window_geometry(oip_ctx *ctx, int *tile_cols, int *tiles, int *radius);
+
 /* The x4 cubic up-sampling of cv::resize (preproc.h:302-307) along one axis as an operator on spectra -- what
  * oip_interband_correlate applies to the transforms of the band windows instead of transforming the up-sampled
  * image.  Host only.  out: 5 x (4 n) complex floats, rows H, G_0 .. G_3:

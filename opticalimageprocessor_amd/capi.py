@@ -104,6 +104,8 @@ _SIGS = {
     "oip_interband_correlate_units": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _dp], _i),
     "oip_interband_correlate": ([_vp, _vp, _l, _l, _l, _vp, _sz, _l, _l, _i, _i, _i, _i, _dp], _i),
     "oip_peak_prune_stats": ([_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], _i),
+    "oip_rows_window_stats": ([_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], _i),
+    "oip_rows_window_geometry": ([_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)], _i),
     "oip_filter_and_fit": ([_dp, _i, _d, _i, _dp, _dp, _cp, _i], _i),
     "oip_filter_and_fit_mode": ([_dp, _i, _d, _i, _i, _dp, _dp, _cp, _i], _i),
     "oip_polyfit": ([_dp, _dp, _i, _i, _dp], _i),
@@ -780,6 +782,20 @@ class Context:
         s, t = C.c_longlong(0), C.c_longlong(0)
         self._ck(self.lib.oip_peak_prune_stats(self.h, C.byref(s), C.byref(t)))
         return s.value, t.value
+
+    def rows_window_stats(self):
+        """(pairs of units correlated with the row stage's stored window, pairs run again with every column stored) since
+        the previous call; starts the count again"""
+        p, r = C.c_longlong(0), C.c_longlong(0)
+        self._ck(self.lib.oip_rows_window_stats(self.h, C.byref(p), C.byref(r)))
+        return p.value, r.value
+
+    def rows_window_geometry(self):
+        """(tile width in columns, tiles, radius R in tiles or -1 when every column was stored) of the latest correlation
+        call: tiles 0 .. R and tiles - R .. tiles - 1 were stored"""
+        v, t, r = C.c_int(0), C.c_int(0), C.c_int(-1)
+        self._ck(self.lib.oip_rows_window_geometry(self.h, C.byref(v), C.byref(t), C.byref(r)))
+        return v.value, t.value, r.value
 
     # -- resampling
     def remap_shift_bicubic_u16(self, src, dst, W, L, dx, dy, section_rows=30000, row_guard=32767,

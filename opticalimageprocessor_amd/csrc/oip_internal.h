@@ -80,6 +80,10 @@ struct oip_ctx {
     oip_fft_state *fft = nullptr;
     std::vector<OipResizeTab> resize_tabs;
     unsigned long long *d_prune_stats = nullptr;   // device: lane tiles searched / in all by the correlation's peak search (oip_peak_prune_stats)
+    // the row stage's stored window (oip_rows_window_stats): groups of units correlated with one / run again with every
+    // column stored since the previous call, and the last call's geometry {tile columns, tiles, radius or -1}
+    long long rows_window_pairs = 0, rows_window_rerun = 0;
+    int rows_window[3] = {0, 0, -1};
 
     // profiling
     bool prof_on = false;

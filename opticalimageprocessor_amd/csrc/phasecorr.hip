@@ -561,6 +561,10 @@ struct UpRowsJob {
     // stored in column x of output o at bound[(g * 4 + o) * P + x], zero before the launch.  A thread owns its columns for
     // the whole launch, so an element is the private accumulator of one thread (no sum depends on an order between threads).
     float *bound;
+    // WIN: only the 16-byte pieces q (columns 2 q, 2 q + 1) with q < win_hi or q >= win_lo are stored -- the circular,
+    // tile-aligned range of columns around column 0 that the pruned peak search reads (rows_window).  The bounds above
+    // are summed over every column all the same.
+    int win_hi, win_lo;
 };
 
 // conj(a) b, acc + a b, acc + conj(a) b on packed-f32 instructions (two each; operand selection as in oipfft::cmul).
@@ -600,7 +604,7 @@ __device__ __forceinline__ float2 sfma(float s, float2 v, float2 acc)
     return make_float2(acc.x + s * v.x, acc.y + s * v.y);
 }
 
-template <int NT, bool VEXP>
+template <int NT, bool VEXP, bool WIN>
 __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, int P, const int *__restrict__ ypos,
                                                           const float2 *__restrict__ twF, const float2 *__restrict__ twS)
 {
@@ -841,7 +845,12 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
             for (int o = 0; o < 2; ++o) {
                 float2 *out = fj.out[o0 + o];
 #pragma unroll
-                for (int it = 0; it < NIT2; ++it) line_pair_store<F>(out, s1 * P, s2 * P, pair, ya[o][it], yb[o][it], tid + it * NT);
+                for (int it = 0; it < NIT2; ++it) {
+                    const int q = tid + it * NT;
+                    // WIN: compared here, from the piece index (wave-uniform but at the window's two ends); nothing is
+                    // carried across the iteration
+                    if (!WIN || q < fj.win_hi || q >= fj.win_lo) line_pair_store<F>(out, s1 * P, s2 * P, pair, ya[o][it], yb[o][it], q);
+                }
             }
         };
         // Column bounds: |Re| + |Im| of what store(o0) has just written is added to the workgroup's rows with the
@@ -1274,6 +1283,9 @@ inline bool smooth_len(long n) { for (int p : {2, 3, 5}) while (n % p == 0) n /=
 // f32 transform's own error is about 1e-5 of sum |x|; 2^-8 = 3.9e-3 covers both four times over and costs nothing, the
 // bound sitting 3 to 20 times below a usable peak.
 constexpr float kPruneMargin = 0x1p-8f;
+// The row stage stores only the columns of the lane tiles 0 .. R and T - R .. T - 1 (inter-band shifts are a few PAN
+// pixels: the surfaces peak in tile 0 or across the wrap), R = OIP_ROWS_WINDOW or this; see correlate_units_up.
+constexpr int kRowsWindowTiles = 8;
 constexpr int kSelThreads = 1024, kSelCols = 64, kSelParts = kSelThreads / kSelCols, kSelMaxTiles = 1024;
 struct PruneWork {
     float *bound;       // [row-stage workgroups][4][P]: the row stage's partial column sums
@@ -1282,9 +1294,19 @@ struct PruneWork {
     int *flags;         // [4][T]: bit 0 column passes done, bit 1 searched
     int *count;         // [2 phases][2: column passes, peak pass][4]
     int *tiles;         // [2][2][4][T]; null: the plan has no list form (the exhaustive passes run)
-    int *ticket;        // [4]: workgroups of col_sel_first_kernel that are done with an array; zero between launches
+    int *ticket;        // [4]: workgroups of col_sel_first_kernel that are done with an array; [4]: arrays col_sel_second_kernel is
+                        // done with; zero between launches
     int T, vshift;      // lane tiles of the column passes and log2 of their width
+    // The stored window of the row stage (rows_window): tiles 0 .. win_r and T - win_r .. T - 1 hold data, the others do
+    // not; win_r < 0: every tile does.  A tile the search would list outside of it makes the pair a miss: *miss is set,
+    // the array lists nothing, the pair adds nothing to the statistics, and the host runs the pair again with every
+    // column stored.
+    int win_r;
+    int *miss;
 };
+// a window of radius r exists for these lists: tiles of whole pieces (two columns), and the two arms do not meet
+inline bool rows_window_fits(const PruneWork &pw, int r) { return r >= 0 && pw.tiles && pw.vshift >= 1 && 2 * r + 1 < pw.T; }
+__device__ __forceinline__ bool tile_stored(const PruneWork &pw, int t) { return pw.win_r < 0 || t <= pw.win_r || t >= pw.T - pw.win_r; }
 
 // grid (ceil(N / kSelCols), arrays): a workgroup sums kSelCols columns -- thread (x, j) the rows j, j + kSelParts, ... of
 // column x, thread (x, 0) the kSelParts partial sums, both in a fixed order -- and leaves the maxima of their tiles; the
@@ -1346,13 +1368,18 @@ __global__ __launch_bounds__(kSelThreads) void col_sel_first_kernel(PruneWork pw
     __syncthreads();
     const int tm = sbest, tp = tm ? tm - 1 : T - 1, tn = tm + 1 < T ? tm + 1 : 0;
     int *listA = pw.tiles + (long)(0 * 4 + a) * T, *listP = pw.tiles + (long)(1 * 4 + a) * T;
+    // the tile and its neighbours (whose edge columns the 5 x 5 window reads) must hold data
+    const bool missed = !full && !(tile_stored(pw, tm) && tile_stored(pw, tp) && tile_stored(pw, tn));
     for (int t = threadIdx.x; t < T; t += kSelThreads) {
-        pw.flags[a * T + t] = full ? 3 : (t == tm ? 3 : (t == tp || t == tn ? 1 : 0));
+        pw.flags[a * T + t] = full ? 3 : (missed ? 0 : (t == tm ? 3 : (t == tp || t == tn ? 1 : 0)));
         if (full) { listA[t] = t; listP[t] = t; }
     }
     if (threadIdx.x == 0) {
         int nA = T, nP = T;
-        if (!full) {
+        if (missed) {
+            atomicExch(pw.miss, 1);
+            nA = nP = 0;
+        } else if (!full) {
             listP[0] = tm;
             nP = 1;
             nA = 0;
@@ -1382,7 +1409,7 @@ __global__ __launch_bounds__(kPeakSlots) void col_sel_second_kernel(PruneWork pw
     constexpr int NW = kPeakSlots / 64;
     __shared__ unsigned long long sb[2][NW];
     __shared__ int sflag[kSelMaxTiles];
-    __shared__ int nA, nP;
+    __shared__ int nA, nP, smiss;
     const int a = blockIdx.x, T = pw.T;
     const unsigned long long *s = slots + (long)a * 2 * kPeakSlots;
     unsigned long long b0 = s[threadIdx.x], b1 = s[kPeakSlots + threadIdx.x];
@@ -1399,15 +1426,25 @@ __global__ __launch_bounds__(kPeakSlots) void col_sel_second_kernel(PruneWork pw
     b0 = sb[0][0]; b1 = sb[1][0];
     for (int w = 1; w < NW; ++w) { b0 = sb[0][w] > b0 ? sb[0][w] : b0; b1 = sb[1][w] > b1 ? sb[1][w] : b1; }
     const float mm = fminf(peak_slot_value(b0), peak_slot_value(b1));         // NaN never enters a slot
-    for (int t = threadIdx.x; t < T; t += kPeakSlots) {
+    // a pair that missed the stored window in the first round (any of its arrays) lists nothing more
+    if (threadIdx.x == 0) smiss = pw.win_r >= 0 ? atomicAdd(pw.miss, 0) : 0;
+    __syncthreads();
+    const bool dead = smiss != 0;
+    __syncthreads();
+    for (int t = threadIdx.x; t < T && !dead; t += kPeakSlots) {
         if (sflag[t] & 2) continue;
         const float bt = pw.bt[a * T + t];
         const bool skip = bt * (1.f + kPruneMargin) < mm && mm < INFINITY;    // false for a NaN and for an infinite candidate
-        if (!skip) sflag[t] |= 4;
+        if (!skip) {
+            sflag[t] |= 4;
+            const int tp = t ? t - 1 : T - 1, tn = t + 1 < T ? t + 1 : 0;
+            if (!(tile_stored(pw, t) && tile_stored(pw, tp) && tile_stored(pw, tn))) smiss = 1;
+        }
     }
     __syncthreads();
+    const bool missed = smiss != 0;
     int *listA = pw.tiles + (long)(2 * 4 + a) * T, *listP = pw.tiles + (long)(3 * 4 + a) * T;
-    for (int t = threadIdx.x; t < T; t += kPeakSlots) {
+    for (int t = threadIdx.x; t < T && !missed; t += kPeakSlots) {
         if (!(sflag[t] & 4)) continue;
         listP[atomicAdd(&nP, 1)] = t;
         const int nb[3] = {t ? t - 1 : T - 1, t, t + 1 < T ? t + 1 : 0};
@@ -1419,8 +1456,20 @@ __global__ __launch_bounds__(kPeakSlots) void col_sel_second_kernel(PruneWork pw
     if (threadIdx.x == 0) {
         pw.count[2 * 4 + a] = nA;
         pw.count[3 * 4 + a] = nP;
-        atomicAdd(&stats[0], (unsigned long long)(pw.count[1 * 4 + a] + nP));
-        atomicAdd(&stats[1], (unsigned long long)T);
+        if (missed && !dead) atomicExch(pw.miss, 1);
+        // the pair's counters are added once, by the array that finishes last, and only if no array missed: the attempt
+        // whose result is kept counts
+        __threadfence();
+        if (atomicAdd(&pw.ticket[4], 1) == (int)gridDim.x - 1) {
+            __threadfence();
+            atomicExch(&pw.ticket[4], 0);           // for the next launch
+            if (pw.win_r < 0 || atomicAdd(pw.miss, 0) == 0) {
+                unsigned long long searched = 0;
+                for (int o = 0; o < (int)gridDim.x; ++o) searched += (unsigned long long)(atomicAdd(&pw.count[1 * 4 + o], 0) + atomicAdd(&pw.count[3 * 4 + o], 0));
+                atomicAdd(&stats[0], searched);
+                atomicAdd(&stats[1], (unsigned long long)T * gridDim.x);
+            }
+        }
     }
 }
 
@@ -1440,6 +1489,7 @@ int carve(oip_ctx *ctx, const OipFft2dPlan *pl, int rows, int cols, int small_el
 {
     const int M = pl->M;
     memset(&w->prune, 0, sizeof w->prune);
+    w->prune.win_r = -1;
     size_t bbytes = 0, tbytes = 0;
     if (prune) {
         PruneWork &pw = w->prune;
@@ -1448,7 +1498,7 @@ int carve(oip_ctx *ctx, const OipFft2dPlan *pl, int rows, int cols, int small_el
         pw.vshift = pl->passes[0].vshift;
         bbytes = align_up(sizeof(float) * (size_t)pw.groups * 4 * pl->P, 256);
         if (oip_fft_col_list_ok(pl, 4) && (1 << pw.vshift) <= kSelCols && pw.T <= kSelMaxTiles)
-            tbytes = align_up(sizeof(int) * ((size_t)(4 + 4 + 16) * pw.T + 16 + 4), 256);
+            tbytes = align_up(sizeof(int) * ((size_t)(4 + 4 + 16) * pw.T + 16 + 8), 256);
     }
     const size_t zbytes = align_up(sizeof(float2) * (size_t)M * pl->P, 256);
     const size_t fbytes = align_up(sizeof(float) * (size_t)rows * cols, 256);
@@ -1467,7 +1517,7 @@ int carve(oip_ctx *ctx, const OipFft2dPlan *pl, int rows, int cols, int small_el
         pw.flags = (int *)p + 4 * pw.T;
         pw.count = (int *)p + 8 * pw.T;
         pw.ticket = (int *)p + 8 * pw.T + 16;
-        pw.tiles = (int *)p + 8 * pw.T + 16 + 4;
+        pw.tiles = (int *)p + 8 * pw.T + 16 + 8;
         p += tbytes;
     }
     for (int i = 0; i < 5; ++i) { w->z[i] = i < nz ? (float2 *)p : nullptr; if (i < nz) p += zbytes; }
@@ -1479,7 +1529,7 @@ int carve(oip_ctx *ctx, const OipFft2dPlan *pl, int rows, int cols, int small_el
     // the slots must start empty (later surfaces are cleaned by peak_window_kernel)
     ctx->prof_chain = nullptr;
     OIP_HIP(ctx, hipMemsetAsync(w->slots, 0, sizeof(unsigned long long) * 4 * 2 * kPeakSlots, ctx->stream));
-    if (w->prune.ticket) OIP_HIP(ctx, hipMemsetAsync(w->prune.ticket, 0, sizeof(int) * 4, ctx->stream));
+    if (w->prune.ticket) OIP_HIP(ctx, hipMemsetAsync(w->prune.ticket, 0, sizeof(int) * 8, ctx->stream));
     return OIP_OK;
 }
 
@@ -1930,7 +1980,8 @@ __global__ __launch_bounds__(128) void pack_bands_kernel(BandPackJob job, int m,
 }
 
 int correlate_units_up(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, const PcWork &w, RealSrc aA, RealSrc aB, const RealSrc *v /* 4 or 8: V images */,
-                       const IbUnit *const *units, int nunits, int rows, int cols, int band_rows, int band_cols, double *d_resA, double *d_resB)
+                       const IbUnit *const *units, int nunits, int rows, int cols, int band_rows, int band_cols, double *d_resA, double *d_resB,
+                       int win_r = -1, int *d_miss = nullptr)
 {
     int rc;
     if ((rc = forward_packed(ctx, pl, w.z[0], aA, nunits > 1 ? aB : src_none(), rows, cols, true))) return rc;
@@ -1995,19 +2046,36 @@ int correlate_units_up(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, c
     fj.bound = w.prune.bound;
     if (!fj.bound) return oip_fail(ctx, OIP_E_RUNTIME, "correlate_units_up: no storage for the column bounds");
     OIP_HIP(ctx, hipMemsetAsync(fj.bound, 0, sizeof(float) * (size_t)w.prune.groups * 4 * pl->P, ctx->stream));     // the kernel adds to it
+    // The stored window (rows_window): tiles 0 .. win_r and T - win_r .. T - 1 of the column passes' lane tiles, as pieces
+    // of two columns.  The peak search below tells a pair that needs a tile outside of it (PruneWork::miss).
+    PruneWork pw = w.prune;
+    const char *pe = getenv("OIP_PEAK_PRUNE");
+    const int full = pe && atoi(pe) == 0 ? 1 : 0;           // every tile is listed: every column is stored
+    if (full || !up.vtab || !rows_window_fits(pw, win_r) || !d_miss) win_r = -1;
+    pw.win_r = win_r;
+    pw.miss = d_miss;
+    if (win_r >= 0) {
+        fj.win_hi = ((win_r + 1) << pw.vshift) / 2;
+        fj.win_lo = ((pw.T - win_r) << pw.vshift) / 2;
+    }
+    {
+        const char *pz = getenv("OIP_ROWS_WINDOW_POISON");      // debug: what the window leaves unwritten reads as NaN, not as the last pair's data
+        if (pz && atoi(pz) > 0)
+            for (int o = 0; o < narr; ++o) OIP_HIP(ctx, hipMemsetAsync(w.y[o], 0xff, sizeof(float2) * (size_t)pl->M * pl->P, ctx->stream));
+    }
     {
         OipProfScope prof(ctx, "corr_rows_up_kernel");
         const long grid = w.prune.groups;
         const dim3 g((unsigned)grid);
-        if (up.vtab)       // measured in bench.py: 1.275 ms with 512 threads (244 VGPRs, no scratch), 1.36 with 768 (168, 28 spilled)
-            hipLaunchKernelGGL((corr_rows_up_kernel<512, true>), g, dim3(512), 0, ctx->stream, fj, pl->M, pl->P, pl->d_ypos, twF, twS);
-        else
-            hipLaunchKernelGGL((corr_rows_up_kernel<512, false>), g, dim3(512), 0, ctx->stream, fj, pl->M, pl->P, pl->d_ypos, twF, twS);
+        // (no windowed instance without VEXP: that kernel already spills, and the predicate doubles it -- 24 -> 48 VGPRs)
+        auto k = up.vtab ? (win_r >= 0 ? corr_rows_up_kernel<512, true, true> : corr_rows_up_kernel<512, true, false>)
+                         : corr_rows_up_kernel<512, false, false>;
+        // measured in bench.py, VEXP: 1.275 ms with 512 threads (244 VGPRs, no scratch), 1.36 with 768 (168, 28 spilled)
+        hipLaunchKernelGGL(k, g, dim3(512), 0, ctx->stream, fj, pl->M, pl->P, pl->d_ypos, twF, twS);
         OIP_HIP(ctx, hipGetLastError());
     }
     double *res[4];
     for (int o = 0; o < narr; ++o) res[o] = (o < 2 ? d_resA : d_resB) + 6 * (o & 1);
-    const PruneWork &pw = w.prune;
     if (!pw.tiles) {
         // a plan without list forms of its column passes: the exhaustive passes, each output into its own slot set
         for (int o = 0; o < narr; ++o)
@@ -2018,8 +2086,6 @@ int correlate_units_up(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, c
     // passes, peak pass -- twice.  OIP_PEAK_PRUNE=0 (read per call) lists every tile the first time: the exhaustive
     // search through the same kernels.  A tile that is not searched keeps its untransformed data in y[o]; nothing else
     // reads it (peak_window_kernel reads the two columns either side of a searched tile at most, and those are done).
-    const char *pe = getenv("OIP_PEAK_PRUNE");
-    const int full = pe && atoi(pe) == 0 ? 1 : 0;
     if (!ctx->d_prune_stats) {
         OIP_HIP(ctx, hipMalloc((void **)&ctx->d_prune_stats, 2 * sizeof(unsigned long long)));
         OIP_HIP(ctx, hipMemsetAsync(ctx->d_prune_stats, 0, 2 * sizeof(unsigned long long), ctx->stream));
@@ -2122,12 +2188,14 @@ int correlate_units_vup(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, 
     return peak_windows(ctx, pl, w, w.y, res, narr, 2);
 }
 
-int fetch_results(oip_ctx *ctx, int count, double *host_out)
+// nflags ints that follow the results in d_small (the miss flags of the row stage's window) ride the same copy
+int fetch_results(oip_ctx *ctx, int count, double *host_out, int nflags = 0, int *flags_out = nullptr)
 {
     ctx->prof_chain = nullptr;
-    OIP_HIP(ctx, hipMemcpyAsync(ctx->h_small, ctx->d_small, sizeof(double) * count, hipMemcpyDeviceToHost, ctx->stream));
+    OIP_HIP(ctx, hipMemcpyAsync(ctx->h_small, ctx->d_small, sizeof(double) * count + sizeof(int) * nflags, hipMemcpyDeviceToHost, ctx->stream));
     OIP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     memcpy(host_out, ctx->h_small, sizeof(double) * count);
+    if (nflags) memcpy(flags_out, (const char *)ctx->h_small + sizeof(double) * count, sizeof(int) * nflags);
     return OIP_OK;
 }
 
@@ -2284,8 +2352,23 @@ static int interband_units(oip_ctx *ctx, const IbUnit *units, int n, int rows, i
     PcWork w;
     const bool spectral = up.xtab || up.vonly;
     if ((rc = carve(ctx, pl, rows, band_cols, up.vonly ? 32 * N : 0, spectral ? 2 : 5, spectral ? 4 : 2, 8, &w, up.xtab != nullptr))) return rc;      // f32 scratch: the V images
-    if ((rc = oip_small(ctx, sizeof(double) * 12 * (size_t)(n > 0 ? n : 1)))) return rc;
+    // The row stage's window (rows_window): OIP_ROWS_WINDOW, read per call, is its radius in lane tiles, 0
+    // stores every column.  One miss flag per group of units follows the results in d_small.
+    int win_r = -1;
+    if (up.xtab && up.vtab) {
+        const char *e = getenv("OIP_ROWS_WINDOW");
+        win_r = e ? atoi(e) : kRowsWindowTiles;
+        const char *pe = getenv("OIP_PEAK_PRUNE");          // 0: every tile is searched, so every column is stored
+        win_r = win_r > 0 && !(pe && atoi(pe) == 0) && rows_window_fits(w.prune, win_r) ? win_r : -1;
+    }
+    ctx->rows_window[0] = w.prune.tiles ? 1 << w.prune.vshift : 0;
+    ctx->rows_window[1] = w.prune.tiles ? w.prune.T : 0;
+    ctx->rows_window[2] = win_r;
+    const int ngroups = (n + 1) / 2;
+    if ((rc = oip_small(ctx, sizeof(double) * 12 * (size_t)(n > 0 ? n : 1) + sizeof(int) * (size_t)(ngroups + 1)))) return rc;
     double *d_res = (double *)ctx->d_small;
+    int *d_miss = reinterpret_cast<int *>(d_res + 12 * (size_t)n);
+    if (win_r >= 0) OIP_HIP(ctx, hipMemsetAsync(d_miss, 0, sizeof(int) * ngroups, ctx->stream));
     // vertical passes of all bands of one or two units in one launch
     auto upsample = [&](const IbUnit *const *uns, int nun, float *const *fb, RealSrc *out) -> int {
         const uint16_t *srcs[kVBatch];
@@ -2298,42 +2381,52 @@ static int interband_units(oip_ctx *ctx, const IbUnit *units, int n, int rows, i
             }
         return launch_resize_v<uint16_t>(ctx, srcs, fb, 4 * nun, pitches, band_cols, band_rows, cols, rows, &tab);
     };
-    int k = 0;
     RealSrc sAB[8];
-    for (; k + 1 < n; k += 2) {
-        const IbUnit &A = units[k], &B = units[k + 1];
-        const IbUnit *two[2] = {&A, &B};
-        if (up.vonly) {
-            if ((rc = correlate_units_vup(ctx, pl, up, w, tab, src_u16(A.pan, A.pan_pitch), src_u16(B.pan, B.pan_pitch), two, 2, rows, cols, band_rows,
-                                          band_cols, d_res + 12 * k, d_res + 12 * (k + 1)))) return rc;
-            continue;
+    // units k, k + 1 (or the last one alone); wr: the row stage's window, -1 for every column
+    auto run_group = [&](int k, int wr) -> int {
+        if (k + 1 < n) {
+            const IbUnit &A = units[k], &B = units[k + 1];
+            const IbUnit *two[2] = {&A, &B};
+            if (up.vonly)
+                return correlate_units_vup(ctx, pl, up, w, tab, src_u16(A.pan, A.pan_pitch), src_u16(B.pan, B.pan_pitch), two, 2, rows, cols, band_rows,
+                                           band_cols, d_res + 12 * k, d_res + 12 * (k + 1));
+            if (!up.vtab && (rc = upsample(two, 2, w.fb, sAB))) return rc;
+            if (up.xtab)
+                return correlate_units_up(ctx, pl, up, w, src_u16(A.pan, A.pan_pitch), src_u16(B.pan, B.pan_pitch), sAB, two, 2, rows, cols, band_rows,
+                                          band_cols, d_res + 12 * k, d_res + 12 * (k + 1), wr, d_miss + k / 2);
+            const HTaps vt{band_cols, tab->d_xofs, tab->d_alpha, tab->x4h};
+            return correlate_two_units(ctx, pl, w, src_u16(A.pan, A.pan_pitch), sAB, src_u16(B.pan, B.pan_pitch), sAB + 4, rows, cols,
+                                       d_res + 12 * k, d_res + 12 * (k + 1), &vt);
         }
-        if (!up.vtab && (rc = upsample(two, 2, w.fb, sAB))) return rc;
-        if (up.xtab) {
-            if ((rc = correlate_units_up(ctx, pl, up, w, src_u16(A.pan, A.pan_pitch), src_u16(B.pan, B.pan_pitch), sAB, two, 2, rows, cols, band_rows,
-                                         band_cols, d_res + 12 * k, d_res + 12 * (k + 1)))) return rc;
-            continue;
-        }
-        const HTaps vt{band_cols, tab->d_xofs, tab->d_alpha, tab->x4h};
-        if ((rc = correlate_two_units(ctx, pl, w, src_u16(A.pan, A.pan_pitch), sAB, src_u16(B.pan, B.pan_pitch), sAB + 4, rows, cols,
-                                      d_res + 12 * k, d_res + 12 * (k + 1), &vt))) return rc;
-    }
-    if (k < n) {
         const IbUnit &A = units[k];
         const IbUnit *one[1] = {&A};
-        if (up.vonly) {
-            if ((rc = correlate_units_vup(ctx, pl, up, w, tab, src_u16(A.pan, A.pan_pitch), src_none(), one, 1, rows, cols, band_rows, band_cols,
-                                          d_res + 12 * k, nullptr))) return rc;
-        } else {
+        if (up.vonly)
+            return correlate_units_vup(ctx, pl, up, w, tab, src_u16(A.pan, A.pan_pitch), src_none(), one, 1, rows, cols, band_rows, band_cols,
+                                       d_res + 12 * k, nullptr);
         if (!up.vtab && (rc = upsample(one, 1, w.fb, sAB))) return rc;
-        if (up.xtab) {
-            if ((rc = correlate_units_up(ctx, pl, up, w, src_u16(A.pan, A.pan_pitch), src_none(), sAB, one, 1, rows, cols, band_rows, band_cols,
-                                         d_res + 12 * k, nullptr))) return rc;
-        } else {
-            const HTaps vt{band_cols, tab->d_xofs, tab->d_alpha, tab->x4h};
-            if ((rc = correlate_one_to_four(ctx, pl, w, src_u16(A.pan, A.pan_pitch), sAB, rows, cols, d_res + 12 * k, &vt))) return rc;
-        }
-        }
+        if (up.xtab)
+            return correlate_units_up(ctx, pl, up, w, src_u16(A.pan, A.pan_pitch), src_none(), sAB, one, 1, rows, cols, band_rows, band_cols,
+                                      d_res + 12 * k, nullptr, wr, d_miss + k / 2);
+        const HTaps vt{band_cols, tab->d_xofs, tab->d_alpha, tab->x4h};
+        return correlate_one_to_four(ctx, pl, w, src_u16(A.pan, A.pan_pitch), sAB, rows, cols, d_res + 12 * k, &vt);
+    };
+    for (int k = 0; k < n; k += 2)
+        if ((rc = run_group(k, win_r))) return rc;
+    if (n > 0 && win_r >= 0) {
+        // Groups whose peak search needed a tile outside the stored window (their flags came with the results) run again
+        // from the top with every column stored -- with the same partner, on which a unit's last digits depend -- and the
+        // results are fetched again.  Nothing waits but this call's own fetch.
+        std::vector<int> miss((size_t)ngroups);
+        if ((rc = fetch_results(ctx, 12 * n, host_out, ngroups, miss.data()))) return rc;
+        int again = 0;
+        for (int g = 0; g < ngroups; ++g)
+            if (miss[g]) {
+                ++again;
+                if ((rc = run_group(2 * g, -1))) return rc;
+            }
+        ctx->rows_window_pairs += ngroups;
+        ctx->rows_window_rerun += again;
+        if (!again) return OIP_OK;
     }
     if (n > 0 && (rc = fetch_results(ctx, 12 * n, host_out))) return rc;
     return OIP_OK;
@@ -2353,6 +2446,24 @@ extern "C" int oip_peak_prune_stats(oip_ctx *ctx, long long *tiles_searched, lon
     }
     if (tiles_searched) *tiles_searched = h ? (long long)h[0] : 0;
     if (tiles_total) *tiles_total = h ? (long long)h[1] : 0;
+    return OIP_OK;
+}
+
+extern "C" int oip_rows_window_stats(oip_ctx *ctx, long long *pairs, long long *pairs_rerun)
+{
+    OIP_CHECK_CTX(ctx);
+    if (pairs) *pairs = ctx->rows_window_pairs;
+    if (pairs_rerun) *pairs_rerun = ctx->rows_window_rerun;
+    ctx->rows_window_pairs = ctx->rows_window_rerun = 0;
+    return OIP_OK;
+}
+
+extern "C" int oip_rows_window_geometry(oip_ctx *ctx, int *tile_cols, int *tiles, int *radius)
+{
+    OIP_CHECK_CTX(ctx);
+    if (tile_cols) *tile_cols = ctx->rows_window[0];
+    if (tiles) *tiles = ctx->rows_window[1];
+    if (radius) *radius = ctx->rows_window[2];
     return OIP_OK;
 }
 
