@@ -741,6 +741,60 @@ int oip_match_peak(const uint64_t *record, int T, int S, double min_score, doubl
  * and its maximum; all zero where n_ok = 0.  No context. */
 int oip_match_summary(const double *dx, const double *dy, const int *flags, long n, double *out);
 
+/* ---- regfix: resampling of a raster by the shift field regcheck measured (`oip regfix`; not in the reference) ----
+ * The reference's geometric models are a constant shift per CCD pair and, per MSS band, a polynomial in the column alone; this
+ * is the resampler that takes a field.  Everything is integer except the 16-tap sum.
+ * Field.  A lattice of nx x ny nodes, nx, ny >= 1, nx * ny <= 2^27, at pixel (gx0 + i * sx, gy0 + j * sy) of the raster to be
+ * resampled; steps 1 <= sx, sy <= OIP_WARP_MAX_STEP; gx0, gy0 any value.  Node (j, i) carries NX[j * nx + i] and NY[j * nx + i],
+ * int32 in Q10 (1/1024 px), |value| <= OIP_WARP_MAX_Q10 (64 px).
+ * Per axis (x shown; y the same with gy0, sy, ny):
+ *   p = x - gx0;  ci = clamp(floor(p / sx), 0, nx - 2);  t = clamp(p - ci * sx, 0, sx);  wx = (t * 4096 + sx / 2) / sx   (Q12)
+ *   with one node on the axis ci = 0, wx = 0 and node ci + 1 is never read.  Outside the lattice the edge value holds.
+ * Per output sample, y first, then x, with lerp(a, b, w) = a + (((b - a) * w + 2048) >> 12) (arithmetic shift; every product
+ * fits int32), for N = NX and N = NY alike:
+ *   R[i] = lerp(N[cj][i], N[cj + 1][i], wy);   d = lerp(R[ci], R[ci + 1], wx);   s = 32 * coordinate + ((d + 16) >> 5)   (1/32 px)
+ * Sampling is cv::remap(INTER_CUBIC, BORDER_CONSTANT 0) as csrc/oip_bicubic.h states it: first tap X = (s_x >> 5) - 1, phase
+ * s_x & 31, the same in y, w = wy * wx as one f32 product, the interior and the border summation order,
+ * saturate_cast<ushort>(cvRound(sum)), nothing contracted.  There is no `short` saturation of coordinates and there are no
+ * sections: the source is the whole W x L raster.  The convention is regcheck's: out(y, x) = src(y + dy, x + dx).
+ * Raster and window conventions are oip_convolve_u16's; spp 1 or 4 (pixel-interleaved); band_mask: bit c set for the channels
+ * that are resampled, 1 <= band_mask < 2^spp; the other channels are copied through.  nodes_x / nodes_y are host arrays, copied
+ * during the call.  OIP_E_INVALID: a value outside the stated ranges, a NULL or odd pointer, d_dst == d_src, output lines
+ * outside [0, L), a source line that oip_warp_grid_src_range names and that is not resident.  out_rows == 0 is a no-op.
+ * Asynchronous on the context's stream; lines and pitches in 64 bits. */
+#define OIP_WARP_MAX_STEP 65536
+#define OIP_WARP_MAX_Q10 65536
+#define OIP_REGFIX_SUFFIX ".REGFIX"
+#define OIP_REGFIX_MAX_SMOOTH 16
+int oip_warp_grid_bicubic_u16(oip_ctx *ctx, const uint16_t *d_src, long src_row0, long src_rows, uint16_t *d_dst, long out_row0,
+                              long out_rows, int W, long L, int spp, int band_mask, const int32_t *nodes_x, const int32_t *nodes_y,
+                              int nx, int ny, long gx0, long gy0, int sx, int sy);
+/* host: source lines [first, last), inside [0, L), that contain every source line output lines [out_row0, out_row0 + out_rows)
+ * read (0, 0 if none): from the extremes of NY over the node lines those output lines lie between, so a few lines more than a
+ * pixel-by-pixel count.  include_output != 0: the output lines themselves as well (a band_mask that copies channels through
+ * reads them).  OIP_E_INVALID for arguments out of range or a node above 64 px in those node lines.  No context needed. */
+int oip_warp_grid_src_range(long out_row0, long out_rows, long L, const int32_t *nodes_y, int nx, int ny, long gy0, int sy,
+                            int include_output, long *first, long *last);
+
+/* host, no context needed: the field of `oip regfix` from a regcheck report (csrc/oip_warpfield.hpp; tests/_regfix_ref.py
+ * restates all three).
+ * oip_regfix_load_report: the `# oip regcheck ...` line gives scale, shift-x, shift-y and band2 as key=value tokens; the tile
+ *   lines x,y,dx,dy,score,flags must form a row-major regular lattice with x and y divisible by scale.  Node (j, i) lies at
+ *   (x / scale - shift-x, y / scale - shift-y) in image-2 pixels and carries rint(d * 1024) (fp64, ties to even) where
+ *   flags == 0; the other nodes are filled by oip_regfix_fill.  geom[8] = nx, ny, gx0, gy0, sx, sy, band2, tiles used.  nx * ny
+ *   may not exceed cap (nodes_x / nodes_y: room for cap values each); a step on an axis with one node is 1.  w, h > 0: the image
+ *   the field is for -- a node outside [0, w) x [0, h) is an error; 0: not checked.  OIP_E_IO when the file cannot be read,
+ *   OIP_E_INVALID (err says why) for a missing header token, a ragged or irregular lattice, a number that is not finite, a value
+ *   above 64 px, a node outside the image, no usable tile.
+ * oip_regfix_fill: set[q] != 0 marks the nodes that carry a value.  In passes, every unset node with k >= 1 set 4-neighbours as
+ *   of the pass's start gets floor((2 * sum + k) / (2 k)) per component and becomes set; until none is left.  OIP_E_INVALID if no
+ *   node is set.
+ * oip_regfix_smooth: `passes` (0 .. OIP_REGFIX_MAX_SMOOTH) times [1 2 1] along the node lines, then across them, with replicated
+ *   edges: (a + 2 b + c + 2) >> 2, arithmetic shift. */
+int oip_regfix_load_report(const char *path, long w, long h, int32_t *nodes_x, int32_t *nodes_y, long cap, long *geom, char *err, int errlen);
+int oip_regfix_fill(int32_t *nodes_x, int32_t *nodes_y, const uint8_t *set, int nx, int ny);
+int oip_regfix_smooth(int32_t *nodes_x, int32_t *nodes_y, int nx, int ny, int passes);
+
 /* ---- instrumentation --------------------------------------------------------------- */
 /* name + accumulated device time of the kernels launched through this context since the
  * last reset, measured with HIP events on the context's stream (off by default). */

@@ -29,6 +29,9 @@ from .capi import (  # noqa: F401
     mtfc_quantise,
     overview_levels,
     polyfit,
+    regfix_fill,
+    regfix_load_report,
+    regfix_smooth,
     remap_shift_src_range,
     rrc_dead_columns,
     rrc_fit_columns,
@@ -39,6 +42,7 @@ from .capi import (  # noqa: F401
     stretch_lut_u8,
     stt_mean,
     upsample_operator,
+    warp_grid_src_range,
     write_column_list,
     write_rrc_param_file,
     write_tiff_u8,

@@ -142,6 +142,11 @@ _SIGS = {
     "oip_match_grid": ([_i, _l, _i, _i, _i, C.POINTER(_i), _lp, C.POINTER(_i), _lp], _i),
     "oip_match_peak": ([C.POINTER(C.c_uint64), _i, _i, _d, _dp, _dp, _dp, C.POINTER(_i)], _i),
     "oip_match_summary": ([_dp, _dp, C.POINTER(_i), _l, _dp], _i),
+    "oip_warp_grid_bicubic_u16": ([_vp, _vp, _l, _l, _vp, _l, _l, _i, _l, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _l, _l, _i, _i], _i),
+    "oip_warp_grid_src_range": ([_l, _l, _l, C.POINTER(C.c_int32), _i, _i, _l, _i, _i, _lp, _lp], _i),
+    "oip_regfix_load_report": ([_cp, _l, _l, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _l, _lp, _cp, _i], _i),
+    "oip_regfix_fill": ([C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _i, _i], _i),
+    "oip_regfix_smooth": ([C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _i], _i),
     "oip_merge_subimages_be16": ([_vp, _vp, _vp, _i, _i, _i, _i], _i),
     "oip_profile_enable": ([_vp, _i], _i),
     "oip_profile_reset": ([_vp], _i),
@@ -457,6 +462,65 @@ def match_summary(dx, dy, flags) -> np.ndarray:
     if load_library().oip_match_summary(x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), f.ctypes.data_as(C.POINTER(_i)), x.size, out.ctypes.data_as(_dp)):
         raise ValueError("oip_match_summary: bad argument")
     return out
+
+
+_i32p = C.POINTER(C.c_int32)
+
+
+def _nodes(nodes_x, nodes_y):
+    """the two (ny, nx) int32 node arrays of a warp field, contiguous"""
+    x, y = np.ascontiguousarray(nodes_x, dtype=np.int32), np.ascontiguousarray(nodes_y, dtype=np.int32)
+    if x.ndim != 2 or x.shape != y.shape or x.size == 0:
+        raise ValueError("warp field: two (ny, nx) node arrays of one shape expected")
+    return x, y
+
+
+def warp_grid_src_range(out_row0: int, out_rows: int, L: int, nodes_y, gy0: int, sy: int, include_output: bool = False):
+    """source lines [first, last) that output lines [out_row0, out_row0 + out_rows) of Context.warp_grid_bicubic_u16 read
+    (include/oip_c.h: oip_warp_grid_src_range)"""
+    y = np.ascontiguousarray(nodes_y, dtype=np.int32)
+    if y.ndim != 2 or y.size == 0:
+        raise ValueError("warp field: a (ny, nx) node array expected")
+    first, last = _l(), _l()
+    if load_library().oip_warp_grid_src_range(out_row0, out_rows, L, y.ctypes.data_as(_i32p), y.shape[1], y.shape[0], gy0, sy, int(include_output),
+                                              C.byref(first), C.byref(last)):
+        raise ValueError("oip_warp_grid_src_range: bad argument")
+    return first.value, last.value
+
+
+def regfix_load_report(path: str, w: int = 0, h: int = 0, cap: int = 1 << 22):
+    """the field of a regcheck report: (nodes_x, nodes_y (ny, nx) int32 Q10, dict(gx0, gy0, sx, sy, band2, used)); w, h: the image
+    it is for, 0: not checked (include/oip_c.h: oip_regfix_load_report)"""
+    x, y = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    geom = (C.c_long * 8)()
+    err = C.create_string_buffer(1024)
+    rc = load_library().oip_regfix_load_report(os.fsencode(path), w, h, x.ctypes.data_as(_i32p), y.ctypes.data_as(_i32p), cap, geom, err, 1024)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode(errors="replace"))
+    nx, ny = geom[0], geom[1]
+    return (x[:nx * ny].reshape(ny, nx).copy(), y[:nx * ny].reshape(ny, nx).copy(),
+            dict(gx0=geom[2], gy0=geom[3], sx=geom[4], sy=geom[5], band2=geom[6], used=geom[7]))
+
+
+def regfix_fill(nodes_x, nodes_y, is_set):
+    """the nodes where is_set is false filled from their set 4-neighbours in passes (include/oip_c.h: oip_regfix_fill)"""
+    x, y = _nodes(nodes_x, nodes_y)
+    x, y = x.copy(), y.copy()
+    m = np.ascontiguousarray(is_set, dtype=np.uint8)
+    if m.shape != x.shape:
+        raise ValueError("regfix_fill: a mask of the nodes' shape expected")
+    if load_library().oip_regfix_fill(x.ctypes.data_as(_i32p), y.ctypes.data_as(_i32p), m.ctypes.data_as(C.POINTER(C.c_uint8)), x.shape[1], x.shape[0]):
+        raise ValueError("oip_regfix_fill: no node is set, or a value above 64 px")
+    return x, y
+
+
+def regfix_smooth(nodes_x, nodes_y, passes: int):
+    """`passes` times [1 2 1] along and across the node lines, replicated edges (include/oip_c.h: oip_regfix_smooth)"""
+    x, y = _nodes(nodes_x, nodes_y)
+    x, y = x.copy(), y.copy()
+    if load_library().oip_regfix_smooth(x.ctypes.data_as(_i32p), y.ctypes.data_as(_i32p), x.shape[1], x.shape[0], passes):
+        raise ValueError("oip_regfix_smooth: 0 <= passes <= 16 and values within 64 px expected")
+    return x, y
 
 
 FIT_MODES = {"reference": 0, "lstsq": 1}
@@ -879,6 +943,20 @@ class Context:
         out_rows = L if out_rows is None else out_rows
         self._ck(self.lib.oip_convolve_u16(self.h, _ptr(src), src_row0, src_rows, _ptr(dst), out_row0, out_rows, W, L, spp,
                                            t.ctypes.data_as(C.POINTER(C.c_int32)), t.shape[0], t.shape[1], valid_min))
+
+    # -- regfix
+    def warp_grid_bicubic_u16(self, src, dst, W, L, spp, nodes_x, nodes_y, gx0, gy0, sx, sy, band_mask=None, src_row0=0, src_rows=None,
+                              out_row0=0, out_rows=None):
+        """lines [out_row0, out_row0 + out_rows) of the W x L x spp raster whose lines [src_row0, src_row0 + src_rows) are at src,
+        resampled (OpenCV-exact bicubic) by the field of the (ny, nx) int32 Q10 node arrays (host) at (gx0 + i sx, gy0 + j sy);
+        band_mask: the channels resampled (default: all), the others are copied; not in place (include/oip_c.h:
+        oip_warp_grid_bicubic_u16)"""
+        x, y = _nodes(nodes_x, nodes_y)
+        src_rows = L if src_rows is None else src_rows
+        out_rows = L if out_rows is None else out_rows
+        band_mask = (1 << spp) - 1 if band_mask is None else band_mask
+        self._ck(self.lib.oip_warp_grid_bicubic_u16(self.h, _ptr(src), src_row0, src_rows, _ptr(dst), out_row0, out_rows, W, L, spp, band_mask,
+                                                    x.ctypes.data_as(_i32p), y.ctypes.data_as(_i32p), x.shape[1], x.shape[0], gx0, gy0, sx, sy))
 
     # -- despike
     def despike_u16(self, src, dst, W, L, spp, thr_abs, thr_rel_q8=0, valid_min=1, groups=1, coltab=None, count=None,

@@ -2,7 +2,8 @@
 // the RRC parameter file loader, its counterpart (column fit + writer), the seam fits of `oip stitch --balance` (per strip, per
 // block of lines, and the per-line tables), the shift
 // filtering / polynomial fit, the contrast stretch of `oip quicklook` (percentile limits, 8-bit table, 8-bit TIFF) and the
-// taps of `oip mtfc` (design, quantisation, kernel file) and the column lists and column table of `oip despike`.
+// taps of `oip mtfc` (design, quantisation, kernel file), the column lists and column table of `oip despike` and the field of
+// `oip regfix` (report, fill, smoothing: oip_warpfield.hpp).
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -14,6 +15,7 @@
 
 #include "oip_c.h"
 #include "oip_tiff.hpp"
+#include "oip_warpfield.hpp"
 
 // IMO::LoadRRCParamFile (imageop.h:140-192): three header lines (only the second -- the
 // column count -- is checked outside DEBUG builds), then one "k , b" row per column parsed
@@ -922,5 +924,54 @@ extern "C" int oip_despike_column_table(const int *bad, int nbad, int w, int gro
         }
     }
     if (longest_run) *longest_run = longest;
+    return OIP_OK;
+}
+
+// ---- oip regfix, host side: the node lattice of oip_warp_grid_bicubic_u16 from a regcheck report (oip_warpfield.hpp;
+// include/oip_c.h states the steps, tests/_regfix_ref.py restates them) ----------------------------------------------------
+extern "C" int oip_regfix_load_report(const char *path, long w, long h, int32_t *nodes_x, int32_t *nodes_y, long cap, long *geom, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *msg) {
+        if (err && errlen > 0) snprintf(err, errlen, "%s", msg);
+        return code;
+    };
+    if (!path || !geom || cap < 0 || (cap > 0 && (!nodes_x || !nodes_y)) || w < 0 || h < 0) return fail(OIP_E_INVALID, "oip_regfix_load_report: bad argument");
+    try {
+        const OIPGPU::WarpField f = OIPGPU::ParseRegReport(OIPGPU::ReadRegReport(path), w, h);
+        const long n = (long)f.nx * f.ny;
+        if (n > cap) return fail(OIP_E_INVALID, ("oip_regfix_load_report: " + std::to_string(n) + " nodes, room for " + std::to_string(cap)).c_str());
+        std::copy(f.X.begin(), f.X.end(), nodes_x);
+        std::copy(f.Y.begin(), f.Y.end(), nodes_y);
+        const long g[8] = {f.nx, f.ny, f.gx0, f.gy0, f.sx, f.sy, f.band2, f.used};
+        std::copy(g, g + 8, geom);
+    } catch (const std::invalid_argument &e) {
+        return fail(OIP_E_INVALID, e.what());
+    } catch (const std::exception &e) {
+        return fail(OIP_E_IO, e.what());
+    }
+    return OIP_OK;
+}
+
+static bool regfix_lattice_ok(const int32_t *nodes_x, const int32_t *nodes_y, int nx, int ny)
+{
+    return nodes_x && nodes_y && nx >= 1 && ny >= 1 && (long)nx * ny <= OIPGPU::kWarpMaxNodes;
+}
+
+extern "C" int oip_regfix_fill(int32_t *nodes_x, int32_t *nodes_y, const uint8_t *set, int nx, int ny)
+{
+    if (!regfix_lattice_ok(nodes_x, nodes_y, nx, ny) || !set) return OIP_E_INVALID;
+    for (long q = 0; q < (long)nx * ny; ++q)                       // the sums of four stay far inside 64 bits whatever is given; the results
+        if (set[q] && (nodes_x[q] < -OIP_WARP_MAX_Q10 || nodes_x[q] > OIP_WARP_MAX_Q10 || nodes_y[q] < -OIP_WARP_MAX_Q10 || nodes_y[q] > OIP_WARP_MAX_Q10))
+            return OIP_E_INVALID;                                  // lie between the values they average, so inside the range as well
+    return OIPGPU::FillField(nodes_x, nodes_y, set, nx, ny) ? OIP_OK : OIP_E_INVALID;
+}
+
+extern "C" int oip_regfix_smooth(int32_t *nodes_x, int32_t *nodes_y, int nx, int ny, int passes)
+{
+    if (!regfix_lattice_ok(nodes_x, nodes_y, nx, ny) || passes < 0 || passes > OIP_REGFIX_MAX_SMOOTH) return OIP_E_INVALID;
+    for (long q = 0; q < (long)nx * ny; ++q)                       // (a + 2 b + c + 2 stays inside int32)
+        if (nodes_x[q] < -OIP_WARP_MAX_Q10 || nodes_x[q] > OIP_WARP_MAX_Q10 || nodes_y[q] < -OIP_WARP_MAX_Q10 || nodes_y[q] > OIP_WARP_MAX_Q10) return OIP_E_INVALID;
+    OIPGPU::SmoothField(nodes_x, nx, ny, passes);
+    OIPGPU::SmoothField(nodes_y, nx, ny, passes);
     return OIP_OK;
 }

@@ -19,13 +19,15 @@
 //   oip regcheck --image1 A [--image2 B] [--band1 k] [--band2 k] [--scale F] [--shift-x N] [--shift-y N] [--tile T] [--search S]
 //                               how well two rasters are registered: tile matching (ZNCC), a shift and a score per tile and a
 //                               summary in <A>.REG.CSV, see run_regcheck()
+//   oip regfix --report R.CSV --image B [--bands k[,k...]|all] [--smooth N] [--width N] [-o OUT]   resamples image 2 of a regcheck
+//                               report by the shift field the report holds, so that it lands on image 1, see run_regfix()
 //   oip -v | --version          prints 1.1
 // plus --width N (pixels per PAN line; the reference hard-codes 12288, oipshared.h:28).
 // `auxsep` is outside this build.  TIFF input and output go through oip_tiff.hpp (uncompressed and LZW, with
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
 // --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
-// despike, overviews and regcheck sub-commands.
+// despike, overviews, regcheck and regfix sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -209,7 +211,13 @@ void usage()
          "             [--tile T] (multiple of 8, 8..128; default 64) [--search S] (1..16; default 4) [--step N] (default T)\n"
          "             [--valid-min N] [--valid-max N] (samples outside are no data; default 1, 65535) [--min-score X] (default 0.5)\n"
          "             flags: 1 no data in the tile, 2 flat, 4 peak on the border of the search range, 8 score below --min-score\n"
-         "             [--width N] [--width2 N] (RAW: samples per line of A / B) [-o,--out report.csv] [--force]");
+         "             [--width N] [--width2 N] (RAW: samples per line of A / B) [-o,--out report.csv] [--force]\n"
+         "  regfix     --report R.CSV --image B: resamples B, the image 2 of the regcheck report R.CSV (TIFF of 1 or 4 samples, or\n"
+         "             single-band RAW), by the shift field the report's tiles hold, so that it lands on the report's image 1; flagged\n"
+         "             tiles are filled from their neighbours, the field is bilinear between tiles, the resampling the product's\n"
+         "             bicubic; the output has the container of the input and is written to <stem>.REGFIX.<ext>:\n"
+         "             [--bands k[,k...]|all] (1-based; default: the report's band2; the other bands are copied)\n"
+         "             [--smooth N] (0..16 passes of [1 2 1] over the field; default 0) [--width N] [-o,--out FILE] [--force]");
 }
 
 int run_prestitch(const std::vector<std::string> &args, int width)
@@ -727,6 +735,48 @@ int run_regcheck(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip regfix --report R.CSV --image B: resampling of the image 2 of a regcheck report by the report's shift field (RunRegfix).
+// Bad option values end in 105, a missing --report or --image in 106, a report that cannot be used in 2, all before a device
+// is touched.
+int run_regfix(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--report", "--image", "--bands", "--smooth", "--width", "--out"};
+    sp.flags = {"--force", "--bil"};
+    sp.alias = {{"-o", "--out"}};
+    Parsed p = parse(sp, args);
+    require(p, "--report");
+    require(p, "--image");
+    existing_file(p, "--report");
+    existing_file(p, "--image");
+    RegfixOptions o;
+    o.report = p.str("--report");
+    o.smooth = p.integer("--smooth", 0);
+    if (o.smooth < 0 || o.smooth > OIP_REGFIX_MAX_SMOOTH) throw cli_error(105, "--smooth: 0 <= N <= 16 expected");
+    o.width = p.integer("--width", width);
+    if (o.width <= 0) throw cli_error(105, "--width: a positive line width expected");
+    if (p.has("--bands")) {
+        const std::string b = p.str("--bands");
+        if (b == "all") {
+            o.allBands = true;
+        } else {
+            size_t a = 0;
+            while (a <= b.size()) {
+                size_t c = b.find(',', a);
+                if (c == std::string::npos) c = b.size();
+                const std::string t = b.substr(a, c - a);
+                if (t.empty() || t.size() > 1 || t[0] < '1' || t[0] > '0' + MSS_BANDS) throw cli_error(105, "--bands: band indices 1..4 separated by commas, or all, expected");
+                o.bands.push_back(t[0] - '0');
+                a = c + 1;
+            }
+        }
+    }
+    o.bil = p.flag.count("--bil") != 0;
+    o.force = p.flag.count("--force") != 0;
+    RunRegfix(p.str("--image"), p.str("--out"), o);
+    return 0;
+}
+
 }  // namespace
 
 static int oip_main(int argc, const char *argv[]);
@@ -779,6 +829,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "despike") return run_despike({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "overviews") return run_overviews({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regcheck") return run_regcheck({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "regfix") return run_regfix({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "auxsep")
                 throw std::invalid_argument("auxsep (down-link de-framing) is outside this build: run the reference's auxsep, then this tool");
             if (args.empty()) { usage(); return 0; }

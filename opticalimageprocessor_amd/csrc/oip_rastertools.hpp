@@ -1,5 +1,5 @@
 // oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, overviews,
-// regcheck) above the host layer of oip_host.hpp: what they check before a device is touched, the one driver that streams a
+// regcheck, regfix) above the host layer of oip_host.hpp: what they check before a device is touched, the one driver that streams a
 // RAW strip through the device in line blocks (geometry: oip_stripplan.hpp), the resident filter of a TIFF product, and the
 // six tools.
 #pragma once
@@ -7,6 +7,7 @@
 #include "oip_host.hpp"
 #include "oip_regreport.hpp"
 #include "oip_stripplan.hpp"
+#include "oip_warpfield.hpp"
 
 namespace OIPGPU {
 
@@ -53,7 +54,7 @@ inline std::string FilterOutputPath(const std::string &file, const std::string &
     return path;
 }
 
-// OIP_MTFC_BLOCK_LINES / OIP_DESPIKE_BLOCK_LINES / OIP_OVERVIEWS_BLOCK_LINES (test hooks: several blocks on a small image); 0 without one
+// OIP_MTFC_BLOCK_LINES / OIP_DESPIKE_BLOCK_LINES / OIP_OVERVIEWS_BLOCK_LINES / OIP_REGFIX_BLOCK_LINES (test hooks: several blocks on a small image); 0 without one
 inline long BlockLinesHook(const char *name) { const char *e = getenv(name); return e ? atol(e) : 0; }
 
 // ---- the strip-streaming driver ---------------------------------------------------------------------------------
@@ -771,6 +772,93 @@ inline void RunRegcheck(const std::string &file, const std::string &out, const R
     if (fclose(f) != 0 || !ok) throw std::runtime_error("write file [" + outPath + "] failed");
     OLOG("regcheck: %s", RegSummaryLine(sum).c_str());
     OLOG("Report written to '%s' in %.3f seconds.", outPath.c_str(), total.tick());
+}
+
+// ---- oip regfix: resample a raster by the shift field regcheck measured -----------------------------------------------------
+// `oip regcheck` reports, per tile of a regular lattice, where image 1's content is found in image 2.  This tool turns that
+// report into a displacement field (oip_warpfield.hpp: the tiles without a flag, the others filled from their neighbours,
+// optional smoothing) and resamples image 2 by it (oip_warp_grid_bicubic_u16: the product's OpenCV-exact bicubic with a phase
+// of its own per pixel), so that image 2 lands on image 1.  The three uses are regcheck's: a band of an aligned MSS product,
+// an MSS band against PAN, CCD 2 on the overlap.  The output has the container of the input.  Not in the reference.
+struct RegfixOptions {
+    std::string report;
+    std::vector<int> bands;                 // 1-based; empty: the report's band2
+    bool allBands = false;
+    int smooth = 0;
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    bool bil = false;                       // refused, as regcheck refuses it
+    bool force = false;
+};
+
+// everything that can be refused without a device: the container, the report against the image's size, the bands, the output;
+// returns the output path
+inline std::string RegfixCheck(const std::string &file, const std::string &out, const RegfixOptions &o, bool *isTiff, WarpField *field, int *bandMask)
+{
+    const std::string ext = RasterContainer(file, "regfix");
+    *isTiff = ext == ".tiff";
+    if (o.bil) throw std::invalid_argument("regfix: a BIL RAW strip is not supported: split the bands first (the default action writes them)");
+    if (o.smooth < 0 || o.smooth > OIP_REGFIX_MAX_SMOOTH) throw usage_error("--smooth: 0 <= N <= 16 expected");
+    int w = 0, spp = 1;
+    long h = 0;
+    if (*isTiff) {
+        TiffLayout lay;
+        read_tiff_u16(file, &w, &h, &spp, nullptr, &lay);
+        if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument("regfix: a TIFF of 1 or 4 samples per pixel expected");
+    } else {
+        if (o.width <= 0) throw std::invalid_argument("--width: a positive line width expected");
+        w = o.width;
+        h = RawLineCount(file, "image", (size_t)o.width * BYTES_PER_PIXEL);
+    }
+    *field = ParseRegReport(ReadRegReport(o.report), w, h);
+    SmoothField(field->X.data(), field->nx, field->ny, o.smooth);
+    SmoothField(field->Y.data(), field->nx, field->ny, o.smooth);
+    std::vector<int> bands = o.bands;
+    if (o.allBands) { bands.clear(); for (int b = 1; b <= spp; ++b) bands.push_back(b); }
+    else if (bands.empty()) bands.push_back(field->band2);
+    *bandMask = 0;
+    for (int b : bands) {
+        if (b < 1 || b > spp) throw usage_error("--bands: band index out of range (1.." + std::to_string(spp) + ")");
+        *bandMask |= 1 << (b - 1);
+    }
+    return FilterOutputPath(file, out, OIP_REGFIX_SUFFIX, ext, "regfix", o.force);
+}
+
+inline void RunRegfix(const std::string &file, const std::string &out, const RegfixOptions &o)
+{
+    bool isTiff = false;
+    WarpField f;
+    int mask = 0;
+    const std::string outPath = RegfixCheck(file, out, o, &isTiff, &f, &mask);
+    int minX = INT_MAX, maxX = INT_MIN, minY = INT_MAX, maxY = INT_MIN;
+    for (size_t q = 0; q < f.X.size(); ++q) {
+        minX = std::min(minX, f.X[q]); maxX = std::max(maxX, f.X[q]);
+        minY = std::min(minY, f.Y[q]); maxY = std::max(maxY, f.Y[q]);
+    }
+    OLOG("regfix: %d x %d nodes at (%ld, %ld), step %d x %d, %ld of %ld tiles used, smooth %d", f.nx, f.ny, f.gx0, f.gy0, f.sx, f.sy, f.used,
+         (long)f.nx * f.ny, o.smooth);
+    OLOG("regfix: dx in [%.4f, %.4f], dy in [%.4f, %.4f] px, band mask %d", minX / 1024.0, maxX / 1024.0, minY / 1024.0, maxY / 1024.0, mask);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    size_t bytes = 0;
+    if (isTiff) {
+        bytes = FilterTiffResident(file, outPath, "regfix", "resampled", [&](const uint16_t *src, uint16_t *dst, int w, long h, int spp) {
+            ck(oip_warp_grid_bicubic_u16(ctx, src, 0, h, dst, 0, h, w, h, spp, mask, f.X.data(), f.Y.data(), f.nx, f.ny, f.gx0, f.gy0, f.sx, f.sy));
+        });
+    } else {
+        // the kernel runs per line block of the strip; the halo holds the largest vertical shift and the bicubic window
+        const int W = o.width;
+        const size_t lineBytes = (size_t)W * BYTES_PER_PIXEL;
+        const long L = RawLineCount(file, "image", lineBytes);
+        const long halo = (f.maxAbsY() + 1023) / 1024 + 3;
+        StreamStrip(file, StripPlan{0, L, L, halo, StripBlockLines(lineBytes, 1, BlockLinesHook("OIP_REGFIX_BLOCK_LINES")), lineBytes}, &outPath,
+                   [&](const uint16_t *d, long s0, long sn, uint16_t *q, long r, long m) {
+                       ck(oip_warp_grid_bicubic_u16(ctx, d, s0, sn, q, r, m, W, L, 1, 1, f.X.data(), f.Y.data(), f.nx, f.ny, f.gx0, f.gy0, f.sx, f.sy));
+                   });
+        bytes = (size_t)L * lineBytes;
+    }
+    const double es = total.tick();
+    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
 }
 
 }  // namespace OIPGPU
