@@ -795,6 +795,42 @@ int oip_regfix_load_report(const char *path, long w, long h, int32_t *nodes_x, i
 int oip_regfix_fill(int32_t *nodes_x, int32_t *nodes_y, const uint8_t *set, int nx, int ny);
 int oip_regfix_smooth(int32_t *nodes_x, int32_t *nodes_y, int nx, int ny, int passes);
 
+/* ---- pansharpen: fusion of the PAN strip with the aligned MSS product (`oip pansharpen`; not in the reference) ----
+ * Smoothing-filter intensity modulation, fused_b = up(MSS_b) * PAN / up(low(PAN)), stated to the bit; tests/_pansharpen_ref.py
+ * restates it.  P: PAN, W x Hp u16.  M: the MSS product, w x h pixels of 4 pixel-interleaved u16 samples.  off >= 0: the first
+ * PAN line used.  W = 4 w; hh = min(h, (Hp - off) / 4) >= 1 MSS lines are used; the product is 4 w x 4 hh x 4 u16,
+ * pixel-interleaved.  MSS pixel (j, i) covers PAN pixels (off + 4 j .. off + 4 j + 3, 4 i .. 4 i + 3), regcheck --scale 4's
+ * convention.
+ * 1. Lm (w x hh) = (S + 8) >> 4 of the 4 x 4 PAN block: oip_decimate_box_u16 with factor 4 on full blocks.
+ * 2. Up-sampling by 4, the same for each band of M and for Lm.  Output coordinate x: cell i = x >> 2, phase r = x & 3; first tap
+ *    c0 = i - 2 for r in {0, 1}, i - 1 for r in {2, 3}; taps clamp(c0 + k, 0, n - 1), k = 0 .. 3.  Weights: the OpenCV cubic
+ *    (a = -0.75) at t = 5/8, 7/8, 1/8, 3/8 times 2048, exact integers, each row summing to 2048:
+ *      r=0: -135  873 1535 -225      r=1: -21  235 1981 -147      r=2: -147 1981  235  -21      r=3: -225 1535  873 -135
+ *    along the lines  Hq = (sum wx[k] s[k] + 128) >> 8   (arithmetic shift; 3 fractional bits), then across them, same indexing,
+ *    U = clamp((sum wy[k] Hq[k] + 1024) >> 11, 0, 8 * 65535).  Everything fits int32 (|Hq| <= 616439, 616439 * 2768 + 1024 <
+ *    2^31) and both operands of every product fit 24 signed bits.
+ * 3. Modulation in IEEE single precision, every operation rounded on its own, nothing contracted.  UL = U(Lm), U_b = U(M_b), both
+ *    exact in f32.  g = UL == 0 ? 0.125f : min(__fdiv_rn((float)P, (float)UL), gmax), gmax = (float)max_gain * 0.125f;
+ *    out_b = saturate_u16(rintf(__fmul_rn((float)U_b, g))), ties to even.  One division per pixel, shared by the four bands.
+ * 4. Counters: pixels with UL == 0; pixels whose quotient was above gmax.
+ * oip_pansharpen_sfim_u16: d_mss and d_low are the WHOLE low-resolution rasters (w x h; h is the hh above), d_pan and d_dst point
+ * at output line out_row0 of their rasters -- a caller can stream PAN and product in line blocks; any out_row0 / out_rows with
+ * 0 <= out_row0, out_row0 + out_rows <= 4 h, multiples of 4 or not; out_rows == 0 is a no-op.  Pitches in SAMPLES; lines and
+ * offsets in 64 bits.  d_stats: NULL, or two uint64 on the device that the two counters of the call's pixels are ADDED to.
+ * Asynchronous on the context's stream.  OIP_E_INVALID: a NULL or odd pointer, a pitch shorter than its line (4 w, 4 w, w,
+ * 16 w), w or h < 1, lines outside [0, 4 h), max_gain outside [1, OIP_PANSHARPEN_MAX_GAIN], a product that overlaps an input.
+ * A PAN or MSS base off an 8-byte boundary or pitch off a multiple of 4 samples, or a product off a 16-byte boundary or a pitch
+ * off a multiple of 8, takes a slower kernel (2-byte accesses) with the same bytes. */
+#define OIP_PANSHARPEN_SUFFIX ".PSH"
+#define OIP_PANSHARPEN_DEF_GAIN 4
+#define OIP_PANSHARPEN_MAX_GAIN 64
+int oip_pansharpen_sfim_u16(oip_ctx *ctx, const uint16_t *d_pan, long pan_pitch, const uint16_t *d_mss, long mss_pitch,
+                            const uint16_t *d_low, long low_pitch, int w, long h, uint16_t *d_dst, long dst_pitch, long out_row0,
+                            long out_rows, int max_gain, uint64_t *d_stats);
+/* host, no context needed: the geometry rule above.  out_w = 4 w, out_h = 4 hh, mss_lines = hh (each may be NULL).
+ * OIP_E_INVALID for W != 4 w, w or h < 1, a negative line_offset, fewer than 4 PAN lines from line_offset on. */
+int oip_pansharpen_geometry(long W, long Hp, long w, long h, long line_offset, long *out_w, long *out_h, long *mss_lines);
+
 /* ---- instrumentation --------------------------------------------------------------- */
 /* name + accumulated device time of the kernels launched through this context since the
  * last reset, measured with HIP events on the context's stream (off by default). */

@@ -28,6 +28,7 @@ from .capi import (  # noqa: F401
     mtfc_load_kernel,
     mtfc_quantise,
     overview_levels,
+    pansharpen_geometry,
     polyfit,
     regfix_fill,
     regfix_load_report,

@@ -147,6 +147,8 @@ _SIGS = {
     "oip_regfix_load_report": ([_cp, _l, _l, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _l, _lp, _cp, _i], _i),
     "oip_regfix_fill": ([C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _i, _i], _i),
     "oip_regfix_smooth": ([C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _i], _i),
+    "oip_pansharpen_sfim_u16": ([_vp, _vp, _l, _vp, _l, _vp, _l, _i, _l, _vp, _l, _l, _l, _i, _vp], _i),
+    "oip_pansharpen_geometry": ([_l, _l, _l, _l, _l, _lp, _lp, _lp], _i),
     "oip_merge_subimages_be16": ([_vp, _vp, _vp, _i, _i, _i, _i], _i),
     "oip_profile_enable": ([_vp, _i], _i),
     "oip_profile_reset": ([_vp], _i),
@@ -521,6 +523,15 @@ def regfix_smooth(nodes_x, nodes_y, passes: int):
     if load_library().oip_regfix_smooth(x.ctypes.data_as(_i32p), y.ctypes.data_as(_i32p), x.shape[1], x.shape[0], passes):
         raise ValueError("oip_regfix_smooth: 0 <= passes <= 16 and values within 64 px expected")
     return x, y
+
+
+def pansharpen_geometry(W: int, Hp: int, w: int, h: int, line_offset: int = 0):
+    """(out_w, out_h, mss_lines) of `oip pansharpen` for a W x Hp PAN raster used from line_offset on and a w x h MSS product
+    (include/oip_c.h: oip_pansharpen_geometry)"""
+    ow, oh, ml = _l(), _l(), _l()
+    if load_library().oip_pansharpen_geometry(W, Hp, w, h, line_offset, C.byref(ow), C.byref(oh), C.byref(ml)):
+        raise ValueError("oip_pansharpen_geometry: W = 4 w, w, h >= 1, line_offset >= 0 and 4 PAN lines from it on expected")
+    return ow.value, oh.value, ml.value
 
 
 FIT_MODES = {"reference": 0, "lstsq": 1}
@@ -957,6 +968,18 @@ class Context:
         band_mask = (1 << spp) - 1 if band_mask is None else band_mask
         self._ck(self.lib.oip_warp_grid_bicubic_u16(self.h, _ptr(src), src_row0, src_rows, _ptr(dst), out_row0, out_rows, W, L, spp, band_mask,
                                                     x.ctypes.data_as(_i32p), y.ctypes.data_as(_i32p), x.shape[1], x.shape[0], gx0, gy0, sx, sy))
+
+    # -- pansharpen
+    def pansharpen_sfim_u16(self, pan, mss, low, w, h, dst, max_gain=4, stats=None, out_row0=0, out_rows=None, pan_pitch=None, mss_pitch=None,
+                            low_pitch=None, dst_pitch=None):
+        """lines [out_row0, out_row0 + out_rows) of the 4 w x 4 h x 4 product fused from the PAN lines under them (pan: the first of
+        them), the whole w x h x 4 MSS product and the whole w x h low-resolution PAN (decimate_box_u16, factor 4); dst: the first
+        of the lines; stats: None or two uint64 on the device that the counters (UL == 0, gain cut) are added to; pitches in
+        samples (include/oip_c.h: oip_pansharpen_sfim_u16)"""
+        out_rows = 4 * h - out_row0 if out_rows is None else out_rows
+        self._ck(self.lib.oip_pansharpen_sfim_u16(self.h, _ptr(pan), 4 * w if pan_pitch is None else pan_pitch, _ptr(mss),
+                                                  4 * w if mss_pitch is None else mss_pitch, _ptr(low), w if low_pitch is None else low_pitch, w, h,
+                                                  _ptr(dst), 16 * w if dst_pitch is None else dst_pitch, out_row0, out_rows, max_gain, _ptr(stats)))
 
     # -- despike
     def despike_u16(self, src, dst, W, L, spp, thr_abs, thr_rel_q8=0, valid_min=1, groups=1, coltab=None, count=None,

@@ -2,8 +2,8 @@
 // the RRC parameter file loader, its counterpart (column fit + writer), the seam fits of `oip stitch --balance` (per strip, per
 // block of lines, and the per-line tables), the shift
 // filtering / polynomial fit, the contrast stretch of `oip quicklook` (percentile limits, 8-bit table, 8-bit TIFF) and the
-// taps of `oip mtfc` (design, quantisation, kernel file), the column lists and column table of `oip despike` and the field of
-// `oip regfix` (report, fill, smoothing: oip_warpfield.hpp).
+// taps of `oip mtfc` (design, quantisation, kernel file), the column lists and column table of `oip despike`, the field of
+// `oip regfix` (report, fill, smoothing: oip_warpfield.hpp) and the geometry rule of `oip pansharpen`.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -973,5 +973,17 @@ extern "C" int oip_regfix_smooth(int32_t *nodes_x, int32_t *nodes_y, int nx, int
         if (nodes_x[q] < -OIP_WARP_MAX_Q10 || nodes_x[q] > OIP_WARP_MAX_Q10 || nodes_y[q] < -OIP_WARP_MAX_Q10 || nodes_y[q] > OIP_WARP_MAX_Q10) return OIP_E_INVALID;
     OIPGPU::SmoothField(nodes_x, nx, ny, passes);
     OIPGPU::SmoothField(nodes_y, nx, ny, passes);
+    return OIP_OK;
+}
+
+// ---- oip pansharpen, host side: which MSS lines a PAN raster covers from line_offset on, and the product's size
+// (include/oip_c.h states the rule, tests/_pansharpen_ref.py restates it) ------------------------------------------------
+extern "C" int oip_pansharpen_geometry(long W, long Hp, long w, long h, long line_offset, long *out_w, long *out_h, long *mss_lines)
+{
+    if (w < 1 || h < 1 || w > (1L << 26) || W != 4 * w || line_offset < 0 || Hp < 4 || line_offset > Hp - 4) return OIP_E_INVALID;
+    const long hh = std::min(h, (Hp - line_offset) / 4);
+    if (out_w) *out_w = 4 * w;
+    if (out_h) *out_h = 4 * hh;
+    if (mss_lines) *mss_lines = hh;
     return OIP_OK;
 }

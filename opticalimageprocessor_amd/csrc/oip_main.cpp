@@ -21,13 +21,16 @@
 //                               summary in <A>.REG.CSV, see run_regcheck()
 //   oip regfix --report R.CSV --image B [--bands k[,k...]|all] [--smooth N] [--width N] [-o OUT]   resamples image 2 of a regcheck
 //                               report by the shift field the report holds, so that it lands on image 1, see run_regfix()
+//   oip pansharpen --pan P --mss M [--line-offset N] [--max-gain G] [--width N] [-o OUT] [--force] [--overviews [--levels N]]
+//                               fuses the PAN strip and the aligned MSS product into a 4-band product at PAN resolution, see
+//                               run_pansharpen()
 //   oip -v | --version          prints 1.1
 // plus --width N (pixels per PAN line; the reference hard-codes 12288, oipshared.h:28).
 // `auxsep` is outside this build.  TIFF input and output go through oip_tiff.hpp (uncompressed and LZW, with
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
 // --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
-// despike, overviews, regcheck and regfix sub-commands.
+// despike, overviews, regcheck, regfix and pansharpen sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -217,7 +220,13 @@ void usage()
          "             tiles are filled from their neighbours, the field is bilinear between tiles, the resampling the product's\n"
          "             bicubic; the output has the container of the input and is written to <stem>.REGFIX.<ext>:\n"
          "             [--bands k[,k...]|all] (1-based; default: the report's band2; the other bands are copied)\n"
-         "             [--smooth N] (0..16 passes of [1 2 1] over the field; default 0) [--width N] [-o,--out FILE] [--force]");
+         "             [--smooth N] (0..16 passes of [1 2 1] over the field; default 0) [--width N] [-o,--out FILE] [--force]\n"
+         "  pansharpen --pan P --mss M: fuses the PAN strip P (TIFF of 1 sample, or single-band RAW) and the aligned MSS product M (TIFF\n"
+         "             of 4 samples, a quarter of P's line) into a 4-band product at PAN resolution: every band up-sampled by 4 (cubic)\n"
+         "             and multiplied by PAN / up-sampled 4 x 4 mean of PAN; written to <stem of M>.PSH.TIFF:\n"
+         "             [--line-offset N] (first PAN line used; default 0) [--max-gain G] (1..64, the ratio is cut there; default 4)\n"
+         "             [--width N] (RAW: samples per PAN line) [-o,--out FILE] [--force]\n"
+         "             [--overviews] [--levels N] also write the product's pyramid to <output>.ovr, as `overviews` does");
 }
 
 int run_prestitch(const std::vector<std::string> &args, int width)
@@ -777,6 +786,36 @@ int run_regfix(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip pansharpen --pan P --mss M: the 4-band product at PAN resolution (RunPansharpen).  Bad option values end in 105, a missing
+// --pan or --mss in 106, inputs that cannot be used (sample counts, W != 4 w, too few lines) in 2, all before a device is touched.
+int run_pansharpen(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--pan", "--mss", "--line-offset", "--max-gain", "--width", "--out", "--levels"};
+    sp.flags = {"--force", "--overviews"};
+    sp.alias = {{"-o", "--out"}};
+    Parsed p = parse(sp, args);
+    require(p, "--pan");
+    require(p, "--mss");
+    existing_file(p, "--pan");
+    existing_file(p, "--mss");
+    PansharpenOptions o;
+    o.pan = p.str("--pan");
+    o.mss = p.str("--mss");
+    o.lineOffset = p.integer("--line-offset", 0);
+    if (o.lineOffset < 0) throw cli_error(105, "--line-offset: N >= 0 expected");
+    o.maxGain = p.integer("--max-gain", OIP_PANSHARPEN_DEF_GAIN);
+    if (o.maxGain < 1 || o.maxGain > OIP_PANSHARPEN_MAX_GAIN) throw cli_error(105, "--max-gain: 1 <= G <= 64 expected");
+    o.width = p.integer("--width", width);
+    if (o.width <= 0) throw cli_error(105, "--width: a positive line width expected");
+    if (p.has("--levels") && !p.has("--overviews")) throw cli_error(107, "--levels requires --overviews");
+    o.overviews = p.has("--overviews");
+    o.pyramid.levels = overview_levels(p);
+    o.force = p.flag.count("--force") != 0;
+    RunPansharpen(p.str("--out"), o);
+    return 0;
+}
+
 }  // namespace
 
 static int oip_main(int argc, const char *argv[]);
@@ -830,6 +869,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "overviews") return run_overviews({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regcheck") return run_regcheck({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regfix") return run_regfix({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "pansharpen") return run_pansharpen({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "auxsep")
                 throw std::invalid_argument("auxsep (down-link de-framing) is outside this build: run the reference's auxsep, then this tool");
             if (args.empty()) { usage(); return 0; }

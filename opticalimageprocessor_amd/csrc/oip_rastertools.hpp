@@ -1,7 +1,7 @@
 // oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, overviews,
-// regcheck, regfix) above the host layer of oip_host.hpp: what they check before a device is touched, the one driver that streams a
+// regcheck, regfix, pansharpen) above the host layer of oip_host.hpp: what they check before a device is touched, the one driver that streams a
 // RAW strip through the device in line blocks (geometry: oip_stripplan.hpp), the resident filter of a TIFF product, and the
-// six tools.
+// tools.
 #pragma once
 
 #include "oip_host.hpp"
@@ -857,6 +857,114 @@ inline void RunRegfix(const std::string &file, const std::string &out, const Reg
                    });
         bytes = (size_t)L * lineBytes;
     }
+    const double es = total.tick();
+    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+}
+
+// ---- oip pansharpen: fuse the PAN strip and the aligned MSS product -------------------------------------------------------------
+// The two products of one scene -- the stitched PAN strip and the stitched, band-aligned MSS product at a quarter of its
+// resolution -- become one 4-band product at PAN resolution by smoothing-filter intensity modulation: each band is up-sampled by
+// 4 and multiplied by PAN / up(low(PAN)), low(PAN) being the 4 x 4 box mean (oip_decimate_box_u16) -- the detail PAN holds beyond
+// the MSS resolution, as a ratio (include/oip_c.h: oip_pansharpen_sfim_u16 states it to the bit).  All rasters are resident, as
+// in `oip stitch` of TIFFs: about 1.33 bytes of device memory per output byte.  Not in the reference.
+struct PansharpenOptions {
+    std::string pan, mss;
+    long lineOffset = 0;                    // the first PAN line used
+    int maxGain = OIP_PANSHARPEN_DEF_GAIN;
+    int width = OIP_PIXELS_PER_LINE;        // RAW PAN: samples per line
+    bool force = false;
+    bool overviews = false;                 // also <output>.ovr, as `stitch --overviews`
+    OverviewOptions pyramid;
+};
+
+struct PansharpenGeometry {
+    bool panTiff = false;
+    int W = 0, w = 0;
+    long Hp = 0, h = 0, outW = 0, outH = 0, mssLines = 0;
+};
+
+// everything that can be refused without a device: the containers, the sample counts, the geometry, the output; returns the
+// output path
+inline std::string PansharpenCheck(const std::string &out, const PansharpenOptions &o, PansharpenGeometry *g)
+{
+    g->panTiff = RasterContainer(o.pan, "pansharpen") == ".tiff";
+    if (RasterContainer(o.mss, "pansharpen") != ".tiff") throw std::invalid_argument("pansharpen: the MSS product is a TIFF of 4 samples per pixel");
+    if (o.maxGain < 1 || o.maxGain > OIP_PANSHARPEN_MAX_GAIN) throw usage_error("--max-gain: 1 <= G <= 64 expected");
+    if (o.lineOffset < 0) throw usage_error("--line-offset: N >= 0 expected");
+    int spp = 1;
+    TiffLayout lay;
+    if (g->panTiff) {
+        read_tiff_u16(o.pan, &g->W, &g->Hp, &spp, nullptr, &lay);
+        if (spp != 1) throw std::invalid_argument("pansharpen: a PAN TIFF of 1 sample per pixel expected, not " + std::to_string(spp));
+    } else {
+        if (o.width <= 0) throw std::invalid_argument("--width: a positive line width expected");
+        g->W = o.width;
+        g->Hp = RawLineCount(o.pan, "PAN", (size_t)o.width * BYTES_PER_PIXEL);
+    }
+    read_tiff_u16(o.mss, &g->w, &g->h, &spp, nullptr, &lay);
+    if (spp != MSS_BANDS) throw std::invalid_argument("pansharpen: an MSS TIFF of 4 samples per pixel expected, not " + std::to_string(spp));
+    if (g->W != 4L * g->w)
+        throw std::invalid_argument("pansharpen: the PAN line (" + std::to_string(g->W) + ") is not 4 times the MSS line (" + std::to_string(g->w) + ")");
+    if (oip_pansharpen_geometry(g->W, g->Hp, g->w, g->h, o.lineOffset, &g->outW, &g->outH, &g->mssLines) != OIP_OK)
+        throw std::invalid_argument("pansharpen: the PAN raster has " + std::to_string(g->Hp) + " lines: fewer than 4 from --line-offset " +
+                                    std::to_string(o.lineOffset) + " on");
+    const std::string path = out.empty() ? IMO::BuildOutputFilePath(o.mss, OIP_PANSHARPEN_SUFFIX, ".TIFF") : out;
+    if (to_lower(std::filesystem::path(path).extension().string()) != ".tiff") throw std::invalid_argument("pansharpen: the output is a TIFF");
+    for (const std::string &q : o.overviews ? std::vector<std::string>{path, path + OIP_OVERVIEW_SUFFIX} : std::vector<std::string>{path}) {
+        struct stat st;
+        if (stat(q.c_str(), &st) != 0) continue;
+        if (std::filesystem::equivalent(q, o.pan) || std::filesystem::equivalent(q, o.mss)) throw std::invalid_argument("output file [" + q + "] is an input image");
+        if (!o.force) throw std::runtime_error("output file [" + q + "] exists: pansharpen does not replace a file without --force");
+    }
+    return path;
+}
+
+inline void RunPansharpen(const std::string &out, const PansharpenOptions &o)
+{
+    PansharpenGeometry g;
+    const std::string outPath = PansharpenCheck(out, o, &g);
+    OLOG("pansharpen: PAN %d x %ld from line %ld, MSS %d x %ld -> %ld x %ld x %d, max gain %d", g.W, g.Hp, o.lineOffset, g.w, g.h, g.outW, g.outH,
+         MSS_BANDS, o.maxGain);
+    if (g.mssLines < g.h) OLOG("pansharpen: the PAN raster ends first: the last %ld MSS lines are left unused", g.h - g.mssLines);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    DevBuf<uint16_t> pan, mss;
+    int w = 0, spp = 0;
+    long h = 0;
+    if (g.panTiff) {
+        OLOG("Reading image from file `%s' ...", o.pan.c_str());
+        read_tiff_to_device(o.pan, &w, &h, &spp, pan);
+        if (w != g.W || h != g.Hp || spp != 1) throw std::runtime_error("pansharpen: the PAN file changed while it was read");
+    } else {
+        pan.alloc((size_t)g.W * g.Hp);
+        pan.load_file(o.pan, (size_t)g.W * g.Hp);
+    }
+    OLOG("Reading image from file `%s' ...", o.mss.c_str());
+    read_tiff_to_device(o.mss, &w, &h, &spp, mss);
+    if (w != g.w || h != g.h || spp != MSS_BANDS) throw std::runtime_error("pansharpen: the MSS file changed while it was read");
+
+    const uint16_t *p0 = pan.p + (size_t)o.lineOffset * g.W;
+    DevBuf<uint16_t> low((size_t)g.w * g.mssLines), res((size_t)g.outW * g.outH * MSS_BANDS);
+    DevBuf<uint64_t> stats(2);
+    const uint64_t none[2] = {0, 0};
+    uint64_t count[2] = {0, 0};
+    stats.upload(none, 2);
+    stop_watch sw;
+    ck(oip_decimate_box_u16(ctx, p0, g.W, g.W, g.outH, 1, 4, low.p, g.w, 0));
+    ck(oip_pansharpen_sfim_u16(ctx, p0, g.W, mss.p, (long)g.w * MSS_BANDS, low.p, g.w, g.w, g.mssLines, res.p, g.outW * MSS_BANDS, 0, g.outH, o.maxGain,
+                               stats.p));
+    stats.download(count, 2);
+    const double px = (double)g.outW * g.outH;
+    OLOG("pansharpen: fused in %.3f seconds; low-resolution PAN zero on %.4f %% of the pixels (gain 1), gain cut at %d on %.4f %%", sw.tick(),
+         100.0 * count[0] / px, o.maxGain, 100.0 * count[1] / px);
+    pan.release();
+    mss.release();
+    low.release();
+    OLOG("Write fused image to file '%s' ...", outPath.c_str());
+    write_tiff_from_device(outPath, res.p, (int)g.outW, g.outH, MSS_BANDS, tiff_compression(TIFF_LZW), false);
+    if (o.overviews) write_overviews_of_device_image(outPath + OIP_OVERVIEW_SUFFIX, res.p, (int)g.outW, g.outH, MSS_BANDS, o.pyramid);
+    const size_t bytes = (size_t)g.outW * g.outH * MSS_BANDS * BYTES_PER_PIXEL;
     const double es = total.tick();
     OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
 }
