@@ -640,6 +640,68 @@ int oip_load_column_list(const char *path, int w, int *cols, int cap, int *n, ch
 int oip_write_column_list(const char *path, const int *cols, int n, const char *comment, char *err, int errlen);
 int oip_despike_column_table(const int *bad, int nbad, int w, int groups, int32_t *tab, int *longest_run, char *err, int errlen);
 
+/* ---- noise: the noise-level function of a strip or product (`oip noise`; not in the reference) ----------------------
+ * sigma as a function of the signal level (read noise plus shot noise), measured on the image itself by the local-means /
+ * local-standard-deviations method (Gao 1993): many small blocks, and per signal level the mode of their standard deviations.
+ * A block that holds an edge or a ramp would put the scene's variance into that mode; an exact integer F test on the block's
+ * four quadrants keeps such blocks out.  What `oip despike --noise` derives its two threshold parameters from. */
+#define OIP_NOISE_SUFFIX        ".NOISE"   /* <stem>.NOISE.CSV */
+#define OIP_NOISE_KEY_NODATA     0x00FF
+#define OIP_NOISE_KEY_STRUCTURED 0x01FF
+
+/* One u16 key per B x B block and channel of a u16 raster window, the one pass over the full-size image.  Raster conventions
+ * are oip_decimate_box_u16's: rows lines of w pixels of spp samples (1, or 4 pixel-interleaved), lines `pitch` SAMPLES apart,
+ * the window inside the lines of its raster.  block B is 8 or 16.  Blocks are anchored at the window's first sample; only whole
+ * blocks exist, floor(w / B) per line of blocks and floor(rows / B) lines of blocks: trailing columns and lines are ignored.
+ * Plane c of the keys is at d_keys + c * key_plane_stride (keys), its lines key_pitch keys apart.  For a block and channel,
+ * with v its n = B * B samples and Sq[0..3] the sums of its four (B/2 x B/2) quadrants, all in unsigned 64-bit integers:
+ *   S1 = sum v,  S2 = sum v * v,  D = n * S2 - S1 * S1           (n (n - 1) times the sample variance)
+ *   E = 4 * (Sq[0]^2 + Sq[1]^2 + Sq[2]^2 + Sq[3]^2) - S1 * S1    (n times the between-quadrant sum of squares: D - E >= 0)
+ *   any v < valid_min or v > valid_max:   key = 0x00FF           (no data)
+ *   E * (n - 4) > 12 * (D - E):           key = 0x01FF           (structured: the F ratio of the between-quadrant mean square
+ *                                                                 E / 3 to the within-quadrant one (D - E) / (n - 4) exceeds
+ *                                                                 4; equality passes, and so does a constant block)
+ *   otherwise  level = min(255, (S1 / n) >> level_shift)
+ *              q     = min(254, isqrt(floor(16 * D / (n * (n - 1)))))      isqrt exact: the sample standard deviation in
+ *              key   = level << 8 | q                                      quarter DN
+ * The largest product is E * (n - 4) < 2^56 at B = 16.  The sentinels have q = 255, which no real key has.  The keys are 16-bit:
+ * oip_histogram_u16 over a key plane gives the 256 x 256 (level x q) counts of the band, additive over line blocks, with
+ * hist[0x00FF] and hist[0x01FF] the no-data and structured counts.  A strip cut into calls at lines that are multiples of B
+ * (writing from key line first / B on) gives the keys of one call.  Asynchronous on the context's stream.  OIP_E_INVALID: block
+ * not 8 or 16, spp not 1 or 4, level_shift outside 0..8, a valid range that is empty or outside 0..65535, pitch < w * spp,
+ * key_pitch < floor(w / B).  rows < B or w < B is a no-op.  A pitch that is not a multiple of 8 samples, or a window that does
+ * not start on a 16-byte boundary, takes a slower kernel with the same keys. */
+int oip_noise_blocks_u16(oip_ctx *ctx, const uint16_t *d_src, long pitch, int w, long rows, int spp, int block, int level_shift,
+                         int valid_min, int valid_max, uint16_t *d_keys, long key_pitch, size_t key_plane_stride);
+
+/* The sigma of every signal level from the key histogram of a band, host, fp64 in this order.  hist: the 65536 counts of
+ * oip_histogram_u16 over a key plane, hist[l * 256 + q].  Per level l:
+ *   N = sum over q = 0..254 of hist[l][q]      (real blocks only: the sentinels' q = 255 never counts);  blocks[l] = N
+ *   usable: N >= max(min_blocks, 1), and a mode k* exists: the smallest q in 0..253 with the largest non-zero count
+ *   r = k* / 8 + 1 (integers), window [max(0, k* - r), min(253, k* + r)], c_w = the count inside it
+ *   and 10 * c_w >= 3 * N: the distribution is peaked around its mode, which a level reached only by textured blocks is not
+ *   sigma[l] = 0.25 * (sum over the window, q ascending, of ((double)q + 0.5) * (double)c_q) / (double)c_w
+ * sigma[l] = -1 for a level that is not usable.  *n_usable (may be NULL): the usable levels.  No context needed. */
+int oip_noise_levels(const uint64_t *hist, uint64_t min_blocks, double *sigma, uint64_t *blocks, int *n_usable);
+
+/* sigma^2 = a + b * mu fitted to the usable levels (sigma[l] >= 0) of oip_noise_levels, host, fp64.  Per usable level
+ * mu = ((double)l + 0.5) * 2^level_shift, v = sigma * sigma, weight w = (double)blocks[l]; plain sums in ascending l:
+ *   sw = sum w, mx = (sum w mu) / sw, mv = (sum w v) / sw, sxx = sum w (mu - mx)^2, sxy = sum w (mu - mx) (v - mv)
+ *   b = sxy / sxx, a = mv - b * mx
+ *   fewer than two usable levels, or sxx == 0, or b < 0:   b = 0, a = mv
+ *   else a < 0:                                            a = 0, b = (sum w mu v) / (sum w mu mu)
+ * *mu_ref: the mu of the first usable level, ascending, at which twice the cumulative block count reaches the total (integers).
+ * OIP_E_RUNTIME (err says so) without a usable level; OIP_E_INVALID for level_shift outside 0..8. */
+int oip_noise_fit(const double *sigma, const uint64_t *blocks, int level_shift, double *a, double *b, double *mu_ref, char *err, int errlen);
+
+/* The two threshold parameters of oip_despike_u16 from a noise model: the tangent to the concave k * sqrt(a + b * mu) at mu_ref,
+ * which lies above the curve everywhere.  fp64:
+ *   st = sqrt(a + b * mu_ref),  R = k * b / (2 * st),  N0 = k * st - R * mu_ref
+ *   thr_rel_q8 = ceil(256 * R),  thr_abs = ceil(N0) + 1          (the + 1 covers the floor in despike's >> 8)
+ * so that thr_abs + ((m * thr_rel_q8) >> 8) >= k * sqrt(a + b * m) for every m in 0..65535.  OIP_E_INVALID unless a, b, mu_ref
+ * are finite and >= 0 and k is finite and > 0; OIP_E_RUNTIME (err says why) if st == 0, thr_rel_q8 > 256 or thr_abs > 65535. */
+int oip_noise_despike_threshold(double a, double b, double mu_ref, double k, int *thr_abs, int *thr_rel_q8, char *err, int errlen);
+
 /* The strips of an LZW TIFF product, encoded on the device (cv::imwrite's TIFF encoder behind preproc.h:167-185 and GDAL's
  * COMPRESS=LZW PREDICTOR=2 behind imageop.h:460-567 do this on the host, strip by strip).  d_img: rows x width x spp u16,
  * interleaved, in file sample order (oip_permute_u16x4 first where cv::imwrite / a band map reorder); spp 1 or 4; strip k

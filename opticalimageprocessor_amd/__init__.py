@@ -27,6 +27,9 @@ from .capi import (  # noqa: F401
     mtfc_design3,
     mtfc_load_kernel,
     mtfc_quantise,
+    noise_despike_threshold,
+    noise_fit,
+    noise_levels,
     overview_levels,
     pansharpen_geometry,
     polyfit,

@@ -136,6 +136,10 @@ _SIGS = {
     "oip_load_column_list": ([_cp, _i, C.POINTER(_i), _i, C.POINTER(_i), _cp, _i], _i),
     "oip_write_column_list": ([_cp, C.POINTER(_i), _i, _cp, _cp, _i], _i),
     "oip_despike_column_table": ([C.POINTER(_i), _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(_i), _cp, _i], _i),
+    "oip_noise_blocks_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _i, _i, _i, _vp, _l, _sz], _i),
+    "oip_noise_levels": ([C.POINTER(C.c_uint64), C.c_uint64, _dp, C.POINTER(C.c_uint64), C.POINTER(_i)], _i),
+    "oip_noise_fit": ([_dp, C.POINTER(C.c_uint64), _i, _dp, _dp, _dp, _cp, _i], _i),
+    "oip_noise_despike_threshold": ([_d, _d, _d, _d, C.POINTER(_i), C.POINTER(_i), _cp, _i], _i),
     "oip_halve_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _vp, _l], _i),
     "oip_overview_levels": ([_i, _l], _i),
     "oip_match_tiles_u16": ([_vp, _vp, _l, _i, _vp, _l, _i, _i, _l, _i, _i, _i, _l, _i, _l, _i, _l, _i, _i, _vp, _vp], _i),
@@ -287,6 +291,46 @@ def despike_column_table(bad, w: int, groups: int = 1):
     if rc:
         raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
     return tab, run.value
+
+
+def noise_levels(hist, min_blocks: int = 100):
+    """(sigma (256,) float64 with -1 for a level that is not usable, blocks (256,) uint64, usable levels) from the (65536,)
+    uint64 histogram of a key plane of Context.noise_blocks_u16 (include/oip_c.h: oip_noise_levels)"""
+    lib = load_library()
+    h = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
+    assert h.size == 65536, h.size
+    sigma, blocks, n = np.zeros(256), np.zeros(256, np.uint64), _i()
+    rc = lib.oip_noise_levels(h.ctypes.data_as(C.POINTER(C.c_uint64)), min_blocks, sigma.ctypes.data_as(_dp),
+                              blocks.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n))
+    if rc:
+        raise ValueError("oip_noise_levels: bad argument")
+    return sigma, blocks, n.value
+
+
+def noise_fit(sigma, blocks, level_shift: int):
+    """(a, b, mu_ref) of sigma^2 = a + b mu over the usable levels of noise_levels (include/oip_c.h: oip_noise_fit)"""
+    lib = load_library()
+    s = _dbl(sigma, 256)
+    n = np.ascontiguousarray(blocks, dtype=np.uint64).reshape(-1)
+    assert n.size == 256, n.size
+    a, b, mu = _d(), _d(), _d()
+    err = C.create_string_buffer(1024)
+    rc = lib.oip_noise_fit(s.ctypes.data_as(_dp), n.ctypes.data_as(C.POINTER(C.c_uint64)), level_shift, C.byref(a), C.byref(b), C.byref(mu), err, 1024)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    return a.value, b.value, mu.value
+
+
+def noise_despike_threshold(a: float, b: float, mu_ref: float, k: float = 5.0):
+    """(thr_abs, thr_rel_q8) of Context.despike_u16 from a noise model: the tangent at mu_ref to k sqrt(a + b mu)
+    (include/oip_c.h: oip_noise_despike_threshold)"""
+    lib = load_library()
+    ta, q8 = _i(), _i()
+    err = C.create_string_buffer(1024)
+    rc = lib.oip_noise_despike_threshold(a, b, mu_ref, k, C.byref(ta), C.byref(q8), err, 1024)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    return ta.value, q8.value
 
 
 SEAM_MODES = {"moments": 0, "gain": 1, "offset": 2}
@@ -992,6 +1036,14 @@ class Context:
         out_rows = L if out_rows is None else out_rows
         self._ck(self.lib.oip_despike_u16(self.h, _ptr(src), src_row0, src_rows, _ptr(dst), out_row0, out_rows, W, L, spp, groups,
                                           _ptr(coltab), thr_abs, thr_rel_q8, valid_min, _ptr(count)))
+
+    # -- noise
+    def noise_blocks_u16(self, src, pitch, w, rows, spp, block, level_shift, keys, key_pitch, key_plane_stride=0, valid_min=1,
+                         valid_max=65535):
+        """one u16 key per block x block block and channel of rows lines of w pixels of spp samples (lines `pitch` samples
+        apart) into spp planes of key lines key_pitch keys apart (include/oip_c.h: oip_noise_blocks_u16)"""
+        self._ck(self.lib.oip_noise_blocks_u16(self.h, _ptr(src), pitch, w, rows, spp, block, level_shift, valid_min, valid_max, _ptr(keys),
+                                               key_pitch, key_plane_stride))
 
     # -- instrumentation
     def merge_subimages_be16(self, tiles, out, vparts, hparts, sub_lines, sub_cols):

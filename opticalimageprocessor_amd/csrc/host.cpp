@@ -987,3 +987,101 @@ extern "C" int oip_pansharpen_geometry(long W, long Hp, long w, long h, long lin
     if (mss_lines) *mss_lines = hh;
     return OIP_OK;
 }
+
+// ---- oip noise, host side: the sigma of every signal level from a band's key histogram, the fit sigma^2 = a + b mu, and the
+// despike threshold that follows from it (include/oip_c.h states the operation order, tests/_noise_ref.py restates it) ------
+extern "C" int oip_noise_levels(const uint64_t *hist, uint64_t min_blocks, double *sigma, uint64_t *blocks, int *n_usable)
+{
+    if (!hist || !sigma || !blocks) return OIP_E_INVALID;
+    const uint64_t need = min_blocks > 1 ? min_blocks : 1;
+    int usable = 0;
+    for (int l = 0; l < 256; ++l) {
+        const uint64_t *h = hist + (size_t)l * 256;
+        uint64_t N = 0;
+        for (int q = 0; q <= 254; ++q) N += h[q];
+        blocks[l] = N;
+        sigma[l] = -1.0;
+        if (N < need) continue;
+        int mode = -1;
+        for (int q = 0; q <= 253; ++q)
+            if (h[q] > (mode < 0 ? 0 : h[mode])) mode = q;
+        if (mode < 0) continue;
+        const int r = mode / 8 + 1, lo = std::max(0, mode - r), hi = std::min(253, mode + r);
+        uint64_t cw = 0;
+        for (int q = lo; q <= hi; ++q) cw += h[q];
+        // (N < 2^61 for any histogram of real blocks: the products below do not wrap)
+        if (10 * cw < 3 * N) continue;
+        double sum = 0.0;
+        for (int q = lo; q <= hi; ++q) sum += ((double)q + 0.5) * (double)h[q];
+        sigma[l] = 0.25 * sum / (double)cw;
+        ++usable;
+    }
+    if (n_usable) *n_usable = usable;
+    return OIP_OK;
+}
+
+extern "C" int oip_noise_fit(const double *sigma, const uint64_t *blocks, int level_shift, double *a, double *b, double *mu_ref, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *msg) {
+        if (err && errlen > 0) snprintf(err, errlen, "%s", msg);
+        return code;
+    };
+    if (!sigma || !blocks || !a || !b || !mu_ref || level_shift < 0 || level_shift > 8) return fail(OIP_E_INVALID, "oip_noise_fit: bad argument");
+    const double scale = (double)(1 << level_shift);
+    auto mu_of = [&](int l) { return ((double)l + 0.5) * scale; };
+    double sw = 0.0, swx = 0.0, swv = 0.0, swxv = 0.0, swxx = 0.0;
+    uint64_t total = 0;
+    int count = 0;
+    for (int l = 0; l < 256; ++l) {
+        if (!(sigma[l] >= 0.0)) continue;
+        const double mu = mu_of(l), v = sigma[l] * sigma[l], w = (double)blocks[l];
+        sw += w; swx += w * mu; swv += w * v; swxv += w * mu * v; swxx += w * mu * mu;
+        total += blocks[l];
+        ++count;
+    }
+    if (count == 0 || total == 0) return fail(OIP_E_RUNTIME, "oip_noise_fit: no usable signal level");
+    const double mx = swx / sw, mv = swv / sw;
+    double sxx = 0.0, sxy = 0.0;
+    for (int l = 0; l < 256; ++l) {
+        if (!(sigma[l] >= 0.0)) continue;
+        const double mu = mu_of(l), v = sigma[l] * sigma[l], w = (double)blocks[l];
+        sxx += w * (mu - mx) * (mu - mx);
+        sxy += w * (mu - mx) * (v - mv);
+    }
+    double bb = 0.0, aa = mv;
+    if (count >= 2 && sxx != 0.0) {
+        bb = sxy / sxx;
+        aa = mv - bb * mx;
+        if (bb < 0.0) { bb = 0.0; aa = mv; }
+        else if (aa < 0.0) { aa = 0.0; bb = swxv / swxx; }
+    }
+    uint64_t cum = 0;
+    for (int l = 0; l < 256; ++l) {
+        if (!(sigma[l] >= 0.0)) continue;
+        cum += blocks[l];
+        if (2 * cum >= total) { *mu_ref = mu_of(l); break; }
+    }
+    *a = aa;
+    *b = bb;
+    return OIP_OK;
+}
+
+extern "C" int oip_noise_despike_threshold(double a, double b, double mu_ref, double k, int *thr_abs, int *thr_rel_q8, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *fmt, auto... v) {
+        if (err && errlen > 0) snprintf(err, errlen, fmt, v...);
+        return code;
+    };
+    if (!thr_abs || !thr_rel_q8 || !std::isfinite(a) || !std::isfinite(b) || !std::isfinite(mu_ref) || !std::isfinite(k) || a < 0.0 || b < 0.0 ||
+        mu_ref < 0.0 || !(k > 0.0))
+        return fail(OIP_E_INVALID, "%s", "oip_noise_despike_threshold: bad argument");
+    const double st = std::sqrt(a + b * mu_ref);
+    if (st == 0.0) return fail(OIP_E_RUNTIME, "%s", "oip_noise_despike_threshold: the noise model gives sigma 0 at the reference level");
+    const double R = k * b / (2.0 * st), N0 = k * st - R * mu_ref;
+    const double q8 = std::ceil(256.0 * R), ta = std::ceil(N0) + 1.0;
+    if (!(q8 <= 256.0)) return fail(OIP_E_RUNTIME, "oip_noise_despike_threshold: the slope %.6g of the threshold exceeds 1", R);
+    if (!(ta <= 65535.0)) return fail(OIP_E_RUNTIME, "oip_noise_despike_threshold: the threshold %.6g exceeds 65535", ta);
+    *thr_abs = (int)ta;
+    *thr_rel_q8 = (int)q8;
+    return OIP_OK;
+}

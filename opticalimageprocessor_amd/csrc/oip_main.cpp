@@ -13,7 +13,10 @@
 //   oip quicklook IMAGE [-o OUT.TIFF] [--factor 16 ...]   8-bit browse image of a strip or product, see run_quicklook()
 //   oip mtfc IMAGE [-o OUT] (--kernel FILE | --mtf-x M --mtf-y M)   MTF-compensation filter of a strip or product, see run_mtfc()
 //   oip despike IMAGE [-o OUT] [--threshold N] [--relative R] [--bad-columns FILE] [--bil]   repair of a raw strip ahead of RRC:
-//                               bad columns interpolated, impulse pixels replaced by a conditional 3 x 3 median, see run_despike()
+//                               bad columns interpolated, impulse pixels replaced by a conditional 3 x 3 median, see run_despike();
+//                               --noise REPORT [--k-sigma K] takes the threshold from the report of `oip noise`
+//   oip noise IMAGE [-o OUT.csv] [--block 8|16] [--bits N] [--min-blocks N] [--bil]   the noise-level function of a strip or
+//                               product (sigma per signal level, the fit sigma^2 = a + b mu, SNR) in <stem>.NOISE.CSV, see run_noise()
 //   oip overviews IMAGE [-o OUT] [--levels N] [--valid-min N]   the reduced-resolution pyramid of a strip or product as
 //                               <IMAGE>.ovr beside it; `stitch --overviews [--levels N]` writes its product's, see run_overviews()
 //   oip regcheck --image1 A [--image2 B] [--band1 k] [--band2 k] [--scale F] [--shift-x N] [--shift-y N] [--tile T] [--search S]
@@ -30,7 +33,7 @@
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
 // --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
-// despike, overviews, regcheck, regfix and pansharpen sub-commands.
+// despike, noise, overviews, regcheck, regfix and pansharpen sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -109,7 +112,7 @@ Parsed parse(const Spec &sp, const std::vector<std::string> &args)
     return p;
 }
 
-// The tools with one positional argument (quicklook, mtfc, despike, overviews): IMAGE, an existing regular file, is the first argument
+// The tools with one positional argument (quicklook, mtfc, despike, noise, overviews): IMAGE, an existing regular file, is the first argument
 // that is neither an option nor the value of one (an option's value stays with it, alias or not); the rest is parsed as usual.
 Parsed parse_with_image(const Spec &sp, const std::vector<std::string> &args, std::string *image)
 {
@@ -195,12 +198,23 @@ void usage()
          "             | --mtf-x M --mtf-y M (the MTF at Nyquist across / along the lines, 0 < M <= 1) [--max-gain G] (default 2.0)\n"
          "             [--valid-min N] (samples below are no data and pass through; default 1) [--width N] [--force]\n"
          "  despike    IMAGE.RAW|IMAGE.TIFF: repair of a raw strip ahead of RRC; the output has the container of the input and is\n"
-         "             written to <stem>.DSPK.<ext> in the working directory.  At least one of --threshold and --bad-columns:\n"
+         "             written to <stem>.DSPK.<ext> in the working directory.  At least one of --threshold, --noise and --bad-columns:\n"
          "             [-o,--out FILE] [--threshold N] a sample further than N (0..65535) + R * median from the median of its 3 x 3\n"
          "             neighbourhood is replaced by it (there is no default: measure the sensor's noise) [--relative R] (0..1, default 0)\n"
+         "             [--noise REPORT] (in place of --threshold / --relative) N and R from the report of `oip noise`: the tangent at the\n"
+         "             report's reference level to K times its noise model, the largest over its bands [--k-sigma K] (1..100; default 5,\n"
+         "             the usual convention, nothing measured)\n"
          "             [--bad-columns FILE] (RAW; text: 0-based columns, # comments) interpolated from their good neighbours\n"
          "             [--bil] (RAW: the MSS line layout, bands never mix) [--valid-min N] (samples below are no data; default 1)\n"
          "             [--width N] [--report FILE] (`column count' of the replaced samples) [--force]\n"
+         "  noise      IMAGE.RAW|IMAGE.TIFF: the noise-level function of a strip or product, measured on the image itself: the standard\n"
+         "             deviation of every B x B block without an edge or a ramp in it, per signal level the mode of those, and the fit\n"
+         "             sigma^2 = a + b * level; level_lo,level_hi,blocks,sigma,snr per band and level and the fit per band are written\n"
+         "             to <stem>.NOISE.CSV in the working directory, which `despike --noise` reads:\n"
+         "             [-o,--out FILE] [--block 8|16] (default 8) [--bits N] (8..16, the sensor's depth: 256 levels of 2^(N-8); default 12)\n"
+         "             [--valid-min N] [--valid-max N] (a block with a sample outside is no data; default 1, 65535)\n"
+         "             [--min-blocks N] (blocks a level needs; default 100) [--bil] (RAW: the MSS line layout, bands measured apart)\n"
+         "             [--width N] [--line-offset N] (a multiple of the block) [--lines N] [--force]\n"
          "  overviews  IMAGE.RAW|IMAGE.TIFF: the reduced-resolution pyramid of a strip or product, every band at 16 bits, each level\n"
          "             the 2 x 2 average of the one before; written to IMAGE.ovr beside the image, where GDAL-based viewers look for it:\n"
          "             [-o,--out FILE] [--levels N] (1..16; default: until a level fits 256 x 256) [--valid-min N] (samples below are\n"
@@ -646,13 +660,16 @@ int run_mtfc(const std::vector<std::string> &args, int width)
 int run_despike(const std::vector<std::string> &args, int width)
 {
     Spec sp;
-    sp.valued = {"--out", "--threshold", "--relative", "--bad-columns", "--valid-min", "--width", "--report"};
+    sp.valued = {"--out", "--threshold", "--relative", "--bad-columns", "--valid-min", "--width", "--report", "--noise", "--k-sigma"};
     sp.flags = {"--bil", "--force"};
     sp.alias = {{"-o", "--out"}};
     std::string image;
     Parsed p = parse_with_image(sp, args, &image);
-    // nobody has measured this sensor's noise: there is no default threshold, and without one only the listed columns are repaired
-    if (!p.has("--threshold") && !p.has("--bad-columns")) throw usage_error("--threshold N or --bad-columns FILE expected");
+    // there is no default threshold: it is given, or follows from the noise `oip noise` measured (--noise), and without one only
+    // the listed columns are repaired
+    if (p.has("--noise") && (p.has("--threshold") || p.has("--relative"))) throw cli_error(107, "--noise excludes --threshold and --relative");
+    if (p.has("--k-sigma") && !p.has("--noise")) throw cli_error(107, "--k-sigma requires --noise");
+    if (!p.has("--threshold") && !p.has("--noise") && !p.has("--bad-columns")) throw usage_error("--threshold N, --noise REPORT or --bad-columns FILE expected");
     if (p.has("--relative") && !p.has("--threshold")) throw cli_error(107, "--relative requires --threshold");
     DespikeOptions o;
     o.width = p.integer("--width", width);
@@ -670,7 +687,48 @@ int run_despike(const std::vector<std::string> &args, int width)
     if (p.has("--bad-columns") && o.badColumns.empty()) throw cli_error(105, "--bad-columns: a file name expected");
     o.report = p.str("--report");
     o.force = p.flag.count("--force") != 0;
+    existing_file(p, "--noise");
+    // --k-sigma 5 is the usual convention for an impulse, nothing measured
+    const double kSigma = p.real("--k-sigma", 5.0);
+    if (!(kSigma >= 1.0 && kSigma <= 100.0)) throw cli_error(105, "--k-sigma: 1 <= K <= 100 expected");
+    if (p.has("--noise")) DespikeNoiseThreshold(p.str("--noise"), kSigma, &o);
     RunDespike(image, p.str("--out"), o);
+    return 0;
+}
+
+// oip noise IMAGE: the noise-level function of a strip (.RAW, --width samples per line, with --bil the MSS line layout) or a
+// product (.TIFF of 1 or 4 samples) as <stem>.NOISE.CSV (RunNoise).  IMAGE is the one positional argument, as for mtfc.  Bad
+// values end in 105 before any file is read.
+int run_noise(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--out", "--block", "--bits", "--valid-min", "--valid-max", "--min-blocks", "--width", "--line-offset", "--lines"};
+    sp.flags = {"--bil", "--force"};
+    sp.alias = {{"-o", "--out"}};
+    std::string image;
+    Parsed p = parse_with_image(sp, args, &image);
+    NoiseOptions o;
+    o.width = p.integer("--width", width);
+    o.bil = p.flag.count("--bil") != 0;
+    o.block = p.integer("--block", 8);
+    if (o.block != 8 && o.block != 16) throw cli_error(105, "--block: 8 or 16 expected");
+    o.bits = p.integer("--bits", 12);
+    if (o.bits < 8 || o.bits > 16) throw cli_error(105, "--bits: 8 <= N <= 16 expected");
+    o.validMin = p.integer("--valid-min", 1);
+    o.validMax = p.integer("--valid-max", 65535);
+    if (o.validMin < 0 || o.validMax > 65535 || o.validMin > o.validMax) throw cli_error(105, "--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
+    o.minBlocks = p.integer("--min-blocks", 100);
+    if (o.minBlocks < 0) throw cli_error(105, "--min-blocks: N >= 0 expected");
+    o.lineOffset = p.integer("--line-offset", 0);
+    o.lines = p.integer("--lines", 0);
+    if (o.lineOffset < 0 || o.lines < 0) throw cli_error(105, "--line-offset, --lines: non-negative values expected");
+    if (o.lineOffset % o.block != 0) throw cli_error(105, "--line-offset: a multiple of --block expected");
+    o.force = p.flag.count("--force") != 0;
+    char buf[256];
+    snprintf(buf, sizeof buf, " block=%d bits=%d valid-min=%d valid-max=%d min-blocks=%ld bil=%d line-offset=%ld lines=%ld", o.block, o.bits, o.validMin,
+             o.validMax, o.minBlocks, o.bil ? 1 : 0, o.lineOffset, o.lines);
+    o.params = "oip noise image=" + image + buf + " columns=band,level_lo,level_hi,blocks,sigma,snr";
+    RunNoise(image, p.str("--out"), o);
     return 0;
 }
 
@@ -866,6 +924,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "quicklook") return run_quicklook({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "mtfc") return run_mtfc({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "despike") return run_despike({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "noise") return run_noise({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "overviews") return run_overviews({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regcheck") return run_regcheck({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regfix") return run_regfix({args.begin() + 1, args.end()}, width);

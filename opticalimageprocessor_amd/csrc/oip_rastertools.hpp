@@ -1,10 +1,11 @@
-// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, overviews,
+// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, noise, overviews,
 // regcheck, regfix, pansharpen) above the host layer of oip_host.hpp: what they check before a device is touched, the one driver that streams a
 // RAW strip through the device in line blocks (geometry: oip_stripplan.hpp), the resident filter of a TIFF product, and the
 // tools.
 #pragma once
 
 #include "oip_host.hpp"
+#include "oip_noisereport.hpp"
 #include "oip_regreport.hpp"
 #include "oip_stripplan.hpp"
 #include "oip_warpfield.hpp"
@@ -54,7 +55,7 @@ inline std::string FilterOutputPath(const std::string &file, const std::string &
     return path;
 }
 
-// OIP_MTFC_BLOCK_LINES / OIP_DESPIKE_BLOCK_LINES / OIP_OVERVIEWS_BLOCK_LINES / OIP_REGFIX_BLOCK_LINES (test hooks: several blocks on a small image); 0 without one
+// OIP_MTFC_BLOCK_LINES / OIP_DESPIKE_BLOCK_LINES / OIP_NOISE_BLOCK_LINES / OIP_OVERVIEWS_BLOCK_LINES / OIP_REGFIX_BLOCK_LINES (test hooks: several blocks on a small image); 0 without one
 inline long BlockLinesHook(const char *name) { const char *e = getenv(name); return e ? atol(e) : 0; }
 
 // ---- the strip-streaming driver ---------------------------------------------------------------------------------
@@ -572,6 +573,143 @@ inline void RunDespike(const std::string &file, const std::string &out, const De
     }
     const double es = total.tick();
     OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+}
+
+// `oip despike --noise REPORT [--k-sigma K]`: the two threshold parameters from the report of `oip noise`, each the maximum
+// over the report's bands of oip_noise_despike_threshold.  No device is touched.
+inline void DespikeNoiseThreshold(const std::string &report, double kSigma, DespikeOptions *o)
+{
+    std::vector<NoiseModel> models;
+    std::string err;
+    if (!ParseNoiseReport(report, &models, &err)) throw std::runtime_error(err);
+    if (!NoiseDespikeThreshold(models, kSigma, &o->thrAbs, &o->thrRelQ8, &err)) throw std::runtime_error("noise report [" + report + "], " + err);
+    o->hasThreshold = true;
+    OLOG("despike: %g sigma of the noise model of [%s] (%zu band%s): threshold %d, relative %d / 256", kSigma, report.c_str(), models.size(),
+         models.size() == 1 ? "" : "s", o->thrAbs, o->thrRelQ8);
+}
+
+// ---- oip noise: the noise-level function of a strip or product ----------------------------------------------------------
+// The measuring side of despike's threshold.  One read-only pass gives every B x B block a key (oip_noise_blocks_u16: signal
+// level and standard deviation, or a sentinel for a block with no data or with structure); per band the histogram of the keys
+// (oip_histogram_u16), the sigma of every level (oip_noise_levels) and the fit sigma^2 = a + b mu (oip_noise_fit) follow, and
+// go to <stem>.NOISE.CSV (oip_noisereport.hpp).  A RAW strip streams through in blocks of lines that are multiples of B; a TIFF
+// product is resident.  Not in the reference.
+struct NoiseOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    bool bil = false;                       // RAW input: the MSS line layout, 4 bands of width / 4 next to each other
+    int block = 8, bits = 12;               // level_shift = bits - 8
+    int validMin = 1, validMax = 65535;
+    long minBlocks = 100;
+    long lineOffset = 0, lines = 0;         // lines == 0: to the end of the image
+    bool force = false;
+    std::string params;                     // the first line of the report
+};
+
+// everything that can be refused without a device; returns the output path and whether the input is a TIFF
+inline std::string NoiseCheck(const std::string &file, const std::string &out, const NoiseOptions &o, bool *isTiff)
+{
+    *isTiff = RasterContainer(file, "noise") == ".tiff";
+    if (o.block != 8 && o.block != 16) throw usage_error("--block: 8 or 16 expected");
+    if (o.bits < 8 || o.bits > 16) throw usage_error("--bits: 8 <= N <= 16 expected");
+    if (o.validMin < 0 || o.validMax > 65535 || o.validMin > o.validMax) throw usage_error("--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
+    if (o.minBlocks < 0 || o.lineOffset < 0 || o.lines < 0) throw usage_error("--min-blocks, --line-offset, --lines: non-negative values expected");
+    if (o.lineOffset % o.block != 0) throw usage_error("--line-offset: a multiple of --block expected");
+    if (*isTiff) {
+        if (o.bil) throw std::invalid_argument("noise: --bil applies to a RAW strip: a TIFF product holds its bands per pixel");
+    } else {
+        if (o.width <= 0 || (o.bil && o.width % MSS_BANDS != 0)) throw std::invalid_argument("--width: a positive line width (a multiple of 4 with --bil) expected");
+        long first = 0, n = 0;
+        RawLineRange(file, "image", o.width, o.lineOffset, o.lines, &first, &n);
+        if (n < o.block || o.width / (o.bil ? MSS_BANDS : 1) < o.block) throw std::invalid_argument("noise: the image holds no block of " + std::to_string(o.block) + " x " + std::to_string(o.block));
+    }
+    const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_NOISE_SUFFIX, ".CSV") : out;
+    struct stat st;
+    if (stat(path.c_str(), &st) == 0) {
+        if (std::filesystem::equivalent(path, file)) throw std::invalid_argument("output file [" + path + "] is the input image");
+        if (!o.force) throw std::runtime_error("output file [" + path + "] exists: noise does not replace a file without --force");
+    }
+    return path;
+}
+
+inline void RunNoise(const std::string &file, const std::string &out, const NoiseOptions &o)
+{
+    bool isTiff = false;
+    const std::string outPath = NoiseCheck(file, out, o, &isTiff);
+    const int B = o.block, shift = o.bits - 8;
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    size_t inBytes = 0;
+    DevBuf<uint16_t> keys;                  // one plane of nbx x nby keys per band
+    int nb = 0, nbx = 0;
+    long nby = 0, nLines = 0;
+    size_t plane = 0;
+    auto alloc_keys = [&](int bandWidth) {
+        nbx = bandWidth / B;
+        nby = nLines / B;
+        if (nbx < 1 || nby < 1) throw std::invalid_argument("noise: the image holds no block of " + std::to_string(B) + " x " + std::to_string(B));
+        plane = (size_t)nbx * nby;
+        keys.alloc(plane * nb);
+    };
+    if (isTiff) {
+        int w = 0, spp = 0;
+        long h = 0;
+        DevBuf<uint16_t> img;
+        OLOG("Reading image from file `%s' ...", file.c_str());
+        read_tiff_to_device(file, &w, &h, &spp, img);
+        if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument("noise: a TIFF of 1 or 4 samples per pixel expected");
+        if (o.lineOffset >= h) throw std::invalid_argument("image has " + std::to_string(h) + " lines: --line-offset is beyond them");
+        nLines = o.lines > 0 ? std::min(o.lines, h - o.lineOffset) : h - o.lineOffset;
+        nb = spp;
+        alloc_keys(w);
+        ck(oip_noise_blocks_u16(ctx, img.p + (size_t)o.lineOffset * w * spp, (long)w * spp, w, nLines, spp, B, shift, o.validMin, o.validMax, keys.p, nbx, plane));
+        ck(oip_sync(ctx));                  // img is released at the end of this block
+        inBytes = (size_t)nLines * w * spp * BYTES_PER_PIXEL;
+    } else {
+        // the kernel runs per line block of the strip (ReadStrip), a block being a multiple of B lines; a BIL band is a window
+        // of the line, so that no block straddles two bands
+        long first = 0;
+        const long fileLines = RawLineRange(file, "image", o.width, o.lineOffset, o.lines, &first, &nLines);
+        const size_t lineBytes = (size_t)o.width * BYTES_PER_PIXEL;
+        nb = o.bil ? MSS_BANDS : 1;
+        const int bw = o.width / nb;
+        alloc_keys(bw);
+        const long hook = BlockLinesHook("OIP_NOISE_BLOCK_LINES");
+        ReadStrip(file, StripPlan{first, nLines, fileLines, 0, StripBlockLines(lineBytes, B, hook > 0 ? std::max<long>(B, hook / B * B) : 0), lineBytes},
+                  [&](const uint16_t *d, long r, long m) {
+                      for (int b = 0; b < nb; ++b)
+                          ck(oip_noise_blocks_u16(ctx, d + (size_t)b * bw, o.width, bw, m, 1, B, shift, o.validMin, o.validMax,
+                                                  keys.p + (size_t)b * plane + (size_t)(r / B) * nbx, nbx, 0));
+                  });
+        ck(oip_sync(ctx));
+        inBytes = (size_t)nLines * lineBytes;
+    }
+
+    // per band: histogram of the key plane -> sigma per level -> fit; every band is fitted before the report is written
+    DevBuf<uint64_t> hist(65536);
+    std::vector<uint64_t> h(65536);
+    std::vector<NoiseBand> bands(nb);
+    for (int b = 0; b < nb; ++b) {
+        NoiseBand &n = bands[b];
+        ck(oip_memset(ctx, hist.p, 0, 65536 * sizeof(uint64_t)));
+        ck(oip_histogram_u16(ctx, keys.p + (size_t)b * plane, nbx, nbx, nby, hist.p));
+        hist.download(h.data(), h.size());
+        n.nodata = h[OIP_NOISE_KEY_NODATA];
+        n.structured = h[OIP_NOISE_KEY_STRUCTURED];
+        char err[512] = "";
+        if (oip_noise_levels(h.data(), (uint64_t)o.minBlocks, n.sigma, n.blocks, &n.levels) != OIP_OK) throw std::invalid_argument("oip_noise_levels: bad argument");
+        const int rc = oip_noise_fit(n.sigma, n.blocks, shift, &n.a, &n.b, &n.muRef, err, sizeof err);
+        if (rc != OIP_OK)
+            throw std::runtime_error("band " + std::to_string(b + 1) + ": " + err + " (" + std::to_string(n.realBlocks()) + " blocks, " + std::to_string(n.nodata) +
+                                     " without data, " + std::to_string(n.structured) + " structured; --min-blocks " + std::to_string(o.minBlocks) + ")");
+    }
+    FILE *f = fopen(outPath.c_str(), "w");
+    if (!f) throw std::runtime_error("open file [" + outPath + "] failed: " + std::to_string(errno));
+    const bool ok = WriteNoiseReport(f, o.params, bands, shift);
+    if (fclose(f) != 0 || !ok) throw std::runtime_error("write file [" + outPath + "] failed");
+    for (int b = 0; b < nb; ++b) OLOG("noise: %s", NoiseBandLine(b + 1, bands[b]).c_str());
+    const double es = total.tick();
+    OLOG("Report written to '%s'; %zu bytes in %.3f seconds (%.1f MBps).", outPath.c_str(), inBytes, es, inBytes / es / 1024.0 / 1024.0);
 }
 
 // ---- oip overviews: the reduced-resolution pyramid of a strip or product ------------------------------------------------
