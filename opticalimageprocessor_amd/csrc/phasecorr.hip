@@ -557,9 +557,11 @@ struct UpRowsJob {
     const uint2 *raw16;     // [4 rows][4 arrays x n / 2]: (bX | bY << 16) of two neighbouring points
     const int *ypos_s;      // row position of frequency line k in zn, k in [0, m)
     int m;
-    // Column bounds for the peak search (col_sel_first_kernel): workgroup g leaves sum |Re| + |Im| of everything it
-    // stored in column x of output o at bound[(g * 4 + o) * P + x], zero before the launch.  A thread owns its columns for
-    // the whole launch, so an element is the private accumulator of one thread (no sum depends on an order between threads).
+    // Column bounds for the peak search (col_sel_first_kernel): workgroup g leaves sum |Re| + |Im| of every line it
+    // transformed, in column x < N of output o, at bound[(g * 4 + o) * P + x].  A thread owns its columns for the whole
+    // launch and sums them in registers, in the order of its line pairs (no sum depends on an order between threads);
+    // after its last line pair every workgroup of the grid writes its four rows in full -- zeros for the outputs a single
+    // unit does not have -- so nothing has to clear the rows before the launch.
     float *bound;
     // WIN: only the 16-byte pieces q (columns 2 q, 2 q + 1) with q < win_hi or q >= win_lo are stored -- the circular,
     // tile-aligned range of columns around column 0 that the pruned peak search reads (rows_window).  The bounds above
@@ -622,14 +624,36 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
     float4 *buf4 = reinterpret_cast<float4 *>(buf), *buf4N = reinterpret_cast<float4 *>(bufN);
     const int half = M / 2;
     int ky = blockIdx.x;
-    if (ky > half) return;
+    constexpr int NIT2 = (F / 2 + NT - 1) / NT;
+    // Column bounds (UpRowsJob::bound): sum |Re| + |Im| of this thread's columns over the workgroup's line pairs, [output]
+    // [piece]: 24 registers for the whole launch.  (They fit since the read-out below stores and sums a piece as it leaves
+    // LDS: the 48 registers that held a whole round's results between the transform and the stores are gone.)
+    float2 acc[4][NIT2];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+#pragma unroll
+        for (int it = 0; it < NIT2; ++it) acc[o][it] = make_float2(0.f, 0.f);
+    }
+    // the workgroup's four rows, written once (plain 8-byte stores: the pitch of every plan is a multiple of 16 elements);
+    // a workgroup without a line pair leaves zeros
+    auto write_bounds = [&]() {
+        float *brow = fj.bound + (long)blockIdx.x * 4 * P;
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+#pragma unroll
+            for (int it = 0; it < NIT2; ++it) {
+                const int q = threadIdx.x + it * NT;
+                if (q < F / 2) *reinterpret_cast<float2 *>(brow + o * P + 2 * q) = acc[o][it];
+            }
+        }
+    };
+    if (ky > half) { write_bounds(); return; }
     for (int i = threadIdx.x; i < TWF; i += NT) tw[i] = twF[i];
     for (int i = threadIdx.x; i < TWS; i += NT) tws[i] = twS[i];
     if (threadIdx.x < 10) edgeT[threadIdx.x / 5][threadIdx.x % 5] = fj.xtab[(threadIdx.x % 5) * F + (threadIdx.x / 5) * (F / 2)];
-    // H and G of the thread's bins: re-read from the L2-resident table (120 KB) for each of the two cross-power rounds
-    // (held across the inverse transforms they cost the registers the prefetched lines need).  Vector-memory
-    // operations complete in order: the second load is issued before the stores of the first round and before the
-    // prefetch, so that waiting for it waits for nothing else.
+    // H and G of the thread's bins (30 registers): read once, before the first line pair, and held for the whole launch.
+    // (They used to be re-read from L2 for each of the two cross-power rounds, when the results of a round waited in 48
+    // registers for their stores; see the read-out in finish().)
     float2 H[NB], G[NB][4];
     auto load_tables = [&](int tid) {
 #pragma unroll
@@ -641,7 +665,6 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
             for (int j = 0; j < 4; ++j) G[r][j] = fj.xtab[(1 + j) * F + kx];
         }
     };
-    constexpr int NIT2 = (F / 2 + NT - 1) / NT;
     constexpr int NQ = 4 * (S / 2);                 // 16-byte pieces of one line of the four narrow arrays
     constexpr int NITN = (NQ + NT - 1) / NT;
     float4 la[NIT2], lb[NIT2], na[NITN], nb[NITN];
@@ -655,7 +678,9 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
     // VEXP: the narrow lines, their coefficients and the raw rows are requested at the commit itself -- their
     // registers (58 per thread) held across the second round's transforms spill, and a spilled load is waited for
     // where it is issued.  They are a quarter of the input bytes and mostly L2 / Infinity Cache hits (every line of
-    // a band transform serves four frequency lines, the raw rows serve all).
+    // a band transform serves four frequency lines, the raw rows serve all).  (With the tables held for the launch the
+    // lines and coefficients requested with the prefetch, or the raw rows held for the launch, spill again; either of
+    // them without the held tables fits and does not do as well as the tables: DESIGN.md 4.3.)
     auto fetch_narrow = [&](int tid) {
         if (VEXP) {
 #pragma unroll
@@ -730,16 +755,13 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
     commit(threadIdx.x);
     long s1 = n1, s2 = n2;
     __syncthreads();
-    bool first = true;
-    char *const brow = reinterpret_cast<char *>(fj.bound + (long)blockIdx.x * 4 * P);
+    load_tables(threadIdx.x);
     for (; ky <= half; ky += gridDim.x) {
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const bool pair = s1 != s2;
         const int kn = ky + gridDim.x;
         const bool more = kn <= half;
-        if (first) load_tables(tid);            // later iterations: requested before the previous iteration's last stores
-        first = false;
         __builtin_amdgcn_sched_barrier(0);
         oipfft::StagesDual3<F, 1, S, 4, NT, 25, 15, 8, 2>::run(buf, tw, bufN, tws, tid);
         // PAN spectra of this thread's bins (unit A in the real slot, unit B in the imaginary one); those of the two
@@ -828,71 +850,44 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
                 }
             }
         };
-        float4 ya[2][NIT2], yb[2][NIT2];
-        auto finish = [&]() {           // inverse row transform of the two buffers; results to registers
+        // Inverse row transform of the two buffers and the read-out: a piece leaves LDS, is stored if it lies in the window
+        // (WIN: compared here, from the piece index -- wave-uniform but at the window's two ends; nothing is carried across
+        // the iteration) and |Re| + |Im| of it is added to the thread's column bounds.  An unpaired line (ky = 0, M / 2)
+        // counts once.  The order of the additions is the order of the line pairs: the sums are the same bits every run.
+        auto finish = [&](int o0) {
             __syncthreads();
             asm volatile("" : "+v"(tid));
             oipfft::StagesAll<F, NT, 2, 1, 25, 15, 8>::run(buf, tw, tid);
-#pragma unroll
-            for (int o = 0; o < 2; ++o) {
-#pragma unroll
-                for (int it = 0; it < NIT2; ++it) line_pair_read_conj<F>(ya[o][it], yb[o][it], buf4, o * F, tid + it * NT);
-            }
-            __syncthreads();
-        };
-        auto store = [&](int o0) {
 #pragma unroll
             for (int o = 0; o < 2; ++o) {
                 float2 *out = fj.out[o0 + o];
 #pragma unroll
                 for (int it = 0; it < NIT2; ++it) {
                     const int q = tid + it * NT;
-                    // WIN: compared here, from the piece index (wave-uniform but at the window's two ends); nothing is
-                    // carried across the iteration
-                    if (!WIN || q < fj.win_hi || q >= fj.win_lo) line_pair_store<F>(out, s1 * P, s2 * P, pair, ya[o][it], yb[o][it], q);
-                }
-            }
-        };
-        // Column bounds: |Re| + |Im| of what store(o0) has just written is added to the workgroup's rows with the
-        // hardware's f32 add (no value comes back: nothing to wait for, no register held).  Every address has one writer,
-        // this thread, so the order of the additions is the order of the line pairs: the sums are the same bits every run.
-        // (Read-add-write through registers was measured: the 12 registers of a round's sums spill three of the prefetched
-        // lines, whose reload waits for the prefetch -- 1.16 -> 1.38 ms per launch; this form runs at 1.19.)
-        auto bound_add = [&](int o0) {
-            int tb = tid;
-            asm volatile("" : "+v"(tb));            // addresses formed here, not carried through the iteration
-#pragma unroll
-            for (int o = 0; o < 2; ++o) {
-#pragma unroll
-                for (int it = 0; it < NIT2; ++it) {
-                    const int q = tb + it * NT;
                     if (q < F / 2) {
-                        const float4 a = ya[o][it], b = yb[o][it];
+                        float4 a, b;
+                        line_pair_read_conj<F>(a, b, buf4, o * F, q);
+                        if (!WIN || q < fj.win_hi || q >= fj.win_lo) line_pair_store<F>(out, s1 * P, s2 * P, pair, a, b, q);
                         float2 s = make_float2(fabsf(a.x) + fabsf(a.y), fabsf(a.z) + fabsf(a.w));
-                        if (pair) { s.x += fabsf(b.x) + fabsf(b.y); s.y += fabsf(b.z) + fabsf(b.w); }     // an unpaired line counts once
-                        // (uniform base + 32-bit byte offset: no 64-bit address arithmetic per element)
-                        float *bp = reinterpret_cast<float *>(brow + (unsigned)((o0 + o) * P + 2 * q) * 4u);
-                        unsafeAtomicAdd(bp, s.x);
-                        unsafeAtomicAdd(bp + 1, s.y);
+                        if (pair) { s.x += fabsf(b.x) + fabsf(b.y); s.y += fabsf(b.z) + fabsf(b.w); }
+                        acc[o0 + o][it].x += s.x;
+                        acc[o0 + o][it].y += s.y;
                     }
                 }
             }
+            __syncthreads();
         };
         xround(0, Aa);
-        finish();
-        if (fj.nout == 4) load_tables(tid);
+        finish(0);
         __builtin_amdgcn_sched_barrier(0);
-        store(0);
-        __builtin_amdgcn_sched_barrier(0);
-        bound_add(0);
         if (fj.nout == 4) xround(2, Ab);
         __builtin_amdgcn_sched_barrier(0);
         // The lines of the NEXT pair are requested here -- after the last consumer of anything the compiler may have
         // spilled (a reload is a vector-memory load: younger than the prefetch, it would wait for it) -- and committed at
         // the bottom of this same iteration: three quarters of the iteration run without their registers.
         if (more) {
-            // (scalar loads: as vector loads these look-ups put an s_waitcnt vmcnt(0) -- the stores of store(0) and the table
-            // loads -- in front of the prefetch.  ABAB on one box: 1.1677 / 1.1696 -> 1.1509 / 1.1427 ms per launch)
+            // (scalar loads: as vector loads these look-ups put an s_waitcnt vmcnt(0) -- the stores of the first read-out
+            // -- in front of the prefetch.  ABAB on one box: 1.1677 / 1.1696 -> 1.1509 / 1.1427 ms per launch)
             n1 = oip_sload_i32(ypos, kn);
             n2 = oip_sload_i32(ypos, M - kn);
             m1 = VEXP ? (long)oip_sload_i32(fj.ypos_s, kn % fj.m) : n1;
@@ -901,19 +896,12 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
             fetch(tid);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (fj.nout == 4) finish();
+        if (fj.nout == 4) finish(2);
         if (more) commit(tid);
-        __builtin_amdgcn_sched_barrier(0);
-        if (more) load_tables(tid);             // ahead of the stores: waiting for them then waits for nothing younger
-        __builtin_amdgcn_sched_barrier(0);
-        if (fj.nout == 4) {
-            store(2);
-            __builtin_amdgcn_sched_barrier(0);
-            bound_add(2);
-        }
         s1 = n1; s2 = n2;
         __syncthreads();
     }
+    write_bounds();
 }
 
 // ---- row stage with the VERTICAL x4 up-sampling applied to the band spectra (padded row lengths) ---------------------
@@ -1288,7 +1276,7 @@ constexpr float kPruneMargin = 0x1p-8f;
 constexpr int kRowsWindowTiles = 8;
 constexpr int kSelThreads = 1024, kSelCols = 64, kSelParts = kSelThreads / kSelCols, kSelMaxTiles = 1024;
 struct PruneWork {
-    float *bound;       // [row-stage workgroups][4][P]: the row stage's partial column sums
+    float *bound;       // [row-stage workgroups][4][P]: the row stage's partial column sums (every row is written by every launch)
     int groups;         // workgroups of the row stage
     float *bt;          // [4][T]
     int *flags;         // [4][T]: bit 0 column passes done, bit 1 searched
@@ -2045,7 +2033,8 @@ int correlate_units_up(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, c
     fj.m = band_rows;
     fj.bound = w.prune.bound;
     if (!fj.bound) return oip_fail(ctx, OIP_E_RUNTIME, "correlate_units_up: no storage for the column bounds");
-    OIP_HIP(ctx, hipMemsetAsync(fj.bound, 0, sizeof(float) * (size_t)w.prune.groups * 4 * pl->P, ctx->stream));     // the kernel adds to it
+    // (not cleared: every workgroup of the launch below writes its four rows in full, with 8-byte stores)
+    if (pl->P & 1) return oip_fail(ctx, OIP_E_RUNTIME, "correlate_units_up: odd row pitch %d", pl->P);
     // The stored window (rows_window): tiles 0 .. win_r and T - win_r .. T - 1 of the column passes' lane tiles, as pieces
     // of two columns.  The peak search below tells a pair that needs a tile outside of it (PruneWork::miss).
     PruneWork pw = w.prune;
@@ -2067,7 +2056,7 @@ int correlate_units_up(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, c
         OipProfScope prof(ctx, "corr_rows_up_kernel");
         const long grid = w.prune.groups;
         const dim3 g((unsigned)grid);
-        // (no windowed instance without VEXP: that kernel already spills, and the predicate doubles it -- 24 -> 48 VGPRs)
+        // (no windowed instance without VEXP: it has not been built since that kernel stopped spilling -- DESIGN.md 4.3)
         auto k = up.vtab ? (win_r >= 0 ? corr_rows_up_kernel<512, true, true> : corr_rows_up_kernel<512, true, false>)
                          : corr_rows_up_kernel<512, false, false>;
         // measured in bench.py, VEXP: 1.275 ms with 512 threads (244 VGPRs, no scratch), 1.36 with 768 (168, 28 spilled)
