@@ -83,6 +83,103 @@ def lzw_encode(data: bytes) -> bytes:
     return bytes(out)
 
 
+class LzwTrace:
+    """What lzw_trace saw: `stream` (the encoded bytes), `codes` -- one (value, width, kwkwk, pos) per emitted code, ClearCode and
+    EndOfInformation included; kwkwk: the value is the entry the previous miss assigned, so the decoder meets code == its own next;
+    pos: index of the input byte whose miss sent the code, len(data) for what goes out after the last byte -- `clears` (indices
+    into codes), `end_next` (next after the final code's increment, before a ClearCode that increment may cause), `eoi_width`,
+    `last_byte` (what the LAST input byte caused inside the loop: "clear", "widen10" / "widen11" / "widen12" or None) and
+    `max_next` (the highest value next reached: clear_at, where a variant's threshold was really met)."""
+
+    def __init__(self):
+        self.stream, self.codes, self.clears = b"", [], []
+        self.end_next = self.eoi_width = self.max_next = 0
+        self.last_byte = None
+
+    def kwkwk_values(self):
+        return {v for v, _, k, _ in self.codes if k}
+
+    def last_data_code(self):
+        """the last code that is neither ClearCode nor EndOfInformation"""
+        return [c for c in self.codes if c[0] not in (256, 257)][-1]
+
+
+def lzw_trace(data: bytes, clear_at=4094, extra_clear_every=0, double_clear=False, leading_clear=True, trailing_bytes=0) -> LzwTrace:
+    """The dictionary coder of lzw_encode once more, recording the events of the stream (LzwTrace).  With the defaults the stream is
+    lzw_encode's (libtiff's).  The knobs write streams that are legal TIFF LZW but that libtiff's encoder never produces:
+    clear_at -- the value of next at which ClearCode is sent (4094 libtiff; 4095; 4096: the table really full, TIFF 6.0's text);
+    extra_clear_every=N -- a ClearCode after every N-th assigned entry as well, in the middle of a half-filled table;
+    double_clear -- every ClearCode twice; leading_clear=False -- the strip does not start with one; trailing_bytes=k -- k junk
+    bytes after EndOfInformation."""
+    assert clear_at in (4094, 4095, 4096)
+    t = LzwTrace()
+    codes = {bytes([i]): i for i in range(256)}
+    out, acc, nbits = bytearray(), 0, 0
+    width, nxt, assigned, fresh = 9, 258, 0, None              # fresh: the entry the previous miss assigned
+
+    def put(code, w, kwkwk, pos):
+        nonlocal acc, nbits
+        t.codes.append((code, w, kwkwk, pos))
+        acc = (acc << w) | code
+        nbits += w
+        while nbits >= 8:
+            out.append((acc >> (nbits - 8)) & 0xFF)
+            nbits -= 8
+
+    def clear(pos):
+        nonlocal codes, width, nxt, fresh
+        for _ in range(2 if double_clear else 1):
+            t.clears.append(len(t.codes))
+            put(256, width, False, pos)
+            width = 9
+        codes = {bytes([i]): i for i in range(256)}
+        nxt, fresh = 258, None
+
+    if leading_clear:
+        clear(0)
+    ent = b""
+    for i, b in enumerate(data):
+        cur = ent + bytes([b])
+        t.last_byte = None
+        if cur in codes:
+            ent = cur
+            continue
+        put(codes[ent], width, codes[ent] == fresh, i)
+        codes[cur] = fresh = nxt
+        nxt += 1
+        assigned += 1
+        t.max_next = max(t.max_next, nxt)
+        ent = bytes([b])
+        if nxt == clear_at:
+            clear(i)
+            t.last_byte = "clear"
+        elif nxt == (1 << width) and width < 12:
+            width += 1
+            t.last_byte = "widen%d" % width
+        if extra_clear_every and assigned % extra_clear_every == 0 and nxt != 258:
+            clear(i)
+    if ent:
+        put(codes[ent], width, codes[ent] == fresh, len(data))
+        nxt += 1
+        t.max_next = max(t.max_next, nxt)
+        t.end_next = nxt
+        if nxt == clear_at:
+            clear(len(data))
+        elif nxt == (1 << width) and width < 12:
+            width += 1
+    t.eoi_width = width
+    put(257, width, False, len(data))
+    if nbits:
+        out.append((acc << (8 - nbits)) & 0xFF)
+    t.stream = bytes(out) + b"\xa5" * trailing_bytes
+    return t
+
+
+def lzw_encode_variant(data: bytes, **knobs) -> bytes:
+    """a foreign-but-legal stream for `data` (the knobs of lzw_trace)"""
+    return lzw_trace(data, **knobs).stream
+
+
 def read_tags(path):
     """directory only (no pixel decoding)"""
     return read_tiff_u16(path, tags_only=True)[1]
@@ -171,13 +268,21 @@ def write_tiff_u16(path, arr, lzw=False, predictor=1, rows_per_strip=None):
         f.write(struct.pack("<I", 0))
 
 
-def _write_tiff_lzw(path, a, predictor, rps):
+def write_tiff_lzw_strips(path, strips, shape, predictor, rows_per_strip):
+    """a classic TIFF around LZW strips somebody else encoded; shape: (rows, width, samples per pixel)"""
+    _write_tiff_lzw(path, np.zeros(shape, dtype="<u2"), predictor, rows_per_strip, strips=list(strips))
+
+
+def _write_tiff_lzw(path, a, predictor, rps, strips=None):
     h, w, s = a.shape
-    if predictor == 2:
+    if strips is not None:
+        assert len(strips) == (h + rps - 1) // rps
+    elif predictor == 2:
         d = a.astype(np.int64)
         d[:, 1:, :] = d[:, 1:, :] - a[:, :-1, :].astype(np.int64)
         a = (d & 0xFFFF).astype("<u2")
-    strips = [lzw_encode(a[r:r + rps].tobytes()) for r in range(0, h, rps)]
+    if strips is None:
+        strips = [lzw_encode(a[r:r + rps].tobytes()) for r in range(0, h, rps)]
     body, offs = b"", []
     for st in strips:
         if len(body) & 1:

@@ -2,10 +2,13 @@
 sections 13 (LZW as libtiff writes it) and 14 (horizontal predictor): tests/_tiff.py::lzw_encode -- a dictionary of byte strings,
 nothing in common with the open-addressing coders of the product -- on the predictor-2 byte stream of every strip, bit for bit.
 The reference encodes these strips on the host through cv::imwrite (preproc.h:167-185) and GDAL (imageop.h:460-567)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
+import _lzw_cases as L
 import _tiff
 
 pytestmark = pytest.mark.gpu
@@ -158,3 +161,175 @@ def test_device_lzw_decoder_rejects_corrupt_strips(ctx):
         assert np.array_equal(d_img.cpu().numpy().view(np.uint16), img)
     except RuntimeError as e:                      # (cutting the last byte may also cut the last code: then the strip is short)
         assert "decodes to" in str(e)
+
+
+# ---- the coder states random data reaches only by luck (tests/_lzw_cases.py) ---------------------------------------------------
+# Every case is one strip whose predictor-2 bytes put the independent coder into a named state: the end of a strip at a code-width
+# boundary or at the table clear, a width change or a clear on the strip's last byte, KwKwK codes around the decoder's early width
+# change.  Each test first asserts, through _tiff.lzw_trace, that its input still produces the event it is named for.
+
+
+@functools.lru_cache(maxsize=None)
+def _ref_strip(seed, width, spp, kind, prefix):
+    """(row, its predictor-2 bytes, the independent coder's strip) of one generator at one width, computed once"""
+    row = L.row_of(seed, width, spp, kind, prefix)
+    data = L.predict2(row, spp)
+    return row, data, _tiff.lzw_encode(data)
+
+
+def _neighbourhood(case):
+    """A 3-row image at the case's width: the case in the middle, above and below it the generators of the cases before and after it
+    in the table (same samples per pixel), cut or continued to this width -- adjacent lanes of the wave sit in other states.
+    Returns (image rows x (width * spp), the independent coder's three strips)."""
+    same = [c for c in L.CASES if c[2] == case[2]]
+    i = same.index(case)
+    rows, strips = [], []
+    for c in (same[i - 1], case, same[(i + 1) % len(same)]):
+        row, data, strip = _ref_strip(c[0], case[1], c[2], c[3], c[5])
+        rows.append(row); strips.append(strip)
+    t = _tiff.lzw_trace(_ref_strip(case[0], case[1], case[2], case[3], case[5])[1])
+    assert L.has_event(t, case[4]), "the input no longer produces %s" % case[4]
+    return np.stack(rows), strips
+
+
+def _device_strips(ctx, img, rows, width, spp, rps):
+    """the device encoder's strips, with the layout rules every caller relies on: even offsets, a zero pad byte after an odd strip"""
+    d_img = torch.from_numpy(np.ascontiguousarray(img).view(np.int16)).cuda()
+    cap = ctx.tiff_lzw_worst_bytes(rows, width, spp, rps)
+    d_pay = torch.full((cap,), 0xEE, dtype=torch.uint8, device="cuda")
+    off, ln, total = ctx.tiff_lzw_strips(d_img, rows, width, spp, rps, d_pay)
+    pay = d_pay.cpu().numpy()
+    nstrips = (rows + rps - 1) // rps
+    assert len(off) == nstrips and off[0] == 0 and total == off[-1] + ln[-1] and total <= cap
+    pos, out = 0, []
+    for k in range(nstrips):
+        assert off[k] % 2 == 0 and off[k] == pos + (pos & 1), k
+        out.append(pay[int(off[k]):int(off[k] + ln[k])].tobytes())
+        if ln[k] % 2 and k + 1 < nstrips:
+            assert pay[int(off[k] + ln[k])] == 0, k              # the pad byte between an odd strip and the next
+        pos = int(off[k] + ln[k])
+    return out, (d_img, d_pay, off, ln)
+
+
+def _device_decode(ctx, strips, rows, width, spp, rps, pred):
+    blob, off, ln = _pack(strips)
+    d_img = torch.full((rows, width * spp), -1, dtype=torch.int16, device="cuda")
+    ctx.tiff_lzw_decode(torch.from_numpy(blob).cuda(), off, ln, rows, width, spp, rps, pred, d_img)
+    return d_img.cpu().numpy().view(np.uint16)
+
+
+@pytest.mark.parametrize("case", L.CASES, ids=L.case_id)
+def test_device_encoder_at_a_named_coder_state(ctx, case):
+    img, want = _neighbourhood(case)
+    got, _ = _device_strips(ctx, img, 3, case[1], case[2], 1)
+    for k in range(3):
+        assert got[k] == want[k], (k, len(got[k]), len(want[k]))
+
+
+@pytest.mark.parametrize("case", L.CASES, ids=L.case_id)
+def test_device_decoder_at_a_named_coder_state(ctx, case):
+    """the independent coder's strips; with predictor 2 the image is the case's row, with predictor 1 it is the row's differences:
+    the same strip, the same coder states, either way"""
+    img, strips = _neighbourhood(case)
+    width, spp = case[1], case[2]
+    assert np.array_equal(_device_decode(ctx, strips, 3, width, spp, 1, 2), img)
+    diff = np.frombuffer(L.predict2(img, spp), dtype="<u2").reshape(3, -1)
+    assert np.array_equal(_device_decode(ctx, strips, 3, width, spp, 1, 1), diff)
+
+
+@pytest.mark.parametrize("spp", L.SPPS)
+def test_device_round_trip_through_every_named_state(ctx, spp):
+    """Device encoder into device decoder.  Rows of one image share a width and the cases do not, so there is one image per distinct
+    width: every generator of the table at that width, one row each; the rows whose case has that width end in their state."""
+    inputs = [c for c in L.distinct_inputs() if c[2] == spp]
+    for c in [c for c in L.CASES if c[2] == spp]:
+        assert L.has_event(_tiff.lzw_trace(_ref_strip(c[0], c[1], c[2], c[3], c[5])[1]), c[4])
+    for width in sorted({c[1] for c in inputs}):
+        img = np.stack([L.row_of(c[0], width, spp, c[3], c[5]) for c in inputs])
+        rows = len(inputs)
+        strips, (d_img, d_pay, off, ln) = _device_strips(ctx, img, rows, width, spp, 1)
+        for k, c in enumerate(inputs):
+            if c[1] == width:
+                assert strips[k] == _ref_strip(c[0], c[1], c[2], c[3], c[5])[2], (width, k)
+        d_back = torch.zeros_like(d_img)
+        ctx.tiff_lzw_decode(d_pay, off, ln, rows, width, spp, 1, 2, d_back)
+        assert torch.equal(d_back, d_img), width
+
+
+@pytest.mark.parametrize("spp", L.SPPS)
+@pytest.mark.parametrize("name", list(L.VARIANTS))
+def test_device_decoder_reads_legal_streams_libtiff_never_writes(ctx, name, spp):
+    """16000-byte noise strips as a foreign encoder may write them (tests/_lzw_cases.py::VARIANTS: those the independent decoder and
+    libtiff read -- tests/test_tifflzw_cpu.py); libtiff's own form of the same row in the lane beside it"""
+    knobs, width = L.VARIANTS[name], L.VARIANT_WIDTH[spp]
+    row = L.variant_row(spp)
+    data = L.predict2(row, spp)
+    t = _tiff.lzw_trace(data, **knobs)
+    assert L.variant_reaches_its_state(t, knobs) and _tiff.lzw_decode(t.stream) == data
+    img = np.stack([row, row])
+    for strips in ([_tiff.lzw_encode(data), t.stream], [t.stream, _tiff.lzw_encode(data)]):
+        assert np.array_equal(_device_decode(ctx, strips, 2, width, spp, 1, 2), img)
+
+
+def test_device_decoder_reports_a_table_that_fills_without_clearcode(ctx):
+    """status 3: literal codes for ever and no ClearCode; the decoder's next reaches 4096 after 3839 of them (3839 bytes, less than the
+    strip).  The error names that strip, whichever side of the good one it is on."""
+    rows, width, spp = 2, 2048, 1
+    img = _image("noise12", rows, width, spp, seed=9)
+    good = [_tiff.lzw_encode(_predict(img[k:k + 1], spp)) for k in range(rows)]
+    acc = nb = 0
+    out = bytearray()
+    w, nxt, first = 9, 258, True
+    for c in [256] + [(i * 37) % 256 for i in range(6000)]:    # packed at the widths the decoder reads them with
+        acc = (acc << w) | c; nb += w
+        while nb >= 8:
+            out.append((acc >> (nb - 8)) & 0xFF); nb -= 8
+        if c == 256 or first:
+            first = c == 256
+        else:
+            nxt += 1
+            if nxt >= (1 << w) - 1 and w < 12:
+                w += 1
+    assert nxt > 4096 and w == 12
+    bad = bytes(out)
+    d_img = torch.zeros((rows, width), dtype=torch.int16, device="cuda")
+    for strips, k in (([good[0], bad], 1), ([bad, good[1]], 0)):
+        blob, off, ln = _pack(strips)
+        with pytest.raises(RuntimeError, match="table full without ClearCode.*strip %d" % k):
+            ctx.tiff_lzw_decode(torch.from_numpy(blob).cuda(), off, ln, rows, width, spp, 1, 2, d_img)
+    assert np.array_equal(_device_decode(ctx, good, rows, width, spp, 1, 2), img)
+
+
+def test_device_decoder_packed_predictor_add_at_full_range(ctx):
+    """Predictor 2 of 4 samples is undone by four 16-bit adds in one 64-bit register: 15 bits carry on their own, the top bits go by
+    xor.  Full-range samples, and 0x7FFF, 0x8000, 0xFFFF, 0x0000 side by side in every order (a sequence that holds all 16 ordered
+    pairs), each channel one step further along it than the one before -- so every carry out of bit 14 meets every pair of top bits, and
+    neighbouring 16-bit fields differ in it."""
+    rows, width, spp = 6, 257, 4
+    img = np.random.default_rng(11).integers(0, 65536, (rows, width, spp), dtype=np.uint16)
+    vals = np.array([0x7FFF, 0x8000, 0xFFFF, 0x0000], dtype=np.uint16)
+    seq = [0, 0, 1, 0, 2, 0, 3, 1, 1, 2, 1, 3, 2, 2, 3, 3, 0]
+    assert {(a, b) for a, b in zip(seq, seq[1:])} == {(a, b) for a in range(4) for b in range(4)}
+    ring = seq[:-1]
+    for r in range(rows):
+        for c in range(spp):
+            x0 = (0, 1, 100, 239, 240 - 17, 57)[r]              # from the row's first pixel on, up to its last, in between
+            n = min(len(seq) + 3, width - x0)
+            img[r, x0:x0 + n, c] = vals[[ring[(i + c) % 16] for i in range(n)]]
+    img = img.reshape(rows, width * spp)
+    strips = [_tiff.lzw_encode(_predict(img[k:k + 1], spp)) for k in range(rows)]
+    assert np.array_equal(_device_decode(ctx, strips, rows, width, spp, 1, 2), img)
+    got, _ = _device_strips(ctx, img, rows, width, spp, 1)
+    assert got == strips
+
+
+@pytest.mark.parametrize("rows,width,spp,rps", [(3, 1, 1, 1), (3, 1, 4, 1), (1, 2, 4, 1), (5, 1, 4, 2)])
+def test_device_lzw_on_tiny_strips(ctx, rows, width, spp, rps):
+    """strips of 2 to 16 bytes, a one-pixel row (the 4-sample loader's look-ahead guard on its first pixel), a short last strip"""
+    img = np.random.default_rng(rows * 7 + width + spp).integers(0, 65536, (rows, width * spp), dtype=np.uint16)
+    want = [_tiff.lzw_encode(_predict(img[k:k + rps], spp)) for k in range(0, rows, rps)]
+    got, _ = _device_strips(ctx, img, rows, width, spp, rps)
+    assert got == want
+    assert np.array_equal(_device_decode(ctx, want, rows, width, spp, rps, 2), img)
+    plain = [_tiff.lzw_encode(img[k:k + rps].astype("<u2").tobytes()) for k in range(0, rows, rps)]
+    assert np.array_equal(_device_decode(ctx, plain, rows, width, spp, rps, 1), img)
