@@ -37,7 +37,8 @@
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
-// codes (RequiredError 106, ValidationError 105, ExtrasError 109, ConversionError 104).
+// codes (RequiredError 106, ValidationError 105, ExtrasError 109, ConversionError 104).  A raster tool's run_* refuses bad option
+// values with those; what needs the container, a file or the image is refused in its *Check (oip_rastertools.hpp) with 2 or 254.
 #include <climits>
 #include <cstdlib>
 #include <unistd.h>
@@ -86,6 +87,29 @@ struct Parsed {
         if (!e || *e) throw cli_error(104, "Could not convert: " + k + " = " + it->second);
         return v;
     }
+    // an integer option of the raster tools that lies in [lo, hi], or 105 and "<option>: <expected>"
+    int within(const std::string &k, int def, int lo, int hi, const char *expected) const
+    {
+        const int v = integer(k, def);
+        if (v < lo || v > hi) throw cli_error(105, k + ": " + expected);
+        return v;
+    }
+    // ... and the ranges several of them share, each with its one message
+    int valid_min() const { return within("--valid-min", 1, 0, 65535, "0 <= N <= 65535 expected"); }
+    int positive_width(int def) const { return within("--width", def, 1, INT_MAX, "a positive line width expected"); }
+    void valid_range(int defMin, int *lo, int *hi) const
+    {
+        *lo = integer("--valid-min", defMin);
+        *hi = integer("--valid-max", 65535);
+        if (*lo < 0 || *hi > 65535 || *lo > *hi) throw cli_error(105, "--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
+    }
+    // --line-offset / --lines (0: to the end); `also` is a count that `alsoKeys` names in the same message (rrc-calib's --min-count)
+    void line_range(long *offset, long *lines, const std::string &alsoKeys = "", long also = 0) const
+    {
+        *offset = integer("--line-offset", 0);
+        *lines = integer("--lines", 0);
+        if (also < 0 || *offset < 0 || *lines < 0) throw cli_error(105, alsoKeys + "--line-offset, --lines: non-negative values expected");
+    }
 };
 
 Parsed parse(const Spec &sp, const std::vector<std::string> &args)
@@ -112,8 +136,9 @@ Parsed parse(const Spec &sp, const std::vector<std::string> &args)
     return p;
 }
 
-// The tools with one positional argument (quicklook, mtfc, despike, noise, overviews): IMAGE, an existing regular file, is the first argument
-// that is neither an option nor the value of one (an option's value stays with it, alias or not); the rest is parsed as usual.
+// The tools with one positional argument (quicklook, mtfc, despike, noise, overviews; regcheck, regfix and pansharpen name their
+// images by options): IMAGE, an existing regular file, is the first argument that is neither an option nor the value of one (an
+// option's value stays with it, alias or not); the rest is parsed as usual.
 Parsed parse_with_image(const Spec &sp, const std::vector<std::string> &args, std::string *image)
 {
     std::vector<std::string> rest;
@@ -568,14 +593,10 @@ int run_rrc_calib(const std::vector<std::string> &args, int width)
     if (mode == "moments") o.mode = OIP_RRCFIT_MOMENTS;
     else if (mode == "gain") o.mode = OIP_RRCFIT_GAIN;
     else throw cli_error(105, "--mode: moments or gain expected");
-    o.validMin = p.integer("--valid-min", 0);
-    o.validMax = p.integer("--valid-max", 65535);
-    if (o.validMin < 0 || o.validMax > 65535 || o.validMin > o.validMax) throw cli_error(105, "--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
+    p.valid_range(0, &o.validMin, &o.validMax);
     o.minCount = p.integer("--min-count", 0);
-    o.lineOffset = p.integer("--line-offset", 0);
-    o.lines = p.integer("--lines", 0);
-    if (o.minCount < 0 || o.lineOffset < 0 || o.lines < 0) throw cli_error(105, "--min-count, --line-offset, --lines: non-negative values expected");
-    o.force = p.flag.count("--force") != 0;
+    p.line_range(&o.lineOffset, &o.lines, "--min-count, ", o.minCount);
+    o.force = p.has("--force");
     o.badPan = p.str("--bad-pan");
     o.badMss = p.str("--bad-mss");
     if ((p.has("--bad-pan") && o.badPan.empty()) || (p.has("--bad-mss") && o.badMss.empty())) throw cli_error(105, "--bad-pan, --bad-mss: a file name expected");
@@ -596,18 +617,14 @@ int run_quicklook(const std::vector<std::string> &args, int width)
     Parsed p = parse_with_image(sp, args, &image);
     QuicklookOptions o;
     o.width = p.integer("--width", width);
-    o.bil = p.flag.count("--bil") != 0;
+    o.bil = p.has("--bil");
     o.factor = p.integer("--factor", OIP_QUICKLOOK_DEF_FACTOR);
     o.clipLow = p.real("--clip-low", OIP_QUICKLOOK_DEF_CLIPLOW);
     o.clipHigh = p.real("--clip-high", OIP_QUICKLOOK_DEF_CLIPHIGH);
     if (!(o.clipLow >= 0.0 && o.clipLow <= o.clipHigh && o.clipHigh <= 100.0)) throw cli_error(105, "--clip-low/--clip-high: 0 <= low <= high <= 100 expected");
-    o.validMin = p.integer("--valid-min", 1);
-    o.validMax = p.integer("--valid-max", 65535);
-    if (o.validMin < 0 || o.validMax > 65535 || o.validMin > o.validMax) throw cli_error(105, "--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
-    o.lineOffset = p.integer("--line-offset", 0);
-    o.lines = p.integer("--lines", 0);
-    if (o.lineOffset < 0 || o.lines < 0) throw cli_error(105, "--line-offset, --lines: non-negative values expected");
-    o.force = p.flag.count("--force") != 0;
+    p.valid_range(1, &o.validMin, &o.validMax);
+    p.line_range(&o.lineOffset, &o.lines);
+    o.force = p.has("--force");
     if (p.has("--bands")) {
         const std::string b = p.str("--bands");
         int v[4] = {0, 0, 0, 0};
@@ -648,9 +665,8 @@ int run_mtfc(const std::vector<std::string> &args, int width)
         existing_file(p, "--kernel");
         o.kernelFile = p.str("--kernel");
     }
-    o.validMin = p.integer("--valid-min", 1);
-    if (o.validMin < 0 || o.validMin > 65535) throw cli_error(105, "--valid-min: 0 <= N <= 65535 expected");
-    o.force = p.flag.count("--force") != 0;
+    o.validMin = p.valid_min();
+    o.force = p.has("--force");
     RunMtfc(image, p.str("--out"), o);
     return 0;
 }
@@ -673,20 +689,18 @@ int run_despike(const std::vector<std::string> &args, int width)
     if (p.has("--relative") && !p.has("--threshold")) throw cli_error(107, "--relative requires --threshold");
     DespikeOptions o;
     o.width = p.integer("--width", width);
-    o.bil = p.flag.count("--bil") != 0;
+    o.bil = p.has("--bil");
     o.hasThreshold = p.has("--threshold");
-    o.thrAbs = p.integer("--threshold", 65535);
-    if (o.thrAbs < 0 || o.thrAbs > 65535) throw cli_error(105, "--threshold: 0 <= N <= 65535 expected");
+    o.thrAbs = p.within("--threshold", 65535, 0, 65535, "0 <= N <= 65535 expected");
     const double rel = p.real("--relative", 0.0);
     if (!(rel >= 0.0 && rel <= 1.0)) throw cli_error(105, "--relative: 0 <= R <= 1 expected");
     o.thrRelQ8 = (int)std::rint(rel * 256.0);
-    o.validMin = p.integer("--valid-min", 1);
-    if (o.validMin < 0 || o.validMin > 65535) throw cli_error(105, "--valid-min: 0 <= N <= 65535 expected");
+    o.validMin = p.valid_min();
     existing_file(p, "--bad-columns");
     o.badColumns = p.str("--bad-columns");
     if (p.has("--bad-columns") && o.badColumns.empty()) throw cli_error(105, "--bad-columns: a file name expected");
     o.report = p.str("--report");
-    o.force = p.flag.count("--force") != 0;
+    o.force = p.has("--force");
     existing_file(p, "--noise");
     // --k-sigma 5 is the usual convention for an impulse, nothing measured
     const double kSigma = p.real("--k-sigma", 5.0);
@@ -709,21 +723,15 @@ int run_noise(const std::vector<std::string> &args, int width)
     Parsed p = parse_with_image(sp, args, &image);
     NoiseOptions o;
     o.width = p.integer("--width", width);
-    o.bil = p.flag.count("--bil") != 0;
+    o.bil = p.has("--bil");
     o.block = p.integer("--block", 8);
     if (o.block != 8 && o.block != 16) throw cli_error(105, "--block: 8 or 16 expected");
-    o.bits = p.integer("--bits", 12);
-    if (o.bits < 8 || o.bits > 16) throw cli_error(105, "--bits: 8 <= N <= 16 expected");
-    o.validMin = p.integer("--valid-min", 1);
-    o.validMax = p.integer("--valid-max", 65535);
-    if (o.validMin < 0 || o.validMax > 65535 || o.validMin > o.validMax) throw cli_error(105, "--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
-    o.minBlocks = p.integer("--min-blocks", 100);
-    if (o.minBlocks < 0) throw cli_error(105, "--min-blocks: N >= 0 expected");
-    o.lineOffset = p.integer("--line-offset", 0);
-    o.lines = p.integer("--lines", 0);
-    if (o.lineOffset < 0 || o.lines < 0) throw cli_error(105, "--line-offset, --lines: non-negative values expected");
+    o.bits = p.within("--bits", 12, 8, 16, "8 <= N <= 16 expected");
+    p.valid_range(1, &o.validMin, &o.validMax);
+    o.minBlocks = p.within("--min-blocks", 100, 0, INT_MAX, "N >= 0 expected");
+    p.line_range(&o.lineOffset, &o.lines);
     if (o.lineOffset % o.block != 0) throw cli_error(105, "--line-offset: a multiple of --block expected");
-    o.force = p.flag.count("--force") != 0;
+    o.force = p.has("--force");
     char buf[256];
     snprintf(buf, sizeof buf, " block=%d bits=%d valid-min=%d valid-max=%d min-blocks=%ld bil=%d line-offset=%ld lines=%ld", o.block, o.bits, o.validMin,
              o.validMax, o.minBlocks, o.bil ? 1 : 0, o.lineOffset, o.lines);
@@ -745,9 +753,8 @@ int run_overviews(const std::vector<std::string> &args, int width)
     OverviewsOptions o;
     o.width = p.integer("--width", width);
     o.pyramid.levels = overview_levels(p);
-    o.pyramid.validMin = p.integer("--valid-min", 1);
-    if (o.pyramid.validMin < 0 || o.pyramid.validMin > 65535) throw cli_error(105, "--valid-min: 0 <= N <= 65535 expected");
-    o.force = p.flag.count("--force") != 0;
+    o.pyramid.validMin = p.valid_min();
+    o.force = p.has("--force");
     RunOverviews(image, p.str("--out"), o);
     return 0;
 }
@@ -779,20 +786,16 @@ int run_regcheck(const std::vector<std::string> &args, int width)
     o.shiftY = p.integer("--shift-y", 0);
     o.tile = p.integer("--tile", 64);
     if (o.tile < OIP_MATCH_MIN_T || o.tile > OIP_MATCH_MAX_T || o.tile % 8 != 0) throw cli_error(105, "--tile: a multiple of 8, 8 <= T <= 128 expected");
-    o.search = p.integer("--search", 4);
-    if (o.search < 1 || o.search > OIP_MATCH_MAX_S) throw cli_error(105, "--search: 1 <= S <= 16 expected");
-    o.step = p.integer("--step", o.tile);
-    if (o.step < 1) throw cli_error(105, "--step: N >= 1 expected");
-    o.validMin = p.integer("--valid-min", 1);
-    o.validMax = p.integer("--valid-max", 65535);
-    if (o.validMin < 0 || o.validMax > 65535 || o.validMin > o.validMax) throw cli_error(105, "--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
+    o.search = p.within("--search", 4, 1, OIP_MATCH_MAX_S, "1 <= S <= 16 expected");
+    o.step = p.within("--step", o.tile, 1, INT_MAX, "N >= 1 expected");
+    p.valid_range(1, &o.validMin, &o.validMax);
     o.minScore = p.real("--min-score", 0.5);
     if (!(o.minScore >= -1.0 && o.minScore <= 1.0)) throw cli_error(105, "--min-score: -1 <= X <= 1 expected");
     o.width = p.integer("--width", width);
     o.width2 = p.integer("--width2", 0);
     if (o.width <= 0 || (p.has("--width2") && o.width2 <= 0)) throw cli_error(105, "--width/--width2: a positive line width expected");
-    o.bil = p.flag.count("--bil") != 0;
-    o.force = p.flag.count("--force") != 0;
+    o.bil = p.has("--bil");
+    o.force = p.has("--force");
     char buf[256];
     snprintf(buf, sizeof buf, " band1=%d band2=%d scale=%d shift-x=%ld shift-y=%ld tile=%d search=%d step=%d valid-min=%d valid-max=%d min-score=%g",
              o.band1, o.band2, o.scale, o.shiftX, o.shiftY, o.tile, o.search, o.step, o.validMin, o.validMax, o.minScore);
@@ -818,10 +821,8 @@ int run_regfix(const std::vector<std::string> &args, int width)
     existing_file(p, "--image");
     RegfixOptions o;
     o.report = p.str("--report");
-    o.smooth = p.integer("--smooth", 0);
-    if (o.smooth < 0 || o.smooth > OIP_REGFIX_MAX_SMOOTH) throw cli_error(105, "--smooth: 0 <= N <= 16 expected");
-    o.width = p.integer("--width", width);
-    if (o.width <= 0) throw cli_error(105, "--width: a positive line width expected");
+    o.smooth = p.within("--smooth", 0, 0, OIP_REGFIX_MAX_SMOOTH, "0 <= N <= 16 expected");
+    o.width = p.positive_width(width);
     if (p.has("--bands")) {
         const std::string b = p.str("--bands");
         if (b == "all") {
@@ -838,8 +839,8 @@ int run_regfix(const std::vector<std::string> &args, int width)
             }
         }
     }
-    o.bil = p.flag.count("--bil") != 0;
-    o.force = p.flag.count("--force") != 0;
+    o.bil = p.has("--bil");
+    o.force = p.has("--force");
     RunRegfix(p.str("--image"), p.str("--out"), o);
     return 0;
 }
@@ -860,16 +861,13 @@ int run_pansharpen(const std::vector<std::string> &args, int width)
     PansharpenOptions o;
     o.pan = p.str("--pan");
     o.mss = p.str("--mss");
-    o.lineOffset = p.integer("--line-offset", 0);
-    if (o.lineOffset < 0) throw cli_error(105, "--line-offset: N >= 0 expected");
-    o.maxGain = p.integer("--max-gain", OIP_PANSHARPEN_DEF_GAIN);
-    if (o.maxGain < 1 || o.maxGain > OIP_PANSHARPEN_MAX_GAIN) throw cli_error(105, "--max-gain: 1 <= G <= 64 expected");
-    o.width = p.integer("--width", width);
-    if (o.width <= 0) throw cli_error(105, "--width: a positive line width expected");
+    o.lineOffset = p.within("--line-offset", 0, 0, INT_MAX, "N >= 0 expected");
+    o.maxGain = p.within("--max-gain", OIP_PANSHARPEN_DEF_GAIN, 1, OIP_PANSHARPEN_MAX_GAIN, "1 <= G <= 64 expected");
+    o.width = p.positive_width(width);
     if (p.has("--levels") && !p.has("--overviews")) throw cli_error(107, "--levels requires --overviews");
     o.overviews = p.has("--overviews");
     o.pyramid.levels = overview_levels(p);
-    o.force = p.flag.count("--force") != 0;
+    o.force = p.has("--force");
     RunPansharpen(p.str("--out"), o);
     return 0;
 }

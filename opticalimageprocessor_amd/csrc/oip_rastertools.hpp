@@ -1,7 +1,11 @@
 // oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, noise, overviews,
-// regcheck, regfix, pansharpen) above the host layer of oip_host.hpp: what they check before a device is touched, the one driver that streams a
-// RAW strip through the device in line blocks (geometry: oip_stripplan.hpp), the resident filter of a TIFF product, and the
-// tools.
+// regcheck, regfix, pansharpen) above the host layer of oip_host.hpp.  Stated once for all of them: the file checks made before a
+// device is touched (container, RAW size rule, line range, GuardOutput), the loaders of a resident image, the driver that streams
+// a RAW strip through the device in line blocks (geometry: oip_stripplan.hpp), the filter driver above it, the closing
+// throughput line and the text-report writer.  Then the tools, each as Options / Check / Run.  The ranges of option values are
+// refused by the tool's run_* in oip_main.cpp (exit 104-109); a *Check holds what needs the container, a file or a combination
+// with the image (exit 2 or 254), and the few option checks of the older tools that run_* does not make (quicklook's --factor
+// and --bands, a --width nothing else tests).  No condition is stated in both.
 #pragma once
 
 #include "oip_host.hpp"
@@ -30,33 +34,91 @@ inline long RawLineCount(const std::string &file, const char *what, size_t lineB
     return (long)(size / lineBytes);
 }
 
-// the lines [first, first + count) of `file` that --line-offset / --lines (0: to the end) select; returns the file's lines
+// the lines [first, first + count) of the `total` lines of `what` that --line-offset / --lines (0: to the end) select
+inline void LineRange(const std::string &what, long total, long lineOffset, long lines, long *first, long *count)
+{
+    if (lineOffset >= total) throw std::invalid_argument(what + " has " + std::to_string(total) + " lines: --line-offset is beyond them");
+    *first = lineOffset;
+    *count = lines > 0 ? std::min(lines, total - lineOffset) : total - lineOffset;
+}
+
+// ... of a RAW file of `width` samples per line; returns the file's lines
 inline long RawLineRange(const std::string &file, const char *what, int width, long lineOffset, long lines, long *first, long *count)
 {
     const long total = RawLineCount(file, what, (size_t)width * BYTES_PER_PIXEL);
-    if (lineOffset >= total) throw std::invalid_argument(std::string(what) + " file has " + std::to_string(total) + " lines: --line-offset is beyond them");
-    *first = lineOffset;
-    *count = lines > 0 ? std::min(lines, total - lineOffset) : total - lineOffset;
+    LineRange(std::string(what) + " file", total, lineOffset, lines, first, count);
     return total;
 }
 
-// the product of a filter (mtfc, despike): <stem><suffix><ext> unless named, in the container `ext` of the input, never the
-// input itself, and an existing file only with --force
+// the output rule of every tool that reads an image and writes one file for it (all but rrc-calib, whose coefficient files
+// have RrcCalibCheck's): `path` is none of the input files, and an existing file only with --force
+inline void GuardOutput(const std::string &path, const std::vector<std::string> &inputs, const char *tool, bool force)
+{
+    struct stat st;
+    if (stat(path.c_str(), &st) != 0) return;
+    for (const std::string &in : inputs)
+        if (std::filesystem::equivalent(path, in))
+            throw std::invalid_argument("output file [" + path + "] is " + (inputs.size() == 1 ? "the input image" : "an input image"));
+    if (!force) throw std::runtime_error("output file [" + path + "] exists: " + tool + " does not replace a file without --force");
+}
+
+// the product of a filter (mtfc, despike, regfix): <stem><suffix><ext> unless named, in the container `ext` of the input
 inline std::string FilterOutputPath(const std::string &file, const std::string &out, const char *suffix, const std::string &ext, const char *tool, bool force)
 {
     const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, suffix) : out;
     if (to_lower(std::filesystem::path(path).extension().string()) != ext)
         throw std::invalid_argument(std::string(tool) + ": the output has the container of the input (" + ext + ")");
-    struct stat st;
-    if (stat(path.c_str(), &st) == 0) {
-        if (std::filesystem::equivalent(path, file)) throw std::invalid_argument("output file [" + path + "] is the input image");
-        if (!force) throw std::runtime_error("output file [" + path + "] exists: " + tool + " does not replace a file without --force");
-    }
+    GuardOutput(path, {file}, tool, force);
     return path;
 }
 
-// OIP_MTFC_BLOCK_LINES / OIP_DESPIKE_BLOCK_LINES / OIP_NOISE_BLOCK_LINES / OIP_OVERVIEWS_BLOCK_LINES / OIP_REGFIX_BLOCK_LINES (test hooks: several blocks on a small image); 0 without one
-inline long BlockLinesHook(const char *name) { const char *e = getenv(name); return e ? atol(e) : 0; }
+// OIP_<TOOL>_BLOCK_LINES of mtfc, despike, noise, overviews and regfix (test hooks: several blocks on a small image), rounded
+// down to the multiple q of lines the tool needs and never below q; 0 without one
+inline long BlockLinesHook(const char *name, long q = 1)
+{
+    const char *e = getenv(name);
+    const long v = e ? atol(e) : 0;
+    return v > 0 ? std::max(q, v / q * q) : 0;
+}
+
+// the closing line of a tool
+inline void LogThroughput(size_t bytes, double seconds) { OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, seconds, bytes / seconds / 1024.0 / 1024.0); }
+
+// a text report: write(FILE *) returns whether every line went out; a failed open, write or close is an error
+template <class Write> inline void WriteTextFile(const std::string &path, Write write)
+{
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) throw std::runtime_error("open file [" + path + "] failed: " + std::to_string(errno));
+    const bool ok = write(f);
+    if (fclose(f) != 0 || !ok) throw std::runtime_error("write file [" + path + "] failed");
+}
+
+// ---- resident images --------------------------------------------------------------------------------------------
+struct ResidentImage {
+    DevBuf<uint16_t> buf;
+    int w = 0, spp = 1;
+    long h = 0;
+    size_t bytes() const { return (size_t)w * h * spp * BYTES_PER_PIXEL; }
+};
+
+// a TIFF product of 1 or 4 samples per pixel, read to the device
+inline void LoadTiffProduct(const std::string &file, const char *tool, ResidentImage *m)
+{
+    OLOG("Reading image from file `%s' ...", file.c_str());
+    read_tiff_to_device(file, &m->w, &m->h, &m->spp, m->buf);
+    if (m->spp != 1 && m->spp != MSS_BANDS) throw std::invalid_argument(std::string(tool) + ": a TIFF of 1 or 4 samples per pixel expected");
+}
+
+// ... or a whole single-band RAW strip of rawWidth samples per line, which `what` names in the size rule
+inline void LoadResident(const std::string &file, bool isTiff, int rawWidth, const char *what, const char *tool, ResidentImage *m)
+{
+    if (isTiff) return LoadTiffProduct(file, tool, m);
+    m->w = rawWidth;
+    m->spp = 1;
+    m->h = RawLineCount(file, what, (size_t)rawWidth * BYTES_PER_PIXEL);
+    m->buf.alloc((size_t)m->w * m->h);
+    m->buf.load_file(file, (size_t)m->w * m->h);
+}
 
 // ---- the strip-streaming driver ---------------------------------------------------------------------------------
 // A RAW strip is never resident.  The line blocks of `plan` go file -> pinned ring -> one of two device blocks; work(src,
@@ -114,21 +176,29 @@ template <class Work> inline void ReadStrip(const std::string &file, const Strip
     StreamStrip(file, plan, nullptr, [&](const uint16_t *src, long s0, long lines, uint16_t *, long, long) { work(src, s0 - plan.first, lines); });
 }
 
-// A TIFF product is filtered resident, by one work(src, dst, w, h, spp), and leaves through the product writer of `oip
-// stitch`; `word` is the tool's for what it writes.  Returns the bytes of the image.
-template <class Work> inline size_t FilterTiffResident(const std::string &file, const std::string &outPath, const char *tool, const char *word, Work work)
+// The filters (mtfc, despike, regfix) write an image of the size and container of their input through one
+// work(src, srcFirst, srcLines, dst, dstFirst, dstLines, w, L, spp), the argument order of their kernels.  A TIFF product is
+// resident: one call over the whole image, which leaves through the product writer of `oip stitch` (`word` is the tool's for
+// what it writes).  A RAW strip of rawWidth samples per line streams through StreamStrip with `halo` lines either side of a
+// block, one call per block with spp == 1; `hook` is the tool's OIP_*_BLOCK_LINES.  Returns the bytes of the image.
+template <class Work>
+inline size_t FilterImage(const std::string &file, const std::string &outPath, bool isTiff, int rawWidth, long halo, const char *hook, const char *tool,
+                          const char *word, Work work)
 {
-    int w = 0, spp = 0;
-    long h = 0;
-    DevBuf<uint16_t> img;
-    OLOG("Reading image from file `%s' ...", file.c_str());
-    read_tiff_to_device(file, &w, &h, &spp, img);
-    if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument(std::string(tool) + ": a TIFF of 1 or 4 samples per pixel expected");
-    DevBuf<uint16_t> res((size_t)w * h * spp);
-    work(img.p, res.p, w, h, spp);
-    OLOG("Write %s image to file '%s' ...", word, outPath.c_str());
-    write_tiff_from_device(outPath, res.p, w, h, spp, tiff_compression(spp == 1 ? TIFF_NONE : TIFF_LZW), false);
-    return (size_t)w * h * spp * BYTES_PER_PIXEL;
+    if (isTiff) {
+        ResidentImage m;
+        LoadTiffProduct(file, tool, &m);
+        DevBuf<uint16_t> res((size_t)m.w * m.h * m.spp);
+        work(m.buf.p, 0, m.h, res.p, 0, m.h, m.w, m.h, m.spp);
+        OLOG("Write %s image to file '%s' ...", word, outPath.c_str());
+        write_tiff_from_device(outPath, res.p, m.w, m.h, m.spp, tiff_compression(m.spp == 1 ? TIFF_NONE : TIFF_LZW), false);
+        return m.bytes();
+    }
+    const size_t lineBytes = (size_t)rawWidth * BYTES_PER_PIXEL;
+    const long L = RawLineCount(file, "image", lineBytes);
+    StreamStrip(file, StripPlan{0, L, L, halo, StripBlockLines(lineBytes, 1, BlockLinesHook(hook)), lineBytes}, &outPath,
+                [&](const uint16_t *d, long s0, long sn, uint16_t *q, long r, long m) { work(d, s0, sn, q, r, m, rawWidth, L, 1); });
+    return (size_t)L * lineBytes;
 }
 
 // ---- oip rrc-calib: the coefficient files every other action consumes --------------------------------
@@ -163,9 +233,7 @@ inline std::vector<double> RrcCalibImage(const std::string &file, const char *wh
               [&](const uint16_t *d, long, long m) { ck(oip_colstats_u16(ctx, d, W, W, m, o.validMin, o.validMax, acc.p)); });
     std::vector<uint64_t> totals((size_t)3 * W);
     acc.download(totals.data(), totals.size());
-    const double es = sw.tick();
-    const size_t bytes = (size_t)nLines * lineBytes;
-    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+    LogThroughput((size_t)nLines * lineBytes, sw.tick());
 
     std::vector<double> kb((size_t)2 * W), ref((size_t)2 * groups);
     std::vector<int> dead(groups);
@@ -192,7 +260,8 @@ inline std::vector<double> RrcCalibImage(const std::string &file, const char *wh
     return kb;
 }
 
-// everything that can be refused without a device: sizes, line range, outputs named twice, outputs that exist
+// what is refused without a device, all of it stated here alone: --width (a multiple of 4 for MSS), the file sizes, the line
+// range, outputs named twice, outputs that exist
 inline void RrcCalibCheck(const std::string &pan, const std::string &mss, const std::string &outPan, const std::string *outMss, const RrcCalibOptions &o)
 {
     long a = 0, b = 0;
@@ -258,7 +327,8 @@ struct QuicklookOptions {
     bool force = false;
 };
 
-// everything that can be refused without a device; returns the output path and whether the input is a TIFF
+// what is refused without a device and stated here alone: --factor and --bands, --width with --bil, the output; returns the
+// output path and whether the input is a TIFF
 inline std::string QuicklookCheck(const std::string &file, const std::string &out, const QuicklookOptions &o, bool *isTiff)
 {
     *isTiff = RasterContainer(file, "quicklook") == ".tiff";
@@ -274,11 +344,9 @@ inline std::string QuicklookCheck(const std::string &file, const std::string &ou
         for (int b : o.bands)
             if (b < 1 || b > MSS_BANDS) throw usage_error("--bands: band index out of range (1.." + std::to_string(MSS_BANDS) + ")");
     }
-    // (not FilterOutputPath: a quick look is a .TIFF whatever the input is, and may be named like anything but an existing file)
+    // (not FilterOutputPath: a quick look is a .TIFF whatever the input is, and may be named like anything)
     const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_QUICKLOOK_SUFFIX, ".TIFF") : out;
-    struct stat st;
-    if (!o.force && stat(path.c_str(), &st) == 0)
-        throw std::runtime_error("output file [" + path + "] exists: quicklook does not replace a file without --force");
+    GuardOutput(path, {file}, "quicklook", o.force);
     return path;
 }
 
@@ -309,23 +377,17 @@ inline void RunQuicklook(const std::string &file, const std::string &out, const 
         planes.alloc(plane * nb);
     };
     if (isTiff) {
-        int w = 0, spp = 0;
-        long h = 0;
-        DevBuf<uint16_t> img;
-        OLOG("Reading image from file `%s' ...", file.c_str());
-        read_tiff_to_device(file, &w, &h, &spp, img);
-        if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument("quicklook: a TIFF of 1 or 4 samples per pixel expected");
-        if (o.lineOffset >= h) throw std::invalid_argument("image has " + std::to_string(h) + " lines: --line-offset is beyond them");
-        first = o.lineOffset;
-        nLines = o.lines > 0 ? std::min(o.lines, h - first) : h - first;
-        nb = spp;
-        bw = w;
+        ResidentImage m;
+        LoadTiffProduct(file, "quicklook", &m);
+        LineRange("image", m.h, o.lineOffset, o.lines, &first, &nLines);
+        nb = m.spp;
+        bw = m.w;
         for (int b : o.bands)
             if (b > nb) throw usage_error("--bands: band index out of range (1.." + std::to_string(nb) + ")");
         alloc_planes();
-        ck(oip_decimate_box_u16(ctx, img.p + (size_t)first * w * spp, (long)w * spp, w, nLines, spp, F, planes.p, ow, plane));
-        ck(oip_sync(ctx));                  // img is released at the end of this block
-        inBytes = (size_t)nLines * w * spp * BYTES_PER_PIXEL;
+        ck(oip_decimate_box_u16(ctx, m.buf.p + (size_t)first * m.w * m.spp, (long)m.w * m.spp, m.w, nLines, m.spp, F, planes.p, ow, plane));
+        ck(oip_sync(ctx));                  // the image is released at the end of this block
+        inBytes = (size_t)nLines * m.w * m.spp * BYTES_PER_PIXEL;
     } else {
         // the decimation runs per line block of the strip (ReadStrip), a block being a multiple of F lines
         const size_t lineBytes = (size_t)o.width * BYTES_PER_PIXEL;
@@ -366,8 +428,7 @@ inline void RunQuicklook(const std::string &file, const std::string &out, const 
     img8.download(host.data(), host.size());
     OLOG("Write quick look (%d x %ld, %s) to file '%s' ...", ow, oh, nch == 1 ? "grey" : "RGB", outPath.c_str());
     write_tiff_u8(outPath, host.data(), ow, oh, nch);
-    const double es = total.tick();
-    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", inBytes, es, inBytes / es / 1024.0 / 1024.0);
+    LogThroughput(inBytes, total.tick());
 }
 
 // ---- oip mtfc: MTF compensation of a strip or product ---------------------------------------------------------------
@@ -388,7 +449,8 @@ struct MtfcTaps {
     int32_t t[OIP_CONVOLVE_MAX_K * OIP_CONVOLVE_MAX_K];
 };
 
-// everything that can be refused without a device: the container, the taps, the output; returns the output path
+// what is refused without a device and stated here alone: the container, --width and the size of a RAW file, the taps, the
+// output; returns the output path
 inline std::string MtfcCheck(const std::string &file, const std::string &out, const MtfcOptions &o, bool *isTiff, MtfcTaps *taps)
 {
     const std::string ext = RasterContainer(file, "mtfc");
@@ -416,7 +478,7 @@ inline void RunMtfc(const std::string &file, const std::string &out, const MtfcO
     bool isTiff = false;
     MtfcTaps taps;
     const std::string outPath = MtfcCheck(file, out, o, &isTiff, &taps);
-    const int ky = taps.ky, kx = taps.kx, ry = ky / 2;
+    const int ky = taps.ky, kx = taps.kx;
     long absSum = 0;
     OLOG("MTFC taps (Q12, %d x %d):", ky, kx);
     for (int j = 0; j < ky; ++j) {
@@ -431,23 +493,12 @@ inline void RunMtfc(const std::string &file, const std::string &out, const MtfcO
     oip_ctx *ctx = Device::get().ctx();
     auto ck = [](int rc) { Device::get().check(rc); };
     stop_watch total;
-    size_t bytes = 0;
-    if (isTiff) {
-        bytes = FilterTiffResident(file, outPath, "mtfc", "filtered", [&](const uint16_t *src, uint16_t *dst, int w, long h, int spp) {
-            ck(oip_convolve_u16(ctx, src, 0, h, dst, 0, h, w, h, spp, taps.t, ky, kx, o.validMin));
-        });
-    } else {
-        // the filter runs per line block of the strip, with ry halo lines either side (StreamStrip)
-        const size_t lineBytes = (size_t)o.width * BYTES_PER_PIXEL;
-        const long L = RawLineCount(file, "image", lineBytes);
-        StreamStrip(file, StripPlan{0, L, L, ry, StripBlockLines(lineBytes, 1, BlockLinesHook("OIP_MTFC_BLOCK_LINES")), lineBytes}, &outPath,
-                   [&](const uint16_t *d, long s0, long sn, uint16_t *q, long r, long m) {
-                       ck(oip_convolve_u16(ctx, d, s0, sn, q, r, m, o.width, L, 1, taps.t, ky, kx, o.validMin));
-                   });
-        bytes = (size_t)L * lineBytes;
-    }
-    const double es = total.tick();
-    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+    // a block of a strip needs ky / 2 halo lines either side
+    const size_t bytes = FilterImage(file, outPath, isTiff, o.width, ky / 2, "OIP_MTFC_BLOCK_LINES", "mtfc", "filtered",
+                                     [&](const uint16_t *src, long s0, long sn, uint16_t *dst, long r, long m, int w, long L, int spp) {
+                                         ck(oip_convolve_u16(ctx, src, s0, sn, dst, r, m, w, L, spp, taps.t, ky, kx, o.validMin));
+                                     });
+    LogThroughput(bytes, total.tick());
 }
 
 // ---- oip despike: repair of a raw strip ahead of RRC ------------------------------------------------------------------
@@ -469,7 +520,8 @@ struct DespikeTable {
     int listed = 0, longestRun = 0;
 };
 
-// everything that can be refused without a device: the container, sizes, the list and its table, the outputs; returns the output path
+// what is refused without a device and stated here alone: the container and what it excludes, --width with --bil, the size of a
+// RAW file, the list and its table, the output and the report; returns the output path
 inline std::string DespikeCheck(const std::string &file, const std::string &out, const DespikeOptions &o, bool *isTiff, DespikeTable *table)
 {
     const std::string ext = RasterContainer(file, "despike");
@@ -517,37 +569,21 @@ inline void RunDespike(const std::string &file, const std::string &out, const De
     oip_ctx *ctx = Device::get().ctx();
     auto ck = [](int rc) { Device::get().check(rc); };
     stop_watch total;
-    size_t bytes = 0;
     DevBuf<uint64_t> cnt;                                               // replacements per sample column; only a threshold replaces
     std::vector<uint64_t> counts;
-    auto alloc_counts = [&](size_t n) {
-        if (!o.hasThreshold) return;
-        cnt.alloc(n);
-        ck(oip_memset(ctx, cnt.p, 0, n * sizeof(uint64_t)));
-        counts.resize(n);
-    };
-    if (isTiff) {
-        bytes = FilterTiffResident(file, outPath, "despike", "repaired", [&](const uint16_t *src, uint16_t *dst, int w, long h, int spp) {
-            alloc_counts((size_t)w * spp);
-            ck(oip_despike_u16(ctx, src, 0, h, dst, 0, h, w, h, spp, 1, nullptr, o.thrAbs, o.thrRelQ8, o.validMin, cnt.p));
-        });
-    } else {
-        // the kernel runs per line block of the strip, with one halo line either side (StreamStrip)
-        const int W = o.width;
-        const size_t lineBytes = (size_t)W * BYTES_PER_PIXEL;
-        const long L = RawLineCount(file, "image", lineBytes);
-        DevBuf<int32_t> tab;
-        if (!table.tab.empty()) {
-            tab.alloc(table.tab.size());
-            tab.upload(table.tab.data(), table.tab.size());
-        }
-        alloc_counts((size_t)W);
-        StreamStrip(file, StripPlan{0, L, L, 1, StripBlockLines(lineBytes, 1, BlockLinesHook("OIP_DESPIKE_BLOCK_LINES")), lineBytes}, &outPath,
-                   [&](const uint16_t *d, long s0, long sn, uint16_t *q, long r, long m) {
-                       ck(oip_despike_u16(ctx, d, s0, sn, q, r, m, W, L, 1, o.bil ? MSS_BANDS : 1, tab.p, o.thrAbs, o.thrRelQ8, o.validMin, cnt.p));
-                   });
-        bytes = (size_t)L * lineBytes;
-    }
+    DevBuf<int32_t> tab;                                                // the column table and --bil: a RAW strip's alone (DespikeCheck)
+    if (!table.tab.empty()) tab.assign(table.tab);
+    // a block of a strip needs one halo line either side
+    const size_t bytes = FilterImage(file, outPath, isTiff, o.width, 1, "OIP_DESPIKE_BLOCK_LINES", "despike", "repaired",
+                                     [&](const uint16_t *src, long s0, long sn, uint16_t *dst, long r, long m, int w, long L, int spp) {
+                                         if (o.hasThreshold && !cnt.p) {                        // the first block knows the columns
+                                             counts.resize((size_t)w * spp);
+                                             cnt.alloc(counts.size());
+                                             ck(oip_memset(ctx, cnt.p, 0, counts.size() * sizeof(uint64_t)));
+                                         }
+                                         ck(oip_despike_u16(ctx, src, s0, sn, dst, r, m, w, L, spp, o.bil ? MSS_BANDS : 1, tab.p, o.thrAbs, o.thrRelQ8,
+                                                            o.validMin, cnt.p));
+                                     });
     if (o.hasThreshold) {
         cnt.download(counts.data(), counts.size());                     // (synchronises: the last kernel has run)
         uint64_t sum = 0;
@@ -556,23 +592,19 @@ inline void RunDespike(const std::string &file, const std::string &out, const De
             if (counts[x]) { sum += counts[x]; hit.push_back(x); }
         OLOG("%llu samples replaced in %zu of %zu columns", (unsigned long long)sum, hit.size(), counts.size());
         if (!o.report.empty()) {
-            FILE *f = fopen(o.report.c_str(), "wb");
-            if (!f) throw std::runtime_error("open file [" + o.report + "] failed: " + std::to_string(errno));
-            fprintf(f, "# column count: samples replaced by oip despike --threshold %d in %s\n", o.thrAbs, file.c_str());
-            for (size_t x : hit) fprintf(f, "%zu %llu\n", x, (unsigned long long)counts[x]);
-            if (fclose(f) != 0) throw std::runtime_error("write of file [" + o.report + "] failed");
+            WriteTextFile(o.report, [&](FILE *f) {
+                fprintf(f, "# column count: samples replaced by oip despike --threshold %d in %s\n", o.thrAbs, file.c_str());
+                for (size_t x : hit) fprintf(f, "%zu %llu\n", x, (unsigned long long)counts[x]);
+                return true;
+            });
             OLOG("Replacement counts written to file [%s].", o.report.c_str());
         }
         std::stable_sort(hit.begin(), hit.end(), [&](size_t a, size_t b) { return counts[a] > counts[b]; });
         for (size_t i = 0; i < hit.size() && i < 10; ++i) RLOG("    column %zu: %llu", hit[i], (unsigned long long)counts[hit[i]]);
     } else if (!o.report.empty()) {
-        FILE *f = fopen(o.report.c_str(), "wb");
-        if (!f) throw std::runtime_error("open file [" + o.report + "] failed: " + std::to_string(errno));
-        fprintf(f, "# column count: no --threshold, no sample replaced in %s\n", file.c_str());
-        fclose(f);
+        WriteTextFile(o.report, [&](FILE *f) { return fprintf(f, "# column count: no --threshold, no sample replaced in %s\n", file.c_str()) > 0; });
     }
-    const double es = total.tick();
-    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+    LogThroughput(bytes, total.tick());
 }
 
 // `oip despike --noise REPORT [--k-sigma K]`: the two threshold parameters from the report of `oip noise`, each the maximum
@@ -605,15 +637,12 @@ struct NoiseOptions {
     std::string params;                     // the first line of the report
 };
 
-// everything that can be refused without a device; returns the output path and whether the input is a TIFF
+// what is refused without a device and depends on the image (the option ranges are run_noise's): the container, --bil on a
+// TIFF, --width with --bil, the size and line range of a RAW file, an image without a block, the output; returns the output path
+// and whether the input is a TIFF
 inline std::string NoiseCheck(const std::string &file, const std::string &out, const NoiseOptions &o, bool *isTiff)
 {
     *isTiff = RasterContainer(file, "noise") == ".tiff";
-    if (o.block != 8 && o.block != 16) throw usage_error("--block: 8 or 16 expected");
-    if (o.bits < 8 || o.bits > 16) throw usage_error("--bits: 8 <= N <= 16 expected");
-    if (o.validMin < 0 || o.validMax > 65535 || o.validMin > o.validMax) throw usage_error("--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
-    if (o.minBlocks < 0 || o.lineOffset < 0 || o.lines < 0) throw usage_error("--min-blocks, --line-offset, --lines: non-negative values expected");
-    if (o.lineOffset % o.block != 0) throw usage_error("--line-offset: a multiple of --block expected");
     if (*isTiff) {
         if (o.bil) throw std::invalid_argument("noise: --bil applies to a RAW strip: a TIFF product holds its bands per pixel");
     } else {
@@ -623,11 +652,7 @@ inline std::string NoiseCheck(const std::string &file, const std::string &out, c
         if (n < o.block || o.width / (o.bil ? MSS_BANDS : 1) < o.block) throw std::invalid_argument("noise: the image holds no block of " + std::to_string(o.block) + " x " + std::to_string(o.block));
     }
     const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_NOISE_SUFFIX, ".CSV") : out;
-    struct stat st;
-    if (stat(path.c_str(), &st) == 0) {
-        if (std::filesystem::equivalent(path, file)) throw std::invalid_argument("output file [" + path + "] is the input image");
-        if (!o.force) throw std::runtime_error("output file [" + path + "] exists: noise does not replace a file without --force");
-    }
+    GuardOutput(path, {file}, "noise", o.force);
     return path;
 }
 
@@ -642,7 +667,7 @@ inline void RunNoise(const std::string &file, const std::string &out, const Nois
     size_t inBytes = 0;
     DevBuf<uint16_t> keys;                  // one plane of nbx x nby keys per band
     int nb = 0, nbx = 0;
-    long nby = 0, nLines = 0;
+    long nby = 0, first = 0, nLines = 0;
     size_t plane = 0;
     auto alloc_keys = [&](int bandWidth) {
         nbx = bandWidth / B;
@@ -652,30 +677,24 @@ inline void RunNoise(const std::string &file, const std::string &out, const Nois
         keys.alloc(plane * nb);
     };
     if (isTiff) {
-        int w = 0, spp = 0;
-        long h = 0;
-        DevBuf<uint16_t> img;
-        OLOG("Reading image from file `%s' ...", file.c_str());
-        read_tiff_to_device(file, &w, &h, &spp, img);
-        if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument("noise: a TIFF of 1 or 4 samples per pixel expected");
-        if (o.lineOffset >= h) throw std::invalid_argument("image has " + std::to_string(h) + " lines: --line-offset is beyond them");
-        nLines = o.lines > 0 ? std::min(o.lines, h - o.lineOffset) : h - o.lineOffset;
-        nb = spp;
-        alloc_keys(w);
-        ck(oip_noise_blocks_u16(ctx, img.p + (size_t)o.lineOffset * w * spp, (long)w * spp, w, nLines, spp, B, shift, o.validMin, o.validMax, keys.p, nbx, plane));
-        ck(oip_sync(ctx));                  // img is released at the end of this block
-        inBytes = (size_t)nLines * w * spp * BYTES_PER_PIXEL;
+        ResidentImage m;
+        LoadTiffProduct(file, "noise", &m);
+        LineRange("image", m.h, o.lineOffset, o.lines, &first, &nLines);
+        nb = m.spp;
+        alloc_keys(m.w);
+        ck(oip_noise_blocks_u16(ctx, m.buf.p + (size_t)first * m.w * m.spp, (long)m.w * m.spp, m.w, nLines, m.spp, B, shift, o.validMin, o.validMax, keys.p,
+                                nbx, plane));
+        ck(oip_sync(ctx));                  // the image is released at the end of this block
+        inBytes = (size_t)nLines * m.w * m.spp * BYTES_PER_PIXEL;
     } else {
         // the kernel runs per line block of the strip (ReadStrip), a block being a multiple of B lines; a BIL band is a window
         // of the line, so that no block straddles two bands
-        long first = 0;
         const long fileLines = RawLineRange(file, "image", o.width, o.lineOffset, o.lines, &first, &nLines);
         const size_t lineBytes = (size_t)o.width * BYTES_PER_PIXEL;
         nb = o.bil ? MSS_BANDS : 1;
         const int bw = o.width / nb;
         alloc_keys(bw);
-        const long hook = BlockLinesHook("OIP_NOISE_BLOCK_LINES");
-        ReadStrip(file, StripPlan{first, nLines, fileLines, 0, StripBlockLines(lineBytes, B, hook > 0 ? std::max<long>(B, hook / B * B) : 0), lineBytes},
+        ReadStrip(file, StripPlan{first, nLines, fileLines, 0, StripBlockLines(lineBytes, B, BlockLinesHook("OIP_NOISE_BLOCK_LINES", B)), lineBytes},
                   [&](const uint16_t *d, long r, long m) {
                       for (int b = 0; b < nb; ++b)
                           ck(oip_noise_blocks_u16(ctx, d + (size_t)b * bw, o.width, bw, m, 1, B, shift, o.validMin, o.validMax,
@@ -703,10 +722,7 @@ inline void RunNoise(const std::string &file, const std::string &out, const Nois
             throw std::runtime_error("band " + std::to_string(b + 1) + ": " + err + " (" + std::to_string(n.realBlocks()) + " blocks, " + std::to_string(n.nodata) +
                                      " without data, " + std::to_string(n.structured) + " structured; --min-blocks " + std::to_string(o.minBlocks) + ")");
     }
-    FILE *f = fopen(outPath.c_str(), "w");
-    if (!f) throw std::runtime_error("open file [" + outPath + "] failed: " + std::to_string(errno));
-    const bool ok = WriteNoiseReport(f, o.params, bands, shift);
-    if (fclose(f) != 0 || !ok) throw std::runtime_error("write file [" + outPath + "] failed");
+    WriteTextFile(outPath, [&](FILE *f) { return WriteNoiseReport(f, o.params, bands, shift); });
     for (int b = 0; b < nb; ++b) OLOG("noise: %s", NoiseBandLine(b + 1, bands[b]).c_str());
     const double es = total.tick();
     OLOG("Report written to '%s'; %zu bytes in %.3f seconds (%.1f MBps).", outPath.c_str(), inBytes, es, inBytes / es / 1024.0 / 1024.0);
@@ -724,7 +740,8 @@ struct OverviewsOptions {
     bool force = false;
 };
 
-// everything that can be refused without a device: the container, sizes, the ranges, the output; returns the output path
+// what is refused without a device and depends on the image (--levels and --valid-min are run_overviews'): the container,
+// --width and the size of a RAW file, the output; returns the output path
 inline std::string OverviewsCheck(const std::string &file, const std::string &out, const OverviewsOptions &o, bool *isTiff)
 {
     *isTiff = RasterContainer(file, "overviews") == ".tiff";
@@ -732,15 +749,9 @@ inline std::string OverviewsCheck(const std::string &file, const std::string &ou
         if (o.width <= 0) throw std::invalid_argument("--width: a positive line width expected");
         RawLineCount(file, "image", (size_t)o.width * BYTES_PER_PIXEL);
     }
-    if (o.pyramid.levels < 0 || o.pyramid.levels > 16) throw std::invalid_argument("--levels: 1 <= N <= 16 expected");
-    if (o.pyramid.validMin < 0 || o.pyramid.validMin > 65535) throw std::invalid_argument("--valid-min: 0 <= N <= 65535 expected");
     // (not FilterOutputPath: the overview file is a TIFF named after the whole file name of the image, beside it)
     const std::string path = out.empty() ? file + OIP_OVERVIEW_SUFFIX : out;
-    struct stat st;
-    if (stat(path.c_str(), &st) == 0) {
-        if (std::filesystem::equivalent(path, file)) throw std::invalid_argument("output file [" + path + "] is the input image");
-        if (!o.force) throw std::runtime_error("output file [" + path + "] exists: overviews does not replace a file without --force");
-    }
+    GuardOutput(path, {file}, "overviews", o.force);
     return path;
 }
 
@@ -753,14 +764,10 @@ inline void RunOverviews(const std::string &file, const std::string &out, const 
     stop_watch total;
     size_t bytes = 0;
     if (isTiff) {
-        int w = 0, spp = 0;
-        long h = 0;
-        DevBuf<uint16_t> img;
-        OLOG("Reading image from file `%s' ...", file.c_str());
-        read_tiff_to_device(file, &w, &h, &spp, img);
-        if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument("overviews: a TIFF of 1 or 4 samples per pixel expected");
-        write_overviews_of_device_image(outPath, img.p, w, h, spp, o.pyramid);
-        bytes = (size_t)w * h * spp * BYTES_PER_PIXEL;
+        ResidentImage m;
+        LoadTiffProduct(file, "overviews", &m);
+        write_overviews_of_device_image(outPath, m.buf.p, m.w, m.h, m.spp, o.pyramid);
+        bytes = m.bytes();
     } else {
         // level 1 is built per line block of the strip (ReadStrip), a block being an even number of lines
         const int W = o.width;
@@ -768,16 +775,13 @@ inline void RunOverviews(const std::string &file, const std::string &out, const 
         const long L = RawLineCount(file, "image", lineBytes);
         const int w1 = (W + 1) / 2;
         DevBuf<uint16_t> level1((size_t)w1 * ((L + 1) / 2));
-        long hook = BlockLinesHook("OIP_OVERVIEWS_BLOCK_LINES");
-        if (hook > 0) hook = std::max<long>(2, hook / 2 * 2);
-        ReadStrip(file, StripPlan{0, L, L, 0, StripBlockLines(lineBytes, 2, hook), lineBytes}, [&](const uint16_t *d, long r, long m) {
+        ReadStrip(file, StripPlan{0, L, L, 0, StripBlockLines(lineBytes, 2, BlockLinesHook("OIP_OVERVIEWS_BLOCK_LINES", 2)), lineBytes}, [&](const uint16_t *d, long r, long m) {
             ck(oip_halve_u16(ctx, d, W, W, m, 1, o.pyramid.validMin, level1.p + (size_t)(r / 2) * w1, w1));
         });
         write_overviews_from_device(outPath, level1, W, L, 1, o.pyramid.levels > 0 ? o.pyramid.levels : oip_overview_levels(W, L), o.pyramid.validMin);
         bytes = (size_t)L * lineBytes;
     }
-    const double es = total.tick();
-    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+    LogThroughput(bytes, total.tick());
 }
 
 // ---- oip regcheck: how well two rasters are registered ------------------------------------------------------------------
@@ -800,36 +804,24 @@ struct RegcheckOptions {
     std::string params;                     // the first line of the report
 };
 
-// everything that can be refused without a device; returns the output path
+// what is refused without a device and depends on the images (the option ranges are run_regcheck's): the containers, --bil, a
+// band index beyond the container's bands, the sizes of RAW files, the output; returns the output path
 inline std::string RegcheckCheck(const std::string &file, const std::string &out, const RegcheckOptions &o, bool *isTiff1, bool *isTiff2)
 {
     const std::string file2 = o.image2.empty() ? file : o.image2;
     *isTiff1 = RasterContainer(file, "regcheck") == ".tiff";
     *isTiff2 = RasterContainer(file2, "regcheck") == ".tiff";
     if (o.bil) throw std::invalid_argument("regcheck: a BIL RAW strip is not supported: split the bands first (the default action writes them)");
-    const int T = o.tile, S = o.search, F = o.scale;
-    if (T < OIP_MATCH_MIN_T || T > OIP_MATCH_MAX_T || T % 8 != 0) throw usage_error("--tile: a multiple of 8, 8 <= T <= 128 expected");
-    if (S < 1 || S > OIP_MATCH_MAX_S) throw usage_error("--search: 1 <= S <= 16 expected");
-    if (o.step < 0) throw usage_error("--step: N >= 1 expected");
-    if (F != 1 && F != 2 && F != 4 && F != 8 && F != 16 && F != 32 && F != 64) throw usage_error("--scale: one of 2, 4, 8, 16, 32, 64 expected");
-    if (o.validMin < 0 || o.validMax > 65535 || o.validMin > o.validMax) throw usage_error("--valid-min/--valid-max: 0 <= min <= max <= 65535 expected");
-    if (!(o.minScore >= -1.0 && o.minScore <= 1.0)) throw usage_error("--min-score: -1 <= X <= 1 expected");
     const int bands[2] = {o.band1, o.band2};
     const bool tiff[2] = {*isTiff1, *isTiff2};
     for (int k = 0; k < 2; ++k) {
         const int nb = tiff[k] ? MSS_BANDS : 1;
         if (bands[k] < 1 || bands[k] > nb) throw usage_error(std::string(k ? "--band2" : "--band1") + ": band index out of range (1.." + std::to_string(nb) + ")");
     }
-    const int W2 = o.width2 > 0 ? o.width2 : o.width;
-    if ((!*isTiff1 && o.width <= 0) || (!*isTiff2 && W2 <= 0)) throw std::invalid_argument("--width / --width2: a positive line width expected");
     if (!*isTiff1) RawLineCount(file, "image1", (size_t)o.width * BYTES_PER_PIXEL);
-    if (!*isTiff2) RawLineCount(file2, "image2", (size_t)W2 * BYTES_PER_PIXEL);
+    if (!*isTiff2) RawLineCount(file2, "image2", (size_t)(o.width2 > 0 ? o.width2 : o.width) * BYTES_PER_PIXEL);
     const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_REGCHECK_SUFFIX, ".CSV") : out;
-    struct stat st;
-    if (stat(path.c_str(), &st) == 0) {
-        if (std::filesystem::equivalent(path, file) || std::filesystem::equivalent(path, file2)) throw std::invalid_argument("output file [" + path + "] is an input image");
-        if (!o.force) throw std::runtime_error("output file [" + path + "] exists: regcheck does not replace a file without --force");
-    }
+    GuardOutput(path, {file, file2}, "regcheck", o.force);
     return path;
 }
 
@@ -841,31 +833,16 @@ inline void RunRegcheck(const std::string &file, const std::string &out, const R
     oip_ctx *ctx = Device::get().ctx();
     auto ck = [](int rc) { Device::get().check(rc); };
     stop_watch total;
-    // a resident image: TIFF of 1 or 4 samples, or single-band RAW
-    struct Image {
-        DevBuf<uint16_t> buf;
-        int w = 0, spp = 1;
-        long h = 0;
-    } img[2];
-    auto load = [&](int k, const std::string &path, int rawWidth, int band) {
-        Image &m = img[k];
-        if (isTiff[k]) {
-            OLOG("Reading image from file `%s' ...", path.c_str());
-            read_tiff_to_device(path, &m.w, &m.h, &m.spp, m.buf);
-            if (m.spp != 1 && m.spp != MSS_BANDS) throw std::invalid_argument("regcheck: a TIFF of 1 or 4 samples per pixel expected");
-            if (band > m.spp) throw usage_error(std::string(k ? "--band2" : "--band1") + ": band index out of range (1.." + std::to_string(m.spp) + ")");
-        } else {
-            m.w = rawWidth;
-            m.h = RawLineCount(path, k ? "image2" : "image1", (size_t)rawWidth * BYTES_PER_PIXEL);
-            m.buf.alloc((size_t)m.w * m.h);
-            m.buf.load_file(path, (size_t)m.w * m.h);
-        }
+    ResidentImage img[2];
+    auto bandWithin = [](const char *key, int band, const ResidentImage &m) {
+        if (band > m.spp) throw usage_error(std::string(key) + ": band index out of range (1.." + std::to_string(m.spp) + ")");
     };
-    load(0, file, o.width, o.band1);
+    LoadResident(file, isTiff[0], o.width, "image1", "regcheck", &img[0]);
+    bandWithin("--band1", o.band1, img[0]);
     const bool shared = o.image2.empty() || std::filesystem::equivalent(file, file2);          // one file: read once
-    if (!shared) load(1, file2, o.width2 > 0 ? o.width2 : o.width, o.band2);
-    else if (o.band2 > img[0].spp) throw usage_error("--band2: band index out of range (1.." + std::to_string(img[0].spp) + ")");
-    const Image &m2 = shared ? img[0] : img[1];
+    if (!shared) LoadResident(file2, isTiff[1], o.width2 > 0 ? o.width2 : o.width, "image2", "regcheck", &img[1]);
+    const ResidentImage &m2 = shared ? img[0] : img[1];
+    bandWithin("--band2", o.band2, m2);
 
     // plane A: band1 of image 1, or of its F x F box decimation (one plane per band)
     const uint16_t *A = img[0].buf.p + (o.band1 - 1);
@@ -903,11 +880,8 @@ inline void RunRegcheck(const std::string &file, const std::string &out, const R
     records.download(rec.data(), rec.size());
     ck(oip_sync(ctx));
     OLOG("Matched in %.3f seconds.", sw.tick());
-    FILE *f = fopen(outPath.c_str(), "w");
-    if (!f) throw std::runtime_error("open file [" + outPath + "] failed: " + std::to_string(errno));
     RegSummary sum;
-    const bool ok = WriteRegReport(f, o.params, rec.data(), g, o.minScore, &sum);
-    if (fclose(f) != 0 || !ok) throw std::runtime_error("write file [" + outPath + "] failed");
+    WriteTextFile(outPath, [&](FILE *f) { return WriteRegReport(f, o.params, rec.data(), g, o.minScore, &sum); });
     OLOG("regcheck: %s", RegSummaryLine(sum).c_str());
     OLOG("Report written to '%s' in %.3f seconds.", outPath.c_str(), total.tick());
 }
@@ -928,14 +902,13 @@ struct RegfixOptions {
     bool force = false;
 };
 
-// everything that can be refused without a device: the container, the report against the image's size, the bands, the output;
-// returns the output path
+// what is refused without a device and depends on the image (--smooth and --width are run_regfix's): the container, --bil, the
+// samples of a TIFF, the size of a RAW file, the report against the image's size, the bands, the output; returns the output path
 inline std::string RegfixCheck(const std::string &file, const std::string &out, const RegfixOptions &o, bool *isTiff, WarpField *field, int *bandMask)
 {
     const std::string ext = RasterContainer(file, "regfix");
     *isTiff = ext == ".tiff";
     if (o.bil) throw std::invalid_argument("regfix: a BIL RAW strip is not supported: split the bands first (the default action writes them)");
-    if (o.smooth < 0 || o.smooth > OIP_REGFIX_MAX_SMOOTH) throw usage_error("--smooth: 0 <= N <= 16 expected");
     int w = 0, spp = 1;
     long h = 0;
     if (*isTiff) {
@@ -943,7 +916,6 @@ inline std::string RegfixCheck(const std::string &file, const std::string &out, 
         read_tiff_u16(file, &w, &h, &spp, nullptr, &lay);
         if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument("regfix: a TIFF of 1 or 4 samples per pixel expected");
     } else {
-        if (o.width <= 0) throw std::invalid_argument("--width: a positive line width expected");
         w = o.width;
         h = RawLineCount(file, "image", (size_t)o.width * BYTES_PER_PIXEL);
     }
@@ -978,25 +950,13 @@ inline void RunRegfix(const std::string &file, const std::string &out, const Reg
     oip_ctx *ctx = Device::get().ctx();
     auto ck = [](int rc) { Device::get().check(rc); };
     stop_watch total;
-    size_t bytes = 0;
-    if (isTiff) {
-        bytes = FilterTiffResident(file, outPath, "regfix", "resampled", [&](const uint16_t *src, uint16_t *dst, int w, long h, int spp) {
-            ck(oip_warp_grid_bicubic_u16(ctx, src, 0, h, dst, 0, h, w, h, spp, mask, f.X.data(), f.Y.data(), f.nx, f.ny, f.gx0, f.gy0, f.sx, f.sy));
-        });
-    } else {
-        // the kernel runs per line block of the strip; the halo holds the largest vertical shift and the bicubic window
-        const int W = o.width;
-        const size_t lineBytes = (size_t)W * BYTES_PER_PIXEL;
-        const long L = RawLineCount(file, "image", lineBytes);
-        const long halo = (f.maxAbsY() + 1023) / 1024 + 3;
-        StreamStrip(file, StripPlan{0, L, L, halo, StripBlockLines(lineBytes, 1, BlockLinesHook("OIP_REGFIX_BLOCK_LINES")), lineBytes}, &outPath,
-                   [&](const uint16_t *d, long s0, long sn, uint16_t *q, long r, long m) {
-                       ck(oip_warp_grid_bicubic_u16(ctx, d, s0, sn, q, r, m, W, L, 1, 1, f.X.data(), f.Y.data(), f.nx, f.ny, f.gx0, f.gy0, f.sx, f.sy));
-                   });
-        bytes = (size_t)L * lineBytes;
-    }
-    const double es = total.tick();
-    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+    // the halo of a strip's block holds the largest vertical shift and the bicubic window; a RAW strip's band mask is 1 (RegfixCheck)
+    const size_t bytes = FilterImage(file, outPath, isTiff, o.width, (f.maxAbsY() + 1023) / 1024 + 3, "OIP_REGFIX_BLOCK_LINES", "regfix", "resampled",
+                                     [&](const uint16_t *src, long s0, long sn, uint16_t *dst, long r, long m, int w, long L, int spp) {
+                                         ck(oip_warp_grid_bicubic_u16(ctx, src, s0, sn, dst, r, m, w, L, spp, mask, f.X.data(), f.Y.data(), f.nx, f.ny,
+                                                                      f.gx0, f.gy0, f.sx, f.sy));
+                                     });
+    LogThroughput(bytes, total.tick());
 }
 
 // ---- oip pansharpen: fuse the PAN strip and the aligned MSS product -------------------------------------------------------------
@@ -1021,21 +981,18 @@ struct PansharpenGeometry {
     long Hp = 0, h = 0, outW = 0, outH = 0, mssLines = 0;
 };
 
-// everything that can be refused without a device: the containers, the sample counts, the geometry, the output; returns the
-// output path
+// what is refused without a device and depends on the images (--max-gain, --line-offset and --width are run_pansharpen's): the
+// containers, the sample counts, the size of a RAW file, the geometry, the output and its overview file; returns the output path
 inline std::string PansharpenCheck(const std::string &out, const PansharpenOptions &o, PansharpenGeometry *g)
 {
     g->panTiff = RasterContainer(o.pan, "pansharpen") == ".tiff";
     if (RasterContainer(o.mss, "pansharpen") != ".tiff") throw std::invalid_argument("pansharpen: the MSS product is a TIFF of 4 samples per pixel");
-    if (o.maxGain < 1 || o.maxGain > OIP_PANSHARPEN_MAX_GAIN) throw usage_error("--max-gain: 1 <= G <= 64 expected");
-    if (o.lineOffset < 0) throw usage_error("--line-offset: N >= 0 expected");
     int spp = 1;
     TiffLayout lay;
     if (g->panTiff) {
         read_tiff_u16(o.pan, &g->W, &g->Hp, &spp, nullptr, &lay);
         if (spp != 1) throw std::invalid_argument("pansharpen: a PAN TIFF of 1 sample per pixel expected, not " + std::to_string(spp));
     } else {
-        if (o.width <= 0) throw std::invalid_argument("--width: a positive line width expected");
         g->W = o.width;
         g->Hp = RawLineCount(o.pan, "PAN", (size_t)o.width * BYTES_PER_PIXEL);
     }
@@ -1048,12 +1005,8 @@ inline std::string PansharpenCheck(const std::string &out, const PansharpenOptio
                                     std::to_string(o.lineOffset) + " on");
     const std::string path = out.empty() ? IMO::BuildOutputFilePath(o.mss, OIP_PANSHARPEN_SUFFIX, ".TIFF") : out;
     if (to_lower(std::filesystem::path(path).extension().string()) != ".tiff") throw std::invalid_argument("pansharpen: the output is a TIFF");
-    for (const std::string &q : o.overviews ? std::vector<std::string>{path, path + OIP_OVERVIEW_SUFFIX} : std::vector<std::string>{path}) {
-        struct stat st;
-        if (stat(q.c_str(), &st) != 0) continue;
-        if (std::filesystem::equivalent(q, o.pan) || std::filesystem::equivalent(q, o.mss)) throw std::invalid_argument("output file [" + q + "] is an input image");
-        if (!o.force) throw std::runtime_error("output file [" + q + "] exists: pansharpen does not replace a file without --force");
-    }
+    GuardOutput(path, {o.pan, o.mss}, "pansharpen", o.force);
+    if (o.overviews) GuardOutput(path + OIP_OVERVIEW_SUFFIX, {o.pan, o.mss}, "pansharpen", o.force);
     return path;
 }
 
@@ -1067,22 +1020,13 @@ inline void RunPansharpen(const std::string &out, const PansharpenOptions &o)
     oip_ctx *ctx = Device::get().ctx();
     auto ck = [](int rc) { Device::get().check(rc); };
     stop_watch total;
-    DevBuf<uint16_t> pan, mss;
-    int w = 0, spp = 0;
-    long h = 0;
-    if (g.panTiff) {
-        OLOG("Reading image from file `%s' ...", o.pan.c_str());
-        read_tiff_to_device(o.pan, &w, &h, &spp, pan);
-        if (w != g.W || h != g.Hp || spp != 1) throw std::runtime_error("pansharpen: the PAN file changed while it was read");
-    } else {
-        pan.alloc((size_t)g.W * g.Hp);
-        pan.load_file(o.pan, (size_t)g.W * g.Hp);
-    }
-    OLOG("Reading image from file `%s' ...", o.mss.c_str());
-    read_tiff_to_device(o.mss, &w, &h, &spp, mss);
-    if (w != g.w || h != g.h || spp != MSS_BANDS) throw std::runtime_error("pansharpen: the MSS file changed while it was read");
+    ResidentImage pan, mss;
+    LoadResident(o.pan, g.panTiff, g.W, "PAN", "pansharpen", &pan);
+    if (pan.w != g.W || pan.h != g.Hp || pan.spp != 1) throw std::runtime_error("pansharpen: the PAN file changed while it was read");
+    LoadTiffProduct(o.mss, "pansharpen", &mss);
+    if (mss.w != g.w || mss.h != g.h || mss.spp != MSS_BANDS) throw std::runtime_error("pansharpen: the MSS file changed while it was read");
 
-    const uint16_t *p0 = pan.p + (size_t)o.lineOffset * g.W;
+    const uint16_t *p0 = pan.buf.p + (size_t)o.lineOffset * g.W;
     DevBuf<uint16_t> low((size_t)g.w * g.mssLines), res((size_t)g.outW * g.outH * MSS_BANDS);
     DevBuf<uint64_t> stats(2);
     const uint64_t none[2] = {0, 0};
@@ -1090,21 +1034,19 @@ inline void RunPansharpen(const std::string &out, const PansharpenOptions &o)
     stats.upload(none, 2);
     stop_watch sw;
     ck(oip_decimate_box_u16(ctx, p0, g.W, g.W, g.outH, 1, 4, low.p, g.w, 0));
-    ck(oip_pansharpen_sfim_u16(ctx, p0, g.W, mss.p, (long)g.w * MSS_BANDS, low.p, g.w, g.w, g.mssLines, res.p, g.outW * MSS_BANDS, 0, g.outH, o.maxGain,
+    ck(oip_pansharpen_sfim_u16(ctx, p0, g.W, mss.buf.p, (long)g.w * MSS_BANDS, low.p, g.w, g.w, g.mssLines, res.p, g.outW * MSS_BANDS, 0, g.outH, o.maxGain,
                                stats.p));
     stats.download(count, 2);
     const double px = (double)g.outW * g.outH;
     OLOG("pansharpen: fused in %.3f seconds; low-resolution PAN zero on %.4f %% of the pixels (gain 1), gain cut at %d on %.4f %%", sw.tick(),
          100.0 * count[0] / px, o.maxGain, 100.0 * count[1] / px);
-    pan.release();
-    mss.release();
+    pan.buf.release();
+    mss.buf.release();
     low.release();
     OLOG("Write fused image to file '%s' ...", outPath.c_str());
     write_tiff_from_device(outPath, res.p, (int)g.outW, g.outH, MSS_BANDS, tiff_compression(TIFF_LZW), false);
     if (o.overviews) write_overviews_of_device_image(outPath + OIP_OVERVIEW_SUFFIX, res.p, (int)g.outW, g.outH, MSS_BANDS, o.pyramid);
-    const size_t bytes = (size_t)g.outW * g.outH * MSS_BANDS * BYTES_PER_PIXEL;
-    const double es = total.tick();
-    OLOG("%zu bytes in %.3f seconds (%.1f MBps).", bytes, es, bytes / es / 1024.0 / 1024.0);
+    LogThroughput((size_t)g.outW * g.outH * MSS_BANDS * BYTES_PER_PIXEL, total.tick());
 }
 
 }  // namespace OIPGPU
