@@ -702,6 +702,80 @@ int oip_noise_fit(const double *sigma, const uint64_t *blocks, int level_shift, 
  * are finite and >= 0 and k is finite and > 0; OIP_E_RUNTIME (err says why) if st == 0, thr_rel_q8 > 256 or thr_abs > 65535. */
 int oip_noise_despike_threshold(double a, double b, double mu_ref, double k, int *thr_abs, int *thr_rel_q8, char *err, int errlen);
 
+/* ---- mtf: the MTF at Nyquist from the straight edges of a strip or product (`oip mtf`; not in the reference) --------
+ * The slanted-edge method (ISO 12233) on every 32 x 32 tile that holds one straight, high-contrast, slightly slanted edge.
+ * What `oip mtfc --mtf REPORT` takes its two numbers from.  The device part is exact integers: any launch geometry and any
+ * cut of the strip give the same bytes.  The host part is fp64, one correctly rounded operation at a time in the stated order.
+ *
+ * A tile is 32 profiles of 32 samples p[r][i].  axis 0 (x, the MTF across the lines): a profile is a piece of a line and i
+ * runs over columns; tile (ty, tx) starts at line 32 ty, column 16 tx, tx = 0 .. floor((w - 32) / 16).  axis 1 (y, along the
+ * lines): a profile is a piece of a column and i runs over lines; tile (ty, tx) starts at line 16 ty, column 32 tx.  Tiles are
+ * staggered by half a tile along the profile; the centring window lets an edge pass in at most one of two overlapping tiles.
+ * Only whole tiles exist.  Channel c of pixel i is src[i * spp + c].  Den = 32 * sum r^2 - (sum r)^2 = 87296 (r = 0..31).
+ *
+ * The record of a tile and channel is four int32 {status, s, Sc, Num}.  With
+ *   D_r = p[r][31] - p[r][0],  d[r][i] = p[r][i + 1] - p[r][i] (i = 0..30),  s = sign(sum_r D_r),  e = s * d,  S0_r = s * D_r,
+ *   TV_r = sum_i |d[r][i]|,  S1_r = sum_i (2 i + 1) * e[r][i],
+ *   c_r = (64 * S1_r) / S0_r          (integers, both non-negative: the centroid of the derivative in Q7 samples, sample i at i)
+ *   Sc = sum_r c_r,  Num = 32 * sum_r r * c_r - 496 * Sc,
+ *   f_r = floor((2 * Den * Sc + 32 * Num * (2 r - 31)) / (64 * Den))  in int64  (the least-squares line through the centroids, Q7)
+ * the tests run in this order, each over all 32 profiles; the first that fails gives the status and the other words are 0:
+ *   1 NODATA       a sample lies outside [valid_min, valid_max]
+ *   2 FLAT         sum_r D_r == 0
+ *   3 LOWCONTRAST  some S0_r < contrast_min
+ *   4 TEXTURED     some 4 * TV_r > 5 * S0_r + 4 * tv_slack, or some S1_r < 0
+ *   5 OFFCENTRE    some c_r < 1280 or c_r > 2688        (the edge 10 to 21 samples in: 8 samples covered on either side)
+ *   6 SLANT        not 4 * Den <= |Num| <= 32 * Den     (the edge crosses 1 to 8 samples over the 32 profiles)
+ *   7 CURVED       some |c_r - f_r| > 64                (half a sample off the line)
+ *   0 OK           the record holds s, Sc, Num */
+#define OIP_MTF_SUFFIX      ".MTF"   /* <stem>.MTF.CSV */
+#define OIP_MTF_NO_VALUE    16       /* oip_mtf_tile: the tile gives no value (EMPTYBIN) */
+enum { OIP_MTF_OK = 0, OIP_MTF_NODATA, OIP_MTF_FLAT, OIP_MTF_LOWCONTRAST, OIP_MTF_TEXTURED, OIP_MTF_OFFCENTRE, OIP_MTF_SLANT, OIP_MTF_CURVED };
+
+/* Pass 1: the records of every whole tile of the resident window (rows lines of w pixels of spp samples, lines `pitch` SAMPLES
+ * apart, the window inside the lines of its raster).  The record of channel c, tile (ty, tx) is at
+ * d_rec + 4 * (c * rec_plane_stride + ty * rec_pitch + tx): pitch and plane stride count records.  A strip cut into calls at
+ * multiples of 32 lines (axis 1: the next call starts 16 lines before the end of the previous one's last tile) gives the
+ * records of one call.  OIP_E_INVALID: axis not 0 or 1, spp not 1 or 4, contrast_min < 1, tv_slack outside 0..65535, a valid
+ * range that is empty or outside 0..65535, pitch < w * spp, rec_pitch below the tiles per tile line, overlapping planes.  A
+ * window smaller than one tile is a no-op.  Axis 0 at spp 1 with a pitch that is a multiple of 8 samples and a window on a
+ * 16-byte boundary reads 16 bytes at a time; everything else takes sample loads, with the same records.  Asynchronous on the
+ * context's stream. */
+int oip_mtf_tiles_u16(oip_ctx *ctx, const uint16_t *d_src, long pitch, int w, long rows, int spp, int axis, int contrast_min, int tv_slack,
+                      int valid_min, int valid_max, int32_t *d_rec, long rec_pitch, size_t rec_plane_stride);
+
+/* Pass 2: the edge-spread function (the mean profile across the edge, oversampled by 4) of n listed tiles of the same window
+ * under the same parameters.  d_list: n entries {channel, ty, tx} of int32 in HBM.  Per entry the record is recomputed from the
+ * samples; with status 0, for every r and i:
+ *   u = 128 * i - f_r,  b = (u + 1024) >> 5 (arithmetic: a floor);  0 <= b < 64:  sum[b] += p[r][i], cnt[b] += 1
+ * d_esf receives 128 uint32 per entry, the 64 sums and then the 64 counts; all zero for a tile whose status is not 0.  d_s0:
+ * NULL, or n int32 that receive sum_r S0_r (0 unless the status is 0): 32 times the contrast the report states.  The list is
+ * read back and checked before anything is launched (the call synchronises the stream): OIP_E_INVALID for an entry outside
+ * the window's channels and tiles, and for what oip_mtf_tiles_u16 refuses.  n == 0 is a no-op. */
+int oip_mtf_esf_u16(oip_ctx *ctx, const uint16_t *d_src, long pitch, int w, long rows, int spp, int axis, int contrast_min, int tv_slack,
+                    int valid_min, int valid_max, const int32_t *d_list, long n, uint32_t *d_esf, int32_t *d_s0);
+
+/* The MTF at Nyquist of one tile from its polarity s (+1 or -1) and its 64 sums and 64 counts, host, fp64 in this order:
+ *   any cnt[b] == 0:  OIP_MTF_NO_VALUE
+ *   E_b = (double)s * (double)sum[b] / (double)cnt[b]                       (the product first)
+ *   L_j = E_(j+1) - E_j,  w_j = 0.54 - 0.46 * cos(2.0 * pi * (double)j / 62.0),  t_j = w_j * L_j      j = 0..62
+ *   k = (j - 31) mod 8 in 0..7,  C8[k] = cos(pi k / 4),  S8[k] = sin(pi k / 4) from a table of the literals 0, +-1 and
+ *   +-0.70710678118654752      (Nyquist of the original sampling is 1/8 cycle per bin)
+ *   A0 = sum t_j,  Re = sum t_j * C8[k],  Im = sum t_j * S8[k], each from 0.0 in ascending j
+ *   not A0 > 0:  OIP_MTF_NO_VALUE
+ *   *mtf = hypot(Re, Im) / A0 / (q * q),  q = sin(pi / 8.0) / (pi / 8.0)     (the two-point difference and the quarter-sample bin)
+ * OIP_E_INVALID for s other than +-1 or a NULL pointer. */
+int oip_mtf_tile(int s, const uint32_t *sum, const uint32_t *cnt, double *mtf);
+
+/* median = v[(n - 1) / 2], p75 = v[3 (n - 1) / 4], p90 = v[9 (n - 1) / 10] of the n values sorted ascending (integer indices;
+ * the input is not modified).  OIP_E_INVALID for n < 1 or a value that is not finite. */
+int oip_mtf_summary(const double *values, long n, double *median, double *p75, double *p90);
+
+/* The tv_slack that lets noise of sigma_ref DN through the TEXTURED test: ceil(48 * sigma_ref), at most 65535.  The 31 noise
+ * differences of a profile have mean |.| 1.13 sigma each and sum to 35 sigma; the rest is margin.  -1 for a sigma_ref that is
+ * negative or not a number. */
+int oip_mtf_tv_slack(double sigma_ref);
+
 /* The strips of an LZW TIFF product, encoded on the device (cv::imwrite's TIFF encoder behind preproc.h:167-185 and GDAL's
  * COMPRESS=LZW PREDICTOR=2 behind imageop.h:460-567 do this on the host, strip by strip).  d_img: rows x width x spp u16,
  * interleaved, in file sample order (oip_permute_u16x4 first where cv::imwrite / a band map reorder); spp 1 or 4; strip k

@@ -24,6 +24,9 @@ from .capi import (  # noqa: F401
     match_grid,
     match_peak,
     match_summary,
+    mtf_summary,
+    mtf_tile,
+    mtf_tv_slack,
     mtfc_design3,
     mtfc_load_kernel,
     mtfc_quantise,

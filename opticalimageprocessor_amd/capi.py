@@ -140,6 +140,11 @@ _SIGS = {
     "oip_noise_levels": ([C.POINTER(C.c_uint64), C.c_uint64, _dp, C.POINTER(C.c_uint64), C.POINTER(_i)], _i),
     "oip_noise_fit": ([_dp, C.POINTER(C.c_uint64), _i, _dp, _dp, _dp, _cp, _i], _i),
     "oip_noise_despike_threshold": ([_d, _d, _d, _d, C.POINTER(_i), C.POINTER(_i), _cp, _i], _i),
+    "oip_mtf_tiles_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _i, _i, _i, _i, _vp, _l, _sz], _i),
+    "oip_mtf_esf_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp], _i),
+    "oip_mtf_tile": ([_i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _dp], _i),
+    "oip_mtf_summary": ([_dp, _l, _dp, _dp, _dp], _i),
+    "oip_mtf_tv_slack": ([_d], _i),
     "oip_halve_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _vp, _l], _i),
     "oip_overview_levels": ([_i, _l], _i),
     "oip_match_tiles_u16": ([_vp, _vp, _l, _i, _vp, _l, _i, _i, _l, _i, _i, _i, _l, _i, _l, _i, _l, _i, _i, _vp, _vp], _i),
@@ -331,6 +336,44 @@ def noise_despike_threshold(a: float, b: float, mu_ref: float, k: float = 5.0):
     if rc:
         raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
     return ta.value, q8.value
+
+
+MTF_NO_VALUE = 16
+MTF_AXES = {"x": 0, "y": 1}
+
+
+def mtf_tile(s: int, sums, cnts):
+    """the MTF at Nyquist of a tile from its polarity and its 64 edge-spread sums and counts (Context.mtf_esf_u16), or None for
+    a tile without a value (include/oip_c.h: oip_mtf_tile)"""
+    lib = load_library()
+    a = np.ascontiguousarray(sums, dtype=np.uint32).reshape(-1)
+    c = np.ascontiguousarray(cnts, dtype=np.uint32).reshape(-1)
+    assert a.size == 64 and c.size == 64, (a.size, c.size)
+    m = _d()
+    rc = lib.oip_mtf_tile(int(s), a.ctypes.data_as(C.POINTER(C.c_uint32)), c.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(m))
+    if rc == MTF_NO_VALUE:
+        return None
+    if rc:
+        raise ValueError("oip_mtf_tile: bad argument")
+    return m.value
+
+
+def mtf_summary(values):
+    """(median, p75, p90) of the tile values of a band and axis (include/oip_c.h: oip_mtf_summary)"""
+    lib = load_library()
+    v = _dbl(values).reshape(-1)
+    med, p75, p90 = _d(), _d(), _d()
+    if lib.oip_mtf_summary(v.ctypes.data_as(_dp), v.size, C.byref(med), C.byref(p75), C.byref(p90)):
+        raise ValueError("oip_mtf_summary: bad argument")
+    return med.value, p75.value, p90.value
+
+
+def mtf_tv_slack(sigma_ref: float) -> int:
+    """the --tv-slack that fits noise of sigma_ref DN (include/oip_c.h: oip_mtf_tv_slack)"""
+    t = load_library().oip_mtf_tv_slack(sigma_ref)
+    if t < 0:
+        raise ValueError("oip_mtf_tv_slack: bad argument")
+    return t
 
 
 SEAM_MODES = {"moments": 0, "gain": 1, "offset": 2}
@@ -1044,6 +1087,21 @@ class Context:
         apart) into spp planes of key lines key_pitch keys apart (include/oip_c.h: oip_noise_blocks_u16)"""
         self._ck(self.lib.oip_noise_blocks_u16(self.h, _ptr(src), pitch, w, rows, spp, block, level_shift, valid_min, valid_max, _ptr(keys),
                                                key_pitch, key_plane_stride))
+
+    # -- mtf
+    def mtf_tiles_u16(self, src, pitch, w, rows, spp, axis, rec, rec_pitch, rec_plane_stride=0, contrast_min=200, tv_slack=256, valid_min=1,
+                      valid_max=65535):
+        """the {status, s, Sc, Num} int32 record of every whole slanted-edge tile and channel of rows lines of w pixels of spp
+        samples (lines `pitch` samples apart); axis "x" / 0 or "y" / 1; pitch and plane stride of the records count records
+        (include/oip_c.h: oip_mtf_tiles_u16)"""
+        self._ck(self.lib.oip_mtf_tiles_u16(self.h, _ptr(src), pitch, w, rows, spp, MTF_AXES.get(axis, axis), contrast_min, tv_slack, valid_min,
+                                            valid_max, _ptr(rec), rec_pitch, rec_plane_stride))
+
+    def mtf_esf_u16(self, src, pitch, w, rows, spp, axis, entries, n, esf, s0=None, contrast_min=200, tv_slack=256, valid_min=1, valid_max=65535):
+        """the 64 edge-spread sums and 64 counts (uint32) of the n tiles {channel, ty, tx} (int32, on the device) of the same
+        window; s0: None or n int32 on the device for sum S0_r (include/oip_c.h: oip_mtf_esf_u16)"""
+        self._ck(self.lib.oip_mtf_esf_u16(self.h, _ptr(src), pitch, w, rows, spp, MTF_AXES.get(axis, axis), contrast_min, tv_slack, valid_min,
+                                          valid_max, _ptr(entries), n, _ptr(esf), _ptr(s0)))
 
     # -- instrumentation
     def merge_subimages_be16(self, tiles, out, vparts, hparts, sub_lines, sub_cols):

@@ -3,7 +3,8 @@
 // block of lines, and the per-line tables), the shift
 // filtering / polynomial fit, the contrast stretch of `oip quicklook` (percentile limits, 8-bit table, 8-bit TIFF) and the
 // taps of `oip mtfc` (design, quantisation, kernel file), the column lists and column table of `oip despike`, the field of
-// `oip regfix` (report, fill, smoothing: oip_warpfield.hpp) and the geometry rule of `oip pansharpen`.
+// `oip regfix` (report, fill, smoothing: oip_warpfield.hpp), the geometry rule of `oip pansharpen`, the noise model of `oip noise`
+// and the tile value, order statistics and slack of `oip mtf`.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -1084,4 +1085,52 @@ extern "C" int oip_noise_despike_threshold(double a, double b, double mu_ref, do
     *thr_abs = (int)ta;
     *thr_rel_q8 = (int)q8;
     return OIP_OK;
+}
+
+// ---- oip mtf, host side: the MTF at Nyquist of a tile from its edge-spread sums, the order statistics of a band, and the slack
+// that follows from a noise level (include/oip_c.h states the operation order, tests/_mtf_ref.py restates it) ---------------
+extern "C" int oip_mtf_tile(int s, const uint32_t *sum, const uint32_t *cnt, double *mtf)
+{
+    if ((s != 1 && s != -1) || !sum || !cnt || !mtf) return OIP_E_INVALID;
+    static const double H = 0.70710678118654752;
+    static const double C8[8] = {1.0, H, 0.0, -H, -1.0, -H, 0.0, H}, S8[8] = {0.0, H, 1.0, H, 0.0, -H, -1.0, -H};
+    const double pi = 3.14159265358979323846;
+    double E[64];
+    for (int b = 0; b < 64; ++b) {
+        if (cnt[b] == 0) return OIP_MTF_NO_VALUE;
+        E[b] = (double)s * (double)sum[b] / (double)cnt[b];
+    }
+    double A0 = 0.0, Re = 0.0, Im = 0.0;
+    for (int j = 0; j < 63; ++j) {
+        const double w = 0.54 - 0.46 * std::cos(2.0 * pi * (double)j / 62.0);
+        const double t = w * (E[j + 1] - E[j]);
+        const int k = (j - 31) & 7;
+        A0 += t;
+        Re += t * C8[k];
+        Im += t * S8[k];
+    }
+    if (!(A0 > 0.0)) return OIP_MTF_NO_VALUE;
+    const double q = std::sin(pi / 8.0) / (pi / 8.0);
+    *mtf = std::hypot(Re, Im) / A0 / (q * q);
+    return OIP_OK;
+}
+
+extern "C" int oip_mtf_summary(const double *values, long n, double *median, double *p75, double *p90)
+{
+    if (!values || n < 1 || !median || !p75 || !p90) return OIP_E_INVALID;
+    for (long i = 0; i < n; ++i)
+        if (!std::isfinite(values[i])) return OIP_E_INVALID;
+    std::vector<double> v(values, values + n);
+    std::sort(v.begin(), v.end());
+    *median = v[(size_t)((n - 1) / 2)];
+    *p75 = v[(size_t)(3 * (n - 1) / 4)];
+    *p90 = v[(size_t)(9 * (n - 1) / 10)];
+    return OIP_OK;
+}
+
+extern "C" int oip_mtf_tv_slack(double sigma_ref)
+{
+    if (!(sigma_ref >= 0.0)) return -1;
+    const double t = std::ceil(48.0 * sigma_ref);
+    return t < 65535.0 ? (int)t : 65535;
 }

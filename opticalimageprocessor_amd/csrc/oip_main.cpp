@@ -17,6 +17,9 @@
 //                               --noise REPORT [--k-sigma K] takes the threshold from the report of `oip noise`
 //   oip noise IMAGE [-o OUT.csv] [--block 8|16] [--bits N] [--min-blocks N] [--bil]   the noise-level function of a strip or
 //                               product (sigma per signal level, the fit sigma^2 = a + b mu, SNR) in <stem>.NOISE.CSV, see run_noise()
+//   oip mtf IMAGE [-o OUT.csv] [--axis x|y|both] [--contrast-min DN] [--tv-slack DN | --noise REPORT]   the MTF at Nyquist across
+//                               and along the lines from the slanted edges of a strip or product, in <stem>.MTF.CSV, see run_mtf();
+//                               `mtfc --mtf REPORT [--mtf-stat median|p75|p90]` designs its filter from the report
 //   oip overviews IMAGE [-o OUT] [--levels N] [--valid-min N]   the reduced-resolution pyramid of a strip or product as
 //                               <IMAGE>.ovr beside it; `stitch --overviews [--levels N]` writes its product's, see run_overviews()
 //   oip regcheck --image1 A [--image2 B] [--band1 k] [--band2 k] [--scale F] [--shift-x N] [--shift-y N] [--tile T] [--search S]
@@ -33,7 +36,7 @@
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
 // --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
-// despike, noise, overviews, regcheck, regfix and pansharpen sub-commands.
+// despike, noise, mtf, overviews, regcheck, regfix and pansharpen sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -136,7 +139,7 @@ Parsed parse(const Spec &sp, const std::vector<std::string> &args)
     return p;
 }
 
-// The tools with one positional argument (quicklook, mtfc, despike, noise, overviews; regcheck, regfix and pansharpen name their
+// The tools with one positional argument (quicklook, mtfc, despike, noise, mtf, overviews; regcheck, regfix and pansharpen name their
 // images by options): IMAGE, an existing regular file, is the first argument that is neither an option nor the value of one (an
 // option's value stays with it, alias or not); the rest is parsed as usual.
 Parsed parse_with_image(const Spec &sp, const std::vector<std::string> &args, std::string *image)
@@ -221,6 +224,8 @@ void usage()
          "             the container of the input and is written to <stem>.MTFC.<ext> in the working directory:\n"
          "             [-o,--out FILE] --kernel FILE (text: `ky kx', then ky rows of kx coefficients summing to 1)\n"
          "             | --mtf-x M --mtf-y M (the MTF at Nyquist across / along the lines, 0 < M <= 1) [--max-gain G] (default 2.0)\n"
+         "             | --mtf REPORT (the report of `oip mtf`: M of either axis from its `# all' lines) [--mtf-stat median|p75|p90]\n"
+         "             (default median; p75 / p90 where soft natural edges pull the median down)\n"
          "             [--valid-min N] (samples below are no data and pass through; default 1) [--width N] [--force]\n"
          "  despike    IMAGE.RAW|IMAGE.TIFF: repair of a raw strip ahead of RRC; the output has the container of the input and is\n"
          "             written to <stem>.DSPK.<ext> in the working directory.  At least one of --threshold, --noise and --bad-columns:\n"
@@ -240,6 +245,14 @@ void usage()
          "             [--valid-min N] [--valid-max N] (a block with a sample outside is no data; default 1, 65535)\n"
          "             [--min-blocks N] (blocks a level needs; default 100) [--bil] (RAW: the MSS line layout, bands measured apart)\n"
          "             [--width N] [--line-offset N] (a multiple of the block) [--lines N] [--force]\n"
+         "  mtf        IMAGE.RAW|IMAGE.TIFF: the MTF at Nyquist across (x) and along (y) the lines, measured on the image itself by the\n"
+         "             slanted-edge method: every 32 x 32 tile with one straight edge of at least --contrast-min DN that crosses 1 to 8\n"
+         "             samples gives a value; band,axis,ty,tx,polarity,slope_q,contrast,mtf per tile and count, median, p75 and p90 per\n"
+         "             band and axis are written to <stem>.MTF.CSV in the working directory, which `mtfc --mtf` reads:\n"
+         "             [-o,--out FILE] [--axis x|y|both] (default both) [--contrast-min DN] (1..65535; default 200)\n"
+         "             [--tv-slack DN] (0..65535; what a profile may vary beyond its edge; default 256) | [--noise REPORT] (48 times\n"
+         "             the sigma_ref of each band of a report of `oip noise`) [--valid-min N] [--valid-max N] (a tile with a sample\n"
+         "             outside is no data; default 1, 65535) [--width N] [--line-offset N] [--lines N] [--force]\n"
          "  overviews  IMAGE.RAW|IMAGE.TIFF: the reduced-resolution pyramid of a strip or product, every band at 16 bits, each level\n"
          "             the 2 x 2 average of the one before; written to IMAGE.ovr beside the image, where GDAL-based viewers look for it:\n"
          "             [-o,--out FILE] [--levels N] (1..16; default: until a level fits 256 x 256) [--valid-min N] (samples below are\n"
@@ -643,21 +656,36 @@ int run_quicklook(const std::vector<std::string> &args, int width)
 int run_mtfc(const std::vector<std::string> &args, int width)
 {
     Spec sp;
-    sp.valued = {"--out", "--kernel", "--mtf-x", "--mtf-y", "--max-gain", "--valid-min", "--width"};
+    sp.valued = {"--out", "--kernel", "--mtf-x", "--mtf-y", "--max-gain", "--valid-min", "--width", "--mtf", "--mtf-stat"};
     sp.flags = {"--force"};
     sp.alias = {{"-o", "--out"}};
     std::string image;
     Parsed p = parse_with_image(sp, args, &image);
-    const bool design = p.has("--mtf-x") || p.has("--mtf-y") || p.has("--max-gain");
+    // --mtf REPORT stands in for --mtf-x / --mtf-y: the two numbers come from the report of `oip mtf`
+    if (p.has("--mtf") && (p.has("--kernel") || p.has("--mtf-x") || p.has("--mtf-y"))) throw cli_error(107, "--mtf excludes --kernel and --mtf-x/--mtf-y");
+    if (p.has("--mtf-stat") && !p.has("--mtf")) throw cli_error(107, "--mtf-stat requires --mtf");
+    const std::string stat = p.str("--mtf-stat", "median");
+    if (stat != "median" && stat != "p75" && stat != "p90") throw cli_error(105, "--mtf-stat: median, p75 or p90 expected");
+    const bool design = p.has("--mtf-x") || p.has("--mtf-y") || p.has("--max-gain") || p.has("--mtf");
     if (p.has("--kernel") && design) throw usage_error("--kernel and --mtf-x/--mtf-y/--max-gain exclude each other");
     if (!p.has("--kernel") && !design) throw usage_error("--kernel FILE or --mtf-x M --mtf-y M expected");
     MtfcOptions o;
     o.width = p.integer("--width", width);
     if (design) {
-        require(p, "--mtf-x");
-        require(p, "--mtf-y");
-        o.mtfX = p.real("--mtf-x", 0.0);
-        o.mtfY = p.real("--mtf-y", 0.0);
+        if (p.has("--mtf")) {
+            existing_file(p, "--mtf");
+            MtfAxisSummary s[2];
+            std::string err;
+            if (!ParseMtfReport(p.str("--mtf"), s, &err)) throw std::runtime_error(err);
+            if (!MtfcValueOf(s[0], 0, stat, &o.mtfX, &err) || !MtfcValueOf(s[1], 1, stat, &o.mtfY, &err))
+                throw cli_error(105, "--mtf: MTF report [" + p.str("--mtf") + "]: " + err);
+            OLOG("mtfc: %s of the MTF report [%s]: mtf-x %.17g, mtf-y %.17g", stat.c_str(), p.str("--mtf").c_str(), o.mtfX, o.mtfY);
+        } else {
+            require(p, "--mtf-x");
+            require(p, "--mtf-y");
+            o.mtfX = p.real("--mtf-x", 0.0);
+            o.mtfY = p.real("--mtf-y", 0.0);
+        }
         o.maxGain = p.real("--max-gain", OIP_MTFC_DEF_MAXGAIN);
         if (!(o.mtfX > 0.0 && o.mtfX <= 1.0) || !(o.mtfY > 0.0 && o.mtfY <= 1.0)) throw cli_error(105, "--mtf-x/--mtf-y: 0 < M <= 1 expected");
         if (!(o.maxGain >= 1.0)) throw cli_error(105, "--max-gain: G >= 1 expected");
@@ -737,6 +765,38 @@ int run_noise(const std::vector<std::string> &args, int width)
              o.validMax, o.minBlocks, o.bil ? 1 : 0, o.lineOffset, o.lines);
     o.params = "oip noise image=" + image + buf + " columns=band,level_lo,level_hi,blocks,sigma,snr";
     RunNoise(image, p.str("--out"), o);
+    return 0;
+}
+
+// oip mtf IMAGE: the MTF at Nyquist of a strip (.RAW, --width samples per line) or a product (.TIFF of 1 or 4 samples) from its
+// slanted edges, as <stem>.MTF.CSV (RunMtf).  IMAGE is the one positional argument, as for mtfc.  Bad values end in 105 before
+// any file is read.
+int run_mtf(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--out", "--axis", "--contrast-min", "--tv-slack", "--noise", "--valid-min", "--valid-max", "--width", "--line-offset", "--lines"};
+    sp.flags = {"--force"};
+    sp.alias = {{"-o", "--out"}};
+    std::string image;
+    Parsed p = parse_with_image(sp, args, &image);
+    if (p.has("--noise") && p.has("--tv-slack")) throw cli_error(107, "--noise excludes --tv-slack");
+    MtfOptions o;
+    o.width = p.integer("--width", width);
+    const std::string axis = p.str("--axis", "both");
+    if (axis != "x" && axis != "y" && axis != "both") throw cli_error(105, "--axis: x, y or both expected");
+    o.axes = axis == "x" ? 1 : axis == "y" ? 2 : 3;
+    o.contrastMin = p.within("--contrast-min", 200, 1, 65535, "1 <= DN <= 65535 expected");
+    o.tvSlack = p.within("--tv-slack", 256, 0, 65535, "0 <= DN <= 65535 expected");
+    p.valid_range(1, &o.validMin, &o.validMax);
+    p.line_range(&o.lineOffset, &o.lines);
+    o.force = p.has("--force");
+    existing_file(p, "--noise");
+    o.noiseReport = p.str("--noise");
+    char buf[256];
+    snprintf(buf, sizeof buf, " axis=%s contrast-min=%d tv-slack=%s valid-min=%d valid-max=%d line-offset=%ld lines=%ld", axis.c_str(), o.contrastMin,
+             p.has("--noise") ? "noise" : std::to_string(o.tvSlack).c_str(), o.validMin, o.validMax, o.lineOffset, o.lines);
+    o.params = "oip mtf image=" + image + buf + " columns=band,axis,ty,tx,polarity,slope_q,contrast,mtf";
+    RunMtf(image, p.str("--out"), o);
     return 0;
 }
 
@@ -923,6 +983,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "mtfc") return run_mtfc({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "despike") return run_despike({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "noise") return run_noise({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "mtf") return run_mtf({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "overviews") return run_overviews({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regcheck") return run_regcheck({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regfix") return run_regfix({args.begin() + 1, args.end()}, width);

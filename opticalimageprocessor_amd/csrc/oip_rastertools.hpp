@@ -1,4 +1,4 @@
-// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, noise, overviews,
+// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, noise, mtf, overviews,
 // regcheck, regfix, pansharpen) above the host layer of oip_host.hpp.  Stated once for all of them: the file checks made before a
 // device is touched (container, RAW size rule, line range, GuardOutput), the loaders of a resident image, the driver that streams
 // a RAW strip through the device in line blocks (geometry: oip_stripplan.hpp), the filter driver above it, the closing
@@ -9,6 +9,7 @@
 #pragma once
 
 #include "oip_host.hpp"
+#include "oip_mtfreport.hpp"
 #include "oip_noisereport.hpp"
 #include "oip_regreport.hpp"
 #include "oip_stripplan.hpp"
@@ -72,7 +73,7 @@ inline std::string FilterOutputPath(const std::string &file, const std::string &
     return path;
 }
 
-// OIP_<TOOL>_BLOCK_LINES of mtfc, despike, noise, overviews and regfix (test hooks: several blocks on a small image), rounded
+// OIP_<TOOL>_BLOCK_LINES of mtfc, despike, noise, mtf, overviews and regfix (test hooks: several blocks on a small image), rounded
 // down to the multiple q of lines the tool needs and never below q; 0 without one
 inline long BlockLinesHook(const char *name, long q = 1)
 {
@@ -724,6 +725,162 @@ inline void RunNoise(const std::string &file, const std::string &out, const Nois
     }
     WriteTextFile(outPath, [&](FILE *f) { return WriteNoiseReport(f, o.params, bands, shift); });
     for (int b = 0; b < nb; ++b) OLOG("noise: %s", NoiseBandLine(b + 1, bands[b]).c_str());
+    const double es = total.tick();
+    OLOG("Report written to '%s'; %zu bytes in %.3f seconds (%.1f MBps).", outPath.c_str(), inBytes, es, inBytes / es / 1024.0 / 1024.0);
+}
+
+// ---- oip mtf: the MTF at Nyquist from the edges of a strip or product -------------------------------------------------------
+// The measuring side of mtfc's --mtf-x / --mtf-y.  Per line block, axis and band: every 32 x 32 tile gets a record
+// (oip_mtf_tiles_u16), the status-0 tiles are listed in (channel, ty, tx) order and binned into edge-spread functions
+// (oip_mtf_esf_u16), and oip_mtf_tile turns each into a value.  Rows, status counts and order statistics go to <stem>.MTF.CSV
+// (oip_mtfreport.hpp).  Tiles are anchored at the first line of the range; a RAW strip streams through in blocks that are
+// multiples of 32 lines with 32 halo lines, of which the y tiles that start in a block read up to 16 below it, so the report
+// does not depend on the block size; a TIFF product is resident.  Not in the reference.
+struct MtfOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    int axes = 3;                           // bit 0: x (across the lines), bit 1: y (along the lines)
+    int contrastMin = 200, tvSlack = 256;
+    std::string noiseReport;                // --noise: tv_slack per band from the sigma_ref of a report of `oip noise`
+    int validMin = 1, validMax = 65535;
+    long lineOffset = 0, lines = 0;         // lines == 0: to the end of the image
+    bool force = false;
+    std::string params;                     // the first line of the report
+};
+
+// what is refused without a device and depends on the image (the option ranges are run_mtf's): the container, the size and line
+// range of a RAW file, an image without a tile, the noise report, the output; returns the output path and whether the input is
+// a TIFF, and in *slack the slack of every band of a --noise report (empty without one)
+inline std::string MtfCheck(const std::string &file, const std::string &out, const MtfOptions &o, bool *isTiff, std::vector<int> *slack)
+{
+    *isTiff = RasterContainer(file, "mtf") == ".tiff";
+    if (!*isTiff) {
+        if (o.width <= 0) throw std::invalid_argument("--width: a positive line width expected");
+        long first = 0, n = 0;
+        RawLineRange(file, "image", o.width, o.lineOffset, o.lines, &first, &n);
+        if (n < 32 || o.width < 32) throw std::invalid_argument("mtf: the image holds no tile of 32 x 32");
+    }
+    slack->clear();
+    if (!o.noiseReport.empty()) {
+        std::vector<NoiseModel> models;
+        std::string err;
+        if (!ParseNoiseReport(o.noiseReport, &models, &err)) throw std::runtime_error(err);
+        for (const NoiseModel &m : models) slack->push_back(oip_mtf_tv_slack(std::sqrt(m.a + m.b * m.muRef)));
+    }
+    const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_MTF_SUFFIX, ".CSV") : out;
+    GuardOutput(path, {file}, "mtf", o.force);
+    return path;
+}
+
+inline void RunMtf(const std::string &file, const std::string &out, const MtfOptions &o)
+{
+    bool isTiff = false;
+    std::vector<int> noiseSlack;
+    const std::string outPath = MtfCheck(file, out, o, &isTiff, &noiseSlack);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    std::vector<MtfRow> rows;
+    std::vector<std::vector<MtfGroup>> groups;                          // [band][axis]
+    DevBuf<int32_t> rec, list, s0;
+    DevBuf<uint32_t> esf;
+    std::vector<int32_t> hrec, hlist, hs0;
+    std::vector<uint32_t> hesf;
+    auto slack_of = [&](int band) {                                     // band: 0-based
+        if (noiseSlack.empty()) return o.tvSlack;
+        if ((size_t)band >= noiseSlack.size())
+            throw std::runtime_error("noise report [" + o.noiseReport + "] holds " + std::to_string(noiseSlack.size()) + " band(s), the image more");
+        return noiseSlack[band];
+    };
+    // the tiles that START in lines [a, a + m) of the n-line range, of which `src` holds line a first and at least 16 lines
+    // past a + m where the range has them
+    auto block = [&](const uint16_t *src, long pitch, int w, int spp, long a, long m, long n) {
+        if ((int)groups.size() < spp) groups.resize(spp, std::vector<MtfGroup>(2));
+        for (int axis = 0; axis < 2; ++axis) {
+            if (!(o.axes >> axis & 1)) continue;
+            const long step = axis == 0 ? 32 : 16;
+            const long ty0 = a / step, tyEnd = std::min((a + m + step - 1) / step, n >= 32 ? (n - 32) / step + 1 : 0);
+            const long nty = tyEnd - ty0, ntx = axis == 0 ? (w - 32) / 16 + 1 : w / 32;
+            if (nty < 1 || ntx < 1) continue;
+            const long rowsIn = step * (nty - 1) + 32;
+            const size_t plane = (size_t)nty * ntx;
+            if (rec.n < plane * spp * 4) rec.alloc(plane * spp * 4);
+            hrec.resize(plane * spp * 4);
+            int slackDone = -1;                                         // the slack the records on the host were made with
+            for (int c = 0; c < spp; ++c) {
+                const int slack = slack_of(c);
+                if (slack != slackDone) {                               // (only bands of a --noise report differ)
+                    ck(oip_mtf_tiles_u16(ctx, src, pitch, w, rowsIn, spp, axis, o.contrastMin, slack, o.validMin, o.validMax, rec.p, ntx, plane));
+                    rec.download(hrec.data(), plane * spp * 4);
+                    slackDone = slack;
+                }
+                const int32_t *crec = &hrec[(size_t)c * plane * 4];
+                hlist.clear();
+                MtfGroup &g = groups[c][axis];
+                for (long ty = 0; ty < nty; ++ty)
+                    for (long tx = 0; tx < ntx; ++tx) {
+                        const int32_t *r = &crec[((size_t)ty * ntx + tx) * 4];
+                        ++g.tiles;
+                        ++g.status[r[0] & 7];
+                        if (r[0] == OIP_MTF_OK) { hlist.push_back(c); hlist.push_back((int32_t)ty); hlist.push_back((int32_t)tx); }
+                    }
+                const size_t k = hlist.size() / 3;
+                if (k == 0) continue;
+                if (list.n < k * 3) { list.alloc(k * 3); esf.alloc(k * 128); s0.alloc(k); }
+                list.upload(hlist.data(), k * 3);
+                ck(oip_mtf_esf_u16(ctx, src, pitch, w, rowsIn, spp, axis, o.contrastMin, slack, o.validMin, o.validMax, list.p, (long)k, esf.p, s0.p));
+                hesf.resize(k * 128);
+                hs0.resize(k);
+                esf.download(hesf.data(), k * 128);
+                s0.download(hs0.data(), k);
+                for (size_t i = 0; i < k; ++i) {
+                    const int32_t *r = &crec[((size_t)hlist[3 * i + 1] * ntx + hlist[3 * i + 2]) * 4];
+                    MtfRow row;
+                    const int rc = oip_mtf_tile(r[1], &hesf[i * 128], &hesf[i * 128 + 64], &row.mtf);
+                    if (rc == OIP_MTF_NO_VALUE) { ++g.emptybin; continue; }
+                    if (rc != OIP_OK) throw std::runtime_error("oip_mtf_tile: bad argument");
+                    row.band = c + 1; row.axis = axis; row.ty = ty0 + hlist[3 * i + 1]; row.tx = hlist[3 * i + 2];
+                    row.polarity = r[1]; row.slopeQ = r[3]; row.sumS0 = hs0[i];
+                    rows.push_back(row);
+                    g.values.push_back(row.mtf);
+                }
+            }
+        }
+    };
+    size_t inBytes = 0;
+    long first = 0, nLines = 0;
+    if (isTiff) {
+        ResidentImage m;
+        LoadTiffProduct(file, "mtf", &m);
+        LineRange("image", m.h, o.lineOffset, o.lines, &first, &nLines);
+        if (nLines < 32 || m.w < 32) throw std::invalid_argument("mtf: the image holds no tile of 32 x 32");
+        const long bl = BlockLinesHook("OIP_MTF_BLOCK_LINES", 32);
+        for (long a = 0; a < nLines; a += bl > 0 ? bl : nLines)
+            block(m.buf.p + (size_t)(first + a) * m.w * m.spp, (long)m.w * m.spp, m.w, m.spp, a, std::min(bl > 0 ? bl : nLines, nLines - a), nLines);
+        inBytes = (size_t)nLines * m.w * m.spp * BYTES_PER_PIXEL;
+    } else {
+        const long fileLines = RawLineRange(file, "image", o.width, o.lineOffset, o.lines, &first, &nLines);
+        const size_t lineBytes = (size_t)o.width * BYTES_PER_PIXEL;
+        StreamStrip(file, StripPlan{first, nLines, fileLines, 32, StripBlockLines(lineBytes, 32, BlockLinesHook("OIP_MTF_BLOCK_LINES", 32)), lineBytes}, nullptr,
+                    [&](const uint16_t *d, long s0Line, long, uint16_t *, long r, long m) {
+                        block(d + (size_t)(r - s0Line) * o.width, o.width, o.width, 1, r - first, m, nLines);
+                    });
+        inBytes = (size_t)nLines * lineBytes;
+    }
+    ck(oip_sync(ctx));
+    for (int a = 0; a < 2; ++a) {
+        if (!(o.axes >> a & 1)) continue;
+        size_t values = 0;
+        for (const auto &g : groups) values += g[a].values.size();
+        if (values == 0) {
+            MtfGroup all;
+            for (const auto &g : groups) all.add(g[a]);
+            throw std::runtime_error("mtf: no tile with a value on axis " + std::string(MtfAxisName(a)) + " (" + MtfGroupLine("all", a, all) + ")");
+        }
+    }
+    WriteTextFile(outPath, [&](FILE *f) { return WriteMtfReport(f, o.params, rows, groups, o.axes); });
+    for (size_t b = 0; b < groups.size(); ++b)
+        for (int a = 0; a < 2; ++a)
+            if (o.axes >> a & 1) OLOG("mtf: %s", MtfGroupLine("band " + std::to_string(b + 1), a, groups[b][a]).c_str());
     const double es = total.tick();
     OLOG("Report written to '%s'; %zu bytes in %.3f seconds (%.1f MBps).", outPath.c_str(), inBytes, es, inBytes / es / 1024.0 / 1024.0);
 }

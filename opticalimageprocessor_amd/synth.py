@@ -134,3 +134,37 @@ def ccd_pair(row0: int, rows: int, W: int, overlap: int, kb1: np.ndarray, kb2: n
         x2 = pad + W - overlap - sx
         p2[y:y + m] = _raw_u16(sc[pad - sy:pad - sy + m, x2:x2 + W], kb2)
     return p1, p2
+
+
+def edge_field(rows: int, cols: int, seed: int = 0, device="cuda", block=(512, 2048), sigma: float = 0.5, noise: float = 3.0) -> torch.Tensor:
+    """(rows, cols) u16 raster for the `oip mtf` kernels: one block of 32 x 32 cells repeated over the raster -- in turn an edge
+    blurred by a Gaussian of `sigma` samples that crosses 1.5 to 6 columns of its cell (measured by axis x), the same transposed
+    (axis y), a flat patch and 12-bit texture, every cell with noise of `noise` DN."""
+    rng = np.random.default_rng(seed)
+    bh, bw = block
+    erf = np.vectorize(math.erf, otypes=[float])
+    r, i = np.meshgrid(np.arange(32.0), np.arange(32.0), indexing="ij")
+    blk = np.empty((bh, bw))
+    k = 0
+    for j in range(0, bh, 32):
+        for c in range(0, bw, 32):
+            kind = k % 4
+            k += 1
+            if kind == 2:
+                cell = np.full((32, 32), rng.uniform(300.0, 3500.0))
+            elif kind == 3:
+                cell = rng.uniform(1.0, 4095.0, (32, 32))
+            else:
+                x0 = 15.5 + rng.uniform(-2.0, 2.0) + rng.uniform(1.5, 6.0) * rng.choice((-1.0, 1.0)) * (r - 15.5) / 32.0
+                e = 0.5 * (1.0 + erf((i - x0) / (sigma * math.sqrt(2.0))))
+                cell = 1000.0 + 2000.0 * (e if rng.random() < 0.5 else 1.0 - e)
+                cell = cell.T if kind == 1 else cell
+            blk[j:j + 32, c:c + 32] = cell + rng.normal(0.0, noise, (32, 32))
+    t = torch.from_numpy(np.clip(np.rint(blk), 1, 65535).astype(np.int32)).to(device).to(torch.int16).view(torch.uint16)
+    out = torch.empty(rows, cols, dtype=torch.uint16, device=device)
+    for j in range(0, rows, bh):
+        m = min(bh, rows - j)
+        for c in range(0, cols, bw):
+            n = min(bw, cols - c)
+            out[j:j + m, c:c + n] = t[:m, :n]
+    return out
