@@ -702,6 +702,49 @@ int oip_noise_fit(const double *sigma, const uint64_t *blocks, int level_shift, 
  * are finite and >= 0 and k is finite and > 0; OIP_E_RUNTIME (err says why) if st == 0, thr_rel_q8 > 256 or thr_abs > 65535. */
 int oip_noise_despike_threshold(double a, double b, double mu_ref, double k, int *thr_abs, int *thr_rel_q8, char *err, int errlen);
 
+/* ---- denoise: a sigma filter driven by the noise model (`oip denoise`; not in the reference) ------------------------
+ * The acting partner of `oip noise` for the noise itself: Lee's sigma filter with a pilot estimate, an edge-preserving
+ * smoother whose strength at every signal level comes from the measured sigma^2 = a + b * level.  It runs behind the
+ * radiometric correction and ahead of `oip mtfc`, which amplifies what noise is left.  Specified in exact integers: any
+ * evaluation order gives the same bytes. */
+#define OIP_DENOISE_SUFFIX     ".DNS"   /* <stem>.DNS.<ext>, built like the reference's other product names (imageop.h:99-108) */
+
+/* Raster and window conventions are oip_convolve_u16's: W pixels x L lines of spp samples (1, or 4 pixel-interleaved); d_src
+ * holds global lines [src_row0, src_row0 + src_rows), d_dst receives [out_row0, out_row0 + out_rows), the first at d_dst; a
+ * strip cut into calls gives the bytes of one call.  The border is replicated: s(v, u) = src[clamp(v, 0, L-1)][clamp(u, 0,
+ * W-1)][ch], the channel kept.  radius r is 1, 2 or 3.  d_thr: spp * 256 uint16 in HBM, thr[ch][level]: the half width of the
+ * range around a value of level (value >> 8).  For output line y, pixel x, channel ch, c = s(y, x), all in integers:
+ *   c < valid_min:   out = c                                             no data passes through
+ *   T0 = thr[ch][c >> 8],    lo0 = max(c - T0, valid_min),   hi0 = min(c + T0, 65535)
+ *   stage 1, the pilot: over the 3 x 3 neighbours n = s(y + j, x + i), |j|, |i| <= 1:
+ *                    S1 = sum and m1 = count of the n with lo0 <= n <= hi0           (m1 >= 1: the centre)
+ *                    c1 = (2 * S1 + m1) / (2 * m1)                       integer division: the mean, half up
+ *   T1 = thr[ch][c1 >> 8],   lo = max(c1 - T1, valid_min),   hi = min(c1 + T1, 65535)
+ *   stage 2: over the (2r+1) x (2r+1) neighbours: S = sum and m = count of the n with lo <= n <= hi
+ *   m < min_members: out = c;   otherwise out = (2 * S + m) / (2 * m)
+ * A neighbour below valid_min is never a member (lo >= valid_min).  2 * S + m <= 2 * 49 * 65535 + 49 < 2^24.  It follows that
+ * |c1 - c| <= T0, that |out - c1| <= T1 wherever m >= min_members, and that a sample further than T0 from all its neighbours
+ * has c1 = c and m = 1: with min_members > 1 an impulse stays as it is (impulses are oip_despike_u16's business).
+ * d_stats: NULL, or 4 uint64 in HBM that are ADDED into, over the output samples; the caller zeroes them (oip_memset):
+ *   [0] samples with c >= valid_min   [1] of those, the samples left alone because m < min_members
+ *   [2] sum of m over the filtered samples   [3] samples with out != c
+ * The counters are exact and do not depend on the launch geometry or on how the strip is cut.
+ * OIP_E_INVALID: radius outside 1..3, min_members outside 1..(2r+1)^2, valid_min outside 0..65535, spp other than 1 or 4, W < 1,
+ * L < 1, output lines outside [0, L), a needed source line clamp(out_row0 - r, 0, L-1) .. clamp(out_row0 + out_rows - 1 + r,
+ * 0, L-1) that is not resident, d_dst == d_src (the call is not in place).  out_rows == 0 is a no-op.  A line that is not a
+ * multiple of 8 samples, or bases that are not 16-byte aligned, take a slower kernel with the same result.  Asynchronous on
+ * the context's stream. */
+int oip_sigma_filter_u16(oip_ctx *ctx, const uint16_t *d_src, long src_row0, long src_rows, uint16_t *d_dst, long out_row0,
+                         long out_rows, int W, long L, int spp, int radius, const uint16_t *d_thr, int min_members, int valid_min,
+                         uint64_t *d_stats);
+
+/* The threshold table of one band from its noise model, host, no context needed.  fp64, per level l = 0..255, one correctly
+ * rounded operation at a time in this order:
+ *   thr256[l] = min(65535, ceil(k * sqrt(a + b * (256 * l + 128))))      k sigma at the middle of the level
+ * OIP_E_INVALID unless a, b are finite and >= 0 and k is finite and > 0; OIP_E_RUNTIME (err says so) for a = b = 0, a model
+ * without noise. */
+int oip_denoise_thresholds(double a, double b, double k, uint16_t *thr256, char *err, int errlen);
+
 /* ---- mtf: the MTF at Nyquist from the straight edges of a strip or product (`oip mtf`; not in the reference) --------
  * The slanted-edge method (ISO 12233) on every 32 x 32 tile that holds one straight, high-contrast, slightly slanted edge.
  * What `oip mtfc --mtf REPORT` takes its two numbers from.  The device part is exact integers: any launch geometry and any

@@ -15,6 +15,7 @@ from .capi import (  # noqa: F401
     STATUS_NAMES,
     build,
     declared_symbols,
+    denoise_thresholds,
     despike_column_table,
     filter_and_fit,
     library_path,

@@ -140,6 +140,8 @@ _SIGS = {
     "oip_noise_levels": ([C.POINTER(C.c_uint64), C.c_uint64, _dp, C.POINTER(C.c_uint64), C.POINTER(_i)], _i),
     "oip_noise_fit": ([_dp, C.POINTER(C.c_uint64), _i, _dp, _dp, _dp, _cp, _i], _i),
     "oip_noise_despike_threshold": ([_d, _d, _d, _d, C.POINTER(_i), C.POINTER(_i), _cp, _i], _i),
+    "oip_sigma_filter_u16": ([_vp, _vp, _l, _l, _vp, _l, _l, _i, _l, _i, _i, _vp, _i, _i, _vp], _i),
+    "oip_denoise_thresholds": ([_d, _d, _d, C.POINTER(C.c_uint16), _cp, _i], _i),
     "oip_mtf_tiles_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _i, _i, _i, _i, _vp, _l, _sz], _i),
     "oip_mtf_esf_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp], _i),
     "oip_mtf_tile": ([_i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _dp], _i),
@@ -336,6 +338,18 @@ def noise_despike_threshold(a: float, b: float, mu_ref: float, k: float = 5.0):
     if rc:
         raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
     return ta.value, q8.value
+
+
+def denoise_thresholds(a: float, b: float, k: float = 2.0):
+    """the 256 uint16 thresholds of one band of Context.sigma_filter_u16 from its noise model: ceil(k sqrt(a + b level)) at the
+    middle of every level, cut at 65535 (include/oip_c.h: oip_denoise_thresholds)"""
+    lib = load_library()
+    thr = np.zeros(256, dtype=np.uint16)
+    err = C.create_string_buffer(1024)
+    rc = lib.oip_denoise_thresholds(a, b, k, thr.ctypes.data_as(C.POINTER(C.c_uint16)), err, 1024)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    return thr
 
 
 MTF_NO_VALUE = 16
@@ -1079,6 +1093,20 @@ class Context:
         out_rows = L if out_rows is None else out_rows
         self._ck(self.lib.oip_despike_u16(self.h, _ptr(src), src_row0, src_rows, _ptr(dst), out_row0, out_rows, W, L, spp, groups,
                                           _ptr(coltab), thr_abs, thr_rel_q8, valid_min, _ptr(count)))
+
+    # -- denoise
+    def sigma_filter_u16(self, src, dst, W, L, spp, radius, thr, min_members=None, valid_min=1, stats=None,
+                         src_row0=0, src_rows=None, out_row0=0, out_rows=None):
+        """Lee's sigma filter with a pilot estimate over (2 radius + 1)^2 on lines [out_row0, out_row0 + out_rows) of the
+        W x L x spp raster whose lines [src_row0, src_row0 + src_rows) are at src; thr: (spp, 256) uint16 on the device, the
+        half width of the range per channel and level (value >> 8); min_members defaults to 2 radius + 1; the four counters
+        (valid, left alone, members, changed) are ADDED into stats ((4,) uint64 on the device, or None); not in place
+        (include/oip_c.h: oip_sigma_filter_u16)"""
+        src_rows = L if src_rows is None else src_rows
+        out_rows = L if out_rows is None else out_rows
+        min_members = 2 * radius + 1 if min_members is None else min_members
+        self._ck(self.lib.oip_sigma_filter_u16(self.h, _ptr(src), src_row0, src_rows, _ptr(dst), out_row0, out_rows, W, L, spp, radius,
+                                               _ptr(thr), min_members, valid_min, _ptr(stats)))
 
     # -- noise
     def noise_blocks_u16(self, src, pitch, w, rows, spp, block, level_shift, keys, key_pitch, key_plane_stride=0, valid_min=1,

@@ -1087,6 +1087,24 @@ extern "C" int oip_noise_despike_threshold(double a, double b, double mu_ref, do
     return OIP_OK;
 }
 
+// ---- oip denoise, host side: the threshold table of oip_sigma_filter_u16 from a noise model (include/oip_c.h states the
+// operation order, tests/_denoise_ref.py restates it) ------------------------------------------------------------------------
+extern "C" int oip_denoise_thresholds(double a, double b, double k, uint16_t *thr256, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *msg) {
+        if (err && errlen > 0) snprintf(err, errlen, "%s", msg);
+        return code;
+    };
+    if (!thr256 || !std::isfinite(a) || !std::isfinite(b) || !std::isfinite(k) || a < 0.0 || b < 0.0 || !(k > 0.0))
+        return fail(OIP_E_INVALID, "oip_denoise_thresholds: bad argument");
+    if (a == 0.0 && b == 0.0) return fail(OIP_E_RUNTIME, "oip_denoise_thresholds: the noise model gives sigma 0 at every level");
+    for (int l = 0; l < 256; ++l) {
+        const double t = std::ceil(k * std::sqrt(a + b * (double)(256 * l + 128)));
+        thr256[l] = (uint16_t)(t < 65535.0 ? t : 65535.0);       // (a + b * level can overflow to inf with finite a, b: inf -> 65535)
+    }
+    return OIP_OK;
+}
+
 // ---- oip mtf, host side: the MTF at Nyquist of a tile from its edge-spread sums, the order statistics of a band, and the slack
 // that follows from a noise level (include/oip_c.h states the operation order, tests/_mtf_ref.py restates it) ---------------
 extern "C" int oip_mtf_tile(int s, const uint32_t *sum, const uint32_t *cnt, double *mtf)

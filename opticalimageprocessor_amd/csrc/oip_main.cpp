@@ -15,6 +15,9 @@
 //   oip despike IMAGE [-o OUT] [--threshold N] [--relative R] [--bad-columns FILE] [--bil]   repair of a raw strip ahead of RRC:
 //                               bad columns interpolated, impulse pixels replaced by a conditional 3 x 3 median, see run_despike();
 //                               --noise REPORT [--k-sigma K] takes the threshold from the report of `oip noise`
+//   oip denoise IMAGE [-o OUT] (--noise REPORT | --sigma S) [--k-sigma K] [--radius 1|2|3] [--min-members M]   noise reduction of a
+//                               strip or product behind RRC and ahead of mtfc: a sigma filter whose range at every signal level
+//                               comes from the report of `oip noise`, see run_denoise()
 //   oip noise IMAGE [-o OUT.csv] [--block 8|16] [--bits N] [--min-blocks N] [--bil]   the noise-level function of a strip or
 //                               product (sigma per signal level, the fit sigma^2 = a + b mu, SNR) in <stem>.NOISE.CSV, see run_noise()
 //   oip mtf IMAGE [-o OUT.csv] [--axis x|y|both] [--contrast-min DN] [--tv-slack DN | --noise REPORT]   the MTF at Nyquist across
@@ -36,7 +39,7 @@
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
 // --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
-// despike, noise, mtf, overviews, regcheck, regfix and pansharpen sub-commands.
+// despike, denoise, noise, mtf, overviews, regcheck, regfix and pansharpen sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -139,7 +142,7 @@ Parsed parse(const Spec &sp, const std::vector<std::string> &args)
     return p;
 }
 
-// The tools with one positional argument (quicklook, mtfc, despike, noise, mtf, overviews; regcheck, regfix and pansharpen name their
+// The tools with one positional argument (quicklook, mtfc, despike, denoise, noise, mtf, overviews; regcheck, regfix and pansharpen name their
 // images by options): IMAGE, an existing regular file, is the first argument that is neither an option nor the value of one (an
 // option's value stays with it, alias or not); the rest is parsed as usual.
 Parsed parse_with_image(const Spec &sp, const std::vector<std::string> &args, std::string *image)
@@ -237,6 +240,15 @@ void usage()
          "             [--bad-columns FILE] (RAW; text: 0-based columns, # comments) interpolated from their good neighbours\n"
          "             [--bil] (RAW: the MSS line layout, bands never mix) [--valid-min N] (samples below are no data; default 1)\n"
          "             [--width N] [--report FILE] (`column count' of the replaced samples) [--force]\n"
+         "  denoise    IMAGE.RAW|IMAGE.TIFF: noise reduction behind RRC / prestitch and ahead of mtfc, Lee's sigma filter with a pilot\n"
+         "             estimate: a sample becomes the mean of the neighbours of its (2 R + 1)^2 window that lie within K sigma of the\n"
+         "             pilot (the same mean over 3 x 3), sigma taken at the pilot's signal level; edges and impulses stay.  The output\n"
+         "             has the container of the input and is written to <stem>.DNS.<ext> in the working directory:\n"
+         "             [-o,--out FILE] --noise REPORT (the report of `oip noise` on the same file: sigma^2 = a + b * level per band; its\n"
+         "             bands must be the image's samples per pixel) | --sigma S (one sigma > 0 at every level of every band)\n"
+         "             [--k-sigma K] (0 < K <= 100; default 2) [--radius 1|2|3] (default 2) [--min-members M] (a sample with fewer\n"
+         "             neighbours in range stays as it is; 1..(2 R + 1)^2, default 2 R + 1) [--valid-min N] (samples below are no\n"
+         "             data: they pass through and enter no mean; default 1) [--width N] [--force]\n"
          "  noise      IMAGE.RAW|IMAGE.TIFF: the noise-level function of a strip or product, measured on the image itself: the standard\n"
          "             deviation of every B x B block without an edge or a ramp in it, per signal level the mode of those, and the fit\n"
          "             sigma^2 = a + b * level; level_lo,level_hi,blocks,sigma,snr per band and level and the fit per band are written\n"
@@ -738,6 +750,40 @@ int run_despike(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip denoise IMAGE: the sigma filter of a strip (.RAW, --width samples per line) or a product (.TIFF of 1 or 4 samples), its
+// thresholds from the report of `oip noise` on the same file (--noise) or from one --sigma (RunDenoise).  IMAGE is the one
+// positional argument, as for mtfc.  Bad values end in 105 before any file is read.
+int run_denoise(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--out", "--noise", "--sigma", "--k-sigma", "--radius", "--min-members", "--valid-min", "--width"};
+    sp.flags = {"--force"};
+    sp.alias = {{"-o", "--out"}};
+    std::string image;
+    Parsed p = parse_with_image(sp, args, &image);
+    if (p.has("--noise") && p.has("--sigma")) throw usage_error("--noise and --sigma exclude each other");
+    if (!p.has("--noise") && !p.has("--sigma")) throw usage_error("--noise REPORT or --sigma S expected");
+    DenoiseOptions o;
+    o.width = p.integer("--width", width);
+    o.radius = p.within("--radius", 2, 1, 3, "1, 2 or 3 expected");
+    const int side = 2 * o.radius + 1;
+    o.minMembers = p.within("--min-members", side, 1, side * side, "1 <= M <= (2 * radius + 1)^2 expected");
+    o.validMin = p.valid_min();
+    // --k-sigma 2 is Lee's choice (95 % of a Gaussian): a wider range keeps more of an edge's other side
+    o.kSigma = p.real("--k-sigma", 2.0);
+    if (!(o.kSigma > 0.0 && o.kSigma <= 100.0)) throw cli_error(105, "--k-sigma: 0 < K <= 100 expected");
+    if (p.has("--sigma")) {
+        o.sigma = p.real("--sigma", 0.0);
+        if (!(o.sigma > 0.0) || !std::isfinite(o.sigma)) throw cli_error(105, "--sigma: a finite S > 0 expected");
+    }
+    existing_file(p, "--noise");
+    o.noiseReport = p.str("--noise");
+    if (p.has("--noise") && o.noiseReport.empty()) throw cli_error(105, "--noise: a file name expected");
+    o.force = p.has("--force");
+    RunDenoise(image, p.str("--out"), o);
+    return 0;
+}
+
 // oip noise IMAGE: the noise-level function of a strip (.RAW, --width samples per line, with --bil the MSS line layout) or a
 // product (.TIFF of 1 or 4 samples) as <stem>.NOISE.CSV (RunNoise).  IMAGE is the one positional argument, as for mtfc.  Bad
 // values end in 105 before any file is read.
@@ -982,6 +1028,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "quicklook") return run_quicklook({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "mtfc") return run_mtfc({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "despike") return run_despike({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "denoise") return run_denoise({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "noise") return run_noise({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "mtf") return run_mtf({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "overviews") return run_overviews({args.begin() + 1, args.end()}, width);

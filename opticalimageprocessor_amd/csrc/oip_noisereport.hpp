@@ -1,5 +1,5 @@
 // oip_noisereport.hpp -- the report of `oip noise` (<stem>.NOISE.CSV): written from the per-level table and the fit of every
-// band, and read back by `oip despike --noise`, which needs each band's (a, b, mu_ref).  Free of HIP, so
+// band, and read back by `oip despike --noise` and `oip denoise --noise`, which need each band's (a, b, mu_ref).  Free of HIP, so
 // tests/cpp/noisereport_test.cpp runs it under ASan + UBSan.
 #pragma once
 
@@ -137,6 +137,29 @@ inline bool NoiseDespikeThreshold(const std::vector<NoiseModel> &models, double 
         if (q8 > *thrRelQ8) *thrRelQ8 = q8;
     }
     return !models.empty();
+}
+
+// The threshold tables `oip denoise --noise` uses: thr[band][256] from oip_denoise_thresholds(a, b, kSigma), one per band of the
+// report, which must hold as many bands as the image has samples per pixel.  Returns false with a message that names both counts,
+// or with the entry point's where a band's model cannot be used.
+inline bool NoiseDenoiseTables(const std::vector<NoiseModel> &models, int spp, double kSigma, std::vector<uint16_t> *thr, std::string *err)
+{
+    thr->clear();
+    if ((int)models.size() != spp) {
+        *err = "holds " + std::to_string(models.size()) + " band" + (models.size() == 1 ? "" : "s") + ", the image has " + std::to_string(spp) +
+               " sample" + (spp == 1 ? "" : "s") + " per pixel";
+        return false;
+    }
+    thr->resize((size_t)spp * 256);
+    for (int c = 0; c < spp; ++c) {
+        char msg[512] = "";
+        if (oip_denoise_thresholds(models[c].a, models[c].b, kSigma, thr->data() + (size_t)c * 256, msg, sizeof msg) != OIP_OK) {
+            *err = "band " + std::to_string(models[c].band) + ": " + msg;
+            thr->clear();
+            return false;
+        }
+    }
+    return true;
 }
 
 }  // namespace OIPGPU

@@ -1,4 +1,4 @@
-// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, noise, mtf, overviews,
+// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, denoise, noise, mtf, overviews,
 // regcheck, regfix, pansharpen) above the host layer of oip_host.hpp.  Stated once for all of them: the file checks made before a
 // device is touched (container, RAW size rule, line range, GuardOutput), the loaders of a resident image, the driver that streams
 // a RAW strip through the device in line blocks (geometry: oip_stripplan.hpp), the filter driver above it, the closing
@@ -63,7 +63,7 @@ inline void GuardOutput(const std::string &path, const std::vector<std::string> 
     if (!force) throw std::runtime_error("output file [" + path + "] exists: " + tool + " does not replace a file without --force");
 }
 
-// the product of a filter (mtfc, despike, regfix): <stem><suffix><ext> unless named, in the container `ext` of the input
+// the product of a filter (mtfc, despike, denoise, regfix): <stem><suffix><ext> unless named, in the container `ext` of the input
 inline std::string FilterOutputPath(const std::string &file, const std::string &out, const char *suffix, const std::string &ext, const char *tool, bool force)
 {
     const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, suffix) : out;
@@ -73,7 +73,7 @@ inline std::string FilterOutputPath(const std::string &file, const std::string &
     return path;
 }
 
-// OIP_<TOOL>_BLOCK_LINES of mtfc, despike, noise, mtf, overviews and regfix (test hooks: several blocks on a small image), rounded
+// OIP_<TOOL>_BLOCK_LINES of mtfc, despike, denoise, noise, mtf, overviews and regfix (test hooks: several blocks on a small image), rounded
 // down to the multiple q of lines the tool needs and never below q; 0 without one
 inline long BlockLinesHook(const char *name, long q = 1)
 {
@@ -177,7 +177,7 @@ template <class Work> inline void ReadStrip(const std::string &file, const Strip
     StreamStrip(file, plan, nullptr, [&](const uint16_t *src, long s0, long lines, uint16_t *, long, long) { work(src, s0 - plan.first, lines); });
 }
 
-// The filters (mtfc, despike, regfix) write an image of the size and container of their input through one
+// The filters (mtfc, despike, denoise, regfix) write an image of the size and container of their input through one
 // work(src, srcFirst, srcLines, dst, dstFirst, dstLines, w, L, spp), the argument order of their kernels.  A TIFF product is
 // resident: one call over the whole image, which leaves through the product writer of `oip stitch` (`word` is the tool's for
 // what it writes).  A RAW strip of rawWidth samples per line streams through StreamStrip with `halo` lines either side of a
@@ -619,6 +619,93 @@ inline void DespikeNoiseThreshold(const std::string &report, double kSigma, Desp
     o->hasThreshold = true;
     OLOG("despike: %g sigma of the noise model of [%s] (%zu band%s): threshold %d, relative %d / 256", kSigma, report.c_str(), models.size(),
          models.size() == 1 ? "" : "s", o->thrAbs, o->thrRelQ8);
+}
+
+// ---- oip denoise: the sigma filter that the noise model drives ---------------------------------------------------------------
+// The acting side of `oip noise` for the noise itself (oip_sigma_filter_u16): an edge-preserving mean over the neighbours that lie
+// within K sigma of a pilot estimate, sigma taken at the pilot's signal level from the report's model of the band (or one --sigma
+// for every level).  It runs behind RRC / prestitch and ahead of mtfc.  The output has the container of the input.  Not in the
+// reference.
+struct DenoiseOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    std::string noiseReport;                // --noise, or
+    double sigma = 0.0;                     // --sigma: one sigma at every level of every band
+    double kSigma = 2.0;
+    int radius = 2;
+    int minMembers = 5;                     // 2 * radius + 1 unless given
+    int validMin = 1;                       // 0 is the border value of prestitch and the aligner (BORDER_CONSTANT)
+    bool force = false;
+};
+
+// thr[spp][256] of a run: from the report's models (one per sample of a pixel), or --sigma at every level; no device is touched
+inline std::vector<uint16_t> DenoiseThresholds(const DenoiseOptions &o, const std::vector<NoiseModel> &models, int spp)
+{
+    std::vector<uint16_t> thr;
+    if (o.noiseReport.empty()) {
+        const double t = std::ceil(o.kSigma * o.sigma);
+        thr.assign((size_t)spp * 256, (uint16_t)(t < 65535.0 ? t : 65535.0));
+        return thr;
+    }
+    std::string err;
+    if (!NoiseDenoiseTables(models, spp, o.kSigma, &thr, &err)) throw std::runtime_error("noise report [" + o.noiseReport + "] " + err);
+    return thr;
+}
+
+// what is refused without a device and stated here alone: the container, --width and the size of a RAW file, the report and, for
+// a RAW strip (one band), its tables, the output; returns the output path
+inline std::string DenoiseCheck(const std::string &file, const std::string &out, const DenoiseOptions &o, bool *isTiff, std::vector<NoiseModel> *models)
+{
+    const std::string ext = RasterContainer(file, "denoise");
+    *isTiff = ext == ".tiff";
+    if (!*isTiff) {
+        if (o.width <= 0) throw std::invalid_argument("--width: a positive line width expected");
+        RawLineCount(file, "image", (size_t)o.width * BYTES_PER_PIXEL);
+    }
+    if (!o.noiseReport.empty()) {
+        std::string err;
+        if (!ParseNoiseReport(o.noiseReport, models, &err)) throw std::runtime_error(err);
+    }
+    if (!*isTiff) DenoiseThresholds(o, *models, 1);                      // (a TIFF's samples per pixel are known once it is read)
+    return FilterOutputPath(file, out, OIP_DENOISE_SUFFIX, ext, "denoise", o.force);
+}
+
+inline void RunDenoise(const std::string &file, const std::string &out, const DenoiseOptions &o)
+{
+    bool isTiff = false;
+    std::vector<NoiseModel> models;
+    const std::string outPath = DenoiseCheck(file, out, o, &isTiff, &models);
+    const int side = 2 * o.radius + 1;
+    OLOG("denoise: sigma filter %d x %d, %g sigma of %s, min-members %d, valid-min %d", side, side, o.kSigma,
+         o.noiseReport.empty() ? ("--sigma " + std::to_string(o.sigma)).c_str() : ("the noise model of [" + o.noiseReport + "]").c_str(), o.minMembers,
+         o.validMin);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    std::vector<uint16_t> table;                                        // the first block knows the samples per pixel
+    DevBuf<uint16_t> thr;
+    DevBuf<uint64_t> stats(4);
+    ck(oip_memset(ctx, stats.p, 0, 4 * sizeof(uint64_t)));
+    // a block of a strip needs `radius` halo lines either side
+    const size_t bytes = FilterImage(file, outPath, isTiff, o.width, o.radius, "OIP_DENOISE_BLOCK_LINES", "denoise", "denoised",
+                                     [&](const uint16_t *src, long s0, long sn, uint16_t *dst, long r, long m, int w, long L, int spp) {
+                                         if (!thr.p) {
+                                             table = DenoiseThresholds(o, models, spp);          // refuses a report of another band count
+                                             for (int c = 0; c < spp; ++c)
+                                                 OLOG("denoise: band %d thresholds at levels 0, 64, 128, 255: %d %d %d %d", c + 1, table[c * 256],
+                                                      table[c * 256 + 64], table[c * 256 + 128], table[c * 256 + 255]);
+                                             thr.assign(table);
+                                         }
+                                         ck(oip_sigma_filter_u16(ctx, src, s0, sn, dst, r, m, w, L, spp, o.radius, thr.p, o.minMembers, o.validMin, stats.p));
+                                     });
+    uint64_t s[4];
+    stats.download(s, 4);                                               // (synchronises: the last kernel has run)
+    const uint64_t filtered = s[0] - s[1];
+    OLOG("denoise: %llu samples with data, %llu filtered (mean members %.2f of %d), %.3f %% left alone, %.3f %% changed", (unsigned long long)s[0],
+         (unsigned long long)filtered, filtered ? (double)s[2] / (double)filtered : 0.0, side * side, s[0] ? 100.0 * (double)s[1] / (double)s[0] : 0.0,
+         s[0] ? 100.0 * (double)s[3] / (double)s[0] : 0.0);
+    RLOG("    counters: valid %llu alone %llu members %llu changed %llu", (unsigned long long)s[0], (unsigned long long)s[1], (unsigned long long)s[2],
+         (unsigned long long)s[3]);
+    LogThroughput(bytes, total.tick());
 }
 
 // ---- oip noise: the noise-level function of a strip or product ----------------------------------------------------------
