@@ -9,15 +9,9 @@
 // Everything is integer and exact: a sum of at most 49 samples is below 2^22 and their count below 2^6, so both live in ONE
 // int32 as S | m << 24 -- a sample is unpacked from LDS as n | 1 << 24 once and a member is one add.
 //
-// Layout / mapping: that of convolve.hip.  Lines are handled in SAMPLE units (Ws = W * spp; the channel of sample s is
-// s % spp, a horizontal neighbour is spp samples away).  A block of 256 lanes owns a tile of 512 samples x 16 lines.  The tile
-// plus its halo (R lines above and below, R * spp samples left and right rounded up to 8 = HP) goes to LDS once, in 16-byte
-// chunks: an aligned global_load_dwordx4 where the chunk lies inside the line, eight clamped 2-byte loads where it crosses
-// the image border (pixel index clamped, channel kept).  Lines are clamped the same way and fetched from the resident window.
-// The spp x 256 threshold table (2 KB at spp 4) is copied to LDS beside it; a sample reads it twice, by c >> 8 and c1 >> 8.
-// Then a lane owns ONE aligned 16-byte store: 8 consecutive samples of a line; a wave takes a line, the four waves every
-// fourth line of the tile.  The tile starts at a multiple of 512 samples, so the channel of a lane's sample k is k % spp, a
-// compile-time constant.
+// Layout / mapping: the tile, grid and LDS layout of oip_tile.h with ry = rx = R; the fill's minimum is not used (no tile form
+// without the no-data rules).  The spp x 256 threshold table (2 KB at spp 4) is copied to LDS beside the tile; a sample reads
+// it twice, by c >> 8 and c1 >> 8.  LDS with the table: 21.6 KB at R = 2, spp 1; 26.0 KB at R = 3, spp 4.
 //
 // Per neighbour and output sample: d = n - lo (unsigned wrap), d <= hi - lo, select n | 1 << 24 or 0, add: four vector
 // instructions (v_sub, v_cmp, v_cndmask, v_add).  The packed 16-bit forms do not pay: v_pk_sub_u16 / v_pk_min_u16 exist, but a
@@ -27,33 +21,17 @@
 //
 // Counters (d_stats): a lane keeps the four in registers, a wave adds them by shuffles, the four waves meet in LDS and four
 // lanes issue one 64-bit atomicAdd each per block.  STATS is a template parameter: without d_stats none of that is compiled.
-//
-// A line that is not a multiple of 8 samples, or bases that are not 16-byte aligned, take the same kernel with ALIGNED =
-// false: 2-byte loads into the same LDS image, the same arithmetic, 2-byte stores.
-//
-// One tile per block, no grid-stride loop.  LDS: (16 + 2 R) lines x (512 + 2 HP) samples x 2 bytes + the table: 21.6 KB at
-// R = 2, spp 1; 26.0 KB at R = 3, spp 4.
-#include "oip_internal.h"
+#include "oip_tile.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int kTileW = 512;                  // samples: 64 lanes x 8
-constexpr int kTileH = 16;                   // lines
+constexpr int kBlock = kOipTileBlock;
 constexpr int kOne = 1 << 24;                // the member count's unit in an accumulator
 
-struct SigmaArgs {
-    const uint16_t *src;
-    uint16_t *dst;
+struct SigmaArgs : OipTileArgs {
     const uint16_t *thr;                     // spp x 256
     unsigned long long *stats;               // 4, or NULL
-    long Ws, L;                              // samples per line, lines of the raster
-    long src_row0, out_row0, out_rows;
-    int W;                                   // pixels per line
     int minm;
-    int vmin;
-    int tiles_x;
 };
 
 // the NW samples of a lane's window on one LDS line, each as n | 1 << 24
@@ -92,13 +70,12 @@ __device__ __forceinline__ void range_of(int c, int T, int vmin, int *lo, int *r
     *rng = h - l;
 }
 
-// the 8 output samples of one lane on one line.  win: the lane's first LDS sample of the tile's LDS line `lr` (= output line
-// - first output line of the tile; window line j reads LDS line lr + j).  nk: the lane's samples inside the line (8 if ALIGNED).
+// the 8 output samples of one lane on one line.  win, nk: as oip_tile_lines() hands them over.
 // st: [0] centres >= vmin, [1] of those left alone, [2] sum of m over the filtered, [3] samples changed
 template <int SPP, int R, bool STATS>
 __device__ __forceinline__ uint4 sigma_lane(const uint16_t *win, const uint16_t *tab, int vmin, int minm, int nk, unsigned (&st)[4])
 {
-    constexpr int HP = (R * SPP + 7) / 8 * 8, NW = 8 + 2 * HP, PITCH = kTileW + 2 * HP;
+    constexpr int HP = oip_tile_hp(SPP, R), NW = 8 + 2 * HP, PITCH = oip_tile_pitch(HP);
     int w[NW], ctr[8], lo[8], rng[8], acc[8];
     load_line<NW>(win + R * PITCH, w);
 #pragma unroll
@@ -152,78 +129,28 @@ __device__ __forceinline__ uint4 sigma_lane(const uint16_t *win, const uint16_t 
             st[3] += v != c ? 1 : 0;
         }
     }
-    return make_uint4(o[0] | (o[1] << 16), o[2] | (o[3] << 16), o[4] | (o[5] << 16), o[6] | (o[7] << 16));
+    return oip_pack8(o);
 }
 
-// ALIGNED requires: Ws % 8 == 0, src and dst 16-byte aligned
 template <int SPP, int R, bool ALIGNED, bool STATS>
 __global__ __launch_bounds__(kBlock) void sigma_filter_u16_kernel(const SigmaArgs a)
 {
-    constexpr int HP = (R * SPP + 7) / 8 * 8, PITCH = kTileW + 2 * HP, NCH = PITCH / 8, SH = SPP == 4 ? 2 : 0;
-    __shared__ uint4 tile4[(kTileH + 2 * R) * NCH];
+    constexpr int HP = oip_tile_hp(SPP, R);
+    __shared__ uint4 tile4[(kOipTileH + 2 * R) * oip_tile_nch(HP)];
     __shared__ uint16_t tab[SPP * 256];
-    __shared__ unsigned wsum[kWaves][4];
-    const long ty = (long)blockIdx.x / a.tiles_x;
-    const int tx = (int)((long)blockIdx.x - ty * a.tiles_x);
-    const long y0 = a.out_row0 + ty * kTileH;                    // first output line of the tile (global)
-    const long left = a.out_row0 + a.out_rows - y0;
-    const int rows = left < kTileH ? (int)left : kTileH;         // output lines of the tile, >= 1
-    const long x0 = (long)tx * kTileW;                           // first output sample of the tile
-    const long wleft = a.Ws - x0;
-    const int cols = wleft < kTileW ? (int)wleft : kTileW;       // output samples of the tile, >= 1
-    const int nch = (cols + 2 * HP + 7) >> 3;                    // chunks of an LDS line that are read later
-    const int nfill = (rows + 2 * R) * NCH;
-
-    // ---- the threshold table, the tile and its halo -> LDS ------------------------------------------------------------------
+    __shared__ unsigned wsum[kOipTileWaves][4];
+    const OipTile t = oip_tile_of(a, blockIdx.x, SPP, HP, R);
 #pragma unroll
     for (int c = 0; c < SPP; ++c) tab[c * 256 + threadIdx.x] = a.thr[c * 256 + threadIdx.x];
-    for (int e = threadIdx.x; e < nfill; e += kBlock) {
-        const int r = e / NCH, c = e - r * NCH;
-        if (c >= nch) continue;
-        long v = y0 - R + r;
-        v = v < 0 ? 0 : (v > a.L - 1 ? a.L - 1 : v);             // inside [src_row0, src_row0 + src_rows): host-checked
-        const uint16_t *line = a.src + (v - a.src_row0) * a.Ws;
-        const long s = x0 - HP + c * 8;
-        uint4 q;
-        if (ALIGNED && s >= 0 && s + 8 <= a.Ws) {
-            q = *reinterpret_cast<const uint4 *>(line + s);
-        } else {
-            unsigned t[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const long ss = s + k;
-                long p = ss >> SH;                               // arithmetic shift: the floor for ss < 0 as well
-                p = p < 0 ? 0 : (p > a.W - 1 ? a.W - 1 : p);
-                t[k] = line[(p << SH) + (ss & (SPP - 1))];
-            }
-            q = make_uint4(t[0] | (t[1] << 16), t[2] | (t[3] << 16), t[4] | (t[5] << 16), t[6] | (t[7] << 16));
-        }
-        tile4[e] = q;
-    }
+    oip_tile_fill<SPP, HP, ALIGNED>(tile4, a, t, R, OipTileEdge());
     __syncthreads();
-
-    // ---- a wave per line, a lane per 16 bytes of it -------------------------------------------------------------------------
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     unsigned st[4] = {0, 0, 0, 0};
-    if (lane * 8 < cols) {
-        const uint16_t *tile = reinterpret_cast<const uint16_t *>(tile4);
-        const int nk = ALIGNED ? 8 : (cols - lane * 8 < 8 ? cols - lane * 8 : 8);
-        for (int r = wave; r < rows; r += kWaves) {
-            const uint4 o = sigma_lane<SPP, R, STATS>(tile + r * PITCH + lane * 8, tab, a.vmin, a.minm, nk, st);
-            uint16_t *out = a.dst + (y0 - a.out_row0 + r) * a.Ws + x0 + lane * 8;
-            if (ALIGNED) {
-                *reinterpret_cast<uint4 *>(out) = o;             // cols % 8 == 0: the whole chunk is inside the line
-            } else {
-                const unsigned d[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (k < nk) out[k] = (uint16_t)(d[k >> 1] >> ((k & 1) * 16));
-            }
-        }
-    }
+    oip_tile_lines<HP, ALIGNED>(tile4, a, t,
+                                [&](const uint16_t *win, int nk) { return sigma_lane<SPP, R, STATS>(win, tab, a.vmin, a.minm, nk, st); });
     if (!STATS) return;
 
     // ---- counters: lanes -> wave (shuffles) -> block (LDS) -> one atomic per counter ---------------------------------------
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         unsigned v = st[i];                                      // a lane's <= 32 samples x <= 49 members: a wave's sum is below 2^17
@@ -235,7 +162,7 @@ __global__ __launch_bounds__(kBlock) void sigma_filter_u16_kernel(const SigmaArg
     if (threadIdx.x < 4) {
         unsigned v = 0;
 #pragma unroll
-        for (int w = 0; w < kWaves; ++w) v += wsum[w][threadIdx.x];
+        for (int w = 0; w < kOipTileWaves; ++w) v += wsum[w][threadIdx.x];
         if (v) atomicAdd(a.stats + threadIdx.x, (unsigned long long)v);
     }
 }
@@ -268,39 +195,21 @@ extern "C" int oip_sigma_filter_u16(oip_ctx *ctx, const uint16_t *d_src, long sr
                                     int W, long L, int spp, int radius, const uint16_t *d_thr, int min_members, int valid_min, uint64_t *d_stats)
 {
     OIP_CHECK_CTX(ctx);
-    if (!d_src || !d_dst || !d_thr || ((uintptr_t)d_src & 1) || ((uintptr_t)d_dst & 1) || ((uintptr_t)d_thr & 1) || ((uintptr_t)d_stats & 7) ||
-        (spp != 1 && spp != 4) || W < 1 || L < 1 || radius < 1 || radius > 3 || min_members < 1 ||
-        min_members > (2 * radius + 1) * (2 * radius + 1) || valid_min < 0 || valid_min > 65535 || src_row0 < 0 || src_rows < 0 || out_row0 < 0 ||
-        out_rows < 0 || out_rows > L || out_row0 > L - out_rows)
-        return oip_fail(ctx, OIP_E_INVALID, "oip_sigma_filter_u16: bad argument");
-    if ((const uint16_t *)d_dst == d_src) return oip_fail(ctx, OIP_E_INVALID, "oip_sigma_filter_u16: the call is not in place (d_dst == d_src)");
-    if (out_rows == 0) return OIP_OK;
-    const long first = out_row0 - radius < 0 ? 0 : out_row0 - radius;
-    const long last = out_row0 + out_rows - 1 + radius > L - 1 ? L - 1 : out_row0 + out_rows - 1 + radius;
-    if (first < src_row0 || last >= src_row0 + src_rows)
-        return oip_fail(ctx, OIP_E_INVALID, "oip_sigma_filter_u16: source lines [%ld, %ld] needed, [%ld, %ld) resident", first, last, src_row0,
-                        src_row0 + src_rows);
+    const char *fn = "oip_sigma_filter_u16";
+    if (!d_thr || ((uintptr_t)d_thr & 1) || ((uintptr_t)d_stats & 7) || radius < 1 || radius > 3 || min_members < 1 ||
+        min_members > (2 * radius + 1) * (2 * radius + 1))
+        return oip_fail(ctx, OIP_E_INVALID, "%s: bad argument", fn);
+    const OipTilePlan p = oip_tile_plan(d_src, src_row0, src_rows, d_dst, out_row0, out_rows, W, L, spp, valid_min, radius, 1, W);
+    if (const int rc = oip_tile_refusal(ctx, fn, p)) return rc;
+    if (!p.blocks) return OIP_OK;
     SigmaArgs a;
-    a.src = d_src;
-    a.dst = d_dst;
+    static_cast<OipTileArgs &>(a) = p.args;
     a.thr = d_thr;
     a.stats = reinterpret_cast<unsigned long long *>(d_stats);
-    a.Ws = (long)W * spp;
-    a.L = L;
-    a.src_row0 = src_row0;
-    a.out_row0 = out_row0;
-    a.out_rows = out_rows;
-    a.W = W;
     a.minm = min_members;
-    a.vmin = valid_min;
-    const long tiles_x = (a.Ws + kTileW - 1) / kTileW, tiles_y = (out_rows + kTileH - 1) / kTileH;
-    if (tiles_x * tiles_y >= (1L << 31)) return oip_fail(ctx, OIP_E_UNSUPPORTED, "oip_sigma_filter_u16: more than 2^31 tiles in one call");
-    a.tiles_x = (int)tiles_x;
-    const bool aligned = a.Ws % 8 == 0 && ((uintptr_t)d_src & 15) == 0 && ((uintptr_t)d_dst & 15) == 0;
-    const unsigned blocks = (unsigned)(tiles_x * tiles_y);
     OipProfScope prof(ctx, "sigma_filter_u16_kernel");
-    if (spp == 1) launch_radius<1>(radius, aligned, blocks, ctx->stream, a);
-    else launch_radius<4>(radius, aligned, blocks, ctx->stream, a);
+    if (spp == 1) launch_radius<1>(radius, p.aligned, p.blocks, ctx->stream, a);
+    else launch_radius<4>(radius, p.aligned, p.blocks, ctx->stream, a);
     OIP_HIP(ctx, hipGetLastError());
     return OIP_OK;
 }
