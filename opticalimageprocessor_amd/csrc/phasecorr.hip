@@ -606,6 +606,12 @@ __device__ __forceinline__ float2 sfma(float s, float2 v, float2 acc)
     return make_float2(acc.x + s * v.x, acc.y + s * v.y);
 }
 
+// the value of lane ^ 1 (DPP quad_perm [1, 0, 3, 2]: no LDS traffic); both lanes of the pair must be active
+__device__ __forceinline__ float quad_swap1(float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
+}
+
 template <int NT, bool VEXP, bool WIN>
 __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, int P, const int *__restrict__ ypos,
                                                           const float2 *__restrict__ twF, const float2 *__restrict__ twS)
@@ -615,6 +621,8 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
     // A thread owns the bins kx = tid + NT r <= N/2 of line ky and their mirrors N - kx of the same line: H and G are
     // transforms of real sequences, so the mirror's table values are the conjugates -- half the table registers.
     constexpr int NB = (F / 2 + 1 + NT - 1) / NT;
+    constexpr int WE = (F / 2) % NT / 64;           // the wave that owns bin N/2 (bin 0 is wave 0's)
+    static_assert(WE != 0, "the two edge columns are evaluated by two waves");
     __shared__ __align__(16) float2 buf[2 * 2 * F + 4 * 2 * S];    // PAN / output 0 | output 1 | narrow arrays; [point][line]
     __shared__ float2 tw[TWF], tws[TWS];
     __shared__ float2 edge[4][2][4];                               // [array][line][j]: narrow line samples 0, 1, S-2, S-1
@@ -825,28 +833,36 @@ __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, i
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            // the two edge columns again with their own formulas (one copy of that code, two threads of the block)
-#pragma unroll 1
-            for (int r = 0; r < NB; ++r) {
-                const int kx = tid + NT * r;
-                if (kx != 0 && 2 * kx != F) continue;
-                const bool real_bin = ky == 0 || 2 * ky == M;
-                const float2 Ae = edgeA[kx ? 1 : 0][o0 ? 1 : 0];
-                // (from LDS: a vector-memory load here would be younger than the prefetch and wait for it)
-                float2 He = edgeT[kx ? 1 : 0][0], Ge[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) Ge[j] = edgeT[kx ? 1 : 0][1 + j];
-#pragma unroll 1
-                for (int h = 0; h < 2; ++h) {
+            // The two edge columns again with their own formulas.  The four evaluations of a round -- (h, C1 | C2) -- are
+            // independent chains of double-precision divisions and a square root: each takes one of the first four lanes
+            // of the wave that owns the column, side by side (in series in the owning lane they were more f64 work than
+            // both main loops, with the rest of the workgroup waiting at finish()'s barrier).  That wave wrote edgeA and
+            // the bins these lanes overwrite itself: the LDS accesses of one wave complete in order, so a wave-level
+            // fence for the compiler is enough and no barrier is added.  The test is wave-uniform: the other six waves
+            // branch over the block.
+            const int wv = __builtin_amdgcn_readfirstlane(tid) >> 6;
+            if (wv == 0 || wv == WE) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                const int ec = wv ? 1 : 0, kx = ec * (F / 2), lane = tid & 63;
+                if (lane < 4) {
+                    const int h = lane >> 1, part = lane & 1;
+                    const bool real_bin = ky == 0 || 2 * ky == M;
+                    const float2 Ae = edgeA[ec][o0 ? 1 : 0];
+                    // (from LDS: a vector-memory load here would be younger than the prefetch and wait for it)
+                    const float2 He = edgeT[ec][0];
                     const float2 *zn = bufN + (o0 + h) * 2 * S;
                     float2 Z0 = oipfft::cmul(He, zn[0]), Z1 = cmulj(He, zn[1]);       // kx = 0 and N/2 both map to narrow bin 0
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) { Z0 = cfma(Ge[j], edge[o0 + h][0][j], Z0); Z1 = cfmaj(Ge[j], edge[o0 + h][1][j], Z1); }
-                    const float2 C1 = cross_power_bin(Ae, spec2_of(0, Z0, Z1), real_bin, true);
-                    const float2 C2 = cross_power_bin(Ae, spec2_of(1, Z0, Z1), real_bin, true);
+                    for (int j = 0; j < 4; ++j) {
+                        const float2 Ge = edgeT[ec][1 + j];
+                        Z0 = cfma(Ge, edge[o0 + h][0][j], Z0); Z1 = cfmaj(Ge, edge[o0 + h][1][j], Z1);
+                    }
+                    const float2 C = cross_power_bin(Ae, spec2_of(part, Z0, Z1), real_bin, true);
+                    const float2 D = make_float2(quad_swap1(C.x), quad_swap1(C.y));    // the neighbour's: C2 for C1, C1 for C2
+                    const float2 C1 = part ? D : C, C2 = part ? C : D;
                     float2 *ob = buf + h * 2 * F;
-                    ob[2 * kx] = make_float2(C1.x - C2.y, -(C1.y + C2.x));
-                    ob[2 * kx + 1] = pair ? make_float2(C1.x + C2.y, -(C2.x - C1.y)) : make_float2(0.f, 0.f);   // -kx == kx here
+                    if (part == 0) ob[2 * kx] = make_float2(C1.x - C2.y, -(C1.y + C2.x));
+                    else ob[2 * kx + 1] = pair ? make_float2(C1.x + C2.y, -(C2.x - C1.y)) : make_float2(0.f, 0.f);   // -kx == kx here
                 }
             }
         };
