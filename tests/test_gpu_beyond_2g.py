@@ -264,8 +264,8 @@ def test_seam_moments_whole_raster(ctx, spp):
 @pytest.mark.parametrize("spp,h,tag", [(1, 16, ""), (4, 0, ""), (1, 0, ""), (4, 16, ""), (1, 16, "_scalar")])
 def test_stitch_balanced_whole_raster(ctx, probes, spp, h, tag, lines):
     """oip_stitch_balanced_u16 and, with a (G, O) per line in tables of 65600 entries (their own pair on every line of the
-    bands), oip_stitch_balanced_lines_u16.  fs = 100 samples, output line 65320: the vector kernels; "_scalar": fs = 99, output
-    line 65322, not a multiple of 8: stitch_balanced_scalar_kernel / stitch_balanced_lines_scalar_kernel.
+    bands), oip_stitch_balanced_lines_u16.  fs = 100 samples, output line 65320: the vector form; "_scalar": fs = 99, output
+    line 65322, not a multiple of 8: the per-sample form of either.
     Peak: 2 x 4.3 + 8.6 = 17.2 GB."""
     p = probes["stitch_balanced_%sspp%d_h%d%s" % ("lines_" if lines else "", spp, h, tag)]
     e = p.extra

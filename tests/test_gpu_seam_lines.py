@@ -15,6 +15,7 @@ import _seam_lines_ref as lref
 pytestmark = pytest.mark.gpu
 
 STITCH_SHAPES = [(96, 64, 8, 1), (520, 257, 13, 1), (131, 1000, 3, 4), (64, 1, 4, 1), (1024, 37, 100, 1), (256, 300, 25, 4)]
+MOMENT_SHAPES = STITCH_SHAPES[:4]                                      # test_gpu_seam.py's
 # (W, L, fold, spp, B).  The last one is not the issue's: 2500 line ranges are more than the 2048 workgroups a column group gets
 # on 256 CUs, so workgroups take a second range (the kernel's grid-stride loop, with its second barrier)
 MOMENT_CASES = [(96, 64, 8, 1, 16), (96, 64, 8, 1, 1), (520, 257, 13, 1, 50), (131, 1000, 3, 4, 64), (64, 1, 4, 1, 8), (131, 1000, 3, 4, 5000),
@@ -114,6 +115,38 @@ def test_block_moments_top_of_the_range(ctx, B):
         n = 2 * fold * (r1 - r0)
         assert got[k, :, 0].tolist() == [n, n * 65535, n * 65535, n * 65535 ** 2, n * 65535 ** 2, n * 65535 ** 2], k
     assert len(lref.blocks(L, B)) == nb and (B != 70000 or 2 * fold * L * 65535 ** 2 > 2 ** 48)
+
+
+@pytest.mark.parametrize("window", [(), (64, 4095)])
+@pytest.mark.parametrize("W,L,fold,spp", MOMENT_SHAPES)
+def test_strip_moments_are_plane_0_of_one_block(ctx, W, L, fold, spp, window):
+    """the strip entry and the blocks entry are one kernel: with B = L and with B = L + 1 there is one block, and its plane
+    holds the strip entry's 6 * spp words; unmasked and with the valid window [64, 4095]"""
+    left, right = _pair(W, L, fold, spp)
+    dl, dr = _cuda(left), _cuda(right)
+    strip = _acc(1, spp)
+    ctx.seam_moments_u16(dl, dr, W * spp, L, fold * spp, spp, strip[0], *window)
+    for B in (L, L + 1):
+        acc = _acc(1, spp)
+        ctx.seam_moments_blocks_u16(dl, dr, W * spp, L, fold * spp, spp, B, acc, *window)
+        ctx.sync()
+        assert np.array_equal(_host(acc)[0], _host(strip)[0]), B
+    assert window or (_host(strip)[0, 0] == 2 * fold * L).all()
+
+
+def test_strip_and_block_moments_keep_their_profiler_names(ctx):
+    W, L, fold = 96, 64, 8
+    left, right = _pair(W, L, fold, 1)
+    dl, dr = _cuda(left), _cuda(right)
+    ctx.profile_enable(True)
+    ctx.profile_reset()
+    strip, acc = _acc(1, 1), _acc(4, 1)
+    ctx.seam_moments_u16(dl, dr, W, L, fold, 1, strip[0])
+    ctx.seam_moments_blocks_u16(dl, dr, W, L, fold, 1, 16, acc)
+    ctx.sync()
+    prof = ctx.profile()
+    ctx.profile_enable(False)
+    assert prof["seam_moments_kernel"][1] == 1 and prof["seam_moments_blocks_kernel"][1] == 1
 
 
 # ---- the stitch with a (G, O) per line ------------------------------------------------------------------------------------------
