@@ -745,6 +745,70 @@ int oip_sigma_filter_u16(oip_ctx *ctx, const uint16_t *d_src, long src_row0, lon
  * without noise. */
 int oip_denoise_thresholds(double a, double b, double k, uint16_t *thr256, char *err, int errlen);
 
+/* ---- mask: no-data, saturation and cloud mask of a strip or product (`oip mask`; not in the reference) ---------------
+ * Which parts of a raster are usable: one flag byte per C x C cell, then an opening and a buffer on the grid of cells.  It sits
+ * behind `oip align` / `oip stitch` and ahead of `oip regcheck --mask`, `oip regfix` and `oip pansharpen`.  Specified in exact
+ * integers: any launch geometry and any cutting of a strip gives the same bytes and the same counters. */
+#define OIP_MASK_SUFFIX     ".MASK"   /* <stem>.MASK.TIFF, <stem>.MASK.CSV */
+#define OIP_MASK_NODATA     1         /* the cell holds a pixel with a channel below valid_min */
+#define OIP_MASK_SATURATED  2         /* the cell holds a saturated pixel */
+#define OIP_MASK_CLOUD      4         /* the cell lies in the opening of the candidates (oip_mask_morph_u8) */
+#define OIP_MASK_BUFFER     8         /* the cell lies within buffer_radius of CLOUD and is not CLOUD */
+#define OIP_MASK_CANDIDATE 16         /* the cell passed every enabled spectral test */
+
+/* One flag byte per cell of a u16 raster window, the one pass over the full-size image.  Raster conventions are
+ * oip_noise_blocks_u16's: rows lines of w pixels of spp samples (1, or 4 pixel-interleaved), lines `pitch` SAMPLES apart, the
+ * window inside the lines of its raster.  cell C is 4, 8 or 16.  Cell (j, i) covers pixels [iC, min(w, iC + C)) x [jC,
+ * min(rows, jC + C)): the grid is gw = ceil(w / C) by gh = ceil(rows / C), and the cells at the right and bottom edge may hold
+ * fewer than C * C pixels, n_cell.  The byte of cell (j, i) goes to d_flags[j * flag_pitch + i].
+ * Per pixel:   nodata: any channel < valid_min;   sat: not nodata and any channel >= sat_level;   good: neither.
+ * Per cell, in unsigned 64-bit integers (every sum is below 256 * 65535 < 2^24 and fits 32 bits):
+ *   m = good pixels, n_nd = nodata pixels, n_sat = saturated pixels
+ *   spp 4, band[4] = the channel of (blue, green, red, nir):  b, g, r, n = the sums of those channels over the good pixels,
+ *   V = b + g + r,  mx = max(b, g, r),  mn = min(b, g, r)
+ * Bits:   1 NODATA: n_nd > 0        2 SATURATED: n_sat > 0
+ *        16 CANDIDATE: spp 4 only; the cell is tested (2 * m >= n_cell and m >= 1) and every enabled test holds, in signed
+ *           64-bit integers (the largest product, 3 * m * full * q8, is below 2^35), `full` = full_scale:
+ *             bright           256 * V >= 3 * m * full * bright_q8
+ *             white            768 * (mx - mn) <= white_q8 * V
+ *             haze (HOT)       256 * (2 * b - r) >= 2 * m * full * hot_q8           (blue - red / 2)
+ *             not vegetation   256 * (n - r) <= ndvi_q8 * (n + r)
+ *           A test whose q8 parameter is -1 is disabled; otherwise the parameter is in 0..256.
+ * With spp 1 no cell is tested and bit 16 is never set (band is ignored and may be NULL).  Bits 4 and 8 are written as 0.
+ * d_counts: NULL, or 8 uint64 in HBM that are ADDED into; the caller zeroes them (oip_memset).  This call adds
+ *   [0] cells   [1] NODATA cells   [2] SATURATED cells   [3] tested cells   [4] CANDIDATE cells   [7] saturated pixels
+ * ([5] and [6] belong to oip_mask_morph_u8).  The counters are exact and do not depend on the launch geometry or on how a strip
+ * is cut.  A strip cut into calls at lines that are multiples of C (each call writing from cell line first / C on) gives the
+ * bytes and the counters of one call.  Lines and offsets are 64-bit.  Asynchronous on the context's stream.  OIP_E_INVALID:
+ * cell not 4, 8 or 16, spp not 1 or 4, w < 0, rows < 0, pitch < w * spp, flag_pitch < gw, valid_min outside 0..65535, sat_level
+ * or full_scale outside 1..65535, a q8 parameter outside -1..256, with spp 4 a band that is not a permutation of 0..3.  w == 0
+ * or rows == 0 is a no-op.  A pitch that is not a multiple of 8 samples, or a window that does not start on a 16-byte
+ * boundary, takes a slower kernel with the same bytes. */
+int oip_mask_cells_u16(oip_ctx *ctx, const uint16_t *d_src, long pitch, int w, long rows, int spp, int cell, int valid_min, int sat_level,
+                       int full_scale, const int *band, int bright_q8, int white_q8, int hot_q8, int ndvi_q8, uint8_t *d_flags,
+                       long flag_pitch, uint64_t *d_counts);
+
+/* Opening and buffer on the whole gw x gh grid of flag bytes, in place.  X = the cells with bit 16.
+ *   E (erosion): a cell is in E iff every cell of the (2a+1) x (2a+1) square around it that lies inside the grid is in X;
+ *                what lies outside the grid does not constrain
+ *   O = the cells within Chebyshev distance a of a cell of E (the opening);   D = the cells within Chebyshev distance d of O
+ *   bit 4 CLOUD = O,   bit 8 BUFFER = D \ O
+ * a = open_radius in 0..32, d = buffer_radius in 0..64; a radius may exceed the grid.  Bits 1, 2 and 16 are kept, bits 4 and 8
+ * are overwritten: a second call changes nothing.  It follows that O is a subset of X, that a = 0 gives O = X and that the
+ * opening is idempotent.  d_counts (NULL, or the 8 uint64 of oip_mask_cells_u16): [5] += CLOUD cells, [6] += BUFFER cells.
+ * Scratch (3 bits per cell) comes from the context's grow-only workspace.  OIP_E_INVALID: a radius out of range, gw < 0,
+ * gh < 0, flag_pitch < gw.  An empty grid is a no-op.  Asynchronous on the context's stream. */
+int oip_mask_morph_u8(oip_ctx *ctx, uint8_t *d_flags, long flag_pitch, int gw, long gh, int open_radius, int buffer_radius,
+                      uint64_t *d_counts);
+
+/* gw = ceil(w / cell), gh = ceil(h / cell).  Host, no context needed.  OIP_E_INVALID: cell not 4, 8 or 16, w < 0, h < 0. */
+int oip_mask_grid(int w, long h, int cell, int *gw, long *gh);
+
+/* 1 if any cell of the gw x gh grid (host bytes, lines flag_pitch apart) that intersects the pixel rectangle [x, x + tw) x
+ * [y, y + th) has a bit of `bits` set, else 0: the part of the rectangle outside the grid holds no cell, and neither does an
+ * empty rectangle.  Host, no context needed.  What `oip regcheck --mask` asks per tile. */
+int oip_mask_tile_flag(const uint8_t *flags, long flag_pitch, int gw, long gh, int cell, long x, long y, long tw, long th, int bits);
+
 /* ---- mtf: the MTF at Nyquist from the straight edges of a strip or product (`oip mtf`; not in the reference) --------
  * The slanted-edge method (ISO 12233) on every 32 x 32 tile that holds one straight, high-contrast, slightly slanted edge.
  * What `oip mtfc --mtf REPORT` takes its two numbers from.  The device part is exact integers: any launch geometry and any
@@ -902,6 +966,7 @@ int oip_overview_levels(int w, long h);
 #define OIP_MATCH_FLAT   2      /* no offset has a score */
 #define OIP_MATCH_EDGE   4      /* |dy| = S or |dx| = S at the peak */
 #define OIP_MATCH_WEAK   8      /* score < min_score */
+#define OIP_MATCH_MASKED 16     /* `oip regcheck --mask`: the template's footprint touches a masked cell (oip_mask_tile_flag); OR-ed in on the host */
 #define OIP_REGCHECK_SUFFIX ".REG"
 int oip_match_tiles_u16(oip_ctx *ctx, const uint16_t *d_a, long pitch_a, int stride_a, const uint16_t *d_b, long pitch_b,
                         int stride_b, int w, long rows, int T, int S, int x0, long y0, int step_x, long step_y, int nx, long ny,

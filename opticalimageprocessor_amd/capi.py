@@ -142,6 +142,10 @@ _SIGS = {
     "oip_noise_despike_threshold": ([_d, _d, _d, _d, C.POINTER(_i), C.POINTER(_i), _cp, _i], _i),
     "oip_sigma_filter_u16": ([_vp, _vp, _l, _l, _vp, _l, _l, _i, _l, _i, _i, _vp, _i, _i, _vp], _i),
     "oip_denoise_thresholds": ([_d, _d, _d, C.POINTER(C.c_uint16), _cp, _i], _i),
+    "oip_mask_cells_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _i, _i, _i, C.POINTER(_i), _i, _i, _i, _i, _vp, _l, _vp], _i),
+    "oip_mask_morph_u8": ([_vp, _vp, _l, _i, _l, _i, _i, _vp], _i),
+    "oip_mask_grid": ([_i, _l, _i, C.POINTER(_i), _lp], _i),
+    "oip_mask_tile_flag": ([C.POINTER(C.c_uint8), _l, _i, _l, _i, _l, _l, _l, _l, _i], _i),
     "oip_mtf_tiles_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _i, _i, _i, _i, _vp, _l, _sz], _i),
     "oip_mtf_esf_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp], _i),
     "oip_mtf_tile": ([_i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _dp], _i),
@@ -298,6 +302,31 @@ def despike_column_table(bad, w: int, groups: int = 1):
     if rc:
         raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
     return tab, run.value
+
+
+MASK_NODATA, MASK_SATURATED, MASK_CLOUD, MASK_BUFFER, MASK_CANDIDATE = 1, 2, 4, 8, 16
+MASK_COUNTERS = ("cells", "nodata_cells", "saturated_cells", "tested_cells", "candidate_cells", "cloud_cells", "buffer_cells",
+                 "saturated_pixels")
+
+
+def mask_grid(w: int, h: int, cell: int):
+    """(gw, gh) = (ceil(w / cell), ceil(h / cell)) of the mask of a w x h raster (include/oip_c.h: oip_mask_grid)"""
+    gw, gh = _i(), _l()
+    if load_library().oip_mask_grid(w, h, cell, C.byref(gw), C.byref(gh)):
+        raise ValueError("oip_mask_grid: cell 4, 8 or 16 and w, h >= 0 expected")
+    return gw.value, gh.value
+
+
+def mask_tile_flag(flags, cell: int, x: int, y: int, tw: int, th: int, bits: int = MASK_CLOUD | MASK_BUFFER) -> bool:
+    """whether a cell of the (gh, gw) uint8 mask that intersects the pixel rectangle [x, x + tw) x [y, y + th) has a bit of
+    `bits` set (include/oip_c.h: oip_mask_tile_flag)"""
+    f = np.asarray(flags)
+    if f.dtype != np.uint8 or f.ndim != 2 or (f.size and f.strides[1] != 1) or f.strides[0] < f.shape[1]:
+        f = np.ascontiguousarray(flags, dtype=np.uint8)
+        if f.ndim != 2:
+            raise ValueError("mask_tile_flag: a (gh, gw) uint8 mask expected")
+    pitch = f.strides[0] if f.shape[0] > 1 else max(f.shape[1], 1)
+    return bool(load_library().oip_mask_tile_flag(f.ctypes.data_as(C.POINTER(C.c_uint8)), pitch, f.shape[1], f.shape[0], cell, x, y, tw, th, bits))
 
 
 def noise_levels(hist, min_blocks: int = 100):
@@ -1115,6 +1144,22 @@ class Context:
         apart) into spp planes of key lines key_pitch keys apart (include/oip_c.h: oip_noise_blocks_u16)"""
         self._ck(self.lib.oip_noise_blocks_u16(self.h, _ptr(src), pitch, w, rows, spp, block, level_shift, valid_min, valid_max, _ptr(keys),
                                                key_pitch, key_plane_stride))
+
+    # -- mask
+    def mask_cells_u16(self, src, pitch, w, rows, spp, cell, flags, flag_pitch, counts=None, valid_min=1, sat_level=4095, full_scale=4095,
+                       band=(2, 1, 0, 3), bright_q8=77, white_q8=38, hot_q8=20, ndvi_q8=51):
+        """one flag byte (NODATA 1, SATURATED 2, CANDIDATE 16) per cell x cell cell of rows lines of w pixels of spp samples
+        (lines `pitch` samples apart) into flag lines flag_pitch bytes apart; band: the channel of (blue, green, red, nir); a
+        q8 of -1 disables its test; the counters are ADDED into counts ((8,) uint64 on the device, or None)
+        (include/oip_c.h: oip_mask_cells_u16)"""
+        b = (_i * 4)(*[int(v) for v in band]) if band is not None else None
+        self._ck(self.lib.oip_mask_cells_u16(self.h, _ptr(src), pitch, w, rows, spp, cell, valid_min, sat_level, full_scale, b, bright_q8,
+                                             white_q8, hot_q8, ndvi_q8, _ptr(flags), flag_pitch, _ptr(counts)))
+
+    def mask_morph_u8(self, flags, flag_pitch, gw, gh, open_radius=1, buffer_radius=2, counts=None):
+        """CLOUD 4 = the opening of the CANDIDATE cells by open_radius, BUFFER 8 = what lies within buffer_radius of it, in
+        place on the gw x gh grid of flag bytes; counts[5], counts[6] are ADDED into (include/oip_c.h: oip_mask_morph_u8)"""
+        self._ck(self.lib.oip_mask_morph_u8(self.h, _ptr(flags), flag_pitch, gw, gh, open_radius, buffer_radius, _ptr(counts)))
 
     # -- mtf
     def mtf_tiles_u16(self, src, pitch, w, rows, spp, axis, rec, rec_pitch, rec_plane_stride=0, contrast_min=200, tv_slack=256, valid_min=1,

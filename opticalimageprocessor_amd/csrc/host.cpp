@@ -1152,3 +1152,28 @@ extern "C" int oip_mtf_tv_slack(double sigma_ref)
     const double t = std::ceil(48.0 * sigma_ref);
     return t < 65535.0 ? (int)t : 65535;
 }
+
+// ---- mask: the grid of cells and the question `oip regcheck --mask` asks per tile (include/oip_c.h) --------------------------
+extern "C" int oip_mask_grid(int w, long h, int cell, int *gw, long *gh)
+{
+    if ((cell != 4 && cell != 8 && cell != 16) || w < 0 || h < 0 || !gw || !gh) return OIP_E_INVALID;
+    *gw = (w + cell - 1) / cell;
+    *gh = (h + cell - 1) / cell;
+    return OIP_OK;
+}
+
+extern "C" int oip_mask_tile_flag(const uint8_t *flags, long flag_pitch, int gw, long gh, int cell, long x, long y, long tw, long th, int bits)
+{
+    if (!flags || (cell != 4 && cell != 8 && cell != 16) || gw < 0 || gh < 0 || flag_pitch < gw) return 0;
+    if (tw <= 0 || th <= 0) return 0;
+    // floor division: a rectangle may begin left of or above the image
+    const long x1 = x + tw - 1, y1 = y + th - 1;
+    if (x1 < 0 || y1 < 0) return 0;
+    long i0 = x < 0 ? 0 : x / cell, i1 = x1 / cell, j0 = y < 0 ? 0 : y / cell, j1 = y1 / cell;
+    if (i1 > gw - 1) i1 = gw - 1;
+    if (j1 > gh - 1) j1 = gh - 1;
+    for (long j = j0; j <= j1; ++j)
+        for (long i = i0; i <= i1; ++i)
+            if (flags[j * flag_pitch + i] & bits) return 1;
+    return 0;
+}

@@ -20,6 +20,10 @@
 //                               comes from the report of `oip noise`, see run_denoise()
 //   oip noise IMAGE [-o OUT.csv] [--block 8|16] [--bits N] [--min-blocks N] [--bil]   the noise-level function of a strip or
 //                               product (sigma per signal level, the fit sigma^2 = a + b mu, SNR) in <stem>.NOISE.CSV, see run_noise()
+//   oip mask IMAGE [-o OUT.TIFF] [--report OUT.csv] [--cell 4|8|16] [--bits N] [--saturation DN] [--bands B,G,R,N] [--open A] [--buffer D]
+//                               which parts of a strip or product are usable: no data, saturated, cloud and its buffer per cell, in
+//                               <stem>.MASK.TIFF and <stem>.MASK.CSV, see run_mask(); `regcheck --mask FILE --mask-cell C` flags the
+//                               tiles that touch a masked cell
 //   oip mtf IMAGE [-o OUT.csv] [--axis x|y|both] [--contrast-min DN] [--tv-slack DN | --noise REPORT]   the MTF at Nyquist across
 //                               and along the lines from the slanted edges of a strip or product, in <stem>.MTF.CSV, see run_mtf();
 //                               `mtfc --mtf REPORT [--mtf-stat median|p75|p90]` designs its filter from the report
@@ -39,7 +43,7 @@
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
 // --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
-// despike, denoise, noise, mtf, overviews, regcheck, regfix and pansharpen sub-commands.
+// despike, denoise, noise, mask, mtf, overviews, regcheck, regfix and pansharpen sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -142,7 +146,7 @@ Parsed parse(const Spec &sp, const std::vector<std::string> &args)
     return p;
 }
 
-// The tools with one positional argument (quicklook, mtfc, despike, denoise, noise, mtf, overviews; regcheck, regfix and pansharpen name their
+// The tools with one positional argument (quicklook, mtfc, despike, denoise, noise, mask, mtf, overviews; regcheck, regfix and pansharpen name their
 // images by options): IMAGE, an existing regular file, is the first argument that is neither an option nor the value of one (an
 // option's value stays with it, alias or not); the rest is parsed as usual.
 Parsed parse_with_image(const Spec &sp, const std::vector<std::string> &args, std::string *image)
@@ -257,6 +261,19 @@ void usage()
          "             [--valid-min N] [--valid-max N] (a block with a sample outside is no data; default 1, 65535)\n"
          "             [--min-blocks N] (blocks a level needs; default 100) [--bil] (RAW: the MSS line layout, bands measured apart)\n"
          "             [--width N] [--line-offset N] (a multiple of the block) [--lines N] [--force]\n"
+         "  mask       IMAGE.TIFF|IMAGE.RAW: which parts of a product (TIFF of 1 or 4 samples) or a single-band strip are usable, one byte\n"
+         "             per C x C cell: 1 no data (a channel below --valid-min), 2 saturated (a channel at or above --saturation), and with 4\n"
+         "             samples 16 cloud candidate (bright, white, hazy, not vegetation), 4 cloud (the opening of the candidates by A\n"
+         "             cells), 8 buffer (within D cells of cloud); written to <stem>.MASK.TIFF (8-bit) with the counters and the shares\n"
+         "             nodata_pct, saturated_pct, cloud_pct, cloud_or_buffer_pct in <stem>.MASK.CSV in the working directory:\n"
+         "             [-o,--out FILE] [--report FILE] [--cell 4|8|16] (default 8) [--bits N] (8..16, full scale 2^N - 1; default 12)\n"
+         "             [--saturation DN] (default: full scale) [--valid-min N] (default 1)\n"
+         "             [--bands B,G,R,N] (1-based channels of blue, green, red, nir; default 3,2,1,4, the product's R, G, B, alpha order)\n"
+         "             [--bright F] [--white F] [--hot F] [--ndvi F] (fractions 0..1: mean of B, G, R of full scale at least F; spread of\n"
+         "             B, G, R at most F of their mean; blue - red / 2 at least F of full scale; NDVI at most F; defaults 0.30, 0.15,\n"
+         "             0.08, 0.20: conventions for top-of-atmosphere-like DN, nothing was measured on real imagery)\n"
+         "             [--no-cloud] (no cloud stage) [--open A] (0..32 cells; default 1) [--buffer D] (0..64 cells; default 2)\n"
+         "             [--width N] [--force]\n"
          "  mtf        IMAGE.RAW|IMAGE.TIFF: the MTF at Nyquist across (x) and along (y) the lines, measured on the image itself by the\n"
          "             slanted-edge method: every 32 x 32 tile with one straight edge of at least --contrast-min DN that crosses 1 to 8\n"
          "             samples gives a value; band,axis,ty,tx,polarity,slope_q,contrast,mtf per tile and count, median, p75 and p90 per\n"
@@ -278,6 +295,8 @@ void usage()
          "             [--tile T] (multiple of 8, 8..128; default 64) [--search S] (1..16; default 4) [--step N] (default T)\n"
          "             [--valid-min N] [--valid-max N] (samples outside are no data; default 1, 65535) [--min-score X] (default 0.5)\n"
          "             flags: 1 no data in the tile, 2 flat, 4 peak on the border of the search range, 8 score below --min-score\n"
+         "             [--mask FILE --mask-cell C] (the mask `oip mask --cell C` wrote for A) [--mask-bits B] (default 12: cloud or\n"
+         "             buffer) flag 16: the tile's template touches a cell with a bit of B set; `regfix` leaves such tiles out\n"
          "             [--width N] [--width2 N] (RAW: samples per line of A / B) [-o,--out report.csv] [--force]\n"
          "  regfix     --report R.CSV --image B: resamples B, the image 2 of the regcheck report R.CSV (TIFF of 1 or 4 samples, or\n"
          "             single-band RAW), by the shift field the report's tiles hold, so that it lands on the report's image 1; flagged\n"
@@ -814,6 +833,53 @@ int run_noise(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip mask IMAGE: the no-data / saturation / cloud mask of a strip (.RAW, --width samples per line) or a product (.TIFF of 1 or 4
+// samples) as <stem>.MASK.TIFF and <stem>.MASK.CSV (RunMask).  IMAGE is the one positional argument, as for mtfc.  Bad values
+// end in 105 before any file is read.
+int run_mask(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--out", "--report", "--cell", "--bits", "--saturation", "--valid-min", "--bands", "--bright", "--white", "--hot", "--ndvi",
+                 "--open", "--buffer", "--width"};
+    sp.flags = {"--no-cloud", "--force"};
+    sp.alias = {{"-o", "--out"}};
+    std::string image;
+    Parsed p = parse_with_image(sp, args, &image);
+    MaskOptions o;
+    o.width = p.positive_width(width);
+    o.cell = p.integer("--cell", 8);
+    if (o.cell != 4 && o.cell != 8 && o.cell != 16) throw cli_error(105, "--cell: 4, 8 or 16 expected");
+    o.bits = p.within("--bits", 12, 8, 16, "8 <= N <= 16 expected");
+    const int full = (1 << o.bits) - 1;
+    o.saturation = p.within("--saturation", full, 1, 65535, "1 <= DN <= 65535 expected");
+    o.validMin = p.valid_min();
+    const std::string bands = p.str("--bands", "3,2,1,4");
+    {
+        int v[4] = {0, 0, 0, 0}, seen = 0;
+        char junk = 0;
+        const bool four = sscanf(bands.c_str(), "%d,%d,%d,%d%c", v, v + 1, v + 2, v + 3, &junk) == 4;
+        for (int k = 0; k < 4 && four; ++k)
+            if (v[k] >= 1 && v[k] <= 4) seen |= 1 << (v[k] - 1);
+        if (!four || seen != 15) throw cli_error(105, "--bands: B,G,R,N, a permutation of the channels 1,2,3,4, expected");
+        for (int k = 0; k < 4; ++k) o.band[k] = v[k] - 1;
+    }
+    const char *keys[4] = {"--bright", "--white", "--hot", "--ndvi"};
+    const double defs[4] = {0.30, 0.15, 0.08, 0.20};
+    for (int k = 0; k < 4; ++k) {
+        const double F = p.real(keys[k], defs[k]);
+        if (!(F >= 0.0 && F <= 1.0)) throw cli_error(105, std::string(keys[k]) + ": a fraction 0 <= F <= 1 expected");
+        o.q8[k] = MaskQ8(F);
+    }
+    o.noCloud = p.has("--no-cloud");
+    o.open = p.within("--open", 1, 0, 32, "0 <= A <= 32 expected");
+    o.buffer = p.within("--buffer", 2, 0, 64, "0 <= D <= 64 expected");
+    o.force = p.has("--force");
+    o.report = p.str("--report");
+    if ((p.has("--report") && o.report.empty()) || (p.has("--out") && p.str("--out").empty())) throw cli_error(105, "--out, --report: a file name expected");
+    RunMask(image, p.str("--out"), o);
+    return 0;
+}
+
 // oip mtf IMAGE: the MTF at Nyquist of a strip (.RAW, --width samples per line) or a product (.TIFF of 1 or 4 samples) from its
 // slanted edges, as <stem>.MTF.CSV (RunMtf).  IMAGE is the one positional argument, as for mtfc.  Bad values end in 105 before
 // any file is read.
@@ -871,13 +937,16 @@ int run_regcheck(const std::vector<std::string> &args, int width)
 {
     Spec sp;
     sp.valued = {"--image1", "--image2", "--band1", "--band2", "--scale", "--shift-x", "--shift-y", "--tile", "--search", "--step",
-                 "--valid-min", "--valid-max", "--min-score", "--width", "--width2", "--out"};
+                 "--valid-min", "--valid-max", "--min-score", "--width", "--width2", "--out", "--mask", "--mask-cell", "--mask-bits"};
     sp.flags = {"--force", "--bil"};
     sp.alias = {{"-o", "--out"}};
     Parsed p = parse(sp, args);
     require(p, "--image1");
     existing_file(p, "--image1");
     existing_file(p, "--image2");
+    existing_file(p, "--mask");
+    if (p.has("--mask") && !p.has("--mask-cell")) throw cli_error(107, "--mask requires --mask-cell");
+    if ((p.has("--mask-cell") || p.has("--mask-bits")) && !p.has("--mask")) throw cli_error(107, "--mask-cell / --mask-bits require --mask");
     if (p.has("--width2") && !p.has("--image2")) throw cli_error(107, "--width2 requires --image2");
     if ((p.has("--shift-x") || p.has("--shift-y")) && !p.has("--image2")) throw cli_error(107, "--shift-x / --shift-y require --image2");
     RegcheckOptions o;
@@ -902,10 +971,17 @@ int run_regcheck(const std::vector<std::string> &args, int width)
     if (o.width <= 0 || (p.has("--width2") && o.width2 <= 0)) throw cli_error(105, "--width/--width2: a positive line width expected");
     o.bil = p.has("--bil");
     o.force = p.has("--force");
+    o.mask = p.str("--mask");
+    if (p.has("--mask") && o.mask.empty()) throw cli_error(105, "--mask: a file name expected");
+    o.maskCell = p.integer("--mask-cell", 8);
+    if (o.maskCell != 4 && o.maskCell != 8 && o.maskCell != 16) throw cli_error(105, "--mask-cell: 4, 8 or 16 expected");
+    o.maskBits = p.within("--mask-bits", OIP_MASK_CLOUD | OIP_MASK_BUFFER, 1, 255, "1 <= B <= 255 expected");
     char buf[256];
     snprintf(buf, sizeof buf, " band1=%d band2=%d scale=%d shift-x=%ld shift-y=%ld tile=%d search=%d step=%d valid-min=%d valid-max=%d min-score=%g",
              o.band1, o.band2, o.scale, o.shiftX, o.shiftY, o.tile, o.search, o.step, o.validMin, o.validMax, o.minScore);
-    o.params = "oip regcheck image1=" + p.str("--image1") + " image2=" + (o.image2.empty() ? p.str("--image1") : o.image2) + buf +
+    // (a report without --mask is what it was before the option existed)
+    const std::string maskBits = p.has("--mask") ? " mask-bits=" + std::to_string(o.maskBits) : "";
+    o.params = "oip regcheck image1=" + p.str("--image1") + " image2=" + (o.image2.empty() ? p.str("--image1") : o.image2) + buf + maskBits +
                " columns=x,y,dx,dy,score,flags";
     RunRegcheck(p.str("--image1"), p.str("--out"), o);
     return 0;
@@ -1030,6 +1106,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "despike") return run_despike({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "denoise") return run_denoise({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "noise") return run_noise({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "mask") return run_mask({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "mtf") return run_mtf({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "overviews") return run_overviews({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regcheck") return run_regcheck({args.begin() + 1, args.end()}, width);

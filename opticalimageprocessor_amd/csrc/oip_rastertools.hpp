@@ -1,5 +1,5 @@
-// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, denoise, noise, mtf, overviews,
-// regcheck, regfix, pansharpen) above the host layer of oip_host.hpp.  Stated once for all of them: the file checks made before a
+// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, denoise, noise, mask, mtf,
+// overviews, regcheck, regfix, pansharpen) above the host layer of oip_host.hpp.  Stated once for all of them: the file checks made before a
 // device is touched (container, RAW size rule, line range, GuardOutput), the loaders of a resident image, the driver that streams
 // a RAW strip through the device in line blocks (geometry: oip_stripplan.hpp), the filter driver above it, the closing
 // throughput line and the text-report writer.  Then the tools, each as Options / Check / Run.  The ranges of option values are
@@ -9,6 +9,7 @@
 #pragma once
 
 #include "oip_host.hpp"
+#include "oip_maskreport.hpp"
 #include "oip_mtfreport.hpp"
 #include "oip_noisereport.hpp"
 #include "oip_regreport.hpp"
@@ -73,7 +74,7 @@ inline std::string FilterOutputPath(const std::string &file, const std::string &
     return path;
 }
 
-// OIP_<TOOL>_BLOCK_LINES of mtfc, despike, denoise, noise, mtf, overviews and regfix (test hooks: several blocks on a small image), rounded
+// OIP_<TOOL>_BLOCK_LINES of mtfc, despike, denoise, noise, mask, mtf, overviews and regfix (test hooks: several blocks on a small image), rounded
 // down to the multiple q of lines the tool needs and never below q; 0 without one
 inline long BlockLinesHook(const char *name, long q = 1)
 {
@@ -816,6 +817,118 @@ inline void RunNoise(const std::string &file, const std::string &out, const Nois
     OLOG("Report written to '%s'; %zu bytes in %.3f seconds (%.1f MBps).", outPath.c_str(), inBytes, es, inBytes / es / 1024.0 / 1024.0);
 }
 
+// ---- oip mask: no-data, saturation and cloud mask of a strip or product ------------------------------------------------------
+// Which parts of a product are usable.  One read-only pass gives every C x C cell a flag byte (oip_mask_cells_u16: no data,
+// saturated, and with 4 samples per pixel the cloud candidate of four spectral tests); an opening and a buffer on the grid of
+// cells (oip_mask_morph_u8) turn the candidates into CLOUD and BUFFER.  The grid goes to <stem>.MASK.TIFF (8-bit, one sample),
+// the eight counters and four shares to <stem>.MASK.CSV (oip_maskreport.hpp).  A RAW strip streams through in blocks of lines
+// that are multiples of C; a TIFF product is resident.  With one sample per pixel there is no cloud stage.  Not in the reference.
+struct MaskOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    int cell = 8, bits = 12;                // full_scale = 2^bits - 1
+    int saturation = 0;                     // 0: full_scale
+    int validMin = 1;
+    int band[4] = {2, 1, 0, 3};             // 0-based channel of blue, green, red, nir: the product's R, G, B, alpha order
+    int q8[4] = {77, 38, 20, 51};           // bright, white, hot, ndvi
+    bool noCloud = false;
+    int open = 1, buffer = 2;
+    bool force = false;
+    std::string report;                     // --report: the CSV; empty: <stem>.MASK.CSV
+};
+
+struct MaskPaths {
+    std::string tiff, csv;
+};
+
+// what is refused without a device and depends on the image (the option ranges are run_mask's): the container, the size of a
+// RAW file, the samples of a TIFF, the two outputs; returns the output paths, whether the input is a TIFF and (TIFF) its samples
+inline MaskPaths MaskCheck(const std::string &file, const std::string &out, const MaskOptions &o, bool *isTiff, int *spp)
+{
+    *isTiff = RasterContainer(file, "mask") == ".tiff";
+    *spp = 1;
+    if (*isTiff) {
+        TiffLayout lay;
+        int w = 0;
+        long h = 0;
+        read_tiff_u16(file, &w, &h, spp, nullptr, &lay);
+        if (*spp != 1 && *spp != MSS_BANDS) throw std::invalid_argument("mask: a TIFF of 1 or 4 samples per pixel expected");
+    } else {
+        RawLineCount(file, "image", (size_t)o.width * BYTES_PER_PIXEL);
+    }
+    MaskPaths p;
+    p.tiff = out.empty() ? IMO::BuildOutputFilePath(file, OIP_MASK_SUFFIX, ".TIFF") : out;
+    p.csv = o.report.empty() ? IMO::BuildOutputFilePath(file, OIP_MASK_SUFFIX, ".CSV") : o.report;
+    if (p.tiff == p.csv) throw std::invalid_argument("output file [" + p.tiff + "] is named for the mask and for the report");
+    GuardOutput(p.tiff, {file}, "mask", o.force);
+    GuardOutput(p.csv, {file}, "mask", o.force);
+    return p;
+}
+
+inline void RunMask(const std::string &file, const std::string &out, const MaskOptions &o)
+{
+    bool isTiff = false;
+    int spp = 1;
+    const MaskPaths paths = MaskCheck(file, out, o, &isTiff, &spp);
+    const int C = o.cell, full = (1 << o.bits) - 1, sat = o.saturation > 0 ? o.saturation : full;
+    const bool cloud = spp == MSS_BANDS && !o.noCloud;
+    if (spp != MSS_BANDS && !o.noCloud) OLOG("mask: one sample per pixel: the cloud tests need four and are skipped.");
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    size_t inBytes = 0;
+    DevBuf<uint8_t> flags;
+    DevBuf<uint64_t> counts(8);
+    ck(oip_memset(ctx, counts.p, 0, 8 * sizeof(uint64_t)));
+    int gw = 0, width = 0;
+    long gh = 0, height = 0;
+    auto alloc_flags = [&](int w, long h) {
+        width = w;
+        height = h;
+        if (oip_mask_grid(w, h, C, &gw, &gh) != OIP_OK || gw < 1 || gh < 1) throw std::invalid_argument("mask: the image is empty");
+        flags.alloc((size_t)gw * gh);
+    };
+    if (isTiff) {
+        ResidentImage m;
+        LoadTiffProduct(file, "mask", &m);
+        alloc_flags(m.w, m.h);
+        ck(oip_mask_cells_u16(ctx, m.buf.p, (long)m.w * m.spp, m.w, m.h, m.spp, C, o.validMin, sat, full, o.band, o.q8[0], o.q8[1], o.q8[2], o.q8[3], flags.p,
+                              gw, counts.p));
+        ck(oip_sync(ctx));                  // the image is released at the end of this block
+        inBytes = m.bytes();
+    } else {
+        // the kernel runs per line block of the strip (ReadStrip), a block being a multiple of C lines
+        const size_t lineBytes = (size_t)o.width * BYTES_PER_PIXEL;
+        const long L = RawLineCount(file, "image", lineBytes);
+        alloc_flags(o.width, L);
+        ReadStrip(file, StripPlan{0, L, L, 0, StripBlockLines(lineBytes, C, BlockLinesHook("OIP_MASK_BLOCK_LINES", C)), lineBytes},
+                  [&](const uint16_t *d, long r, long m) {
+                      ck(oip_mask_cells_u16(ctx, d, o.width, o.width, m, 1, C, o.validMin, sat, full, o.band, o.q8[0], o.q8[1], o.q8[2], o.q8[3],
+                                            flags.p + (size_t)(r / C) * gw, gw, counts.p));
+                  });
+        ck(oip_sync(ctx));
+        inBytes = (size_t)L * lineBytes;
+    }
+    if (cloud) ck(oip_mask_morph_u8(ctx, flags.p, gw, gw, gh, o.open, o.buffer, counts.p));
+    std::vector<uint8_t> host((size_t)gw * gh);
+    uint64_t n[8];
+    flags.download(host.data(), host.size());
+    counts.download(n, 8);
+    ck(oip_sync(ctx));
+    if (spp == MSS_BANDS && o.noCloud) {    // --no-cloud on four samples: the candidates are dropped, nothing was opened
+        for (uint8_t &b : host) b &= (uint8_t)(OIP_MASK_NODATA | OIP_MASK_SATURATED);
+        n[3] = n[4] = 0;
+    }
+    OLOG("Write mask (%d x %ld cells of %d x %d) to file '%s' ...", gw, gh, C, C, paths.tiff.c_str());
+    write_tiff_u8(paths.tiff, host.data(), gw, gh, 1);
+    // (without a cloud stage the report says so: the four tests disabled, no opening, no buffer)
+    const int off[4] = {-1, -1, -1, -1};
+    const std::string params = MaskParamsLine(file, C, width, height, o.bits, sat, o.validMin, o.band, cloud ? o.q8 : off, cloud ? o.open : 0, cloud ? o.buffer : 0);
+    WriteTextFile(paths.csv, [&](FILE *f) { return WriteMaskReport(f, params, n); });
+    OLOG("mask: %s", MaskSummaryLine(n).c_str());
+    OLOG("Report written to '%s'.", paths.csv.c_str());
+    LogThroughput(inBytes, total.tick());
+}
+
 // ---- oip mtf: the MTF at Nyquist from the edges of a strip or product -------------------------------------------------------
 // The measuring side of mtfc's --mtf-x / --mtf-y.  Per line block, axis and band: every 32 x 32 tile gets a record
 // (oip_mtf_tiles_u16), the status-0 tiles are listed in (channel, ty, tx) order and binned into edge-spread functions
@@ -1045,12 +1158,23 @@ struct RegcheckOptions {
     int width = OIP_PIXELS_PER_LINE, width2 = 0;      // RAW inputs: samples per line (width2 0: width)
     bool bil = false;                       // refused: BIL RAW is left out on purpose
     bool force = false;
+    std::string mask;                       // --mask: the mask of image 1 (`oip mask`); empty: none
+    int maskCell = 8, maskBits = OIP_MASK_CLOUD | OIP_MASK_BUFFER;
     std::string params;                     // the first line of the report
 };
 
+// the mask of `regcheck --mask` on the host
+struct RegcheckMask {
+    std::vector<uint8_t> flags;
+    int gw = 0;
+    long gh = 0;
+};
+
 // what is refused without a device and depends on the images (the option ranges are run_regcheck's): the containers, --bil, a
-// band index beyond the container's bands, the sizes of RAW files, the output; returns the output path
-inline std::string RegcheckCheck(const std::string &file, const std::string &out, const RegcheckOptions &o, bool *isTiff1, bool *isTiff2)
+// band index beyond the container's bands, the sizes of RAW files, a mask that is not what `oip mask` writes, the output;
+// returns the output path, and the mask if one is named
+inline std::string RegcheckCheck(const std::string &file, const std::string &out, const RegcheckOptions &o, bool *isTiff1, bool *isTiff2,
+                                 RegcheckMask *mask)
 {
     const std::string file2 = o.image2.empty() ? file : o.image2;
     *isTiff1 = RasterContainer(file, "regcheck") == ".tiff";
@@ -1064,15 +1188,21 @@ inline std::string RegcheckCheck(const std::string &file, const std::string &out
     }
     if (!*isTiff1) RawLineCount(file, "image1", (size_t)o.width * BYTES_PER_PIXEL);
     if (!*isTiff2) RawLineCount(file2, "image2", (size_t)(o.width2 > 0 ? o.width2 : o.width) * BYTES_PER_PIXEL);
+    std::vector<std::string> inputs = {file, file2};
+    if (!o.mask.empty()) {
+        read_tiff_u8(o.mask, &mask->gw, &mask->gh, &mask->flags);
+        inputs.push_back(o.mask);
+    }
     const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_REGCHECK_SUFFIX, ".CSV") : out;
-    GuardOutput(path, {file, file2}, "regcheck", o.force);
+    GuardOutput(path, inputs, "regcheck", o.force);
     return path;
 }
 
 inline void RunRegcheck(const std::string &file, const std::string &out, const RegcheckOptions &o)
 {
     bool isTiff[2] = {false, false};
-    const std::string outPath = RegcheckCheck(file, out, o, &isTiff[0], &isTiff[1]);
+    RegcheckMask mask;
+    const std::string outPath = RegcheckCheck(file, out, o, &isTiff[0], &isTiff[1], &mask);
     const std::string file2 = o.image2.empty() ? file : o.image2;
     oip_ctx *ctx = Device::get().ctx();
     auto ck = [](int rc) { Device::get().check(rc); };
@@ -1083,6 +1213,16 @@ inline void RunRegcheck(const std::string &file, const std::string &out, const R
     };
     LoadResident(file, isTiff[0], o.width, "image1", "regcheck", &img[0]);
     bandWithin("--band1", o.band1, img[0]);
+    RegMask rm;
+    if (!o.mask.empty()) {                  // the mask is image 1's: its grid is that of image 1's pixels
+        int gw = 0;
+        long gh = 0;
+        if (oip_mask_grid(img[0].w, img[0].h, o.maskCell, &gw, &gh) != OIP_OK || gw != mask.gw || gh != mask.gh)
+            throw std::invalid_argument("regcheck: the mask [" + o.mask + "] is " + std::to_string(mask.gw) + " x " + std::to_string(mask.gh) + " cells, image 1 (" +
+                                        std::to_string(img[0].w) + " x " + std::to_string(img[0].h) + " pixels) has " + std::to_string(gw) + " x " +
+                                        std::to_string(gh) + " cells of " + std::to_string(o.maskCell));
+        rm.flags = mask.flags.data(); rm.gw = mask.gw; rm.gh = mask.gh; rm.cell = o.maskCell; rm.bits = o.maskBits;
+    }
     const bool shared = o.image2.empty() || std::filesystem::equivalent(file, file2);          // one file: read once
     if (!shared) LoadResident(file2, isTiff[1], o.width2 > 0 ? o.width2 : o.width, "image2", "regcheck", &img[1]);
     const ResidentImage &m2 = shared ? img[0] : img[1];
@@ -1125,7 +1265,7 @@ inline void RunRegcheck(const std::string &file, const std::string &out, const R
     ck(oip_sync(ctx));
     OLOG("Matched in %.3f seconds.", sw.tick());
     RegSummary sum;
-    WriteTextFile(outPath, [&](FILE *f) { return WriteRegReport(f, o.params, rec.data(), g, o.minScore, &sum); });
+    WriteTextFile(outPath, [&](FILE *f) { return WriteRegReport(f, o.params, rec.data(), g, o.minScore, &sum, o.mask.empty() ? nullptr : &rm); });
     OLOG("regcheck: %s", RegSummaryLine(sum).c_str());
     OLOG("Report written to '%s' in %.3f seconds.", outPath.c_str(), total.tick());
 }

@@ -33,8 +33,17 @@ struct RegGrid {
     long y0 = 0, ny = 0, originX = 0, originY = 0;
 };
 
+// the mask of image 1 that `oip regcheck --mask` hands in: gw x gh bytes of `oip mask` with cells of `cell` pixels; a tile
+// whose template footprint touches a cell with a bit of `bits` set gets OIP_MATCH_MASKED
+struct RegMask {
+    const uint8_t *flags = nullptr;
+    int gw = 0, cell = 8, bits = OIP_MASK_CLOUD | OIP_MASK_BUFFER;
+    long gh = 0;
+};
+
 struct RegSummary {
     long tiles = 0, nodata = 0, flat = 0, edge = 0, weak = 0;
+    long masked = -1;                           // -1: no mask was given, and the summary line does not speak of one
     double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // oip_match_summary: count, mean dx, mean dy, std dx, std dy, rms, ce90, max
 };
 
@@ -42,20 +51,25 @@ struct RegSummary {
 inline std::string RegSummaryLine(const RegSummary &r)
 {
     char buf[512];
-    snprintf(buf, sizeof buf, "tiles %ld, used %.0f (nodata %ld, flat %ld, edge %ld, weak %ld): mean dx %.4f dy %.4f, std dx %.4f dy %.4f, rms %.4f, ce90 %.4f, max %.4f",
-             r.tiles, r.s[0], r.nodata, r.flat, r.edge, r.weak, r.s[1], r.s[2], r.s[3], r.s[4], r.s[5], r.s[6], r.s[7]);
+    const std::string masked = r.masked >= 0 ? ", masked " + std::to_string(r.masked) : "";
+    snprintf(buf, sizeof buf, "tiles %ld, used %.0f (nodata %ld, flat %ld, edge %ld, weak %ld%s): mean dx %.4f dy %.4f, std dx %.4f dy %.4f, rms %.4f, ce90 %.4f, max %.4f",
+             r.tiles, r.s[0], r.nodata, r.flat, r.edge, r.weak, masked.c_str(), r.s[1], r.s[2], r.s[3], r.s[4], r.s[5], r.s[6], r.s[7]);
     return buf;
 }
 
 // `# params`, one `x,y,dx,dy,score,flags` line per tile (row-major), then the summary as `#` lines.  records: nx * ny records of
-// OIP_MATCH_RECORD_WORDS words.  Returns false where a record is refused by oip_match_peak or the file cannot be written.
-inline bool WriteRegReport(FILE *f, const std::string &params, const uint64_t *records, const RegGrid &g, double minScore, RegSummary *sum)
+// OIP_MATCH_RECORD_WORDS words.  mask (may be NULL): a tile whose template footprint in image-1 pixels, [x, x + T scale) x
+// [y, y + T scale), touches a masked cell gets OIP_MATCH_MASKED on top of what oip_match_peak gave it.  Returns false where a
+// record is refused by oip_match_peak or the file cannot be written.
+inline bool WriteRegReport(FILE *f, const std::string &params, const uint64_t *records, const RegGrid &g, double minScore, RegSummary *sum,
+                           const RegMask *mask = nullptr)
 {
     const long n = (long)g.nx * g.ny;
     std::vector<double> dx((size_t)n), dy((size_t)n);
     std::vector<int> flags((size_t)n);
     RegSummary r;
     r.tiles = n;
+    if (mask) r.masked = 0;
     if (fprintf(f, "# %s\n", params.c_str()) < 0) return false;
     for (long j = 0; j < g.ny; ++j)
         for (int i = 0; i < g.nx; ++i) {
@@ -66,6 +80,13 @@ inline bool WriteRegReport(FILE *f, const std::string &params, const uint64_t *r
             r.flat += (flags[t] & OIP_MATCH_FLAT) != 0;
             r.edge += (flags[t] & OIP_MATCH_EDGE) != 0;
             r.weak += (flags[t] & OIP_MATCH_WEAK) != 0;
+            if (mask) {
+                const long fx = (g.originX + g.x0 + (long)i * g.step) * g.scale, fy = (g.originY + g.y0 + j * g.step) * g.scale, side = (long)g.T * g.scale;
+                if (oip_mask_tile_flag(mask->flags, mask->gw, mask->gw, mask->gh, mask->cell, fx, fy, side, side, mask->bits)) {
+                    flags[t] |= OIP_MATCH_MASKED;
+                    ++r.masked;
+                }
+            }
             const long x = (g.originX + g.x0 + (long)i * g.step + g.T / 2) * g.scale, y = (g.originY + g.y0 + j * g.step + g.T / 2) * g.scale;
             if (fprintf(f, "%ld,%ld,%.4f,%.4f,%.6f,%d\n", x, y, dx[t], dy[t], sc, flags[t]) < 0) return false;
         }

@@ -834,4 +834,85 @@ inline void write_tiff_u8(const std::string &path, const uint8_t *data, int widt
     if (fclose(f) != 0 || !ok) throw std::runtime_error("write file [" + path + "] failed");
 }
 
+// The reader of a mask (`oip regcheck --mask`): exactly what write_tiff_u8 writes with spp 1 -- classic little-endian TIFF,
+// uncompressed, chunky, 8 bits, one sample, strips in line order -- and nothing else; what it refuses it names.  Every header
+// field is checked before it sizes an allocation or a read.
+inline void read_tiff_u8(const std::string &path, int *width, long *height, std::vector<uint8_t> *out)
+{
+    struct FileGuard {
+        FILE *f;
+        ~FileGuard() { if (f) fclose(f); }
+    } g{fopen(path.c_str(), "rb")};
+    FILE *f = g.f;
+    if (!f) throw std::runtime_error("cannot open file [" + path + "]");
+    auto fail = [&](const std::string &m) -> void { throw std::runtime_error("read 8-bit TIFF [" + path + "]: " + m); };
+    if (fseeko(f, 0, SEEK_END)) fail("seek failed");
+    const uint64_t fsize = (uint64_t)ftello(f);
+    auto rd = [&](uint64_t off, void *p, size_t n) {
+        if (off > fsize || n > fsize - off) fail("truncated file");
+        if (fseeko(f, (off_t)off, SEEK_SET) || fread(p, 1, n, f) != n) fail("truncated file");
+    };
+    unsigned char h[8];
+    rd(0, h, 8);
+    if (h[0] != 'I' || h[1] != 'I') fail("only little-endian TIFF is supported");
+    if (h[2] == 43 && h[3] == 0) fail("BigTIFF is not supported (a mask is a classic TIFF)");
+    if (h[2] != 42 || h[3] != 0) fail("not a TIFF file");
+    uint32_t ifd = 0;
+    memcpy(&ifd, h + 4, 4);
+    uint16_t n = 0;
+    rd(ifd, &n, 2);
+    if (n == 0 || n > 4096) fail("implausible directory");
+    uint64_t W = 0, H = 0, comp = 1, planar = 1, S = 1, bits = 1, rps = 0;
+    std::vector<uint64_t> offs, lens;
+    for (uint64_t i = 0; i < n; ++i) {
+        unsigned char e[12];
+        rd((uint64_t)ifd + 2 + i * 12, e, 12);
+        uint16_t id, type;
+        uint32_t cnt;
+        memcpy(&id, e, 2); memcpy(&type, e + 2, 2); memcpy(&cnt, e + 4, 4);
+        const int ts = type == 3 ? 2 : type == 4 ? 4 : 0;
+        if (!ts || cnt == 0) continue;                                          // unknown type / empty tag: not ours
+        if (cnt > fsize / (uint64_t)ts) fail("tag larger than the file");
+        std::vector<unsigned char> raw((size_t)cnt * ts);
+        if ((uint64_t)cnt * ts <= 4) memcpy(raw.data(), e + 8, (size_t)cnt * ts);
+        else { uint32_t o = 0; memcpy(&o, e + 8, 4); rd(o, raw.data(), raw.size()); }
+        auto val = [&](uint64_t k) { uint64_t v = 0; memcpy(&v, raw.data() + k * ts, ts); return v; };
+        switch (id) {
+            case 256: W = val(0); break;
+            case 257: H = val(0); break;
+            case 258: bits = val(0); for (uint64_t k = 1; k < cnt; ++k) if (val(k) != bits) fail("mixed sample depths"); break;
+            case 259: comp = val(0); break;
+            case 273: offs.resize(cnt); for (uint64_t k = 0; k < cnt; ++k) offs[k] = val(k); break;
+            case 277: S = val(0); break;
+            case 278: rps = val(0); break;
+            case 279: lens.resize(cnt); for (uint64_t k = 0; k < cnt; ++k) lens[k] = val(k); break;
+            case 284: planar = val(0); break;
+            case 322: case 323: case 324: case 325: fail("tiled TIFF is not supported (strips only)"); break;
+            default: break;
+        }
+    }
+    if (comp != TIFF_NONE) fail("compression " + std::to_string(comp) + " is not supported (a mask is uncompressed)");
+    if (bits != 8) fail(std::to_string(bits) + "-bit samples are not supported (a mask has 8)");
+    if (S != 1 || planar != 1) fail(std::to_string(S) + " samples per pixel are not supported (a mask has 1)");
+    if (!W || !H || W > 0x7FFFFFFFull || H > 0x7FFFFFFFull) fail("missing or implausible geometry");
+    if (offs.empty() || offs.size() != lens.size()) fail("missing strip tags");
+    if (H > 0xFFFFFFFFull / W) fail("implausible image size");
+    if (rps == 0 || rps > H) rps = H;
+    if (offs.size() != (H + rps - 1) / rps) fail("strip count does not match RowsPerStrip");
+    uint64_t total = 0;
+    for (size_t k = 0; k < offs.size(); ++k) {
+        if (offs[k] > fsize || lens[k] > fsize - offs[k]) fail("truncated file");
+        if (lens[k] != std::min<uint64_t>(rps, H - k * rps) * W) fail("strip sizes do not cover the image");
+        total += lens[k];
+    }
+    out->resize((size_t)total);
+    size_t pos = 0;
+    for (size_t k = 0; k < offs.size(); ++k) {
+        rd(offs[k], out->data() + pos, (size_t)lens[k]);
+        pos += (size_t)lens[k];
+    }
+    *width = (int)W;
+    *height = (long)H;
+}
+
 }  // namespace OIPGPU

@@ -168,7 +168,7 @@ inline WarpField ParseRegReport(const std::string &text, long w, long h)
         t.dx = number(tok[2], "dx");
         t.dy = number(tok[3], "dy");
         number(tok[4], "score");
-        t.flags = (int)integer(tok[5], "flags", 15);
+        t.flags = (int)integer(tok[5], "flags", 31);                // (16: OIP_MATCH_MASKED of `regcheck --mask`)
         if (t.x < 0 || t.y < 0 || t.flags < 0) throw bad("tile line `" + line.substr(0, 48) + "': a negative position or flag");
         if (t.x % scale || t.y % scale) throw bad("tile position " + std::to_string(t.x) + "," + std::to_string(t.y) + " is not a multiple of scale");
         if ((long)tiles.size() >= kWarpMaxNodes) throw bad("more than 2^27 tiles");
