@@ -809,6 +809,87 @@ int oip_mask_grid(int w, long h, int cell, int *gw, long *gh);
  * empty rectangle.  Host, no context needed.  What `oip regcheck --mask` asks per tile. */
 int oip_mask_tile_flag(const uint8_t *flags, long flag_pitch, int gw, long gh, int cell, long x, long y, long tw, long th, int bits);
 
+/* ---- wallis: local brightness and contrast equalisation of a strip or product (`oip wallis`; not in the reference) ------
+ * The Wallis filter ("dodging"): every sample gets a gain and an offset that pull the mean and the standard deviation of its
+ * neighbourhood toward a target, interpolated bilinearly between the nodes of a coarse grid of B x B blocks.  It removes the
+ * low-frequency unevenness (illumination, haze, residual vignetting) that no other step touches.  Two passes on the device
+ * (block moments; the point transform) around one host step (moments -> node gains and offsets).  Everything on the device
+ * is exact integers: any launch geometry and any cutting of a strip gives the same bytes and the same counters. */
+#define OIP_WALLIS_SUFFIX ".WAL"      /* <stem>.WAL.<ext>, <stem>.WAL.CSV */
+
+/* n, S1, S2 of every block of a u16 raster window, the read-only pass.  Raster conventions are oip_mask_cells_u16's: rows
+ * lines of w pixels of spp samples (1, or 4 pixel-interleaved), lines `pitch` SAMPLES apart, the window inside the lines of
+ * its raster; lines and offsets are 64-bit.  block B is 32, 64, 128 or 256.  Block (j, i) covers pixels [iB, min(w, iB + B)) x
+ * [jB, min(rows, jB + B)): the grid is gw = ceil(w / B) by gh = ceil(rows / B), and the blocks at the right and bottom edge hold
+ * fewer pixels.  Per block and channel c, over the samples v with valid_min <= v <= valid_max, in unsigned 64-bit integers:
+ *   n = count,   S1 = sum v,   S2 = sum v * v          (S2 <= 65536 * 65535^2 < 2^48)
+ * They are STORED, not added:  d_acc[(m * spp + c) * acc_plane_stride + j * acc_pitch + i],  m = 0, 1, 2 for n, S1, S2.
+ * A block without a valid sample stores three zeros.  A strip cut into calls at lines that are multiples of B (each call
+ * writing from block line first / B on: the caller offsets d_acc) gives the entries of one call.  No entry depends on the launch
+ * geometry.  Asynchronous on the context's stream.  OIP_E_INVALID: block not one of the four, spp not 1 or 4, w < 0, rows < 0,
+ * pitch < w * spp, acc_pitch < gw, planes that overlap (acc_plane_stride < (gh - 1) * acc_pitch + gw), valid_min > valid_max
+ * or either outside 0..65535.  w == 0 or rows == 0 is a no-op.  A pitch that is not a multiple of 8 samples, or a window that
+ * does not start on a 16-byte boundary, takes a slower kernel with the same entries. */
+int oip_block_moments_u16(oip_ctx *ctx, const uint16_t *d_src, long pitch, int w, long rows, int spp, int block, int valid_min, int valid_max,
+                          uint64_t *d_acc, long acc_pitch, size_t acc_plane_stride);
+
+/* gw = ceil(w / block), gh = ceil(h / block).  Host, no context needed.  OIP_E_INVALID: block not 32, 64, 128 or 256, w < 0,
+ * h < 0. */
+int oip_wallis_grid(int w, long h, int block, int *gw, long *gh);
+
+/* Node gains and offsets from the block moments.  Host, no context needed.  acc: a host copy of the 3 * spp planes in the
+ * layout above.  contrast c in (0, 1], brightness b in [0, 1], 0 < g_min <= 1 <= g_max <= 16.  target_mean / target_std: NULL,
+ * or spp values; NaN (or NULL) = take the image's own; a given mean lies in 0..65535, a given std is at most 65535.
+ * Every step is one correctly rounded fp64 operation in the stated order; integers below 2^53 convert exactly, the 128-bit
+ * integers D convert to the nearest double (as in oip_seam_fit).
+ *   1. Per channel the totals N, A, Q = the sums of its planes n, S1, S2 (N < 2^63).
+ *        D0 = N * Q - A * A (exact, 128-bit)    m0 = (double)A / (double)N    s0 = sqrt((double)D0) / (double)N
+ *        m_t = the given mean or m0,  s_t = the given std or s0.
+ *      OIP_E_RUNTIME, naming the channel: N < max(min_count, 2), or s_t is not > 0 (a constant channel without --std).
+ *   2. fit(n, S1, S2):   D = n * S2 - S1 * S1 (128-bit)     m = (double)S1 / (double)n     s = sqrt((double)D) / (double)n
+ *        den = c * s + (1 - c) * s_t      g = (c * s_t) / den      g = min(max(g, g_min), g_max)
+ *        o = (b * m_t + (1 - b) * m) - g * m
+ *        G = rint(g * 65536) (Q16)        O = rint(o * 256) (Q8)         |O| <= 256 * 17 * 65535 < 2^29
+ *   3. Node (j, i, c) = fit of its block.  Where n < max(min_count, 2) or D == 0 the node takes the fit of the channel's
+ *      totals (G0_c, O0_c) and substituted[...] = 1: never an error -- the black borders of prestitch and the aligner, water
+ *      and cloud produce such blocks.  With D0 == 0 (a constant channel with a given std) (G0, O0) is the identity (65536, 0).
+ * Q16 keeps a gain of 16 below 2^20 and resolves 1.5e-5, less than half a DN over the full scale; Q8 keeps the offset's
+ * rounding error at 1/512 DN while 256 * O stays below 2^37.
+ * Out: node_gain_q16 / node_offset_q8 / substituted: gh * gw * spp values each, entry [(j * gw + i) * spp + c].  report (may be
+ * NULL): 9 doubles per channel: N, m0, s0, m_t, s_t, nodes, substituted nodes, min G, max G.  With c = b = 1 this is plain
+ * normalisation of every block to (m_t, s_t); smaller c and b leave part of the local statistics in place.
+ * OIP_E_INVALID: a NULL table, spp not 1 or 4, gw < 1, gh < 1, acc_pitch < gw, planes that overlap (acc_plane_stride <
+ * (gh - 1) * acc_pitch + gw, at either spp: there are 3 * spp planes), a parameter outside its range, a channel whose A or Q does not
+ * fit 64 bits (u16 samples with N < 2^48 never get there).  err (may be NULL) receives the text. */
+int oip_wallis_fit(const uint64_t *acc, long acc_pitch, size_t acc_plane_stride, int gw, long gh, int spp, double contrast, double brightness,
+                   double g_min, double g_max, uint64_t min_count, const double *target_mean, const double *target_std, int32_t *node_gain_q16,
+                   int32_t *node_offset_q8, int *substituted, double *report, char *err, int errlen);
+
+/* The point transform, the read-write pass.  The raster is W pixels x L lines of spp samples, lines W * spp samples apart;
+ * d_src holds the global lines [row0, row0 + rows) and d_dst receives the same lines.  The transform is pointwise: any cut of a
+ * strip gives the bytes of one call, and d_dst == d_src is allowed (no other overlap is).  d_gain_q16 / d_offset_q8: the
+ * gh * gw * spp node values of oip_wallis_fit on the device, gains in 0..2^20 and |offset| < 2^29 (values outside are not
+ * checked and give unspecified samples, never an access outside the rasters).  Node (j, i) sits at line jB + B/2, column
+ * iB + B/2.  For either table V (G or O) and channel c, in signed 64-bit integers, floors toward minus infinity (B is a power
+ * of two: every division is an arithmetic shift), as in oip_seam_line_tables:
+ *   along the strip:  u = y - B/2,  k = clamp(floor(u / B), 0, max(gh - 2, 0)),  t = clamp(u - k B, 0, B),  k' = min(k + 1, gh - 1)
+ *                     Vy(i) = floor((V[k][i] * (B - t) + V[k'][i] * t + B/2) / B)
+ *   across the line:  the same formula on Vy with x and gw  ->  G(y, x, c), O(y, x, c)
+ *   v = src[y][x][c]
+ *   v < valid_min or v > valid_max:   out = v                                  (no data and saturation pass through)
+ *   otherwise:                        out = clamp((G * v + 256 * O + 32768) >> 16, valid_min, clamp_max)
+ * The tables are constant before the first node and after the last, in both axes; a value never leaves the interval of its
+ * nodes.  G * v < 2^36, 256 * |O| < 2^37.  Nodes that all hold (65536, 0) give the input's bytes (with clamp_max >= valid_max);
+ * nodes that all hold one (G, O) give the plain per-sample transform.
+ * d_stats: NULL, or 3 uint64 in HBM that are ADDED into: [0] transformed samples, [1] samples clamped at valid_min, [2] samples
+ * clamped at clamp_max.  The counters are exact and independent of the launch geometry and of the cut.
+ * OIP_E_INVALID: block, spp or the valid range as for oip_block_moments_u16, clamp_max outside valid_min..65535, W < 1, L < 1,
+ * gw != ceil(W / B) or gh != ceil(L / B), lines outside [0, L).  rows == 0 is a no-op.  A line that is not a multiple of 8
+ * samples, or bases that are not on 16-byte boundaries, take a slower kernel with the same result.  Asynchronous. */
+int oip_wallis_apply_u16(oip_ctx *ctx, const uint16_t *d_src, uint16_t *d_dst, long row0, long rows, int W, long L, int spp, int block,
+                         const int32_t *d_gain_q16, const int32_t *d_offset_q8, int gw, long gh, int valid_min, int valid_max, int clamp_max,
+                         uint64_t *d_stats);
+
 /* ---- mtf: the MTF at Nyquist from the straight edges of a strip or product (`oip mtf`; not in the reference) --------
  * The slanted-edge method (ISO 12233) on every 32 x 32 tile that holds one straight, high-contrast, slightly slanted edge.
  * What `oip mtfc --mtf REPORT` takes its two numbers from.  The device part is exact integers: any launch geometry and any

@@ -146,6 +146,11 @@ _SIGS = {
     "oip_mask_morph_u8": ([_vp, _vp, _l, _i, _l, _i, _i, _vp], _i),
     "oip_mask_grid": ([_i, _l, _i, C.POINTER(_i), _lp], _i),
     "oip_mask_tile_flag": ([C.POINTER(C.c_uint8), _l, _i, _l, _i, _l, _l, _l, _l, _i], _i),
+    "oip_block_moments_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _i, _i, _vp, _l, _sz], _i),
+    "oip_wallis_grid": ([_i, _l, _i, C.POINTER(_i), _lp], _i),
+    "oip_wallis_fit": ([C.POINTER(C.c_uint64), _l, _sz, _i, _l, _i, _d, _d, _d, _d, C.c_uint64, _dp, _dp, C.POINTER(C.c_int32),
+                        C.POINTER(C.c_int32), C.POINTER(_i), _dp, _cp, _i], _i),
+    "oip_wallis_apply_u16": ([_vp, _vp, _vp, _l, _l, _i, _l, _i, _i, _vp, _vp, _i, _l, _i, _i, _i, _vp], _i),
     "oip_mtf_tiles_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _i, _i, _i, _i, _vp, _l, _sz], _i),
     "oip_mtf_esf_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp], _i),
     "oip_mtf_tile": ([_i, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _dp], _i),
@@ -327,6 +332,41 @@ def mask_tile_flag(flags, cell: int, x: int, y: int, tw: int, th: int, bits: int
             raise ValueError("mask_tile_flag: a (gh, gw) uint8 mask expected")
     pitch = f.strides[0] if f.shape[0] > 1 else max(f.shape[1], 1)
     return bool(load_library().oip_mask_tile_flag(f.ctypes.data_as(C.POINTER(C.c_uint8)), pitch, f.shape[1], f.shape[0], cell, x, y, tw, th, bits))
+
+
+WALLIS_REPORT = ("samples", "mean", "std", "target_mean", "target_std", "nodes", "substituted_nodes", "min_gain_q16", "max_gain_q16")
+
+
+def wallis_grid(w: int, h: int, block: int):
+    """(gw, gh) = (ceil(w / block), ceil(h / block)) of the Wallis nodes of a w x h raster (include/oip_c.h: oip_wallis_grid)"""
+    gw, gh = _i(), _l()
+    if load_library().oip_wallis_grid(w, h, block, C.byref(gw), C.byref(gh)):
+        raise ValueError("oip_wallis_grid: block 32, 64, 128 or 256 and w, h >= 0 expected")
+    return gw.value, gh.value
+
+
+def wallis_fit(acc, contrast: float = 0.8, brightness: float = 0.6, g_min: float = 0.25, g_max: float = 4.0, min_count: int = 0,
+               target_mean=None, target_std=None):
+    """node gains and offsets from the (3, spp, gh, gw) uint64 block moments of Context.block_moments_u16
+    (include/oip_c.h: oip_wallis_fit).  target_mean / target_std: None, or spp values with NaN for the image's own.  Returns
+    (gain_q16 (gh, gw, spp) int32, offset_q8 (gh, gw, spp) int32, substituted (gh, gw, spp) int32, report (spp, 9))."""
+    a = np.ascontiguousarray(acc, dtype=np.uint64)
+    if a.ndim != 4 or a.shape[0] != 3:
+        raise ValueError("wallis_fit: (3, spp, gh, gw) moments expected")
+    spp, gh, gw = a.shape[1:]
+    i32 = C.POINTER(C.c_int32)
+    gain, offset, sub = (np.zeros((gh, gw, spp), np.int32) for _ in range(3))
+    report = np.zeros((spp, 9))
+    tm = None if target_mean is None else _dbl(target_mean, spp)
+    ts = None if target_std is None else _dbl(target_std, spp)
+    err = C.create_string_buffer(1024)
+    rc = load_library().oip_wallis_fit(a.ctypes.data_as(C.POINTER(C.c_uint64)), gw, gh * gw, gw, gh, spp, contrast, brightness, g_min, g_max,
+                                       min_count, None if tm is None else tm.ctypes.data_as(_dp), None if ts is None else ts.ctypes.data_as(_dp),
+                                       gain.ctypes.data_as(i32), offset.ctypes.data_as(i32), sub.ctypes.data_as(C.POINTER(_i)),
+                                       report.ctypes.data_as(_dp), err, 1024)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    return gain, offset, sub, report
 
 
 def noise_levels(hist, min_blocks: int = 100):
@@ -1160,6 +1200,22 @@ class Context:
         """CLOUD 4 = the opening of the CANDIDATE cells by open_radius, BUFFER 8 = what lies within buffer_radius of it, in
         place on the gw x gh grid of flag bytes; counts[5], counts[6] are ADDED into (include/oip_c.h: oip_mask_morph_u8)"""
         self._ck(self.lib.oip_mask_morph_u8(self.h, _ptr(flags), flag_pitch, gw, gh, open_radius, buffer_radius, _ptr(counts)))
+
+    # -- wallis
+    def block_moments_u16(self, src, pitch, w, rows, spp, block, acc, acc_pitch, acc_plane_stride, valid_min=1, valid_max=65535):
+        """n, S1, S2 of every block x block block and channel of rows lines of w pixels of spp samples (lines `pitch` samples
+        apart), STORED into the 3 * spp uint64 planes of acc: entry [(m * spp + c) * acc_plane_stride + j * acc_pitch + i]
+        (include/oip_c.h: oip_block_moments_u16)"""
+        self._ck(self.lib.oip_block_moments_u16(self.h, _ptr(src), pitch, w, rows, spp, block, valid_min, valid_max, _ptr(acc), acc_pitch,
+                                                acc_plane_stride))
+
+    def wallis_apply_u16(self, src, dst, row0, rows, W, L, spp, block, gain_q16, offset_q8, gw, gh, valid_min=1, valid_max=65535, clamp_max=65535,
+                         stats=None):
+        """the lines [row0, row0 + rows) of a W x L x spp raster through out = clamp((G v + 256 O + 32768) >> 16), G and O
+        interpolated between the (gh, gw, spp) int32 nodes on the device; dst may be src; the three counters are ADDED into
+        stats ((3,) uint64 on the device, or None) (include/oip_c.h: oip_wallis_apply_u16)"""
+        self._ck(self.lib.oip_wallis_apply_u16(self.h, _ptr(src), _ptr(dst), row0, rows, W, L, spp, block, _ptr(gain_q16), _ptr(offset_q8), gw, gh,
+                                               valid_min, valid_max, clamp_max, _ptr(stats)))
 
     # -- mtf
     def mtf_tiles_u16(self, src, pitch, w, rows, spp, axis, rec, rec_pitch, rec_plane_stride=0, contrast_min=200, tv_slack=256, valid_min=1,

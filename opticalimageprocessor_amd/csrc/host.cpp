@@ -1177,3 +1177,116 @@ extern "C" int oip_mask_tile_flag(const uint8_t *flags, long flag_pitch, int gw,
             if (flags[j * flag_pitch + i] & bits) return 1;
     return 0;
 }
+
+// ---- wallis: the grid of blocks and the step from block moments to node gains and offsets (include/oip_c.h) ------------------
+extern "C" int oip_wallis_grid(int w, long h, int block, int *gw, long *gh)
+{
+    if ((block != 32 && block != 64 && block != 128 && block != 256) || w < 0 || h < 0 || !gw || !gh) return OIP_E_INVALID;
+    *gw = (w + block - 1) / block;
+    *gh = (h + block - 1) / block;
+    return OIP_OK;
+}
+
+namespace {
+struct WallisFit {
+    double c, b, gmin, gmax, mt, st;
+    uint64_t need;
+};
+// fit(n, S1, S2) of include/oip_c.h: false where the block has too few samples or no variance.  tests/_wallis_ref.py restates
+// the operation order.
+bool wallis_fit_one(const WallisFit &f, uint64_t n, uint64_t S1, uint64_t S2, int32_t *G, int32_t *O)
+{
+    if (n < f.need) return false;
+    const unsigned __int128 a = (unsigned __int128)n * S2, q = (unsigned __int128)S1 * S1;
+    if (a <= q) return false;                // (a D below zero cannot come from real moments; it is treated as 0)
+    const unsigned __int128 D = a - q;
+    const double nd = (double)n;
+    const double m = (double)S1 / nd;
+    const double r = std::sqrt((double)D);
+    const double s = r / nd;
+    const double t1 = f.c * s;
+    const double u = 1.0 - f.c;
+    const double t2 = u * f.st;
+    const double den = t1 + t2;
+    const double num = f.c * f.st;
+    double g = num / den;
+    g = g < f.gmin ? f.gmin : g;
+    g = g > f.gmax ? f.gmax : g;
+    const double p1 = f.b * f.mt;
+    const double v = 1.0 - f.b;
+    const double p2 = v * m;
+    const double p = p1 + p2;
+    const double gm = g * m;
+    const double o = p - gm;
+    *G = (int32_t)std::rint(g * 65536.0);
+    *O = (int32_t)std::rint(o * 256.0);
+    return true;
+}
+}  // namespace
+
+extern "C" int oip_wallis_fit(const uint64_t *acc, long acc_pitch, size_t acc_plane_stride, int gw, long gh, int spp, double contrast, double brightness,
+                              double g_min, double g_max, uint64_t min_count, const double *target_mean, const double *target_std,
+                              int32_t *node_gain_q16, int32_t *node_offset_q8, int *substituted, double *report, char *err, int errlen)
+{
+    auto fail = [&](int code, const char *fmt, auto... a) {
+        if (err && errlen > 0) snprintf(err, errlen, fmt, a...);
+        return code;
+    };
+    bool ok = acc && node_gain_q16 && node_offset_q8 && substituted && (spp == 1 || spp == 4) && gw >= 1 && gh >= 1 && acc_pitch >= gw &&
+              contrast > 0.0 && contrast <= 1.0 && brightness >= 0.0 && brightness <= 1.0 && g_min > 0.0 && g_min <= 1.0 && g_max >= 1.0 && g_max <= 16.0;
+    if (ok && acc_plane_stride < (size_t)((gh - 1) * acc_pitch + gw)) ok = false;              // the 3 * spp planes overlap
+    for (int c = 0; ok && c < spp; ++c) {
+        if (target_mean && !std::isnan(target_mean[c]) && !(target_mean[c] >= 0.0 && target_mean[c] <= 65535.0)) ok = false;
+        if (target_std && !std::isnan(target_std[c]) && !(target_std[c] <= 65535.0)) ok = false;
+    }
+    if (!ok) return fail(OIP_E_INVALID, "%s", "oip_wallis_fit: bad argument");
+    const uint64_t need = min_count > 2u ? min_count : 2u;
+    for (int c = 0; c < spp; ++c) {
+        const uint64_t *pn = acc + (size_t)(0 * spp + c) * acc_plane_stride, *p1 = acc + (size_t)(1 * spp + c) * acc_plane_stride,
+                       *p2 = acc + (size_t)(2 * spp + c) * acc_plane_stride;
+        uint64_t N = 0;
+        unsigned __int128 A128 = 0, Q = 0;
+        for (long j = 0; j < gh; ++j)
+            for (int i = 0; i < gw; ++i) {
+                N += pn[j * acc_pitch + i];
+                A128 += p1[j * acc_pitch + i];
+                Q += p2[j * acc_pitch + i];
+            }
+        if (N < need) return fail(OIP_E_RUNTIME, "oip_wallis_fit: channel %d: %llu valid samples, %llu needed", c, (unsigned long long)N, (unsigned long long)need);
+        if ((A128 >> 64) || (Q >> 64)) return fail(OIP_E_INVALID, "oip_wallis_fit: channel %d: the sum or the sum of squares does not fit 64 bits", c);
+        const uint64_t A = (uint64_t)A128;
+        const unsigned __int128 nq = (unsigned __int128)N * (uint64_t)Q, aa = (unsigned __int128)A * A;
+        const unsigned __int128 D0 = nq > aa ? nq - aa : 0;
+        const double Nd = (double)N;
+        const double m0 = (double)A / Nd;
+        const double r0 = std::sqrt((double)D0);
+        const double s0 = r0 / Nd;
+        WallisFit f;
+        f.c = contrast; f.b = brightness; f.gmin = g_min; f.gmax = g_max; f.need = need;
+        f.mt = target_mean && !std::isnan(target_mean[c]) ? target_mean[c] : m0;
+        f.st = target_std && !std::isnan(target_std[c]) ? target_std[c] : s0;
+        if (!(f.st > 0.0))
+            return fail(OIP_E_RUNTIME, "oip_wallis_fit: channel %d: the target standard deviation %g is not positive (a constant channel needs --std)", c, f.st);
+        int32_t G0 = 65536, O0 = 0;
+        if (D0 != 0) wallis_fit_one(f, N, A, (uint64_t)Q, &G0, &O0);
+        long subs = 0;
+        int32_t lo = INT32_MAX, hi = INT32_MIN;
+        for (long j = 0; j < gh; ++j)
+            for (int i = 0; i < gw; ++i) {
+                const size_t e = ((size_t)j * gw + i) * spp + c;
+                int32_t G = G0, O = O0;
+                const bool own = wallis_fit_one(f, pn[j * acc_pitch + i], p1[j * acc_pitch + i], p2[j * acc_pitch + i], &G, &O);
+                if (!own) { G = G0; O = O0; ++subs; }
+                node_gain_q16[e] = G;
+                node_offset_q8[e] = O;
+                substituted[e] = own ? 0 : 1;
+                lo = G < lo ? G : lo;
+                hi = G > hi ? G : hi;
+            }
+        if (report) {
+            double *r = report + 9 * (size_t)c;
+            r[0] = Nd; r[1] = m0; r[2] = s0; r[3] = f.mt; r[4] = f.st; r[5] = (double)gh * (double)gw; r[6] = (double)subs; r[7] = (double)lo; r[8] = (double)hi;
+        }
+    }
+    return OIP_OK;
+}

@@ -24,6 +24,9 @@
 //                               which parts of a strip or product are usable: no data, saturated, cloud and its buffer per cell, in
 //                               <stem>.MASK.TIFF and <stem>.MASK.CSV, see run_mask(); `regcheck --mask FILE --mask-cell C` flags the
 //                               tiles that touch a masked cell
+//   oip wallis IMAGE [-o OUT] [--report OUT.csv] [--block 32|64|128|256] [--contrast C] [--brightness B] [--mean M] [--std S]
+//                               local brightness and contrast equalisation (the Wallis filter) of a strip or product, in
+//                               <stem>.WAL.<ext> and <stem>.WAL.CSV, see run_wallis()
 //   oip mtf IMAGE [-o OUT.csv] [--axis x|y|both] [--contrast-min DN] [--tv-slack DN | --noise REPORT]   the MTF at Nyquist across
 //                               and along the lines from the slanted edges of a strip or product, in <stem>.MTF.CSV, see run_mtf();
 //                               `mtfc --mtf REPORT [--mtf-stat median|p75|p90]` designs its filter from the report
@@ -43,7 +46,7 @@
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
 // --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
-// despike, denoise, noise, mask, mtf, overviews, regcheck, regfix and pansharpen sub-commands.
+// despike, denoise, noise, mask, wallis, mtf, overviews, regcheck, regfix and pansharpen sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -146,7 +149,7 @@ Parsed parse(const Spec &sp, const std::vector<std::string> &args)
     return p;
 }
 
-// The tools with one positional argument (quicklook, mtfc, despike, denoise, noise, mask, mtf, overviews; regcheck, regfix and pansharpen name their
+// The tools with one positional argument (quicklook, mtfc, despike, denoise, noise, mask, wallis, mtf, overviews; regcheck, regfix and pansharpen name their
 // images by options): IMAGE, an existing regular file, is the first argument that is neither an option nor the value of one (an
 // option's value stays with it, alias or not); the rest is parsed as usual.
 Parsed parse_with_image(const Spec &sp, const std::vector<std::string> &args, std::string *image)
@@ -274,6 +277,16 @@ void usage()
          "             0.08, 0.20: conventions for top-of-atmosphere-like DN, nothing was measured on real imagery)\n"
          "             [--no-cloud] (no cloud stage) [--open A] (0..32 cells; default 1) [--buffer D] (0..64 cells; default 2)\n"
          "             [--width N] [--force]\n"
+         "  wallis     IMAGE.TIFF|IMAGE.RAW: the Wallis filter (dodging) on a product (TIFF of 1 or 4 samples) or a single-band strip: every\n"
+         "             sample gets a gain and an offset that pull the mean and standard deviation of its B x B block toward the image's own\n"
+         "             (or --mean / --std), interpolated between the blocks' centres; removes uneven illumination, haze and vignetting;\n"
+         "             written to <stem>.WAL.<ext> with the figures per band and the clamp counters in <stem>.WAL.CSV:\n"
+         "             [-o,--out FILE] [--report FILE] [--block 32|64|128|256] (default 128) [--contrast C] (0 < C <= 1; default 0.8)\n"
+         "             [--brightness B] (0..1; default 0.6) [--mean M[,M,M,M]] [--std S[,S,S,S]] (targets; default: the image's own)\n"
+         "             [--min-gain G] [--max-gain G] (0 < min <= 1 <= max <= 16; default 0.25, 4) [--min-count N] (samples a block needs)\n"
+         "             [--valid-min DN] [--valid-max DN] (samples outside pass through; default 1, 65535) [--max-value DN] (results are cut\n"
+         "             there; default 65535) (the defaults are conventions, nothing was measured on real imagery)\n"
+         "             [--width N] [--line-offset N] [--lines N] (the selected lines are the raster) [--force]\n"
          "  mtf        IMAGE.RAW|IMAGE.TIFF: the MTF at Nyquist across (x) and along (y) the lines, measured on the image itself by the\n"
          "             slanted-edge method: every 32 x 32 tile with one straight edge of at least --contrast-min DN that crosses 1 to 8\n"
          "             samples gives a value; band,axis,ty,tx,polarity,slope_q,contrast,mtf per tile and count, median, p75 and p90 per\n"
@@ -880,6 +893,60 @@ int run_mask(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip wallis IMAGE: the Wallis filter on a strip (.RAW, --width samples per line) or a product (.TIFF of 1 or 4 samples), as
+// <stem>.WAL.<ext> and <stem>.WAL.CSV (RunWallis).  IMAGE is the one positional argument, as for mtfc.  Bad values end in 105
+// before any file is read.
+int run_wallis(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--out", "--report", "--block", "--contrast", "--brightness", "--mean", "--std", "--min-gain", "--max-gain", "--min-count",
+                 "--valid-min", "--valid-max", "--max-value", "--width", "--line-offset", "--lines"};
+    sp.flags = {"--force"};
+    sp.alias = {{"-o", "--out"}};
+    std::string image;
+    Parsed p = parse_with_image(sp, args, &image);
+    WallisOptions o;
+    o.width = p.positive_width(width);
+    o.block = p.integer("--block", 128);
+    if (o.block != 32 && o.block != 64 && o.block != 128 && o.block != 256) throw cli_error(105, "--block: 32, 64, 128 or 256 expected");
+    o.contrast = p.real("--contrast", 0.8);
+    if (!(o.contrast > 0.0 && o.contrast <= 1.0)) throw cli_error(105, "--contrast: 0 < C <= 1 expected");
+    o.brightness = p.real("--brightness", 0.6);
+    if (!(o.brightness >= 0.0 && o.brightness <= 1.0)) throw cli_error(105, "--brightness: 0 <= B <= 1 expected");
+    o.gMin = p.real("--min-gain", 0.25);
+    o.gMax = p.real("--max-gain", 4.0);
+    if (!(o.gMin > 0.0 && o.gMin <= 1.0 && o.gMax >= 1.0 && o.gMax <= 16.0)) throw cli_error(105, "--min-gain/--max-gain: 0 < min <= 1 <= max <= 16 expected");
+    p.valid_range(1, &o.validMin, &o.validMax);
+    o.maxValue = p.integer("--max-value", 65535);
+    if (o.maxValue < o.validMin || o.maxValue > 65535) throw cli_error(105, "--max-value: --valid-min <= DN <= 65535 expected");
+    o.minCount = p.integer("--min-count", 0);
+    p.line_range(&o.lineOffset, &o.lines, "--min-count, ", o.minCount);
+    // --mean / --std: one value for every channel or one per channel; a mean in 0..65535, a std in (0, 65535]
+    auto targets = [&](const char *key, bool positive, std::vector<double> *out) {
+        if (!p.has(key)) return;
+        const std::string s = p.str(key);
+        size_t at = 0;
+        while (at <= s.size()) {
+            const size_t comma = std::min(s.find(',', at), s.size());
+            const std::string item = s.substr(at, comma - at);
+            char *e = nullptr;
+            const double v = strtod(item.c_str(), &e);
+            if (item.empty() || !e || *e || !(v >= 0.0 && v <= 65535.0) || (positive && !(v > 0.0)))
+                throw cli_error(105, std::string(key) + (positive ? ": 0 < S <= 65535 expected, one value or one per channel" : ": 0 <= M <= 65535 expected, one value or one per channel"));
+            out->push_back(v);
+            at = comma + 1;
+        }
+        if (out->size() != 1 && out->size() != 4) throw cli_error(105, std::string(key) + ": one value, or four (one per channel) expected");
+    };
+    targets("--mean", false, &o.mean);
+    targets("--std", true, &o.std);
+    o.force = p.has("--force");
+    o.report = p.str("--report");
+    if ((p.has("--report") && o.report.empty()) || (p.has("--out") && p.str("--out").empty())) throw cli_error(105, "--out, --report: a file name expected");
+    RunWallis(image, p.str("--out"), o);
+    return 0;
+}
+
 // oip mtf IMAGE: the MTF at Nyquist of a strip (.RAW, --width samples per line) or a product (.TIFF of 1 or 4 samples) from its
 // slanted edges, as <stem>.MTF.CSV (RunMtf).  IMAGE is the one positional argument, as for mtfc.  Bad values end in 105 before
 // any file is read.
@@ -1107,6 +1174,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "denoise") return run_denoise({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "noise") return run_noise({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "mask") return run_mask({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "wallis") return run_wallis({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "mtf") return run_mtf({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "overviews") return run_overviews({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regcheck") return run_regcheck({args.begin() + 1, args.end()}, width);

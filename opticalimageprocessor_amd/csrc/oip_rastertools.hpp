@@ -1,4 +1,4 @@
-// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, denoise, noise, mask, mtf,
+// oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, denoise, noise, mask, wallis, mtf,
 // overviews, regcheck, regfix, pansharpen) above the host layer of oip_host.hpp.  Stated once for all of them: the file checks made before a
 // device is touched (container, RAW size rule, line range, GuardOutput), the loaders of a resident image, the driver that streams
 // a RAW strip through the device in line blocks (geometry: oip_stripplan.hpp), the filter driver above it, the closing
@@ -13,6 +13,7 @@
 #include "oip_mtfreport.hpp"
 #include "oip_noisereport.hpp"
 #include "oip_regreport.hpp"
+#include "oip_wallisreport.hpp"
 #include "oip_stripplan.hpp"
 #include "oip_warpfield.hpp"
 
@@ -74,7 +75,7 @@ inline std::string FilterOutputPath(const std::string &file, const std::string &
     return path;
 }
 
-// OIP_<TOOL>_BLOCK_LINES of mtfc, despike, denoise, noise, mask, mtf, overviews and regfix (test hooks: several blocks on a small image), rounded
+// OIP_<TOOL>_BLOCK_LINES of mtfc, despike, denoise, noise, mask, wallis, mtf, overviews and regfix (test hooks: several blocks on a small image), rounded
 // down to the multiple q of lines the tool needs and never below q; 0 without one
 inline long BlockLinesHook(const char *name, long q = 1)
 {
@@ -927,6 +928,150 @@ inline void RunMask(const std::string &file, const std::string &out, const MaskO
     OLOG("mask: %s", MaskSummaryLine(n).c_str());
     OLOG("Report written to '%s'.", paths.csv.c_str());
     LogThroughput(inBytes, total.tick());
+}
+
+// ---- oip wallis: local brightness and contrast equalisation of a strip or product ------------------------------------------------
+// The Wallis filter.  A read-only pass gives every B x B block its n, S1, S2 (oip_block_moments_u16); the host turns them into a
+// gain and an offset per block and channel (oip_wallis_fit), which pull the block's mean and standard deviation toward the
+// image's own (or a given) pair; the second pass transforms every sample with the gain and offset interpolated between the
+// blocks' centres (oip_wallis_apply_u16).  The product has the size and container of the input (<stem>.WAL.<ext>), the figures
+// go to <stem>.WAL.CSV (oip_wallisreport.hpp).  A TIFF product is resident; a RAW strip is read twice, the node tables stay on
+// the device in between.  With --line-offset / --lines the selected lines are the raster.  The defaults (contrast 0.8,
+// brightness 0.6, gains 0.25 .. 4, blocks of 128) are conventions: nothing was measured on real imagery.  Not in the reference.
+struct WallisOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    int block = 128;
+    double contrast = 0.8, brightness = 0.6, gMin = 0.25, gMax = 4.0;
+    long minCount = 0;
+    int validMin = 1, validMax = 65535, maxValue = 65535;
+    std::vector<double> mean, std;          // --mean / --std: none, one for every channel, or one per channel
+    long lineOffset = 0, lines = 0;         // lines == 0: to the end of the image
+    bool force = false;
+    std::string report;                     // --report: the CSV; empty: <stem>.WAL.CSV
+};
+
+struct WallisPaths {
+    std::string image, csv;
+};
+
+// what is refused without a device and depends on the image (the option ranges are run_wallis's): the container, the size of a
+// RAW file, the samples of a TIFF, the line range, targets that are not one or one per channel, the two outputs; returns the
+// output paths, whether the input is a TIFF and its samples per pixel
+inline WallisPaths WallisCheck(const std::string &file, const std::string &out, const WallisOptions &o, bool *isTiff, int *spp)
+{
+    const std::string ext = RasterContainer(file, "wallis");
+    *isTiff = ext == ".tiff";
+    *spp = 1;
+    long first = 0, n = 0;
+    if (*isTiff) {
+        TiffLayout lay;
+        int w = 0;
+        long h = 0;
+        read_tiff_u16(file, &w, &h, spp, nullptr, &lay);
+        if (*spp != 1 && *spp != MSS_BANDS) throw std::invalid_argument("wallis: a TIFF of 1 or 4 samples per pixel expected");
+        LineRange("image", h, o.lineOffset, o.lines, &first, &n);
+    } else {
+        RawLineRange(file, "image", o.width, o.lineOffset, o.lines, &first, &n);
+    }
+    for (const std::vector<double> *t : {&o.mean, &o.std})
+        if (t->size() > 1 && (int)t->size() != *spp)
+            throw std::invalid_argument("wallis: --mean / --std take one value, or one per sample of a pixel (" + std::to_string(*spp) + ")");
+    WallisPaths p;
+    p.csv = o.report.empty() ? IMO::BuildOutputFilePath(file, OIP_WALLIS_SUFFIX, ".CSV") : o.report;
+    p.image = out.empty() ? IMO::BuildOutputFilePath(file, OIP_WALLIS_SUFFIX) : out;
+    if (p.image == p.csv) throw std::invalid_argument("output file [" + p.image + "] is named for the image and for the report");
+    GuardOutput(p.csv, {file}, "wallis", o.force);
+    FilterOutputPath(file, p.image, OIP_WALLIS_SUFFIX, ext, "wallis", o.force);
+    return p;
+}
+
+inline void RunWallis(const std::string &file, const std::string &out, const WallisOptions &o)
+{
+    bool isTiff = false;
+    int spp = 1;
+    const WallisPaths paths = WallisCheck(file, out, o, &isTiff, &spp);
+    const int B = o.block;
+    OLOG("wallis: blocks of %d, contrast %g, brightness %g, gain %g .. %g, valid %d .. %d, max value %d", B, o.contrast, o.brightness, o.gMin, o.gMax,
+         o.validMin, o.validMax, o.maxValue);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    int W = 0, gw = 0;
+    long L = 0, gh = 0, first = 0;
+    DevBuf<uint64_t> acc, stats(3);
+    DevBuf<int32_t> gain, offset;
+    std::vector<double> report;
+    ck(oip_memset(ctx, stats.p, 0, 3 * sizeof(uint64_t)));
+    auto alloc_acc = [&](int w, long lines) {
+        W = w;
+        L = lines;
+        if (oip_wallis_grid(W, L, B, &gw, &gh) != OIP_OK || gw < 1 || gh < 1) throw std::invalid_argument("wallis: the image is empty");
+        acc.alloc((size_t)3 * spp * gw * gh);
+    };
+    // moments on the host -> node tables on the device
+    auto fit = [&]() {
+        const size_t nodes = (size_t)gw * gh * spp;
+        std::vector<uint64_t> moments((size_t)3 * nodes);
+        ck(oip_sync(ctx));
+        acc.download(moments.data(), moments.size());
+        std::vector<double> tm(spp, std::nan("")), ts(spp, std::nan(""));
+        for (int c = 0; c < spp; ++c) {
+            if (!o.mean.empty()) tm[c] = o.mean[o.mean.size() == 1 ? 0 : c];
+            if (!o.std.empty()) ts[c] = o.std[o.std.size() == 1 ? 0 : c];
+        }
+        std::vector<int32_t> G(nodes), O(nodes);
+        std::vector<int> sub(nodes);
+        report.assign((size_t)9 * spp, 0.0);
+        char err[512] = "";
+        const int rc = oip_wallis_fit(moments.data(), gw, (size_t)gw * gh, gw, gh, spp, o.contrast, o.brightness, o.gMin, o.gMax, (uint64_t)o.minCount,
+                                      tm.data(), ts.data(), G.data(), O.data(), sub.data(), report.data(), err, sizeof err);
+        if (rc == OIP_E_INVALID) throw std::invalid_argument(err);
+        if (rc != OIP_OK) throw std::runtime_error(err);
+        for (int c = 0; c < spp; ++c) OLOG("wallis: %s", WallisSummaryLine(c, report.data() + 9 * c).c_str());
+        gain.assign(G);
+        offset.assign(O);
+    };
+    size_t bytes = 0;
+    if (isTiff) {
+        ResidentImage m;
+        LoadTiffProduct(file, "wallis", &m);
+        long n = 0;
+        LineRange("image", m.h, o.lineOffset, o.lines, &first, &n);
+        alloc_acc(m.w, n);
+        uint16_t *img = m.buf.p + (size_t)first * m.w * spp;
+        ck(oip_block_moments_u16(ctx, img, (long)W * spp, W, L, spp, B, o.validMin, o.validMax, acc.p, gw, (size_t)gw * gh));
+        fit();
+        ck(oip_wallis_apply_u16(ctx, img, img, 0, L, W, L, spp, B, gain.p, offset.p, gw, gh, o.validMin, o.validMax, o.maxValue, stats.p));
+        OLOG("Write equalised image to file '%s' ...", paths.image.c_str());
+        write_tiff_from_device(paths.image, img, W, L, spp, tiff_compression(spp == 1 ? TIFF_NONE : TIFF_LZW), false);
+        bytes = (size_t)W * L * spp * BYTES_PER_PIXEL;
+    } else {
+        const size_t lineBytes = (size_t)o.width * BYTES_PER_PIXEL;
+        long n = 0;
+        const long fileLines = RawLineRange(file, "image", o.width, o.lineOffset, o.lines, &first, &n);
+        alloc_acc(o.width, n);
+        // pass 1: the moments per line block of the strip, a block being a multiple of B lines
+        ReadStrip(file, StripPlan{first, L, fileLines, 0, StripBlockLines(lineBytes, B, BlockLinesHook("OIP_WALLIS_BLOCK_LINES", B)), lineBytes},
+                  [&](const uint16_t *d, long r, long m) {
+                      ck(oip_block_moments_u16(ctx, d, W, W, m, 1, B, o.validMin, o.validMax, acc.p + (size_t)(r / B) * gw, gw, (size_t)gw * gh));
+                  });
+        fit();
+        // pass 2: the transform is pointwise, a block needs no halo and may be cut anywhere
+        StreamStrip(file, StripPlan{first, L, fileLines, 0, StripBlockLines(lineBytes, 1, BlockLinesHook("OIP_WALLIS_BLOCK_LINES")), lineBytes}, &paths.image,
+                    [&](const uint16_t *d, long, long, uint16_t *q, long r, long m) {
+                        ck(oip_wallis_apply_u16(ctx, d, q, r - first, m, W, L, 1, B, gain.p, offset.p, gw, gh, o.validMin, o.validMax, o.maxValue, stats.p));
+                    });
+        bytes = (size_t)L * lineBytes;
+    }
+    uint64_t n[3];
+    ck(oip_sync(ctx));
+    stats.download(n, 3);
+    const std::string params = WallisParamsLine(file, W, first, L, spp, B, o.contrast, o.brightness, o.gMin, o.gMax, o.minCount, o.validMin, o.validMax, o.maxValue);
+    WriteTextFile(paths.csv, [&](FILE *f) { return WriteWallisReport(f, params, spp, report.data(), n); });
+    OLOG("wallis: %llu samples transformed, %llu clamped at %d, %llu clamped at %d", (unsigned long long)n[0], (unsigned long long)n[1], o.validMin,
+         (unsigned long long)n[2], o.maxValue);
+    OLOG("Report written to '%s'.", paths.csv.c_str());
+    LogThroughput(bytes, total.tick());
 }
 
 // ---- oip mtf: the MTF at Nyquist from the edges of a strip or product -------------------------------------------------------
