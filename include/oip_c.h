@@ -1012,6 +1012,42 @@ int oip_halve_u16(oip_ctx *ctx, const uint16_t *d_src, long src_pitch, int w, lo
  * at most 16.  No context needed. */
 int oip_overview_levels(int w, long h);
 
+/* ---- cog: tiled TIFF with internal overviews, and tiled TIFF input (`oip cog`; not in the reference) ---- */
+#define OIP_COG_SUFFIX ".COG"   /* <stem>.COG.TIFF, built like the reference's other product names (imageop.h:99-108) */
+#define OIP_COG_DEF_TILE   256   /* --tile at 1 sample per pixel */
+#define OIP_COG_DEF_TILE_4 128   /* ... at 4: a 256 x 256 x 4 tile is 512 KiB for one lane of the LZW encoder, 3.3 x the time of 128 */
+
+/* The tile-major form of an image, and back.
+ * Grid.  An image is w x h pixels of spp samples (1, or 4 pixel-interleaved), u16.  Tiles are T x T pixels, T a multiple of 16 in
+ * 16..1024.  The grid has tx = ceil(w / T) by ty = ceil(h / T) tiles, numbered row-major: tile (j, i) is number k = j tx + i.
+ * Tile-major form.  ty tx consecutive blocks of T rows of T spp samples (T T spp samples a tile, no gaps).  Sample (r, c, ch) of
+ * tile (j, i) is image sample
+ *   (min(j T + r, h - 1), min(i T + c, w - 1), ch)
+ * so the part of an edge tile outside the image replicates the last column, per channel, and the last line; nothing is
+ * zero-filled (with TIFF's predictor 2 the replicated columns code to runs of zeros, and a reader that ignores the padding sees
+ * nothing of it).  Every byte of the tile-major buffer is defined: oip_retile_u16 writes every sample of every tile it is asked for.
+ * Inverse.  oip_untile_u16 writes exactly the w x h x spp samples of the image (the rows of the selected tile rows) and ignores
+ * the padding, whatever it holds; the slack of a pitched destination is not touched.
+ * Batches.  tile_row0 / tile_rows select tile rows [tile_row0, tile_row0 + tile_rows) of the grid; d_tiles then holds only that
+ * range: tile (j, i) lies at d_tiles + ((j - tile_row0) tx + i) T T spp.  d_img is always the image's first line.  Any cut of
+ * the grid into calls gives the bytes of one call.
+ * d_img: lines `pitch` SAMPLES apart (a window inside a wider raster is allowed).  d_tiles: 16-byte aligned.  A raster whose
+ * pitch is not a multiple of 8 samples, or that does not start on a 16-byte boundary, takes a slower kernel (a lane per sample)
+ * with the same result.  Asynchronous on the context's stream.  OIP_E_INVALID for spp other than 1 or 4, w < 1, h < 1 or >= 2^31,
+ * w spp >= 2^31, T not a multiple of 16 in 16..1024, a pitch shorter than the line, tile rows outside the grid, a NULL or
+ * misaligned pointer, d_img == d_tiles; tile_rows == 0 is a no-op.
+ * The file `oip cog` writes (TiffTiledWriterU16, csrc/oip_tifftiled.hpp), little-endian, classic or BigTIFF (BigTIFF when the
+ * worst-case sum of all payloads would pass 4 GiB, or with OIP_TIFF_FORCE_BIG): (1) the header; (2) directory 0, the image, then
+ * directories 1 .. n, levels 1 .. n of the pyramid above with NewSubfileType (254) = 1, chained by their next-directory offsets,
+ * each followed by its own out-of-line values (BitsPerSample and SampleFormat where they do not fit the entry, TileOffsets,
+ * TileByteCounts); (3) from an even offset, the tiles of the image in tile order, then those of level 1, 2, .. n, every tile on
+ * an even offset.  A tile is the T T spp samples of the tile-major form, uncompressed or one LZW stream with predictor 2 along
+ * each of its rows.  Tags: those of a strip product of the same geometry and spp, with 322, 323, 324, 325 in place of 273, 278, 279. */
+int oip_retile_u16(oip_ctx *ctx, const uint16_t *d_img, long src_pitch_samples, int w, long h, int spp, int T, long tile_row0,
+                   long tile_rows, uint16_t *d_tiles);
+int oip_untile_u16(oip_ctx *ctx, const uint16_t *d_tiles, int w, long h, int spp, int T, long tile_row0, long tile_rows,
+                   uint16_t *d_img, long dst_pitch_samples);
+
 /* ---- regcheck: tile-matching registration check of two rasters (`oip regcheck`; not in the reference) ---- */
 /* Dense template matching by zero-mean normalised cross-correlation in the spatial domain, built from exact integer sums: a
  * measure of registration that shares no code with the phase correlation it judges.

@@ -158,6 +158,8 @@ _SIGS = {
     "oip_mtf_tv_slack": ([_d], _i),
     "oip_halve_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _vp, _l], _i),
     "oip_overview_levels": ([_i, _l], _i),
+    "oip_retile_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _l, _l, _vp], _i),
+    "oip_untile_u16": ([_vp, _vp, _i, _l, _i, _i, _l, _l, _vp, _l], _i),
     "oip_match_tiles_u16": ([_vp, _vp, _l, _i, _vp, _l, _i, _i, _l, _i, _i, _i, _l, _i, _l, _i, _l, _i, _i, _vp, _vp], _i),
     "oip_match_grid": ([_i, _l, _i, _i, _i, C.POINTER(_i), _lp, C.POINTER(_i), _lp], _i),
     "oip_match_peak": ([C.POINTER(C.c_uint64), _i, _i, _d, _dp, _dp, _dp, C.POINTER(_i)], _i),
@@ -849,6 +851,16 @@ class Context:
         """one pyramid level: 2 x 2 means, skipping samples below valid_min, of rows x w pixels of spp samples (lines src_pitch
         samples apart) into ceil(rows / 2) lines of ceil(w / 2) pixels, dst_pitch samples apart (include/oip_c.h: oip_halve_u16)"""
         self._ck(self.lib.oip_halve_u16(self.h, _ptr(src), src_pitch, w, rows, spp, valid_min, _ptr(dst), dst_pitch))
+
+    def retile_u16(self, img, src_pitch, w, h, spp, T, tile_row0, tile_rows, tiles):
+        """tile rows [tile_row0, tile_row0 + tile_rows) of the tile-major form (T x T tiles, edge tiles replicating the last column
+        and line) of the w x h x spp image whose lines are src_pitch samples apart (include/oip_c.h: oip_retile_u16)"""
+        self._ck(self.lib.oip_retile_u16(self.h, _ptr(img), src_pitch, w, h, spp, T, tile_row0, tile_rows, _ptr(tiles)))
+
+    def untile_u16(self, tiles, w, h, spp, T, tile_row0, tile_rows, img, dst_pitch):
+        """the inverse: the image samples of those tile rows from the tile-major buffer, whatever its padding holds
+        (include/oip_c.h: oip_untile_u16)"""
+        self._ck(self.lib.oip_untile_u16(self.h, _ptr(tiles), w, h, spp, T, tile_row0, tile_rows, _ptr(img), dst_pitch))
 
     def match_tiles_u16(self, a, pitch_a, stride_a, b, pitch_b, stride_b, w, rows, T, S, x0, y0, step_x, step_y, nx, ny, valid_min, valid_max,
                         records, sums=None):

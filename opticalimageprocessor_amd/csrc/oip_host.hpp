@@ -37,6 +37,7 @@
 #include "oip_c.h"
 #include "oip_corrgeom.h"
 #include "oip_tiff.hpp"
+#include "oip_tifftiled.hpp"
 
 namespace OIPGPU {
 
@@ -415,6 +416,71 @@ inline void write_tiff_from_device(const std::string &path, uint16_t *d_img, int
     tw.close();
 }
 
+// The tiles of the directory `tw` is writing (w x h x spp u16 in HBM, in file sample order) leave the device, in batches of tile
+// rows of at most 256 MiB of tile-major samples and at least one tile row (OIP_COG_BATCH_MB: test hook, several batches on a small
+// image): oip_retile_u16 into the batch buffer; uncompressed, the batch itself goes into the file; LZW, every tile is one
+// "strip" of the device encoder (a T-wide image of tile_rows tx T lines in strips of T lines) and the packed payload goes.
+// OIP_TIFF_GPU_LZW=0: the tile-major form comes down and the host coders write it (TiffTiledWriterU16::write_tiles; same bytes).
+inline void tiled_image_from_device(TiffTiledWriterU16 &tw, const std::string &path, const uint16_t *d_img, int w, long h, int spp, int T,
+                                    int compression)
+{
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch sw;
+    const long tx = tw.tiles_x(), ty = tw.tiles_y();
+    const size_t tileSamples = (size_t)T * T * spp, rowSamples = (size_t)tx * tileSamples, n = (size_t)tx * ty;
+    size_t batchBytes = (size_t)256 << 20;
+    if (const char *e = getenv("OIP_COG_BATCH_MB")) {
+        const long mb = atol(e);
+        if (mb > 0) batchBytes = (size_t)mb << 20;
+    }
+    const long batchRows = std::max<long>(1, std::min<long>(ty, (long)(batchBytes / (rowSamples * 2))));
+    DevBuf<uint16_t> batch((size_t)batchRows * rowSamples);
+    if (compression == TIFF_LZW && !gpu_lzw()) {
+        std::vector<uint16_t> host(n * tileSamples);
+        for (long j0 = 0; j0 < ty; j0 += batchRows) {
+            const long nr = std::min(batchRows, ty - j0);
+            ck(oip_retile_u16(ctx, d_img, (long)w * spp, w, h, spp, T, j0, nr, batch.p));
+            batch.download(host.data() + (size_t)j0 * rowSamples, (size_t)nr * rowSamples);
+        }
+        tw.write_tiles(host.data());
+        return;
+    }
+    DevBuf<uint8_t> payload, scratch;
+    if (compression == TIFF_LZW) {
+        payload.alloc(oip_tiff_lzw_worst_bytes(batchRows * tx * T, T, spp, T));
+        scratch.alloc(oip_tiff_lzw_scratch_bytes(batchRows * tx * T, T, spp, T));
+    }
+    std::vector<uint64_t> off(n), len(n);
+    const uint64_t at = tw.begin_tiles();
+    uint64_t pos = 0;
+    double tEncode = 0.0, tWrite = 0.0;
+    sw.tick();
+    for (long j0 = 0; j0 < ty; j0 += batchRows) {
+        const long nr = std::min(batchRows, ty - j0);
+        const size_t k0 = (size_t)j0 * tx, nt = (size_t)nr * tx;
+        if (pos & 1) ++pos;                                            // a batch starts on an even offset, as every tile does
+        ck(oip_retile_u16(ctx, d_img, (long)w * spp, w, h, spp, T, j0, nr, batch.p));
+        if (compression == TIFF_NONE) {
+            for (size_t k = 0; k < nt; ++k) { off[k0 + k] = pos + k * tileSamples * 2; len[k0 + k] = tileSamples * 2; }
+            ck(oip_write_device_to_file_at(ctx, batch.p, nt * tileSamples * 2, path.c_str(), (size_t)(at + pos), 0));
+            pos += nt * tileSamples * 2;
+            tWrite += sw.tick();
+        } else {
+            size_t bytes = 0;
+            ck(oip_tiff_lzw_strips_u16(ctx, batch.p, (long)nt * T, T, spp, T, payload.p, payload.n, off.data() + k0, len.data() + k0, &bytes, scratch.p,
+                                       scratch.n));
+            tEncode += sw.tick();
+            for (size_t k = 0; k < nt; ++k) off[k0 + k] += pos;
+            ck(oip_write_device_to_file_at(ctx, payload.p, bytes, path.c_str(), (size_t)(at + pos), 0));
+            pos += bytes;
+            tWrite += sw.tick();
+        }
+    }
+    tw.end_tiles(off.data(), len.data(), n, pos);
+    if (compression == TIFF_LZW) RLOG("TIMING tiff_lzw tiles=%zu tile=%d encode=%.4f write=%.4f bytes=%zu", n, T, tEncode, tWrite, (size_t)pos);
+}
+
 // ---- overviews: <product>.ovr, the reduced-resolution pyramid of a product or strip (not in the reference) ----------------
 // `oip overviews` and `oip stitch --overviews` come through here.  levels: 0 = oip_overview_levels.
 struct OverviewOptions {
@@ -465,15 +531,18 @@ inline void write_overviews_of_device_image(const std::string &path, const uint1
 
 // cv::imread of a 16-bit TIFF (imageop.h:380-388) with the image ending up in HBM.  LZW files -- what the reference's own
 // products are -- go from the file into device memory as they are and their strips are decoded there (csrc/tifflzw.hip: a
-// strip per lane); anything else, and OIP_TIFF_GPU_LZW=0, decodes on the host's threads (read_tiff_u16) and uploads.  Same
+// strip per lane; a tiled file with square tiles of a multiple of 16: a tile per lane into a tile-major buffer, then
+// oip_untile_u16); anything else, and OIP_TIFF_GPU_LZW=0, decodes on the host's threads (read_tiff_u16) and uploads.  Same
 // checks and error texts either way: the header is validated by the host reader in both.
 inline void read_tiff_to_device(const std::string &path, int *width, long *height, int *spp, DevBuf<uint16_t> &img)
 {
     TiffLayout lay;
     read_tiff_u16(path, width, height, spp, nullptr, &lay);
     const size_t samples = (size_t)lay.width * lay.height * lay.spp;
+    // (tiled: square tiles the layout kernel takes -- a multiple of 16 up to 1024 --, each one a "strip" of the decoder)
+    const uint64_t T = lay.tile_width;
     bool device = gpu_lzw() && lay.compression == TIFF_LZW && (lay.spp == 1 || lay.spp == 4) &&
-                  lay.rows_per_strip * lay.width * lay.spp * 2 < ((uint64_t)1 << 32);
+                  (lay.tiled() ? T == lay.tile_length && T % 16 == 0 && T <= 1024 : lay.rows_per_strip * lay.width * lay.spp * 2 < ((uint64_t)1 << 32));
     uint64_t lo = ~(uint64_t)0, hi = 0;
     for (size_t k = 0; k < lay.offs.size(); ++k) { lo = std::min(lo, lay.offs[k]); hi = std::max(hi, lay.offs[k] + lay.lens[k]); }
     if (device && hi - lo > 3 * samples + ((uint64_t)64 << 20)) device = false;       // strips scattered over a far larger file
@@ -485,6 +554,40 @@ inline void read_tiff_to_device(const std::string &path, int *width, long *heigh
         return;
     }
     oip_ctx *ctx = Device::get().ctx();
+    if (lay.tiled()) {
+        // batches of tile rows of at most 1 GiB of tile-major samples: their tiles go from the file into device memory as they
+        // are, are decoded into the tile-major buffer (width T, T rows a "strip") and oip_untile_u16 puts them into the image
+        const long tx = (long)((lay.width + T - 1) / T), ty = (long)((lay.height + T - 1) / T);
+        const size_t rowSamples = (size_t)tx * T * T * lay.spp;
+        size_t batchBytes = (size_t)1 << 30;
+        if (const char *e = getenv("OIP_COG_BATCH_MB")) {              // test hook: several batches on a small image
+            const long mb = atol(e);
+            if (mb > 0) batchBytes = (size_t)mb << 20;
+        }
+        const long batchRows = std::max<long>(1, std::min<long>(ty, (long)(batchBytes / (rowSamples * 2))));
+        DevBuf<uint16_t> tiles((size_t)batchRows * rowSamples);
+        img.alloc(samples);
+        for (long j0 = 0; j0 < ty; j0 += batchRows) {
+            const long nr = std::min(batchRows, ty - j0);
+            const size_t k0 = (size_t)j0 * tx, nt = (size_t)nr * tx;
+            uint64_t blo = ~(uint64_t)0, bhi = 0;
+            for (size_t k = k0; k < k0 + nt; ++k) { blo = std::min(blo, lay.offs[k]); bhi = std::max(bhi, lay.offs[k] + lay.lens[k]); }
+            if (bhi <= blo) throw std::runtime_error("read TIFF [" + path + "]: empty tiles");
+            DevBuf<uint8_t> file((size_t)(bhi - blo));
+            size_t got = 0;
+            Device::get().check(oip_read_file_to_device(ctx, path.c_str(), (size_t)blo, (size_t)(bhi - blo), file.p, &got, nullptr));
+            if (got != (size_t)(bhi - blo)) throw std::runtime_error("read TIFF [" + path + "]: truncated file");
+            Device::get().check(oip_stage_sync(ctx));
+            std::vector<uint64_t> off(lay.offs.begin() + k0, lay.offs.begin() + k0 + nt);
+            for (auto &o : off) o -= blo;
+            const int rc = oip_tiff_lzw_decode_u16(ctx, file.p, file.n, off.data(), lay.lens.data() + k0, (long)nt, (long)(nt * T), (int)T, (int)lay.spp,
+                                                   (long)T, (int)lay.predictor, tiles.p);
+            if (rc != OIP_OK) throw std::runtime_error("read TIFF [" + path + "]: " + std::string(oip_last_error(ctx)) + " (tiles from " + std::to_string(k0) + " on)");
+            Device::get().check(oip_untile_u16(ctx, tiles.p, (int)lay.width, (long)lay.height, (int)lay.spp, (int)T, j0, nr, img.p, (long)(lay.width * lay.spp)));
+        }
+        Device::get().check(oip_sync(ctx));                            // (the last untile reads `tiles`)
+        return;
+    }
     DevBuf<uint8_t> file((size_t)(hi - lo));
     size_t got = 0;
     Device::get().check(oip_read_file_to_device(ctx, path.c_str(), (size_t)lo, (size_t)(hi - lo), file.p, &got, nullptr));

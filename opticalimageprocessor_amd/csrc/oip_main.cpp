@@ -37,6 +37,8 @@
 //                               summary in <A>.REG.CSV, see run_regcheck()
 //   oip regfix --report R.CSV --image B [--bands k[,k...]|all] [--smooth N] [--width N] [-o OUT]   resamples image 2 of a regcheck
 //                               report by the shift field the report holds, so that it lands on image 1, see run_regfix()
+//   oip cog IMAGE [-o OUT] [--tile T] [--levels N] [--valid-min N]   the image as a tiled TIFF with its pyramid inside,
+//                               <stem>.COG.TIFF, see run_cog()
 //   oip pansharpen --pan P --mss M [--line-offset N] [--max-gain G] [--width N] [-o OUT] [--force] [--overviews [--levels N]]
 //                               fuses the PAN strip and the aligned MSS product into a 4-band product at PAN resolution, see
 //                               run_pansharpen()
@@ -46,7 +48,7 @@
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
 // --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
-// despike, denoise, noise, mask, wallis, mtf, overviews, regcheck, regfix and pansharpen sub-commands.
+// despike, denoise, noise, mask, wallis, mtf, overviews, cog, regcheck, regfix and pansharpen sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -149,7 +151,7 @@ Parsed parse(const Spec &sp, const std::vector<std::string> &args)
     return p;
 }
 
-// The tools with one positional argument (quicklook, mtfc, despike, denoise, noise, mask, wallis, mtf, overviews; regcheck, regfix and pansharpen name their
+// The tools with one positional argument (quicklook, mtfc, despike, denoise, noise, mask, wallis, mtf, overviews, cog; regcheck, regfix and pansharpen name their
 // images by options): IMAGE, an existing regular file, is the first argument that is neither an option nor the value of one (an
 // option's value stays with it, alias or not); the rest is parsed as usual.
 Parsed parse_with_image(const Spec &sp, const std::vector<std::string> &args, std::string *image)
@@ -299,6 +301,11 @@ void usage()
          "             the 2 x 2 average of the one before; written to IMAGE.ovr beside the image, where GDAL-based viewers look for it:\n"
          "             [-o,--out FILE] [--levels N] (1..16; default: until a level fits 256 x 256) [--valid-min N] (samples below are\n"
          "             no data and do not enter an average; default 1) [--width N] [--force]\n"
+         "  cog        IMAGE.TIFF|IMAGE.RAW: a product (TIFF of 1 or 4 samples, strips or tiles) or a single-band strip as a tiled TIFF\n"
+         "             with its pyramid inside, the levels of `overviews` as further directories, every directory ahead of the pixels;\n"
+         "             written to <stem>.COG.TIFF in the working directory:\n"
+         "             [-o,--out FILE] [--tile T] (a multiple of 16, 16..1024; default 256, at 4 samples 128) [--levels N] (0..16, 0: none; default: until\n"
+         "             a level fits 256 x 256) [--valid-min N] (as for overviews; default 1) [--width N] [--force]\n"
          "  regcheck   --image1 A [--image2 B]: how well B is registered to A (TIFF of 1 or 4 samples, or single-band RAW), measured by\n"
          "             template matching (zero-mean normalised cross-correlation from exact integer sums) on a grid of tiles; writes\n"
          "             x,y,dx,dy,score,flags per tile and a summary (count, mean, std, RMS, CE90, max) to <stem of A>.REG.CSV:\n"
@@ -998,6 +1005,28 @@ int run_overviews(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip cog IMAGE: a product (.TIFF of 1 or 4 samples, strips or tiles) or a single-band strip (.RAW, --width samples per line)
+// as <stem>.COG.TIFF, tiled and with its pyramid inside (RunCog).  IMAGE is the one positional argument, as for mtfc.  Bad
+// values end in 105 before any file is read.
+int run_cog(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--out", "--tile", "--levels", "--valid-min", "--width"};
+    sp.flags = {"--force"};
+    sp.alias = {{"-o", "--out"}};
+    std::string image;
+    Parsed p = parse_with_image(sp, args, &image);
+    CogOptions o;
+    o.width = p.integer("--width", width);
+    o.tile = p.has("--tile") ? p.within("--tile", 0, 16, 1024, "a multiple of 16, 16 <= T <= 1024, expected") : 0;      // 0: by the samples per pixel
+    if (o.tile % 16 != 0) throw cli_error(105, "--tile: a multiple of 16, 16 <= T <= 1024, expected");
+    o.levels = p.has("--levels") ? p.within("--levels", 0, 0, 16, "0 <= N <= 16 expected") : -1;
+    o.validMin = p.valid_min();
+    o.force = p.has("--force");
+    RunCog(image, p.str("--out"), o);
+    return 0;
+}
+
 // oip regcheck --image1 A [--image2 B]: the registration check of two rasters (RunRegcheck).  Bad values end in 105, an
 // option that needs another in 107, before any file is read.
 int run_regcheck(const std::vector<std::string> &args, int width)
@@ -1177,6 +1206,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "wallis") return run_wallis({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "mtf") return run_mtf({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "overviews") return run_overviews({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "cog") return run_cog({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regcheck") return run_regcheck({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regfix") return run_regfix({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "pansharpen") return run_pansharpen({args.begin() + 1, args.end()}, width);

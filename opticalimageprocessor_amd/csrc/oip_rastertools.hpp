@@ -1,5 +1,5 @@
 // oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, denoise, noise, mask, wallis, mtf,
-// overviews, regcheck, regfix, pansharpen) above the host layer of oip_host.hpp.  Stated once for all of them: the file checks made before a
+// overviews, cog, regcheck, regfix, pansharpen) above the host layer of oip_host.hpp.  Stated once for all of them: the file checks made before a
 // device is touched (container, RAW size rule, line range, GuardOutput), the loaders of a resident image, the driver that streams
 // a RAW strip through the device in line blocks (geometry: oip_stripplan.hpp), the filter driver above it, the closing
 // throughput line and the text-report writer.  Then the tools, each as Options / Check / Run.  The ranges of option values are
@@ -1284,6 +1284,68 @@ inline void RunOverviews(const std::string &file, const std::string &out, const 
         bytes = (size_t)L * lineBytes;
     }
     LogThroughput(bytes, total.tick());
+}
+
+// ---- oip cog: a product or strip as a tiled TIFF with internal overviews -------------------------------------------------
+// The image in T x T tiles and its pyramid -- the levels `oip overviews` writes to <IMAGE>.ovr, sample for sample -- in ONE
+// file whose directories all lie ahead of the pixels (TiffTiledWriterU16, oip_tifftiled.hpp): a reader gets a window at any
+// resolution by decoding the tiles it covers.  The image is resident (a TIFF product, strips or tiles, or a whole single-band
+// RAW strip); every directory leaves through tiled_image_from_device, the levels alternating between two buffers as
+// write_overviews_from_device does.  Not in the reference.
+struct CogOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    int tile = 0;                           // --tile: a multiple of 16 in 16..1024; 0: OIP_COG_DEF_TILE, at 4 samples OIP_COG_DEF_TILE_4
+    int levels = -1;                        // --levels: 0 none, 1..16; -1: oip_overview_levels
+    int validMin = 1;                       // --valid-min, as in `oip overviews`
+    bool force = false;
+};
+
+// what is refused without a device and depends on the image (--tile, --levels and --valid-min are run_cog's): the container,
+// --width and the size of a RAW file, the output; returns the output path
+inline std::string CogCheck(const std::string &file, const std::string &out, const CogOptions &o, bool *isTiff)
+{
+    *isTiff = RasterContainer(file, "cog") == ".tiff";
+    if (!*isTiff) {
+        if (o.width <= 0) throw std::invalid_argument("--width: a positive line width expected");
+        RawLineCount(file, "image", (size_t)o.width * BYTES_PER_PIXEL);
+    }
+    const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_COG_SUFFIX, ".TIFF") : out;
+    GuardOutput(path, {file}, "cog", o.force);
+    return path;
+}
+
+inline void RunCog(const std::string &file, const std::string &out, const CogOptions &o)
+{
+    bool isTiff = false;
+    const std::string outPath = CogCheck(file, out, o, &isTiff);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    ResidentImage m;
+    LoadResident(file, isTiff, o.width, "image", "cog", &m);
+    const int spp = m.spp, T = o.tile > 0 ? o.tile : (spp == MSS_BANDS ? OIP_COG_DEF_TILE_4 : OIP_COG_DEF_TILE);
+    const int levels = o.levels >= 0 ? o.levels : oip_overview_levels(m.w, m.h);
+    const int comp = tiff_compression(spp == 1 ? TIFF_NONE : TIFF_LZW);
+    OLOG("Write image in %d x %d tiles and %d overview levels to file '%s' ...", T, T, levels, outPath.c_str());
+    TiffTiledWriterU16 tw(outPath, m.w, m.h, spp, T, comp, levels);
+    DevBuf<uint16_t> lv[2];
+    const uint16_t *cur = m.buf.p;
+    for (int k = 0; k <= levels; ++k) {
+        const int w = tw.width();
+        const long h = tw.height();
+        RLOG("    level %d: %d x %ld x %d, %ld x %ld tiles", k, w, h, spp, tw.tiles_x(), tw.tiles_y());
+        tiled_image_from_device(tw, outPath, cur, w, h, spp, T, comp);
+        if (k == levels) break;
+        const int nw = (w + 1) / 2;
+        const long nh = (h + 1) / 2;
+        DevBuf<uint16_t> &next = lv[k & 1];
+        if (!next.p) next.alloc((size_t)nw * nh * spp);                 // (level 1 and level 2: every later level fits the one two before it)
+        ck(oip_halve_u16(ctx, cur, (long)w * spp, w, h, spp, o.validMin, next.p, (long)nw * spp));
+        tw.next_directory();
+        cur = next.p;
+    }
+    tw.close();
+    LogThroughput(m.bytes(), total.tick());
 }
 
 // ---- oip regcheck: how well two rasters are registered ------------------------------------------------------------------

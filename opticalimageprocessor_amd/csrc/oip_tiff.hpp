@@ -622,14 +622,20 @@ private:
     bool mPositioned = false;           // positioned writes have moved past the FILE's own position
 };
 
-// Reader for little-endian, chunky, unsigned 16-bit strip TIFF / BigTIFF, uncompressed or LZW (predictor 1 or
-// 2): what the writer above, cv::imwrite and GDAL's GTiff driver (INTERLEAVE=PIXEL, untiled) produce.  Samples
-// are returned in file order.  Every header field is checked before it sizes an allocation or a read.
+// Reader for little-endian, chunky, unsigned 16-bit TIFF / BigTIFF in strips or tiles, uncompressed or LZW (predictor 1 or
+// 2): what the writers here (above, and oip_tifftiled.hpp), cv::imwrite and GDAL's GTiff driver (INTERLEAVE=PIXEL, with or
+// without TILED=YES) produce.  Samples are returned in file order.  Every header field is checked before it sizes an allocation
+// or a read.  Only the first directory is read: the internal overviews of a COG are ignored.
+// Tiles (322 TileWidth, 323 TileLength, 324 TileOffsets, 325 TileByteCounts) may have any positive size; they are numbered
+// row-major, every one holds TileWidth x TileLength pixels (the part outside the image is padding and is dropped), and
+// predictor 2 runs along each row of a tile.
 // layout_only: the checked header alone -- geometry, encoding and strip table -- for a caller that brings the strips in itself
 // (the device decoder: oip_host.hpp::read_tiff_to_device)
 struct TiffLayout {
     uint64_t width = 0, height = 0, spp = 0, compression = 1, predictor = 1, rows_per_strip = 0;
+    uint64_t tile_width = 0, tile_length = 0;          // 0: strips.  Tiled: rows_per_strip is 0 and offs / lens hold the tiles, row-major
     std::vector<uint64_t> offs, lens;
+    bool tiled() const { return tile_width != 0; }
 };
 inline void read_tiff_u16(const std::string &path, int *width, long *height, int *spp, std::vector<uint16_t> *out,
                           TiffLayout *layout_only = nullptr)
@@ -660,7 +666,8 @@ inline void read_tiff_u16(const std::string &path, int *width, long *height, int
     const uint64_t ent = ifd + (big ? 8 : 2);
     const size_t esz = big ? 20 : 12, osz = big ? 8 : 4;
     auto tsize = [](int t) { return t == 3 ? 2 : (t == 4 ? 4 : (t == 16 ? 8 : 0)); };
-    uint64_t W = 0, H = 0, comp = 1, planar = 1, S = 1, bits = 0, fmt = 1, pred = 1, rps = 0;
+    uint64_t W = 0, H = 0, comp = 1, planar = 1, S = 1, bits = 0, fmt = 1, pred = 1, rps = 0, TW = 0, TL = 0;
+    bool stripTags = false, tileTags = false, hasTW = false, hasTL = false;
     std::vector<uint64_t> offs, lens;
     for (uint64_t i = 0; i < n; ++i) {
         unsigned char e[20];
@@ -681,35 +688,57 @@ inline void read_tiff_u16(const std::string &path, int *width, long *height, int
             case 257: H = val(0); break;
             case 258: bits = val(0); for (uint64_t k = 1; k < cnt; ++k) if (val(k) != bits) fail("mixed sample depths"); break;
             case 259: comp = val(0); break;
-            case 273: offs.resize(cnt); for (uint64_t k = 0; k < cnt; ++k) offs[k] = val(k); break;
+            case 273: case 324: (id == 273 ? stripTags : tileTags) = true; offs.resize(cnt); for (uint64_t k = 0; k < cnt; ++k) offs[k] = val(k); break;
             case 277: S = val(0); break;
             case 278: rps = val(0); break;
-            case 279: lens.resize(cnt); for (uint64_t k = 0; k < cnt; ++k) lens[k] = val(k); break;
+            case 279: case 325: (id == 279 ? stripTags : tileTags) = true; lens.resize(cnt); for (uint64_t k = 0; k < cnt; ++k) lens[k] = val(k); break;
             case 284: planar = val(0); break;
             case 317: pred = val(0); break;
             case 339: fmt = val(0); break;
-            case 322: case 323: case 324: case 325: fail("tiled TIFF is not supported (strips only)"); break;
+            case 322: tileTags = hasTW = true; TW = val(0); break;
+            case 323: tileTags = hasTL = true; TL = val(0); break;
             default: break;
         }
     }
+    if (stripTags && tileTags) fail("strip tags and tile tags are both present");
+    const bool tiled = tileTags;
     if (comp != TIFF_NONE && comp != TIFF_LZW) fail("compression " + std::to_string(comp) + " is not supported (none and LZW are)");
     if (pred != 1 && pred != 2) fail("predictor " + std::to_string(pred) + " is not supported");
     if (bits != 16 || fmt != 1 || planar != 1) fail("only chunky unsigned 16-bit samples are supported");
     if (!W || !H || W > 0x7FFFFFFFull || H > 0x7FFFFFFFull || S == 0 || S > 16) fail("missing or implausible geometry");
-    if (offs.empty() || offs.size() != lens.size()) fail("missing strip tags");
+    if (tiled && (!hasTW || !hasTL || !TW || !TL)) fail("a tiled TIFF needs TileWidth and TileLength, both positive");
+    if (offs.empty() || offs.size() != lens.size()) fail(tiled ? "missing tile tags" : "missing strip tags");
     const uint64_t row_bytes = W * S * 2;
     if (H > (~(uint64_t)0) / row_bytes || row_bytes * H > ((uint64_t)1 << 46)) fail("implausible image size");
-    if (rps == 0 || rps > H) rps = H;
-    const uint64_t nstrips = (H + rps - 1) / rps;
-    if (offs.size() != nstrips) fail("strip count does not match RowsPerStrip");
-    for (size_t k = 0; k < offs.size(); ++k)
-        if (offs[k] > fsize || lens[k] > fsize - offs[k]) fail("strip outside the file");
-    if (comp == TIFF_NONE) {
+    uint64_t tile_bytes = 0, ntx = 0;
+    if (tiled) {
+        if (TW > 0xFFFFFFFFull / TL || TW * TL > 0xFFFFFFFFull / (S * 2)) fail("a tile of 4 GiB or more");
+        tile_bytes = TW * TL * S * 2;
+        ntx = (W + TW - 1) / TW;
+        if (offs.size() != ntx * ((H + TL - 1) / TL)) fail("tile count does not match the tile grid");
+        uint64_t packed = 0;
+        for (size_t k = 0; k < offs.size(); ++k) {
+            if (offs[k] > fsize || lens[k] > fsize - offs[k]) fail("tile outside the file");
+            if (comp == TIFF_NONE && lens[k] != tile_bytes) fail("an uncompressed tile does not have the size of a tile");
+            packed += lens[k];
+        }
+        // (the LZW bound of the strips below, on the tiles: what is present bounds what the tiles can decode to)
+        if (comp == TIFF_LZW && (unsigned __int128)tile_bytes * offs.size() / 2560 > (unsigned __int128)packed + 16)
+            fail("image size is implausible for its compressed tiles");
+        rps = 0;
+    }
+    if (!tiled) {
+        if (rps == 0 || rps > H) rps = H;
+        if (offs.size() != (H + rps - 1) / rps) fail("strip count does not match RowsPerStrip");
+        for (size_t k = 0; k < offs.size(); ++k)
+            if (offs[k] > fsize || lens[k] > fsize - offs[k]) fail("strip outside the file");
+    }
+    if (!tiled && comp == TIFF_NONE) {
         uint64_t total = 0;
         for (uint64_t l : lens) { if (l > row_bytes * H - total) fail("strip sizes exceed the image"); total += l; }
         if (total != row_bytes * H) fail("strip sizes do not cover the image");
     }
-    if (comp == TIFF_LZW) {
+    if (!tiled && comp == TIFF_LZW) {
         // header fields alone must not size the allocation: a 12-bit code (1.5 bytes) expands to at most 4096 - 258
         // bytes, so the strips present bound what the image can decode to
         uint64_t packed = 0;
@@ -719,6 +748,7 @@ inline void read_tiff_u16(const std::string &path, int *width, long *height, int
     if (layout_only) {
         layout_only->width = W; layout_only->height = H; layout_only->spp = S; layout_only->compression = comp;
         layout_only->predictor = pred; layout_only->rows_per_strip = rps;
+        layout_only->tile_width = tiled ? TW : 0; layout_only->tile_length = tiled ? TL : 0;
         layout_only->offs = offs; layout_only->lens = lens;
         *width = (int)W; *height = (long)H; *spp = (int)S;
         return;
@@ -729,6 +759,40 @@ inline void read_tiff_u16(const std::string &path, int *width, long *height, int
         fail("not enough memory for a " + std::to_string(W) + " x " + std::to_string(H) + " x " + std::to_string(S) + " image");
     }
     unsigned char *dstb = reinterpret_cast<unsigned char *>(out->data());
+    if (tiled) {
+        // the tiles in batches, each decoded on a worker thread into a tile of its own, un-differenced along the tile's rows, and
+        // its part inside the image copied out
+        const size_t batch = std::max<size_t>(1, std::min<size_t>(64, ((size_t)256 << 20) / (size_t)tile_bytes));
+        for (size_t k0 = 0; k0 < offs.size(); k0 += batch) {
+            const size_t kn = std::min(batch, offs.size() - k0);
+            std::vector<std::vector<unsigned char>> raw(kn);
+            for (size_t j = 0; j < kn; ++j) { raw[j].resize((size_t)lens[k0 + j]); rd(offs[k0 + j], raw[j].data(), raw[j].size()); }
+            tiffdetail::parallel_for(kn, [&](size_t j) {
+                const uint64_t k = k0 + j, tj = k / ntx, ti = k - tj * ntx;
+                std::vector<unsigned char> dec;
+                if (comp == TIFF_LZW) {
+                    dec.resize((size_t)tile_bytes);
+                    const size_t got = tiffdetail::lzw_decode(raw[j].data(), raw[j].size(), dec.data(), dec.size());
+                    if (got != dec.size()) throw std::runtime_error("read TIFF [" + path + "]: tile " + std::to_string(k) + " decodes to " +
+                                                                    std::to_string(got) + " bytes, " + std::to_string(dec.size()) + " expected");
+                }
+                unsigned char *tile = comp == TIFF_LZW ? dec.data() : raw[j].data();
+                const uint64_t nr = std::min<uint64_t>(TL, H - tj * TL), nc = std::min<uint64_t>(TW, W - ti * TW);
+                for (uint64_t r = 0; r < nr; ++r) {
+                    unsigned char *trow = tile + (size_t)(r * TW * S * 2);
+                    if (pred == 2) {
+                        std::vector<uint16_t> line((size_t)(TW * S));     // (a tile's bytes need not be aligned for u16)
+                        memcpy(line.data(), trow, line.size() * 2);
+                        tiffdetail::predictor2_decode(line.data(), (size_t)TW, (int)S);
+                        memcpy(trow, line.data(), line.size() * 2);
+                    }
+                    memcpy(dstb + (size_t)(((tj * TL + r) * W + ti * TW) * S * 2), trow, (size_t)(nc * S * 2));
+                }
+            });
+        }
+        *width = (int)W; *height = (long)H; *spp = (int)S;
+        return;
+    }
     if (comp == TIFF_NONE) {
         size_t pos = 0;
         for (size_t k = 0; k < offs.size(); ++k) {
