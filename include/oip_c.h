@@ -1048,6 +1048,72 @@ int oip_retile_u16(oip_ctx *ctx, const uint16_t *d_img, long src_pitch_samples, 
 int oip_untile_u16(oip_ctx *ctx, const uint16_t *d_tiles, int w, long h, int spp, int T, long tile_row0, long tile_rows,
                    uint16_t *d_img, long dst_pitch_samples);
 
+/* ---- rescale: antialiased resampling of a strip or product to another pixel grid (`oip rescale`; not in the reference) ----
+ * A separable polyphase filter: one table of Q14 taps per axis, built on the host, lines first, then across the line.  Exact
+ * integers on the device: any tile, any launch geometry and any cut of the output into windows give the same bytes.
+ * Lanczos-3 and Q14 taps are conventions; nothing was measured on real imagery. */
+#define OIP_RESCALE_SUFFIX ".RSC"      /* <stem>.RSC.<ext> */
+#define OIP_RESCALE_LANCZOS 0          /* Lanczos-3, a = 3 (the default) */
+#define OIP_RESCALE_CUBIC   1          /* Keys' cubic with -0.5, a = 2 */
+#define OIP_RESCALE_LINEAR  2          /* the triangle, a = 1 */
+
+/* The tap table of an axis that goes from n_in to n_out samples.  Host, no context needed.
+ *   h(x): lanczos  x = 0: 1,  |x| < 3: (sin(pi x) / (pi x)) (sin(pi x / 3) / (pi x / 3)),  else 0
+ *         cubic    |x| <= 1: 1.5 |x|^3 - 2.5 |x|^2 + 1,  |x| < 2: -0.5 |x|^3 + 2.5 |x|^2 - 4 |x| + 2,  else 0
+ *         linear   max(0, 1 - |x|)
+ * On reduction the kernel is stretched by n_in / n_out, which is the antialiasing.  For output index o, in this order:
+ *   1. num = (2 o + 1) n_in - n_out,  den = 2 n_out              (pixel centres: the centre of o lies at num / den)
+ *   2. K = 2 ceil(a max(n_in, n_out) / n_out), in integers        (the same for every o; 2 .. 24)
+ *   3. first[o] = floor(num / den) - K / 2 + 1
+ *   4. w_k = h((2 n_out (first[o] + k) - num) / (2 max(n_in, n_out))),  k = 0 .. K - 1: one fp64 division of two integers
+ *   5. t_k = floor(w_k / S * 16384 + 0.5),  S = w_0 + w_1 + ... in that order
+ *   6. 16384 - sum t_k is added to the largest t_k, among equal ones to the first
+ * taps[o * K + k] = t_k, int16 in Q14; every row sums to exactly 16384; equal sizes give rows 0 0 16384 0 0 0 (lanczos).
+ * first[] may point before the axis or reach beyond it: indices are clamped where they are used.  *K receives K; with first
+ * and taps both NULL that is all the call does.  cap: the int16 values taps has room for.
+ * OIP_E_INVALID: an unknown kind, an empty axis, an axis of 2^31 or more, n_in > 4 n_out (K would pass 24: halve with
+ * `oip overviews` first), n_out > 16 n_in, one table NULL, cap < n_out K.  OIP_E_RUNTIME: a row with sum |t_k| > 32767 (the three
+ * kinds stay below 25 300).  err (may be NULL) receives the text. */
+int oip_rescale_taps(int kind, long n_in, long n_out, int *first, int16_t *taps, size_t cap, int *K, char *err, int errlen);
+
+/* n_out = floor(n_in p / q + 1/2) for a scale p / q, in exact integers.  Host.  OIP_E_INVALID: n_in, p or q below 1, a result of
+ * 2^31 or more.  A result of 0 is returned as such (and refused as an empty axis later). */
+int oip_rescale_size(long n_in, long p, long q, long *n_out);
+
+/* The source samples [*src0, *src0 + *srcs) that the outputs [out0, out0 + outs) of an axis n_in -> n_out with rows of K taps
+ * read: clamp(first[out0]) .. clamp(first[out0 + outs - 1] + K - 1), clamped to 0 .. n_in - 1.  What oip_rescale_u16 wants
+ * resident of its lines.  outs == 0 gives an empty range.  Host.  OIP_E_INVALID: an axis below 1 or of 2^31 or more, K not
+ * even in 2 .. 24, outputs outside [0, n_out). */
+int oip_rescale_src_range(long n_in, long n_out, int K, long out0, long outs, long *src0, long *srcs);
+
+/* The resampler.  The source is W pixels x L lines of spp samples (1, or 4 pixel-interleaved), lines W spp samples apart; d_src
+ * holds its lines [src_row0, src_row0 + src_rows).  The output is Wo x Lo; d_dst receives its lines [out_row0, out_row0 +
+ * out_rows), lines Wo spp samples apart.  d_first_x / d_taps_x (Wo rows of Kx) and d_first_y / d_taps_y (Lo rows of Ky): the
+ * tables of oip_rescale_taps for W -> Wo and L -> Lo, on the device.  With s' = s - 32768, clampL / clampW to the image (the
+ * replicate border), per channel (a horizontal neighbour is spp samples away), >> an arithmetic shift:
+ *   v(y, xs)  = clamp((sum_k ty[y][k] s'(clampL(fy[y] + k), xs) + 8192) >> 14, -32768, 32767)
+ *   out(y, x) = clamp(((sum_k tx[x][k] v(y, clampW(fx[x] + k)) + 8192) >> 14) + 32768, 0, 65535)
+ * The intermediate is clamped to 16 bits, so every operand fits 16 bits; |sum| <= sum |t| * 32768 < 2^31 for any int16 rows with
+ * sum |t| <= 65535.  A constant image maps to itself; equal sizes give the input's bytes.
+ * No data.  valid_min == 0 switches the rule off.  Otherwise an output sample whose footprint -- the clamped index ranges
+ * clampL(fy[y] .. fy[y] + Ky - 1) x clampW(fx[x] .. fx[x] + Kx - 1) of its channel, whatever the taps are -- holds a source
+ * sample below valid_min takes the nearest source sample instead:
+ *   src[floor((2 y + 1) L / (2 Lo))][floor((2 x + 1) W / (2 Wo))]
+ * so no data stays no data and nothing rings across the edge of a fill.  A raster without such samples gives the bytes of
+ * valid_min == 0.
+ * Windows.  The call needs the source lines oip_rescale_src_range(L, Lo, Ky, out_row0, out_rows) states; any cut of the output
+ * lines into calls gives the bytes of one call.  Lines and offsets are 64-bit.  One launch per call; asynchronous on the
+ * context's stream.  Lines that are not multiples of 8 samples, or bases that are not on 16-byte boundaries, take 2-byte
+ * loads (source) or stores (output) in the same kernel, with the same result.
+ * OIP_E_INVALID: a NULL or odd pointer, d_dst == d_src, spp not 1 or 4, a size below 1, L or Lo or a line of 2^31 or more, K not
+ * even in 2 .. 24, W > 4 Wo, Wo > 16 W (and the same for lines), valid_min outside 0..65535, windows outside their rasters, a
+ * source window that does not hold the lines needed ("source lines [a, b] needed, [c, d) resident").  out_rows == 0 is a
+ * no-op.  Tables that oip_rescale_taps did not build are not checked: they give unspecified samples, never an access outside
+ * the rasters. */
+int oip_rescale_u16(oip_ctx *ctx, const uint16_t *d_src, long src_row0, long src_rows, int W, long L, int spp, uint16_t *d_dst, long out_row0,
+                    long out_rows, int Wo, long Lo, const int *d_first_x, const int16_t *d_taps_x, int Kx, const int *d_first_y,
+                    const int16_t *d_taps_y, int Ky, int valid_min);
+
 /* ---- regcheck: tile-matching registration check of two rasters (`oip regcheck`; not in the reference) ---- */
 /* Dense template matching by zero-mean normalised cross-correlation in the spatial domain, built from exact integer sums: a
  * measure of registration that shares no code with the phase correlation it judges.

@@ -160,6 +160,10 @@ _SIGS = {
     "oip_overview_levels": ([_i, _l], _i),
     "oip_retile_u16": ([_vp, _vp, _l, _i, _l, _i, _i, _l, _l, _vp], _i),
     "oip_untile_u16": ([_vp, _vp, _i, _l, _i, _i, _l, _l, _vp, _l], _i),
+    "oip_rescale_taps": ([_i, _l, _l, C.POINTER(_i), C.POINTER(C.c_int16), _sz, C.POINTER(_i), _cp, _i], _i),
+    "oip_rescale_size": ([_l, _l, _l, _lp], _i),
+    "oip_rescale_src_range": ([_l, _l, _i, _l, _l, _lp, _lp], _i),
+    "oip_rescale_u16": ([_vp, _vp, _l, _l, _i, _l, _i, _vp, _l, _l, _i, _l, _vp, _vp, _i, _vp, _vp, _i, _i], _i),
     "oip_match_tiles_u16": ([_vp, _vp, _l, _i, _vp, _l, _i, _i, _l, _i, _i, _i, _l, _i, _l, _i, _l, _i, _i, _vp, _vp], _i),
     "oip_match_grid": ([_i, _l, _i, _i, _i, C.POINTER(_i), _lp, C.POINTER(_i), _lp], _i),
     "oip_match_peak": ([C.POINTER(C.c_uint64), _i, _i, _d, _dp, _dp, _dp, C.POINTER(_i)], _i),
@@ -598,6 +602,44 @@ def write_tiff_u8(path: str, img) -> None:
         raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
 
 
+RESCALE_KERNELS = {"lanczos": 0, "cubic": 1, "linear": 2}
+
+
+def rescale_taps(kind, n_in: int, n_out: int):
+    """(first (n_out,) int32, taps (n_out, K) int16 in Q14, every row summing to 16384) of an axis that goes from n_in to n_out
+    samples; kind is "lanczos", "cubic", "linear" or its number (include/oip_c.h: oip_rescale_taps)"""
+    lib = load_library()
+    kind = RESCALE_KERNELS.get(kind, kind)
+    err = C.create_string_buffer(512)
+    K = _i()
+    rc = lib.oip_rescale_taps(kind, n_in, n_out, None, None, 0, C.byref(K), err, 512)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    first = np.zeros(n_out, np.int32)
+    taps = np.zeros((n_out, K.value), np.int16)
+    rc = lib.oip_rescale_taps(kind, n_in, n_out, first.ctypes.data_as(C.POINTER(_i)), taps.ctypes.data_as(C.POINTER(C.c_int16)), taps.size,
+                              C.byref(K), err, 512)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+    return first, taps
+
+
+def rescale_size(n_in: int, p: int, q: int) -> int:
+    """floor(n_in p / q + 1/2) in exact integers (include/oip_c.h: oip_rescale_size)"""
+    n = _l()
+    if load_library().oip_rescale_size(n_in, p, q, C.byref(n)):
+        raise ValueError("oip_rescale_size: n_in, p, q >= 1 and a result below 2^31 expected")
+    return n.value
+
+
+def rescale_src_range(n_in: int, n_out: int, K: int, out0: int, outs: int):
+    """(src0, srcs): the source samples that outputs [out0, out0 + outs) of an axis read (include/oip_c.h: oip_rescale_src_range)"""
+    a, b = _l(), _l()
+    if load_library().oip_rescale_src_range(n_in, n_out, K, out0, outs, C.byref(a), C.byref(b)):
+        raise ValueError("oip_rescale_src_range: bad argument")
+    return a.value, b.value
+
+
 def overview_levels(w: int, h: int) -> int:
     """the default level count of the pyramid of a w x h image (include/oip_c.h: oip_overview_levels)"""
     return load_library().oip_overview_levels(w, h)
@@ -861,6 +903,13 @@ class Context:
         """the inverse: the image samples of those tile rows from the tile-major buffer, whatever its padding holds
         (include/oip_c.h: oip_untile_u16)"""
         self._ck(self.lib.oip_untile_u16(self.h, _ptr(tiles), w, h, spp, T, tile_row0, tile_rows, _ptr(img), dst_pitch))
+
+    def rescale_u16(self, src, src_row0, src_rows, W, L, spp, dst, out_row0, out_rows, Wo, Lo, first_x, taps_x, Kx, first_y, taps_y, Ky, valid_min=0):
+        """output lines [out_row0, out_row0 + out_rows) of the W x L x spp raster resampled to Wo x Lo with the int32 first / int16
+        Q14 tap tables of rescale_taps on the device; src holds the source lines [src_row0, src_row0 + src_rows), which must
+        cover rescale_src_range(L, Lo, Ky, out_row0, out_rows) (include/oip_c.h: oip_rescale_u16)"""
+        self._ck(self.lib.oip_rescale_u16(self.h, _ptr(src), src_row0, src_rows, W, L, spp, _ptr(dst), out_row0, out_rows, Wo, Lo, _ptr(first_x),
+                                          _ptr(taps_x), Kx, _ptr(first_y), _ptr(taps_y), Ky, valid_min))
 
     def match_tiles_u16(self, a, pitch_a, stride_a, b, pitch_b, stride_b, w, rows, T, S, x0, y0, step_x, step_y, nx, ny, valid_min, valid_max,
                         records, sums=None):

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "oip_c.h"
+#include "oip_rescaleplan.h"
 #include "oip_tiff.hpp"
 #include "oip_warpfield.hpp"
 
@@ -1289,4 +1290,17 @@ extern "C" int oip_wallis_fit(const uint64_t *acc, long acc_pitch, size_t acc_pl
         }
     }
     return OIP_OK;
+}
+
+// ---- rescale: the tap tables, the size of a scaled axis and the lines a window needs (include/oip_c.h; arithmetic: oip_rescaleplan.h)
+extern "C" int oip_rescale_taps(int kind, long n_in, long n_out, int *first, int16_t *taps, size_t cap, int *K, char *err, int errlen)
+{
+    return oip_rescale_taps_impl(kind, n_in, n_out, first, taps, cap, K, err, errlen);
+}
+
+extern "C" int oip_rescale_size(long n_in, long p, long q, long *n_out) { return oip_rescale_size_impl(n_in, p, q, n_out); }
+
+extern "C" int oip_rescale_src_range(long n_in, long n_out, int K, long out0, long outs, long *src0, long *srcs)
+{
+    return oip_rescale_src_range_impl(n_in, n_out, K, out0, outs, src0, srcs);
 }

@@ -39,6 +39,9 @@
 //                               report by the shift field the report holds, so that it lands on image 1, see run_regfix()
 //   oip cog IMAGE [-o OUT] [--tile T] [--levels N] [--valid-min N]   the image as a tiled TIFF with its pyramid inside,
 //                               <stem>.COG.TIFF, see run_cog()
+//   oip rescale IMAGE [-o OUT] (--scale S | --scale-x SX | --scale-y SY | --to-width N | --to-lines N) [--kernel lanczos|cubic|linear]
+//                               [--valid-min V]   the image on another pixel grid by an antialiased polyphase filter, <stem>.RSC.<ext>,
+//                               see run_rescale()
 //   oip pansharpen --pan P --mss M [--line-offset N] [--max-gain G] [--width N] [-o OUT] [--force] [--overviews [--levels N]]
 //                               fuses the PAN strip and the aligned MSS product into a 4-band product at PAN resolution, see
 //                               run_pansharpen()
@@ -48,7 +51,7 @@
 // or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
 // --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
-// despike, denoise, noise, mask, wallis, mtf, overviews, cog, regcheck, regfix and pansharpen sub-commands.
+// despike, denoise, noise, mask, wallis, mtf, overviews, cog, rescale, regcheck, regfix and pansharpen sub-commands.
 //
 // Exit codes as the reference: usage_error -> "USAGE ERROR" + 254; any std::exception -> 2; unknown
 // -> 1; help/version -> 255 (CLI11's Success + 255, main.cpp:262-263); argument errors -> CLI11's
@@ -151,7 +154,7 @@ Parsed parse(const Spec &sp, const std::vector<std::string> &args)
     return p;
 }
 
-// The tools with one positional argument (quicklook, mtfc, despike, denoise, noise, mask, wallis, mtf, overviews, cog; regcheck, regfix and pansharpen name their
+// The tools with one positional argument (quicklook, mtfc, despike, denoise, noise, mask, wallis, mtf, overviews, cog, rescale; regcheck, regfix and pansharpen name their
 // images by options): IMAGE, an existing regular file, is the first argument that is neither an option nor the value of one (an
 // option's value stays with it, alias or not); the rest is parsed as usual.
 Parsed parse_with_image(const Spec &sp, const std::vector<std::string> &args, std::string *image)
@@ -306,6 +309,16 @@ void usage()
          "             written to <stem>.COG.TIFF in the working directory:\n"
          "             [-o,--out FILE] [--tile T] (a multiple of 16, 16..1024; default 256, at 4 samples 128) [--levels N] (0..16, 0: none; default: until\n"
          "             a level fits 256 x 256) [--valid-min N] (as for overviews; default 1) [--width N] [--force]\n"
+         "  rescale    IMAGE.TIFF|IMAGE.RAW: a product (TIFF of 1 or 4 samples) or a single-band strip on another pixel grid, by a separable\n"
+         "             polyphase filter that is stretched on reduction (antialiasing) and replicates the border; a line-rate correction\n"
+         "             (--scale-y), a fixed ground sample distance (--scale 0.8), the MSS product on the PAN grid (--scale 4); written to\n"
+         "             <stem>.RSC.<ext>; -o with the other extension (.TIFF / .RAW) changes the container:\n"
+         "             [-o,--out FILE] (--scale S | --scale-x SX | --scale-y SY | --to-width N | --to-lines N) (S: a decimal such as 0.8, read\n"
+         "             as 8/10, or a fraction p/q; 1/4 .. 16 per axis; an axis that is not named keeps its size; --scale excludes the other\n"
+         "             four, --scale-x excludes --to-width, --scale-y excludes --to-lines) [--kernel lanczos|cubic|linear] (default lanczos,\n"
+         "             Lanczos-3) [--valid-min V] (an output sample whose footprint holds a sample below V takes the nearest source sample:\n"
+         "             no data stays no data; 0: off; default 1) (Lanczos-3 and Q14 taps are conventions, nothing was measured on real\n"
+         "             imagery) [--width N] [--force]\n"
          "  regcheck   --image1 A [--image2 B]: how well B is registered to A (TIFF of 1 or 4 samples, or single-band RAW), measured by\n"
          "             template matching (zero-mean normalised cross-correlation from exact integer sums) on a grid of tiles; writes\n"
          "             x,y,dx,dy,score,flags per tile and a summary (count, mean, std, RMS, CE90, max) to <stem of A>.REG.CSV:\n"
@@ -1027,6 +1040,47 @@ int run_cog(const std::vector<std::string> &args, int width)
     return 0;
 }
 
+// oip rescale IMAGE: a strip (.RAW, --width samples per line) or a product (.TIFF of 1 or 4 samples) on another pixel grid, as
+// <stem>.RSC.<ext> (RunRescale).  IMAGE is the one positional argument, as for mtfc.  A scale is a rational: bad syntax and bad
+// values end in 105, options that exclude each other in 107, none of the five in 106, before any file is read.
+int run_rescale(const std::vector<std::string> &args, int width)
+{
+    Spec sp;
+    sp.valued = {"--out", "--scale", "--scale-x", "--scale-y", "--to-width", "--to-lines", "--kernel", "--valid-min", "--width"};
+    sp.flags = {"--force"};
+    sp.alias = {{"-o", "--out"}};
+    std::string image;
+    Parsed p = parse_with_image(sp, args, &image);
+    RescaleOptions o;
+    o.width = p.positive_width(width);
+    for (const char *k : {"--scale-x", "--scale-y", "--to-width", "--to-lines"})
+        if (p.has("--scale") && p.has(k)) throw cli_error(107, std::string("--scale excludes ") + k);
+    if (p.has("--scale-x") && p.has("--to-width")) throw cli_error(107, "--scale-x excludes --to-width");
+    if (p.has("--scale-y") && p.has("--to-lines")) throw cli_error(107, "--scale-y excludes --to-lines");
+    if (!p.has("--scale") && !p.has("--scale-x") && !p.has("--scale-y") && !p.has("--to-width") && !p.has("--to-lines"))
+        throw cli_error(106, "--scale, --scale-x, --scale-y, --to-width or --to-lines is required");
+    auto scale = [&](const char *key, long *num, long *den) {
+        if (p.has(key) && !oip_rescale_parse_scale(p.str(key).c_str(), num, den))
+            throw cli_error(105, std::string(key) + ": a positive decimal such as 0.8 or a fraction p/q expected (at most 9 digits)");
+    };
+    scale("--scale", &o.px, &o.qx);
+    if (p.has("--scale")) o.py = o.px, o.qy = o.qx;
+    scale("--scale-x", &o.px, &o.qx);
+    scale("--scale-y", &o.py, &o.qy);
+    o.toWidth = p.has("--to-width") ? p.within("--to-width", 0, 1, INT_MAX, "a positive number of pixels expected") : 0;
+    o.toLines = p.has("--to-lines") ? p.within("--to-lines", 0, 1, INT_MAX, "a positive number of lines expected") : 0;
+    const std::string kernel = p.str("--kernel", "lanczos");
+    if (kernel == "lanczos") o.kind = OIP_RESCALE_LANCZOS;
+    else if (kernel == "cubic") o.kind = OIP_RESCALE_CUBIC;
+    else if (kernel == "linear") o.kind = OIP_RESCALE_LINEAR;
+    else throw cli_error(105, "--kernel: lanczos, cubic or linear expected");
+    o.validMin = p.valid_min();
+    o.force = p.has("--force");
+    if (p.has("--out") && p.str("--out").empty()) throw cli_error(105, "--out: a file name expected");
+    RunRescale(image, p.str("--out"), o);
+    return 0;
+}
+
 // oip regcheck --image1 A [--image2 B]: the registration check of two rasters (RunRegcheck).  Bad values end in 105, an
 // option that needs another in 107, before any file is read.
 int run_regcheck(const std::vector<std::string> &args, int width)
@@ -1207,6 +1261,7 @@ static int oip_main(int argc, const char *argv[])
             if (!args.empty() && args[0] == "mtf") return run_mtf({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "overviews") return run_overviews({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "cog") return run_cog({args.begin() + 1, args.end()}, width);
+            if (!args.empty() && args[0] == "rescale") return run_rescale({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regcheck") return run_regcheck({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "regfix") return run_regfix({args.begin() + 1, args.end()}, width);
             if (!args.empty() && args[0] == "pansharpen") return run_pansharpen({args.begin() + 1, args.end()}, width);

@@ -1,5 +1,5 @@
 // oip_rastertools.hpp -- the raster tools that are not in the reference (rrc-calib, quicklook, mtfc, despike, denoise, noise, mask, wallis, mtf,
-// overviews, cog, regcheck, regfix, pansharpen) above the host layer of oip_host.hpp.  Stated once for all of them: the file checks made before a
+// overviews, cog, rescale, regcheck, regfix, pansharpen) above the host layer of oip_host.hpp.  Stated once for all of them: the file checks made before a
 // device is touched (container, RAW size rule, line range, GuardOutput), the loaders of a resident image, the driver that streams
 // a RAW strip through the device in line blocks (geometry: oip_stripplan.hpp), the filter driver above it, the closing
 // throughput line and the text-report writer.  Then the tools, each as Options / Check / Run.  The ranges of option values are
@@ -13,6 +13,7 @@
 #include "oip_mtfreport.hpp"
 #include "oip_noisereport.hpp"
 #include "oip_regreport.hpp"
+#include "oip_rescaleplan.h"
 #include "oip_wallisreport.hpp"
 #include "oip_stripplan.hpp"
 #include "oip_warpfield.hpp"
@@ -1346,6 +1347,110 @@ inline void RunCog(const std::string &file, const std::string &out, const CogOpt
     }
     tw.close();
     LogThroughput(m.bytes(), total.tick());
+}
+
+// ---- oip rescale: a strip or product on another pixel grid ------------------------------------------------------------------
+// Antialiased resampling by a separable polyphase filter (include/oip_c.h: oip_rescale_taps, oip_rescale_u16): a scale along the
+// lines corrects a line rate that does not match the ground speed, a scale on both axes delivers at a stated sample distance,
+// and x 4 brings the aligned MSS product to the PAN grid without fusing it.  A scale is a rational p / q (a decimal is read as
+// one), an axis that is not named keeps its size, --to-width / --to-lines name a size outright.  The image is resident, in and
+// out (2 (W L + Wo Lo) spp bytes of device memory); the tables are built on the host; one kernel call; the output leaves
+// through the product writer (TIFF) or as it lies (RAW).  Lanczos-3 and Q14 taps are conventions: nothing was measured on real
+// imagery.  Not in the reference.
+struct RescaleOptions {
+    int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
+    long px = 1, qx = 1, py = 1, qy = 1;    // the scales across and along as rationals
+    long toWidth = 0, toLines = 0;          // --to-width / --to-lines: the size outright; 0: by the scale
+    int kind = OIP_RESCALE_LANCZOS;
+    int validMin = 1;                       // 0: no no-data rule
+    bool force = false;
+};
+
+struct RescaleGeometry {
+    std::string path;
+    bool inTiff = false, outTiff = false;
+    int W = 0, Wo = 0, spp = 1;
+    long L = 0, Lo = 0;
+};
+
+// what is refused without a device and depends on the image (the option syntax is run_rescale's): the container, the size of a
+// RAW file, the samples of a TIFF, an empty axis or a ratio outside 1/4 .. 16 on either axis, the container of the output (a RAW
+// file holds one sample per pixel), the output itself
+inline RescaleGeometry RescaleCheck(const std::string &file, const std::string &out, const RescaleOptions &o)
+{
+    RescaleGeometry g;
+    const std::string ext = RasterContainer(file, "rescale");
+    g.inTiff = ext == ".tiff";
+    if (g.inTiff) {
+        TiffLayout lay;
+        read_tiff_u16(file, &g.W, &g.L, &g.spp, nullptr, &lay);
+        if (g.spp != 1 && g.spp != MSS_BANDS) throw std::invalid_argument("rescale: a TIFF of 1 or 4 samples per pixel expected");
+    } else {
+        g.W = o.width;
+        g.L = RawLineCount(file, "image", (size_t)o.width * BYTES_PER_PIXEL);
+    }
+    long wo = o.toWidth, lo = o.toLines;
+    if (wo == 0 && oip_rescale_size_impl(g.W, o.px, o.qx, &wo) != OIP_OK) throw std::invalid_argument("rescale: the scale across the line gives no valid width");
+    if (lo == 0 && oip_rescale_size_impl(g.L, o.py, o.qy, &lo) != OIP_OK) throw std::invalid_argument("rescale: the scale along the strip gives no valid line count");
+    if (const char *why = oip_rescale_axis_refusal(g.W, wo))
+        throw std::invalid_argument("rescale: " + std::to_string(g.W) + " -> " + std::to_string(wo) + " pixels a line: " + why + " (ratios of 1/4 .. 16 are supported)");
+    if (const char *why = oip_rescale_axis_refusal(g.L, lo))
+        throw std::invalid_argument("rescale: " + std::to_string(g.L) + " -> " + std::to_string(lo) + " lines: " + why + " (ratios of 1/4 .. 16 are supported)");
+    if (wo * g.spp >= (1L << 31)) throw std::invalid_argument("rescale: an output line of 2^31 samples or more");
+    g.Wo = (int)wo;
+    g.Lo = lo;
+    g.path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_RESCALE_SUFFIX) : out;
+    const std::string oext = to_lower(std::filesystem::path(g.path).extension().string());
+    if (oext != ".tiff" && oext != ".raw") throw std::invalid_argument("rescale: the output is a RAW or a TIFF file");
+    g.outTiff = oext == ".tiff";
+    if (!g.outTiff && g.spp != 1) throw std::invalid_argument("rescale: a RAW file holds one sample per pixel, the image has " + std::to_string(g.spp));
+    GuardOutput(g.path, {file}, "rescale", o.force);
+    return g;
+}
+
+inline void RunRescale(const std::string &file, const std::string &out, const RescaleOptions &o)
+{
+    const RescaleGeometry g = RescaleCheck(file, out, o);
+    static const char *const names[] = {"lanczos", "cubic", "linear"};
+    // the tables of both axes, on the host
+    std::vector<int> first[2];
+    std::vector<int16_t> taps[2];
+    int K[2] = {0, 0};
+    for (int axis = 0; axis < 2; ++axis) {
+        const long n_in = axis ? g.L : g.W, n_out = axis ? g.Lo : g.Wo;
+        char err[256] = "";
+        int rc = oip_rescale_taps(o.kind, n_in, n_out, nullptr, nullptr, 0, &K[axis], err, sizeof err);
+        if (rc == OIP_OK) {
+            first[axis].resize(n_out);
+            taps[axis].resize((size_t)n_out * K[axis]);
+            rc = oip_rescale_taps(o.kind, n_in, n_out, first[axis].data(), taps[axis].data(), taps[axis].size(), &K[axis], err, sizeof err);
+        }
+        if (rc == OIP_E_INVALID) throw std::invalid_argument(err);
+        if (rc != OIP_OK) throw std::runtime_error(err);
+    }
+    OLOG("rescale: %d x %ld -> %d x %ld pixels of %d samples, kernel %s, %d x %d taps, valid-min %d", g.W, g.L, g.Wo, g.Lo, g.spp, names[o.kind], K[0], K[1],
+         o.validMin);
+    oip_ctx *ctx = Device::get().ctx();
+    auto ck = [](int rc) { Device::get().check(rc); };
+    stop_watch total;
+    ResidentImage m;
+    LoadResident(file, g.inTiff, o.width, "image", "rescale", &m);
+    if (m.w != g.W || m.h != g.L || m.spp != g.spp) throw std::runtime_error("rescale: the image changed while it was read");
+    DevBuf<int> fx, fy;
+    DevBuf<int16_t> tx, ty;
+    fx.assign(first[0]), tx.assign(taps[0]), fy.assign(first[1]), ty.assign(taps[1]);
+    const size_t samples = (size_t)g.Wo * g.Lo * g.spp;
+    DevBuf<uint16_t> res(samples);
+    ck(oip_rescale_u16(ctx, m.buf.p, 0, g.L, g.W, g.L, g.spp, res.p, 0, g.Lo, g.Wo, g.Lo, fx.p, tx.p, K[0], fy.p, ty.p, K[1], o.validMin));
+    if (g.outTiff) {
+        OLOG("Write rescaled image of %d x %ld pixels to file '%s' ...", g.Wo, g.Lo, g.path.c_str());
+        write_tiff_from_device(g.path, res.p, g.Wo, g.Lo, g.spp, tiff_compression(g.spp == 1 ? TIFF_NONE : TIFF_LZW), false);
+    } else {
+        OLOG("Write rescaled strip of %d x %ld samples (--width %d) to file '%s' ...", g.Wo, g.Lo, g.Wo, g.path.c_str());
+        ck(oip_sync(ctx));
+        res.save_file(g.path, samples);
+    }
+    LogThroughput(m.bytes() + samples * BYTES_PER_PIXEL, total.tick());
 }
 
 // ---- oip regcheck: how well two rasters are registered ------------------------------------------------------------------
