@@ -988,6 +988,30 @@ int oip_tiff_lzw_decode_u16(oip_ctx *ctx, const uint8_t *d_file, size_t file_byt
                             const uint64_t *strip_len, long nstrips, long rows, int width, int spp, long rows_per_strip,
                             int predictor, uint16_t *d_img);
 
+/* The same for a Deflate TIFF (compression 8, or its older number 32946): every strip -- or tile, passed as a T-wide image in
+ * strips of T rows -- is one zlib stream (RFC 1950 around RFC 1951), inflated by one wave of the device (csrc/tiffdeflate.hip)
+ * with the decoder the host reader runs (csrc/oip_inflate.h; no libz).  Arguments, argument checks and the order of the samples
+ * are those of oip_tiff_lzw_decode_u16; spp up to 16, predictor 1 or 2.  What a stream must be, on the host and on the device
+ * alike (the yardstick is zlib's inflate):
+ *   header    CM = 8, CINFO <= 7, FCHECK valid, FDICT clear.
+ *   blocks    stored, fixed and dynamic; BTYPE 3 is corrupt.  Corrupt as well: a stored block whose LEN is not ~NLEN; HLIT > 286
+ *             or HDIST > 30; a code-length code, literal/length set or distance set that is over-subscribed; one that is
+ *             incomplete -- except, as in zlib, a literal/length or distance set of a single code of length 1, and a distance
+ *             set with no code at all; a repeat code 16 with no length before it; a repeat that runs past HLIT + HDIST; no code
+ *             for end-of-block; literal/length symbols 286 and 287; distance symbols 30 and 31; bits that are no code of an
+ *             incomplete set; a distance that reaches before the start of the stream's own output (there is no dictionary).
+ *   size      exactly the bytes of its strip or tile; more or fewer is an error.
+ *   trailer   where all four Adler-32 bytes are present they must match; a stream that ends after its final block with fewer
+ *             than four bytes left is accepted (libtiff stops reading when the output is full, and such files exist).  A stream
+ *             that ends inside a block is an error.  Bytes after the trailer are ignored.
+ * A stream that breaks a rule ends its own decode: OIP_E_RUNTIME with the first such strip and the cause named; the other
+ * strips are decoded and nothing outside d_img's rows x width x spp samples is written.  Input reads are bounded by the
+ * stream's length, window indices are masked and every store is bounded by the strip's size, whatever the stream holds.
+ * Synchronises the stream. */
+int oip_tiff_deflate_decode_u16(oip_ctx *ctx, const uint8_t *d_file, size_t file_bytes, const uint64_t *strip_off,
+                                const uint64_t *strip_len, long nstrips, long rows, int width, int spp, long rows_per_strip,
+                                int predictor, uint16_t *d_img);
+
 /* ---- overviews: reduced-resolution levels of a strip or product (`oip overviews`; not in the reference) ---- */
 #define OIP_OVERVIEW_SUFFIX ".ovr"   /* appended to the whole file name, GDAL's external-overview convention */
 

@@ -264,6 +264,13 @@ inline bool gpu_lzw()
     return on;
 }
 
+// OIP_TIFF_GPU_DEFLATE=0: the streams of a Deflate input on the host's threads (read_tiff_u16; same image) -- test and A/B knob
+inline bool gpu_deflate()
+{
+    static const bool on = [] { const char *e = getenv("OIP_TIFF_GPU_DEFLATE"); return !(e && atoi(e) == 0); }();
+    return on;
+}
+
 inline void tiff_rows_from_device(TiffWriterU16 &tw, const uint16_t *d_img, long rows, size_t rowSamples, long mark)
 {
     oip_ctx *ctx = Device::get().ctx();
@@ -533,7 +540,15 @@ inline void write_overviews_of_device_image(const std::string &path, const uint1
 // products are -- go from the file into device memory as they are and their strips are decoded there (csrc/tifflzw.hip: a
 // strip per lane; a tiled file with square tiles of a multiple of 16: a tile per lane into a tile-major buffer, then
 // oip_untile_u16); anything else, and OIP_TIFF_GPU_LZW=0, decodes on the host's threads (read_tiff_u16) and uploads.  Same
-// checks and error texts either way: the header is validated by the host reader in both.
+// checks and error texts either way: the header is validated by the host reader in both.  Deflate files take the same two
+// routes, their streams inflated by csrc/tiffdeflate.hip (a stream per wave), under the same conditions and two more, which
+// are what was measured: a wave inflates 4.1 MB/s whatever the layout and the 16 host threads about 60 MB/s
+// each, so the device needs at least 16 x 60 / 4.1 = 234 streams in flight to win, and a stream's time on a shared device is
+// its bytes / 4.1 MB/s.  Hence: at least kDeflateDeviceMinStreams strips or tiles, none decoding to more than
+// kDeflateDeviceMaxStreamBytes (2 MiB, the largest stream measured: half a second).  Everything else -- few streams, long
+// streams -- and OIP_TIFF_GPU_DEFLATE=0 goes to the host.
+constexpr size_t kDeflateDeviceMinStreams = 256;
+constexpr uint64_t kDeflateDeviceMaxStreamBytes = (uint64_t)2 << 20;
 inline void read_tiff_to_device(const std::string &path, int *width, long *height, int *spp, DevBuf<uint16_t> &img)
 {
     TiffLayout lay;
@@ -541,11 +556,17 @@ inline void read_tiff_to_device(const std::string &path, int *width, long *heigh
     const size_t samples = (size_t)lay.width * lay.height * lay.spp;
     // (tiled: square tiles the layout kernel takes -- a multiple of 16 up to 1024 --, each one a "strip" of the decoder)
     const uint64_t T = lay.tile_width;
-    bool device = gpu_lzw() && lay.compression == TIFF_LZW && (lay.spp == 1 || lay.spp == 4) &&
+    const bool deflate = lay.compression == TIFF_DEFLATE;
+    const auto decode = deflate ? oip_tiff_deflate_decode_u16 : oip_tiff_lzw_decode_u16;
+    bool device = (deflate ? gpu_deflate() : gpu_lzw() && lay.compression == TIFF_LZW) && (lay.spp == 1 || lay.spp == 4) &&
                   (lay.tiled() ? T == lay.tile_length && T % 16 == 0 && T <= 1024 : lay.rows_per_strip * lay.width * lay.spp * 2 < ((uint64_t)1 << 32));
     uint64_t lo = ~(uint64_t)0, hi = 0;
     for (size_t k = 0; k < lay.offs.size(); ++k) { lo = std::min(lo, lay.offs[k]); hi = std::max(hi, lay.offs[k] + lay.lens[k]); }
     if (device && hi - lo > 3 * samples + ((uint64_t)64 << 20)) device = false;       // strips scattered over a far larger file
+    if (device && deflate) {
+        const uint64_t streamBytes = (lay.tiled() ? T * T : lay.rows_per_strip * lay.width) * lay.spp * 2;
+        if (lay.offs.size() < kDeflateDeviceMinStreams || streamBytes > kDeflateDeviceMaxStreamBytes) device = false;
+    }
     if (!device) {
         std::vector<uint16_t> host;
         read_tiff_u16(path, width, height, spp, &host);
@@ -580,8 +601,8 @@ inline void read_tiff_to_device(const std::string &path, int *width, long *heigh
             Device::get().check(oip_stage_sync(ctx));
             std::vector<uint64_t> off(lay.offs.begin() + k0, lay.offs.begin() + k0 + nt);
             for (auto &o : off) o -= blo;
-            const int rc = oip_tiff_lzw_decode_u16(ctx, file.p, file.n, off.data(), lay.lens.data() + k0, (long)nt, (long)(nt * T), (int)T, (int)lay.spp,
-                                                   (long)T, (int)lay.predictor, tiles.p);
+            const int rc = decode(ctx, file.p, file.n, off.data(), lay.lens.data() + k0, (long)nt, (long)(nt * T), (int)T, (int)lay.spp, (long)T,
+                                  (int)lay.predictor, tiles.p);
             if (rc != OIP_OK) throw std::runtime_error("read TIFF [" + path + "]: " + std::string(oip_last_error(ctx)) + " (tiles from " + std::to_string(k0) + " on)");
             Device::get().check(oip_untile_u16(ctx, tiles.p, (int)lay.width, (long)lay.height, (int)lay.spp, (int)T, j0, nr, img.p, (long)(lay.width * lay.spp)));
         }
@@ -595,8 +616,8 @@ inline void read_tiff_to_device(const std::string &path, int *width, long *heigh
     Device::get().check(oip_stage_sync(ctx));
     for (auto &o : lay.offs) o -= lo;
     img.alloc(samples);
-    const int rc = oip_tiff_lzw_decode_u16(ctx, file.p, file.n, lay.offs.data(), lay.lens.data(), (long)lay.offs.size(), (long)lay.height,
-                                           (int)lay.width, (int)lay.spp, (long)lay.rows_per_strip, (int)lay.predictor, img.p);
+    const int rc = decode(ctx, file.p, file.n, lay.offs.data(), lay.lens.data(), (long)lay.offs.size(), (long)lay.height, (int)lay.width,
+                          (int)lay.spp, (long)lay.rows_per_strip, (int)lay.predictor, img.p);
     if (rc != OIP_OK) throw std::runtime_error("read TIFF [" + path + "]: " + std::string(oip_last_error(ctx)));
 }
 

@@ -48,7 +48,7 @@
 //   oip -v | --version          prints 1.1
 // plus --width N (pixels per PAN line; the reference hard-codes 12288, oipshared.h:28).
 // `auxsep` is outside this build.  TIFF input and output go through oip_tiff.hpp (uncompressed and LZW, with
-// or without the horizontal predictor).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
+// or without the horizontal predictor; Deflate as input only).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
 // --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
 // despike, denoise, noise, mask, wallis, mtf, overviews, cog, rescale, regcheck, regfix and pansharpen sub-commands.

@@ -12,6 +12,8 @@
 // (259 = 5) with predictor 1 or 2 (317) -- so the files the reference itself produces can be consumed and the
 // files written here open in cv::imread / GDAL.  Pixel payloads match the reference's; file bytes need not
 // (strip sizes and tag order are the libraries' own).  Strips are encoded / decoded on a few threads.
+// The reader also takes Deflate (259 = 8, or 32946: zlib streams, what COMPRESS=DEFLATE and most archive COGs hold) through
+// the decoder of oip_inflate.h; nothing here writes it.
 //
 // LZW as TIFF 6.0 section 13 specifies it and libtiff implements it: MSB-first codes of 9..12 bits, ClearCode
 // 256, EndOfInformation 257, first free code 258, every strip starts with ClearCode; the encoder widens the
@@ -39,9 +41,12 @@
 #include <thread>
 #include <vector>
 
+#include "oip_inflate.h"
+
 namespace OIPGPU {
 
-enum TiffCompression { TIFF_NONE = 1, TIFF_LZW = 5 };
+// (TIFF_DEFLATE is read, never written: 8 is Adobe Deflate, and its older number 32946 is read as the same thing)
+enum TiffCompression { TIFF_NONE = 1, TIFF_LZW = 5, TIFF_DEFLATE = 8 };
 
 namespace tiffdetail {
 
@@ -249,6 +254,18 @@ inline size_t lzw_decode(const uint8_t *src, size_t n, uint8_t *dst, size_t cap)
         if (produced >= cap && pos >= n) break;
     }
     return produced;
+}
+
+// One zlib stream of a Deflate TIFF (csrc/oip_inflate.h, the decoder the device runs as well) into dst[0, cap); returns the number
+// of bytes produced (at most cap); throws on a corrupt stream with the cause named.  `what` names the stream ("strip 3").
+inline size_t deflate_decode(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const std::string &what)
+{
+    thread_local std::unique_ptr<oipinflate::Shared> work;
+    if (!work) work.reset(new oipinflate::Shared);
+    size_t got = 0;
+    const int st = oipinflate::inflate_host(src, n, dst, cap, &got, work.get());
+    if (st != oipinflate::kOk) throw std::runtime_error(std::string("corrupt Deflate stream (") + oipinflate::status_text(st) + ") in " + what);
+    return got;
 }
 
 inline void predictor2_encode(uint16_t *row, size_t width, int spp)
@@ -622,8 +639,8 @@ private:
     bool mPositioned = false;           // positioned writes have moved past the FILE's own position
 };
 
-// Reader for little-endian, chunky, unsigned 16-bit TIFF / BigTIFF in strips or tiles, uncompressed or LZW (predictor 1 or
-// 2): what the writers here (above, and oip_tifftiled.hpp), cv::imwrite and GDAL's GTiff driver (INTERLEAVE=PIXEL, with or
+// Reader for little-endian, chunky, unsigned 16-bit TIFF / BigTIFF in strips or tiles, uncompressed, LZW or Deflate (predictor 1
+// or 2): what the writers here (above, and oip_tifftiled.hpp), cv::imwrite and GDAL's GTiff driver (INTERLEAVE=PIXEL, with or
 // without TILED=YES) produce.  Samples are returned in file order.  Every header field is checked before it sizes an allocation
 // or a read.  Only the first directory is read: the internal overviews of a COG are ignored.
 // Tiles (322 TileWidth, 323 TileLength, 324 TileOffsets, 325 TileByteCounts) may have any positive size; they are numbered
@@ -702,7 +719,9 @@ inline void read_tiff_u16(const std::string &path, int *width, long *height, int
     }
     if (stripTags && tileTags) fail("strip tags and tile tags are both present");
     const bool tiled = tileTags;
-    if (comp != TIFF_NONE && comp != TIFF_LZW) fail("compression " + std::to_string(comp) + " is not supported (none and LZW are)");
+    if (comp == 32946) comp = TIFF_DEFLATE;                                     // the number Deflate had before Adobe's 8
+    if (comp != TIFF_NONE && comp != TIFF_LZW && comp != TIFF_DEFLATE)
+        fail("compression " + std::to_string(comp) + " is not supported (none, LZW and Deflate are)");
     if (pred != 1 && pred != 2) fail("predictor " + std::to_string(pred) + " is not supported");
     if (bits != 16 || fmt != 1 || planar != 1) fail("only chunky unsigned 16-bit samples are supported");
     if (!W || !H || W > 0x7FFFFFFFull || H > 0x7FFFFFFFull || S == 0 || S > 16) fail("missing or implausible geometry");
@@ -725,6 +744,12 @@ inline void read_tiff_u16(const std::string &path, int *width, long *height, int
         // (the LZW bound of the strips below, on the tiles: what is present bounds what the tiles can decode to)
         if (comp == TIFF_LZW && (unsigned __int128)tile_bytes * offs.size() / 2560 > (unsigned __int128)packed + 16)
             fail("image size is implausible for its compressed tiles");
+        // (Deflate's own bound, derived at the strips below)
+        if (comp == TIFF_DEFLATE && (unsigned __int128)tile_bytes * offs.size() / 1032 > (unsigned __int128)packed + 16)
+            fail("image size is implausible for its compressed tiles");
+        if (comp == TIFF_DEFLATE)
+            for (uint64_t l : lens) if (l >= oipinflate::kMaxStream) fail("a compressed tile of 4 GiB or more");
+        if (comp == TIFF_DEFLATE && tile_bytes >= oipinflate::kMaxStream) fail("a tile of 4 GiB or more");
         rps = 0;
     }
     if (!tiled) {
@@ -744,6 +769,15 @@ inline void read_tiff_u16(const std::string &path, int *width, long *height, int
         uint64_t packed = 0;
         for (uint64_t l : lens) packed += l;
         if (row_bytes * H / 2560 > packed + 16) fail("image size is implausible for its compressed strips");
+    }
+    if (!tiled && comp == TIFF_DEFLATE) {
+        // The same rule with Deflate's worst ratio.  The densest thing a Deflate stream holds is a match: it produces at most
+        // 258 bytes (length symbol 285) and costs at least 2 bits, a 1-bit length code and a 1-bit distance code.  So a byte of
+        // input decodes to at most 4 x 258 = 1032 bytes, and block headers, the zlib wrapper and literals only lower that.
+        uint64_t packed = 0;
+        for (uint64_t l : lens) { if (l >= oipinflate::kMaxStream) fail("a compressed strip of 4 GiB or more"); packed += l; }
+        if (row_bytes * H / 1032 > packed + 16) fail("image size is implausible for its compressed strips");
+        if (rps > (oipinflate::kMaxStream - 1) / row_bytes) fail("a strip of 4 GiB or more");
     }
     if (layout_only) {
         layout_only->width = W; layout_only->height = H; layout_only->spp = S; layout_only->compression = comp;
@@ -770,13 +804,15 @@ inline void read_tiff_u16(const std::string &path, int *width, long *height, int
             tiffdetail::parallel_for(kn, [&](size_t j) {
                 const uint64_t k = k0 + j, tj = k / ntx, ti = k - tj * ntx;
                 std::vector<unsigned char> dec;
-                if (comp == TIFF_LZW) {
+                if (comp != TIFF_NONE) {
                     dec.resize((size_t)tile_bytes);
-                    const size_t got = tiffdetail::lzw_decode(raw[j].data(), raw[j].size(), dec.data(), dec.size());
+                    const size_t got = comp == TIFF_LZW ? tiffdetail::lzw_decode(raw[j].data(), raw[j].size(), dec.data(), dec.size())
+                                                        : tiffdetail::deflate_decode(raw[j].data(), raw[j].size(), dec.data(), dec.size(),
+                                                                                     "tile " + std::to_string(k) + " of [" + path + "]");
                     if (got != dec.size()) throw std::runtime_error("read TIFF [" + path + "]: tile " + std::to_string(k) + " decodes to " +
                                                                     std::to_string(got) + " bytes, " + std::to_string(dec.size()) + " expected");
                 }
-                unsigned char *tile = comp == TIFF_LZW ? dec.data() : raw[j].data();
+                unsigned char *tile = comp != TIFF_NONE ? dec.data() : raw[j].data();
                 const uint64_t nr = std::min<uint64_t>(TL, H - tj * TL), nc = std::min<uint64_t>(TW, W - ti * TW);
                 for (uint64_t r = 0; r < nr; ++r) {
                     unsigned char *trow = tile + (size_t)(r * TW * S * 2);
@@ -810,7 +846,10 @@ inline void read_tiff_u16(const std::string &path, int *width, long *height, int
                 const uint64_t k = k0 + j;
                 const uint64_t r0 = k * rps, nr = std::min<uint64_t>(rps, H - r0);
                 const size_t want = (size_t)(nr * row_bytes);
-                const size_t got = tiffdetail::lzw_decode(raw[j].data(), raw[j].size(), dstb + (size_t)(r0 * row_bytes), want);
+                unsigned char *dst = dstb + (size_t)(r0 * row_bytes);
+                const size_t got = comp == TIFF_LZW ? tiffdetail::lzw_decode(raw[j].data(), raw[j].size(), dst, want)
+                                                    : tiffdetail::deflate_decode(raw[j].data(), raw[j].size(), dst, want,
+                                                                                 "strip " + std::to_string(k) + " of [" + path + "]");
                 if (got != want) throw std::runtime_error("read TIFF [" + path + "]: strip " + std::to_string(k) + " decodes to " +
                                                           std::to_string(got) + " bytes, " + std::to_string(want) + " expected");
             });
