@@ -271,6 +271,17 @@ inline bool gpu_deflate()
     return on;
 }
 
+// the bytes of tile-major samples a batch of tile rows may hold on its way to or from a tiled TIFF (OIP_COG_BATCH_MB: test hook, several
+// batches on a small image)
+inline size_t cog_batch_bytes(size_t dflt)
+{
+    if (const char *e = getenv("OIP_COG_BATCH_MB")) {
+        const long mb = atol(e);
+        if (mb > 0) return (size_t)mb << 20;
+    }
+    return dflt;
+}
+
 inline void tiff_rows_from_device(TiffWriterU16 &tw, const uint16_t *d_img, long rows, size_t rowSamples, long mark)
 {
     oip_ctx *ctx = Device::get().ctx();
@@ -436,12 +447,7 @@ inline void tiled_image_from_device(TiffTiledWriterU16 &tw, const std::string &p
     stop_watch sw;
     const long tx = tw.tiles_x(), ty = tw.tiles_y();
     const size_t tileSamples = (size_t)T * T * spp, rowSamples = (size_t)tx * tileSamples, n = (size_t)tx * ty;
-    size_t batchBytes = (size_t)256 << 20;
-    if (const char *e = getenv("OIP_COG_BATCH_MB")) {
-        const long mb = atol(e);
-        if (mb > 0) batchBytes = (size_t)mb << 20;
-    }
-    const long batchRows = std::max<long>(1, std::min<long>(ty, (long)(batchBytes / (rowSamples * 2))));
+    const long batchRows = std::max<long>(1, std::min<long>(ty, (long)(cog_batch_bytes((size_t)256 << 20) / (rowSamples * 2))));
     DevBuf<uint16_t> batch((size_t)batchRows * rowSamples);
     if (compression == TIFF_LZW && !gpu_lzw()) {
         std::vector<uint16_t> host(n * tileSamples);
@@ -549,15 +555,35 @@ inline void write_overviews_of_device_image(const std::string &path, const uint1
 // streams -- and OIP_TIFF_GPU_DEFLATE=0 goes to the host.
 constexpr size_t kDeflateDeviceMinStreams = 256;
 constexpr uint64_t kDeflateDeviceMaxStreamBytes = (uint64_t)2 << 20;
+// Streams [k0, k0 + n) of the file -- strips or tiles -- go from the file into device memory as they are and are decoded into d_out, an
+// image of `rows` x `width` pixels in strips of `rps` rows; `tail` ends the message of a stream the decoder refuses.
+inline void tiff_streams_to_device(const std::string &path, const TiffLayout &lay, size_t k0, size_t n, long rows, int width, long rps, uint16_t *d_out,
+                                   const std::string &tail = "")
+{
+    oip_ctx *ctx = Device::get().ctx();
+    uint64_t lo = ~(uint64_t)0, hi = 0;
+    for (size_t k = k0; k < k0 + n; ++k) { lo = std::min(lo, lay.offs[k]); hi = std::max(hi, lay.offs[k] + lay.lens[k]); }
+    if (lay.tiled() && hi <= lo) throw std::runtime_error("read TIFF [" + path + "]: empty tiles");
+    DevBuf<uint8_t> file((size_t)(hi - lo));
+    size_t got = 0;
+    Device::get().check(oip_read_file_to_device(ctx, path.c_str(), (size_t)lo, (size_t)(hi - lo), file.p, &got, nullptr));
+    if (got != (size_t)(hi - lo)) throw std::runtime_error("read TIFF [" + path + "]: truncated file");
+    Device::get().check(oip_stage_sync(ctx));
+    std::vector<uint64_t> off(lay.offs.begin() + k0, lay.offs.begin() + k0 + n);
+    for (auto &o : off) o -= lo;
+    const auto decode = lay.compression == TIFF_DEFLATE ? oip_tiff_deflate_decode_u16 : oip_tiff_lzw_decode_u16;
+    const int rc = decode(ctx, file.p, file.n, off.data(), lay.lens.data() + k0, (long)n, rows, width, (int)lay.spp, rps, (int)lay.predictor, d_out);
+    if (rc != OIP_OK) throw std::runtime_error("read TIFF [" + path + "]: " + std::string(oip_last_error(ctx)) + tail);
+}
+
 inline void read_tiff_to_device(const std::string &path, int *width, long *height, int *spp, DevBuf<uint16_t> &img)
 {
-    TiffLayout lay;
-    read_tiff_u16(path, width, height, spp, nullptr, &lay);
+    const TiffLayout lay = read_tiff_layout(path);
+    *width = (int)lay.width; *height = (long)lay.height; *spp = (int)lay.spp;
     const size_t samples = (size_t)lay.width * lay.height * lay.spp;
     // (tiled: square tiles the layout kernel takes -- a multiple of 16 up to 1024 --, each one a "strip" of the decoder)
     const uint64_t T = lay.tile_width;
     const bool deflate = lay.compression == TIFF_DEFLATE;
-    const auto decode = deflate ? oip_tiff_deflate_decode_u16 : oip_tiff_lzw_decode_u16;
     bool device = (deflate ? gpu_deflate() : gpu_lzw() && lay.compression == TIFF_LZW) && (lay.spp == 1 || lay.spp == 4) &&
                   (lay.tiled() ? T == lay.tile_length && T % 16 == 0 && T <= 1024 : lay.rows_per_strip * lay.width * lay.spp * 2 < ((uint64_t)1 << 32));
     uint64_t lo = ~(uint64_t)0, hi = 0;
@@ -574,51 +600,25 @@ inline void read_tiff_to_device(const std::string &path, int *width, long *heigh
         img.upload(host.data(), host.size());
         return;
     }
-    oip_ctx *ctx = Device::get().ctx();
-    if (lay.tiled()) {
-        // batches of tile rows of at most 1 GiB of tile-major samples: their tiles go from the file into device memory as they
-        // are, are decoded into the tile-major buffer (width T, T rows a "strip") and oip_untile_u16 puts them into the image
-        const long tx = (long)((lay.width + T - 1) / T), ty = (long)((lay.height + T - 1) / T);
-        const size_t rowSamples = (size_t)tx * T * T * lay.spp;
-        size_t batchBytes = (size_t)1 << 30;
-        if (const char *e = getenv("OIP_COG_BATCH_MB")) {              // test hook: several batches on a small image
-            const long mb = atol(e);
-            if (mb > 0) batchBytes = (size_t)mb << 20;
-        }
-        const long batchRows = std::max<long>(1, std::min<long>(ty, (long)(batchBytes / (rowSamples * 2))));
-        DevBuf<uint16_t> tiles((size_t)batchRows * rowSamples);
-        img.alloc(samples);
-        for (long j0 = 0; j0 < ty; j0 += batchRows) {
-            const long nr = std::min(batchRows, ty - j0);
-            const size_t k0 = (size_t)j0 * tx, nt = (size_t)nr * tx;
-            uint64_t blo = ~(uint64_t)0, bhi = 0;
-            for (size_t k = k0; k < k0 + nt; ++k) { blo = std::min(blo, lay.offs[k]); bhi = std::max(bhi, lay.offs[k] + lay.lens[k]); }
-            if (bhi <= blo) throw std::runtime_error("read TIFF [" + path + "]: empty tiles");
-            DevBuf<uint8_t> file((size_t)(bhi - blo));
-            size_t got = 0;
-            Device::get().check(oip_read_file_to_device(ctx, path.c_str(), (size_t)blo, (size_t)(bhi - blo), file.p, &got, nullptr));
-            if (got != (size_t)(bhi - blo)) throw std::runtime_error("read TIFF [" + path + "]: truncated file");
-            Device::get().check(oip_stage_sync(ctx));
-            std::vector<uint64_t> off(lay.offs.begin() + k0, lay.offs.begin() + k0 + nt);
-            for (auto &o : off) o -= blo;
-            const int rc = decode(ctx, file.p, file.n, off.data(), lay.lens.data() + k0, (long)nt, (long)(nt * T), (int)T, (int)lay.spp, (long)T,
-                                  (int)lay.predictor, tiles.p);
-            if (rc != OIP_OK) throw std::runtime_error("read TIFF [" + path + "]: " + std::string(oip_last_error(ctx)) + " (tiles from " + std::to_string(k0) + " on)");
-            Device::get().check(oip_untile_u16(ctx, tiles.p, (int)lay.width, (long)lay.height, (int)lay.spp, (int)T, j0, nr, img.p, (long)(lay.width * lay.spp)));
-        }
-        Device::get().check(oip_sync(ctx));                            // (the last untile reads `tiles`)
+    img.alloc(samples);
+    if (!lay.tiled()) {
+        tiff_streams_to_device(path, lay, 0, lay.offs.size(), (long)lay.height, (int)lay.width, (long)lay.rows_per_strip, img.p);
         return;
     }
-    DevBuf<uint8_t> file((size_t)(hi - lo));
-    size_t got = 0;
-    Device::get().check(oip_read_file_to_device(ctx, path.c_str(), (size_t)lo, (size_t)(hi - lo), file.p, &got, nullptr));
-    if (got != (size_t)(hi - lo)) throw std::runtime_error("read TIFF [" + path + "]: truncated file");
-    Device::get().check(oip_stage_sync(ctx));
-    for (auto &o : lay.offs) o -= lo;
-    img.alloc(samples);
-    const int rc = decode(ctx, file.p, file.n, lay.offs.data(), lay.lens.data(), (long)lay.offs.size(), (long)lay.height, (int)lay.width,
-                          (int)lay.spp, (long)lay.rows_per_strip, (int)lay.predictor, img.p);
-    if (rc != OIP_OK) throw std::runtime_error("read TIFF [" + path + "]: " + std::string(oip_last_error(ctx)));
+    // batches of tile rows of at most 1 GiB of tile-major samples: decoded into the tile-major buffer (width T, T rows a "strip"), and
+    // oip_untile_u16 puts them into the image
+    oip_ctx *ctx = Device::get().ctx();
+    const long tx = (long)((lay.width + T - 1) / T), ty = (long)((lay.height + T - 1) / T);
+    const size_t rowSamples = (size_t)tx * T * T * lay.spp;
+    const long batchRows = std::max<long>(1, std::min<long>(ty, (long)(cog_batch_bytes((size_t)1 << 30) / (rowSamples * 2))));
+    DevBuf<uint16_t> tiles((size_t)batchRows * rowSamples);
+    for (long j0 = 0; j0 < ty; j0 += batchRows) {
+        const long nr = std::min(batchRows, ty - j0);
+        const size_t k0 = (size_t)j0 * tx, nt = (size_t)nr * tx;
+        tiff_streams_to_device(path, lay, k0, nt, (long)(nt * T), (int)T, (long)T, tiles.p, " (tiles from " + std::to_string(k0) + " on)");
+        Device::get().check(oip_untile_u16(ctx, tiles.p, (int)lay.width, (long)lay.height, (int)lay.spp, (int)T, j0, nr, img.p, (long)(lay.width * lay.spp)));
+    }
+    Device::get().check(oip_sync(ctx));                            // (the last untile reads `tiles`)
 }
 
 // ---- ImageOperations (imageop.h:33-568, hot-path subset) -----------------------------------------

@@ -849,10 +849,9 @@ inline MaskPaths MaskCheck(const std::string &file, const std::string &out, cons
     *isTiff = RasterContainer(file, "mask") == ".tiff";
     *spp = 1;
     if (*isTiff) {
-        TiffLayout lay;
         int w = 0;
         long h = 0;
-        read_tiff_u16(file, &w, &h, spp, nullptr, &lay);
+        read_tiff_geometry(file, &w, &h, spp);
         if (*spp != 1 && *spp != MSS_BANDS) throw std::invalid_argument("mask: a TIFF of 1 or 4 samples per pixel expected");
     } else {
         RawLineCount(file, "image", (size_t)o.width * BYTES_PER_PIXEL);
@@ -965,10 +964,9 @@ inline WallisPaths WallisCheck(const std::string &file, const std::string &out, 
     *spp = 1;
     long first = 0, n = 0;
     if (*isTiff) {
-        TiffLayout lay;
         int w = 0;
         long h = 0;
-        read_tiff_u16(file, &w, &h, spp, nullptr, &lay);
+        read_tiff_geometry(file, &w, &h, spp);
         if (*spp != 1 && *spp != MSS_BANDS) throw std::invalid_argument("wallis: a TIFF of 1 or 4 samples per pixel expected");
         LineRange("image", h, o.lineOffset, o.lines, &first, &n);
     } else {
@@ -1382,8 +1380,7 @@ inline RescaleGeometry RescaleCheck(const std::string &file, const std::string &
     const std::string ext = RasterContainer(file, "rescale");
     g.inTiff = ext == ".tiff";
     if (g.inTiff) {
-        TiffLayout lay;
-        read_tiff_u16(file, &g.W, &g.L, &g.spp, nullptr, &lay);
+        read_tiff_geometry(file, &g.W, &g.L, &g.spp);
         if (g.spp != 1 && g.spp != MSS_BANDS) throw std::invalid_argument("rescale: a TIFF of 1 or 4 samples per pixel expected");
     } else {
         g.W = o.width;
@@ -1608,8 +1605,7 @@ inline std::string RegfixCheck(const std::string &file, const std::string &out, 
     int w = 0, spp = 1;
     long h = 0;
     if (*isTiff) {
-        TiffLayout lay;
-        read_tiff_u16(file, &w, &h, &spp, nullptr, &lay);
+        read_tiff_geometry(file, &w, &h, &spp);
         if (spp != 1 && spp != MSS_BANDS) throw std::invalid_argument("regfix: a TIFF of 1 or 4 samples per pixel expected");
     } else {
         w = o.width;
@@ -1684,15 +1680,14 @@ inline std::string PansharpenCheck(const std::string &out, const PansharpenOptio
     g->panTiff = RasterContainer(o.pan, "pansharpen") == ".tiff";
     if (RasterContainer(o.mss, "pansharpen") != ".tiff") throw std::invalid_argument("pansharpen: the MSS product is a TIFF of 4 samples per pixel");
     int spp = 1;
-    TiffLayout lay;
     if (g->panTiff) {
-        read_tiff_u16(o.pan, &g->W, &g->Hp, &spp, nullptr, &lay);
+        read_tiff_geometry(o.pan, &g->W, &g->Hp, &spp);
         if (spp != 1) throw std::invalid_argument("pansharpen: a PAN TIFF of 1 sample per pixel expected, not " + std::to_string(spp));
     } else {
         g->W = o.width;
         g->Hp = RawLineCount(o.pan, "PAN", (size_t)o.width * BYTES_PER_PIXEL);
     }
-    read_tiff_u16(o.mss, &g->w, &g->h, &spp, nullptr, &lay);
+    read_tiff_geometry(o.mss, &g->w, &g->h, &spp);
     if (spp != MSS_BANDS) throw std::invalid_argument("pansharpen: an MSS TIFF of 4 samples per pixel expected, not " + std::to_string(spp));
     if (g->W != 4L * g->w)
         throw std::invalid_argument("pansharpen: the PAN line (" + std::to_string(g->W) + ") is not 4 times the MSS line (" + std::to_string(g->w) + ")");

@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "oip_inflate.h"
+#include "oip_tiffshared.h"
 
 namespace OIPGPU {
 
@@ -122,18 +123,7 @@ struct LzwTable {
     }
 };
 
-// encoded strip: a buffer that is NOT value-initialised (a vector would zero 1.5 x the strip before the encoder overwrites it)
-struct LzwStrip {
-    std::unique_ptr<uint8_t[]> p;
-    size_t n = 0;
-    const uint8_t *data() const { return p.get(); }
-    size_t size() const { return n; }
-};
-
-// worst case of an encoded strip: one 12-bit code per byte, plus Clear / EOI codes
-inline size_t lzw_worst(size_t n) { return n + n / 2 + n / 1024 + 64; }
-
-// encodes n bytes into dst (lzw_worst(n) bytes); returns the encoded size
+// encodes n bytes into dst (lzw_worst(n) bytes, oip_tiffshared.h); returns the encoded size
 inline size_t lzw_encode_to(const uint8_t *src, size_t n, uint8_t *dst)
 {
     static thread_local std::unique_ptr<LzwTable> tab;  // ~96 KB, once per encoding thread
@@ -189,11 +179,6 @@ inline size_t lzw_encode_to(const uint8_t *src, size_t n, uint8_t *dst)
     put(257, width);
     if (nbits > 0) *o++ = (uint8_t)(acc << (8 - nbits));
     return (size_t)(o - dst);
-}
-inline void lzw_encode(const uint8_t *src, size_t n, LzwStrip &out)
-{
-    out.p.reset(new uint8_t[lzw_worst(n)]);
-    out.n = lzw_encode_to(src, n, out.p.get());
 }
 
 // returns the number of bytes produced (at most cap); throws on a corrupt stream
@@ -277,6 +262,157 @@ inline void predictor2_decode(uint16_t *row, size_t width, int spp)
     for (size_t i = spp; i < width * spp; ++i) row[i] = (uint16_t)(row[i] + row[i - spp]);
 }
 
+// one compressed strip or tile (TIFF_LZW, or Deflate) into dst[0, cap); returns the bytes produced.  `what` names it in Deflate's refusals.
+inline size_t decode_chunk(uint64_t compression, const uint8_t *src, size_t n, uint8_t *dst, size_t cap, const std::string &what)
+{
+    return compression == TIFF_LZW ? lzw_decode(src, n, dst, cap) : deflate_decode(src, n, dst, cap, what);
+}
+
+// a row of 4-sample pixels into OpenCV's sample order
+inline void swap_row(const uint16_t *src, uint16_t *dst, size_t width)
+{
+    for (size_t x = 0; x < width; ++x) {
+        dst[4 * x + 0] = src[4 * x + 2];
+        dst[4 * x + 1] = src[4 * x + 1];
+        dst[4 * x + 2] = src[4 * x + 0];
+        dst[4 * x + 3] = src[4 * x + 3];
+    }
+}
+
+// One strip or tile of an LZW file: `rows` rows of `width` pixels from src into buf (swap: in OpenCV's order), differenced along
+// each row (predictor 2) and encoded into dst (lzw_worst of the chunk's bytes); returns the encoded size.
+inline size_t encode_chunk(const uint16_t *src, long rows, size_t width, int spp, bool swap, uint16_t *buf, uint8_t *dst)
+{
+    const size_t rw = width * spp;
+    for (long r = 0; r < rows; ++r) {
+        uint16_t *d = buf + (size_t)r * rw;
+        if (swap) swap_row(src + (size_t)r * rw, d, width); else memcpy(d, src + (size_t)r * rw, rw * 2);
+        predictor2_encode(d, width, spp);
+    }
+    return lzw_encode_to((const uint8_t *)buf, (size_t)rows * rw * 2, dst);
+}
+
+// n bytes at offset `at` of fd, however many calls it takes; `who` names the writer in the error
+inline void pwrite_all(int fd, const void *p, size_t n, uint64_t at, const char *who)
+{
+    size_t w = 0;
+    while (w < n) {
+        const ssize_t r = pwrite(fd, (const char *)p + w, n - w, (off_t)(at + w));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) throw std::runtime_error(std::string(who) + ": write failed");
+        w += (size_t)r;
+    }
+}
+
+// Classic TIFF offsets are 32 bit.  LZW can also GROW a chunk: at worst one 12-bit code per byte (x1.5), so the choice is made on
+// the worst case of the payload of all directories and a classic file can never overflow half-way (BigTIFF is always valid): the
+// header, page-aligned payload, the chunk tables, the directories.  OIP_TIFF_FORCE_BIG: test hook, BigTIFF at any size.
+inline uint64_t worst_payload(uint64_t bytes, int compression) { return compression == TIFF_LZW ? bytes + bytes / 2 : bytes; }
+inline bool needs_bigtiff(uint64_t worst, uint64_t nchunks)
+{
+    bool big = worst + nchunks * 16 + 16384 > 0xFFFFF000ull;
+    if (const char *e = getenv("OIP_TIFF_FORCE_BIG")) big = big || atoi(e) != 0;
+    return big;
+}
+
+inline void put_le(std::vector<unsigned char> &out, uint64_t v, size_t n)
+{
+    for (size_t i = 0; i < n; ++i) out.push_back((unsigned char)(v >> (8 * i)));
+}
+
+// One directory as the three writers emit it: the tags of a chunky unsigned image in strips or tiles, in tag order, in classic or
+// BigTIFF entries.  The writers differ in where their out-of-line values lie (what does not fit an entry: fits()), not in what a
+// directory says.
+struct TiffDirectory {
+    bool big = false;
+    bool reduced = false;                   // NewSubfileType (254) = 1: a reduced-resolution image
+    uint64_t width = 0, height = 0;
+    int spp = 1, bits = 16, compression = TIFF_NONE;
+    bool sample_format = true;              // SampleFormat (339) = unsigned; the 8-bit writer leaves it out
+    uint64_t bitsAt = 0, formatAt = 0;      // where BitsPerSample / SampleFormat lie, 0: in their entries
+    uint64_t tile = 0;                      // 0: strips of rows_per_strip rows (273 / 278 / 279), else tile x tile tiles (322 - 325)
+    uint64_t rows_per_strip = 0;
+    uint64_t nchunks = 0, offsets = 0, counts = 0;   // of the strips or tiles: the one value, or where the table lies
+
+    size_t field() const { return big ? 8 : 4; }
+    bool fits(uint64_t count, size_t size) const { return count * size <= field(); }
+    static uint64_t shorts(int n, uint16_t v) { uint64_t x = 0; for (int i = 0; i < n; ++i) x |= (uint64_t)v << (16 * i); return x; }
+
+    // the entry count, the entries and the offset of the next directory
+    void append_to(std::vector<unsigned char> &out, uint64_t next) const
+    {
+        struct Tag { uint16_t id, type; uint64_t count, value; };
+        const uint16_t SHORT = 3, LONG = 4, otype = big ? 16 : LONG;      // (16: LONG8)
+        const uint64_t n = (uint64_t)spp;
+        std::vector<Tag> tags = {{256, LONG, 1, width}, {257, LONG, 1, height}, {258, SHORT, n, bitsAt ? bitsAt : shorts(spp, (uint16_t)bits)},
+                                 {259, SHORT, 1, (uint64_t)compression}, {262, SHORT, 1, (uint64_t)(spp >= 3 ? 2 : 1)},     // RGB / BlackIsZero
+                                 {277, SHORT, 1, n}, {284, SHORT, 1, 1}};                                                    // chunky
+        if (reduced) tags.push_back({254, LONG, 1, 1});
+        if (!tile) tags.insert(tags.end(), {{273, otype, nchunks, offsets}, {278, LONG, 1, rows_per_strip}, {279, otype, nchunks, counts}});
+        else tags.insert(tags.end(), {{322, LONG, 1, tile}, {323, LONG, 1, tile}, {324, otype, nchunks, offsets}, {325, otype, nchunks, counts}});
+        if (compression == TIFF_LZW) tags.push_back({317, SHORT, 1, 2});   // horizontal predictor
+        if (spp == 4) tags.push_back({338, SHORT, 1, 2});                  // unassociated alpha
+        if (sample_format) tags.push_back({339, SHORT, n, formatAt ? formatAt : shorts(spp, 1)});
+        std::sort(tags.begin(), tags.end(), [](const Tag &a, const Tag &b) { return a.id < b.id; });
+        put_le(out, tags.size(), big ? 8 : 2);
+        for (const Tag &t : tags) { put_le(out, t.id, 2); put_le(out, t.type, 2); put_le(out, t.count, field()); put_le(out, t.value, field()); }
+        put_le(out, next, field());
+    }
+};
+
+// A TIFF file open for reading: guarded reads, and refusals in the words of the reader that opened it (`reader` [path]: ...)
+struct TiffSource {
+    std::unique_ptr<FILE, int (*)(FILE *)> f;
+    std::string prefix;
+    uint64_t size = 0;
+    TiffSource(const std::string &path, const char *reader) : f(fopen(path.c_str(), "rb"), fclose), prefix(std::string(reader) + " [" + path + "]: ")
+    {
+        if (!f) throw std::runtime_error("cannot open file [" + path + "]");
+        if (fseeko(f.get(), 0, SEEK_END)) fail("seek failed");
+        size = (uint64_t)ftello(f.get());
+    }
+    [[noreturn]] void fail(const std::string &m) const { throw std::runtime_error(prefix + m); }
+    void read(uint64_t off, void *p, size_t n) const
+    {
+        if (off > size || n > size - off) fail("truncated file");
+        if (fseeko(f.get(), (off_t)off, SEEK_SET) || fread(p, 1, n, f.get()) != n) fail("truncated file");
+    }
+};
+
+// The first directory of a little-endian TIFF or BigTIFF: tag(id, count, val) for every entry of type SHORT, LONG or LONG8 that has
+// values, in file order; val(k) is its k-th value, from the entry or from where the entry points.  no_bigtiff: the words in which
+// a reader of classic files refuses BigTIFF -- such a reader does not take LONG8 entries either.
+template <typename F> inline void read_directory(const TiffSource &src, const char *no_bigtiff, F tag)
+{
+    unsigned char h[16];
+    src.read(0, h, 8);
+    if (h[0] != 'I' || h[1] != 'I') src.fail("only little-endian TIFF is supported");
+    const bool big = h[2] == 43;
+    if (big && h[3] == 0 && no_bigtiff) src.fail(no_bigtiff);
+    if ((h[2] != 42 && !big) || h[3] != 0) src.fail("not a TIFF file");
+    uint64_t ifd = 0, n = 0;
+    if (big) { src.read(8, &ifd, 8); src.read(ifd, &n, 8); }
+    else { memcpy(&ifd, h + 4, 4); src.read(ifd, &n, 2); }
+    if (n == 0 || n > 4096) src.fail("implausible directory");
+    const uint64_t ent = ifd + (big ? 8 : 2);
+    const size_t esz = big ? 20 : 12, osz = big ? 8 : 4;
+    for (uint64_t i = 0; i < n; ++i) {
+        unsigned char e[20];
+        src.read(ent + i * esz, e, esz);
+        uint16_t id, type;
+        memcpy(&id, e, 2); memcpy(&type, e + 2, 2);
+        uint64_t cnt = 0;
+        memcpy(&cnt, e + 4, osz);
+        const int ts = type == 3 ? 2 : (type == 4 ? 4 : (type == 16 && !no_bigtiff ? 8 : 0));
+        if (!ts || cnt == 0) continue;                                          // unknown type / empty tag: not ours
+        if (cnt > src.size / (uint64_t)ts) src.fail("tag larger than the file");
+        std::vector<unsigned char> raw((size_t)cnt * ts);
+        if (cnt * ts <= osz) memcpy(raw.data(), e + 4 + osz, (size_t)cnt * ts);
+        else { uint64_t o = 0; memcpy(&o, e + 4 + osz, osz); src.read(o, raw.data(), raw.size()); }
+        tag(id, cnt, [&](uint64_t k) { uint64_t v = 0; memcpy(&v, raw.data() + k * ts, ts); return v; });
+    }
+}
+
 }  // namespace tiffdetail
 
 class TiffWriterU16 {
@@ -293,9 +429,7 @@ public:
         mLevelsLeft = overview_levels;
         if (width <= 0 || height <= 0 || (spp != 1 && spp != 4) || overview_levels < 0) throw std::invalid_argument("TiffWriterU16: bad geometry");
         if (compression != TIFF_NONE && compression != TIFF_LZW) throw std::invalid_argument("TiffWriterU16: unsupported compression");
-        // classic TIFF offsets are 32 bit.  LZW can also GROW a strip: at worst one 12-bit code per byte (x1.5), so the
-        // choice is made on the worst case and a classic file can never overflow half-way (BigTIFF is always valid).
-        // (An overview file: on the sum of its levels.)
+        // classic or BigTIFF (tiffdetail::needs_bigtiff): on the worst case of the payload; an overview file: of the sum of its levels
         size_t worst = 0, nstrips = 0;
         if (overview_levels == 0) {
             set_geometry(width, height, &worst, &nstrips);
@@ -303,8 +437,7 @@ public:
             for (int k = overview_levels; k >= 1; --k)                         // (level 1 last: its geometry is the first directory's)
                 set_geometry((int)(((long)width - 1) >> k) + 1, ((height - 1) >> k) + 1, &worst, &nstrips);
         }
-        mBig = worst + nstrips * 16 + 16384 > 0xFFFFF000ull;                  // header, page-aligned payload, strip tables, directory
-        if (const char *e = getenv("OIP_TIFF_FORCE_BIG")) mBig = mBig || atoi(e) != 0;   // test hook: BigTIFF at any size
+        mBig = tiffdetail::needs_bigtiff(worst, nstrips);
         mF = fopen(path.c_str(), "wb");
         if (!mF) throw std::runtime_error("open file [" + path + "] failed");
         if (mBig) {
@@ -331,7 +464,7 @@ public:
             for (long r = 0; r < count; ++r) {
                 if (mRowsDone % mRowsPerStrip == 0) { mStripOff.push_back(mPos); mStripLen.push_back(0); }
                 const uint16_t *src = rows + (size_t)r * mW * mSpp;
-                if (mSwap) { tmp.resize((size_t)mW * 4); swap_row(src, tmp.data()); src = tmp.data(); }
+                if (mSwap) { tmp.resize((size_t)mW * 4); tiffdetail::swap_row(src, tmp.data(), (size_t)mW); src = tmp.data(); }
                 put(src, mRowBytes);
                 mStripLen.back() += mRowBytes;
                 mPos += mRowBytes;
@@ -468,7 +601,7 @@ private:
         mH = height;
         mRowBytes = (size_t)width * mSpp * 2;
         const size_t data = mRowBytes * (size_t)height;
-        *worst += mComp == TIFF_LZW ? data + data / 2 : data;
+        *worst += tiffdetail::worst_payload(data, mComp);
         // Strips: 8 MiB uncompressed (their offsets are arithmetic); LZW: whole rows up to 64 KiB (cv::imwrite and GDAL write 8
         // KB strips; libtiff's table restarts every ~5 KB of sensor data, so the strip size does not change the ratio).  An
         // LZW strip is the unit of parallel work of whoever encodes it: a lane of the device encoder (csrc/tifflzw.hip: 25000
@@ -489,53 +622,28 @@ private:
         if (mPos & 1) { const unsigned char z = 0; put(&z, 1); ++mPos; }
         // out-of-line arrays first
         const uint64_t nstrips = mStripOff.size();
-        uint64_t offStripOff = 0, offStripLen = 0, offBits = 0, offFmt = 0;
-        const size_t osz = mBig ? 8 : 4, inl = mBig ? 8 : 4;
+        tiffdetail::TiffDirectory d;
+        d.big = mBig; d.reduced = mLevelsLeft > 0; d.width = (uint64_t)mW; d.height = (uint64_t)mH; d.spp = mSpp; d.compression = mComp;
+        d.rows_per_strip = (uint64_t)mRowsPerStrip; d.nchunks = nstrips; d.offsets = mStripOff[0]; d.counts = mStripLen[0];
+        const size_t osz = d.field();
         if (!mBig && mPos + nstrips * 8 + 4096 > 0xFFFFFFFFull) { fclose(mF); mF = nullptr; throw std::runtime_error("TiffWriterU16: classic TIFF overflow"); }
-        if (nstrips * osz > inl) {
-            offStripOff = mPos; for (uint64_t v : mStripOff) putv(v, osz);
-            offStripLen = mPos; for (uint64_t v : mStripLen) putv(v, osz);
+        if (!d.fits(nstrips, osz)) {
+            d.offsets = mPos; for (uint64_t v : mStripOff) putv(v, osz);
+            d.counts = mPos; for (uint64_t v : mStripLen) putv(v, osz);
         }
-        if ((size_t)mSpp * 2 > inl) {
-            offBits = mPos; for (int i = 0; i < mSpp; ++i) putv(16, 2);
-            offFmt = mPos; for (int i = 0; i < mSpp; ++i) putv(1, 2);
+        if (!d.fits((uint64_t)mSpp, 2)) {
+            d.bitsAt = mPos; for (int i = 0; i < mSpp; ++i) putv(16, 2);
+            d.formatAt = mPos; for (int i = 0; i < mSpp; ++i) putv(1, 2);
         }
         if (mPos & 1) { const unsigned char z = 0; put(&z, 1); ++mPos; }
         const uint64_t ifd = mPos;
-        struct Tag { uint16_t id, type; uint64_t count, value; bool is_offset; };
-        const uint16_t SHORT = 3, LONG = 4, LONG8 = 16;
-        const uint16_t otype = mBig ? LONG8 : LONG;
-        std::vector<Tag> tags;
-        auto inline_shorts = [&](int n, uint16_t v) { uint64_t x = 0; for (int i = 0; i < n; ++i) x |= (uint64_t)v << (16 * i); return x; };
-        if (mLevelsLeft > 0) tags.push_back({254, LONG, 1, 1, false});                    // NewSubfileType: reduced-resolution image
-        tags.push_back({256, LONG, 1, (uint64_t)mW, false});
-        tags.push_back({257, LONG, 1, (uint64_t)mH, false});
-        tags.push_back({258, SHORT, (uint64_t)mSpp, offBits ? offBits : inline_shorts(mSpp, 16), offBits != 0});
-        tags.push_back({259, SHORT, 1, (uint64_t)mComp, false});
-        tags.push_back({262, SHORT, 1, (uint64_t)(mSpp == 4 ? 2 : 1), false});            // RGB / BlackIsZero
-        tags.push_back({273, otype, nstrips, offStripOff ? offStripOff : mStripOff[0], offStripOff != 0});
-        tags.push_back({277, SHORT, 1, (uint64_t)mSpp, false});
-        tags.push_back({278, LONG, 1, (uint64_t)mRowsPerStrip, false});
-        tags.push_back({279, otype, nstrips, offStripLen ? offStripLen : mStripLen[0], offStripLen != 0});
-        tags.push_back({284, SHORT, 1, 1, false});                                        // chunky
-        if (mComp == TIFF_LZW) tags.push_back({317, SHORT, 1, 2, false});                 // horizontal predictor
-        if (mSpp == 4) tags.push_back({338, SHORT, 1, 2, false});                         // unassociated alpha
-        tags.push_back({339, SHORT, (uint64_t)mSpp, offFmt ? offFmt : inline_shorts(mSpp, 1), offFmt != 0});
-        if (mBig) {
-            putv(tags.size(), 8);
-            for (auto &t : tags) { putv(t.id, 2); putv(t.type, 2); putv(t.count, 8); putv(t.value, 8); }
-            putv(0, 8);
-            fseeko(mF, (off_t)mLink, SEEK_SET);
-            putv_raw(ifd, 8);
-            mLink = mPos - 8;
-        } else {
-            putv(tags.size(), 2);
-            for (auto &t : tags) { putv(t.id, 2); putv(t.type, 2); putv(t.count, 4); putv(t.value, 4); }
-            putv(0, 4);
-            fseeko(mF, (off_t)mLink, SEEK_SET);
-            putv_raw(ifd, 4);
-            mLink = mPos - 4;
-        }
+        std::vector<unsigned char> dir;
+        d.append_to(dir, 0);
+        put(dir.data(), dir.size());
+        mPos += dir.size();
+        fseeko(mF, (off_t)mLink, SEEK_SET);
+        putv_raw(ifd, osz);
+        mLink = mPos - osz;
     }
 
     // encode `nrows` rows (whole strips, the last one possibly short) on a few threads and append them to the file.
@@ -558,14 +666,7 @@ private:
             const long r0 = (long)k * mRowsPerStrip;
             const long n = std::min<long>(mRowsPerStrip, nrows - r0);
             if (!mScratch[(size_t)t]) mScratch[(size_t)t].reset(new uint16_t[(size_t)mRowsPerStrip * rw]);
-            uint16_t *buf = mScratch[(size_t)t].get();
-            for (long r = 0; r < n; ++r) {
-                const uint16_t *src = rows + (size_t)(r0 + r) * rw;
-                uint16_t *d = buf + (size_t)r * rw;
-                if (mSwap) swap_row(src, d); else memcpy(d, src, rw * 2);
-                tiffdetail::predictor2_encode(d, (size_t)mW, mSpp);
-            }
-            len[k] = tiffdetail::lzw_encode_to((const uint8_t *)buf, (size_t)n * rw * 2, base + k * worst);
+            len[k] = tiffdetail::encode_chunk(rows + (size_t)r0 * rw, n, (size_t)mW, mSpp, mSwap, mScratch[(size_t)t].get(), base + k * worst);
         });
         // the batch goes to the file on a thread of its own (positioned writes) while the caller brings down and encodes the
         // next one; the previous batch's write is waited for -- and its error raised -- first
@@ -583,29 +684,11 @@ private:
         mPositioned = true;
         const int fd = fileno(mF);
         mWrite = std::async(std::launch::async, [fd, base, worst, len, at] {
-            for (size_t k = 0; k < len.size(); ++k) {
-                const uint8_t *p = base + k * worst;
-                size_t n = len[k], w = 0;
-                while (w < n) {
-                    const ssize_t r = pwrite(fd, p + w, n - w, (off_t)(at[k] + w));
-                    if (r < 0 && errno == EINTR) continue;
-                    if (r <= 0) throw std::runtime_error("TiffWriterU16: write failed");
-                    w += (size_t)r;
-                }
-            }
+            for (size_t k = 0; k < len.size(); ++k) tiffdetail::pwrite_all(fd, base + k * worst, len[k], at[k], "TiffWriterU16");
         });
     }
     void wait_write() { if (mWrite.valid()) mWrite.get(); }
 
-    void swap_row(const uint16_t *src, uint16_t *dst) const
-    {
-        for (int x = 0; x < mW; ++x) {
-            dst[4 * x + 0] = src[4 * x + 2];
-            dst[4 * x + 1] = src[4 * x + 1];
-            dst[4 * x + 2] = src[4 * x + 0];
-            dst[4 * x + 3] = src[4 * x + 3];
-        }
-    }
     void put(const void *p, size_t n)
     {
         if (fwrite(p, 1, n, mF) != n) throw std::runtime_error("TiffWriterU16: write failed");
@@ -646,60 +729,41 @@ private:
 // Tiles (322 TileWidth, 323 TileLength, 324 TileOffsets, 325 TileByteCounts) may have any positive size; they are numbered
 // row-major, every one holds TileWidth x TileLength pixels (the part outside the image is padding and is dropped), and
 // predictor 2 runs along each row of a tile.
-// layout_only: the checked header alone -- geometry, encoding and strip table -- for a caller that brings the strips in itself
-// (the device decoder: oip_host.hpp::read_tiff_to_device)
+// read_tiff_layout: the checked header alone -- geometry, encoding and the table of its strips or tiles, its "chunks" -- for a
+// caller that brings the chunks in itself (the device decoder: oip_host.hpp::read_tiff_to_device).
 struct TiffLayout {
     uint64_t width = 0, height = 0, spp = 0, compression = 1, predictor = 1, rows_per_strip = 0;
     uint64_t tile_width = 0, tile_length = 0;          // 0: strips.  Tiled: rows_per_strip is 0 and offs / lens hold the tiles, row-major
     std::vector<uint64_t> offs, lens;
     bool tiled() const { return tile_width != 0; }
-};
-inline void read_tiff_u16(const std::string &path, int *width, long *height, int *spp, std::vector<uint16_t> *out,
-                          TiffLayout *layout_only = nullptr)
-{
-    struct FileGuard {
-        FILE *f;
-        ~FileGuard() { if (f) fclose(f); }
-    } g{fopen(path.c_str(), "rb")};
-    FILE *f = g.f;
-    if (!f) throw std::runtime_error("cannot open file [" + path + "]");
-    auto fail = [&](const std::string &m) -> void { throw std::runtime_error("read TIFF [" + path + "]: " + m); };
-    if (fseeko(f, 0, SEEK_END)) fail("seek failed");
-    const uint64_t fsize = (uint64_t)ftello(f);
-    auto rd = [&](uint64_t off, void *p, size_t n) {
-        if (off > fsize || n > fsize - off) fail("truncated file");
-        if (fseeko(f, (off_t)off, SEEK_SET) || fread(p, 1, n, f) != n) fail("truncated file");
+    const char *chunk_name() const { return tiled() ? "tile" : "strip"; }
+    uint64_t row_bytes() const { return width * spp * 2; }
+    // Chunk k holds `rows` rows of `pitch` pixels; the first `cols` pixels of each belong at (row, col) of the image and on the rows
+    // below it (the rest of a tile is padding).  It decodes to bytes() bytes.
+    struct Chunk {
+        uint64_t row, col, rows, cols, pitch, spp;
+        uint64_t bytes() const { return rows * pitch * spp * 2; }
     };
-    unsigned char h[16];
-    rd(0, h, 8);
-    if (h[0] != 'I' || h[1] != 'I') fail("only little-endian TIFF is supported");
-    const bool big = h[2] == 43;
-    if ((h[2] != 42 && !big) || h[3] != 0) fail("not a TIFF file");
-    uint64_t ifd;
-    if (big) { rd(8, h, 8); memcpy(&ifd, h, 8); } else { uint32_t v; memcpy(&v, h + 4, 4); ifd = v; }
-    uint64_t n = 0;
-    if (big) rd(ifd, &n, 8); else { uint16_t v; rd(ifd, &v, 2); n = v; }
-    if (n == 0 || n > 4096) fail("implausible directory");
-    const uint64_t ent = ifd + (big ? 8 : 2);
-    const size_t esz = big ? 20 : 12, osz = big ? 8 : 4;
-    auto tsize = [](int t) { return t == 3 ? 2 : (t == 4 ? 4 : (t == 16 ? 8 : 0)); };
-    uint64_t W = 0, H = 0, comp = 1, planar = 1, S = 1, bits = 0, fmt = 1, pred = 1, rps = 0, TW = 0, TL = 0;
-    bool stripTags = false, tileTags = false, hasTW = false, hasTL = false;
-    std::vector<uint64_t> offs, lens;
-    for (uint64_t i = 0; i < n; ++i) {
-        unsigned char e[20];
-        rd(ent + i * esz, e, esz);
-        uint16_t id, type;
-        memcpy(&id, e, 2); memcpy(&type, e + 2, 2);
-        uint64_t cnt = 0;
-        memcpy(&cnt, e + 4, osz);
-        const int ts = tsize(type);
-        if (!ts || cnt == 0) continue;                                          // unknown type / empty tag: not ours
-        if (cnt > fsize / (uint64_t)ts) fail("tag larger than the file");
-        std::vector<unsigned char> raw((size_t)cnt * ts);
-        if (cnt * ts <= osz) memcpy(raw.data(), e + 4 + osz, (size_t)cnt * ts);
-        else { uint64_t o = 0; memcpy(&o, e + 4 + osz, osz); rd(o, raw.data(), raw.size()); }
-        auto val = [&](uint64_t k) { uint64_t v = 0; memcpy(&v, raw.data() + k * ts, ts); return v; };
+    Chunk chunk(uint64_t k) const
+    {
+        if (!tiled()) return {k * rows_per_strip, 0, std::min(rows_per_strip, height - k * rows_per_strip), width, width, spp};
+        const uint64_t ntx = (width + tile_width - 1) / tile_width, tj = k / ntx, ti = k - tj * ntx;
+        return {tj * tile_length, ti * tile_width, tile_length, std::min(tile_width, width - ti * tile_width), tile_width, spp};
+    }
+};
+
+namespace tiffdetail {
+inline TiffLayout read_layout(const TiffSource &src)
+{
+    auto fail = [&](const std::string &m) { src.fail(m); };
+    const uint64_t fsize = src.size;
+    TiffLayout lay;
+    uint64_t &W = lay.width, &H = lay.height, &S = lay.spp, &comp = lay.compression, &pred = lay.predictor, &rps = lay.rows_per_strip;
+    uint64_t &TW = lay.tile_width, &TL = lay.tile_length, planar = 1, bits = 0, fmt = 1;
+    bool stripTags = false, tileTags = false;
+    std::vector<uint64_t> &offs = lay.offs, &lens = lay.lens;
+    S = 1;
+    read_directory(src, nullptr, [&](uint16_t id, uint64_t cnt, auto val) {
         switch (id) {
             case 256: W = val(0); break;
             case 257: H = val(0); break;
@@ -712,11 +776,11 @@ inline void read_tiff_u16(const std::string &path, int *width, long *height, int
             case 284: planar = val(0); break;
             case 317: pred = val(0); break;
             case 339: fmt = val(0); break;
-            case 322: tileTags = hasTW = true; TW = val(0); break;
-            case 323: tileTags = hasTL = true; TL = val(0); break;
+            case 322: tileTags = true; TW = val(0); break;
+            case 323: tileTags = true; TL = val(0); break;
             default: break;
         }
-    }
+    });
     if (stripTags && tileTags) fail("strip tags and tile tags are both present");
     const bool tiled = tileTags;
     if (comp == 32946) comp = TIFF_DEFLATE;                                     // the number Deflate had before Adobe's 8
@@ -725,137 +789,112 @@ inline void read_tiff_u16(const std::string &path, int *width, long *height, int
     if (pred != 1 && pred != 2) fail("predictor " + std::to_string(pred) + " is not supported");
     if (bits != 16 || fmt != 1 || planar != 1) fail("only chunky unsigned 16-bit samples are supported");
     if (!W || !H || W > 0x7FFFFFFFull || H > 0x7FFFFFFFull || S == 0 || S > 16) fail("missing or implausible geometry");
-    if (tiled && (!hasTW || !hasTL || !TW || !TL)) fail("a tiled TIFF needs TileWidth and TileLength, both positive");
+    if (tiled && (!TW || !TL)) fail("a tiled TIFF needs TileWidth and TileLength, both positive");
     if (offs.empty() || offs.size() != lens.size()) fail(tiled ? "missing tile tags" : "missing strip tags");
     const uint64_t row_bytes = W * S * 2;
     if (H > (~(uint64_t)0) / row_bytes || row_bytes * H > ((uint64_t)1 << 46)) fail("implausible image size");
-    uint64_t tile_bytes = 0, ntx = 0;
     if (tiled) {
         if (TW > 0xFFFFFFFFull / TL || TW * TL > 0xFFFFFFFFull / (S * 2)) fail("a tile of 4 GiB or more");
-        tile_bytes = TW * TL * S * 2;
-        ntx = (W + TW - 1) / TW;
-        if (offs.size() != ntx * ((H + TL - 1) / TL)) fail("tile count does not match the tile grid");
-        uint64_t packed = 0;
-        for (size_t k = 0; k < offs.size(); ++k) {
-            if (offs[k] > fsize || lens[k] > fsize - offs[k]) fail("tile outside the file");
-            if (comp == TIFF_NONE && lens[k] != tile_bytes) fail("an uncompressed tile does not have the size of a tile");
-            packed += lens[k];
-        }
-        // (the LZW bound of the strips below, on the tiles: what is present bounds what the tiles can decode to)
-        if (comp == TIFF_LZW && (unsigned __int128)tile_bytes * offs.size() / 2560 > (unsigned __int128)packed + 16)
-            fail("image size is implausible for its compressed tiles");
-        // (Deflate's own bound, derived at the strips below)
-        if (comp == TIFF_DEFLATE && (unsigned __int128)tile_bytes * offs.size() / 1032 > (unsigned __int128)packed + 16)
-            fail("image size is implausible for its compressed tiles");
-        if (comp == TIFF_DEFLATE)
-            for (uint64_t l : lens) if (l >= oipinflate::kMaxStream) fail("a compressed tile of 4 GiB or more");
-        if (comp == TIFF_DEFLATE && tile_bytes >= oipinflate::kMaxStream) fail("a tile of 4 GiB or more");
+        if (offs.size() != ((W + TW - 1) / TW) * ((H + TL - 1) / TL)) fail("tile count does not match the tile grid");
         rps = 0;
-    }
-    if (!tiled) {
+    } else {
         if (rps == 0 || rps > H) rps = H;
         if (offs.size() != (H + rps - 1) / rps) fail("strip count does not match RowsPerStrip");
-        for (size_t k = 0; k < offs.size(); ++k)
-            if (offs[k] > fsize || lens[k] > fsize - offs[k]) fail("strip outside the file");
+    }
+    // From here on strips and tiles are chunks: chunk_bytes is what a whole one decodes to, `decoded` what all of them do (the tiles
+    // with their padding, the strips without the rows the last one lacks)
+    const std::string chunk = tiled ? "tile" : "strip";
+    const uint64_t chunk_bytes = tiled ? TW * TL * S * 2 : rps * row_bytes;
+    const unsigned __int128 decoded = tiled ? (unsigned __int128)chunk_bytes * offs.size() : (unsigned __int128)row_bytes * H;
+    unsigned __int128 packed = 0;
+    for (size_t k = 0; k < offs.size(); ++k) {
+        if (offs[k] > fsize || lens[k] > fsize - offs[k]) fail(chunk + " outside the file");
+        if (tiled && comp == TIFF_NONE && lens[k] != chunk_bytes) fail("an uncompressed tile does not have the size of a tile");
+        packed += lens[k];
     }
     if (!tiled && comp == TIFF_NONE) {
         uint64_t total = 0;
         for (uint64_t l : lens) { if (l > row_bytes * H - total) fail("strip sizes exceed the image"); total += l; }
         if (total != row_bytes * H) fail("strip sizes do not cover the image");
     }
-    if (!tiled && comp == TIFF_LZW) {
-        // header fields alone must not size the allocation: a 12-bit code (1.5 bytes) expands to at most 4096 - 258
-        // bytes, so the strips present bound what the image can decode to
-        uint64_t packed = 0;
-        for (uint64_t l : lens) packed += l;
-        if (row_bytes * H / 2560 > packed + 16) fail("image size is implausible for its compressed strips");
+    if (comp != TIFF_NONE) {
+        // Header fields alone must not size the allocation: the chunks present bound what the image can decode to.
+        // LZW: a 12-bit code (1.5 bytes) expands to at most 4096 - 258 bytes, 2560 for each byte of input.
+        // Deflate: the densest thing a stream holds is a match: it produces at most 258 bytes (length symbol 285) and costs at least
+        // 2 bits, a 1-bit length code and a 1-bit distance code.  So a byte of input decodes to at most 4 x 258 = 1032 bytes, and
+        // block headers, the zlib wrapper and literals only lower that.
+        if (comp == TIFF_DEFLATE)
+            for (uint64_t l : lens) if (l >= oipinflate::kMaxStream) fail("a compressed " + chunk + " of 4 GiB or more");
+        if (decoded / (comp == TIFF_LZW ? 2560 : 1032) > packed + 16) fail("image size is implausible for its compressed " + chunk + "s");
+        if (comp == TIFF_DEFLATE && chunk_bytes >= oipinflate::kMaxStream) fail("a " + chunk + " of 4 GiB or more");
     }
-    if (!tiled && comp == TIFF_DEFLATE) {
-        // The same rule with Deflate's worst ratio.  The densest thing a Deflate stream holds is a match: it produces at most
-        // 258 bytes (length symbol 285) and costs at least 2 bits, a 1-bit length code and a 1-bit distance code.  So a byte of
-        // input decodes to at most 4 x 258 = 1032 bytes, and block headers, the zlib wrapper and literals only lower that.
-        uint64_t packed = 0;
-        for (uint64_t l : lens) { if (l >= oipinflate::kMaxStream) fail("a compressed strip of 4 GiB or more"); packed += l; }
-        if (row_bytes * H / 1032 > packed + 16) fail("image size is implausible for its compressed strips");
-        if (rps > (oipinflate::kMaxStream - 1) / row_bytes) fail("a strip of 4 GiB or more");
-    }
-    if (layout_only) {
-        layout_only->width = W; layout_only->height = H; layout_only->spp = S; layout_only->compression = comp;
-        layout_only->predictor = pred; layout_only->rows_per_strip = rps;
-        layout_only->tile_width = tiled ? TW : 0; layout_only->tile_length = tiled ? TL : 0;
-        layout_only->offs = offs; layout_only->lens = lens;
-        *width = (int)W; *height = (long)H; *spp = (int)S;
-        return;
-    }
+    return lay;
+}
+}  // namespace tiffdetail
+
+inline TiffLayout read_tiff_layout(const std::string &path) { return tiffdetail::read_layout(tiffdetail::TiffSource(path, "read TIFF")); }
+
+// width, height and samples per pixel of a file the reader takes
+inline void read_tiff_geometry(const std::string &path, int *width, long *height, int *spp)
+{
+    const TiffLayout lay = read_tiff_layout(path);
+    *width = (int)lay.width; *height = (long)lay.height; *spp = (int)lay.spp;
+}
+
+inline void read_tiff_u16(const std::string &path, int *width, long *height, int *spp, std::vector<uint16_t> *out)
+{
+    const tiffdetail::TiffSource src(path, "read TIFF");
+    const TiffLayout lay = tiffdetail::read_layout(src);
+    const uint64_t W = lay.width, H = lay.height, S = lay.spp, comp = lay.compression, row_bytes = lay.row_bytes();
     try {
         out->resize((size_t)(W * H * S));
     } catch (const std::bad_alloc &) {
-        fail("not enough memory for a " + std::to_string(W) + " x " + std::to_string(H) + " x " + std::to_string(S) + " image");
+        src.fail("not enough memory for a " + std::to_string(W) + " x " + std::to_string(H) + " x " + std::to_string(S) + " image");
     }
     unsigned char *dstb = reinterpret_cast<unsigned char *>(out->data());
-    if (tiled) {
-        // the tiles in batches, each decoded on a worker thread into a tile of its own, un-differenced along the tile's rows, and
-        // its part inside the image copied out
-        const size_t batch = std::max<size_t>(1, std::min<size_t>(64, ((size_t)256 << 20) / (size_t)tile_bytes));
-        for (size_t k0 = 0; k0 < offs.size(); k0 += batch) {
-            const size_t kn = std::min(batch, offs.size() - k0);
-            std::vector<std::vector<unsigned char>> raw(kn);
-            for (size_t j = 0; j < kn; ++j) { raw[j].resize((size_t)lens[k0 + j]); rd(offs[k0 + j], raw[j].data(), raw[j].size()); }
-            tiffdetail::parallel_for(kn, [&](size_t j) {
-                const uint64_t k = k0 + j, tj = k / ntx, ti = k - tj * ntx;
-                std::vector<unsigned char> dec;
-                if (comp != TIFF_NONE) {
-                    dec.resize((size_t)tile_bytes);
-                    const size_t got = comp == TIFF_LZW ? tiffdetail::lzw_decode(raw[j].data(), raw[j].size(), dec.data(), dec.size())
-                                                        : tiffdetail::deflate_decode(raw[j].data(), raw[j].size(), dec.data(), dec.size(),
-                                                                                     "tile " + std::to_string(k) + " of [" + path + "]");
-                    if (got != dec.size()) throw std::runtime_error("read TIFF [" + path + "]: tile " + std::to_string(k) + " decodes to " +
-                                                                    std::to_string(got) + " bytes, " + std::to_string(dec.size()) + " expected");
-                }
-                unsigned char *tile = comp != TIFF_NONE ? dec.data() : raw[j].data();
-                const uint64_t nr = std::min<uint64_t>(TL, H - tj * TL), nc = std::min<uint64_t>(TW, W - ti * TW);
-                for (uint64_t r = 0; r < nr; ++r) {
-                    unsigned char *trow = tile + (size_t)(r * TW * S * 2);
-                    if (pred == 2) {
-                        std::vector<uint16_t> line((size_t)(TW * S));     // (a tile's bytes need not be aligned for u16)
-                        memcpy(line.data(), trow, line.size() * 2);
-                        tiffdetail::predictor2_decode(line.data(), (size_t)TW, (int)S);
-                        memcpy(trow, line.data(), line.size() * 2);
-                    }
-                    memcpy(dstb + (size_t)(((tj * TL + r) * W + ti * TW) * S * 2), trow, (size_t)(nc * S * 2));
-                }
-            });
-        }
-        *width = (int)W; *height = (long)H; *spp = (int)S;
-        return;
-    }
-    if (comp == TIFF_NONE) {
+    if (!lay.tiled() && comp == TIFF_NONE) {
         size_t pos = 0;
-        for (size_t k = 0; k < offs.size(); ++k) {
-            rd(offs[k], dstb + pos, (size_t)lens[k]);
-            pos += (size_t)lens[k];
+        for (size_t k = 0; k < lay.offs.size(); ++k) {
+            src.read(lay.offs[k], dstb + pos, (size_t)lay.lens[k]);
+            pos += (size_t)lay.lens[k];
         }
     } else {
-        // read the compressed strips in batches, decode them on a few threads
-        const size_t batch = 64;
-        for (size_t k0 = 0; k0 < offs.size(); k0 += batch) {
-            const size_t kn = std::min(batch, offs.size() - k0);
+        // The chunks in batches, each decoded on a worker thread.  A strip's rows lie in the image as they lie in the strip: it is
+        // decoded in place.  A tile is decoded into a buffer of its own (an uncompressed one is used as read), un-differenced along
+        // its own rows, and its part inside the image copied out.
+        const std::string name = lay.chunk_name();
+        const size_t batch = lay.tiled() ? std::max<size_t>(1, std::min<size_t>(64, ((size_t)256 << 20) / (size_t)lay.chunk(0).bytes())) : 64;
+        for (size_t k0 = 0; k0 < lay.offs.size(); k0 += batch) {
+            const size_t kn = std::min(batch, lay.offs.size() - k0);
             std::vector<std::vector<unsigned char>> raw(kn);
-            for (size_t j = 0; j < kn; ++j) { raw[j].resize((size_t)lens[k0 + j]); rd(offs[k0 + j], raw[j].data(), raw[j].size()); }
+            for (size_t j = 0; j < kn; ++j) { raw[j].resize((size_t)lay.lens[k0 + j]); src.read(lay.offs[k0 + j], raw[j].data(), raw[j].size()); }
             tiffdetail::parallel_for(kn, [&](size_t j) {
                 const uint64_t k = k0 + j;
-                const uint64_t r0 = k * rps, nr = std::min<uint64_t>(rps, H - r0);
-                const size_t want = (size_t)(nr * row_bytes);
-                unsigned char *dst = dstb + (size_t)(r0 * row_bytes);
-                const size_t got = comp == TIFF_LZW ? tiffdetail::lzw_decode(raw[j].data(), raw[j].size(), dst, want)
-                                                    : tiffdetail::deflate_decode(raw[j].data(), raw[j].size(), dst, want,
-                                                                                 "strip " + std::to_string(k) + " of [" + path + "]");
-                if (got != want) throw std::runtime_error("read TIFF [" + path + "]: strip " + std::to_string(k) + " decodes to " +
-                                                          std::to_string(got) + " bytes, " + std::to_string(want) + " expected");
+                const TiffLayout::Chunk c = lay.chunk(k);
+                const size_t want = (size_t)c.bytes();
+                std::vector<unsigned char> dec;
+                unsigned char *data = raw[j].data();
+                if (comp != TIFF_NONE) {
+                    if (lay.tiled()) dec.resize(want);
+                    data = lay.tiled() ? dec.data() : dstb + (size_t)(c.row * row_bytes);
+                    const size_t got = tiffdetail::decode_chunk(comp, raw[j].data(), raw[j].size(), data, want, name + " " + std::to_string(k) + " of [" + path + "]");
+                    if (got != want) src.fail(name + " " + std::to_string(k) + " decodes to " + std::to_string(got) + " bytes, " + std::to_string(want) + " expected");
+                }
+                if (!lay.tiled()) return;
+                for (uint64_t r = 0; r < std::min<uint64_t>(c.rows, H - c.row); ++r) {
+                    unsigned char *trow = data + (size_t)(r * c.pitch * S * 2);
+                    if (lay.predictor == 2) {
+                        std::vector<uint16_t> line((size_t)(c.pitch * S));     // (a tile's bytes need not be aligned for u16)
+                        memcpy(line.data(), trow, line.size() * 2);
+                        tiffdetail::predictor2_decode(line.data(), (size_t)c.pitch, (int)S);
+                        memcpy(trow, line.data(), line.size() * 2);
+                    }
+                    memcpy(dstb + (size_t)(((c.row + r) * W + c.col) * S * 2), trow, (size_t)(c.cols * S * 2));
+                }
             });
         }
     }
-    if (pred == 2) {
+    if (!lay.tiled() && lay.predictor == 2) {
         uint16_t *px = out->data();
         tiffdetail::parallel_for((size_t)H, [&](size_t r) { tiffdetail::predictor2_decode(px + r * (size_t)(W * S), (size_t)W, (int)S); });
     }
@@ -901,33 +940,21 @@ inline void write_tiff_u8(const std::string &path, const uint8_t *data, int widt
     const uint64_t nstrips = ((uint64_t)height + rps - 1) / rps;
     if (total + nstrips * 8 + 4096 > 0xFFFFF000ull) throw std::invalid_argument("write_tiff_u8: image too large for a classic TIFF");
     std::vector<unsigned char> tail;                                     // everything behind the pixels
-    auto putv = [&](uint64_t v, int n) { for (int i = 0; i < n; ++i) tail.push_back((unsigned char)(v >> (8 * i))); };
+    auto putv = [&](uint64_t v, int n) { tiffdetail::put_le(tail, v, (size_t)n); };
     uint64_t pos = 8 + total;
     if (pos & 1) { putv(0, 1); ++pos; }
-    uint64_t offStripOff = 0, offStripLen = 0, offBits = 0;
-    if (nstrips > 1) {
-        offStripOff = pos; for (uint64_t k = 0; k < nstrips; ++k) putv(8 + k * rps * rowBytes, 4);
-        offStripLen = offStripOff + nstrips * 4;
+    tiffdetail::TiffDirectory d;
+    d.width = (uint64_t)width; d.height = (uint64_t)height; d.spp = spp; d.bits = 8; d.sample_format = false;
+    d.rows_per_strip = (uint64_t)rps; d.nchunks = nstrips; d.offsets = 8; d.counts = total;
+    if (!d.fits(nstrips, 4)) {
+        d.offsets = pos; for (uint64_t k = 0; k < nstrips; ++k) putv(8 + k * rps * rowBytes, 4);
+        d.counts = pos + nstrips * 4;
         for (uint64_t k = 0; k < nstrips; ++k) putv(std::min<uint64_t>((uint64_t)rps, (uint64_t)height - k * rps) * rowBytes, 4);
         pos += nstrips * 8;
     }
-    if (spp == 3) { offBits = pos; for (int i = 0; i < 3; ++i) putv(8, 2); pos += 6; }
+    if (!d.fits((uint64_t)spp, 2)) { d.bitsAt = pos; for (int i = 0; i < spp; ++i) putv(8, 2); pos += (uint64_t)spp * 2; }
     const uint64_t ifd = pos;
-    const uint16_t SHORT = 3, LONG = 4;
-    struct Tag { uint16_t id, type; uint32_t count, value; };
-    const Tag tags[] = {{256, LONG, 1, (uint32_t)width},
-                        {257, LONG, 1, (uint32_t)height},
-                        {258, SHORT, (uint32_t)spp, spp == 3 ? (uint32_t)offBits : 8u},
-                        {259, SHORT, 1, 1},
-                        {262, SHORT, 1, spp == 3 ? 2u : 1u},                 // RGB / BlackIsZero
-                        {273, LONG, (uint32_t)nstrips, nstrips > 1 ? (uint32_t)offStripOff : 8u},
-                        {277, SHORT, 1, (uint32_t)spp},
-                        {278, LONG, 1, (uint32_t)rps},
-                        {279, LONG, (uint32_t)nstrips, nstrips > 1 ? (uint32_t)offStripLen : (uint32_t)total},
-                        {284, SHORT, 1, 1}};                                 // chunky
-    putv(sizeof tags / sizeof tags[0], 2);
-    for (const Tag &t : tags) { putv(t.id, 2); putv(t.type, 2); putv(t.count, 4); putv(t.value, 4); }
-    putv(0, 4);
+    d.append_to(tail, 0);
     unsigned char head[8] = {'I', 'I', 42, 0, 0, 0, 0, 0};
     for (int i = 0; i < 4; ++i) head[4 + i] = (unsigned char)(ifd >> (8 * i));
     FILE *f = fopen(path.c_str(), "wb");
@@ -942,44 +969,12 @@ inline void write_tiff_u8(const std::string &path, const uint8_t *data, int widt
 // field is checked before it sizes an allocation or a read.
 inline void read_tiff_u8(const std::string &path, int *width, long *height, std::vector<uint8_t> *out)
 {
-    struct FileGuard {
-        FILE *f;
-        ~FileGuard() { if (f) fclose(f); }
-    } g{fopen(path.c_str(), "rb")};
-    FILE *f = g.f;
-    if (!f) throw std::runtime_error("cannot open file [" + path + "]");
-    auto fail = [&](const std::string &m) -> void { throw std::runtime_error("read 8-bit TIFF [" + path + "]: " + m); };
-    if (fseeko(f, 0, SEEK_END)) fail("seek failed");
-    const uint64_t fsize = (uint64_t)ftello(f);
-    auto rd = [&](uint64_t off, void *p, size_t n) {
-        if (off > fsize || n > fsize - off) fail("truncated file");
-        if (fseeko(f, (off_t)off, SEEK_SET) || fread(p, 1, n, f) != n) fail("truncated file");
-    };
-    unsigned char h[8];
-    rd(0, h, 8);
-    if (h[0] != 'I' || h[1] != 'I') fail("only little-endian TIFF is supported");
-    if (h[2] == 43 && h[3] == 0) fail("BigTIFF is not supported (a mask is a classic TIFF)");
-    if (h[2] != 42 || h[3] != 0) fail("not a TIFF file");
-    uint32_t ifd = 0;
-    memcpy(&ifd, h + 4, 4);
-    uint16_t n = 0;
-    rd(ifd, &n, 2);
-    if (n == 0 || n > 4096) fail("implausible directory");
+    const tiffdetail::TiffSource src(path, "read 8-bit TIFF");
+    auto fail = [&](const std::string &m) { src.fail(m); };
+    const uint64_t fsize = src.size;
     uint64_t W = 0, H = 0, comp = 1, planar = 1, S = 1, bits = 1, rps = 0;
     std::vector<uint64_t> offs, lens;
-    for (uint64_t i = 0; i < n; ++i) {
-        unsigned char e[12];
-        rd((uint64_t)ifd + 2 + i * 12, e, 12);
-        uint16_t id, type;
-        uint32_t cnt;
-        memcpy(&id, e, 2); memcpy(&type, e + 2, 2); memcpy(&cnt, e + 4, 4);
-        const int ts = type == 3 ? 2 : type == 4 ? 4 : 0;
-        if (!ts || cnt == 0) continue;                                          // unknown type / empty tag: not ours
-        if (cnt > fsize / (uint64_t)ts) fail("tag larger than the file");
-        std::vector<unsigned char> raw((size_t)cnt * ts);
-        if ((uint64_t)cnt * ts <= 4) memcpy(raw.data(), e + 8, (size_t)cnt * ts);
-        else { uint32_t o = 0; memcpy(&o, e + 8, 4); rd(o, raw.data(), raw.size()); }
-        auto val = [&](uint64_t k) { uint64_t v = 0; memcpy(&v, raw.data() + k * ts, ts); return v; };
+    tiffdetail::read_directory(src, "BigTIFF is not supported (a mask is a classic TIFF)", [&](uint16_t id, uint64_t cnt, auto val) {
         switch (id) {
             case 256: W = val(0); break;
             case 257: H = val(0); break;
@@ -993,7 +988,7 @@ inline void read_tiff_u8(const std::string &path, int *width, long *height, std:
             case 322: case 323: case 324: case 325: fail("tiled TIFF is not supported (strips only)"); break;
             default: break;
         }
-    }
+    });
     if (comp != TIFF_NONE) fail("compression " + std::to_string(comp) + " is not supported (a mask is uncompressed)");
     if (bits != 8) fail(std::to_string(bits) + "-bit samples are not supported (a mask has 8)");
     if (S != 1 || planar != 1) fail(std::to_string(S) + " samples per pixel are not supported (a mask has 1)");
@@ -1011,7 +1006,7 @@ inline void read_tiff_u8(const std::string &path, int *width, long *height, std:
     out->resize((size_t)total);
     size_t pos = 0;
     for (size_t k = 0; k < offs.size(); ++k) {
-        rd(offs[k], out->data() + pos, (size_t)lens[k]);
+        src.read(offs[k], out->data() + pos, (size_t)lens[k]);
         pos += (size_t)lens[k];
     }
     *width = (int)W;

@@ -39,22 +39,24 @@ public:
             d.tx = (d.w + tile - 1) / tile;
             d.ty = (d.h + tile - 1) / tile;
             d.n = (uint64_t)d.tx * (uint64_t)d.ty;
-            worst += d.n * (mComp == TIFF_LZW ? mTileBytes + mTileBytes / 2 : mTileBytes);
+            worst += d.n * tiffdetail::worst_payload(mTileBytes, mComp);
             ntiles += d.n;
             mDirs.push_back(std::move(d));
         }
-        mBig = worst + ntiles * 16 + 16384 > 0xFFFFF000ull;                   // (the strip writer's rule)
-        if (const char *e = getenv("OIP_TIFF_FORCE_BIG")) mBig = mBig || atoi(e) != 0;
+        mBig = tiffdetail::needs_bigtiff(worst, ntiles);
         // the head: where every directory and table will lie
-        const uint64_t osz = mBig ? 8 : 4, inl = osz;
         uint64_t pos = mBig ? 16 : 8;
         for (size_t k = 0; k < mDirs.size(); ++k) {
             Dir &d = mDirs[k];
             d.ifd = pos;
-            const uint64_t ntags = 12 + (k > 0) + (mComp == TIFF_LZW) + (mSpp == 4);
-            pos += mBig ? 8 + ntags * 20 + 8 : 2 + ntags * 12 + 4;
-            if ((uint64_t)mSpp * 2 > inl) { d.offBits = pos; pos += (uint64_t)mSpp * 2; d.offFmt = pos; pos += (uint64_t)mSpp * 2; }
-            if (d.n * osz > inl) { d.offOffs = pos; pos += d.n * osz; d.offLens = pos; pos += d.n * osz; }
+            tiffdetail::TiffDirectory &t = d.tags;
+            t.big = mBig; t.reduced = k > 0; t.width = (uint64_t)d.w; t.height = (uint64_t)d.h; t.spp = mSpp; t.compression = mComp;
+            t.tile = (uint64_t)mT; t.nchunks = d.n;
+            std::vector<unsigned char> entries;
+            t.append_to(entries, 0);
+            pos += entries.size();
+            if (!t.fits((uint64_t)mSpp, 2)) { t.bitsAt = pos; pos += (uint64_t)mSpp * 2; t.formatAt = pos; pos += (uint64_t)mSpp * 2; }
+            if (!t.fits(d.n, t.field())) { t.offsets = pos; pos += d.n * t.field(); t.counts = pos; pos += d.n * t.field(); }
             if (pos & 1) ++pos;
         }
         mHead = mPos = pos;
@@ -114,7 +116,7 @@ public:
         if (mComp == TIFF_NONE) {
             for (uint64_t k = 0; k < d.n; ++k) { off[(size_t)k] = k * mTileBytes; len[(size_t)k] = mTileBytes; }
             pos = d.n * mTileBytes;
-            pwrite_all(fd, tileMajor, (size_t)pos, at);
+            tiffdetail::pwrite_all(fd, tileMajor, (size_t)pos, at, "TiffTiledWriterU16");
         } else {
             const size_t tileSamples = (size_t)(mTileBytes / 2), worst = tiffdetail::lzw_worst((size_t)mTileBytes);
             const uint64_t batch = std::max<uint64_t>(2 * (uint64_t)tiffdetail::worker_count(), ((uint64_t)64 << 20) / mTileBytes + 1);
@@ -124,15 +126,13 @@ public:
                 const uint64_t kn = std::min(batch, d.n - k0);
                 tiffdetail::parallel_for_t((size_t)kn, [&](size_t j, int t) {
                     if (!scratch[(size_t)t]) scratch[(size_t)t].reset(new uint16_t[tileSamples]);
-                    uint16_t *buf = scratch[(size_t)t].get();
-                    memcpy(buf, tileMajor + (size_t)(k0 + j) * tileSamples, (size_t)mTileBytes);
-                    for (int r = 0; r < mT; ++r) tiffdetail::predictor2_encode(buf + (size_t)r * mT * mSpp, (size_t)mT, mSpp);
-                    len[(size_t)(k0 + j)] = tiffdetail::lzw_encode_to((const uint8_t *)buf, (size_t)mTileBytes, arena.get() + j * worst);
+                    len[(size_t)(k0 + j)] = tiffdetail::encode_chunk(tileMajor + (size_t)(k0 + j) * tileSamples, mT, (size_t)mT, mSpp, false,
+                                                                     scratch[(size_t)t].get(), arena.get() + j * worst);
                 });
                 for (uint64_t j = 0; j < kn; ++j) {
                     if (pos & 1) ++pos;                                 // tiles start on even offsets (the gap reads as zero)
                     off[(size_t)(k0 + j)] = pos;
-                    pwrite_all(fd, arena.get() + j * worst, (size_t)len[(size_t)(k0 + j)], at + pos);
+                    tiffdetail::pwrite_all(fd, arena.get() + j * worst, (size_t)len[(size_t)(k0 + j)], at + pos, "TiffTiledWriterU16");
                     pos += len[(size_t)(k0 + j)];
                 }
             }
@@ -154,39 +154,17 @@ public:
         if (mCur + 1 != mDirs.size() || !cur().done) { fclose(mF); mF = nullptr; throw std::logic_error("TiffTiledWriterU16: directories missing"); }
         std::vector<unsigned char> head;
         head.reserve((size_t)mHead);
-        auto putv = [&](uint64_t v, size_t n) { for (size_t i = 0; i < n; ++i) head.push_back((unsigned char)(v >> (8 * i))); };
-        const size_t osz = mBig ? 8 : 4, inl = osz;
+        auto putv = [&](uint64_t v, size_t n) { tiffdetail::put_le(head, v, n); };
         if (mBig) { putv('I', 1); putv('I', 1); putv(43, 2); putv(8, 2); putv(0, 2); putv(mDirs[0].ifd, 8); }
         else { putv('I', 1); putv('I', 1); putv(42, 2); putv(mDirs[0].ifd, 4); }
-        const uint16_t SHORT = 3, LONG = 4, LONG8 = 16;
-        const uint16_t otype = mBig ? LONG8 : LONG;
-        struct Tag { uint16_t id, type; uint64_t count, value; };
-        auto inline_shorts = [&](int n, uint16_t v) { uint64_t x = 0; for (int i = 0; i < n; ++i) x |= (uint64_t)v << (16 * i); return x; };
         for (size_t k = 0; k < mDirs.size(); ++k) {
-            const Dir &d = mDirs[k];
+            Dir &d = mDirs[k];
             if (head.size() != d.ifd) { fclose(mF); mF = nullptr; throw std::logic_error("TiffTiledWriterU16: head layout"); }
-            std::vector<Tag> tags;
-            if (k > 0) tags.push_back({254, LONG, 1, 1});                             // NewSubfileType: reduced-resolution image
-            tags.push_back({256, LONG, 1, (uint64_t)d.w});
-            tags.push_back({257, LONG, 1, (uint64_t)d.h});
-            tags.push_back({258, SHORT, (uint64_t)mSpp, d.offBits ? d.offBits : inline_shorts(mSpp, 16)});
-            tags.push_back({259, SHORT, 1, (uint64_t)mComp});
-            tags.push_back({262, SHORT, 1, (uint64_t)(mSpp == 4 ? 2 : 1)});           // RGB / BlackIsZero
-            tags.push_back({277, SHORT, 1, (uint64_t)mSpp});
-            tags.push_back({284, SHORT, 1, 1});                                       // chunky
-            if (mComp == TIFF_LZW) tags.push_back({317, SHORT, 1, 2});                // horizontal predictor
-            tags.push_back({322, LONG, 1, (uint64_t)mT});
-            tags.push_back({323, LONG, 1, (uint64_t)mT});
-            tags.push_back({324, otype, d.n, d.offOffs ? d.offOffs : d.off[0]});
-            tags.push_back({325, otype, d.n, d.offLens ? d.offLens : d.len[0]});
-            if (mSpp == 4) tags.push_back({338, SHORT, 1, 2});                        // unassociated alpha
-            tags.push_back({339, SHORT, (uint64_t)mSpp, d.offFmt ? d.offFmt : inline_shorts(mSpp, 1)});
-            const uint64_t next = k + 1 < mDirs.size() ? mDirs[k + 1].ifd : 0;
-            putv(tags.size(), mBig ? 8 : 2);
-            for (auto &t : tags) { putv(t.id, 2); putv(t.type, 2); putv(t.count, osz); putv(t.value, inl); }
-            putv(next, osz);
-            if (d.offBits) { for (int i = 0; i < mSpp; ++i) putv(16, 2); for (int i = 0; i < mSpp; ++i) putv(1, 2); }
-            if (d.offOffs) { for (uint64_t v : d.off) putv(v, osz); for (uint64_t v : d.len) putv(v, osz); }
+            const bool tables = d.tags.offsets != 0;                                   // (else the one tile's values lie in the entries)
+            if (!tables) { d.tags.offsets = d.off[0]; d.tags.counts = d.len[0]; }
+            d.tags.append_to(head, k + 1 < mDirs.size() ? mDirs[k + 1].ifd : 0);
+            if (d.tags.bitsAt) { for (int i = 0; i < mSpp; ++i) putv(16, 2); for (int i = 0; i < mSpp; ++i) putv(1, 2); }
+            if (tables) { for (uint64_t v : d.off) putv(v, d.tags.field()); for (uint64_t v : d.len) putv(v, d.tags.field()); }
             if (head.size() & 1) putv(0, 1);
         }
         if (head.size() != mHead) { fclose(mF); mF = nullptr; throw std::logic_error("TiffTiledWriterU16: head layout"); }
@@ -204,7 +182,8 @@ private:
         int w = 0;
         long h = 0, tx = 0, ty = 0;
         uint64_t n = 0;                                         // tiles
-        uint64_t ifd = 0, offBits = 0, offFmt = 0, offOffs = 0, offLens = 0;   // where its parts lie in the head (0: inline)
+        uint64_t ifd = 0;                                       // where it lies in the head
+        tiffdetail::TiffDirectory tags;                         // what it says, with the places of its out-of-line values in the head
         std::vector<uint64_t> off, len;
         bool done = false;
     };
@@ -212,16 +191,6 @@ private:
     void put(const void *p, size_t n)
     {
         if (fwrite(p, 1, n, mF) != n) { fclose(mF); mF = nullptr; throw std::runtime_error("TiffTiledWriterU16: write failed"); }
-    }
-    static void pwrite_all(int fd, const void *p, size_t n, uint64_t at)
-    {
-        size_t w = 0;
-        while (w < n) {
-            const ssize_t r = pwrite(fd, (const char *)p + w, n - w, (off_t)(at + w));
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) throw std::runtime_error("TiffTiledWriterU16: write failed");
-            w += (size_t)r;
-        }
     }
 
     FILE *mF = nullptr;

@@ -15,6 +15,7 @@
 // image row (rows are independent; mod-2^16 sums in any order give the same bytes).
 #include "oip_internal.h"
 #include "oip_inflate.h"
+#include "oip_tiffdecode.h"
 
 #include <cstdint>
 #include <vector>
@@ -119,64 +120,28 @@ __global__ __launch_bounds__(64) void deflate_unpredict_any_kernel(uint16_t *img
 }
 }  // namespace
 
+// (oip_tiff_decode's refusals and two of its own: the row kernels take a row per workgroup, so fewer than 2^31 rows, and address the
+// image as u16 whatever the number of samples, so a 2-byte aligned image; the LZW decoder needs neither)
 extern "C" int oip_tiff_deflate_decode_u16(oip_ctx *ctx, const uint8_t *d_file, size_t file_bytes, const uint64_t *strip_off,
                                            const uint64_t *strip_len, long nstrips, long rows, int width, int spp, long rows_per_strip,
                                            int predictor, uint16_t *d_img)
 {
     OIP_CHECK_CTX(ctx);
-    if (!d_file || !strip_off || !strip_len || !d_img || nstrips <= 0 || rows <= 0 || width <= 0 || spp <= 0 || spp > 16 || rows_per_strip <= 0 ||
-        (predictor != 1 && predictor != 2))
-        return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_decode_u16: bad argument");
-    if (nstrips != (rows + rows_per_strip - 1) / rows_per_strip) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_decode_u16: strip count does not match RowsPerStrip");
     if (rows >= ((long)1 << 31)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_decode_u16: 2^31 rows or more");
-    const size_t rowBytes = (size_t)width * spp * 2;
-    if ((size_t)rows_per_strip * rowBytes >= oipinflate::kMaxStream) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_decode_u16: strip of 4 GiB or more");
-    if (spp == 4 && predictor == 2 && (((uintptr_t)d_img) & 7)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_decode_u16: image not 8-byte aligned");
     if (((uintptr_t)d_img) & 1) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_decode_u16: image not 2-byte aligned");
-    for (long k = 0; k < nstrips; ++k)
-        if (strip_off[k] > file_bytes || strip_len[k] > file_bytes - strip_off[k] || strip_len[k] >= oipinflate::kMaxStream)
-            return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_decode_u16: strip %ld outside the buffer", k);
-    // device scratch of one call (laid out as the LZW decoder's, without its per-lane tables): offsets, lengths, decoded bytes, status
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_off = 0, o_len = o_off + up((size_t)nstrips * 8), o_got = o_len + up((size_t)nstrips * 8),
-                 o_status = o_got + up((size_t)nstrips * 4), need = o_status + up((size_t)nstrips * 4);
-    void *scratch = nullptr;
-    OIP_HIP(ctx, hipMalloc(&scratch, need));
-    auto fail = [&](int rc) { (void)hipFree(scratch); return rc; };
-    unsigned long long *d_off = reinterpret_cast<unsigned long long *>((char *)scratch + o_off);
-    unsigned long long *d_len = reinterpret_cast<unsigned long long *>((char *)scratch + o_len);
-    unsigned *d_got = reinterpret_cast<unsigned *>((char *)scratch + o_got);
-    int *d_status = reinterpret_cast<int *>((char *)scratch + o_status);
-    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "strip tables are copied as they are");
-    if (hipMemcpyAsync(d_off, strip_off, (size_t)nstrips * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(d_len, strip_len, (size_t)nstrips * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        return fail(oip_fail(ctx, OIP_E_DEVICE, "oip_tiff_deflate_decode_u16: copying the strip tables failed"));
-    for (long s0 = 0; s0 < nstrips; s0 += kStreamsPerLaunch) {
-        const long ns = nstrips - s0 < kStreamsPerLaunch ? nstrips - s0 : kStreamsPerLaunch;
-        DeflateJob j{d_file, d_off, d_len, rows, width, spp, rows_per_strip, nstrips, s0, d_img, d_got, d_status};
-        OipProfScope prof(ctx, "deflate_decode_kernel");
-        hipLaunchKernelGGL(deflate_decode_kernel, dim3((unsigned)ns), dim3(64), 0, ctx->stream, j);
-    }
-    if (predictor == 2 && width > 1) {
-        OipProfScope prof(ctx, "deflate_unpredict_kernel");
-        if (spp == 4) hipLaunchKernelGGL(deflate_unpredict_kernel<4>, dim3((unsigned)rows), dim3(64), 0, ctx->stream, d_img, rows, width, rows_per_strip, d_got, d_status);
-        else if (spp == 1) hipLaunchKernelGGL(deflate_unpredict_kernel<1>, dim3((unsigned)rows), dim3(64), 0, ctx->stream, d_img, rows, width, rows_per_strip, d_got, d_status);
-        else hipLaunchKernelGGL(deflate_unpredict_any_kernel, dim3((unsigned)rows), dim3(64), 0, ctx->stream, d_img, rows, width, spp, rows_per_strip, d_got, d_status);
-    }
-    std::vector<unsigned> got((size_t)nstrips);
-    std::vector<int> status((size_t)nstrips);
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(got.data(), d_got, (size_t)nstrips * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(status.data(), d_status, (size_t)nstrips * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess)
-        return fail(oip_fail(ctx, OIP_E_DEVICE, "oip_tiff_deflate_decode_u16: decoding failed on the device"));
-    (void)hipFree(scratch);
-    for (long k = 0; k < nstrips; ++k) {
-        const long nr = rows - k * rows_per_strip < rows_per_strip ? rows - k * rows_per_strip : rows_per_strip;
-        const size_t want = (size_t)nr * rowBytes;
-        if (status[(size_t)k] != 0)
-            return oip_fail(ctx, OIP_E_RUNTIME, "corrupt Deflate stream (%s) in strip %ld", oipinflate::status_text(status[(size_t)k]), k);
-        if (got[(size_t)k] != want) return oip_fail(ctx, OIP_E_RUNTIME, "strip %ld decodes to %u bytes, %zu expected", k, got[(size_t)k], want);
-    }
-    return OIP_OK;
+    return oip_tiff_decode(ctx, "oip_tiff_deflate_decode_u16", "Deflate", oipinflate::status_text, oipinflate::kMaxStream, 0, d_file, file_bytes, strip_off,
+                           strip_len, nstrips, rows, width, spp, rows_per_strip, predictor, d_img, [&](const OipTiffStreams &t) {
+        for (long s0 = 0; s0 < nstrips; s0 += kStreamsPerLaunch) {
+            const long ns = nstrips - s0 < kStreamsPerLaunch ? nstrips - s0 : kStreamsPerLaunch;
+            DeflateJob j{d_file, t.off, t.len, rows, width, spp, rows_per_strip, nstrips, s0, d_img, t.got, t.status};
+            OipProfScope prof(ctx, "deflate_decode_kernel");
+            hipLaunchKernelGGL(deflate_decode_kernel, dim3((unsigned)ns), dim3(64), 0, ctx->stream, j);
+        }
+        if (predictor == 2 && width > 1) {
+            OipProfScope prof(ctx, "deflate_unpredict_kernel");
+            if (spp == 4) hipLaunchKernelGGL(deflate_unpredict_kernel<4>, dim3((unsigned)rows), dim3(64), 0, ctx->stream, d_img, rows, width, rows_per_strip, t.got, t.status);
+            else if (spp == 1) hipLaunchKernelGGL(deflate_unpredict_kernel<1>, dim3((unsigned)rows), dim3(64), 0, ctx->stream, d_img, rows, width, rows_per_strip, t.got, t.status);
+            else hipLaunchKernelGGL(deflate_unpredict_any_kernel, dim3((unsigned)rows), dim3(64), 0, ctx->stream, d_img, rows, width, spp, rows_per_strip, t.got, t.status);
+        }
+    });
 }

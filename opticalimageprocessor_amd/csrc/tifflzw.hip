@@ -19,6 +19,8 @@
 // The encoded strips land in fixed slots (worst case: 1.5 bytes per byte); a second kernel packs them behind one another
 // (even offsets, as the host writer places them) so that the payload leaves the device as one block.
 #include "oip_internal.h"
+#include "oip_tiffdecode.h"
+#include "oip_tiffshared.h"
 
 #include <cstdint>
 #include <vector>
@@ -290,7 +292,7 @@ extern "C" size_t oip_tiff_lzw_worst_bytes(long rows, int width, int spp, long r
     if (rows <= 0 || width <= 0 || spp <= 0 || rows_per_strip <= 0) return 0;
     const size_t strip = (size_t)rows_per_strip * width * spp * 2;
     const size_t nstrips = ((size_t)rows + rows_per_strip - 1) / rows_per_strip;
-    return nstrips * (strip + strip / 2 + strip / 1024 + 64 + 2);
+    return nstrips * (OIPGPU::tiffdetail::lzw_worst(strip) + 2);
 }
 
 // device scratch of one call: the lanes' tables, their output slots, the strip lengths and offsets
@@ -310,7 +312,7 @@ extern "C" size_t oip_tiff_lzw_scratch_bytes(long rows, int width, int spp, long
     if (rows <= 0 || width <= 0 || spp <= 0 || rows_per_strip <= 0) return 0;
     const long nstrips = (rows + rows_per_strip - 1) / rows_per_strip;
     const size_t strip = (size_t)rows_per_strip * width * spp * 2;
-    const size_t slot_bytes = (strip + strip / 2 + strip / 1024 + 64 + 3) / 4 * 4;
+    const size_t slot_bytes = (OIPGPU::tiffdetail::lzw_worst(strip) + 3) / 4 * 4;
     size_t a, b, c, d, total;
     lzw_scratch_layout(nstrips, slot_bytes, &a, &b, &c, &d, &total);
     return total;
@@ -329,7 +331,7 @@ extern "C" int oip_tiff_lzw_strips_u16(oip_ctx *ctx, const uint16_t *d_img, long
     const long nstrips = (rows + rows_per_strip - 1) / rows_per_strip;
     const size_t strip = (size_t)rows_per_strip * width * spp * 2;
     if (strip > (1u << 30)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_lzw_strips_u16: strip larger than 1 GiB");
-    const size_t slot_bytes = (strip + strip / 2 + strip / 1024 + 64 + 3) / 4 * 4;
+    const size_t slot_bytes = (OIPGPU::tiffdetail::lzw_worst(strip) + 3) / 4 * 4;
     const long per = nstrips < kStripsPerLaunch ? nstrips : kStripsPerLaunch;
     size_t o_tab, o_slots, o_len, o_off, need;
     lzw_scratch_layout(nstrips, slot_bytes, &o_tab, &o_slots, &o_len, &o_off, &need);
@@ -396,60 +398,28 @@ extern "C" int oip_tiff_lzw_strips_u16(oip_ctx *ctx, const uint16_t *d_img, long
     return OIP_OK;
 }
 
+static const char *lzw_reason(int status)
+{
+    return status == 1 ? "bad first code" : status == 2 ? "code beyond the table" : "table full without ClearCode";
+}
+
+// (the refusals are oip_tiff_decode's and no others: the Deflate decoder has two more)
 extern "C" int oip_tiff_lzw_decode_u16(oip_ctx *ctx, const uint8_t *d_file, size_t file_bytes, const uint64_t *strip_off,
                                        const uint64_t *strip_len, long nstrips, long rows, int width, int spp, long rows_per_strip,
                                        int predictor, uint16_t *d_img)
 {
     OIP_CHECK_CTX(ctx);
-    if (!d_file || !strip_off || !strip_len || !d_img || nstrips <= 0 || rows <= 0 || width <= 0 || spp <= 0 || spp > 16 || rows_per_strip <= 0 ||
-        (predictor != 1 && predictor != 2))
-        return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_lzw_decode_u16: bad argument");
-    if (nstrips != (rows + rows_per_strip - 1) / rows_per_strip) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_lzw_decode_u16: strip count does not match RowsPerStrip");
-    const size_t rowBytes = (size_t)width * spp * 2;
-    if ((size_t)rows_per_strip * rowBytes >= ((size_t)1 << 32)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_lzw_decode_u16: strip of 4 GiB or more");
-    if (spp == 4 && predictor == 2 && (((uintptr_t)d_img) & 7)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_lzw_decode_u16: image not 8-byte aligned");
-    for (long k = 0; k < nstrips; ++k)
-        if (strip_off[k] > file_bytes || strip_len[k] > file_bytes - strip_off[k] || strip_len[k] >= ((uint64_t)1 << 32))
-            return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_lzw_decode_u16: strip %ld outside the buffer", k);
-    const long per = nstrips < kStripsPerLaunch ? nstrips : kStripsPerLaunch;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_off = up((size_t)per * 4096 * 8), o_len = o_off + up((size_t)nstrips * 8), o_got = o_len + up((size_t)nstrips * 8),
-                 o_status = o_got + up((size_t)nstrips * 4), need = o_status + up((size_t)nstrips * 4);
-    void *scratch = nullptr;
-    OIP_HIP(ctx, hipMalloc(&scratch, need));
-    auto fail = [&](int rc) { (void)hipFree(scratch); return rc; };
-    unsigned long long *d_tab = reinterpret_cast<unsigned long long *>(scratch);
-    unsigned long long *d_off = reinterpret_cast<unsigned long long *>((char *)scratch + o_off);
-    unsigned long long *d_len = reinterpret_cast<unsigned long long *>((char *)scratch + o_len);
-    unsigned *d_got = reinterpret_cast<unsigned *>((char *)scratch + o_got);
-    int *d_status = reinterpret_cast<int *>((char *)scratch + o_status);
-    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "strip tables are copied as they are");
-    if (hipMemcpyAsync(d_off, strip_off, (size_t)nstrips * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(d_len, strip_len, (size_t)nstrips * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        return fail(oip_fail(ctx, OIP_E_DEVICE, "oip_tiff_lzw_decode_u16: copying the strip tables failed"));
-    for (long s0 = 0; s0 < nstrips; s0 += per) {
-        const long ns = nstrips - s0 < per ? nstrips - s0 : per;
-        // (the decoder does not gain from emptier waves as the encoder does: 64 / 16 / 8 / 4 lanes 98 / 102 / 115 / 120 ms)
-        const int active = 64;
-        LzwDecJob j{d_file, d_off, d_len, rows, width, spp, rows_per_strip, nstrips, s0, predictor, d_img, d_tab, d_got, d_status, active};
-        OipProfScope prof(ctx, "lzw_decode_kernel");
-        hipLaunchKernelGGL(lzw_decode_kernel, dim3((unsigned)((ns + active - 1) / active)), dim3(64), 0, ctx->stream, j);
-    }
-    std::vector<unsigned> got((size_t)nstrips);
-    std::vector<int> status((size_t)nstrips);
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(got.data(), d_got, (size_t)nstrips * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(status.data(), d_status, (size_t)nstrips * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess)
-        return fail(oip_fail(ctx, OIP_E_DEVICE, "oip_tiff_lzw_decode_u16: decoding failed on the device"));
-    (void)hipFree(scratch);
-    for (long k = 0; k < nstrips; ++k) {
-        const long nr = rows - k * rows_per_strip < rows_per_strip ? rows - k * rows_per_strip : rows_per_strip;
-        const size_t want = (size_t)nr * rowBytes;
-        if (status[(size_t)k] == 1) return oip_fail(ctx, OIP_E_RUNTIME, "corrupt LZW stream (bad first code) in strip %ld", k);
-        if (status[(size_t)k] == 2) return oip_fail(ctx, OIP_E_RUNTIME, "corrupt LZW stream (code beyond the table) in strip %ld", k);
-        if (status[(size_t)k] == 3) return oip_fail(ctx, OIP_E_RUNTIME, "corrupt LZW stream (table full without ClearCode) in strip %ld", k);
-        if (got[(size_t)k] != want) return oip_fail(ctx, OIP_E_RUNTIME, "strip %ld decodes to %u bytes, %zu expected", k, got[(size_t)k], want);
-    }
-    return OIP_OK;
+    const long per = nstrips < kStripsPerLaunch ? nstrips : kStripsPerLaunch;                       // (a lane: 4096 table entries)
+    return oip_tiff_decode(ctx, "oip_tiff_lzw_decode_u16", "LZW", lzw_reason, (uint64_t)1 << 32, per > 0 ? (size_t)per * 4096 * 8 : 0, d_file, file_bytes,
+                           strip_off, strip_len, nstrips, rows, width, spp, rows_per_strip, predictor, d_img, [&](const OipTiffStreams &t) {
+        for (long s0 = 0; s0 < nstrips; s0 += per) {
+            const long ns = nstrips - s0 < per ? nstrips - s0 : per;
+            // (the decoder does not gain from emptier waves as the encoder does: 64 / 16 / 8 / 4 lanes 98 / 102 / 115 / 120 ms)
+            const int active = 64;
+            LzwDecJob j{d_file, t.off, t.len, rows, width, spp, rows_per_strip, nstrips, s0, predictor, d_img,
+                        reinterpret_cast<unsigned long long *>(t.tables), t.got, t.status, active};
+            OipProfScope prof(ctx, "lzw_decode_kernel");
+            hipLaunchKernelGGL(lzw_decode_kernel, dim3((unsigned)((ns + active - 1) / active)), dim3(64), 0, ctx->stream, j);
+        }
+    });
 }

@@ -321,3 +321,41 @@ def _write_tiff_lzw(path, a, predictor, rps, strips=None):
         for t in tags:
             f.write(struct.pack("<HHII", *t))
         f.write(struct.pack("<I", 0))
+
+
+def write_raw_tiff(path, tags, payload=b"", big=False, magic=None, order=b"II", ifd_at=None, count=None):
+    """A little-endian TIFF / BigTIFF put together entry by entry, for files that are wrong in one chosen way.  `payload` lies right
+    behind the header (offset 8, BigTIFF 16), then the out-of-line values, then the directory.  tags: {id: (type, [values])} -- the
+    values go inline where they fit the entry -- or {id: (type, count, field)}: the entry as given, whatever it says.  magic, order,
+    ifd_at and count (of entries) overwrite what the header and the directory would say."""
+    osz, ofmt = (8, "<Q") if big else (4, "<I")
+    tfmt = {3: "H", 4: "I", 16: "Q"}
+    base = (16 if big else 8) + len(payload)
+    extra, entries = b"", []
+    for tid in sorted(tags):
+        t = tags[tid]
+        if len(t) == 3:
+            entries.append((tid, t[0], t[1], struct.pack(ofmt, t[2])))
+            continue
+        raw = struct.pack("<%d%s" % (len(t[1]), tfmt[t[0]]), *t[1])
+        if len(raw) <= osz:
+            field = raw.ljust(osz, b"\0")
+        else:
+            extra += b"\0" * (len(extra) & 1)
+            field = struct.pack(ofmt, base + len(extra))
+            extra += raw
+        entries.append((tid, t[0], len(t[1]), field))
+    extra += b"\0" * (len(extra) & 1)
+    ifd = base + len(extra) if ifd_at is None else ifd_at
+    n = len(entries) if count is None else count
+    with open(path, "wb") as f:
+        if big:
+            f.write(order + struct.pack("<HHHQ", 43 if magic is None else magic, 8, 0, ifd))
+        else:
+            f.write(order + struct.pack("<HI", 42 if magic is None else magic, ifd))
+        f.write(payload)
+        f.write(extra)
+        f.write(struct.pack("<Q" if big else "<H", n))
+        for tid, typ, cnt, field in entries:
+            f.write(struct.pack("<HH", tid, typ) + struct.pack(ofmt, cnt) + field)
+        f.write(struct.pack(ofmt, 0))

@@ -258,7 +258,7 @@ static int run_tiff(const std::string &listPath)
         // the layout-only pass (what the device route starts from) takes and refuses the same files
         TiffLayout lay;
         std::string err2;
-        try { read_tiff_u16(tiff, &w, &h, &spp, nullptr, &lay); }
+        try { lay = read_tiff_layout(tiff); }
         catch (const std::exception &e) { err2 = e.what(); }
         if (raw != "-") CHECK(err2.empty() && lay.compression == TIFF_DEFLATE, "%s: layout: %s", tiff.c_str(), err2.c_str());
         ++n;

@@ -157,8 +157,7 @@ static void round_trip(const std::string &dir, std::ofstream &kept, int w, long 
     try {
         read_tiff_u16(path, &rw, &rh, &rs, &back);
         CHECK(rw == w && rh == h && rs == spp && back == lv[0], "%s: reads back differently", name);
-        TiffLayout lay;
-        read_tiff_u16(path, &rw, &rh, &rs, nullptr, &lay);
+        const TiffLayout lay = read_tiff_layout(path);
         CHECK(lay.tiled() && lay.tile_width == (uint64_t)T && lay.tile_length == (uint64_t)T && lay.rows_per_strip == 0 &&
                   lay.offs.size() == (size_t)(((w + T - 1) / T) * ((h + T - 1) / T)), "%s: layout", name);
     } catch (const std::exception &e) { CHECK(false, "%s: %s", name, e.what()); }
@@ -309,9 +308,8 @@ static void odd_tiles_and_strips(const std::string &dir)
         int rw = 0, rs = 0;
         long rh = 0;
         std::vector<uint16_t> back;
-        TiffLayout lay;
         read_tiff_u16(dir + "/strips.tiff", &rw, &rh, &rs, &back);
-        read_tiff_u16(dir + "/strips.tiff", &rw, &rh, &rs, nullptr, &lay);
+        const TiffLayout lay = read_tiff_layout(dir + "/strips.tiff");
         CHECK(back == img && rw == w && rh == h && !lay.tiled() && lay.tile_length == 0 && lay.rows_per_strip == (uint64_t)h, "strip file, compression %d", comp);
     }
     const int tx = (w + TW - 1) / TW, ty = (int)((h + TL - 1) / TL);

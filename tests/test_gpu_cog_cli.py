@@ -157,3 +157,45 @@ def test_tiles_of_48_x_32_read_on_the_host(tmp_path, spp):
         assert np.array_equal(dirs[0]["img"], img)
         _run("overviews", ["T.TIFF", "-o", "got.ovr", "--force"], d)
         assert _sha(os.path.join(d, "got.ovr")) == _sha(os.path.join(d, "want.ovr")), lzw
+
+
+def _lzw_literals(data):
+    """a legal LZW stream that no encoder writes and numpy packs at once: ClearCode before every 253 bytes, every byte its own
+    9-bit code (the decoder's table stays below 511 entries, so no code ever widens), EndOfInformation"""
+    a = np.frombuffer(data, np.uint8).astype(np.uint16)
+    pad = (-len(a)) % 253
+    g = np.concatenate([a, np.zeros(pad, np.uint16)]).reshape(-1, 253)
+    codes = np.concatenate([np.full((len(g), 1), 256, np.uint16), g], axis=1).ravel()
+    codes = np.concatenate([codes[:len(codes) - pad], [257]]).astype(np.uint16)
+    bits = ((codes[:, None] >> np.arange(8, -1, -1)) & 1).astype(np.uint8)
+    return np.packbits(bits.ravel()).tobytes()
+
+
+def test_a_corrupt_lzw_tile_in_the_second_batch_is_named_with_its_batch(tmp_path):
+    """4100 x 40 of 4 samples in LZW tiles of 16: three tile rows of 257 tiles, 514 KiB of samples each, so that OIP_COG_BATCH_MB=1
+    (the smallest value the hook takes) makes a batch of every tile row -- the reader's stream helper runs three times.  Tile 262,
+    the sixth of the second batch, starts with a code above 255: the device decoder counts a batch's tiles as the strips of a
+    16-wide image and the reader adds where the batch began."""
+    import _tiff
+    d = str(tmp_path)
+    w, h, T = 4100, 40, 16
+    img = _blocks(h, w, 4, 11).reshape(h, w, 4)
+    tx, ty = -(-w // T), -(-h // T)
+    pad = np.zeros((ty * T, tx * T, 4), np.uint16)
+    pad[:h, :w] = img
+    tiles = pad.reshape(ty, T, tx, T, 4).transpose(0, 2, 1, 3, 4).reshape(ty * tx, T, T, 4).astype(np.int64)
+    tiles[:, :, 1:] -= tiles[:, :, :-1].copy()                                            # predictor 2 along each tile row
+    streams = [_lzw_literals((t & 0xFFFF).astype("<u2").tobytes()) for t in tiles]
+    assert len(streams) == 771
+    streams[262] = bytes([0x80, 0x4B, 0x00]) + streams[262][3:]                           # ClearCode, then code 300
+    body, offs = b"", []
+    for s in streams:
+        body += b"\0" * (len(body) & 1)
+        offs.append(8 + len(body))
+        body += s
+    _tiff.write_raw_tiff(os.path.join(d, "bad.TIFF"), {256: (4, [w]), 257: (4, [h]), 258: (3, [16] * 4), 259: (3, [5]), 262: (3, [2]), 277: (3, [4]),
+                                                       284: (3, [1]), 317: (3, [2]), 322: (4, [T]), 323: (4, [T]), 324: (4, offs),
+                                                       325: (4, [len(s) for s in streams]), 338: (3, [2]), 339: (3, [1] * 4)}, body)
+    r = subprocess.run([OIP, "quicklook", "bad.TIFF", "-o", "bad.ql.TIFF"], cwd=d, env=dict(os.environ, LOGFILE=os.path.join(d, "oip.log"), OIP_COG_BATCH_MB="1"),
+                       capture_output=True, text=True)
+    assert r.returncode == 2 and "corrupt LZW stream (bad first code) in strip 5 (tiles from 257 on)" in r.stdout + r.stderr, r.stdout + r.stderr
