@@ -33,6 +33,7 @@
 #include <dlfcn.h>
 
 #include "oip_host.hpp"
+#include "oip_loopcomm.hpp"
 #include "oip_rankguard.hpp"
 
 // RCCL is loaded when the first --gpus run asks for it, not with the executable: a single-GPU `oip` run then depends on
@@ -40,8 +41,66 @@
 // optimisation: an executable linked against the 570 MB librccl.so starts in 13.8 ms, this one in 12.5 ms
 // (profiles/experiments/rccl_link_probe, `--version`, best of five each).  Types come from <rccl/rccl.h>; the entry points
 // are resolved from librccl.so.1 on first use.
+//
+// OIP_COMM=loopback (TEST ONLY) fills the same table from oip_loopcomm.hpp instead: the N ranks meet inside the process and all
+// use one GPU (OIP_LOOPBACK_DEVICE, default 0), so every line of this host runs with N > 1 on a one-GPU machine -- real device
+// buffers, streams and events, a device-to-device copy per matched send / receive.  librccl.so is not loaded in that mode.  It
+// proves the host's ordering and addressing, not RCCL's behaviour or any link rate.
 namespace OIPGPU {
+// the loopback communicator under RCCL's signatures; ncclComm_t is an opaque pointer, a LoopComm stands behind it
+struct LoopbackRccl {
+    static LoopDeviceOps hip_ops()
+    {
+        LoopDeviceOps o;
+        o.record = [](void *stream) -> void * {
+            hipEvent_t e = nullptr;
+            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
+            if (hipEventRecord(e, (hipStream_t)stream) != hipSuccess) { hipEventDestroy(e); return nullptr; }
+            return e;
+        };
+        o.wait = [](void *stream, void *event) { return hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)event, 0) == hipSuccess; };
+        o.copy = [](void *dst, const void *src, size_t bytes, void *stream) {
+            return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess;
+        };
+        o.release = [](void *event) { hipEventDestroy((hipEvent_t)event); };
+        return o;
+    }
+    static ncclResult_t rc(int e) { return e ? ncclInternalError : ncclSuccess; }
+    static LoopComm *lc(ncclComm_t c) { return reinterpret_cast<LoopComm *>(c); }
+    static size_t bytes_of(ncclDataType_t t)                                           // the host sends ncclUint8 and gathers ncclDouble
+    {
+        if (t == ncclUint8) return 1;
+        if (t == ncclDouble) return 8;
+        throw std::invalid_argument("loopback communicator: only ncclUint8 and ncclDouble are bound");
+    }
+    static ncclResult_t CommInitAll(ncclComm_t *comms, int n, const int *)             // (repeated device ids are what it is for)
+    {
+        const std::vector<LoopComm *> v = loop_init_all(n, hip_ops());
+        for (int i = 0; i < n; ++i) comms[i] = reinterpret_cast<ncclComm_t>(v[(size_t)i]);
+        return ncclSuccess;
+    }
+    static ncclResult_t CommDestroy(ncclComm_t c) { return rc(loop_destroy(lc(c))); }
+    static ncclResult_t CommAbort(ncclComm_t c) { return rc(loop_abort(lc(c))); }     // wakes and fails; CommDestroy frees
+    static ncclResult_t GroupStart() { return rc(loop_group_start()); }
+    static ncclResult_t GroupEnd() { return rc(loop_group_end()); }
+    static ncclResult_t Send(const void *buf, size_t count, ncclDataType_t t, int peer, ncclComm_t c, hipStream_t s)
+    {
+        return rc(loop_send(lc(c), buf, count * bytes_of(t), peer, s));
+    }
+    static ncclResult_t Recv(void *buf, size_t count, ncclDataType_t t, int peer, ncclComm_t c, hipStream_t s)
+    {
+        return rc(loop_recv(lc(c), buf, count * bytes_of(t), peer, s));
+    }
+    static ncclResult_t AllGather(const void *send, void *recv, size_t count, ncclDataType_t t, ncclComm_t c, hipStream_t s)
+    {
+        return rc(loop_allgather(lc(c), send, recv, count * bytes_of(t), s));
+    }
+    static const char *GetErrorString(ncclResult_t) { return loop_last_error(); }       // (of the calling thread's last call)
+};
+
 struct RcclApi {
+    bool loopback = false;
+    int loopback_device = 0;
     decltype(&::ncclCommInitAll) CommInitAll;
     decltype(&::ncclCommDestroy) CommDestroy;
     decltype(&::ncclCommAbort) CommAbort;
@@ -59,6 +118,16 @@ struct RcclApi {
 private:
     RcclApi()
     {
+        const char *mode = getenv("OIP_COMM");
+        if (mode && !strcmp(mode, "loopback")) {
+            loopback = true;
+            if (const char *d = getenv("OIP_LOOPBACK_DEVICE")) loopback_device = atoi(d);
+            CommInitAll = &LoopbackRccl::CommInitAll; CommDestroy = &LoopbackRccl::CommDestroy; CommAbort = &LoopbackRccl::CommAbort;
+            GroupStart = &LoopbackRccl::GroupStart; GroupEnd = &LoopbackRccl::GroupEnd; Send = &LoopbackRccl::Send; Recv = &LoopbackRccl::Recv;
+            AllGather = &LoopbackRccl::AllGather; GetErrorString = &LoopbackRccl::GetErrorString;
+            return;
+        }
+        if (mode && *mode && strcmp(mode, "rccl")) throw std::runtime_error(std::string("OIP_COMM: rccl or loopback expected, not ") + mode);
         void *h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
         if (!h) h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
         if (!h) throw std::runtime_error(std::string("--gpus needs RCCL: ") + dlerror());
@@ -446,28 +515,37 @@ inline void LogStageClocks(const std::vector<StageClock> &clk, const std::vector
 // ---- the node: one context, stream and communicator per GPU, one host thread per GPU -------------------------------
 class Node {
 public:
-    explicit Node(int n) : N(n), bar(n), ctx(n, nullptr), comms(n), err(n)
+    explicit Node(int n) : N(n), bar(n), ctx(n, nullptr), comms(n), err(n), first(n), window_stats(n)
     {
+        const RcclApi &api = RcclApi::get();
+        loopback = api.loopback;
         int have = 0;
-        if (hipGetDeviceCount(&have) != hipSuccess || have < n)
+        if (hipGetDeviceCount(&have) != hipSuccess) have = 0;
+        if (loopback) {
+            if (api.loopback_device < 0 || api.loopback_device >= have)
+                throw std::runtime_error("OIP_LOOPBACK_DEVICE " + std::to_string(api.loopback_device) + ": only " + std::to_string(have) + " GPUs visible");
+        } else if (have < n)
             throw std::runtime_error("--gpus " + std::to_string(n) + ": only " + std::to_string(have) + " GPUs visible");
         std::vector<int> devs(n);
         for (int i = 0; i < n; ++i) {
-            devs[i] = i;
-            if (oip_create(i, &ctx[i]) != OIP_OK) throw std::runtime_error("no usable MI355X (gfx950) device " + std::to_string(i));
+            devs[i] = loopback ? api.loopback_device : i;
+            if (oip_create(devs[i], &ctx[i]) != OIP_OK) throw std::runtime_error("no usable MI355X (gfx950) device " + std::to_string(devs[i]));
         }
+        dev_of = devs;
         if (ncclCommInitAll(comms.comm.data(), n, devs.data()) != ncclSuccess) throw std::runtime_error("ncclCommInitAll failed");
         // a communication stream per GPU: the window exchange runs on it, beside the compute stream's kernels
         cstream.assign(n, nullptr);
         for (int i = 0; i < n; ++i) {
-            if (hipSetDevice(i) != hipSuccess || hipStreamCreateWithFlags(&cstream[i], hipStreamNonBlocking) != hipSuccess)
+            if (hipSetDevice(dev_of[i]) != hipSuccess || hipStreamCreateWithFlags(&cstream[i], hipStreamNonBlocking) != hipSuccess)
                 throw std::runtime_error("communication stream of GPU " + std::to_string(i));
         }
     }
     ~Node()
     {
-        for (size_t i = 0; i < cstream.size(); ++i) if (cstream[i]) { hipSetDevice((int)i); hipStreamDestroy(cstream[i]); }
-        if (!comms.aborted()) for (auto c : comms.comm) if (c) ncclCommDestroy(c);       // ncclCommAbort has already freed them otherwise
+        // (the rank threads have joined: run() returned or never started)
+        for (size_t i = 0; i < cstream.size(); ++i) if (cstream[i]) { hipSetDevice(dev_of[i]); hipStreamDestroy(cstream[i]); }
+        // ncclCommAbort has already freed RCCL's communicators; the loopback's abort only wakes and fails, its destroy frees
+        if (!comms.aborted() || loopback) for (auto c : comms.comm) if (c) ncclCommDestroy(c);
         for (auto c : ctx) if (c) oip_destroy(c);
     }
     hipStream_t stream(int r) { return (hipStream_t)oip_get_stream(ctx[r]); }
@@ -488,39 +566,38 @@ public:
             throw std::runtime_error("read file [" + file + "] failed: " + std::to_string(got) + " of " + std::to_string(bytes) +
                                      " bytes at offset " + std::to_string(offset));
     }
-    // run fn(rank) on one thread per GPU; the first exception is re-thrown on the caller
+    // run fn(rank) on one thread per GPU; the exception of the rank that failed first is re-thrown on the caller
     template <typename F> void run(F fn)
     {
         std::vector<std::thread> th;
-        std::vector<std::exception_ptr> ex(N);
         for (int r = 0; r < N; ++r)
             th.emplace_back([&, r] {
-                try { hipSetDevice(r); fn(r); }
+                try { hipSetDevice(dev_of[r]); fn(r); }
                 catch (...) {
                     // A rank that gives up after a pre-exchange barrier leaves its peers inside a grouped send/recv, blocked in
                     // oip_sync on a kernel that waits for this rank for ever: setting a flag does not unblock a device-side wait.
                     // Aborting every communicator makes those kernels exit, the peers' streams drain, their oip_sync returns
                     // and they leave through sync_point(); the process then exits non-zero with this rank's message.
-                    ex[r] = std::current_exception(); failed = true; bar.abort(); abort_comms();
+                    // The failure is noted BEFORE anything that makes the peers fail: what they raise afterwards (PeerFailed, or
+                    // the error of a call that the abort released, see nccl_ok) is a consequence, whatever their rank index.
+                    first.note(r, std::current_exception()); bar.abort(); abort_comms();
                 }
             });
         for (auto &t : th) t.join();
-        // the rank that failed first tells why; the others only report that a peer gave up
-        for (auto &e : ex)
-            if (e) {
-                try { std::rethrow_exception(e); }
-                catch (const PeerFailed &) { continue; }
-            }
-        for (auto &e : ex) if (e) std::rethrow_exception(e);
+        first.rethrow();                    // the rank that failed first tells why
     }
+    bool failed() const { return first.any(); }
     // every rank thread calls this at the same point; a failure on any rank is raised on all (no rank is left waiting
     // in a collective for a peer that has given up)
     void sync_point()
     {
-        if (!bar.wait() || failed) throw PeerFailed();
+        if (!bar.wait() || failed()) throw PeerFailed();
     }
-    // waits for the RCCL calls in flight on the peers' threads (CommGuard), then aborts every communicator once; from then
-    // on with_comm() throws PeerFailed instead of touching a freed communicator
+    // aborts every communicator once, without waiting for the calls in flight on the peers' threads (CommGuard): a peer may
+    // be blocked in one until this rank arrives, and the abort is what releases it.  From the first abort on with_comm()
+    // throws PeerFailed.  (ncclCommAbort also frees: RCCL allows it beside a call in flight on that communicator, but a call
+    // that passed with_comm()'s check and has not entered RCCL yet would meet a freed communicator -- a window of a few
+    // instructions that only a run on real RCCL with N > 1 could show; the loopback's abort frees nothing.)
     void abort_comms()
     {
         comms.abort_all([](ncclComm_t c) { if (c) ncclCommAbort(c); });
@@ -528,14 +605,17 @@ public:
     // every use of a communicator -- one call or a whole ncclGroupStart .. ncclGroupEnd sequence -- goes through here
     template <typename F> void with_comm(int r, F f)
     {
-        if (failed) throw PeerFailed();
+        if (failed()) throw PeerFailed();
         comms.use(r, f);
     }
     // an RCCL call that fails is this rank's failure: raised at once (run() then aborts the communicators), never carried
-    // into a stream synchronisation that a peer may not be able to complete
-    static void nccl_ok(ncclResult_t rc, const char *what)
+    // into a stream synchronisation that a peer may not be able to complete.  Once the node has failed it is a consequence
+    // of the abort instead: PeerFailed, so that run() reports the culprit and not this call
+    void nccl_ok(ncclResult_t rc, const char *what)
     {
-        if (rc != ncclSuccess) throw std::runtime_error(std::string(what) + " failed: " + ncclGetErrorString(rc));
+        if (rc == ncclSuccess) return;
+        if (failed()) throw PeerFailed();
+        throw std::runtime_error(std::string(what) + " failed: " + ncclGetErrorString(rc));
     }
 
     // exchange step 1, overlapped with the correlation: every group of units that is not entirely on its rank is packed and
@@ -618,7 +698,19 @@ public:
         for (void *t : pe->temps) oip_free(ctx[r], t);
         pe->groups.clear();
         pe->temps.clear();
+        if (loopback) window_stats[r] = loop_stats(LoopbackRccl::lc(comms.comm[r]));
         sync_point();
+    }
+    // OIP_COMM=loopback: what every rank sent and received, for the test that compares it with the plan's sums
+    void log_loopback_accounting()
+    {
+        if (!loopback) return;
+        for (int r = 0; r < N; ++r) {
+            const LoopStats s = loop_stats(LoopbackRccl::lc(comms.comm[r])), &w = window_stats[r];
+            RLOG("loopback: GPU %d sent %ld bytes in %ld sends, received %ld bytes in %ld receives", r, s.send_bytes, s.sends, s.recv_bytes, s.recvs);
+            RLOG("loopback: GPU %d window exchange alone: sent %ld bytes in %ld sends, received %ld bytes in %ld receives; %ld all-gathers of %ld bytes",
+                 r, w.send_bytes, w.sends, w.recv_bytes, w.recvs, s.gathers, s.gather_bytes);
+        }
     }
 
     // exchange step 3: whole lines into the halo rows of a raster.  ptr_of(global line, plane) -> device pointer on
@@ -689,7 +781,10 @@ public:
     CommGuard<ncclComm_t> comms;
     std::vector<hipStream_t> cstream;
     std::vector<std::string> err;
-    std::atomic<bool> failed{false};
+    FirstFailure first;
+    bool loopback = false;
+    std::vector<int> dev_of;                    // rank -> HIP device: the identity, or OIP_LOOPBACK_DEVICE for every rank
+    std::vector<LoopStats> window_stats;        // the loopback's accounting when the window exchange had drained
 };
 
 struct MultiGpuDefaultOptions : PreProcessor::DefaultActionOptions {      // (no --write-rrcpan with --gpus)
@@ -854,6 +949,7 @@ inline void RunDefaultActionMultiGpu(const std::string &panFile, const std::stri
         oip_free(c, d_kb); oip_free(c, planes); oip_free(c, pan);
     });
     LogStageClocks(clocks, plan.predicted_finish_us);
+    node.log_loopback_accounting();
     LogShiftCoeffs(cxAll, cyAll);
     // preproc.h:167-185: one ALIGNED.TIFF, the blocks in rank order
     auto save = IMO::BuildOutputFilePath(mssFile, ".ALIGNED", ".TIFF");
@@ -882,6 +978,8 @@ inline void RunPrestitchMultiGpu(const std::string &pan1, const std::string &pan
     if (s1 != s2) throw std::invalid_argument("PAN1 size doesn't match PAN2 size");
     const long L = (long)(s1 / lineBytes);
     CcdPlanC plan(W, L, N, o.sections, o.sectionLines, o.overlapCols, o.edgeCols);
+    OLOG("Strips of %ld lines on %d GPUs: %ld lines per GPU, %d correlation sections dealt %s.", L, N, plan.pb, plan.n_units,
+         plan.correlation_pieces().empty() ? "without moving a line" : "with window exchange");
     if (!o.onlyCalc && L <= OIP_REMAP_ROW_GUARD) throw std::invalid_argument("too few data rows, please use cv::remap()");   // imageop.h:242-244
     std::vector<double> kb1, kb2;
     if (o.doRRC && !o.onlyCalc) {
@@ -1020,6 +1118,7 @@ inline void RunPrestitchMultiGpu(const std::string &pan1, const std::string &pan
         oip_free(c, dst); oip_free(c, r2); oip_free(c, p1);
     });
     LogStageClocks(clocks, plan.predicted_finish_us);
+    node.log_loopback_accounting();
     if (!o.onlyCalc) OLOG("Pre-stitched PAN2 written to file '%s' (dx %.5f, dy %.5f).", fp.c_str(), dxAll, dyAll);
 }
 

@@ -3,16 +3,20 @@
 //
 //   HostBarrier   the ranks' meeting point; abort() releases everybody (wait() returns false from then on).
 //   CommGuard     the communicators.  Every use of a communicator -- a single call or a whole ncclGroupStart..End
-//                 sequence -- runs inside use(), which holds the guard shared; abort_all() takes it exclusively, so it
-//                 waits for the calls in flight, runs the abort function on every communicator exactly once, and every
-//                 later use() throws PeerFailed instead of touching a communicator that ncclCommAbort has freed
-//                 (the failing thread used to abort while its peers were still issuing ncclSend / ncclRecv).
+//                 sequence -- runs inside use().  abort_all() sets the aborted flag first, so every later use() throws
+//                 PeerFailed, then runs the abort function on every communicator exactly once WITHOUT waiting for the calls in
+//                 flight: a peer may sit inside use() in a call that blocks until the failed rank arrives (a connection
+//                 handshake), and the abort is what releases it (the earlier guard took a lock exclusively there and
+//                 could wait for ever).  The abort function therefore only wakes and fails calls; it frees nothing.  The owner
+//                 frees the communicators after the rank threads have joined, so no call can touch a freed one.
+//   FirstFailure  which rank gave up first, and why: the others' exceptions are consequences (PeerFailed, or a call that the
+//                 abort made fail), whatever their rank index.
 #pragma once
 
 #include <atomic>
 #include <condition_variable>
 #include <mutex>
-#include <shared_mutex>
+#include <exception>
 #include <stdexcept>
 #include <vector>
 
@@ -49,26 +53,45 @@ struct HostBarrier {
 template <typename Comm> class CommGuard {
 public:
     explicit CommGuard(int n) : comm((size_t)n, Comm()) {}
-    std::vector<Comm> comm;                     // filled by the owner before the rank threads start
-    // f(communicator of rank r) under the shared lock; PeerFailed once the communicators are gone
+    std::vector<Comm> comm;                     // filled by the owner before the rank threads start, freed by it after they joined
+    // f(communicator of rank r); PeerFailed once the communicators have been aborted
     template <typename F> void use(int r, F f)
     {
-        std::shared_lock<std::shared_mutex> lk(mMu);
         if (mAborted.load()) throw PeerFailed();
         f(comm[(size_t)r]);
     }
-    // abort_one(communicator) for every communicator, once, after the calls in flight have returned
+    // abort_one(communicator) for every communicator, once; it runs beside the calls in flight and must free nothing
     template <typename A> void abort_all(A abort_one)
     {
-        std::unique_lock<std::shared_mutex> lk(mMu);
         if (mAborted.exchange(true)) return;
         for (auto &c : comm) abort_one(c);
     }
     bool aborted() const { return mAborted.load(); }
 
 private:
-    std::shared_mutex mMu;
     std::atomic<bool> mAborted{false};
+};
+
+class FirstFailure {
+public:
+    explicit FirstFailure(int n) : mEx((size_t)n) {}
+    // rank r's thread gives up with exception e; call it before anything that makes the peers fail (barrier abort, communicator abort)
+    void note(int r, std::exception_ptr e)
+    {
+        mEx[(size_t)r] = e;
+        int none = -1;
+        mFirst.compare_exchange_strong(none, r);
+    }
+    bool any() const { return mFirst.load() >= 0; }
+    int rank() const { return mFirst.load(); }
+    void rethrow() const                        // after the rank threads have joined
+    {
+        if (any()) std::rethrow_exception(mEx[(size_t)rank()]);
+    }
+
+private:
+    std::vector<std::exception_ptr> mEx;
+    std::atomic<int> mFirst{-1};
 };
 
 }  // namespace OIPGPU

@@ -328,9 +328,12 @@ def test_fused_task_equals_the_five_command_flow(ctx, tmp_path):
 
 def test_multigpu_host_on_one_gpu_equals_the_plain_cli(tmp_path):
     """`oip --gpus N` / `oip prestitch --gpus N` (csrc/oip_multigpu.hpp: one context, host thread and RCCL communicator per
-    GPU, block-offset file reads, grouped ncclSend/ncclRecv, ncclAllGather).  This box has one GPU, so N = 1 is what can
-    run here: the whole RCCL host path with a single rank must reproduce the plain CLI's product files byte for byte.
-    (The N > 1 plan is checked against dist.py's in tests/test_dist_cpu.py, dist.py itself on gloo.)"""
+    GPU, block-offset file reads, grouped ncclSend/ncclRecv, ncclAllGather) through real RCCL.  RCCL refuses two ranks on one
+    device, so N = 1 is what can run through it on a one-GPU machine: the whole RCCL host path with a single rank must
+    reproduce the plain CLI's product files byte for byte.  With one rank nothing is sent: the exchange machinery, the
+    rank-order writes and the failure protocol run with 2, 3 and 4 ranks over the loopback communicator in
+    tests/test_gpu_multigpu_loopback.py.  (The N > 1 plan is checked against dist.py's in tests/test_dist_cpu.py, dist.py
+    itself on gloo.)"""
     import shutil
     W, L, OV = 1024, 33024, 64
     base = str(tmp_path)

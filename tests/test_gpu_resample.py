@@ -461,6 +461,31 @@ def test_remap_shift_row_shards_equal_whole(ctx, oracle_mod, nshards):
                                     out_row0=o0, out_rows=o1 - o0)
 
 
+@pytest.mark.parametrize("nshards", [2, 3, 8])
+def test_remap_shift_row_shards_equal_whole_f16acc(ctx, nshards):
+    """the fp16-accumulate mode in scan-line blocks, as `oip prestitch --gpus N --fp16-accumulate` runs it: the shards put
+    together equal the unsharded fp16 call bit for bit (that call's distance from the oracle has its own test)"""
+    import torch
+    import opticalimageprocessor_amd as oip
+    W, L, dx, dy, sr, guard = 96, 1500, 2.6, 3.3, 300, 327
+    src = _scene(_rng(99), L, W)
+    whole = torch.zeros(L, W, dtype=torch.uint16, device="cuda")
+    ctx.remap_shift_bicubic_u16(_cuda(src), whole, W, L, dx, dy, sr, guard, f16acc=True)
+    ctx.sync()
+    want = _u16(whole)
+    assert want.any()
+    got = np.zeros_like(want)
+    for k in range(nshards):
+        o0, o1 = L * k // nshards, L * (k + 1) // nshards
+        s0, s1 = oip.remap_shift_src_range(o0, o1 - o0, L, dy, sr)
+        part = torch.zeros(o1 - o0, W, dtype=torch.uint16, device="cuda")
+        ctx.remap_shift_bicubic_u16(_cuda(src[s0:s1]), part, W, L, dx, dy, sr, guard, src_row0=s0, src_rows=s1 - s0,
+                                    out_row0=o0, out_rows=o1 - o0, f16acc=True)
+        ctx.sync()
+        got[o0:o1] = _u16(part)
+    assert np.array_equal(got, want)
+
+
 def test_remap_integer_shift_is_copy(ctx):
     """known answer: integer shift == shifted copy with zero border (per section)"""
     import torch
@@ -544,11 +569,26 @@ def test_align_argument_errors(ctx):
         ctx.align_mss_bicubic_u16x4(planes, 64 * 2000, dst, 64, 2000, z2, z3, 20000, 600, 520)
 
 
-@pytest.mark.parametrize("nshards", [2, 5])
-def test_align_row_shards_equal_whole(ctx, oracle_mod, nshards):
+def _kernels(ctx, call):
+    """run `call` with the context's profiler on -> the names its launches were profiled under"""
+    ctx.sync()
+    ctx.profile_enable(True)
+    try:
+        ctx.profile_reset()
+        call()
+        ctx.sync()
+        return set(ctx.profile())
+    finally:
+        ctx.profile_reset()
+        ctx.profile_enable(False)
+
+
+def _align_row_shards(ctx, oracle_mod, nshards, Wb, head=0, tail=0):
+    """every shard of output rows computed from its window of source lines [s0, s1) only; the window sits `head` lines into
+    planes of head + (s1 - s0) + tail lines whose other lines hold 0xFFFF.  -> (result, oracle, kernels that ran)"""
     import torch
     import opticalimageprocessor_amd as oip
-    Wb, Lm, lps, ovl, minl = 75, 1200, 400, 52, 150
+    Lm, lps, ovl, minl = 1200, 400, 52, 150
     rng = _rng(21)
     bands = [_scene(rng, Lm, Wb) for _ in range(4)]
     cx, cy = _coef(rng, Wb)
@@ -556,15 +596,37 @@ def test_align_row_shards_equal_whole(ctx, oracle_mod, nshards):
     R = want.shape[0]
     got = np.zeros_like(want)
     stack = np.stack(bands, 0)
+    ran = set()
     for k in range(nshards):
         o0, o1 = R * k // nshards, R * (k + 1) // nshards
         s0, s1 = oip.align_mss_src_range(o0, o1 - o0, Lm, cy, Wb, lps, 0, ovl, False, minl)
-        sub = np.ascontiguousarray(stack[:, s0:s1])
+        cap = head + (s1 - s0) + tail
+        sub = np.full((4, cap, Wb), 0xFFFF, np.uint16)
+        sub[:, head:head + s1 - s0] = stack[:, s0:s1]
+        planes = _cuda(sub).view(-1)[head * Wb:]
         part = torch.zeros(o1 - o0, Wb, 4, dtype=torch.uint16, device="cuda")
-        ctx.align_mss_bicubic_u16x4(_cuda(sub), Wb * (s1 - s0), part, Wb, Lm, cx, cy, lps, 0, ovl, False, minl,
-                                    src_row0=s0, src_rows=s1 - s0, out_row0=o0, out_rows=o1 - o0)
-        ctx.sync()
+        ran |= _kernels(ctx, lambda: ctx.align_mss_bicubic_u16x4(planes, Wb * cap, part, Wb, Lm, cx, cy, lps, 0, ovl, False, minl,
+                                                                 src_row0=s0, src_rows=s1 - s0, out_row0=o0, out_rows=o1 - o0))
         got[o0:o1] = _u16(part)
+    return got, want, ran
+
+
+@pytest.mark.parametrize("nshards", [2, 5])
+def test_align_row_shards_equal_whole(ctx, oracle_mod, nshards):
+    got, want, ran = _align_row_shards(ctx, oracle_mod, nshards, 75)
+    assert "align_fix_kernel" not in ran, ran          # an odd width: the general kernel
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("nshards,head,tail", [(2, 0, 0), (5, 0, 0), (5, 3, 7)])
+def test_align_row_shards_equal_whole_even_width(ctx, oracle_mod, nshards, head, tail):
+    """The same at Wb = 96, the form the N-GPU host calls (RunDefaultActionMultiGpu): an even width takes align_mss8_kernel with
+    align_fix_kernel behind it (the profiler says so) on a row window with src_row0 != 0, where the fast kernel's hand-off
+    conditions `l0 >= 0 && l0 + 3 < src_rows` and its prefetch guard `nline < src_rows` decide.  (5, 3, 7): the window sits
+    inside planes with plane_stride > src_rows * Wb, as in the host's m_cap layout; the lines around it hold 0xFFFF, so a tap
+    taken outside the window shows.  Exact equality with the oracle."""
+    got, want, ran = _align_row_shards(ctx, oracle_mod, nshards, 96, head, tail)
+    assert "align_fix_kernel" in ran, ran
     assert np.array_equal(got, want)
 
 
