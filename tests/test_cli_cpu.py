@@ -314,3 +314,20 @@ def test_loopback_communicator_protocol_under_sanitizers(tmp_path):
         subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-pthread", "-I" + inc] + flags + [src, "-o", str(exe)], check=True)
         r = subprocess.run(launch + [str(exe), "200"], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0 and "6 cases, 200 rounds per plan case" in r.stdout and ", 0 bad" in r.stdout, r.stdout + r.stderr
+
+
+def test_node_plan_invariants_under_sanitizers(tmp_path):
+    """csrc/oip_nodeplan.hpp, the plans of the N-GPU host, on the CPU under ASan + UBSan (tests/cpp/nodeplan_test.cpp; no HIP, the two
+    *_src_range calls are stand-ins): for the strips of tests/test_gpu_multigpu_loopback.py (8 x 1 and 9 x 2 inter-band units, five CCD
+    sections) at N = 2, 3, 4 all units of a group have one owner; the local groups and exchange_groups() together cover every unit
+    exactly once in ascending order, so the host's exchange-and-correlate driver computes every unit once; a group is exchanged
+    exactly when one of its units has a piece that changes rank; the mixed pair (8, 9) of 9 x 2 at N = 2 is one exchange group of
+    rank 0; halo transfers never name src == dst, lie inside the source rank's block and leave no rank lacking a line."""
+    src = os.path.join(ROOT, "tests", "cpp", "nodeplan_test.cpp")
+    inc = [os.path.join(ROOT, "opticalimageprocessor_amd", "csrc"), os.path.join(ROOT, "include")]
+    exe = tmp_path / "nodeplan"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] + ["-I" + i for i in inc] +
+                   [src, "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and " checks, 0 bad" in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]
+    assert int(r.stdout.split()[-4]) > 1000, r.stdout[-200:]                 # the checks ran

@@ -1,7 +1,8 @@
 """GPU: the N-GPU host (csrc/oip_multigpu.hpp: `oip --gpus N`, `oip prestitch --gpus N`) with 2, 3 and 4 ranks on ONE GPU, over the
-loopback communicator (OIP_COMM=loopback, csrc/oip_loopcomm.hpp): post_pieces / wait_group / finish_pieces, exchange_lines,
-allgather_table, the rank-order product writes and the failure protocol all execute with peers.  Every product file must equal
-the plain CLI's byte for byte.  The loopback proves ordering and addressing -- not RCCL's behaviour or any link rate.
+loopback communicator (OIP_COMM=loopback, csrc/oip_loopcomm.hpp): exchange_and_correlate (post_pieces, the wait per group,
+finish_pieces), exchange_lines, allgather_table, the rank-order product writes and the failure protocol all execute with peers.
+Every product file must equal the plain CLI's byte for byte.  The loopback proves ordering and addressing -- not RCCL's
+behaviour or any link rate.
 
 No case is vacuous: each asserts from `oip plan` with the same numbers that window pieces move between ranks and that halo lines
 do, that the run logged "with window exchange", and that the bytes and calls the loopback counted per rank for the WINDOW
@@ -30,6 +31,12 @@ INPUTS = ("S_PAN-1.RAW", "S_PAN-2.RAW", "T_PAN.RAW", "T_MSS.RAW", "PAN-1.csv", "
 DEFAULT_SETS = {"8x1": ["--slices", "8", "--ibc-sections", "1"], "9x2": ["--slices", "9", "--ibc-sections", "2"]}
 DEFAULT_PRODUCTS = ("T_MSS.ALIGNED.TIFF",)
 PRESTITCH_PRODUCTS = ("S_PAN-1.RRC.RAW", "S_PAN-2.RRC.RAW", "S_PAN-2.RRC.PRESTT.RAW")
+# the entries of a `  GPU r:` stage row; the RECEIVED_STAGES only on a rank that receives a group of units
+RECEIVED_STAGES = ("exchange_wait", "correlate_received")
+DEFAULT_STAGES = ["read", "rrc", "exchange_post", "correlate_resident", "exchange_wait", "correlate_received", "exchange_drain", "allgather",
+                  "fit+halo", "align+download"]
+PRESTITCH_STAGES = ["read", "rrc", "correlate_resident", "exchange_wait", "correlate_received", "exchange_drain", "allgather", "rrc_x2", "halo",
+                    "remap", "write"]
 
 
 def _csv(path, kb):
@@ -125,7 +132,7 @@ def _loopback_lines(out, n):
     return [[int(v) for v in t[1:]] for t in total], [[int(v) for v in t[1:]] for t in window]
 
 
-def _check_exchange(out, n, pieces, halo, planes_of_kind1, gather_bytes):
+def _check_exchange(out, n, pieces, halo, planes_of_kind1, gather_bytes, stages):
     """the run was not vacuous and moved what the plan says"""
     moved = [p for p in pieces if p[0] != p[1]]
     assert moved and halo, (moved, halo)
@@ -140,8 +147,15 @@ def _check_exchange(out, n, pieces, halo, planes_of_kind1, gather_bytes):
     # beyond the window share only halo lines move: somebody sent some, and what was sent was received
     assert sum(t[0] for t in total) > sum(w[0] for w in want)
     assert sum(t[0] for t in total) == sum(t[2] for t in total) and sum(t[1] for t in total) == sum(t[3] for t in total)
-    # the stage table has one row per GPU
-    assert re.findall(r"^  GPU (\d+): ", out, re.M) == [str(r) for r in range(n)], out
+    # the stage table has one row per GPU, its entries in the work-flow's order; a rank waits for windows and correlates received
+    # units exactly when the plan moves a piece to it
+    rows = re.findall(r"^  GPU (\d+): (.*)$", out, re.M)
+    assert [r for r, _ in rows] == [str(r) for r in range(n)], out
+    receivers = {p[1] for p in moved}
+    for r, (_, row) in enumerate(rows):
+        want_names = [s for s in stages if s not in RECEIVED_STAGES or r in receivers]
+        print("GPU %d: stages %s" % (r, row))
+        assert [e.rsplit(" ", 1)[0] for e in row.split(" | ")] == want_names, (r, row, want_names)
 
 
 def _same_products(strip, plain_key, d, products):
@@ -156,7 +170,7 @@ def _same_products(strip, plain_key, d, products):
 @pytest.mark.parametrize("n", [2, 3, 4])
 def test_default_action_on_n_ranks_equals_the_plain_cli(strip, n, key):
     """8 x 1: every unit's windows move at N = 2, 3, 4.  9 x 2 at N = 2: unit 9 moves while its partner unit 8 is resident -- the
-    mixed pair of the pairing rule in RunDefaultActionMultiGpu; at N = 3, 4 all 18 units move.  The 3000-line align sections
+    mixed pair of the pairing rule in Node::exchange_and_correlate; at N = 3, 4 all 18 units move.  The 3000-line align sections
     straddle the block boundaries (MSS line 4128 at N = 2), so the align fast path runs on row windows with src_row0 != 0."""
     d, r, _ = strip.run("node-%s-%d" % (key, n), _default_args(key) + ["--gpus", str(n)], {"OIP_COMM": "loopback"})
     assert r.returncode == 0, r.stdout + r.stderr
@@ -169,7 +183,7 @@ def test_default_action_on_n_ranks_equals_the_plain_cli(strip, n, key):
                   "--overlap-lines", 100, "--cy=%s,%s,%s" % (cy0.group(3), cy0.group(2), cy0.group(1))])
     if key == "9x2" and n == 2:
         assert plan["assign"][8] == plan["assign"][9] == 0 and {p[3] for p in plan["pieces"] if p[0] != p[1]} == {9}
-    _check_exchange(out, n, plan["pieces"], plan["align_transfers"], 4, int(slices) * int(sections) * 12 * 8)
+    _check_exchange(out, n, plan["pieces"], plan["align_transfers"], 4, int(slices) * int(sections) * 12 * 8, DEFAULT_STAGES)
     _same_products(strip, key, d, DEFAULT_PRODUCTS)
 
 
@@ -186,7 +200,7 @@ def test_prestitch_on_n_ranks_equals_the_plain_cli(strip, n, f16):
     dy = re.search(r" dx: \S+ dy: (\S+),", out).group(1)
     plan = _plan(["ccd", "--width", W, "--lines", L, "--gpus", n, "--sections", 5, "--section-lines", 1600, "--stitch-overlap", OV, "--dy=%s" % dy])
     assert sorted({p[3] for p in plan["pieces"] if p[0] != p[1]}) == {2: [2], 3: [1, 3], 4: [2]}[n]
-    _check_exchange(out, n, plan["pieces"], plan["remap_transfers"], 1, 5 * 3 * 8)
+    _check_exchange(out, n, plan["pieces"], plan["remap_transfers"], 1, 5 * 3 * 8, PRESTITCH_STAGES)
     _same_products(strip, f16, d, PRESTITCH_PRODUCTS)
 
 
