@@ -343,6 +343,16 @@ int oip_rows_window_geometry(oip_ctx *ctx, int *tile_cols, int *tiles, int *radi
  * OIP_E_UNSUPPORTED for n < 8. */
 int oip_upsample_operator(int n, float *out);
 
+/* The plan of the 2-D FFT engine for an M x N transform (rows x columns, each 2^a 3^b 5^c), as its planner makes it for
+ * every correlation of that size.  Host only: no context, no device.  buf receives one line per pass, in forward order
+ * (column passes, then row passes):
+ *   axis=<y|x> F=<factor> mode=<0|1> kind=<ct|generic> vshift=<log2 V> Vp=<LDS pitch> radix=<r,r,..> lds=<bytes>
+ * kind ct: a kernel specialised for (F, mode); generic: the run-time kernel, V = 1 << vshift transforms per tile.  lds:
+ * the dynamic LDS of a generic launch; the tile and twiddle arrays (an upper bound) of a specialised kernel.
+ * Where the planner or the launcher refuses the size, the code of the refusal is returned (OIP_E_INVALID, OIP_E_UNSUPPORTED,
+ * OIP_E_RUNTIME) and buf holds its text; OIP_E_INVALID with an empty buf: null buf or len too short for the lines. */
+int oip_fft_plan_describe(int M, int N, char *buf, int len);
+
 /* The validity filter and means of Stitcher::CalcSttParameters (stitcher.h:181-198), host: table[3*s +
  * {0,1,2}] = dx, dy, response of section s, in section order.  OIP_E_RUNTIME when no section is valid
  * ("No valid delta value found for stitching parameter calculating"). */

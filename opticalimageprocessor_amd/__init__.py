@@ -17,6 +17,7 @@ from .capi import (  # noqa: F401
     declared_symbols,
     denoise_thresholds,
     despike_column_table,
+    fft_plan_describe,
     filter_and_fit,
     library_path,
     load_column_list,

@@ -113,6 +113,7 @@ _SIGS = {
     "oip_polyfit_reference": ([_dp, _dp, _i, _i, _dp], _i),
     "oip_stt_mean": ([_dp, _i, _d, _d, _dp, _dp, _dp, C.POINTER(_i)], _i),
     "oip_upsample_operator": ([_i, C.POINTER(C.c_float)], _i),
+    "oip_fft_plan_describe": ([_i, _i, _cp, _i], _i),
     "oip_remap_shift_bicubic_u16": ([_vp, _vp, _l, _l, _vp, _l, _l, _i, _l, _d, _d, _i, _i], _i),
     "oip_remap_shift_bicubic_u16_f16acc": ([_vp, _vp, _l, _l, _vp, _l, _l, _i, _l, _d, _d, _i, _i], _i),
     "oip_remap_shift_bicubic_u16_window": ([_vp, _vp, _l, _l, _vp, _l, _i, _l, _l, _l, _i, _l, _d, _d, _i, _i, _i], _i),
@@ -799,6 +800,23 @@ def upsample_operator(n):
     if rc:
         raise ValueError("oip_upsample_operator: unsupported length %d" % n)
     return out[..., 0] + 1j * out[..., 1]
+
+
+def fft_plan_describe(M, N):
+    """the FFT plan of an M x N correlation, from the planner (include/oip_c.h): one dict per pass in forward order, with
+    axis ('y' | 'x'), F, mode, kind ('ct' | 'generic'), vshift, Vp, radix (a tuple) and lds; ValueError with the planner's
+    own text where it refuses the size"""
+    lib = load_library()
+    buf = C.create_string_buffer(4096)
+    rc = lib.oip_fft_plan_describe(int(M), int(N), buf, len(buf))
+    if rc:
+        raise ValueError(buf.value.decode() or "oip_fft_plan_describe: bad argument")
+    passes = []
+    for line in buf.value.decode().splitlines():
+        f = dict(kv.split("=", 1) for kv in line.split())
+        passes.append({k: v if k in ("axis", "kind") else tuple(int(r) for r in v.split(",") if r) if k == "radix" else int(v)
+                       for k, v in f.items()})
+    return passes
 
 
 def remap_shift_src_range(out_row0, out_rows, L, dy, section_rows=30000):

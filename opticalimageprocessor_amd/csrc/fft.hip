@@ -40,11 +40,9 @@
 #include <map>
 
 using namespace oipfft;
+using namespace oipfftplan;               // kFftBlock, kMaxTileElems and the planner (oip_fftplan.h)
 
 namespace {
-
-constexpr int kFftBlock = 256;
-constexpr int kMaxTileElems = 5120;       // generic kernel: F * (V+1) complex elements per LDS buffer
 
 // ---- tile addressing shared by the generic and the specialised kernels -------------------------
 struct Tile {
@@ -1305,7 +1303,7 @@ struct FastKernel {
     void (*fn[3])(float2 *, OipFftPass, OipFftIo, const float2 *, const float2 *);         // by IOK: plain, fused load, fused store
     void (*list[2])(OipColList, OipFftPass, const float2 *, const float2 *);               // column passes over a tile list: plain, peak
 };
-const FastKernel kFast[] = {
+constexpr FastKernel kFast[] = {
     // column passes of 16000 = 125 * 128 (and other 5^3 / 2^7 factors): 16 lanes = 128-byte
     // segments, 17 KiB of LDS per workgroup -> 8 workgroups per CU (measured faster than 32 lanes)
     {125, 4, 0, 256, {fft_pass_ct_kernel<125, 4, 0, 256, 0, 5, 5, 5>, fft_pass_ct_kernel<125, 4, 0, 256, 1, 5, 5, 5>, fft_pass_ct_kernel<125, 4, 0, 256, 2, 5, 5, 5>}, {col_list_ct_kernel<125, 4, 256, false, 5, 5, 5>, col_list_ct_kernel<125, 4, 256, true, 5, 5, 5>}},
@@ -1322,80 +1320,14 @@ const FastKernel kFast[] = {
 };
 constexpr int kNumFast = sizeof(kFast) / sizeof(kFast[0]);
 
-// ---- host-side planning --------------------------------------------------------------------
-bool smooth235(long n)
+// ---- host-side planning: oip_fftplan.h; entry i of its keys names the kernels of kFast[i] ------------
+static_assert(kNumFast == kNumFastKeys, "kFast and kFastKeys (oip_fftplan.h) list the same kernels");
+constexpr bool fast_keys_match(int i = 0)
 {
-    if (n < 1) return false;
-    for (int p : {2, 3, 5}) while (n % p == 0) n /= p;
-    return n == 1;
+    return i == kNumFast || (kFast[i].F == kFastKeys[i].F && kFast[i].vshift == kFastKeys[i].vshift && kFast[i].mode == kFastKeys[i].mode && fast_keys_match(i + 1));
 }
-
-std::vector<int> radix_list(int F)
-{
-    std::vector<int> r;
-    int twos = 0;
-    while (F % 2 == 0) { F /= 2; ++twos; }
-    while (F % 3 == 0) { F /= 3; r.push_back(3); }
-    for (; twos >= 3; twos -= 3) r.push_back(8);
-    if (twos == 2) r.push_back(4);
-    if (twos == 1) r.push_back(2);
-    while (F % 5 == 0) { F /= 5; r.push_back(5); }
-    return r;
-}
-
-// split L into pass factors: all but the last limited by max_a (mode A tiles), the last by
-// max_last; fewest passes, then the most balanced split; 125*128 preferred for 16000
-bool split_axis(int L, int max_a, int max_last, std::vector<int> *out)
-{
-    if (L <= max_last) { *out = {L}; return true; }
-    for (int passes = 2; passes <= 4; ++passes) {
-        std::vector<int> best;
-        double best_score = -1;
-        std::vector<int> cur;
-        std::function<void(int, int)> rec = [&](int rem, int left) {
-            if (left == 1) {
-                if (rem <= max_last && rem >= 2) {
-                    cur.push_back(rem);
-                    int mn = 1 << 30;
-                    for (int f : cur) mn = f < mn ? f : mn;
-                    if (mn > best_score) { best_score = mn; best = cur; }
-                    cur.pop_back();
-                }
-                return;
-            }
-            for (int f = 2; f <= max_a && f <= rem; ++f) {
-                if (rem % f) continue;
-                cur.push_back(f);
-                rec(rem / f, left - 1);
-                cur.pop_back();
-            }
-        };
-        rec(L, passes);
-        if (!best.empty()) { *out = best; return true; }
-    }
-    return false;
-}
-
-int pick_vshift(int F, int want)
-{
-    int vs = 0;
-    while ((1 << (vs + 1)) <= want && (long)F * ((1 << (vs + 1)) + 1) <= kMaxTileElems) ++vs;
-    return vs;
-}
-
-void choose_kernel(OipFftPass *p, int want_v)
-{
-    p->fast = -1;
-    for (int i = 0; i < kNumFast; ++i)
-        if (kFast[i].F == p->F && kFast[i].mode == p->mode) {
-            p->fast = i;
-            p->vshift = kFast[i].vshift;
-            p->Vp = p->vshift > 1 ? (1 << p->vshift) + 1 : (1 << p->vshift);
-            return;
-        }
-    p->vshift = pick_vshift(p->F, want_v);
-    p->Vp = p->vshift ? (1 << p->vshift) + 1 : 1;
-}
+static_assert(fast_keys_match(), "kFast and kFastKeys (oip_fftplan.h) differ in (F, log2 V, mode)");
+static_assert(kGenericStaticLds == kFftBlock * 12, "fft_pass_kernel's sval and skey");
 
 }  // namespace
 
@@ -1462,92 +1394,19 @@ void oip_fft_destroy(oip_ctx *ctx)
     ctx->fft = nullptr;
 }
 
-static void fill_radix(OipFftPass *p)
-{
-    std::vector<int> r = radix_list(p->F);
-    p->nradix = (int)r.size();
-    for (int i = 0; i < p->nradix; ++i) p->radix[i] = r[i];
-}
-
 int oip_fft2d_plan(oip_ctx *ctx, int M, int N, const OipFft2dPlan **out)
 {
     if (!ctx->fft) ctx->fft = new oip_fft_state();
     auto key = std::make_pair(M, N);
     auto it = ctx->fft->plans.find(key);
     if (it != ctx->fft->plans.end()) { *out = &it->second; return OIP_OK; }
-    if (!smooth235(M) || !smooth235(N)) return oip_fail(ctx, OIP_E_INVALID, "fft2d: %d x %d is not 2^a3^b5^c", M, N);
-    if (M < 2) return oip_fail(ctx, OIP_E_UNSUPPORTED, "fft2d: fewer than 2 rows");
     OipFft2dPlan pl;
-    pl.M = M; pl.N = N;
-    // row pitch padded to whole 128-byte lines (16 complex): every pass stores full lines
-    const int P = (N + 15) / 16 * 16;
-    pl.P = P;
-    if (!split_axis(N, 256, 4096, &pl.xf)) return oip_fail(ctx, OIP_E_UNSUPPORTED, "fft2d: cannot factor row length %d", N);
-    // 16000 = 128 * 125 with the 128-point pass first: its points are 125 rows apart, an odd multiple of
-    // 512 B for the padded pitches, so a tile spreads over the HBM channels (125 * 128 would put all
-    // points of a tile 47 * 2^16 B apart -- same channel -- and ran at half the bandwidth)
-    if (M == 16000) pl.yf = std::vector<int>{128, 125};
-    else if (M == 4000) pl.yf = std::vector<int>{32, 125};          // the band windows of 16000 correlation lines
-    else if (!split_axis(M, 256, 256, &pl.yf)) return oip_fail(ctx, OIP_E_UNSUPPORTED, "fft2d: cannot factor column length %d", M);
-    // column (y) passes first: always mode A with lanes = x
     {
-        int T = M;
-        for (size_t i = 0; i < pl.yf.size(); ++i) {
-            OipFftPass p;
-            memset(&p, 0, sizeof p);
-            p.F = pl.yf[i];
-            p.M = M; p.N = N; p.P = P;
-            p.axis = 1;
-            fill_radix(&p);
-            const int S = T / p.F;
-            p.mode = 0;
-            choose_kernel(&p, 32);
-            p.nstride = (long)S * P;
-            p.lanes = N;
-            p.lane_tiles = (N + (1 << p.vshift) - 1) >> p.vshift;
-            p.O1 = S;     p.o1_stride = P;              // j: row offset inside the block
-            p.O2 = M / T; p.o2_stride = (long)T * P;    // blocks
-            p.tw_mode = S > 1 ? 2 : 0; p.T = T; p.S = S;
-            pl.passes.push_back(p);
-            T = S;
-        }
-    }
-    pl.n_y = (int)pl.passes.size();
-    // row (x) passes: leading factors in mode A (lanes = j), last factor as whole contiguous
-    // sub-rows in mode B
-    {
-        int T = N;
-        for (size_t i = 0; i < pl.xf.size(); ++i) {
-            OipFftPass p;
-            memset(&p, 0, sizeof p);
-            p.F = pl.xf[i];
-            p.M = M; p.N = N; p.P = P;
-            p.axis = 0;
-            fill_radix(&p);
-            const int S = T / p.F;
-            p.T = T; p.S = S;
-            if (S == 1) {
-                p.mode = 1;
-                choose_kernel(&p, 32);
-                p.lanes = (long)M * (N / p.F);          // contiguous F-point vectors
-                p.tw_mode = 0;
-            } else {
-                p.mode = 0;
-                choose_kernel(&p, 32);
-                p.nstride = S;
-                p.lanes = S;
-                p.lane_tiles = (S + (1 << p.vshift) - 1) >> p.vshift;
-                p.O1 = N / T; p.o1_stride = T;          // blocks of the current sub-problem
-                p.O2 = M;     p.o2_stride = P;          // rows
-                p.tw_mode = 1;
-            }
-            pl.passes.push_back(p);
-            T = S;
-        }
+        char why[128];
+        const int rc = plan(M, N, &pl, why, sizeof why);
+        if (rc) return oip_fail(ctx, rc, "%s", why);
     }
     for (auto &p : pl.passes) {
-        if (p.fast < 0 && (long)p.F * p.Vp > kMaxTileElems)
-            return oip_fail(ctx, OIP_E_UNSUPPORTED, "fft2d: factor %d too long for one LDS tile", p.F);
         const float2 *t;
         int rc = get_table(ctx, p.F, &t);
         if (rc) return rc;
@@ -1571,13 +1430,6 @@ int oip_fft2d_plan(oip_ctx *ctx, int M, int N, const OipFft2dPlan **out)
     return OIP_OK;
 }
 
-static long pass_blocks(const OipFftPass &p)
-{
-    if (p.mode == 0) return (long)p.lane_tiles * p.O1 * p.O2;
-    return (p.lanes + (1 << p.vshift) - 1) >> p.vshift;
-}
-
-
 static int launch_pass(oip_ctx *ctx, float2 *data, OipFftPass p, int inverse, const OipFftIo &io)
 {
     p.inverse = inverse;
@@ -1589,21 +1441,21 @@ static int launch_pass(oip_ctx *ctx, float2 *data, OipFftPass p, int inverse, co
     // The LDS-staged kernels keep the gather from table T: with rows the 125-point passes were 1.4 % SLOWER (0.1328 -> 0.1347 ms,
     // A/B twice on one box).  A tw_mode 2 pass is a column pass with T = F S and O1 = S, and T <= M <= 65535 for every caller.
     const float2 *twR = nullptr;
+    {
+        char why[128];
+        if ((rc = launch_refusal(p, why, sizeof why))) return oip_fail(ctx, rc, "%s", why);       // twiddle rows, grid size, rows and blocks
+    }
     if (p.tw_mode == 2) {
-        if (p.T % p.F != 0 || p.O1 != p.T / p.F || (long)p.T * 8 > (16L << 20))
-            return oip_fail(ctx, OIP_E_RUNTIME, "fft pass: no inter-pass twiddle rows for T = %d, F = %d", p.T, p.F);
         rc = get_pass_table(ctx, p.T, p.F, &twR);
         if (rc) return rc;
     }
     const long blocks = pass_blocks(p);
-    if (blocks <= 0 || blocks > 0x7fffffffL) return oip_fail(ctx, OIP_E_UNSUPPORTED, "fft pass grid too large");
     char pname[64];
     snprintf(pname, sizeof pname, p.fast >= 0 ? "fft_pass_ct_kernel_F%d%s%s" : "fft_pass_kernel_F%d%s%s", p.F,
              io.load_kind == 1 ? "_pack" : (io.store_kind == 1 ? "_peak" : ""), ctx->prof_tag ? ctx->prof_tag : "");
     OipProfScope prof(ctx, pname);
     dim3 grid3((unsigned)blocks);
     p.grid3 = 0;
-    if (p.mode == 0 && (p.O1 > 65535 || p.O2 > 65535)) return oip_fail(ctx, OIP_E_UNSUPPORTED, "fft pass: more than 65535 rows or blocks");
     if (p.mode == 0) {
         p.grid3 = 1;
         p.xcd_chunk = (p.lane_tiles + 7) / 8;
@@ -1641,7 +1493,7 @@ static int launch_pass(oip_ctx *ctx, float2 *data, OipFftPass p, int inverse, co
         p.ntiles = blocks;
         hipLaunchKernelGGL(kFast[p.fast].fn[io.load_kind ? 1 : (io.store_kind ? 2 : 0)], p.grid3 ? grid3 : dim3((unsigned)blocks), dim3(kFast[p.fast].threads), 0, ctx->stream, data, p, io, twF, twT);
     } else {
-        size_t lds = sizeof(float2) * ((size_t)2 * p.F * p.Vp + p.F);
+        const size_t lds = generic_lds_bytes(p);
         hipLaunchKernelGGL(fft_pass_kernel, p.grid3 ? grid3 : dim3((unsigned)blocks), dim3(kFftBlock), lds, ctx->stream, data, p, io, twF, twT);
     }
     OIP_HIP(ctx, hipGetLastError());
@@ -1707,7 +1559,7 @@ int oip_fft_col_list_pass(oip_ctx *ctx, const OipFft2dPlan *pl, int pass, const 
     } else if (p.fast >= 0 && kFast[p.fast].list[peak ? 1 : 0]) {
         hipLaunchKernelGGL(kFast[p.fast].list[peak ? 1 : 0], dim3((unsigned)grid), dim3(kFast[p.fast].threads), 0, ctx->stream, list, p, twF, twT);
     } else {
-        const size_t lds = sizeof(float2) * ((size_t)2 * p.F * p.Vp + p.F);
+        const size_t lds = generic_lds_bytes(p);
         hipLaunchKernelGGL(col_list_pass_kernel, dim3((unsigned)grid), dim3(kFftBlock), lds, ctx->stream, list, p, peak ? 1 : 0, twF, twT);
     }
     OIP_HIP(ctx, hipGetLastError());

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "oip_c.h"
+#include "oip_fftplan.h"
 #include "oip_rescaleplan.h"
 #include "oip_tiff.hpp"
 #include "oip_warpfield.hpp"
@@ -517,6 +518,15 @@ extern "C" int oip_stt_mean(const double *table, int sections, double threshold,
 // out[(t * N + k) * 2 + {0,1}] = re, im of H (t = 0) and G_0..G_3 (t = 1..4), as float.  Built in double from the f32
 // taps of cv::hal::resize's coefficient set-up (fx = (float)((d + 0.5) * scale - 0.5), interpolateCubic(fx - floor)),
 // the same the image-domain kernels apply.  OIP_E_UNSUPPORTED when the taps are not 4-periodic or n < 8.
+// ---- the plan of an M x N transform, stated by the planner itself (include/oip_c.h; arithmetic: oip_fftplan.h)
+static_assert(oipfftplan::kPlanOk == OIP_OK && oipfftplan::kPlanInvalid == OIP_E_INVALID && oipfftplan::kPlanRuntime == OIP_E_RUNTIME &&
+              oipfftplan::kPlanUnsupported == OIP_E_UNSUPPORTED, "the planner's codes are the C interface's");
+extern "C" int oip_fft_plan_describe(int M, int N, char *buf, int len)
+{
+    if (!buf || len < 1) return OIP_E_INVALID;
+    return oipfftplan::describe(M, N, buf, (size_t)len);
+}
+
 static inline void host_interpolate_cubic(float x, float *c)
 {
     const float A = -0.75f;

@@ -7,6 +7,8 @@
 #include <functional>
 #include <vector>
 
+#include "oip_fftplan.h"
+
 struct oip_ctx;
 
 // Arg-max of a correlation surface without a reduction pass: every workgroup of the last inverse pass
@@ -52,40 +54,8 @@ struct OipFftIo {
     unsigned long long *slots;  // store_kind 1: [2][kPeakSlots] arg-max slots (real part, imaginary part)
 };
 
-struct OipFftPass {
-    int F;              // sub-transform length of this pass
-    int nradix;
-    int radix[16];      // Stockham radices, product == F (generic kernel)
-    int vshift;         // log2(V): V adjacent transforms per workgroup tile
-    int Vp;             // LDS row pitch (V+1, or 1 when V == 1)
-    int mode;           // 0: points strided, lanes contiguous; 1: points contiguous
-    int axis;           // 0: x (rows), 1: y (columns)
-    long nstride;       // mode 0: elements between consecutive points
-    long lanes;         // mode 0: lanes in the contiguous direction; mode 1: number of vectors
-    int lane_tiles;
-    int O1;             // mode 0 outer dimension 1 (count, element stride)
-    long o1_stride;
-    int O2;
-    long o2_stride;
-    int tw_mode;        // 0 none; 1: j = lane index; 2: j = o1 index  (twiddle w_T^(j*k))
-    int T;
-    int S;              // stride of the sub-transform in axis elements (T / F)
-    int N;              // row length of the array (to turn offsets into coordinates)
-    int M;
-    int P;              // row pitch in elements (N rounded up to whole 128-byte lines)
-    int inverse;
-    long ntiles;        // tiles of this launch (persistent specialised kernels walk them)
-    int fast;           // index of a compile-time specialised kernel, -1: generic
-    int grid3;          // mode 0 launched as a (lane tile, o1, o2) grid: the tile needs no divisions to decode
-    int xcd_chunk;      // grid3: lane tiles per XCD (grid x = 8 * xcd_chunk >= lane tiles); see decode_tile
-};
-
-struct OipFft2dPlan {
-    int M, N;
-    int P;                            // row pitch of the complex array, elements
-    std::vector<int> xf, yf;          // pass factors per axis, in forward order
-    std::vector<OipFftPass> passes;   // forward order: y passes then x passes
-    int n_y;
+// OipFftPass and the host part of a plan (M, N, P, xf, yf, passes, n_y) come from the planner's header
+struct OipFft2dPlan : OipFftHostPlan {
     const int *d_ypos;                // device: row position of frequency line ky in the scrambled spectrum, ky in [0, M)
 };
 

@@ -66,7 +66,7 @@ static void check_axis(const std::vector<int> &f)
 
 static void check_axes()
 {
-    // what split_axis (csrc/fft.hip) emits for the column lengths of tests/test_gpu_fft_routes.py, the two fixed plans
+    // what split_axis (csrc/oip_fftplan.h) emits for the column lengths of tests/test_gpu_fft_routes.py, the two fixed plans
     // (16000 = 128 * 125, 4000 = 32 * 125), the product's own shapes, the long rows, and the one-factor case
     const std::vector<std::vector<int>> lists = {
         {100, 100}, {160, 160}, {64, 64}, {125, 160}, {100, 128}, {128, 128}, {20, 32}, {100, 125}, {243},

@@ -1,6 +1,6 @@
 """GPU parity of the correlation path on the FFT plan routes and peak positions the product's own shapes never reach.
 
-The planner (csrc/fft.hip: oip_fft2d_plan, split_axis, choose_kernel, launch_pass) hands out a specialised column
+The planner (csrc/oip_fftplan.h: plan, split_axis, choose_kernel; csrc/fft.hip: launch_pass) hands out a specialised column
 kernel per pass factor (kFast: F = 125, 128, 100, 160, 64, 32; plain, fused load `_pack`, fused store `_peak`), multi-pass
 row transforms for rows longer than 4096 points (mode-0 row passes + cross_power_kernel with a two-digit x scramble), and
 peak_window_kernel clamps its 5x5 window at the border of the surface.  test_gpu_correlation.py reaches none of these.

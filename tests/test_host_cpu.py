@@ -255,3 +255,36 @@ def test_fft_index_helpers_under_sanitizers(tmp_path):
                     "-D__HIP_PLATFORM_AMD__", "-I" + rocm, "-I" + inc, src, "-o", str(exe)], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0 and " checks, 0 bad" in r.stdout and "FAILED" not in r.stdout, r.stdout + r.stderr
+
+
+def test_fft_planner_under_sanitizers(tmp_path):
+    """csrc/oip_fftplan.h on the CPU (tests/cpp/fftplan_test.cpp; ASan + UBSan): for every 2^a 3^b 5^c row length up to 2^20 and
+    column length from 2 to 2^18 a plan exists; its factors multiply to the length and keep their limits (256 leading, 256 last
+    column, 4096 last row); at most 16 radices that multiply to F; a generic tile within kMaxTileElems and, with the static
+    arrays, within 160 KiB of LDS; O1, O2 <= 65535 and inter-pass twiddle rows within 16 MiB (nothing the launcher refuses);
+    oip_pos_to_freq / oip_freq_to_pos inverse to each other with the plan's digits.  And what the planner gives today: at most
+    7 radices up to 4096 points, 46875 the first three-pass column length, no four-pass length, the tile class per factor,
+    the lines and refusals of oip_fft_plan_describe."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = os.path.join(root, "tests", "cpp", "fftplan_test.cpp")
+    inc = os.path.join(root, "opticalimageprocessor_amd", "csrc")
+    rocm = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")          # oip_fft.h takes float2 from the HIP headers
+    exe = tmp_path / "fftplan"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-D__HIP_PLATFORM_AMD__", "-I" + rocm, "-I" + inc, src, "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and " checks, 0 bad" in r.stdout and "FAILED" not in r.stdout, r.stdout + r.stderr
+
+
+def test_fft_plan_describe_is_the_planner(tmp_path):
+    """oip_fft_plan_describe through capi: the lines of the product's own shapes, a generic class, and a refusal's text"""
+    got = oip.fft_plan_describe(16000, 3000)
+    assert [(p["axis"], p["F"], p["mode"], p["kind"], p["vshift"], p["Vp"], p["radix"]) for p in got] == [
+        ("y", 128, 0, "ct", 4, 17, (8, 8, 2)), ("y", 125, 0, "ct", 4, 17, (5, 5, 5)), ("x", 3000, 1, "ct", 1, 2, (3, 8, 5, 5, 5))]
+    got = oip.fft_plan_describe(243, 3750)
+    assert [(p["axis"], p["F"], p["kind"], p["vshift"], p["Vp"], p["radix"], p["lds"]) for p in got] == [
+        ("y", 243, "generic", 4, 17, (3,) * 5, 8 * (2 * 243 * 17 + 243)), ("x", 3750, "generic", 0, 1, (3, 2, 5, 5, 5, 5), 8 * 3 * 3750)]
+    with pytest.raises(ValueError, match="14 x 16 is not 2\\^a3\\^b5\\^c"):
+        oip.fft_plan_describe(14, 16)
+    with pytest.raises(ValueError, match="fewer than 2 rows"):
+        oip.fft_plan_describe(1, 16)
