@@ -301,7 +301,8 @@ int oip_stt_correlate_windows(oip_ctx *ctx, const uint16_t *const *d_a, const si
  * image is computed, for slices of 3000 columns whose window is exactly 4 x the band window, as the transform of
  * the band window itself expanded by the up-sampling operator's own transform (an exact identity, see DESIGN.md
  * 4.3); results agree with "up-sample, then transform" to ~4e-6 px.  Environment: OIP_SPECTRAL_UP=0 keeps the
- * up-sampling in the image domain (1: horizontal axis only on the spectra). */
+ * up-sampling in the image domain (1: horizontal axis only on the spectra).  Every correlation entry reads its switches
+ * once, at its top; oip_corr_route_describe states the route they give a geometry. */
 int oip_interband_correlate(oip_ctx *ctx, const uint16_t *d_pan, long Lp, long prow0, long pn,
                             const uint16_t *d_planes, size_t plane_stride, long mrow0, long mn,
                             int W, int slices, int sections, int corr_lines, double *out);
@@ -352,6 +353,17 @@ int oip_upsample_operator(int n, float *out);
  * Where the planner or the launcher refuses the size, the code of the refusal is returned (OIP_E_INVALID, OIP_E_UNSUPPORTED,
  * OIP_E_RUNTIME) and buf holds its text; OIP_E_INVALID with an empty buf: null buf or len too short for the lines. */
 int oip_fft_plan_describe(int M, int N, char *buf, int len);
+
+/* The plan of an inter-band correlation call on units of rows x cols PAN lines (band windows rows / 4 x cols / 4, as
+ * oip_interband_correlate_units derives them) on a device of cu_count CUs, with the switches of the environment as a call
+ * would read them (OIP_SPECTRAL_UP, OIP_SPECTRAL_V, OIP_FUSED_ROWS, OIP_PEAK_PRUNE, OIP_ROWS_WINDOW; csrc/oip_corrroute.h:
+ * CorrKnobs).  Host only: no context, no device.  buf receives one JSON object: "route" ("image", "H", "HV", "V": DESIGN.md
+ * 4.3), the window, band and DFT sizes, "row_kernel" and "pack_kernel" (the profile names of the route's row stage and of
+ * what brings the bands into its arrays), the peak search's "groups", "tiles", "tile_cols" and "lists", "window" (the row
+ * stage's stored radius, -1: every column), and the workspace: "total" bytes, "regions" (name, offset, bytes of a part,
+ * count of parts, in address order) and the arrays "inside" a part of one.  Where the planner refuses the geometry its code
+ * is returned and buf holds {"refused": text, "code": code}; OIP_E_INVALID with an empty buf: bad argument or len too short. */
+int oip_corr_route_describe(int rows, int cols, int cu_count, char *buf, int len);
 
 /* The validity filter and means of Stitcher::CalcSttParameters (stitcher.h:181-198), host: table[3*s +
  * {0,1,2}] = dx, dy, response of section s, in section order.  OIP_E_RUNTIME when no section is valid

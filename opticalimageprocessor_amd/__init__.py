@@ -18,6 +18,7 @@ from .capi import (  # noqa: F401
     denoise_thresholds,
     despike_column_table,
     fft_plan_describe,
+    corr_route_describe,
     filter_and_fit,
     library_path,
     load_column_list,

@@ -114,6 +114,7 @@ _SIGS = {
     "oip_stt_mean": ([_dp, _i, _d, _d, _dp, _dp, _dp, C.POINTER(_i)], _i),
     "oip_upsample_operator": ([_i, C.POINTER(C.c_float)], _i),
     "oip_fft_plan_describe": ([_i, _i, _cp, _i], _i),
+    "oip_corr_route_describe": ([_i, _i, _i, _cp, _i], _i),
     "oip_remap_shift_bicubic_u16": ([_vp, _vp, _l, _l, _vp, _l, _l, _i, _l, _d, _d, _i, _i], _i),
     "oip_remap_shift_bicubic_u16_f16acc": ([_vp, _vp, _l, _l, _vp, _l, _l, _i, _l, _d, _d, _i, _i], _i),
     "oip_remap_shift_bicubic_u16_window": ([_vp, _vp, _l, _l, _vp, _l, _i, _l, _l, _l, _i, _l, _d, _d, _i, _i, _i], _i),
@@ -817,6 +818,22 @@ def fft_plan_describe(M, N):
         passes.append({k: v if k in ("axis", "kind") else tuple(int(r) for r in v.split(",") if r) if k == "radix" else int(v)
                        for k, v in f.items()})
     return passes
+
+
+def corr_route_describe(rows, cols, cu_count=256):
+    """the plan of an inter-band correlation call on rows x cols units, from its planner with the environment's switches
+    (include/oip_c.h): a dict with route ('image' | 'H' | 'HV' | 'V'), row_kernel, pack_kernel, window, regions, ...;
+    ValueError with the planner's own text where it refuses the geometry"""
+    import json
+    lib = load_library()
+    buf = C.create_string_buffer(8192)
+    rc = lib.oip_corr_route_describe(int(rows), int(cols), int(cu_count), buf, len(buf))
+    if not buf.value:
+        raise ValueError("oip_corr_route_describe: bad argument")
+    d = json.loads(buf.value.decode())
+    if rc:
+        raise ValueError(d["refused"])
+    return d
 
 
 def remap_shift_src_range(out_row0, out_rows, L, dy, section_rows=30000):

@@ -42,7 +42,7 @@ extern "C" int oip_create(int device, oip_ctx **out)
         return OIP_E_DEVICE;
     }
     float tab[32 * 4];
-    for (int i = 0; i < 32; ++i) oip_interpolate_cubic_host(i * (1.f / 32), tab + i * 4);
+    for (int i = 0; i < 32; ++i) oipcorr::interpolate_cubic(i * (1.f / 32), tab + i * 4);
     if (hipMalloc(&ctx->d_tab1d, sizeof tab) != hipSuccess ||
         hipMemcpy(ctx->d_tab1d, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess ||
         hipMalloc(&ctx->d_small, 65536) != hipSuccess ||

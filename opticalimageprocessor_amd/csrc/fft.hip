@@ -1522,18 +1522,7 @@ int oip_fft2d_exec(oip_ctx *ctx, const OipFft2dPlan *pl, float2 *data, int inver
     return OIP_OK;
 }
 
-// The list forms take a plan whose column passes all work on lane tiles of one width (the list names tiles of that
-// width) and whose work items fit an int.
-bool oip_fft_col_list_ok(const OipFft2dPlan *pl, int narr)
-{
-    if (pl->n_y < 1) return false;
-    for (int i = 0; i < pl->n_y; ++i) {
-        const OipFftPass &p = pl->passes[i];
-        if (p.mode != 0 || p.axis != 1 || p.vshift != pl->passes[0].vshift || p.tw_mode == 1) return false;
-        if ((long)narr * p.lane_tiles * p.O1 * p.O2 > 0x7fffffffL) return false;
-    }
-    return pl->passes[0].O2 == 1;       // the last inverse pass spans the whole axis
-}
+bool oip_fft_col_list_ok(const OipFft2dPlan *pl, int narr) { return oipfftplan::col_list_ok(*pl, narr); }
 
 // Inverse column pass `pass` (index in forward order; 0 is the last one of the inverse) of the arrays of `list` over
 // its tile lists; peak: only per-tile maxima are left, in list.slots.  `name` is the profiler's name of the launch.

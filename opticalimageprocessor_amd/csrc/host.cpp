@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "oip_c.h"
+#include "oip_corrroute.h"
 #include "oip_fftplan.h"
 #include "oip_rescaleplan.h"
 #include "oip_tiff.hpp"
@@ -527,14 +528,21 @@ extern "C" int oip_fft_plan_describe(int M, int N, char *buf, int len)
     return oipfftplan::describe(M, N, buf, (size_t)len);
 }
 
-static inline void host_interpolate_cubic(float x, float *c)
+// ---- the route and storage of an inter-band correlation call, stated by its planner (include/oip_c.h; arithmetic: oip_corrroute.h)
+extern "C" int oip_corr_route_describe(int rows, int cols, int cu_count, char *buf, int len)
 {
-    const float A = -0.75f;
-    c[0] = ((A * (x + 1) - 5 * A) * (x + 1) + 8 * A) * (x + 1) - 4 * A;
-    c[1] = ((A + 2) * x - (A + 3)) * x * x + 1;
-    c[2] = ((A + 2) * (1 - x) - (A + 3)) * (1 - x) * (1 - x) + 1;
-    c[3] = 1.f - c[0] - c[1] - c[2];
+    if (!buf || len < 1) return OIP_E_INVALID;
+    buf[0] = 0;
+    if (rows < OIP_MSS_BANDS || cols < OIP_MSS_BANDS || cu_count < 1) return OIP_E_INVALID;
+    oipcorr::CorrPlan plan;
+    char why[160] = "";
+    const int rc = oipcorr::plan_interband(rows, cols, rows / OIP_MSS_BANDS, cols / OIP_MSS_BANDS, cu_count, oipcorr::CorrKnobs::from_env(), &plan, why, sizeof why);
+    const std::string s = oipcorr::describe(plan, rc, why);
+    if (s.size() >= (size_t)len) return OIP_E_INVALID;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return rc;
 }
+
 extern "C" int oip_upsample_operator(int n, float *out)
 {
     if (n < 8 || !out) return OIP_E_UNSUPPORTED;
@@ -550,7 +558,7 @@ extern "C" int oip_upsample_operator(int n, float *out)
         const int sx = (int)floorf(fx);
         fx -= sx;
         float w[4];
-        host_interpolate_cubic(fx, w);
+        oipcorr::interpolate_cubic(fx, w);
         for (int j = 0; j < 4; ++j) {
             const int p = sx - 1 + j;
             const int e = ((d - 4 * p) % N + N) % N;

@@ -16,8 +16,7 @@ struct oip_ctx;
 // (order-preserving bits of the f32 value) << 32 | (0xFFFFFFFF - key), key = row-major index in the
 // fftShift-ed image (< 2^32), so the largest value wins and, among equal values, the smallest key -- the
 // first maximum in minMaxLoc's scan order.  0 = empty (NaN never enters).  peak_window_kernel (phasecorr.hip)
-// reduces the slots and zeroes them for the next surface.
-constexpr int kPeakSlots = 256;
+// reduces the slots and zeroes them for the next surface.  (kPeakSlots: oip_fftplan.h)
 __host__ __device__ inline unsigned long long oip_peak_pack(float v, long key)
 {
     if (v != v) return 0ull;                                   // NaN

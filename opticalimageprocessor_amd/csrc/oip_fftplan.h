@@ -48,6 +48,8 @@ struct OipFftHostPlan {
     int n_y;
 };
 
+constexpr int kPeakSlots = 256;       // arg-max slots per correlation surface (oip_fft.h: oip_peak_pack)
+
 namespace oipfftplan {
 
 // codes of a refusal: the values of OIP_OK, OIP_E_INVALID, OIP_E_RUNTIME and OIP_E_UNSUPPORTED (include/oip_c.h; host.cpp asserts it)
@@ -170,6 +172,19 @@ inline long pass_blocks(const OipFftPass &p)
 {
     if (p.mode == 0) return (long)p.lane_tiles * p.O1 * p.O2;
     return (p.lanes + (1 << p.vshift) - 1) >> p.vshift;
+}
+
+// The list forms of the inverse column passes (oip_fft_col_list_pass) take a plan whose column passes all work on lane tiles of
+// one width (the list names tiles of that width) and whose work items fit an int.
+inline bool col_list_ok(const OipFftHostPlan &pl, int narr)
+{
+    if (pl.n_y < 1) return false;
+    for (int i = 0; i < pl.n_y; ++i) {
+        const OipFftPass &p = pl.passes[i];
+        if (p.mode != 0 || p.axis != 1 || p.vshift != pl.passes[0].vshift || p.tw_mode == 1) return false;
+        if ((long)narr * p.lane_tiles * p.O1 * p.O2 > 0x7fffffffL) return false;
+    }
+    return pl.passes[0].O2 == 1;       // the last inverse pass spans the whole axis
 }
 
 // What the launcher refuses of a planned pass: kPlanOk, or the code with its text in `why`.  A tw_mode 2 pass is a column

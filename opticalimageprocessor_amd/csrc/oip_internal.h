@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "oip_c.h"
+#include "oip_corrroute.h"
 
 struct oip_prof_entry {
     std::string name;
@@ -42,17 +43,6 @@ struct OipResizeTab {
     int yspec_state;
 };
 
-// OpenCV imgwarp.cpp interpolateCubic, f32, evaluated on the host exactly as OpenCV does
-// (x86-64, no contraction: every TU is built with -ffp-contract=off)
-static inline void oip_interpolate_cubic_host(float x, float *coeffs)
-{
-    const float A = -0.75f;
-    coeffs[0] = ((A * (x + 1) - 5 * A) * (x + 1) + 8 * A) * (x + 1) - 4 * A;
-    coeffs[1] = ((A + 2) * x - (A + 3)) * x * x + 1;
-    coeffs[2] = ((A + 2) * (1 - x) - (A + 3)) * (1 - x) * (1 - x) + 1;
-    coeffs[3] = 1.f - coeffs[0] - coeffs[1] - coeffs[2];
-}
-
 struct oip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -79,6 +69,7 @@ struct oip_ctx {
 
     oip_fft_state *fft = nullptr;
     std::vector<OipResizeTab> resize_tabs;
+    std::vector<oipcorr::CorrPlan> corr_plans;     // the inter-band plans made so far, per geometry and switches (phasecorr.hip)
     unsigned long long *d_prune_stats = nullptr;   // device: lane tiles searched / in all by the correlation's peak search (oip_peak_prune_stats)
     // the row stage's stored window (oip_rows_window_stats): groups of units correlated with one / run again with every
     // column stored since the previous call, and the last call's geometry {tile columns, tiles, radius or -1}

@@ -19,6 +19,7 @@
 // differs from OpenCV's own DFT, so shifts agree to ~1e-4 px, not bitwise (parity unpinned:
 // OpenCV is not in the reference tree).
 #include "oip_corrgeom.h"
+#include "oip_corrroute.h"
 #include "oip_fft.h"
 #include "oip_fft_dev.h"
 #include "oip_internal.h"
@@ -27,6 +28,8 @@
 #include <cmath>
 
 namespace {
+
+using namespace oipcorr;      // the plan of a correlation call: switches, route, FFT plans, workspace (oip_corrroute.h)
 
 constexpr int kBlock = 256;
 
@@ -616,7 +619,7 @@ template <int NT, bool VEXP, bool WIN>
 __global__ __launch_bounds__(NT) void corr_rows_up_kernel(UpRowsJob fj, int M, int P, const int *__restrict__ ypos,
                                                           const float2 *__restrict__ twF, const float2 *__restrict__ twS)
 {
-    constexpr int F = 3000, S = F / 4;
+    constexpr int F = kUpRowsN, S = kUpRowsBandN;
     constexpr int TWF = oipfft::TwTable<F, 25, 15, 8>::value(), TWS = oipfft::TwTable<S, 25, 15, 2>::value();
     // A thread owns the bins kx = tid + NT r <= N/2 of line ky and their mirrors N - kx of the same line: H and G are
     // transforms of real sequences, so the mirror's table values are the conjugates -- half the table registers.
@@ -1096,11 +1099,12 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void corr_rows_v_kernel(VRowsJob 
 // complex value: array a = H(bX) + i H(bY) occupies columns [a stride, a stride + cols) of an m x (4 stride) array of
 // pitch Pn, columns [cols, stride) zero (cv::phaseCorrelate's right padding); rows {0, 1, m-2, m-1} also go to
 // raw[r][a][x] for the vertical operator's edge terms.
-struct HPackJob {
+// (BandPackJob: the band windows of the four arrays of a launch, array a = bx[a] + i by[a]; also pack_bands_kernel's)
+struct BandPackJob {
     const uint16_t *bx[4], *by[4];
     long pitch[4];
 };
-__global__ __launch_bounds__(128) void hpack_bands_kernel(HPackJob job, int m, int n, int cols, int stride, int Pn, const int *__restrict__ xofs,
+__global__ __launch_bounds__(128) void hpack_bands_kernel(BandPackJob job, int m, int n, int cols, int stride, int Pn, const int *__restrict__ xofs,
                                                           const float4 *__restrict__ alpha, float2 *__restrict__ z, float2 *__restrict__ raw)
 {
     const int x = blockIdx.x * 128 + threadIdx.x;
@@ -1154,9 +1158,9 @@ struct FusedRow {
 // xpower_stage's grid rule gives this entry one workgroup per CU, the grid it was tuned at: its LDS estimate is
 // 8 * (3 * 2 * 3000 + 1500) = 156000 B, so per_cu = min(163840 / 156000, 2048 / 768) = min(1, 2) = 1.
 const FusedRow kFusedRow[] = {
-    {3000, 768, corr_rows_kernel<3000, 768, 1, 1, false, 3, 5, 5, 5, 8>, corr_rows_kernel<3000, 768, 3, 2, /*all*/ true, 25, 15, 8>},
-    {1250, 512, corr_rows_kernel<1250, 512, 1, 1, false, 5, 5, 5, 5, 2>, corr_rows_kernel<1250, 512, 3, 2, false, 5, 5, 5, 5, 2>},
-    {200, 256, corr_rows_kernel<200, 256, 1, 1, false, 5, 5, 8>, corr_rows_kernel<200, 256, 3, 2, false, 5, 5, 8>},
+    {kUpRowsN, 768, corr_rows_kernel<3000, 768, 1, 1, false, 3, 5, 5, 5, 8>, corr_rows_kernel<3000, 768, 3, 2, /*all*/ true, 25, 15, 8>},
+    {kVRowsN, 512, corr_rows_kernel<1250, 512, 1, 1, false, 5, 5, 5, 5, 2>, corr_rows_kernel<1250, 512, 3, 2, false, 5, 5, 5, 5, 2>},
+    {kStitchRowsN, 256, corr_rows_kernel<200, 256, 1, 1, false, 5, 5, 8>, corr_rows_kernel<200, 256, 3, 2, false, 5, 5, 8>},
 };
 
 // ---- peak: first maximum of the fftShift-ed surface + 5x5 weighted centroid ----------------------
@@ -1245,19 +1249,6 @@ __global__ __launch_bounds__(kPeakWinThreads) void peak_window_kernel(PeakWinJob
     result[3 * part + 2] = response;
 }
 
-int optimal_dft_size(int n)
-{
-    // cv::getOptimalDFTSize: smallest 2^a 3^b 5^c >= n
-    long best = -1;
-    for (long p5 = 1; p5 < 2L * n + 1; p5 *= 5)
-        for (long p35 = p5; p35 < 2L * n + 1; p35 *= 3) {
-            long v = p35;
-            while (v < n) v *= 2;
-            if (best < 0 || v < best) best = v;
-        }
-    return (int)best;
-}
-
 OipAxisDigits digits_of(const std::vector<int> &f, int L)
 {
     OipAxisDigits d;
@@ -1266,9 +1257,6 @@ OipAxisDigits digits_of(const std::vector<int> &f, int L)
     for (int i = 0; i < 4; ++i) d.f[i] = i < d.n ? f[i] : 1;
     return d;
 }
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline bool smooth_len(long n) { for (int p : {2, 3, 5}) while (n % p == 0) n /= p; return n == 1; }
 
 // ---- peak search of the spectral route: which lane tiles can hold a surface's maximum -------------------------------
 // After the inverse row transform an output array Y~(ky, x) holds two real surfaces, y = c1 + i c2, and the inverse
@@ -1287,10 +1275,7 @@ inline bool smooth_len(long n) { for (int p : {2, 3, 5}) while (n % p == 0) n /=
 // f32 transform's own error is about 1e-5 of sum |x|; 2^-8 = 3.9e-3 covers both four times over and costs nothing, the
 // bound sitting 3 to 20 times below a usable peak.
 constexpr float kPruneMargin = 0x1p-8f;
-// The row stage stores only the columns of the lane tiles 0 .. R and T - R .. T - 1 (inter-band shifts are a few PAN
-// pixels: the surfaces peak in tile 0 or across the wrap), R = OIP_ROWS_WINDOW or this; see correlate_units_up.
-constexpr int kRowsWindowTiles = 8;
-constexpr int kSelThreads = 1024, kSelCols = 64, kSelParts = kSelThreads / kSelCols, kSelMaxTiles = 1024;
+constexpr int kSelThreads = 1024, kSelParts = kSelThreads / kSelCols;       // kSelCols, kSelMaxTiles: oip_corrroute.h
 struct PruneWork {
     float *bound;       // [row-stage workgroups][4][P]: the row stage's partial column sums (every row is written by every launch)
     int groups;         // workgroups of the row stage
@@ -1308,8 +1293,6 @@ struct PruneWork {
     int win_r;
     int *miss;
 };
-// a window of radius r exists for these lists: tiles of whole pieces (two columns), and the two arms do not meet
-inline bool rows_window_fits(const PruneWork &pw, int r) { return r >= 0 && pw.tiles && pw.vshift >= 1 && 2 * r + 1 < pw.T; }
 __device__ __forceinline__ bool tile_stored(const PruneWork &pw, int t) { return pw.win_r < 0 || t <= pw.win_r || t >= pw.T - pw.win_r; }
 
 // grid (ceil(N / kSelCols), arrays): a workgroup sums kSelCols columns -- thread (x, j) the rows j, j + kSelParts, ... of
@@ -1477,7 +1460,7 @@ __global__ __launch_bounds__(kPeakSlots) void col_sel_second_kernel(PruneWork pw
     }
 }
 
-// Workspace carve-up for one correlation unit
+// The carved workspace of one correlation call (CorrPlan::reg)
 struct PcWork {
     PruneWork prune;
     float2 *z[5];
@@ -1486,54 +1469,44 @@ struct PcWork {
     float *fb[8];       // second images, f32 (up-sampled bands; two units' worth)
     float *fsmall;      // MSS window before resize
     unsigned long long *slots;  // [4 arrays][2][kPeakSlots] arg-max slots, empty between surfaces
+    float2 *band;       // the band array(s) of a spectral route, inside z[1] (CorrPlan::band_sub)
+    void *raw;          // their raw edge rows: behind the band array (HV) or in fsmall (V) (CorrPlan::raw_sub)
 };
 
-// prune: the storage of the peak search of the spectral route (PruneWork) as well
-int carve(oip_ctx *ctx, const OipFft2dPlan *pl, int rows, int cols, int small_elems, int nz, int ny, int nfb, PcWork *w, bool prune = false)
+int carve(oip_ctx *ctx, const CorrPlan &plan, PcWork *w)
 {
-    const int M = pl->M;
-    memset(&w->prune, 0, sizeof w->prune);
-    w->prune.win_r = -1;
-    size_t bbytes = 0, tbytes = 0;
-    if (prune) {
-        PruneWork &pw = w->prune;
-        pw.groups = ctx->cu_count < M / 2 + 1 ? ctx->cu_count : M / 2 + 1;       // the row stage's grid
-        pw.T = pl->passes[0].lane_tiles;
-        pw.vshift = pl->passes[0].vshift;
-        bbytes = align_up(sizeof(float) * (size_t)pw.groups * 4 * pl->P, 256);
-        if (oip_fft_col_list_ok(pl, 4) && (1 << pw.vshift) <= kSelCols && pw.T <= kSelMaxTiles)
-            tbytes = align_up(sizeof(int) * ((size_t)(4 + 4 + 16) * pw.T + 16 + 8), 256);
-    }
-    const size_t zbytes = align_up(sizeof(float2) * (size_t)M * pl->P, 256);
-    const size_t fbytes = align_up(sizeof(float) * (size_t)rows * cols, 256);
-    const size_t sbytes = align_up(sizeof(float) * (size_t)(small_elems > 0 ? small_elems : 1), 256);
-    const size_t pbytes = align_up(sizeof(unsigned long long) * 4 * 2 * kPeakSlots, 256);
-    size_t total = zbytes * (nz + ny) + fbytes * (1 + nfb) + sbytes + pbytes + bbytes + tbytes;
     void *ws;
-    int rc = oip_workspace(ctx, total, &ws);
+    int rc = oip_workspace(ctx, plan.total, &ws);
     if (rc) return rc;
-    char *p = (char *)ws;
-    if (bbytes) { w->prune.bound = (float *)p; p += bbytes; }
-    if (tbytes) {
-        // but for the tickets (cleared below) every word of these is written by col_sel_first_kernel before anything reads it
-        PruneWork &pw = w->prune;
-        pw.bt = (float *)p;
-        pw.flags = (int *)p + 4 * pw.T;
-        pw.count = (int *)p + 8 * pw.T;
-        pw.ticket = (int *)p + 8 * pw.T + 16;
-        pw.tiles = (int *)p + 8 * pw.T + 16 + 8;
-        p += tbytes;
+    auto at = [&](CorrRegionId r, int i) { return i < plan.reg[r].count ? (char *)ws + plan.reg[r].part(i) : nullptr; };
+    auto sub = [&](const CorrSubRegion &s) { return s.bytes ? at(s.in, s.part) + s.offset : nullptr; };
+    memset(w, 0, sizeof *w);
+    PruneWork &pw = w->prune;
+    pw.win_r = -1;
+    pw.groups = plan.groups;
+    pw.T = plan.T;
+    pw.vshift = plan.vshift;
+    pw.bound = (float *)at(kRegBound, 0);
+    if (int *l = (int *)at(kRegLists, 0)) {
+        // (prune_list_bytes) but for the tickets (cleared below) every word of these is written by col_sel_first_kernel before anything reads it
+        pw.bt = (float *)l;
+        pw.flags = l + 4 * pw.T;
+        pw.count = l + 8 * pw.T;
+        pw.ticket = l + 8 * pw.T + 16;
+        pw.tiles = l + 8 * pw.T + 16 + 8;
     }
-    for (int i = 0; i < 5; ++i) { w->z[i] = i < nz ? (float2 *)p : nullptr; if (i < nz) p += zbytes; }
-    for (int i = 0; i < 4; ++i) { w->y[i] = i < ny ? (float2 *)p : nullptr; if (i < ny) p += zbytes; }
-    w->fa = (float *)p; p += fbytes;
-    for (int i = 0; i < 8; ++i) { w->fb[i] = i < nfb ? (float *)p : nullptr; if (i < nfb) p += fbytes; }
-    w->fsmall = (float *)p; p += sbytes;
-    w->slots = (unsigned long long *)p;
+    for (int i = 0; i < 5; ++i) w->z[i] = (float2 *)at(kRegZ, i);
+    for (int i = 0; i < 4; ++i) w->y[i] = (float2 *)at(kRegY, i);
+    w->fa = (float *)at(kRegFa, 0);
+    for (int i = 0; i < 8; ++i) w->fb[i] = (float *)at(kRegFb, i);
+    w->fsmall = (float *)at(kRegSmall, 0);
+    w->slots = (unsigned long long *)at(kRegSlots, 0);
+    w->band = (float2 *)sub(plan.band_sub);
+    w->raw = sub(plan.raw_sub);
     // the slots must start empty (later surfaces are cleaned by peak_window_kernel)
     ctx->prof_chain = nullptr;
     OIP_HIP(ctx, hipMemsetAsync(w->slots, 0, sizeof(unsigned long long) * 4 * 2 * kPeakSlots, ctx->stream));
-    if (w->prune.ticket) OIP_HIP(ctx, hipMemsetAsync(w->prune.ticket, 0, sizeof(int) * 8, ctx->stream));
+    if (pw.ticket) OIP_HIP(ctx, hipMemsetAsync(pw.ticket, 0, sizeof(int) * 8, ctx->stream));
     return OIP_OK;
 }
 
@@ -1551,40 +1524,21 @@ int launch_window(oip_ctx *ctx, const uint16_t *img, size_t pitch, long row0, in
     return OIP_OK;
 }
 
-int resize_tables(oip_ctx *ctx, int sw, int sh, int dw, int dh, const OipResizeTab **out)
+int resize_tables(oip_ctx *ctx, int sw, int sh, int dw, int dh, OipResizeTab **out)
 {
     for (auto &t : ctx->resize_tabs)
         if (t.sw == sw && t.sh == sh && t.dw == dw && t.dh == dh) { *out = &t; return OIP_OK; }
-    // cv::hal::resize coefficient set-up (resize.cpp), on the host in the same float/double mix
-    const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
-    std::vector<int> xofs(dw), yofs(dh);
-    std::vector<float> alpha((size_t)dw * 4), beta((size_t)dh * 4);
-    for (int dx = 0; dx < dw; ++dx) {
-        float fx = (float)((dx + 0.5) * scale_x - 0.5);
-        int sx = (int)floorf(fx);
-        fx -= sx;
-        xofs[dx] = sx;
-        oip_interpolate_cubic_host(fx, &alpha[(size_t)dx * 4]);
-    }
-    for (int dy = 0; dy < dh; ++dy) {
-        float fy = (float)((dy + 0.5) * scale_y - 0.5);
-        int sy = (int)floorf(fy);
-        fy -= sy;
-        yofs[dy] = sy;
-        oip_interpolate_cubic_host(fy, &beta[(size_t)dy * 4]);
-    }
+    std::vector<int> xofs, yofs;
+    std::vector<float> alpha, beta;
+    resize_axis(sw, dw, &xofs, &alpha);
+    resize_axis(sh, dh, &yofs, &beta);
     OipResizeTab t;
     t.sw = sw; t.sh = sh; t.dw = dw; t.dh = dh;
     t.d_xspec = nullptr; t.xspec_state = 0;
     t.d_yspec = nullptr; t.yspec_state = 0;
-    // the x4 kernel needs every output's first tap inside its source pixel's 5-wide window
-    t.x4 = dw == 4 * sw && dh == 4 * sh;
-    for (int dx = 0; dx < dw && t.x4; ++dx) { int o = (xofs[dx] - 1) - (dx / 4 - 2); t.x4 = o == 0 || o == 1; }
-    for (int dy = 0; dy < dh && t.x4; ++dy) { int o = (yofs[dy] - 1) - (dy / 4 - 2); t.x4 = o == 0 || o == 1; }
-    t.x4h = 1;
-    for (int dx = 0; dx < dw && t.x4h; ++dx) t.x4h = xofs[dx] == ((dx - 2) >> 2);
-    t.x4v = 1;
-    for (int dy = 0; dy < dh && t.x4v; ++dy) t.x4v = yofs[dy] == ((dy - 2) >> 2);
+    t.x4 = dw == 4 * sw && dh == 4 * sh && axis_in_x4_window(xofs) && axis_in_x4_window(yofs);
+    t.x4h = axis_is_x4(xofs);
+    t.x4v = axis_is_x4(yofs);
     OIP_HIP(ctx, hipMalloc((void **)&t.d_xofs, sizeof(int) * dw));
     OIP_HIP(ctx, hipMalloc((void **)&t.d_alpha, sizeof(float) * 4 * dw));
     OIP_HIP(ctx, hipMalloc((void **)&t.d_yofs, sizeof(int) * dh));
@@ -1601,7 +1555,7 @@ int resize_tables(oip_ctx *ctx, int sw, int sh, int dw, int dh, const OipResizeT
 template <typename SrcT>
 int launch_resize(oip_ctx *ctx, const SrcT *src, long spitch, int sw, int sh, float *dst, int dw, int dh)
 {
-    const OipResizeTab *t;
+    OipResizeTab *t;
     int rc = resize_tables(ctx, sw, sh, dw, dh, &t);
     if (rc) return rc;
     if (t->x4 && ((uintptr_t)dst & 15) == 0) {
@@ -1668,30 +1622,27 @@ __global__ __launch_bounds__(kV4Threads) void resize_cubic_v_x4_kernel(VBatch<Sr
     }
 }
 
-// vertical half only (see resize_cubic_v_kernel) of `count` equally shaped images in one launch; *tab
-// carries the horizontal taps for the FFT loader
+// vertical half only (see resize_cubic_v_kernel) of `count` equally shaped images in one launch by the tables of their
+// geometry (which carry the horizontal taps for the FFT loader); generic: not the x4 kernel (CorrKnobs::v_generic)
 template <typename SrcT>
-int launch_resize_v(oip_ctx *ctx, const SrcT *const *src, float *const *dst, int count, const long *spitch, int sw, int sh, int dw, int dh,
-                    const OipResizeTab **tab)
+int launch_resize_v(oip_ctx *ctx, const SrcT *const *src, float *const *dst, int count, const long *spitch, const OipResizeTab *tab, bool generic)
 {
-    int rc = resize_tables(ctx, sw, sh, dw, dh, tab);
-    if (rc) return rc;
+    const int sw = tab->sw, sh = tab->sh, dh = tab->dh;
     if (count < 1 || count > kVBatch) return oip_fail(ctx, OIP_E_RUNTIME, "launch_resize_v: bad batch");
     VBatch<SrcT> vb;
     for (int i = 0; i < kVBatch; ++i) { vb.src[i] = src[i < count ? i : 0]; vb.dst[i] = dst[i < count ? i : 0]; vb.spitch[i] = spitch[i < count ? i : 0]; }
     OipProfScope prof(ctx, "resize_cubic_v_kernel");
-    bool aligned = (sw & 1) == 0 && dh == 4 * sh && (*tab)->x4v;
+    bool aligned = !generic && (sw & 1) == 0 && dh == 4 * sh && tab->x4v;
     for (int i = 0; i < count; ++i)
         aligned = aligned && (spitch[i] & 1) == 0 && ((size_t)src[i] % (2 * sizeof(SrcT))) == 0 && ((size_t)dst[i] & 7) == 0;
-    { const char *e = getenv("OIP_V_GENERIC"); if (e && atoi(e)) aligned = false; }      // test knob: force the generic kernel
     if (aligned) {
         hipLaunchKernelGGL(resize_cubic_v_x4_kernel<SrcT>, dim3((sw / 2 + kV4Threads - 1) / kV4Threads, (sh + kV4Blocks - 1) / kV4Blocks, count),
-                           dim3(kV4Threads), 0, ctx->stream, vb, sw, sh, dh, reinterpret_cast<const float4 *>((*tab)->d_beta));
+                           dim3(kV4Threads), 0, ctx->stream, vb, sw, sh, dh, reinterpret_cast<const float4 *>(tab->d_beta));
         OIP_HIP(ctx, hipGetLastError());
         return OIP_OK;
     }
     hipLaunchKernelGGL(resize_cubic_v_kernel<SrcT>, dim3((sw + kBlock - 1) / kBlock, (dh + kVRows - 1) / kVRows, count), dim3(kBlock), 0,
-                       ctx->stream, vb, sw, sh, dh, (*tab)->d_yofs, reinterpret_cast<const float4 *>((*tab)->d_beta));
+                       ctx->stream, vb, sw, sh, dh, tab->d_yofs, reinterpret_cast<const float4 *>(tab->d_beta));
     OIP_HIP(ctx, hipGetLastError());
     return OIP_OK;
 }
@@ -1699,9 +1650,8 @@ int launch_resize_v(oip_ctx *ctx, const SrcT *const *src, float *const *dst, int
 // H and G_j of the x4 cubic up-sampling n -> N = 4 n along one axis (0: horizontal, 1: vertical) as an operator on
 // spectra (see corr_rows_up_kernel; oip_upsample_operator in host.cpp builds them), cached on the device per resize
 // geometry.  *out stays null when the geometry has no such form.
-int upsample_spectrum_tables(oip_ctx *ctx, const OipResizeTab *ctab, int axis, const float2 **out)
+int upsample_spectrum_tables(oip_ctx *ctx, OipResizeTab *t, int axis, const float2 **out)
 {
-    OipResizeTab *t = const_cast<OipResizeTab *>(ctab);
     *out = nullptr;
     int &state = axis ? t->yspec_state : t->xspec_state;
     void *&d_spec = axis ? t->d_yspec : t->d_xspec;
@@ -1769,14 +1719,39 @@ int launch_xpower(oip_ctx *ctx, float2 *out, const XpowerJob &job, const OipFft2
     return OIP_OK;
 }
 
-// The fused row-stage kernel of this plan (forward rows + cross-power + inverse rows in one kernel), or null:
-// forward row passes, cross_power_kernel and inverse row passes.  OIP_FUSED_ROWS=0 forces the latter.
-const FusedRow *row_stage(const OipFft2dPlan *pl)
+// What the drivers of one correlation call share: its plan (with the switches), the device forms of its FFT plans, its workspace,
+// and for the inter-band routes the tables of the band -> PAN resize and the up-sampling operators the route applies
+struct CorrCall {
+    oip_ctx *ctx;
+    const CorrPlan *plan;
+    const OipFft2dPlan *pl, *band;      // plan->main, plan->band (null on the image route)
+    OipResizeTab *tab;
+    const float2 *xtab, *vtab;
+    PcWork w;
+};
+
+int open_call(oip_ctx *ctx, const CorrPlan &plan, CorrCall *c)
 {
-    const char *env = getenv("OIP_FUSED_ROWS");          // read per call: a test switches it between two correlations
-    if ((env && atoi(env) <= 0) || pl->xf.size() != 1) return nullptr;
+    *c = CorrCall{ctx, &plan, nullptr, nullptr, nullptr, nullptr, nullptr, {}};
+    int rc = oip_fft2d_plan(ctx, plan.M, plan.N, &c->pl);
+    if (!rc && plan.route != kImage) rc = oip_fft2d_plan(ctx, plan.band.M, plan.band.N, &c->band);
+    return rc ? rc : carve(ctx, plan, &c->w);
+}
+
+// plan and open a call on one pair of rows x cols images; too_tall: the caller's refusal of more than 65535 lines
+int open_pair(oip_ctx *ctx, int rows, int cols, const CorrKnobs &knobs, const char *too_tall, CorrPlan *plan, CorrCall *c)
+{
+    char why[160];
+    const int rc = plan_pair(rows, cols, knobs, too_tall, plan, why, sizeof why);
+    return rc ? oip_fail(ctx, rc, "%s", why) : open_call(ctx, *plan, c);
+}
+
+// The fused row-stage kernel of this plan (forward rows + cross-power + inverse rows in one kernel), or null:
+// forward row passes, cross_power_kernel and inverse row passes.
+const FusedRow *row_stage(const CorrPlan &plan)
+{
     for (const FusedRow &k : kFusedRow)
-        if (k.F == pl->N) return &k;
+        if (plan.fused_rows && k.F == plan.N) return &k;
     return nullptr;
 }
 
@@ -1841,8 +1816,10 @@ int xpower_stage(oip_ctx *ctx, const OipFft2dPlan *pl, const FusedRow *rk, const
 
 // arg-max -> 5x5 window -> centroid of both parts (the real and imaginary surface) of `narr` arrays whose last inverse
 // pass left per-tile maxima in slot sets 0 .. narr-1: one launch
-int peak_windows(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, float2 *const *y, double *const *d_results, int narr, int nparts)
+int peak_windows(const CorrCall &c, float2 *const *y, double *const *d_results, int narr, int nparts)
 {
+    oip_ctx *ctx = c.ctx;
+    const OipFft2dPlan *pl = c.pl;
     const float2 *twM;
     int rc;
     if ((rc = oip_fft_table(ctx, pl->M, &twM))) return rc;
@@ -1851,88 +1828,51 @@ int peak_windows(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, float2 *
     for (int j = 0; j < 4; ++j) { job.data[j] = y[j < narr ? j : 0]; job.result[j] = d_results[j < narr ? j : 0]; }
     OipProfScope prof(ctx, "peak_window_kernel");
     hipLaunchKernelGGL(peak_window_kernel, dim3(narr * nparts), dim3(kPeakWinThreads), 0, ctx->stream, job, pl->M, pl->N, pl->P, F1, pl->M / F1, twM,
-                       w.slots, nparts);
+                       c.w.slots, nparts);
     OIP_HIP(ctx, hipGetLastError());
     return OIP_OK;
 }
 
 // inverse transform of y whose last pass only leaves per-tile maxima, in slot set `slot_set`; peak_windows turns them
 // into results
-int inverse_to_slots(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, float2 *y, bool rows_done, int slot_set)
+int inverse_to_slots(const CorrCall &c, float2 *y, bool rows_done, int slot_set)
 {
     OipFftIo io;
     memset(&io, 0, sizeof io);
     io.store_kind = 1;
-    io.slots = w.slots + (long)slot_set * 2 * kPeakSlots;
-    return oip_fft2d_exec(ctx, pl, y, 1, &io, rows_done ? 1 : 0);
+    io.slots = c.w.slots + (long)slot_set * 2 * kPeakSlots;
+    return oip_fft2d_exec(c.ctx, c.pl, y, 1, &io, rows_done ? 1 : 0);
 }
 
 // one pair (a, b) -> result slot
-int correlate_pair(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, RealSrc a, RealSrc b, int rows,
-                   int cols, double *d_result)
+int correlate_pair(const CorrCall &c, RealSrc a, RealSrc b, double *d_result)
 {
-    const FusedRow *rk = row_stage(pl);
-    int rc = forward_packed(ctx, pl, w.z[0], a, b, rows, cols, rk != nullptr);
+    const PcWork &w = c.w;
+    const FusedRow *rk = row_stage(*c.plan);
+    int rc = forward_packed(c.ctx, c.pl, w.z[0], a, b, c.plan->rows, c.plan->cols, rk != nullptr);
     if (rc) return rc;
     const SpecRef sa[1] = {{w.z[0], 0}}, sb[1] = {{w.z[0], 1}};
     float2 *const y[2] = {w.y[0], nullptr};
-    if ((rc = xpower_stage(ctx, pl, rk, sa, sb, 1, y))) return rc;
-    if ((rc = inverse_to_slots(ctx, pl, w, w.y[0], rk != nullptr, 0))) return rc;
+    if ((rc = xpower_stage(c.ctx, c.pl, rk, sa, sb, 1, y))) return rc;
+    if ((rc = inverse_to_slots(c, w.y[0], rk != nullptr, 0))) return rc;
     double *const res[1] = {d_result};
-    return peak_windows(ctx, pl, w, y, res, 1, 1);
+    return peak_windows(c, y, res, 1, 1);
 }
 
 // base image (real slot of zp) against (imag slot of zp, both slots of zq, slot `last_part` of zl)
-int correlate_four(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, const FusedRow *rk, float2 *zp, float2 *zq,
-                   float2 *zl, int last_part, double *d_results /* 4 x 3 */)
+int correlate_four(const CorrCall &c, const FusedRow *rk, float2 *zp, float2 *zq, float2 *zl, int last_part, double *d_results /* 4 x 3 */)
 {
     const SpecRef sa[4] = {{zp, 0}, {zp, 0}, {zp, 0}, {zp, 0}};
     const SpecRef sb[4] = {{zp, 1}, {zq, 0}, {zq, 1}, {zl, last_part}};
-    float2 *const y[2] = {w.y[0], w.y[1]};
+    float2 *const y[2] = {c.w.y[0], c.w.y[1]};
     int rc;
-    if ((rc = xpower_stage(ctx, pl, rk, sa, sb, 4, y))) return rc;
-    if ((rc = inverse_to_slots(ctx, pl, w, w.y[0], rk != nullptr, 0))) return rc;
-    if ((rc = inverse_to_slots(ctx, pl, w, w.y[1], rk != nullptr, 1))) return rc;
+    if ((rc = xpower_stage(c.ctx, c.pl, rk, sa, sb, 4, y))) return rc;
+    if ((rc = inverse_to_slots(c, y[0], rk != nullptr, 0))) return rc;
+    if ((rc = inverse_to_slots(c, y[1], rk != nullptr, 1))) return rc;
     double *const res[2] = {d_results, d_results + 6};
-    return peak_windows(ctx, pl, w, y, res, 2, 2);
+    return peak_windows(c, y, res, 2, 2);
 }
 
-// base image a against four images b0..b3: 3 forward + 2 inverse complex transforms
-int correlate_one_to_four(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, RealSrc a, const RealSrc b[4],
-                          int rows, int cols, double *d_results /* 4 x 3 */, const HTaps *vt)
-{
-    const FusedRow *rk = row_stage(pl);
-    const bool skip = rk != nullptr;
-    int rc;
-    if ((rc = forward_packed(ctx, pl, w.z[0], a, b[0], rows, cols, skip, vt))) return rc;
-    if ((rc = forward_packed(ctx, pl, w.z[1], b[1], b[2], rows, cols, skip, vt))) return rc;
-    if ((rc = forward_packed(ctx, pl, w.z[2], b[3], src_none(), rows, cols, skip, vt))) return rc;
-    return correlate_four(ctx, pl, w, rk, w.z[0], w.z[1], w.z[2], 0, d_results);
-}
-
-// Two units (base image + four bands each) at once: the fourth bands of the two units share one
-// complex transform (b3 of unit A in the real slot, b3 of unit B in the imaginary slot), so the
-// pair costs 5 forward transforms instead of 6.
-int correlate_two_units(oip_ctx *ctx, const OipFft2dPlan *pl, const PcWork &w, RealSrc aA, const RealSrc bA[4], RealSrc aB,
-                        const RealSrc bB[4], int rows, int cols, double *d_resA /* 4 x 3 */, double *d_resB, const HTaps *vt)
-{
-    const FusedRow *rk = row_stage(pl);
-    const bool skip = rk != nullptr;
-    int rc;
-    if ((rc = forward_packed(ctx, pl, w.z[0], aA, bA[0], rows, cols, skip, vt))) return rc;
-    if ((rc = forward_packed(ctx, pl, w.z[1], bA[1], bA[2], rows, cols, skip, vt))) return rc;
-    if ((rc = forward_packed(ctx, pl, w.z[2], aB, bB[0], rows, cols, skip, vt))) return rc;
-    if ((rc = forward_packed(ctx, pl, w.z[3], bB[1], bB[2], rows, cols, skip, vt))) return rc;
-    if ((rc = forward_packed(ctx, pl, w.z[4], bA[3], bB[3], rows, cols, skip, vt))) return rc;
-    if ((rc = correlate_four(ctx, pl, w, rk, w.z[0], w.z[1], w.z[4], 0, d_resA))) return rc;
-    return correlate_four(ctx, pl, w, rk, w.z[2], w.z[3], w.z[4], 1, d_resB);
-}
-
-// The same pair of units with the horizontal up-sampling applied to the band spectra (corr_rows_up_kernel): one
-// full-width forward transform (PAN_A + i PAN_B; aB may be absent), four quarter-width column transforms of the
-// vertically up-sampled bands (V images, rows x band_cols, packed two by two), one row-stage launch, four inverse
-// column transforms.  Against correlate_two_units: 2 instead of 5 array-sized forward column transforms, 6 instead of
-// 10 row transforms of 3000 points (in units of one).
 // One inter-band unit: a PAN window (rows x cols u16) and the matching windows of the four bands
 // (band_rows x band_cols u16), each with its own pitch -- a window of the resident raster or a compact
 // copy received from another rank.
@@ -1942,22 +1882,92 @@ struct IbUnit {
     const uint16_t *band[OIP_MSS_BANDS];
     long band_pitch;
 };
-
-struct UpPath {
-    const OipFft2dPlan *narrow;     // M x band_cols (vertical taps in the image domain), or
-    const OipFft2dPlan *small;      // band_rows x (4 band_cols): both axes on the spectra (vtab set)
-    const float2 *xtab, *vtab;
-    bool vonly;                     // padded row lengths (1228 -> 1250): horizontal taps in the image domain, vertical axis on
-                                    // the spectra (corr_rows_v_kernel); small = band_rows x (4 N)
+// The units a driver takes at once: two (which share transforms) or the last one alone; res[u]: the 4 x 3 results of unit
+// u; miss: the group's flag of the row stage's window
+struct UnitGroup {
+    const IbUnit *unit[2];
+    int n;
+    double *res[2];
+    int *miss;
+    RealSrc pan(int u) const { return u < n ? src_u16(unit[u]->pan, unit[u]->pan_pitch) : src_none(); }
 };
+
+// vertical cubic passes of all bands of the group in one launch (u16 -> f32 V images, rows x band_cols, in fb)
+int upsample_bands(const CorrCall &c, const UnitGroup &g, RealSrc *v /* 4 per unit */)
+{
+    const uint16_t *srcs[kVBatch];
+    long pitches[kVBatch];
+    for (int u = 0; u < g.n; ++u)
+        for (int b = 0; b < OIP_MSS_BANDS; ++b) {
+            srcs[4 * u + b] = g.unit[u]->band[b];
+            pitches[4 * u + b] = g.unit[u]->band_pitch;
+            v[4 * u + b] = src_v(c.w.fb[4 * u + b]);
+        }
+    return launch_resize_v<uint16_t>(c.ctx, srcs, c.w.fb, 4 * g.n, pitches, c.tab, c.plan->knobs.v_generic);
+}
+
+// The image route: base image against four up-sampled bands per unit, the horizontal taps in the FFT loader.  A unit is
+// PAN + i b0 and b1 + i b2; the fourth bands of two units share one complex transform (b3 of unit A in the real slot, b3
+// of unit B in the imaginary slot), so a pair costs 5 forward transforms instead of 6, a single unit 3; 2 inverse each.
+int correlate_units_image(const CorrCall &c, const UnitGroup &g)
+{
+    const PcWork &w = c.w;
+    const FusedRow *rk = row_stage(*c.plan);
+    const HTaps vt{c.plan->band_cols, c.tab->d_xofs, c.tab->d_alpha, c.tab->x4h};
+    auto forward = [&](float2 *z, RealSrc re, RealSrc im) { return forward_packed(c.ctx, c.pl, z, re, im, c.plan->rows, c.plan->cols, rk != nullptr, &vt); };
+    RealSrc v[8];
+    int rc;
+    if ((rc = upsample_bands(c, g, v))) return rc;
+    for (int u = 0; u < g.n; ++u)
+        if ((rc = forward(w.z[2 * u], g.pan(u), v[4 * u])) || (rc = forward(w.z[2 * u + 1], v[4 * u + 1], v[4 * u + 2]))) return rc;
+    float2 *zl = w.z[2 * g.n];
+    if ((rc = forward(zl, v[3], g.n > 1 ? v[7] : src_none()))) return rc;
+    for (int u = 0; u < g.n; ++u)
+        if ((rc = correlate_four(c, rk, w.z[2 * u], w.z[2 * u + 1], zl, u, g.res[u]))) return rc;
+    return OIP_OK;
+}
+
+// ---- the spectral routes: the up-sampling applied to the band spectra in the row stage ----------------------------------
+// Their shared head: one full-size forward transform (PAN_A + i PAN_B; B may be absent) up to its row passes
+int forward_pans(const CorrCall &c, const UnitGroup &g)
+{
+    return forward_packed(c.ctx, c.pl, c.w.z[0], g.pan(0), g.pan(1), c.plan->rows, c.plan->cols, true);
+}
+// the band windows of the four arrays of a launch: array a = bX + i bY of unit a / 2 (a single unit's twice)
+BandPackJob band_pack_job(const UnitGroup &g)
+{
+    BandPackJob bj;
+    for (int a = 0; a < 4; ++a) {
+        const IbUnit *u = g.unit[(a < 2 * g.n ? a : 0) / 2];
+        bj.bx[a] = u->band[2 * (a & 1)]; bj.by[a] = u->band[2 * (a & 1) + 1]; bj.pitch[a] = u->band_pitch;
+    }
+    return bj;
+}
+// the column passes of the packed band array (four arrays side by side), reported apart
+int band_columns(const CorrCall &c)
+{
+    c.ctx->prof_tag = "_band";
+    const int rc = oip_fft2d_exec(c.ctx, c.band, c.w.band, 0, nullptr, 1);
+    c.ctx->prof_tag = nullptr;
+    return rc;
+}
+// Their shared tail: the results of output o = 2 u + h are bands 2 h, 2 h + 1 of unit u.  exhaustive: the inverse column
+// passes of every output into its own slot set (else the caller has searched them); then the peak windows.
+int finish_outputs(const CorrCall &c, const UnitGroup &g, bool exhaustive)
+{
+    const int narr = 2 * g.n;
+    double *res[4];
+    for (int o = 0; o < narr; ++o) {
+        res[o] = g.res[o / 2] + 6 * (o & 1);
+        if (exhaustive)
+            if (int rc = inverse_to_slots(c, c.w.y[o], true, o)) return rc;
+    }
+    return peak_windows(c, c.w.y, res, narr, 2);
+}
 
 // The band windows of a launch as one complex array: array a = bX + i bY occupies columns [n a, n a + n) of an
 // m x (4 n) array of pitch Pn (the column passes then run over all four at once); rows {0, 1, m-2, m-1} of each array
 // also go to raw16[r][a n / 2 + p / 2] as (bX | bY << 16) of the points p, p + 1 (n even).
-struct BandPackJob {
-    const uint16_t *bx[4], *by[4];
-    long pitch[4];
-};
 template <bool PAIRS>        // PAIRS: two neighbouring columns per thread through 4-byte loads (host-checked alignment)
 __global__ __launch_bounds__(128) void pack_bands_kernel(BandPackJob job, int m, int n, int Pn, float2 *__restrict__ z, unsigned *__restrict__ raw16)
 {
@@ -1983,112 +1993,90 @@ __global__ __launch_bounds__(128) void pack_bands_kernel(BandPackJob job, int m,
     }
 }
 
-int correlate_units_up(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, const PcWork &w, RealSrc aA, RealSrc aB, const RealSrc *v /* 4 or 8: V images */,
-                       const IbUnit *const *units, int nunits, int rows, int cols, int band_rows, int band_cols, double *d_resA, double *d_resB,
-                       int win_r = -1, int *d_miss = nullptr)
+// The H and HV routes (3000-point rows, corr_rows_up_kernel): the band arrays are four quarter-width (`_quarter`) column
+// transforms of the vertically up-sampled bands (H: V images, rows x band_cols, packed two by two), or the column
+// transform of the band windows themselves, four arrays side by side (HV); one row-stage launch, four inverse column
+// transforms.  Against the image route: 2 instead of 5 array-sized forward column transforms, 6 instead of 10 row
+// transforms of 3000 points (in units of one).  win_r: the stored window of this run, -1 for every column.
+int correlate_units_up(const CorrCall &c, const UnitGroup &g, int win_r)
 {
+    oip_ctx *ctx = c.ctx;
+    const CorrPlan &plan = *c.plan;
+    const OipFft2dPlan *pl = c.pl;
+    const PcWork &w = c.w;
+    const bool both = plan.route == kSpectralHV;
+    const int narr = 2 * g.n, Pn = c.band->P;
     int rc;
-    if ((rc = forward_packed(ctx, pl, w.z[0], aA, nunits > 1 ? aB : src_none(), rows, cols, true))) return rc;
-    const int narr = 2 * nunits;
-    long zn_stride;
-    int Pn;
-    const int *ypos_s = nullptr;
-    unsigned *raw = nullptr;
-    if (up.vtab) {
-        // band windows -> one m x 3000 complex array (four arrays side by side) -> its column passes
-        Pn = up.small->P;
-        zn_stride = band_cols;
-        raw = reinterpret_cast<unsigned *>(w.z[1] + (long)up.small->M * Pn);
-        BandPackJob bj;
-        for (int a = 0; a < 4; ++a) {
-            const IbUnit *u = units[(a < narr ? a : 0) / 2];
-            bj.bx[a] = u->band[2 * (a & 1)]; bj.by[a] = u->band[2 * (a & 1) + 1]; bj.pitch[a] = u->band_pitch;
-        }
+    if ((rc = forward_pans(c, g))) return rc;
+    if (both) {
+        const BandPackJob bj = band_pack_job(g);
         {
             OipProfScope prof(ctx, "pack_bands_kernel");
+            const int band_rows = plan.band_rows, band_cols = plan.band_cols;
             bool pairs = (band_cols & 1) == 0 && (Pn & 1) == 0;
             for (int a = 0; a < 4; ++a)
                 pairs = pairs && (bj.pitch[a] & 1) == 0 && ((size_t)bj.bx[a] & 3) == 0 && ((size_t)bj.by[a] & 3) == 0;
             const int gy = band_rows < 128 ? band_rows : 128;
             if (pairs)
                 hipLaunchKernelGGL(pack_bands_kernel<true>, dim3((band_cols / 2 + 127) / 128, gy, 4), dim3(128), 0, ctx->stream, bj, band_rows, band_cols, Pn,
-                                   w.z[1], raw);
+                                   w.band, (unsigned *)w.raw);
             else
                 hipLaunchKernelGGL(pack_bands_kernel<false>, dim3((band_cols + 127) / 128, gy, 4), dim3(128), 0, ctx->stream, bj, band_rows, band_cols, Pn,
-                                   w.z[1], raw);
+                                   w.band, (unsigned *)w.raw);
             OIP_HIP(ctx, hipGetLastError());
         }
-        ctx->prof_tag = "_band";
-        rc = oip_fft2d_exec(ctx, up.small, w.z[1], 0, nullptr, 1);
-        ctx->prof_tag = nullptr;
-        if (rc) return rc;
-        ypos_s = up.small->d_ypos;
+        if ((rc = band_columns(c))) return rc;
     } else {
-        Pn = up.narrow->P;
-        zn_stride = (long)up.narrow->M * Pn;
+        RealSrc v[8];
+        if ((rc = upsample_bands(c, g, v))) return rc;
         ctx->prof_tag = "_quarter";
         for (int a = 0; a < narr && !rc; ++a)
-            rc = forward_packed(ctx, up.narrow, w.z[1] + a * zn_stride, src_f32(v[2 * a].v), src_f32(v[2 * a + 1].v), rows, band_cols, true);
+            rc = forward_packed(ctx, c.band, w.band + a * (long)plan.M * Pn, src_f32(v[2 * a].v), src_f32(v[2 * a + 1].v), plan.rows, plan.band_cols, true);
         ctx->prof_tag = nullptr;
         if (rc) return rc;
     }
     const float2 *twF, *twS;
-    if ((rc = oip_fft_table(ctx, 3000, &twF)) || (rc = oip_fft_table(ctx, 750, &twS))) return rc;
+    if ((rc = oip_fft_table(ctx, kUpRowsN, &twF)) || (rc = oip_fft_table(ctx, kUpRowsBandN, &twS))) return rc;
     UpRowsJob fj;
     memset(&fj, 0, sizeof fj);
     fj.zp = w.z[0];
-    fj.zn = w.z[1];
-    fj.zn_stride = zn_stride;
+    fj.zn = w.band;
+    fj.zn_stride = both ? plan.band_cols : (long)plan.M * Pn;
     fj.Pn = Pn;
     for (int o = 0; o < 4; ++o) fj.out[o] = w.y[o];
-    fj.xtab = up.xtab;
+    fj.xtab = c.xtab;
     fj.nout = narr;
-    fj.vtab = up.vtab;
-    fj.raw16 = reinterpret_cast<const uint2 *>(raw);
-    fj.ypos_s = ypos_s;
-    fj.m = band_rows;
+    fj.vtab = c.vtab;
+    fj.raw16 = reinterpret_cast<const uint2 *>(w.raw);
+    fj.ypos_s = both ? c.band->d_ypos : nullptr;
+    fj.m = plan.band_rows;
     fj.bound = w.prune.bound;
-    if (!fj.bound) return oip_fail(ctx, OIP_E_RUNTIME, "correlate_units_up: no storage for the column bounds");
     // (not cleared: every workgroup of the launch below writes its four rows in full, with 8-byte stores)
-    if (pl->P & 1) return oip_fail(ctx, OIP_E_RUNTIME, "correlate_units_up: odd row pitch %d", pl->P);
     // The stored window (rows_window): tiles 0 .. win_r and T - win_r .. T - 1 of the column passes' lane tiles, as pieces
     // of two columns.  The peak search below tells a pair that needs a tile outside of it (PruneWork::miss).
     PruneWork pw = w.prune;
-    const char *pe = getenv("OIP_PEAK_PRUNE");
-    const int full = pe && atoi(pe) == 0 ? 1 : 0;           // every tile is listed: every column is stored
-    if (full || !up.vtab || !rows_window_fits(pw, win_r) || !d_miss) win_r = -1;
+    const int full = c.plan->knobs.peak_prune ? 0 : 1;           // every tile is listed: every column is stored
     pw.win_r = win_r;
-    pw.miss = d_miss;
+    pw.miss = g.miss;
     if (win_r >= 0) {
         fj.win_hi = ((win_r + 1) << pw.vshift) / 2;
         fj.win_lo = ((pw.T - win_r) << pw.vshift) / 2;
     }
-    {
-        const char *pz = getenv("OIP_ROWS_WINDOW_POISON");      // debug: what the window leaves unwritten reads as NaN, not as the last pair's data
-        if (pz && atoi(pz) > 0)
-            for (int o = 0; o < narr; ++o) OIP_HIP(ctx, hipMemsetAsync(w.y[o], 0xff, sizeof(float2) * (size_t)pl->M * pl->P, ctx->stream));
-    }
+    if (c.plan->knobs.window_poison)      // debug: what the window leaves unwritten reads as NaN, not as the last pair's data
+        for (int o = 0; o < narr; ++o) OIP_HIP(ctx, hipMemsetAsync(w.y[o], 0xff, sizeof(float2) * (size_t)pl->M * pl->P, ctx->stream));
     {
         OipProfScope prof(ctx, "corr_rows_up_kernel");
-        const long grid = w.prune.groups;
-        const dim3 g((unsigned)grid);
         // (no windowed instance without VEXP: it has not been built since that kernel stopped spilling -- DESIGN.md 4.3)
-        auto k = up.vtab ? (win_r >= 0 ? corr_rows_up_kernel<512, true, true> : corr_rows_up_kernel<512, true, false>)
-                         : corr_rows_up_kernel<512, false, false>;
+        auto k = both ? (win_r >= 0 ? corr_rows_up_kernel<512, true, true> : corr_rows_up_kernel<512, true, false>)
+                      : corr_rows_up_kernel<512, false, false>;
         // measured in bench.py, VEXP: 1.275 ms with 512 threads (244 VGPRs, no scratch), 1.36 with 768 (168, 28 spilled)
-        hipLaunchKernelGGL(k, g, dim3(512), 0, ctx->stream, fj, pl->M, pl->P, pl->d_ypos, twF, twS);
+        hipLaunchKernelGGL(k, dim3((unsigned)w.prune.groups), dim3(512), 0, ctx->stream, fj, pl->M, pl->P, pl->d_ypos, twF, twS);
         OIP_HIP(ctx, hipGetLastError());
     }
-    double *res[4];
-    for (int o = 0; o < narr; ++o) res[o] = (o < 2 ? d_resA : d_resB) + 6 * (o & 1);
-    if (!pw.tiles) {
-        // a plan without list forms of its column passes: the exhaustive passes, each output into its own slot set
-        for (int o = 0; o < narr; ++o)
-            if ((rc = inverse_to_slots(ctx, pl, w, w.y[o], true, o))) return rc;
-        return peak_windows(ctx, pl, w, w.y, res, narr, 2);
-    }
+    // a plan without list forms of its column passes: the exhaustive passes, each output into its own slot set
+    if (!pw.tiles) return finish_outputs(c, g, true);
     // The inverse column passes of all outputs over the tiles that can hold a maximum (see PruneWork): select, column
-    // passes, peak pass -- twice.  OIP_PEAK_PRUNE=0 (read per call) lists every tile the first time: the exhaustive
+    // passes, peak pass -- twice.  OIP_PEAK_PRUNE=0 lists every tile the first time: the exhaustive
     // search through the same kernels.  A tile that is not searched keeps its untransformed data in y[o]; nothing else
     // reads it (peak_window_kernel reads the two columns either side of a searched tile at most, and those are done).
     if (!ctx->d_prune_stats) {
@@ -2127,70 +2115,56 @@ int correlate_units_up(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, c
             }
         }
     }
-    return peak_windows(ctx, pl, w, w.y, res, narr, 2);
+    return finish_outputs(c, g, false);
 }
 
-// A pair of units (or one) of a padded geometry -- the reference's 12288-wide strips: 1228-column slices, 1250-point
-// rows -- with the vertical up-sampling on the spectra (corr_rows_v_kernel): one full-height forward column transform
-// (PAN_A + i PAN_B), the horizontally up-sampled bands transformed at their own height (four arrays side by side), one
-// row-stage launch, four inverse column transforms.
-int correlate_units_vup(oip_ctx *ctx, const OipFft2dPlan *pl, const UpPath &up, const PcWork &w, const OipResizeTab *tab, RealSrc aA, RealSrc aB,
-                        const IbUnit *const *units, int nunits, int rows, int cols, int band_rows, int band_cols, double *d_resA, double *d_resB)
+// The V route, a padded geometry -- the reference's 12288-wide strips: 1228-column slices, 1250-point rows -- with the
+// vertical up-sampling on the spectra (corr_rows_v_kernel): the horizontally up-sampled bands transformed at their own
+// height (four arrays side by side in z[1], their four raw edge rows in the small scratch), one row-stage launch per
+// unit, four inverse column transforms.
+int correlate_units_vup(const CorrCall &c, const UnitGroup &g)
 {
+    oip_ctx *ctx = c.ctx;
+    const CorrPlan &plan = *c.plan;
+    const OipFft2dPlan *pl = c.pl;
+    const PcWork &w = c.w;
+    const int N = plan.N, Pn = c.band->P;
     int rc;
-    if ((rc = forward_packed(ctx, pl, w.z[0], aA, nunits > 1 ? aB : src_none(), rows, cols, true))) return rc;
-    const int narr = 2 * nunits;
-    const int N = pl->N, Pn = up.small->P;
-    // z[1] holds the m x (4 N) band array; the four raw rows of the four arrays live in the small scratch (carve: 32 N floats)
-    float2 *zn = w.z[1];
-    float2 *raw = reinterpret_cast<float2 *>(w.fsmall);
-    if ((long)up.small->M * Pn > (long)pl->M * pl->P) return oip_fail(ctx, OIP_E_RUNTIME, "correlate_units_vup: band array exceeds its slot");
-    HPackJob hj;
-    for (int a = 0; a < 4; ++a) {
-        const IbUnit *u = units[(a < narr ? a : 0) / 2];
-        hj.bx[a] = u->band[2 * (a & 1)]; hj.by[a] = u->band[2 * (a & 1) + 1]; hj.pitch[a] = u->band_pitch;
-    }
+    if ((rc = forward_pans(c, g))) return rc;
+    float2 *raw = reinterpret_cast<float2 *>(w.raw);
+    const BandPackJob hj = band_pack_job(g);
     {
         OipProfScope prof(ctx, "hpack_bands_kernel");
-        const int gy = band_rows < 256 ? band_rows : 256;
-        hipLaunchKernelGGL(hpack_bands_kernel, dim3((N + 127) / 128, gy, 4), dim3(128), 0, ctx->stream, hj, band_rows, band_cols, cols, N, Pn, tab->d_xofs,
-                           reinterpret_cast<const float4 *>(tab->d_alpha), zn, raw);
+        const int gy = plan.band_rows < 256 ? plan.band_rows : 256;
+        hipLaunchKernelGGL(hpack_bands_kernel, dim3((N + 127) / 128, gy, 4), dim3(128), 0, ctx->stream, hj, plan.band_rows, plan.band_cols, plan.cols, N, Pn,
+                           c.tab->d_xofs, reinterpret_cast<const float4 *>(c.tab->d_alpha), w.band, raw);
         OIP_HIP(ctx, hipGetLastError());
     }
-    ctx->prof_tag = "_band";
-    rc = oip_fft2d_exec(ctx, up.small, zn, 0, nullptr, 1);
-    ctx->prof_tag = nullptr;
-    if (rc) return rc;
+    if ((rc = band_columns(c))) return rc;
     const float2 *twF;
-    if ((rc = oip_fft_table(ctx, N, &twF))) return rc;
+    if ((rc = oip_fft_table(ctx, kVRowsN, &twF))) return rc;
     VRowsJob fj;
     memset(&fj, 0, sizeof fj);
     fj.zp = w.z[0];
-    fj.zn = zn;
+    fj.zn = w.band;
     fj.zn_stride = N;
     fj.Pn = Pn;
     for (int o = 0; o < 4; ++o) fj.out[o] = w.y[o];
-    fj.nout = narr;
-    fj.vtab = up.vtab;
+    fj.nout = 2 * g.n;
+    fj.vtab = c.vtab;
     fj.raw = raw;
-    fj.ypos_s = up.small->d_ypos;
-    fj.m = band_rows;
+    fj.ypos_s = c.band->d_ypos;
+    fj.m = plan.band_rows;
     {
         OipProfScope prof(ctx, "corr_rows_v_kernel");
         long grid = 2L * ctx->cu_count;     // two workgroups per CU (60 KB of LDS, <= 128 VGPRs each)
         if (grid > pl->M / 2 + 1) grid = pl->M / 2 + 1;
-        if (N != 1250) return oip_fail(ctx, OIP_E_RUNTIME, "correlate_units_vup: no row stage for %d-point rows", N);
-        for (int u = 0; u < nunits; ++u)
+        for (int u = 0; u < g.n; ++u)
             hipLaunchKernelGGL((corr_rows_v_kernel<1250, 512, 5, 5, 5, 5, 2>), dim3((unsigned)grid), dim3(512), 0, ctx->stream, fj, 2 * u, u, pl->M, pl->P,
                                pl->d_ypos, twF);
         OIP_HIP(ctx, hipGetLastError());
     }
-    double *res[4];
-    for (int o = 0; o < narr; ++o) {
-        res[o] = (o < 2 ? d_resA : d_resB) + 6 * (o & 1);
-        if ((rc = inverse_to_slots(ctx, pl, w, w.y[o], true, o))) return rc;
-    }
-    return peak_windows(ctx, pl, w, w.y, res, narr, 2);
+    return finish_outputs(c, g, true);
 }
 
 // nflags ints that follow the results in d_small (the miss flags of the row stage's window) ride the same copy
@@ -2228,15 +2202,13 @@ extern "C" int oip_phase_correlate_f32(oip_ctx *ctx, const float *d_a, const flo
 {
     OIP_CHECK_CTX(ctx);
     if (!d_a || !d_b || rows <= 0 || cols <= 0) return oip_fail(ctx, OIP_E_INVALID, "oip_phase_correlate_f32: bad argument");
-    const int M = optimal_dft_size(rows), N = optimal_dft_size(cols);
-    if (M > 65535) return oip_fail(ctx, OIP_E_UNSUPPORTED, "oip_phase_correlate_f32: more than 65535 rows");
-    const OipFft2dPlan *pl;
-    int rc = oip_fft2d_plan(ctx, M, N, &pl);
+    const CorrKnobs knobs = CorrKnobs::from_env();
+    CorrPlan plan;
+    CorrCall c;
+    int rc = open_pair(ctx, rows, cols, knobs, "oip_phase_correlate_f32: more than 65535 rows", &plan, &c);
     if (rc) return rc;
-    PcWork w;
-    if ((rc = carve(ctx, pl, 1, 1, 0, 1, 1, 0, &w))) return rc;
     double *d_res = (double *)ctx->d_small;
-    if ((rc = correlate_pair(ctx, pl, w, src_f32(d_a), src_f32(d_b), rows, cols, d_res))) return rc;
+    if ((rc = correlate_pair(c, src_f32(d_a), src_f32(d_b), d_res))) return rc;
     double r[3];
     if ((rc = fetch_results(ctx, 3, r))) return rc;
     if (dx) *dx = r[0];
@@ -2247,20 +2219,17 @@ extern "C" int oip_phase_correlate_f32(oip_ctx *ctx, const float *d_a, const flo
 
 // CCD-pair correlations of n window pairs (the loop body of stitcher.h:166-191 after the colRange): window i is
 // rows x cols u16 at a[i] / b[i] with its own pitch; results go to d_res[3 * i]
-static int stt_pairs(oip_ctx *ctx, const uint16_t *const *a, const size_t *pitch_a, const uint16_t *const *b,
+static int stt_pairs(oip_ctx *ctx, const CorrKnobs &knobs, const uint16_t *const *a, const size_t *pitch_a, const uint16_t *const *b,
                      const size_t *pitch_b, int n, int rows, int cols, double *host_out)
 {
-    const int M = optimal_dft_size(rows), N = optimal_dft_size(cols);
-    if (M > 65535) return oip_fail(ctx, OIP_E_UNSUPPORTED, "correlation window taller than 65535 lines");
-    const OipFft2dPlan *pl;
-    int rc = oip_fft2d_plan(ctx, M, N, &pl);
+    CorrPlan plan;
+    CorrCall c;
+    int rc = open_pair(ctx, rows, cols, knobs, "correlation window taller than 65535 lines", &plan, &c);
     if (rc) return rc;
-    PcWork w;
-    if ((rc = carve(ctx, pl, 1, 1, 0, 1, 1, 0, &w))) return rc;
     if ((rc = oip_small(ctx, sizeof(double) * 3 * (size_t)(n > 0 ? n : 1)))) return rc;
     double *d_res = (double *)ctx->d_small;
     for (int i = 0; i < n; ++i)
-        if ((rc = correlate_pair(ctx, pl, w, src_u16(a[i], (long)pitch_a[i]), src_u16(b[i], (long)pitch_b[i]), rows, cols, d_res + 3 * i)))
+        if ((rc = correlate_pair(c, src_u16(a[i], (long)pitch_a[i]), src_u16(b[i], (long)pitch_b[i]), d_res + 3 * i)))
             return rc;
     if (n > 0 && (rc = fetch_results(ctx, 3 * n, host_out))) return rc;
     return OIP_OK;
@@ -2276,7 +2245,7 @@ extern "C" int oip_stt_correlate_windows(oip_ctx *ctx, const uint16_t *const *d_
     for (int i = 0; i < n; ++i)
         if (!d_a[i] || !d_b[i] || pitch_a[i] < (size_t)cols || pitch_b[i] < (size_t)cols)
             return oip_fail(ctx, OIP_E_INVALID, "oip_stt_correlate_windows: window %d has a null pointer or a pitch below %d", i, cols);
-    return stt_pairs(ctx, d_a, pitch_a, d_b, pitch_b, n, rows, cols, out);
+    return stt_pairs(ctx, CorrKnobs::from_env(), d_a, pitch_a, d_b, pitch_b, n, rows, cols, out);
 }
 
 extern "C" int oip_stt_correlate(oip_ctx *ctx, const uint16_t *d_pan1, const uint16_t *d_pan2, int W, long L, long row0,
@@ -2300,7 +2269,7 @@ extern "C" int oip_stt_correlate(oip_ctx *ctx, const uint16_t *d_pan1, const uin
     }
     std::vector<size_t> pitch(which.size(), (size_t)W);
     std::vector<double> r(3 * which.size() + 3);
-    int rc = stt_pairs(ctx, a.data(), pitch.data(), b.data(), pitch.data(), (int)which.size(), g.rows, g.cols, r.data());
+    int rc = stt_pairs(ctx, CorrKnobs::from_env(), a.data(), pitch.data(), b.data(), pitch.data(), (int)which.size(), g.rows, g.cols, r.data());
     if (rc) return rc;
     for (int s = 0; s < sections; ++s)
         for (int k = 0; k < 3; ++k) out[3 * s + k] = NAN;
@@ -2310,124 +2279,62 @@ extern "C" int oip_stt_correlate(oip_ctx *ctx, const uint16_t *d_pan1, const uin
 }
 
 // The loop body of preproc.h:262-329 for n units: per unit and band (dx, dy, response) -> host_out[12 * u + 3 * b].
-// Units go two at a time (five forward and four inverse transforms per pair).
-static int interband_units(oip_ctx *ctx, const IbUnit *units, int n, int rows, int cols, int band_rows, int band_cols,
+// Units go two at a time by the route of the plan (oip_corrroute.h: plan_interband).
+static int interband_units(oip_ctx *ctx, const CorrKnobs &knobs, const IbUnit *units, int n, int rows, int cols, int band_rows, int band_cols,
                            double *host_out)
 {
-    const int M = optimal_dft_size(rows), N = optimal_dft_size(cols);
-    if (M > 65535) return oip_fail(ctx, OIP_E_UNSUPPORTED, "oip_interband_correlate: more than 65535 correlation lines");
-    const OipFft2dPlan *pl;
-    int rc = oip_fft2d_plan(ctx, M, N, &pl);
-    if (rc) return rc;
-    // PAN window: read as u16 by the FFT loader.  MSS windows: the vertical cubic pass runs as a kernel
-    // (u16 -> f32, rows x band_cols), the horizontal pass inside the FFT loader -- or, for the exact x4 geometry at
-    // 3000 columns, on the band spectra in the row stage (corr_rows_up_kernel; OIP_SPECTRAL_UP=0 keeps the loader).
-    const OipResizeTab *tab = nullptr;
-    if ((rc = resize_tables(ctx, band_cols, band_rows, cols, rows, &tab))) return rc;
-    UpPath up{nullptr, nullptr, nullptr, nullptr, false};
-    {
-        // OIP_SPECTRAL_UP: 0 = image domain, 1 = horizontal axis on the spectra, 2 (default) = both axes
-        const char *e = getenv("OIP_SPECTRAL_UP");
-        const int want = e ? atoi(e) : 2;
-        if (want > 0 && rows == 4 * band_rows && cols == 4 * band_cols && M == rows && N == cols && N == 3000 && row_stage(pl)) {
-            if ((rc = upsample_spectrum_tables(ctx, tab, 0, &up.xtab))) return rc;
-            if (up.xtab) {
-                if ((rc = oip_fft2d_plan(ctx, M, band_cols, &up.narrow))) return rc;
-                if (4 * up.narrow->P > pl->P || up.narrow->N != band_cols) up.xtab = nullptr;      // the four narrow arrays share one array-sized slot
-            }
-            if (up.xtab && want > 1 && optimal_dft_size(band_rows) == band_rows && band_rows >= 8) {
-                if ((rc = upsample_spectrum_tables(ctx, tab, 1, &up.vtab))) return rc;
-                if (up.vtab && (rc = oip_fft2d_plan(ctx, band_rows, cols, &up.small))) return rc;      // four arrays side by side
-            }
-        }
-        // the reference's own 12288-wide strips: 1228-column slices padded to 1250-point rows.  The horizontal taps stay in
-        // the image domain (1250 is not 4 x the band width); the vertical axis (16000 = 4 x 4000) goes to the spectra
-        // (corr_rows_v_kernel).  OIP_SPECTRAL_V=0 keeps the image-domain route.
-        const char *ev = getenv("OIP_SPECTRAL_V");
-        if (!up.xtab && !(ev && atoi(ev) == 0) && want > 0 && rows == 4 * band_rows && cols == 4 * band_cols && M == rows && N == 1250 &&
-            (cols & 1) == 0 && row_stage(pl) && optimal_dft_size(band_rows) == band_rows && band_rows >= 8 && smooth_len(4 * N)) {
-            if ((rc = upsample_spectrum_tables(ctx, tab, 1, &up.vtab))) return rc;
-            if (up.vtab) {
-                if ((rc = oip_fft2d_plan(ctx, band_rows, 4 * N, &up.small))) return rc;
-                up.vonly = (long)up.small->M * up.small->P <= (long)pl->M * pl->P;
-                if (!up.vonly) up.vtab = nullptr;
-            }
-        }
+    // planned once per geometry and switches (0.1 ms of host arithmetic, most of it the x4 test of the resize offsets)
+    const CorrPlan *cached = nullptr;
+    for (const CorrPlan &p : ctx->corr_plans)
+        if (p.rows == rows && p.cols == cols && p.band_rows == band_rows && p.band_cols == band_cols && p.knobs == knobs) cached = &p;
+    int rc;
+    if (!cached) {
+        CorrPlan p;
+        char why[160];
+        if ((rc = plan_interband(rows, cols, band_rows, band_cols, ctx->cu_count, knobs, &p, why, sizeof why))) return oip_fail(ctx, rc, "%s", why);
+        ctx->corr_plans.push_back(p);
+        cached = &ctx->corr_plans.back();
     }
-    PcWork w;
-    const bool spectral = up.xtab || up.vonly;
-    if ((rc = carve(ctx, pl, rows, band_cols, up.vonly ? 32 * N : 0, spectral ? 2 : 5, spectral ? 4 : 2, 8, &w, up.xtab != nullptr))) return rc;      // f32 scratch: the V images
-    // The row stage's window (rows_window): OIP_ROWS_WINDOW, read per call, is its radius in lane tiles, 0
-    // stores every column.  One miss flag per group of units follows the results in d_small.
-    int win_r = -1;
-    if (up.xtab && up.vtab) {
-        const char *e = getenv("OIP_ROWS_WINDOW");
-        win_r = e ? atoi(e) : kRowsWindowTiles;
-        const char *pe = getenv("OIP_PEAK_PRUNE");          // 0: every tile is searched, so every column is stored
-        win_r = win_r > 0 && !(pe && atoi(pe) == 0) && rows_window_fits(w.prune, win_r) ? win_r : -1;
-    }
-    ctx->rows_window[0] = w.prune.tiles ? 1 << w.prune.vshift : 0;
-    ctx->rows_window[1] = w.prune.tiles ? w.prune.T : 0;
-    ctx->rows_window[2] = win_r;
+    const CorrPlan &plan = *cached;
+    CorrCall c;
+    if ((rc = open_call(ctx, plan, &c))) return rc;
+    const bool haxis = plan.route == kSpectralH || plan.route == kSpectralHV, vaxis = plan.route == kSpectralHV || plan.route == kSpectralV;
+    if ((rc = resize_tables(ctx, band_cols, band_rows, cols, rows, &c.tab))) return rc;
+    if (haxis && (rc = upsample_spectrum_tables(ctx, c.tab, 0, &c.xtab))) return rc;
+    if (vaxis && (rc = upsample_spectrum_tables(ctx, c.tab, 1, &c.vtab))) return rc;
+    if ((haxis && !c.xtab) || (vaxis && !c.vtab)) return oip_fail(ctx, OIP_E_RUNTIME, "inter-band correlation: no up-sampling operator for the planned route");
+    ctx->rows_window[0] = plan.lists ? 1 << plan.vshift : 0;
+    ctx->rows_window[1] = plan.lists ? plan.T : 0;
+    ctx->rows_window[2] = plan.win_r;
+    // One miss flag of the row stage's window per group of units follows the results in d_small.
     const int ngroups = (n + 1) / 2;
     if ((rc = oip_small(ctx, sizeof(double) * 12 * (size_t)(n > 0 ? n : 1) + sizeof(int) * (size_t)(ngroups + 1)))) return rc;
     double *d_res = (double *)ctx->d_small;
     int *d_miss = reinterpret_cast<int *>(d_res + 12 * (size_t)n);
-    if (win_r >= 0) OIP_HIP(ctx, hipMemsetAsync(d_miss, 0, sizeof(int) * ngroups, ctx->stream));
-    // vertical passes of all bands of one or two units in one launch
-    auto upsample = [&](const IbUnit *const *uns, int nun, float *const *fb, RealSrc *out) -> int {
-        const uint16_t *srcs[kVBatch];
-        long pitches[kVBatch];
-        for (int u = 0; u < nun; ++u)
-            for (int b = 0; b < OIP_MSS_BANDS; ++b) {
-                srcs[4 * u + b] = uns[u]->band[b];
-                pitches[4 * u + b] = uns[u]->band_pitch;
-                out[4 * u + b] = src_v(fb[4 * u + b]);
-            }
-        return launch_resize_v<uint16_t>(ctx, srcs, fb, 4 * nun, pitches, band_cols, band_rows, cols, rows, &tab);
-    };
-    RealSrc sAB[8];
-    // units k, k + 1 (or the last one alone); wr: the row stage's window, -1 for every column
-    auto run_group = [&](int k, int wr) -> int {
-        if (k + 1 < n) {
-            const IbUnit &A = units[k], &B = units[k + 1];
-            const IbUnit *two[2] = {&A, &B};
-            if (up.vonly)
-                return correlate_units_vup(ctx, pl, up, w, tab, src_u16(A.pan, A.pan_pitch), src_u16(B.pan, B.pan_pitch), two, 2, rows, cols, band_rows,
-                                           band_cols, d_res + 12 * k, d_res + 12 * (k + 1));
-            if (!up.vtab && (rc = upsample(two, 2, w.fb, sAB))) return rc;
-            if (up.xtab)
-                return correlate_units_up(ctx, pl, up, w, src_u16(A.pan, A.pan_pitch), src_u16(B.pan, B.pan_pitch), sAB, two, 2, rows, cols, band_rows,
-                                          band_cols, d_res + 12 * k, d_res + 12 * (k + 1), wr, d_miss + k / 2);
-            const HTaps vt{band_cols, tab->d_xofs, tab->d_alpha, tab->x4h};
-            return correlate_two_units(ctx, pl, w, src_u16(A.pan, A.pan_pitch), sAB, src_u16(B.pan, B.pan_pitch), sAB + 4, rows, cols,
-                                       d_res + 12 * k, d_res + 12 * (k + 1), &vt);
+    if (plan.win_r >= 0) OIP_HIP(ctx, hipMemsetAsync(d_miss, 0, sizeof(int) * ngroups, ctx->stream));
+    // group k: units 2 k, 2 k + 1 (or the last one alone); win_r: the row stage's window, -1 for every column
+    auto run_group = [&](int k, int win_r) -> int {
+        UnitGroup g{{&units[2 * k], &units[2 * k + (2 * k + 1 < n ? 1 : 0)]}, 2 * k + 1 < n ? 2 : 1, {d_res + 24 * k, d_res + 24 * k + 12}, d_miss + k};
+        switch (plan.route) {
+        case kSpectralH:
+        case kSpectralHV: return correlate_units_up(c, g, win_r);
+        case kSpectralV: return correlate_units_vup(c, g);
+        default: return correlate_units_image(c, g);
         }
-        const IbUnit &A = units[k];
-        const IbUnit *one[1] = {&A};
-        if (up.vonly)
-            return correlate_units_vup(ctx, pl, up, w, tab, src_u16(A.pan, A.pan_pitch), src_none(), one, 1, rows, cols, band_rows, band_cols,
-                                       d_res + 12 * k, nullptr);
-        if (!up.vtab && (rc = upsample(one, 1, w.fb, sAB))) return rc;
-        if (up.xtab)
-            return correlate_units_up(ctx, pl, up, w, src_u16(A.pan, A.pan_pitch), src_none(), sAB, one, 1, rows, cols, band_rows, band_cols,
-                                      d_res + 12 * k, nullptr, wr, d_miss + k / 2);
-        const HTaps vt{band_cols, tab->d_xofs, tab->d_alpha, tab->x4h};
-        return correlate_one_to_four(ctx, pl, w, src_u16(A.pan, A.pan_pitch), sAB, rows, cols, d_res + 12 * k, &vt);
     };
-    for (int k = 0; k < n; k += 2)
-        if ((rc = run_group(k, win_r))) return rc;
-    if (n > 0 && win_r >= 0) {
+    for (int k = 0; k < ngroups; ++k)
+        if ((rc = run_group(k, plan.win_r))) return rc;
+    if (n > 0 && plan.win_r >= 0) {
         // Groups whose peak search needed a tile outside the stored window (their flags came with the results) run again
         // from the top with every column stored -- with the same partner, on which a unit's last digits depend -- and the
         // results are fetched again.  Nothing waits but this call's own fetch.
         std::vector<int> miss((size_t)ngroups);
         if ((rc = fetch_results(ctx, 12 * n, host_out, ngroups, miss.data()))) return rc;
         int again = 0;
-        for (int g = 0; g < ngroups; ++g)
-            if (miss[g]) {
+        for (int k = 0; k < ngroups; ++k)
+            if (miss[k]) {
                 ++again;
-                if ((rc = run_group(2 * g, -1))) return rc;
+                if ((rc = run_group(k, -1))) return rc;
             }
         ctx->rows_window_pairs += ngroups;
         ctx->rows_window_rerun += again;
@@ -2491,7 +2398,7 @@ extern "C" int oip_interband_correlate_units(oip_ctx *ctx, const uint16_t *const
         for (int b = 0; b < OIP_MSS_BANDS; ++b) { units[i].band[b] = d_bands[4 * i + b]; ok = ok && d_bands[4 * i + b]; }
         if (!ok) return oip_fail(ctx, OIP_E_INVALID, "oip_interband_correlate_units: unit %d has a null pointer or a short pitch", i);
     }
-    return interband_units(ctx, units.data(), n, rows, cols, band_rows, band_cols, out);
+    return interband_units(ctx, CorrKnobs::from_env(), units.data(), n, rows, cols, band_rows, band_cols, out);
 }
 
 extern "C" int oip_interband_correlate(oip_ctx *ctx, const uint16_t *d_pan, long Lp, long prow0, long pn,
@@ -2521,7 +2428,7 @@ extern "C" int oip_interband_correlate(oip_ctx *ctx, const uint16_t *d_pan, long
         }
     }
     std::vector<double> r(12 * units.size() + 12);
-    int rc = interband_units(ctx, units.data(), (int)units.size(), g.base_rows, g.base_cols, g.band_rows, g.band_cols, r.data());
+    int rc = interband_units(ctx, CorrKnobs::from_env(), units.data(), (int)units.size(), g.base_rows, g.base_cols, g.band_rows, g.band_cols, r.data());
     if (rc) return rc;
     OIPGPU::ShiftTableInit(g, out);
     for (size_t j = 0; j < which.size(); ++j) OIPGPU::ShiftTablePut(g, out, which[j], &r[12 * j]);
