@@ -1034,6 +1034,41 @@ int oip_tiff_deflate_decode_u16(oip_ctx *ctx, const uint8_t *d_file, size_t file
                                 const uint64_t *strip_len, long nstrips, long rows, int width, int spp, long rows_per_strip,
                                 int predictor, uint16_t *d_img);
 
+/* ... and written: the strips of a Deflate TIFF product (compression 8, predictor 2) encoded on the device, the mirror of
+ * oip_tiff_lzw_strips_u16 with its arguments, its refusals (OIP_E_INVALID with nothing launched: a null pointer, rows, width or
+ * rows_per_strip below 1, spp other than 1 or 4, a strip above 1 GiB, payload_cap below oip_tiff_deflate_worst_bytes(), a scratch
+ * buffer below oip_tiff_deflate_scratch_bytes() or not 8-byte aligned) and its packing: streams at even offsets of d_payload in
+ * strip order, strip_off / strip_len (host) say where, *payload_bytes ends the last one.  A tile batch is a T-wide image in strips
+ * of T rows.  d_img (2-byte aligned) is read, never written: the predictor-2 differences (sample minus the same channel of the
+ * previous pixel mod 2^16, restarting at every row, little-endian bytes) are made as the input is staged.  Every strip is one zlib
+ * stream from one wave of the device (csrc/tiffdeflate.hip) running the encoder the host writers run (csrc/oip_deflate.h; no libz):
+ *   validity  zlib's inflate and oip_tiff_deflate_decode_u16 accept it and get exactly the strip's bytes.  Header 0x78 0x01 (CM 8,
+ *             CINFO 7, FDICT clear, FCHECK valid), the Adler-32 of the bytes as trailer, BFINAL on the last block, no dictionary;
+ *             lengths 3..258; distances 1..30656, never before the stream's start.
+ *   blocks    dynamic Huffman blocks (BTYPE 2) of at most 16384 input bytes or 2048 matches, their literal/length, distance and
+ *             code-length codes built from the block's own histogram and limited to 15 / 15 / 7 bits; every set sent is complete
+ *             (a set with fewer than two used symbols gets symbols 0 / 1 added, as zlib does).  A block goes out fixed (BTYPE 1)
+ *             or stored (BTYPE 0, neighbours merged up to 65535 bytes) where that is smaller, stored on ties.
+ *   size      never more than n + 5 ceil(n / 65535) + 6 bytes for a strip of n bytes (11 for none): a stream that would pass
+ *             that is written again as stored blocks only.  oip_tiff_deflate_worst_bytes() is that bound for every strip plus
+ *             the padding to even offsets.
+ *   matching  one hashed candidate (4 bytes, 4096 slots, the last position of an earlier 64-position round) and distance 1 per
+ *             position, greedy; see csrc/oip_deflate.h.  A floor, not zlib's ratio on compressible scenes.
+ *   function  the bytes of a stream depend on the strip's bytes alone: not on the launch, the batch, the strip's index, any
+ *             alignment, or on whether the host or the device ran the coder (oip_deflate_stream_host gives the same bytes).
+ * LDS indices are masked or bounded and every store of a stream is bounded by its slot, whatever the image holds.  The scratch
+ * (output slots of one launch, lengths, offsets) does not hold tokens: those stay in LDS.  Synchronises the context's stream. */
+size_t oip_tiff_deflate_worst_bytes(long rows, int width, int spp, long rows_per_strip);
+size_t oip_tiff_deflate_scratch_bytes(long rows, int width, int spp, long rows_per_strip);
+int oip_tiff_deflate_strips_u16(oip_ctx *ctx, const uint16_t *d_img, long rows, int width, int spp, long rows_per_strip,
+                                uint8_t *d_payload, size_t payload_cap, uint64_t *strip_off, uint64_t *strip_len,
+                                size_t *payload_bytes, void *d_scratch, size_t scratch_bytes);
+
+/* The same encoder in its host instantiation, for one stream and without a context: src[0, n) as a zlib stream into dst[0, cap).
+ * Returns the stream's size, or 0 when cap is too small (never when cap >= n + 5 ceil(n / 65535) + 6, or 11 for n = 0), when n is
+ * 0xFFFF0000 or more, or when a pointer is null.  No alignment is asked of either buffer; nothing past either is touched. */
+size_t oip_deflate_stream_host(const uint8_t *src, size_t n, uint8_t *dst, size_t cap);
+
 /* ---- overviews: reduced-resolution levels of a strip or product (`oip overviews`; not in the reference) ---- */
 #define OIP_OVERVIEW_SUFFIX ".ovr"   /* appended to the whole file name, GDAL's external-overview convention */
 

@@ -37,6 +37,8 @@ from .capi import (  # noqa: F401
     noise_fit,
     noise_levels,
     overview_levels,
+    deflate_stored_bound,
+    deflate_stream_host,
     pansharpen_geometry,
     polyfit,
     regfix_fill,

@@ -88,6 +88,10 @@ _SIGS = {
     "oip_tiff_lzw_decode_u16": ([_vp, _vp, _sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _l, _l, _i, _i, _l, _i, _vp], _i),
     "oip_tiff_deflate_decode_u16": ([_vp, _vp, _sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _l, _l, _i, _i, _l, _i, _vp], _i),
     "oip_tiff_lzw_strips_u16": ([_vp, _vp, _l, _i, _i, _l, _vp, _sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_sz), _vp, _sz], _i),
+    "oip_tiff_deflate_worst_bytes": ([_l, _i, _i, _l], _sz),
+    "oip_tiff_deflate_scratch_bytes": ([_l, _i, _i, _l], _sz),
+    "oip_tiff_deflate_strips_u16": ([_vp, _vp, _l, _i, _i, _l, _vp, _sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_sz), _vp, _sz], _i),
+    "oip_deflate_stream_host": ([_vp, _sz, _vp, _sz], _sz),
     "oip_upload_staged": ([_vp, _vp, _vp, _sz, _lp], _i),
     "oip_upload_staged_2d": ([_vp, _vp, _sz, _vp, _sz, _sz, _sz, _lp], _i),
     "oip_download_staged": ([_vp, _vp, _vp, _sz], _i),
@@ -648,6 +652,22 @@ def overview_levels(w: int, h: int) -> int:
     return load_library().oip_overview_levels(w, h)
 
 
+def deflate_stored_bound(n: int) -> int:
+    """the most a zlib stream of the project's encoder takes for n bytes: all of it in stored blocks (include/oip_c.h)"""
+    return n + 5 * ((n + 65534) // 65535) + 6 if n else 11
+
+
+def deflate_stream_host(data, cap: int = None) -> bytes:
+    """`data` as one zlib stream by the host instantiation of the Deflate encoder (include/oip_c.h: oip_deflate_stream_host);
+    cap: the room it is given (default: the stored bound).  b"" where it does not fit."""
+    data = bytes(data)
+    cap = deflate_stored_bound(len(data)) if cap is None else cap
+    src = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
+    dst = (C.c_uint8 * max(cap, 1))()
+    size = load_library().oip_deflate_stream_host(src, len(data), dst, cap)
+    return bytes(dst[:size])
+
+
 MATCH_RECORD_WORDS = 20
 MATCH_NODATA, MATCH_FLAT, MATCH_EDGE, MATCH_WEAK = 1, 2, 4, 8
 
@@ -1033,6 +1053,27 @@ class Context:
         ln = (C.c_uint64 * n)(*[int(v) for v in strip_len])
         self._ck(self.lib.oip_tiff_deflate_decode_u16(self.h, _ptr(d_file), d_file.numel() * d_file.element_size(), off, ln, n, rows, width, spp,
                                                       rows_per_strip, predictor, _ptr(d_img)))
+
+    def tiff_deflate_strips(self, img, rows, width, spp, rows_per_strip, payload, scratch=None, payload_cap=None, scratch_bytes=None):
+        """Deflate strips (zlib streams, predictor 2) of a device image into `payload` (device, uint8); returns (offsets, lengths,
+        payload_bytes).  payload_cap / scratch_bytes: what the call is told the buffers hold, where that is not all of them"""
+        n = (rows + rows_per_strip - 1) // max(rows_per_strip, 1) if rows > 0 else 1
+        off = (C.c_uint64 * max(n, 1))()
+        ln = (C.c_uint64 * max(n, 1))()
+        total = C.c_size_t()
+        if payload_cap is None:
+            payload_cap = payload.numel() * payload.element_size()
+        if scratch_bytes is None:
+            scratch_bytes = scratch.numel() * scratch.element_size() if scratch is not None else 0
+        self._ck(self.lib.oip_tiff_deflate_strips_u16(self.h, _ptr(img), rows, width, spp, rows_per_strip, _ptr(payload), payload_cap, off, ln,
+                                                      C.byref(total), _ptr(scratch) if scratch is not None else None, scratch_bytes))
+        return np.array(off[:], dtype=np.uint64), np.array(ln[:], dtype=np.uint64), total.value
+
+    def tiff_deflate_scratch_bytes(self, rows, width, spp, rows_per_strip):
+        return int(self.lib.oip_tiff_deflate_scratch_bytes(rows, width, spp, rows_per_strip))
+
+    def tiff_deflate_worst_bytes(self, rows, width, spp, rows_per_strip):
+        return int(self.lib.oip_tiff_deflate_worst_bytes(rows, width, spp, rows_per_strip))
 
     def tiff_lzw_scratch_bytes(self, rows, width, spp, rows_per_strip):
         return int(self.lib.oip_tiff_lzw_scratch_bytes(rows, width, spp, rows_per_strip))

@@ -85,14 +85,16 @@ struct stop_watch {
 // Which compression a TIFF product gets.  "reference" (default) = what the reference's libraries do for that product:
 // cv::imwrite -> LZW + horizontal predictor (ALIGNED.TIFF, stitched MSS without -g), GDAL with COMPRESS=LZW
 // PREDICTOR=2 (stitched MSS with -g, imageop.h:471-472), GDAL with default options -> none (stitched PAN,
-// imageop.h:316-328).  --tiff-compress none|lzw (or $OIP_TIFF_COMPRESS) forces one for every product.
-inline int &tiff_policy() { static int p = -1; return p; }       // -1 reference, else TIFF_NONE / TIFF_LZW
+// imageop.h:316-328).  --tiff-compress none|lzw|deflate (or $OIP_TIFF_COMPRESS) forces one for every product; deflate (259 = 8,
+// predictor 2, csrc/oip_deflate.h) is what no reference product has and archive COGs do.
+inline int &tiff_policy() { static int p = -1; return p; }       // -1 reference, else TIFF_NONE / TIFF_LZW / TIFF_DEFLATE
 inline int tiff_compression(int reference_choice)
 {
     if (tiff_policy() < 0) {
         const char *e = getenv("OIP_TIFF_COMPRESS");
         if (e && std::string(e) == "none") return TIFF_NONE;
         if (e && std::string(e) == "lzw") return TIFF_LZW;
+        if (e && std::string(e) == "deflate") return TIFF_DEFLATE;
         return reference_choice;
     }
     return tiff_policy();
@@ -264,11 +266,51 @@ inline bool gpu_lzw()
     return on;
 }
 
-// OIP_TIFF_GPU_DEFLATE=0: the streams of a Deflate input on the host's threads (read_tiff_u16; same image) -- test and A/B knob
+// OIP_TIFF_GPU_DEFLATE=0: the streams of a Deflate input on the host's threads (read_tiff_u16; same image), and those of a Deflate
+// product on the host's threads as well (the encoder of oip_tiff.hpp; same file bytes) -- test and A/B knob
 inline bool gpu_deflate()
 {
     static const bool on = [] { const char *e = getenv("OIP_TIFF_GPU_DEFLATE"); return !(e && atoi(e) == 0); }();
     return on;
+}
+
+// Which way the streams of a Deflate PRODUCT go.  Both ways run the same coder (csrc/oip_deflate.h) and write the same file; what
+// differs is where the time goes.  Measured (profiles/deflate_encode.md, profiles/deflate_encode.json by
+// profiles/deflate_encode_bench.py: 6144 x 20000 x 4 of 12-bit noise; device events, medians of 20 alternating repetitions; the
+// tools' wall time twice each), device against the host's 16 threads:
+//   strips of one row (48 KiB, 20000 streams)   encode 0.351 s against 0.732 s; `oip overviews` 1.01-1.13 s against 1.16-1.39 s: device
+//   tiles of 128 (128 KiB, 7536 streams)        encode 0.352 s against 0.717 s; `oip cog` 1.32-1.54 s against 2.69-2.96 s:       device
+//   tiles of 512 (2 MiB, 480 streams)           encode 0.379 s against 0.784 s in ONE call -- but `oip cog` 4.97-5.03 s against
+//                                               3.35-3.66 s, because it encodes batch by batch: a 256 MiB batch is 120 such
+//                                               streams for 512 resident waves, and a call lasts as long as its longest stream:  host
+// A wave codes 5.5 MB/s, the 16 threads 1.35 GB/s together: a call wins from about 245 streams on and is at its best with 512 or
+// more, so a layout goes to the device by default -- the rule being that the device beats the host by more than the 5 % box-to-box
+// spread of the tool's wall time -- when it has at least 256 streams and a 256 MiB batch holds at least 512 of them (512 KiB a
+// stream: tiles of 256 at 4 samples, of 512 at one; between 128 KiB and 2 MiB nothing was measured, the bound is the model's).
+// OIP_TIFF_GPU_DEFLATE=0 sends everything to the host, =2 everything the device encoder takes to the device (test knob).
+constexpr size_t kDeflateEncodeDeviceMinStreams = 256;
+constexpr uint64_t kDeflateEncodeDeviceMaxStreamBytes = (uint64_t)512 << 10;
+inline bool deflate_encode_on_device(size_t nstreams, uint64_t streamBytes)
+{
+    static const int knob = [] { const char *e = getenv("OIP_TIFF_GPU_DEFLATE"); return e ? atoi(e) : 1; }();
+    if (knob == 0 || streamBytes > ((uint64_t)1 << 30)) return false;
+    if (knob == 2) return true;
+    return nstreams >= kDeflateEncodeDeviceMinStreams && streamBytes <= kDeflateEncodeDeviceMaxStreamBytes;
+}
+
+// the device encoder of a compression's strips (include/oip_c.h): LZW's and Deflate's take the same arguments
+inline size_t tiff_strips_worst_bytes(int compression, long rows, int width, int spp, long rps)
+{
+    return compression == TIFF_DEFLATE ? oip_tiff_deflate_worst_bytes(rows, width, spp, rps) : oip_tiff_lzw_worst_bytes(rows, width, spp, rps);
+}
+inline size_t tiff_strips_scratch_bytes(int compression, long rows, int width, int spp, long rps)
+{
+    return compression == TIFF_DEFLATE ? oip_tiff_deflate_scratch_bytes(rows, width, spp, rps) : oip_tiff_lzw_scratch_bytes(rows, width, spp, rps);
+}
+// whether the strips (or tiles) of a compressed product are encoded on the device
+inline bool tiff_encode_on_device(int compression, size_t nstreams, uint64_t streamBytes)
+{
+    return compression == TIFF_DEFLATE ? deflate_encode_on_device(nstreams, streamBytes) : gpu_lzw();
 }
 
 // the bytes of tile-major samples a batch of tile rows may hold on its way to or from a tiled TIFF (OIP_COG_BATCH_MB: test hook, several
@@ -314,52 +356,52 @@ inline void tiff_rows_from_device(TiffWriterU16 &tw, const uint16_t *d_img, long
     }
 }
 
-// An LZW product whose pixels are in HBM, in file sample order: the strips are encoded where the image is (csrc/tifflzw.hip:
-// a lane per strip) and leave the device packed, as one block that goes into the file behind the header.  The encoder runs on
-// the compute stream: everything the image waits for is ahead of it there.
-// TiffLzwPrep: what a caller that knows the product's geometry before its pixels exist prepares meanwhile (the pipelined
+// An LZW or Deflate product whose pixels are in HBM, in file sample order: the strips are encoded where the image is
+// (csrc/tifflzw.hip: a lane per strip; csrc/tiffdeflate.hip: a wave per strip) and leave the device packed, as one block that goes
+// into the file behind the header.  The encoder runs on the compute stream: everything the image waits for is ahead of it there.
+// TiffStripPrep: what a caller that knows the product's geometry before its pixels exist prepares meanwhile (the pipelined
 // default action, on its product writer's thread while the strip is still being read): the device buffers, and the file with
 // the worst-case size reserved and mapped -- writing a NEW file is bound by the allocation of its pages; the
 // file is cut back to the encoded size afterwards.
-struct TiffLzwPrep {
+struct TiffStripPrep {
     DevBuf<uint8_t> payload, scratch;
     oip_file_sink *sink = nullptr;
     uint64_t payloadAt = 0;
-    void prepare(TiffWriterU16 &tw, const std::string &path, int width, long height, int spp, bool withSink)
+    void prepare(TiffWriterU16 &tw, const std::string &path, int width, long height, int spp, int compression, bool withSink)
     {
         const long rps = tw.rows_per_strip();
-        payload.alloc(oip_tiff_lzw_worst_bytes(height, width, spp, rps));
-        scratch.alloc(oip_tiff_lzw_scratch_bytes(height, width, spp, rps));
+        payload.alloc(tiff_strips_worst_bytes(compression, height, width, spp, rps));
+        scratch.alloc(tiff_strips_scratch_bytes(compression, height, width, spp, rps));
         if (withSink) {
             payloadAt = tw.begin_external_strips();
             Device::get().check(oip_file_sink_open(Device::get().ctx(), path.c_str(), (size_t)payloadAt + payload.n, &sink));
         }
     }
-    ~TiffLzwPrep() { if (sink) oip_file_sink_close(nullptr, sink); }
+    ~TiffStripPrep() { if (sink) oip_file_sink_close(nullptr, sink); }
 };
 
-inline void tiff_lzw_from_device(TiffWriterU16 &tw, const std::string &path, const uint16_t *d_img, int width, long height, int spp,
-                                 TiffLzwPrep *prep = nullptr)
+inline void tiff_strips_from_device(TiffWriterU16 &tw, const std::string &path, const uint16_t *d_img, int width, long height, int spp,
+                                    int compression, TiffStripPrep *prep = nullptr)
 {
     oip_ctx *ctx = Device::get().ctx();
     stop_watch sw;
     const long rps = tw.rows_per_strip();
     const size_t nstrips = (size_t)((height + rps - 1) / rps);
-    TiffLzwPrep own;
+    TiffStripPrep own;
     std::future<int> reserving;
     size_t reserved = 0;
     if (!prep) {
         // nothing was prepared: the product file is reserved and mapped by a helper thread WHILE the strips are being encoded
-        // -- at the size sensor data encodes to (raw + 3 %: LZW does not compress it); a payload that turns out larger goes
-        // the plain way.  (Writing a new file is bound by the allocation of its pages)
+        // -- at the size sensor data encodes to (raw + 3 %: LZW does not compress it, and Deflate's worst case is below that); a
+        // payload that turns out larger goes the plain way.  (Writing a new file is bound by the allocation of its pages)
         prep = &own;
-        const size_t worst = oip_tiff_lzw_worst_bytes(height, width, spp, rps);
+        const size_t worst = tiff_strips_worst_bytes(compression, height, width, spp, rps);
         prep->payload.alloc(worst);
         const size_t raw = (size_t)height * width * spp * 2;
         if (raw >= ((size_t)64 << 20)) {
             reserved = std::min(worst, raw + raw / 32 + ((size_t)64 << 10));
             own.payloadAt = tw.begin_external_strips();
-            TiffLzwPrep *op = &own;
+            TiffStripPrep *op = &own;
             reserving = std::async(std::launch::async, [=] { return oip_file_sink_open(ctx, path.c_str(), (size_t)op->payloadAt + reserved, &op->sink); });
         }
     } else if (prep->sink) {
@@ -368,8 +410,9 @@ inline void tiff_lzw_from_device(TiffWriterU16 &tw, const std::string &path, con
     std::vector<uint64_t> off(nstrips), len(nstrips);
     size_t bytes = 0;
     const double tAlloc = sw.tick();
-    const int rcEncode = oip_tiff_lzw_strips_u16(ctx, d_img, height, width, spp, rps, prep->payload.p, prep->payload.n, off.data(), len.data(), &bytes,
-                                                 prep->scratch.p, prep->scratch.n);
+    const auto encode = compression == TIFF_DEFLATE ? oip_tiff_deflate_strips_u16 : oip_tiff_lzw_strips_u16;
+    const int rcEncode = encode(ctx, d_img, height, width, spp, rps, prep->payload.p, prep->payload.n, off.data(), len.data(), &bytes, prep->scratch.p,
+                                prep->scratch.n);
     if (reserving.valid() && reserving.get() != OIP_OK && prep->sink) { oip_file_sink_close(nullptr, prep->sink); prep->sink = nullptr; }
     Device::get().check(rcEncode);
     const double tEncode = sw.tick();
@@ -394,11 +437,13 @@ inline void tiff_lzw_from_device(TiffWriterU16 &tw, const std::string &path, con
     }
     tw.end_external_strips(off.data(), len.data(), nstrips, bytes);
     const double tWrite = sw.tick();
-    RLOG("TIMING tiff_lzw strips=%zu alloc=%.4f encode=%.4f write=%.4f bytes=%zu prepared=%d", nstrips, tAlloc, tEncode, tWrite, bytes, prep != &own);
+    RLOG("TIMING %s strips=%zu alloc=%.4f encode=%.4f write=%.4f bytes=%zu prepared=%d", compression == TIFF_DEFLATE ? "tiff_deflate" : "tiff_lzw", nstrips,
+         tAlloc, tEncode, tWrite, bytes, prep != &own);
 }
 
 // The pixels of the directory `tw` is writing (width x height x spp u16 in HBM, in file sample order) leave the device:
-// uncompressed as one external payload, LZW strips from the device encoder where gpu_lzw() says so, else through the host's.
+// uncompressed as one external payload, LZW and Deflate strips from the device encoder where tiff_encode_on_device() says so, else
+// through the host's.
 inline void tiff_image_from_device(TiffWriterU16 &tw, const std::string &path, const uint16_t *d_img, int width, long height, int spp,
                                    int compression, long mark)
 {
@@ -407,8 +452,8 @@ inline void tiff_image_from_device(TiffWriterU16 &tw, const std::string &path, c
         const uint64_t at = tw.begin_external_payload();
         Device::get().check(oip_write_device_to_file_at(Device::get().ctx(), d_img, (size_t)height * rowSamples * 2, path.c_str(), (size_t)at, mark));
         tw.end_external_payload();
-    } else if (gpu_lzw()) {
-        tiff_lzw_from_device(tw, path, d_img, width, height, spp);
+    } else if (tiff_encode_on_device(compression, (size_t)((height + tw.rows_per_strip() - 1) / tw.rows_per_strip()), (uint64_t)tw.rows_per_strip() * rowSamples * 2)) {
+        tiff_strips_from_device(tw, path, d_img, width, height, spp, compression);
     } else {
         tiff_rows_from_device(tw, d_img, height, rowSamples, mark);
     }
@@ -436,9 +481,10 @@ inline void write_tiff_from_device(const std::string &path, uint16_t *d_img, int
 
 // The tiles of the directory `tw` is writing (w x h x spp u16 in HBM, in file sample order) leave the device, in batches of tile
 // rows of at most 256 MiB of tile-major samples and at least one tile row (OIP_COG_BATCH_MB: test hook, several batches on a small
-// image): oip_retile_u16 into the batch buffer; uncompressed, the batch itself goes into the file; LZW, every tile is one
-// "strip" of the device encoder (a T-wide image of tile_rows tx T lines in strips of T lines) and the packed payload goes.
-// OIP_TIFF_GPU_LZW=0: the tile-major form comes down and the host coders write it (TiffTiledWriterU16::write_tiles; same bytes).
+// image): oip_retile_u16 into the batch buffer; uncompressed, the batch itself goes into the file; LZW and Deflate, every tile is
+// one "strip" of the device encoder (a T-wide image of tile_rows tx T lines in strips of T lines) and the packed payload goes.
+// OIP_TIFF_GPU_LZW=0, and Deflate where deflate_encode_on_device() says host (on the directory's tile count: the same for every
+// batch size): the tile-major form comes down and the host coders write it (TiffTiledWriterU16::write_tiles; same bytes).
 inline void tiled_image_from_device(TiffTiledWriterU16 &tw, const std::string &path, const uint16_t *d_img, int w, long h, int spp, int T,
                                     int compression)
 {
@@ -449,7 +495,7 @@ inline void tiled_image_from_device(TiffTiledWriterU16 &tw, const std::string &p
     const size_t tileSamples = (size_t)T * T * spp, rowSamples = (size_t)tx * tileSamples, n = (size_t)tx * ty;
     const long batchRows = std::max<long>(1, std::min<long>(ty, (long)(cog_batch_bytes((size_t)256 << 20) / (rowSamples * 2))));
     DevBuf<uint16_t> batch((size_t)batchRows * rowSamples);
-    if (compression == TIFF_LZW && !gpu_lzw()) {
+    if (compression != TIFF_NONE && !tiff_encode_on_device(compression, n, (uint64_t)tileSamples * 2)) {
         std::vector<uint16_t> host(n * tileSamples);
         for (long j0 = 0; j0 < ty; j0 += batchRows) {
             const long nr = std::min(batchRows, ty - j0);
@@ -460,10 +506,11 @@ inline void tiled_image_from_device(TiffTiledWriterU16 &tw, const std::string &p
         return;
     }
     DevBuf<uint8_t> payload, scratch;
-    if (compression == TIFF_LZW) {
-        payload.alloc(oip_tiff_lzw_worst_bytes(batchRows * tx * T, T, spp, T));
-        scratch.alloc(oip_tiff_lzw_scratch_bytes(batchRows * tx * T, T, spp, T));
+    if (compression != TIFF_NONE) {
+        payload.alloc(tiff_strips_worst_bytes(compression, batchRows * tx * T, T, spp, T));
+        scratch.alloc(tiff_strips_scratch_bytes(compression, batchRows * tx * T, T, spp, T));
     }
+    const auto encode = compression == TIFF_DEFLATE ? oip_tiff_deflate_strips_u16 : oip_tiff_lzw_strips_u16;
     std::vector<uint64_t> off(n), len(n);
     const uint64_t at = tw.begin_tiles();
     uint64_t pos = 0;
@@ -481,8 +528,7 @@ inline void tiled_image_from_device(TiffTiledWriterU16 &tw, const std::string &p
             tWrite += sw.tick();
         } else {
             size_t bytes = 0;
-            ck(oip_tiff_lzw_strips_u16(ctx, batch.p, (long)nt * T, T, spp, T, payload.p, payload.n, off.data() + k0, len.data() + k0, &bytes, scratch.p,
-                                       scratch.n));
+            ck(encode(ctx, batch.p, (long)nt * T, T, spp, T, payload.p, payload.n, off.data() + k0, len.data() + k0, &bytes, scratch.p, scratch.n));
             tEncode += sw.tick();
             for (size_t k = 0; k < nt; ++k) off[k0 + k] += pos;
             ck(oip_write_device_to_file_at(ctx, payload.p, bytes, path.c_str(), (size_t)(at + pos), 0));
@@ -491,7 +537,8 @@ inline void tiled_image_from_device(TiffTiledWriterU16 &tw, const std::string &p
         }
     }
     tw.end_tiles(off.data(), len.data(), n, pos);
-    if (compression == TIFF_LZW) RLOG("TIMING tiff_lzw tiles=%zu tile=%d encode=%.4f write=%.4f bytes=%zu", n, T, tEncode, tWrite, (size_t)pos);
+    if (compression != TIFF_NONE)
+        RLOG("TIMING %s tiles=%zu tile=%d encode=%.4f write=%.4f bytes=%zu", compression == TIFF_DEFLATE ? "tiff_deflate" : "tiff_lzw", n, T, tEncode, tWrite, (size_t)pos);
 }
 
 // ---- overviews: <product>.ovr, the reduced-resolution pyramid of a product or strip (not in the reference) ----------------
@@ -1410,9 +1457,15 @@ private:
         uint64_t payloadAt = 0;
         JobThread writer;
         TiffWriterU16 tiff;
-        std::unique_ptr<TiffLzwPrep> lzwPrep;
+        std::unique_ptr<TiffStripPrep> stripPrep;
 
         size_t bytes() const { return (size_t)rows * Wb * MSS_BANDS * 2; }
+        // the strips of a compressed product are encoded on the device
+        bool on_device() const
+        {
+            const long rps = tiff.rows_per_strip();
+            return tiff_encode_on_device(comp, (size_t)((rows + rps - 1) / rps), (uint64_t)rps * Wb * MSS_BANDS * 2);
+        }
         AlignedProduct(const std::string &path_, int Wb_, long rows_)
             : path(path_), comp(tiff_compression(TIFF_LZW)), Wb(Wb_), rows(rows_), tiff(path, Wb, rows, MSS_BANDS, false, comp)
         {
@@ -1430,10 +1483,10 @@ private:
             oip_ctx *ctx = Device::get().ctx();
             // (an empty transfer: the writer's download lane pins its two slots now, not when the product is waiting for them)
             writer.post([=] { Device::get().check(oip_download_staged_after(ctx, nullptr, nullptr, 0, 0)); });
-            if (comp == TIFF_LZW && gpu_lzw()) {
-                // likewise for the LZW product: device buffers of the strip encoder, the file reserved at its worst-case size
-                lzwPrep.reset(new TiffLzwPrep());
-                writer.post([this] { lzwPrep->prepare(tiff, path, Wb, rows, MSS_BANDS, true); });
+            if (comp != TIFF_NONE && on_device()) {
+                // likewise for the LZW or Deflate product: device buffers of the strip encoder, the file reserved at its worst-case size
+                stripPrep.reset(new TiffStripPrep());
+                writer.post([this] { stripPrep->prepare(tiff, path, Wb, rows, MSS_BANDS, comp, true); });
             }
             if (comp == TIFF_NONE) {
                 // the writer thread has nothing to do until the fit is in: it prepares the product file -- header out, blocks
@@ -1460,8 +1513,8 @@ private:
                     sink = nullptr;
                     Device::get().check(oip_file_sink_close(ctx, k));
                     tiff.end_external_payload();
-                } else if (gpu_lzw()) {
-                    tiff_lzw_from_device(tiff, path, img, Wb, rows, MSS_BANDS, lzwPrep.get());
+                } else if (on_device()) {
+                    tiff_strips_from_device(tiff, path, img, Wb, rows, MSS_BANDS, comp, stripPrep.get());
                 } else {
                     tiff_rows_from_device(tiff, img, rows, (size_t)Wb * MSS_BANDS, mark);     // download || encode || write
                 }

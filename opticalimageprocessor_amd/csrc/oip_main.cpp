@@ -48,7 +48,7 @@
 //   oip -v | --version          prints 1.1
 // plus --width N (pixels per PAN line; the reference hard-codes 12288, oipshared.h:28).
 // `auxsep` is outside this build.  TIFF input and output go through oip_tiff.hpp (uncompressed and LZW, with
-// or without the horizontal predictor; Deflate as input only).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
+// or without the horizontal predictor, and Deflate with it: --tiff-compress deflate).  Not the reference's: --fit, --fp16-accumulate, the seam options of stitch
 // (--balance, --balance-lines, --feather and their --valid-min / --valid-max / --min-count; `task` takes them too, with
 // --feather-pan / --feather-mss for its two stitches), --overviews / --levels of stitch and the rrc-calib, quicklook, mtfc,
 // despike, denoise, noise, mask, wallis, mtf, overviews, cog, rescale, regcheck, regfix and pansharpen sub-commands.
@@ -203,7 +203,7 @@ void usage()
     puts("Optical Satellite Image Pre-Processing/Processing Utility (MI355X build)\n"
          "Usage: oip [OPTIONS] [SUBCOMMAND]\n\n"
          "Options:\n"
-         "  -h,--help  -v,--version  --width N  --tiff-compress reference|none|lzw\n"
+         "  -h,--help  -v,--version  --width N  --tiff-compress reference|none|lzw|deflate\n"
          "  --pan FILE --mss FILE [--do-rrc4pan --rrc-pan FILE --write-rrcpan/--no-rrcpan] [--no-rrc4mss]\n"
          "  --rrc-msb1 FILE --rrc-msb2 FILE --rrc-msb3 FILE --rrc-msb4 FILE\n"
          "  --slices N --ibc-sections N --ibc-threshold X --line-offset N --lines-section N --overlap-lines N -k,--keep-leading\n"
@@ -1234,7 +1234,7 @@ static int oip_main(int argc, const char *argv[])
                 if (a == "-h" || a == "--help") { usage(); return 255; }
                 if (a == "-v" || a == "--version") { puts("1.1"); return 255; }
             }
-            // --tiff-compress reference|none|lzw (not in the reference; anywhere on the line)
+            // --tiff-compress reference|none|lzw|deflate (not in the reference; anywhere on the line)
             for (size_t i = 0; i < args.size(); ++i) {
                 std::string v;
                 if (args[i] == "--tiff-compress" && i + 1 < args.size()) { v = args[i + 1]; args.erase(args.begin() + i, args.begin() + i + 2); }
@@ -1243,7 +1243,8 @@ static int oip_main(int argc, const char *argv[])
                 if (v == "reference") tiff_policy() = -1;
                 else if (v == "none") tiff_policy() = TIFF_NONE;
                 else if (v == "lzw") tiff_policy() = TIFF_LZW;
-                else throw cli_error(105, "--tiff-compress: reference, none or lzw expected");
+                else if (v == "deflate") tiff_policy() = TIFF_DEFLATE;
+                else throw cli_error(105, "--tiff-compress: reference, none, lzw or deflate expected");
                 break;
             }
             if (!args.empty() && args[0] == "prestitch") return run_prestitch({args.begin() + 1, args.end()}, width);

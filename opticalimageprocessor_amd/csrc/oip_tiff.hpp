@@ -13,7 +13,8 @@
 // files written here open in cv::imread / GDAL.  Pixel payloads match the reference's; file bytes need not
 // (strip sizes and tag order are the libraries' own).  Strips are encoded / decoded on a few threads.
 // The reader also takes Deflate (259 = 8, or 32946: zlib streams, what COMPRESS=DEFLATE and most archive COGs hold) through
-// the decoder of oip_inflate.h; nothing here writes it.
+// the decoder of oip_inflate.h, and the writers take TIFF_DEFLATE (259 = 8, predictor 2): zlib streams of the encoder of
+// oip_deflate.h, in the strips and tiles LZW has.  No product defaults to it (--tiff-compress deflate asks for it).
 //
 // LZW as TIFF 6.0 section 13 specifies it and libtiff implements it: MSB-first codes of 9..12 bits, ClearCode
 // 256, EndOfInformation 257, first free code 258, every strip starts with ClearCode; the encoder widens the
@@ -41,12 +42,13 @@
 #include <thread>
 #include <vector>
 
+#include "oip_deflate.h"
 #include "oip_inflate.h"
 #include "oip_tiffshared.h"
 
 namespace OIPGPU {
 
-// (TIFF_DEFLATE is read, never written: 8 is Adobe Deflate, and its older number 32946 is read as the same thing)
+// (TIFF_DEFLATE: 8, Adobe Deflate, is what is written; its older number 32946 is read as the same thing)
 enum TiffCompression { TIFF_NONE = 1, TIFF_LZW = 5, TIFF_DEFLATE = 8 };
 
 namespace tiffdetail {
@@ -279,9 +281,13 @@ inline void swap_row(const uint16_t *src, uint16_t *dst, size_t width)
     }
 }
 
-// One strip or tile of an LZW file: `rows` rows of `width` pixels from src into buf (swap: in OpenCV's order), differenced along
-// each row (predictor 2) and encoded into dst (lzw_worst of the chunk's bytes); returns the encoded size.
-inline size_t encode_chunk(const uint16_t *src, long rows, size_t width, int spp, bool swap, uint16_t *buf, uint8_t *dst)
+// the most an encoded strip or tile of n bytes takes (LZW: oip_tiffshared.h; Deflate: all of it in stored blocks, oip_deflate.h)
+inline size_t chunk_worst(size_t n, int compression) { return compression == TIFF_DEFLATE ? oipdeflate::stored_bound(n) : lzw_worst(n); }
+
+// One strip or tile of an LZW or Deflate file: `rows` rows of `width` pixels from src into buf (swap: in OpenCV's order), differenced
+// along each row (predictor 2) and encoded into dst (chunk_worst of the chunk's bytes); returns the encoded size.  Deflate: the host
+// instantiation of the coder the device runs (csrc/oip_deflate.h), so a file is the same bytes whoever encoded it.
+inline size_t encode_chunk(const uint16_t *src, long rows, size_t width, int spp, bool swap, uint16_t *buf, uint8_t *dst, int compression = TIFF_LZW)
 {
     const size_t rw = width * spp;
     for (long r = 0; r < rows; ++r) {
@@ -289,7 +295,13 @@ inline size_t encode_chunk(const uint16_t *src, long rows, size_t width, int spp
         if (swap) swap_row(src + (size_t)r * rw, d, width); else memcpy(d, src + (size_t)r * rw, rw * 2);
         predictor2_encode(d, width, spp);
     }
-    return lzw_encode_to((const uint8_t *)buf, (size_t)rows * rw * 2, dst);
+    const size_t n = (size_t)rows * rw * 2;
+    if (compression != TIFF_DEFLATE) return lzw_encode_to((const uint8_t *)buf, n, dst);
+    thread_local std::unique_ptr<oipdeflate::Shared> work;
+    if (!work) work.reset(new oipdeflate::Shared);
+    const size_t size = oipdeflate::deflate_host((const uint8_t *)buf, n, dst, oipdeflate::stored_bound(n), work.get());
+    if (!size) throw std::runtime_error("Deflate encoder: a strip or tile of 4 GiB or more");
+    return size;
 }
 
 // n bytes at offset `at` of fd, however many calls it takes; `who` names the writer in the error
@@ -307,7 +319,12 @@ inline void pwrite_all(int fd, const void *p, size_t n, uint64_t at, const char 
 // Classic TIFF offsets are 32 bit.  LZW can also GROW a chunk: at worst one 12-bit code per byte (x1.5), so the choice is made on
 // the worst case of the payload of all directories and a classic file can never overflow half-way (BigTIFF is always valid): the
 // header, page-aligned payload, the chunk tables, the directories.  OIP_TIFF_FORCE_BIG: test hook, BigTIFF at any size.
-inline uint64_t worst_payload(uint64_t bytes, int compression) { return compression == TIFF_LZW ? bytes + bytes / 2 : bytes; }
+// Deflate: a chunk of c bytes is at most c + 5 ceil(c / 65535) + 6 (stored blocks, oip_deflate.h) plus a byte to the next even offset.
+inline uint64_t worst_payload(uint64_t bytes, int compression, uint64_t nchunks = 1)
+{
+    if (compression == TIFF_DEFLATE) return bytes + 5 * (bytes / 65535 + nchunks) + 12 * nchunks;
+    return compression == TIFF_LZW ? bytes + bytes / 2 : bytes;
+}
 inline bool needs_bigtiff(uint64_t worst, uint64_t nchunks)
 {
     bool big = worst + nchunks * 16 + 16384 > 0xFFFFF000ull;
@@ -350,7 +367,7 @@ struct TiffDirectory {
         if (reduced) tags.push_back({254, LONG, 1, 1});
         if (!tile) tags.insert(tags.end(), {{273, otype, nchunks, offsets}, {278, LONG, 1, rows_per_strip}, {279, otype, nchunks, counts}});
         else tags.insert(tags.end(), {{322, LONG, 1, tile}, {323, LONG, 1, tile}, {324, otype, nchunks, offsets}, {325, otype, nchunks, counts}});
-        if (compression == TIFF_LZW) tags.push_back({317, SHORT, 1, 2});   // horizontal predictor
+        if (compression == TIFF_LZW || compression == TIFF_DEFLATE) tags.push_back({317, SHORT, 1, 2});   // horizontal predictor
         if (spp == 4) tags.push_back({338, SHORT, 1, 2});                  // unassociated alpha
         if (sample_format) tags.push_back({339, SHORT, n, formatAt ? formatAt : shorts(spp, 1)});
         std::sort(tags.begin(), tags.end(), [](const Tag &a, const Tag &b) { return a.id < b.id; });
@@ -418,7 +435,8 @@ template <typename F> inline void read_directory(const TiffSource &src, const ch
 class TiffWriterU16 {
 public:
     // rows are appended top to bottom with write_rows(); close() writes the directory.
-    // compression: TIFF_NONE, or TIFF_LZW (always with predictor 2, what cv::imwrite and the reference's GDAL call use)
+    // compression: TIFF_NONE, TIFF_LZW (always with predictor 2, what cv::imwrite and the reference's GDAL call use) or
+    // TIFF_DEFLATE (259 = 8, predictor 2 as well: zlib streams of csrc/oip_deflate.h, in the strips LZW has)
     // overview_levels = n > 0: the file is the external overview file (<product>.ovr) of a width x height product instead --
     // n directories, directory k the pyramid's level k + 1 (each half the one before, rounded up), every one with the tags of a
     // product of its geometry plus NewSubfileType (254) = 1, chained by their next-directory offsets.  The rows of level 1 come
@@ -428,7 +446,7 @@ public:
     {
         mLevelsLeft = overview_levels;
         if (width <= 0 || height <= 0 || (spp != 1 && spp != 4) || overview_levels < 0) throw std::invalid_argument("TiffWriterU16: bad geometry");
-        if (compression != TIFF_NONE && compression != TIFF_LZW) throw std::invalid_argument("TiffWriterU16: unsupported compression");
+        if (compression != TIFF_NONE && compression != TIFF_LZW && compression != TIFF_DEFLATE) throw std::invalid_argument("TiffWriterU16: unsupported compression");
         // classic or BigTIFF (tiffdetail::needs_bigtiff): on the worst case of the payload; an overview file: of the sum of its levels
         size_t worst = 0, nstrips = 0;
         if (overview_levels == 0) {
@@ -568,13 +586,14 @@ public:
         if (fseeko(mF, (off_t)mPos, SEEK_SET) != 0) throw std::runtime_error("TiffWriterU16: seek failed");
     }
 
-    // LZW files whose strips were encoded elsewhere (the device: oip_tiff_lzw_strips_u16 on an image in file sample order):
+    // LZW and Deflate files whose strips were encoded elsewhere (the device: oip_tiff_lzw_strips_u16 / oip_tiff_deflate_strips_u16 on
+    // an image in file sample order):
     // the packed strips are written by the caller at the offset begin_external_strips() returns -- where write_rows() would
     // have put the first one -- and end_external_strips() takes their offsets inside that block and their sizes.
     long rows_per_strip() const { return mRowsPerStrip; }
     uint64_t begin_external_strips()
     {
-        if (mComp != TIFF_LZW || mRowsDone != 0) throw std::logic_error("TiffWriterU16: external strips need an empty LZW file");
+        if (mComp == TIFF_NONE || mRowsDone != 0) throw std::logic_error("TiffWriterU16: external strips need an empty LZW or Deflate file");
         if (mSwap) throw std::logic_error("TiffWriterU16: external strips are written in file sample order");
         if (fflush(mF) != 0) throw std::runtime_error("TiffWriterU16: write failed");
         return mPos;
@@ -601,16 +620,18 @@ private:
         mH = height;
         mRowBytes = (size_t)width * mSpp * 2;
         const size_t data = mRowBytes * (size_t)height;
-        *worst += tiffdetail::worst_payload(data, mComp);
         // Strips: 8 MiB uncompressed (their offsets are arithmetic); LZW: whole rows up to 64 KiB (cv::imwrite and GDAL write 8
         // KB strips; libtiff's table restarts every ~5 KB of sensor data, so the strip size does not change the ratio).  An
         // LZW strip is the unit of parallel work of whoever encodes it: a lane of the device encoder (csrc/tifflzw.hip: 25000
         // strips for a 7500 x 25000 x 4 product), a thread of the host encoder below -- both write the same strips, so a file
         // is the same bytes whoever encoded it.
-        mRowsPerStrip = mComp == TIFF_LZW ? (long)((64u << 10) / mRowBytes) : (long)((8u << 20) / mRowBytes);
+        // Deflate takes the same strips: a stream is a wave of the device encoder (csrc/tiffdeflate.hip).
+        mRowsPerStrip = mComp != TIFF_NONE ? (long)((64u << 10) / mRowBytes) : (long)((8u << 20) / mRowBytes);
         if (mRowsPerStrip < 1) mRowsPerStrip = 1;
         if (mRowsPerStrip > height) mRowsPerStrip = height;
-        *nstrips += ((size_t)height + mRowsPerStrip - 1) / mRowsPerStrip;
+        const size_t ns = ((size_t)height + mRowsPerStrip - 1) / mRowsPerStrip;
+        *worst += tiffdetail::worst_payload(data, mComp, ns);
+        *nstrips += ns;
     }
 
     // the strip tables and the directory of the image whose rows are complete, linked behind the header or the previous directory
@@ -655,7 +676,7 @@ private:
     {
         const size_t rw = (size_t)mW * mSpp;
         const long nstrips = (nrows + mRowsPerStrip - 1) / mRowsPerStrip;
-        const size_t stripBytes = (size_t)mRowsPerStrip * rw * 2, worst = tiffdetail::lzw_worst(stripBytes);
+        const size_t stripBytes = (size_t)mRowsPerStrip * rw * 2, worst = tiffdetail::chunk_worst(stripBytes, mComp);
         Arena &ar = mArena[mArenaCur];
         mArenaCur ^= 1;
         if (ar.cap < (size_t)nstrips * worst) { ar.p.reset(new uint8_t[(size_t)nstrips * worst]); ar.cap = (size_t)nstrips * worst; }
@@ -666,7 +687,7 @@ private:
             const long r0 = (long)k * mRowsPerStrip;
             const long n = std::min<long>(mRowsPerStrip, nrows - r0);
             if (!mScratch[(size_t)t]) mScratch[(size_t)t].reset(new uint16_t[(size_t)mRowsPerStrip * rw]);
-            len[k] = tiffdetail::encode_chunk(rows + (size_t)r0 * rw, n, (size_t)mW, mSpp, mSwap, mScratch[(size_t)t].get(), base + k * worst);
+            len[k] = tiffdetail::encode_chunk(rows + (size_t)r0 * rw, n, (size_t)mW, mSpp, mSwap, mScratch[(size_t)t].get(), base + k * worst, mComp);
         });
         // the batch goes to the file on a thread of its own (positioned writes) while the caller brings down and encodes the
         // next one; the previous batch's write is waited for -- and its error raised -- first

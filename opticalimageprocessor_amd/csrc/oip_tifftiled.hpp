@@ -13,9 +13,9 @@
 // fetches ranges gets them with its first request.  (GDAL's COG driver writes the payloads smallest level first and a ghost
 // header; this writer does neither.)
 // Tags: those TiffWriterU16 writes for a product of the same geometry and spp, with 322 TileWidth, 323 TileLength, 324
-// TileOffsets, 325 TileByteCounts in place of 273 / 278 / 279; 317 = 2 with LZW.  A tile is the T x T x spp block of the
+// TileOffsets, 325 TileByteCounts in place of 273 / 278 / 279; 317 = 2 with LZW and Deflate.  A tile is the T x T x spp block of the
 // tile-major form (include/oip_c.h: oip_retile_u16) -- edge tiles replicate the last column and line --, uncompressed or, one
-// LZW stream per tile, with predictor 2 along each tile row.  Tiles start on even offsets.
+// LZW or zlib (Deflate, csrc/oip_deflate.h) stream per tile, with predictor 2 along each tile row.  Tiles start on even offsets.
 #pragma once
 
 #include "oip_tiff.hpp"
@@ -29,7 +29,7 @@ public:
     {
         if (width <= 0 || height <= 0 || (spp != 1 && spp != 4) || levels < 0 || levels > 16 || tile < 16 || tile > 1024 || tile % 16 != 0)
             throw std::invalid_argument("TiffTiledWriterU16: bad geometry");
-        if (compression != TIFF_NONE && compression != TIFF_LZW) throw std::invalid_argument("TiffTiledWriterU16: unsupported compression");
+        if (compression != TIFF_NONE && compression != TIFF_LZW && compression != TIFF_DEFLATE) throw std::invalid_argument("TiffTiledWriterU16: unsupported compression");
         mTileBytes = (uint64_t)tile * tile * spp * 2;
         uint64_t worst = 0, ntiles = 0;
         for (int k = 0; k <= levels; ++k) {
@@ -118,7 +118,7 @@ public:
             pos = d.n * mTileBytes;
             tiffdetail::pwrite_all(fd, tileMajor, (size_t)pos, at, "TiffTiledWriterU16");
         } else {
-            const size_t tileSamples = (size_t)(mTileBytes / 2), worst = tiffdetail::lzw_worst((size_t)mTileBytes);
+            const size_t tileSamples = (size_t)(mTileBytes / 2), worst = tiffdetail::chunk_worst((size_t)mTileBytes, mComp);
             const uint64_t batch = std::max<uint64_t>(2 * (uint64_t)tiffdetail::worker_count(), ((uint64_t)64 << 20) / mTileBytes + 1);
             std::unique_ptr<uint8_t[]> arena(new uint8_t[(size_t)std::min(batch, d.n) * worst]);
             std::vector<std::unique_ptr<uint16_t[]>> scratch((size_t)tiffdetail::worker_count());
@@ -127,7 +127,7 @@ public:
                 tiffdetail::parallel_for_t((size_t)kn, [&](size_t j, int t) {
                     if (!scratch[(size_t)t]) scratch[(size_t)t].reset(new uint16_t[tileSamples]);
                     len[(size_t)(k0 + j)] = tiffdetail::encode_chunk(tileMajor + (size_t)(k0 + j) * tileSamples, mT, (size_t)mT, mSpp, false,
-                                                                     scratch[(size_t)t].get(), arena.get() + j * worst);
+                                                                     scratch[(size_t)t].get(), arena.get() + j * worst, mComp);
                 });
                 for (uint64_t j = 0; j < kn; ++j) {
                     if (pos & 1) ++pos;                                 // tiles start on even offsets (the gap reads as zero)

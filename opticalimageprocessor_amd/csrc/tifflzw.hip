@@ -17,9 +17,10 @@
 // Every step is a dependent 8-byte load from a 2 GB region: the kernel is bound by HBM latency, not bandwidth -- ~1 us a
 // byte, 60 ms for any number of strips up to the 32768 a launch takes -- which is still eight times what the host cores did.
 // The encoded strips land in fixed slots (worst case: 1.5 bytes per byte); a second kernel packs them behind one another
-// (even offsets, as the host writer places them) so that the payload leaves the device as one block.
+// (even offsets, as the host writer places them; oip_tiffpack.h) so that the payload leaves the device as one block.
 #include "oip_internal.h"
 #include "oip_tiffdecode.h"
+#include "oip_tiffpack.h"
 #include "oip_tiffshared.h"
 
 #include <cstdint>
@@ -165,25 +166,6 @@ __global__ __launch_bounds__(64) void lzw_strips_kernel(LzwJob j)
     if (s.nbits > 0) s.out[s.o++] = (uint8_t)(s.acc << (8 - s.nbits));
     j.len[k] = s.o;
 }
-
-// strip k of this launch: slot -> payload + off[k] (even), (len + 1) / 2 two-byte units; an odd length's pad byte is zero
-__global__ __launch_bounds__(256) void lzw_pack_kernel(const uint8_t *__restrict__ slots, size_t slot_bytes, const unsigned *__restrict__ len,
-                                                       const unsigned long long *__restrict__ off, long strip0, long nstrips,
-                                                       uint8_t *__restrict__ payload)
-{
-    const long k = strip0 + blockIdx.x;
-    if (k >= nstrips) return;
-    const unsigned n = len[k];
-    const uint16_t *src = reinterpret_cast<const uint16_t *>(slots + (size_t)blockIdx.x * slot_bytes);
-    uint16_t *dst = reinterpret_cast<uint16_t *>(payload + off[k]);
-    const unsigned units = (n + 1) / 2;
-    for (unsigned i = threadIdx.x; i < units; i += 256) {
-        uint16_t v = src[i];
-        if (2 * i + 1 >= n) v &= 0x00ffu;
-        dst[i] = v;
-    }
-}
-
 
 // ---- the other direction: the LZW strips of a TIFF file decoded on the device ------------------------------------------------
 // cv::imread of the two ALIGNED.TIFF inputs of the MSS stitch (imageop.h:380-388) decodes on the host; here the strips' bytes go
@@ -386,7 +368,7 @@ extern "C" int oip_tiff_lzw_strips_u16(oip_ctx *ctx, const uint16_t *d_img, long
         OIP_LZW_HIP(hipMemcpyAsync(d_off + s0, off.data() + s0, (size_t)ns * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
         {
             OipProfScope prof(ctx, "lzw_pack_kernel");
-            hipLaunchKernelGGL(lzw_pack_kernel, dim3((unsigned)ns), dim3(256), 0, ctx->stream, d_slots, slot_bytes, d_len, d_off, s0, nstrips, d_payload);
+            hipLaunchKernelGGL(tiff_pack_kernel, dim3((unsigned)ns), dim3(256), 0, ctx->stream, d_slots, slot_bytes, d_len, d_off, s0, nstrips, d_payload);
         }
         OIP_LZW_HIP(hipGetLastError());
         OIP_LZW_HIP(hipStreamSynchronize(ctx->stream));                          // the slots and off[] are reused by the next launch

@@ -1,0 +1,191 @@
+"""GPU: the tools writing Deflate TIFFs (--tiff-compress deflate, $OIP_TIFF_COMPRESS=deflate).  `oip cog` writes the COG that
+_cog_ref.py and _overview_ref.py describe with zlib streams as tiles; strip products (overviews, denoise, the default action, stitch)
+hold the pixels of their uncompressed runs; a file is the same bytes whoever encoded its streams -- the device (OIP_TIFF_GPU_DEFLATE=2
+sends every layout the device encoder takes there; by default files of fewer than 256 streams or of streams above 512 KiB go to the host's threads,
+csrc/oip_host.hpp), the host (=0) -- and however it was cut into batches and blocks; the tools read back what they wrote; and a run
+without the option writes what it wrote before the option took `deflate`.  The reader is tests/_deflate_write_ref.py (Python's zlib)."""
+import hashlib
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import _deflate_write_ref as R
+import _overview_ref as ovr
+import _synth
+from _tiff import write_tiff_u16
+
+pytestmark = pytest.mark.gpu
+OIP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "opticalimageprocessor_amd", "lib", "oip")
+DEVICE, HOST = {"OIP_TIFF_GPU_DEFLATE": "2"}, {"OIP_TIFF_GPU_DEFLATE": "0"}
+
+
+def _run(tool, args, cwd, rc=0, **env):
+    env = dict(os.environ, LOGFILE=os.path.join(cwd, "oip.log"), **env)
+    r = subprocess.run([OIP] + ([tool] if tool else []) + args, cwd=cwd, env=env, capture_output=True, text=True)
+    assert r.returncode == rc, (tool, args, r.stdout + r.stderr)
+    return r
+
+
+def _sha(path):
+    with open(path, "rb") as f:
+        return hashlib.sha256(f.read()).hexdigest()
+
+
+@pytest.fixture(scope="module")
+def products(tmp_path_factory):
+    """tests/test_gpu_cog_cli.py's: M.TIFF, 700 x 900 of 4 samples; P.TIFF, 1000 x 600 of 1 sample; both in strips, uncompressed"""
+    d = str(tmp_path_factory.mktemp("deflate_encode_cli"))
+    m, p = R.blocks(900, 700, 4, 1, 28), R.blocks(600, 1000, 1, 2)
+    write_tiff_u16(os.path.join(d, "M.TIFF"), m.reshape(900, 700, 4))
+    write_tiff_u16(os.path.join(d, "P.TIFF"), p)
+    return d, m, p
+
+
+@pytest.mark.parametrize("name", ["M", "P"])
+def test_cog_with_deflate_tiles(products, name):
+    d, m, p = products
+    img, spp = (m, 4) if name == "M" else (p, 1)
+    want = [img] + ovr.pyramid(img, 2, 1, spp)
+    T = 128 if spp == 4 else 256                                   # the default tile
+    dflt = ["cog", name + ".TIFF", "--force", "--tiff-compress", "deflate", "-o"]
+    r = _run(None, dflt + ["d.COG.TIFF"], d, **DEVICE)
+    assert "TIMING tiff_deflate tiles=" in r.stdout
+    R.assert_is_deflate_cog(os.path.join(d, "d.COG.TIFF"), want, spp, T, big=False)
+    # the host's threads, the default route, and tile rows one batch each write the same file
+    r = _run(None, dflt + ["h.COG.TIFF"], d, **HOST)
+    assert "TIMING tiff_deflate" not in r.stdout
+    _run(None, dflt + ["p.COG.TIFF"], d)
+    _run(None, dflt + ["b.COG.TIFF"], d, OIP_COG_BATCH_MB="1", **DEVICE)
+    assert _sha(os.path.join(d, "d.COG.TIFF")) == _sha(os.path.join(d, "h.COG.TIFF")) == _sha(os.path.join(d, "p.COG.TIFF")) == _sha(os.path.join(d, "b.COG.TIFF"))
+    # another tile and more levels; BigTIFF
+    opt = ["cog", name + ".TIFF", "--force", "--tiff-compress", "deflate", "--tile", "64", "--levels", "3", "-o"]
+    _run(None, opt + ["t64.COG.TIFF"], d, **DEVICE)
+    R.assert_is_deflate_cog(os.path.join(d, "t64.COG.TIFF"), [img] + ovr.pyramid(img, 3, 1, spp), spp, 64)
+    _run(None, opt + ["t64h.COG.TIFF"], d, **HOST)
+    _run(None, opt + ["t64b.COG.TIFF"], d, OIP_COG_BATCH_MB="1")
+    assert _sha(os.path.join(d, "t64.COG.TIFF")) == _sha(os.path.join(d, "t64h.COG.TIFF")) == _sha(os.path.join(d, "t64b.COG.TIFF"))
+    _run(None, dflt + ["big.COG.TIFF"], d, OIP_TIFF_FORCE_BIG="1", **DEVICE)
+    R.assert_is_deflate_cog(os.path.join(d, "big.COG.TIFF"), want, spp, T, big=True)
+    _run(None, dflt + ["bigh.COG.TIFF"], d, OIP_TIFF_FORCE_BIG="1", **HOST)
+    assert _sha(os.path.join(d, "big.COG.TIFF")) == _sha(os.path.join(d, "bigh.COG.TIFF"))
+
+
+@pytest.mark.parametrize("name", ["M", "P"])
+def test_strip_products_with_deflate(products, name):
+    """`oip overviews` and `oip denoise`: the pixels of the --tiff-compress none run behind 259 = 8 and 317 = 2, and one file
+    whichever route encoded it and however the rows came down"""
+    d, m, p = products
+    spp = 4 if name == "M" else 1
+    for tool, args, out in (("overviews", [name + ".TIFF", "--force"], "o.ovr"), ("denoise", [name + ".TIFF", "--sigma", "37.3", "--radius", "1", "--force"], "n.TIFF")):
+        _run(tool, args + ["--tiff-compress", "none", "-o", "none." + out], d)
+        r = _run(tool, args + ["--tiff-compress", "deflate", "-o", "dev." + out], d, **DEVICE)
+        assert "TIMING tiff_deflate strips=" in r.stdout
+        _run(tool, args + ["--tiff-compress", "deflate", "-o", "host." + out], d, **HOST)
+        _run(tool, args + ["--tiff-compress", "deflate", "-o", "chunk." + out], d, OIP_TIFF_CHUNK_MB="1", **HOST)
+        _run(tool, args + ["--tiff-compress", "deflate", "-o", "dflt." + out], d, OIP_TIFF_CHUNK_MB="1")
+        shas = {_sha(os.path.join(d, k + "." + out)) for k in ("dev", "host", "chunk", "dflt")}
+        assert len(shas) == 1, (tool, name)
+        got, _ = R.read_dirs(os.path.join(d, "dev." + out))
+        want, _ = R.read_dirs(os.path.join(d, "none." + out))
+        assert len(got) == len(want) and len(got) >= 1
+        for g, w in zip(got, want):
+            R.assert_deflate_tags(g, spp)
+            assert w["tags"][259] == [1] and np.array_equal(g["img"], w["img"]) and g["img"].any(), (tool, name)
+
+
+def _csv(path, kb):
+    with open(path, "w") as f:
+        f.write("1\n%d\n0\n" % len(kb))
+        for k, b in kb:
+            f.write("%.6f , %.4f\n" % (k, b))
+
+
+def test_default_action_with_deflate(tmp_path):
+    """the small strip of tests/test_gpu_cli.py (a 256 x 8156 x 4 product: 255 strips of 32 rows, one short of the device's default,
+    so OIP_TIFF_GPU_DEFLATE=2 sends it there) with $OIP_TIFF_COMPRESS=deflate: the step-by-step run (OIP_PIPELINE=0) with its strips
+    from the host's threads and the pipelined one with its prepared device buffers write one file, which holds the pixels of the
+    `none` run"""
+    W, L = 1024, 33024
+    pan, bands = _synth.pan_mss(L, W, [(2, -1), (1, 1), (-1, -2), (-2, 1)], seed=6)
+    bil = np.concatenate(bands, axis=1)
+    out = {}
+    for comp, pl, knob in (("none", "1", "1"), ("deflate", "0", "0"), ("deflate", "1", "2")):
+        d = os.path.join(str(tmp_path), comp + pl)
+        os.makedirs(d)
+        pan.tofile(os.path.join(d, "T_PAN.RAW")); bil.tofile(os.path.join(d, "T_MSS.RAW"))
+        args = ["--width", str(W), "--pan", "T_PAN.RAW", "--mss", "T_MSS.RAW", "--slices", "8", "--ibc-sections", "1", "--ibc-threshold", "0",
+                "--lines-section", "3000", "--overlap-lines", "100"]
+        for b in range(4):
+            _csv(os.path.join(d, "MSS.B%d.csv" % (b + 1)), _synth.lut(W // 4, 20 + b))
+            args += ["--rrc-msb%d" % (b + 1), "MSS.B%d.csv" % (b + 1)]
+        r = _run(None, args, d, OIP_TIFF_COMPRESS=comp, OIP_PIPELINE=pl, OIP_TIFF_GPU_DEFLATE=knob)
+        assert ("TIMING default_action pipelined=1" in r.stdout) == (pl == "1")
+        assert ("TIMING tiff_deflate strips=" in r.stdout and "prepared=1" in r.stdout) == (comp == "deflate" and pl == "1"), r.stdout[-2000:]
+        out[(comp, pl)] = os.path.join(d, "T_MSS.ALIGNED.TIFF")
+    assert _sha(out[("deflate", "0")]) == _sha(out[("deflate", "1")])
+    got, _ = R.read_dirs(out[("deflate", "1")])
+    want, _ = R.read_dirs(out[("none", "1")])
+    R.assert_deflate_tags(got[0], 4)
+    assert len(got) == 1 and got[0]["tags"][278] == [32] and np.array_equal(got[0]["img"], want[0]["img"]) and want[0]["img"].any()
+
+
+OUTS = {"quicklook": "ql.TIFF", "overviews": "o.ovr", "cog": "c.TIFF"}
+
+
+@pytest.mark.parametrize("name", ["M", "P"])
+def test_the_tools_read_what_they_wrote(products, name):
+    """quicklook, overviews and cog fed the Deflate COG write the bytes they write for the uncompressed strip TIFF; a stitch of two
+    Deflate products, written as Deflate, decodes to the pixels of the uncompressed stitch"""
+    d, m, p = products
+    _run("cog", [name + ".TIFF", "-o", name + ".dcog.TIFF", "--force", "--tiff-compress", "deflate", "--tile", "16", "--levels", "0"], d)    # >= 256 tiles: read on the device
+    _run("cog", [name + ".TIFF", "-o", name + ".dcog128.TIFF", "--force", "--tiff-compress", "deflate", "--tile", "128"], d)                 # a few tiles: read on the host
+    for tool, out in OUTS.items():
+        _run(tool, [name + ".TIFF", "-o", "want." + out, "--force"], d)
+        for src in (name + ".dcog.TIFF", name + ".dcog128.TIFF"):
+            _run(tool, [src, "-o", "got." + out, "--force"], d)
+            assert _sha(os.path.join(d, "got." + out)) == _sha(os.path.join(d, "want." + out)), (tool, src)
+    if name == "M":
+        _run("denoise", ["M.TIFF", "--sigma", "37.3", "--radius", "1", "--force", "--tiff-compress", "deflate", "-o", "A.TIFF"], d)
+        _run("denoise", ["M.TIFF", "--sigma", "80", "--radius", "1", "--force", "--tiff-compress", "deflate", "-o", "B.TIFF"], d, **DEVICE)
+        _run("denoise", ["M.TIFF", "--sigma", "37.3", "--radius", "1", "--force", "--tiff-compress", "none", "-o", "An.TIFF"], d)
+        _run("denoise", ["M.TIFF", "--sigma", "80", "--radius", "1", "--force", "--tiff-compress", "none", "-o", "Bn.TIFF"], d)
+        _run("stitch", ["--image1", "A.TIFF", "--image2", "B.TIFF", "--fold-cols", "12", "--tiff-compress", "deflate", "-o", "st.TIFF"], d, **DEVICE)
+        _run("stitch", ["--image1", "An.TIFF", "--image2", "Bn.TIFF", "--fold-cols", "12", "--tiff-compress", "none", "-o", "stn.TIFF"], d)
+        got, _ = R.read_dirs(os.path.join(d, "st.TIFF"))
+        want, _ = R.read_dirs(os.path.join(d, "stn.TIFF"))
+        R.assert_deflate_tags(got[0], 4)
+        assert want[0]["tags"][259] == [1] and np.array_equal(got[0]["img"], want[0]["img"]) and got[0]["img"].shape == (900, 4 * 2 * (700 - 6))
+
+
+def test_an_unknown_compression_is_refused_with_the_four_values_named(products):
+    d = products[0]
+    r = _run("cog", ["M.TIFF", "--tiff-compress", "zip", "-o", "zip.TIFF"], d, rc=105)
+    text = r.stdout + r.stderr
+    assert all(v in text for v in ("reference", "none", "lzw", "deflate")) and not os.path.exists(os.path.join(d, "zip.TIFF"))
+    r = _run("cog", ["M.TIFF", "-o", "env.TIFF", "--force"], d, OIP_TIFF_COMPRESS="deflate")
+    assert R.read_dirs(os.path.join(d, "env.TIFF"))[0][0]["tags"][259] == [8]
+
+
+# what these commands wrote when built from the parent commit 3039788 (computed on an MI355X with that build)
+PARENT_SHA = {
+    "cog M": "138e98aca01a912edfdea0abba6e197d2d9b126dcb93aed0a55ab359bfbf7abf",
+    "cog P": "50300695ec70b3dfc8d887f14f25a444ecb39cc741d3fd0c891de0643b70e64c",
+    "overviews M": "1c68e0c266b9723269df8b6b86d5f78778e8f22611d31838023b995e171d39b9",
+    "denoise M": "65f4fda5abafb9e277f8024ec60fa89f40ffeb89931d5a20d0a8a38c2471a9ad",
+}
+
+
+def test_no_default_changed(products):
+    """without --tiff-compress every product is byte for byte what the parent commit (3039788) wrote: the SHA-256 of `oip cog`,
+    `oip overviews` and `oip denoise` on the fixture's products, computed once with that commit's build on an MI355X"""
+    d = products[0]
+    _run("cog", ["M.TIFF", "-o", "same.M.COG.TIFF", "--force"], d)
+    _run("cog", ["P.TIFF", "-o", "same.P.COG.TIFF", "--force"], d)
+    _run("overviews", ["M.TIFF", "-o", "same.M.ovr", "--force"], d)
+    _run("denoise", ["M.TIFF", "--sigma", "37.3", "--radius", "1", "-o", "same.M.DN.TIFF", "--force"], d)
+    got = {"cog M": _sha(os.path.join(d, "same.M.COG.TIFF")), "cog P": _sha(os.path.join(d, "same.P.COG.TIFF")),
+           "overviews M": _sha(os.path.join(d, "same.M.ovr")), "denoise M": _sha(os.path.join(d, "same.M.DN.TIFF"))}
+    print(got)
+    assert got == PARENT_SHA
