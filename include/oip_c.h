@@ -994,7 +994,10 @@ int oip_mtf_tv_slack(double sigma_ref);
  * The encoded strips are packed into d_payload at even offsets in strip order; strip_off / strip_len (host arrays, one
  * entry per strip) say where, *payload_bytes is the end of the last one.  payload_cap >= oip_tiff_lzw_worst_bytes().
  * d_scratch: NULL (the call allocates and frees its own) or >= oip_tiff_lzw_scratch_bytes() of device memory, 8-byte aligned,
- * that a caller who knows the product's geometry early prepares off the critical path.  Synchronises the context's stream. */
+ * that a caller who knows the product's geometry early prepares off the critical path.  Refusals are OIP_E_INVALID with nothing
+ * launched, the ones oip_tiff_deflate_strips_u16 has: a null pointer, rows, width or rows_per_strip below 1, spp other than 1 or
+ * 4, a strip above 1 GiB, an image of 4 samples that is not 8-byte aligned, payload_cap below oip_tiff_lzw_worst_bytes(), a
+ * scratch buffer below oip_tiff_lzw_scratch_bytes() or not 8-byte aligned.  Synchronises the context's stream. */
 size_t oip_tiff_lzw_worst_bytes(long rows, int width, int spp, long rows_per_strip);
 size_t oip_tiff_lzw_scratch_bytes(long rows, int width, int spp, long rows_per_strip);
 int oip_tiff_lzw_strips_u16(oip_ctx *ctx, const uint16_t *d_img, long rows, int width, int spp, long rows_per_strip,

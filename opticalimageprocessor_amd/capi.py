@@ -1026,36 +1026,8 @@ class Context:
         o = (C.c_int * 4)(*[int(v) for v in order])
         self._ck(self.lib.oip_permute_u16x4(self.h, _ptr(img), npixels, o))
 
-    def tiff_lzw_strips(self, img, rows, width, spp, rows_per_strip, payload, scratch=None):
-        """LZW strips (predictor 2) of a device image into `payload` (device, uint8); returns (offsets, lengths, payload_bytes)"""
-        n = (rows + rows_per_strip - 1) // rows_per_strip
-        off = (C.c_uint64 * n)()
-        ln = (C.c_uint64 * n)()
-        total = C.c_size_t()
-        self._ck(self.lib.oip_tiff_lzw_strips_u16(self.h, _ptr(img), rows, width, spp, rows_per_strip, _ptr(payload),
-                                                  payload.numel() * payload.element_size(), off, ln, C.byref(total),
-                                                  _ptr(scratch) if scratch is not None else None,
-                                                  scratch.numel() * scratch.element_size() if scratch is not None else 0))
-        return np.array(off[:], dtype=np.uint64), np.array(ln[:], dtype=np.uint64), total.value
-
-    def tiff_lzw_decode(self, d_file, strip_off, strip_len, rows, width, spp, rows_per_strip, predictor, d_img):
-        """LZW strips in `d_file` (device, uint8; offsets relative to it) decoded into d_img (device, rows x width x spp u16)"""
-        n = len(strip_off)
-        off = (C.c_uint64 * n)(*[int(v) for v in strip_off])
-        ln = (C.c_uint64 * n)(*[int(v) for v in strip_len])
-        self._ck(self.lib.oip_tiff_lzw_decode_u16(self.h, _ptr(d_file), d_file.numel() * d_file.element_size(), off, ln, n, rows, width, spp,
-                                                  rows_per_strip, predictor, _ptr(d_img)))
-
-    def tiff_deflate_decode(self, d_file, strip_off, strip_len, rows, width, spp, rows_per_strip, predictor, d_img):
-        """Deflate (zlib) strips in `d_file` (device, uint8; offsets relative to it) inflated into d_img (device, rows x width x spp u16)"""
-        n = len(strip_off)
-        off = (C.c_uint64 * n)(*[int(v) for v in strip_off])
-        ln = (C.c_uint64 * n)(*[int(v) for v in strip_len])
-        self._ck(self.lib.oip_tiff_deflate_decode_u16(self.h, _ptr(d_file), d_file.numel() * d_file.element_size(), off, ln, n, rows, width, spp,
-                                                      rows_per_strip, predictor, _ptr(d_img)))
-
-    def tiff_deflate_strips(self, img, rows, width, spp, rows_per_strip, payload, scratch=None, payload_cap=None, scratch_bytes=None):
-        """Deflate strips (zlib streams, predictor 2) of a device image into `payload` (device, uint8); returns (offsets, lengths,
+    def _tiff_strips(self, entry, img, rows, width, spp, rows_per_strip, payload, scratch, payload_cap, scratch_bytes):
+        """one device strip encoder (include/oip_c.h: LZW's and Deflate's take the same arguments); returns (offsets, lengths,
         payload_bytes).  payload_cap / scratch_bytes: what the call is told the buffers hold, where that is not all of them"""
         n = (rows + rows_per_strip - 1) // max(rows_per_strip, 1) if rows > 0 else 1
         off = (C.c_uint64 * max(n, 1))()
@@ -1065,9 +1037,32 @@ class Context:
             payload_cap = payload.numel() * payload.element_size()
         if scratch_bytes is None:
             scratch_bytes = scratch.numel() * scratch.element_size() if scratch is not None else 0
-        self._ck(self.lib.oip_tiff_deflate_strips_u16(self.h, _ptr(img), rows, width, spp, rows_per_strip, _ptr(payload), payload_cap, off, ln,
-                                                      C.byref(total), _ptr(scratch) if scratch is not None else None, scratch_bytes))
+        self._ck(entry(self.h, _ptr(img), rows, width, spp, rows_per_strip, _ptr(payload), payload_cap, off, ln, C.byref(total),
+                       _ptr(scratch) if scratch is not None else None, scratch_bytes))
         return np.array(off[:], dtype=np.uint64), np.array(ln[:], dtype=np.uint64), total.value
+
+    def _tiff_decode(self, entry, d_file, strip_off, strip_len, rows, width, spp, rows_per_strip, predictor, d_img):
+        """one device stream decoder: the streams in `d_file` (device, uint8; offsets relative to it) into d_img (device, rows x width x spp u16)"""
+        n = len(strip_off)
+        off = (C.c_uint64 * n)(*[int(v) for v in strip_off])
+        ln = (C.c_uint64 * n)(*[int(v) for v in strip_len])
+        self._ck(entry(self.h, _ptr(d_file), d_file.numel() * d_file.element_size(), off, ln, n, rows, width, spp, rows_per_strip, predictor, _ptr(d_img)))
+
+    def tiff_lzw_strips(self, img, rows, width, spp, rows_per_strip, payload, scratch=None, payload_cap=None, scratch_bytes=None):
+        """LZW strips (predictor 2) of a device image into `payload` (device, uint8)"""
+        return self._tiff_strips(self.lib.oip_tiff_lzw_strips_u16, img, rows, width, spp, rows_per_strip, payload, scratch, payload_cap, scratch_bytes)
+
+    def tiff_deflate_strips(self, img, rows, width, spp, rows_per_strip, payload, scratch=None, payload_cap=None, scratch_bytes=None):
+        """Deflate strips (zlib streams, predictor 2) of a device image into `payload` (device, uint8)"""
+        return self._tiff_strips(self.lib.oip_tiff_deflate_strips_u16, img, rows, width, spp, rows_per_strip, payload, scratch, payload_cap, scratch_bytes)
+
+    def tiff_lzw_decode(self, d_file, strip_off, strip_len, rows, width, spp, rows_per_strip, predictor, d_img):
+        """LZW strips decoded on the device"""
+        self._tiff_decode(self.lib.oip_tiff_lzw_decode_u16, d_file, strip_off, strip_len, rows, width, spp, rows_per_strip, predictor, d_img)
+
+    def tiff_deflate_decode(self, d_file, strip_off, strip_len, rows, width, spp, rows_per_strip, predictor, d_img):
+        """Deflate (zlib) strips inflated on the device"""
+        self._tiff_decode(self.lib.oip_tiff_deflate_decode_u16, d_file, strip_off, strip_len, rows, width, spp, rows_per_strip, predictor, d_img)
 
     def tiff_deflate_scratch_bytes(self, rows, width, spp, rows_per_strip):
         return int(self.lib.oip_tiff_deflate_scratch_bytes(rows, width, spp, rows_per_strip))

@@ -256,61 +256,32 @@ template <typename T> struct DevBuf {              // RAII device buffer
 constexpr int BYTES_PER_PIXEL = 2;
 constexpr int MSS_BANDS = OIP_MSS_BANDS;
 
-// rows x rowSamples u16 in HBM -> the writer, 256 MiB of lines at a time, the next block coming down (staging download lane)
-// while the strips of the current one are encoded (a few threads) and the previous one's are written (TiffWriterU16's own
-// thread): download || encode || write
-// OIP_TIFF_GPU_LZW=0: LZW strips on the host's threads (the encoder of oip_tiff.hpp; same file bytes) -- test and A/B knob
-inline bool gpu_lzw()
+// The device codec of a TIFF compression: its numbers (csrc/oip_tiffstreams.h), its entry points (include/oip_c.h: LZW's and
+// Deflate's take the same arguments) and its knob.  nullptr: the compression has none.
+struct TiffDeviceCodec {
+    const OipTiffCodec &codec;
+    int knob;                                    // the value of its environment variable, 1 where unset; 0 sends its streams to the host's threads
+                                                 // (same file bytes, same image: test and A/B knob), the other values: tiff_streams_on_device
+    decltype(&oip_tiff_lzw_worst_bytes) worst_bytes, scratch_bytes;
+    decltype(&oip_tiff_lzw_strips_u16) strips;
+    decltype(&oip_tiff_lzw_decode_u16) decode;
+};
+inline const TiffDeviceCodec *tiff_device_codec(int compression)
 {
-    static const bool on = [] { const char *e = getenv("OIP_TIFF_GPU_LZW"); return !(e && atoi(e) == 0); }();
-    return on;
+    // (both variables are read at the first call, whichever compression it asks for, and hold for the life of the process)
+    auto knob = [](const char *name) { const char *e = getenv(name); return e ? atoi(e) : 1; };
+    static const TiffDeviceCodec lzw{kOipTiffLzw, knob("OIP_TIFF_GPU_LZW"), oip_tiff_lzw_worst_bytes, oip_tiff_lzw_scratch_bytes, oip_tiff_lzw_strips_u16, oip_tiff_lzw_decode_u16};
+    static const TiffDeviceCodec deflate{kOipTiffDeflate, knob("OIP_TIFF_GPU_DEFLATE"), oip_tiff_deflate_worst_bytes, oip_tiff_deflate_scratch_bytes,
+                                         oip_tiff_deflate_strips_u16, oip_tiff_deflate_decode_u16};
+    return compression == TIFF_LZW ? &lzw : compression == TIFF_DEFLATE ? &deflate : nullptr;
 }
 
-// OIP_TIFF_GPU_DEFLATE=0: the streams of a Deflate input on the host's threads (read_tiff_u16; same image), and those of a Deflate
-// product on the host's threads as well (the encoder of oip_tiff.hpp; same file bytes) -- test and A/B knob
-inline bool gpu_deflate()
+// whether the streams (strips or tiles) of a compressed file being read or written go through the device codec: the route rule of
+// csrc/oip_tiffstreams.h with the codec's knob
+inline bool tiff_on_device(int compression, OipTiffDirection dir, size_t nstreams, uint64_t streamBytes)
 {
-    static const bool on = [] { const char *e = getenv("OIP_TIFF_GPU_DEFLATE"); return !(e && atoi(e) == 0); }();
-    return on;
-}
-
-// Which way the streams of a Deflate PRODUCT go.  Both ways run the same coder (csrc/oip_deflate.h) and write the same file; what
-// differs is where the time goes.  Measured (profiles/deflate_encode.md, profiles/deflate_encode.json by
-// profiles/deflate_encode_bench.py: 6144 x 20000 x 4 of 12-bit noise; device events, medians of 20 alternating repetitions; the
-// tools' wall time twice each), device against the host's 16 threads:
-//   strips of one row (48 KiB, 20000 streams)   encode 0.351 s against 0.732 s; `oip overviews` 1.01-1.13 s against 1.16-1.39 s: device
-//   tiles of 128 (128 KiB, 7536 streams)        encode 0.352 s against 0.717 s; `oip cog` 1.32-1.54 s against 2.69-2.96 s:       device
-//   tiles of 512 (2 MiB, 480 streams)           encode 0.379 s against 0.784 s in ONE call -- but `oip cog` 4.97-5.03 s against
-//                                               3.35-3.66 s, because it encodes batch by batch: a 256 MiB batch is 120 such
-//                                               streams for 512 resident waves, and a call lasts as long as its longest stream:  host
-// A wave codes 5.5 MB/s, the 16 threads 1.35 GB/s together: a call wins from about 245 streams on and is at its best with 512 or
-// more, so a layout goes to the device by default -- the rule being that the device beats the host by more than the 5 % box-to-box
-// spread of the tool's wall time -- when it has at least 256 streams and a 256 MiB batch holds at least 512 of them (512 KiB a
-// stream: tiles of 256 at 4 samples, of 512 at one; between 128 KiB and 2 MiB nothing was measured, the bound is the model's).
-// OIP_TIFF_GPU_DEFLATE=0 sends everything to the host, =2 everything the device encoder takes to the device (test knob).
-constexpr size_t kDeflateEncodeDeviceMinStreams = 256;
-constexpr uint64_t kDeflateEncodeDeviceMaxStreamBytes = (uint64_t)512 << 10;
-inline bool deflate_encode_on_device(size_t nstreams, uint64_t streamBytes)
-{
-    static const int knob = [] { const char *e = getenv("OIP_TIFF_GPU_DEFLATE"); return e ? atoi(e) : 1; }();
-    if (knob == 0 || streamBytes > ((uint64_t)1 << 30)) return false;
-    if (knob == 2) return true;
-    return nstreams >= kDeflateEncodeDeviceMinStreams && streamBytes <= kDeflateEncodeDeviceMaxStreamBytes;
-}
-
-// the device encoder of a compression's strips (include/oip_c.h): LZW's and Deflate's take the same arguments
-inline size_t tiff_strips_worst_bytes(int compression, long rows, int width, int spp, long rps)
-{
-    return compression == TIFF_DEFLATE ? oip_tiff_deflate_worst_bytes(rows, width, spp, rps) : oip_tiff_lzw_worst_bytes(rows, width, spp, rps);
-}
-inline size_t tiff_strips_scratch_bytes(int compression, long rows, int width, int spp, long rps)
-{
-    return compression == TIFF_DEFLATE ? oip_tiff_deflate_scratch_bytes(rows, width, spp, rps) : oip_tiff_lzw_scratch_bytes(rows, width, spp, rps);
-}
-// whether the strips (or tiles) of a compressed product are encoded on the device
-inline bool tiff_encode_on_device(int compression, size_t nstreams, uint64_t streamBytes)
-{
-    return compression == TIFF_DEFLATE ? deflate_encode_on_device(nstreams, streamBytes) : gpu_lzw();
+    const TiffDeviceCodec *dc = tiff_device_codec(compression);
+    return dc && tiff_streams_on_device(dc->codec, dir, nstreams, streamBytes, dc->knob);
 }
 
 // the bytes of tile-major samples a batch of tile rows may hold on its way to or from a tiled TIFF (OIP_COG_BATCH_MB: test hook, several
@@ -324,6 +295,9 @@ inline size_t cog_batch_bytes(size_t dflt)
     return dflt;
 }
 
+// rows x rowSamples u16 in HBM -> the writer, 256 MiB of lines at a time, the next block coming down (staging download lane)
+// while the strips of the current one are encoded (a few threads) and the previous one's are written (TiffWriterU16's own
+// thread): download || encode || write
 inline void tiff_rows_from_device(TiffWriterU16 &tw, const uint16_t *d_img, long rows, size_t rowSamples, long mark)
 {
     oip_ctx *ctx = Device::get().ctx();
@@ -370,8 +344,9 @@ struct TiffStripPrep {
     void prepare(TiffWriterU16 &tw, const std::string &path, int width, long height, int spp, int compression, bool withSink)
     {
         const long rps = tw.rows_per_strip();
-        payload.alloc(tiff_strips_worst_bytes(compression, height, width, spp, rps));
-        scratch.alloc(tiff_strips_scratch_bytes(compression, height, width, spp, rps));
+        const TiffDeviceCodec &dc = *tiff_device_codec(compression);
+        payload.alloc(dc.worst_bytes(height, width, spp, rps));
+        scratch.alloc(dc.scratch_bytes(height, width, spp, rps));
         if (withSink) {
             payloadAt = tw.begin_external_strips();
             Device::get().check(oip_file_sink_open(Device::get().ctx(), path.c_str(), (size_t)payloadAt + payload.n, &sink));
@@ -384,6 +359,7 @@ inline void tiff_strips_from_device(TiffWriterU16 &tw, const std::string &path, 
                                     int compression, TiffStripPrep *prep = nullptr)
 {
     oip_ctx *ctx = Device::get().ctx();
+    const TiffDeviceCodec &dc = *tiff_device_codec(compression);
     stop_watch sw;
     const long rps = tw.rows_per_strip();
     const size_t nstrips = (size_t)((height + rps - 1) / rps);
@@ -395,7 +371,7 @@ inline void tiff_strips_from_device(TiffWriterU16 &tw, const std::string &path, 
         // -- at the size sensor data encodes to (raw + 3 %: LZW does not compress it, and Deflate's worst case is below that); a
         // payload that turns out larger goes the plain way.  (Writing a new file is bound by the allocation of its pages)
         prep = &own;
-        const size_t worst = tiff_strips_worst_bytes(compression, height, width, spp, rps);
+        const size_t worst = dc.worst_bytes(height, width, spp, rps);
         prep->payload.alloc(worst);
         const size_t raw = (size_t)height * width * spp * 2;
         if (raw >= ((size_t)64 << 20)) {
@@ -410,8 +386,7 @@ inline void tiff_strips_from_device(TiffWriterU16 &tw, const std::string &path, 
     std::vector<uint64_t> off(nstrips), len(nstrips);
     size_t bytes = 0;
     const double tAlloc = sw.tick();
-    const auto encode = compression == TIFF_DEFLATE ? oip_tiff_deflate_strips_u16 : oip_tiff_lzw_strips_u16;
-    const int rcEncode = encode(ctx, d_img, height, width, spp, rps, prep->payload.p, prep->payload.n, off.data(), len.data(), &bytes, prep->scratch.p,
+    const int rcEncode = dc.strips(ctx, d_img, height, width, spp, rps, prep->payload.p, prep->payload.n, off.data(), len.data(), &bytes, prep->scratch.p,
                                 prep->scratch.n);
     if (reserving.valid() && reserving.get() != OIP_OK && prep->sink) { oip_file_sink_close(nullptr, prep->sink); prep->sink = nullptr; }
     Device::get().check(rcEncode);
@@ -437,12 +412,12 @@ inline void tiff_strips_from_device(TiffWriterU16 &tw, const std::string &path, 
     }
     tw.end_external_strips(off.data(), len.data(), nstrips, bytes);
     const double tWrite = sw.tick();
-    RLOG("TIMING %s strips=%zu alloc=%.4f encode=%.4f write=%.4f bytes=%zu prepared=%d", compression == TIFF_DEFLATE ? "tiff_deflate" : "tiff_lzw", nstrips,
+    RLOG("TIMING %s strips=%zu alloc=%.4f encode=%.4f write=%.4f bytes=%zu prepared=%d", dc.codec.timing, nstrips,
          tAlloc, tEncode, tWrite, bytes, prep != &own);
 }
 
 // The pixels of the directory `tw` is writing (width x height x spp u16 in HBM, in file sample order) leave the device:
-// uncompressed as one external payload, LZW and Deflate strips from the device encoder where tiff_encode_on_device() says so, else
+// uncompressed as one external payload, LZW and Deflate strips from the device encoder where tiff_on_device() says so, else
 // through the host's.
 inline void tiff_image_from_device(TiffWriterU16 &tw, const std::string &path, const uint16_t *d_img, int width, long height, int spp,
                                    int compression, long mark)
@@ -452,7 +427,7 @@ inline void tiff_image_from_device(TiffWriterU16 &tw, const std::string &path, c
         const uint64_t at = tw.begin_external_payload();
         Device::get().check(oip_write_device_to_file_at(Device::get().ctx(), d_img, (size_t)height * rowSamples * 2, path.c_str(), (size_t)at, mark));
         tw.end_external_payload();
-    } else if (tiff_encode_on_device(compression, (size_t)((height + tw.rows_per_strip() - 1) / tw.rows_per_strip()), (uint64_t)tw.rows_per_strip() * rowSamples * 2)) {
+    } else if (tiff_on_device(compression, OIP_TIFF_WRITE, (size_t)((height + tw.rows_per_strip() - 1) / tw.rows_per_strip()), (uint64_t)tw.rows_per_strip() * rowSamples * 2)) {
         tiff_strips_from_device(tw, path, d_img, width, height, spp, compression);
     } else {
         tiff_rows_from_device(tw, d_img, height, rowSamples, mark);
@@ -483,8 +458,8 @@ inline void write_tiff_from_device(const std::string &path, uint16_t *d_img, int
 // rows of at most 256 MiB of tile-major samples and at least one tile row (OIP_COG_BATCH_MB: test hook, several batches on a small
 // image): oip_retile_u16 into the batch buffer; uncompressed, the batch itself goes into the file; LZW and Deflate, every tile is
 // one "strip" of the device encoder (a T-wide image of tile_rows tx T lines in strips of T lines) and the packed payload goes.
-// OIP_TIFF_GPU_LZW=0, and Deflate where deflate_encode_on_device() says host (on the directory's tile count: the same for every
-// batch size): the tile-major form comes down and the host coders write it (TiffTiledWriterU16::write_tiles; same bytes).
+// Where tiff_on_device() says host (OIP_TIFF_GPU_LZW=0; Deflate on the directory's tile count: the same for every batch size):
+// the tile-major form comes down and the host coders write it (TiffTiledWriterU16::write_tiles; same bytes).
 inline void tiled_image_from_device(TiffTiledWriterU16 &tw, const std::string &path, const uint16_t *d_img, int w, long h, int spp, int T,
                                     int compression)
 {
@@ -495,7 +470,7 @@ inline void tiled_image_from_device(TiffTiledWriterU16 &tw, const std::string &p
     const size_t tileSamples = (size_t)T * T * spp, rowSamples = (size_t)tx * tileSamples, n = (size_t)tx * ty;
     const long batchRows = std::max<long>(1, std::min<long>(ty, (long)(cog_batch_bytes((size_t)256 << 20) / (rowSamples * 2))));
     DevBuf<uint16_t> batch((size_t)batchRows * rowSamples);
-    if (compression != TIFF_NONE && !tiff_encode_on_device(compression, n, (uint64_t)tileSamples * 2)) {
+    if (compression != TIFF_NONE && !tiff_on_device(compression, OIP_TIFF_WRITE, n, (uint64_t)tileSamples * 2)) {
         std::vector<uint16_t> host(n * tileSamples);
         for (long j0 = 0; j0 < ty; j0 += batchRows) {
             const long nr = std::min(batchRows, ty - j0);
@@ -505,12 +480,12 @@ inline void tiled_image_from_device(TiffTiledWriterU16 &tw, const std::string &p
         tw.write_tiles(host.data());
         return;
     }
+    const TiffDeviceCodec *dc = tiff_device_codec(compression);      // (nullptr: uncompressed)
     DevBuf<uint8_t> payload, scratch;
-    if (compression != TIFF_NONE) {
-        payload.alloc(tiff_strips_worst_bytes(compression, batchRows * tx * T, T, spp, T));
-        scratch.alloc(tiff_strips_scratch_bytes(compression, batchRows * tx * T, T, spp, T));
+    if (dc) {
+        payload.alloc(dc->worst_bytes(batchRows * tx * T, T, spp, T));
+        scratch.alloc(dc->scratch_bytes(batchRows * tx * T, T, spp, T));
     }
-    const auto encode = compression == TIFF_DEFLATE ? oip_tiff_deflate_strips_u16 : oip_tiff_lzw_strips_u16;
     std::vector<uint64_t> off(n), len(n);
     const uint64_t at = tw.begin_tiles();
     uint64_t pos = 0;
@@ -521,14 +496,14 @@ inline void tiled_image_from_device(TiffTiledWriterU16 &tw, const std::string &p
         const size_t k0 = (size_t)j0 * tx, nt = (size_t)nr * tx;
         if (pos & 1) ++pos;                                            // a batch starts on an even offset, as every tile does
         ck(oip_retile_u16(ctx, d_img, (long)w * spp, w, h, spp, T, j0, nr, batch.p));
-        if (compression == TIFF_NONE) {
+        if (!dc) {
             for (size_t k = 0; k < nt; ++k) { off[k0 + k] = pos + k * tileSamples * 2; len[k0 + k] = tileSamples * 2; }
             ck(oip_write_device_to_file_at(ctx, batch.p, nt * tileSamples * 2, path.c_str(), (size_t)(at + pos), 0));
             pos += nt * tileSamples * 2;
             tWrite += sw.tick();
         } else {
             size_t bytes = 0;
-            ck(encode(ctx, batch.p, (long)nt * T, T, spp, T, payload.p, payload.n, off.data() + k0, len.data() + k0, &bytes, scratch.p, scratch.n));
+            ck(dc->strips(ctx, batch.p, (long)nt * T, T, spp, T, payload.p, payload.n, off.data() + k0, len.data() + k0, &bytes, scratch.p, scratch.n));
             tEncode += sw.tick();
             for (size_t k = 0; k < nt; ++k) off[k0 + k] += pos;
             ck(oip_write_device_to_file_at(ctx, payload.p, bytes, path.c_str(), (size_t)(at + pos), 0));
@@ -537,8 +512,8 @@ inline void tiled_image_from_device(TiffTiledWriterU16 &tw, const std::string &p
         }
     }
     tw.end_tiles(off.data(), len.data(), n, pos);
-    if (compression != TIFF_NONE)
-        RLOG("TIMING %s tiles=%zu tile=%d encode=%.4f write=%.4f bytes=%zu", compression == TIFF_DEFLATE ? "tiff_deflate" : "tiff_lzw", n, T, tEncode, tWrite, (size_t)pos);
+    if (dc)
+        RLOG("TIMING %s tiles=%zu tile=%d encode=%.4f write=%.4f bytes=%zu", dc->codec.timing, n, T, tEncode, tWrite, (size_t)pos);
 }
 
 // ---- overviews: <product>.ovr, the reduced-resolution pyramid of a product or strip (not in the reference) ----------------
@@ -594,14 +569,8 @@ inline void write_overviews_of_device_image(const std::string &path, const uint1
 // strip per lane; a tiled file with square tiles of a multiple of 16: a tile per lane into a tile-major buffer, then
 // oip_untile_u16); anything else, and OIP_TIFF_GPU_LZW=0, decodes on the host's threads (read_tiff_u16) and uploads.  Same
 // checks and error texts either way: the header is validated by the host reader in both.  Deflate files take the same two
-// routes, their streams inflated by csrc/tiffdeflate.hip (a stream per wave), under the same conditions and two more, which
-// are what was measured: a wave inflates 4.1 MB/s whatever the layout and the 16 host threads about 60 MB/s
-// each, so the device needs at least 16 x 60 / 4.1 = 234 streams in flight to win, and a stream's time on a shared device is
-// its bytes / 4.1 MB/s.  Hence: at least kDeflateDeviceMinStreams strips or tiles, none decoding to more than
-// kDeflateDeviceMaxStreamBytes (2 MiB, the largest stream measured: half a second).  Everything else -- few streams, long
-// streams -- and OIP_TIFF_GPU_DEFLATE=0 goes to the host.
-constexpr size_t kDeflateDeviceMinStreams = 256;
-constexpr uint64_t kDeflateDeviceMaxStreamBytes = (uint64_t)2 << 20;
+// routes, their streams inflated by csrc/tiffdeflate.hip (a stream per wave), under the same conditions and the two of the route
+// rule (csrc/oip_tiffstreams.h: at least 256 streams, none decoding to more than 2 MiB; what was measured is told there).
 // Streams [k0, k0 + n) of the file -- strips or tiles -- go from the file into device memory as they are and are decoded into d_out, an
 // image of `rows` x `width` pixels in strips of `rps` rows; `tail` ends the message of a stream the decoder refuses.
 inline void tiff_streams_to_device(const std::string &path, const TiffLayout &lay, size_t k0, size_t n, long rows, int width, long rps, uint16_t *d_out,
@@ -618,8 +587,7 @@ inline void tiff_streams_to_device(const std::string &path, const TiffLayout &la
     Device::get().check(oip_stage_sync(ctx));
     std::vector<uint64_t> off(lay.offs.begin() + k0, lay.offs.begin() + k0 + n);
     for (auto &o : off) o -= lo;
-    const auto decode = lay.compression == TIFF_DEFLATE ? oip_tiff_deflate_decode_u16 : oip_tiff_lzw_decode_u16;
-    const int rc = decode(ctx, file.p, file.n, off.data(), lay.lens.data() + k0, (long)n, rows, width, (int)lay.spp, rps, (int)lay.predictor, d_out);
+    const int rc = tiff_device_codec((int)lay.compression)->decode(ctx, file.p, file.n, off.data(), lay.lens.data() + k0, (long)n, rows, width, (int)lay.spp, rps, (int)lay.predictor, d_out);
     if (rc != OIP_OK) throw std::runtime_error("read TIFF [" + path + "]: " + std::string(oip_last_error(ctx)) + tail);
 }
 
@@ -630,16 +598,12 @@ inline void read_tiff_to_device(const std::string &path, int *width, long *heigh
     const size_t samples = (size_t)lay.width * lay.height * lay.spp;
     // (tiled: square tiles the layout kernel takes -- a multiple of 16 up to 1024 --, each one a "strip" of the decoder)
     const uint64_t T = lay.tile_width;
-    const bool deflate = lay.compression == TIFF_DEFLATE;
-    bool device = (deflate ? gpu_deflate() : gpu_lzw() && lay.compression == TIFF_LZW) && (lay.spp == 1 || lay.spp == 4) &&
+    const uint64_t streamBytes = (lay.tiled() ? T * T : lay.rows_per_strip * lay.width) * lay.spp * 2;
+    bool device = tiff_on_device((int)lay.compression, OIP_TIFF_READ, lay.offs.size(), streamBytes) && (lay.spp == 1 || lay.spp == 4) &&
                   (lay.tiled() ? T == lay.tile_length && T % 16 == 0 && T <= 1024 : lay.rows_per_strip * lay.width * lay.spp * 2 < ((uint64_t)1 << 32));
     uint64_t lo = ~(uint64_t)0, hi = 0;
     for (size_t k = 0; k < lay.offs.size(); ++k) { lo = std::min(lo, lay.offs[k]); hi = std::max(hi, lay.offs[k] + lay.lens[k]); }
     if (device && hi - lo > 3 * samples + ((uint64_t)64 << 20)) device = false;       // strips scattered over a far larger file
-    if (device && deflate) {
-        const uint64_t streamBytes = (lay.tiled() ? T * T : lay.rows_per_strip * lay.width) * lay.spp * 2;
-        if (lay.offs.size() < kDeflateDeviceMinStreams || streamBytes > kDeflateDeviceMaxStreamBytes) device = false;
-    }
     if (!device) {
         std::vector<uint16_t> host;
         read_tiff_u16(path, width, height, spp, &host);
@@ -1464,7 +1428,7 @@ private:
         bool on_device() const
         {
             const long rps = tiff.rows_per_strip();
-            return tiff_encode_on_device(comp, (size_t)((rows + rps - 1) / rps), (uint64_t)rps * Wb * MSS_BANDS * 2);
+            return tiff_on_device(comp, OIP_TIFF_WRITE, (size_t)((rows + rps - 1) / rps), (uint64_t)rps * Wb * MSS_BANDS * 2);
         }
         AlignedProduct(const std::string &path_, int Wb_, long rows_)
             : path(path_), comp(tiff_compression(TIFF_LZW)), Wb(Wb_), rows(rows_), tiff(path, Wb, rows, MSS_BANDS, false, comp)

@@ -103,6 +103,16 @@ int oip_rrc_launch(oip_ctx *ctx, hipStream_t stream, const uint16_t *d_src, uint
                             hipGetErrorString(e__), __FILE__, __LINE__);                \
     } while (0)
 
+// a device allocation of a call's own: freed on every way out of its scope, OIP_HIP's returns included
+struct OipDeviceBlock {
+    void *p = nullptr;
+    OipDeviceBlock() = default;
+    OipDeviceBlock(const OipDeviceBlock &) = delete;
+    OipDeviceBlock &operator=(const OipDeviceBlock &) = delete;
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+    ~OipDeviceBlock() { if (p) (void)hipFree(p); }
+};
+
 #define OIP_CHECK_CTX(ctx)                                                              \
     do {                                                                                \
         if (!(ctx)) return OIP_E_INVALID;                                               \

@@ -44,7 +44,7 @@
 
 #include "oip_deflate.h"
 #include "oip_inflate.h"
-#include "oip_tiffshared.h"
+#include "oip_tiffstreams.h"
 
 namespace OIPGPU {
 
@@ -125,7 +125,7 @@ struct LzwTable {
     }
 };
 
-// encodes n bytes into dst (lzw_worst(n) bytes, oip_tiffshared.h); returns the encoded size
+// encodes n bytes into dst (lzw_worst(n) bytes, oip_tiffstreams.h); returns the encoded size
 inline size_t lzw_encode_to(const uint8_t *src, size_t n, uint8_t *dst)
 {
     static thread_local std::unique_ptr<LzwTable> tab;  // ~96 KB, once per encoding thread
@@ -281,7 +281,7 @@ inline void swap_row(const uint16_t *src, uint16_t *dst, size_t width)
     }
 }
 
-// the most an encoded strip or tile of n bytes takes (LZW: oip_tiffshared.h; Deflate: all of it in stored blocks, oip_deflate.h)
+// the most an encoded strip or tile of n bytes takes (LZW: oip_tiffstreams.h; Deflate: all of it in stored blocks, oip_deflate.h)
 inline size_t chunk_worst(size_t n, int compression) { return compression == TIFF_DEFLATE ? oipdeflate::stored_bound(n) : lzw_worst(n); }
 
 // One strip or tile of an LZW or Deflate file: `rows` rows of `width` pixels from src into buf (swap: in OpenCV's order), differenced

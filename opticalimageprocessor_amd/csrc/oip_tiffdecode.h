@@ -4,17 +4,26 @@
 #pragma once
 
 #include "oip_internal.h"
+#include "oip_tiffstreams.h"
 
 #include <cstdint>
 #include <vector>
 
-// the scratch of one call: [the codec's tables | off | len | got | status], every part from a multiple of 256 bytes
+// the scratch of one call (tiff_decode_layout, oip_tiffstreams.h), as the kernels see it
 struct OipTiffStreams {
     void *tables;
     const unsigned long long *off, *len;         // [nstrips] stream offsets inside the file buffer, byte counts
     unsigned *got;                               // [nstrips] bytes a stream decoded to
     int *status;                                 // [nstrips] 0, or the codec's reason
 };
+
+// predictor 2 of 4-sample pixels, both decoders: four 16-bit adds in one register -- the low 15 bits of every field carry on their
+// own, the top bits by xor
+__device__ __forceinline__ unsigned long long padd16(unsigned long long a, unsigned long long b)
+{
+    const unsigned long long m = 0x7fff7fff7fff7fffull;
+    return ((a & m) + (b & m)) ^ ((a ^ b) & ~m);
+}
 
 // fn: the entry point, for its messages; limit: a stream and what it decodes to are smaller than this; launch(OipTiffStreams): the
 // codec's kernels on ctx->stream; codec, reason(status): the words for a stream the kernels refused
@@ -33,32 +42,27 @@ inline int oip_tiff_decode(oip_ctx *ctx, const char *fn, const char *codec, cons
     for (long k = 0; k < nstrips; ++k)
         if (strip_off[k] > file_bytes || strip_len[k] > file_bytes - strip_off[k] || strip_len[k] >= limit)
             return oip_fail(ctx, OIP_E_INVALID, "%s: strip %ld outside the buffer", fn, k);
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_off = up(table_bytes), o_len = o_off + up((size_t)nstrips * 8), o_got = o_len + up((size_t)nstrips * 8),
-                 o_status = o_got + up((size_t)nstrips * 4), need = o_status + up((size_t)nstrips * 4);
-    void *scratch = nullptr;
-    OIP_HIP(ctx, hipMalloc(&scratch, need));
-    auto fail = [&](int rc) { (void)hipFree(scratch); return rc; };
-    unsigned long long *d_off = reinterpret_cast<unsigned long long *>((char *)scratch + o_off);
-    unsigned long long *d_len = reinterpret_cast<unsigned long long *>((char *)scratch + o_len);
-    unsigned *d_got = reinterpret_cast<unsigned *>((char *)scratch + o_got);
-    int *d_status = reinterpret_cast<int *>((char *)scratch + o_status);
+    const OipTiffDecodeLayout l = tiff_decode_layout(table_bytes, (size_t)nstrips);
+    OipDeviceBlock scratch;
+    OIP_HIP(ctx, scratch.alloc(l.bytes));
+    unsigned long long *d_off = reinterpret_cast<unsigned long long *>((char *)scratch.p + l.o_off);
+    unsigned long long *d_len = reinterpret_cast<unsigned long long *>((char *)scratch.p + l.o_len);
+    unsigned *d_got = reinterpret_cast<unsigned *>((char *)scratch.p + l.o_got);
+    int *d_status = reinterpret_cast<int *>((char *)scratch.p + l.o_status);
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "strip tables are copied as they are");
     if (hipMemcpyAsync(d_off, strip_off, (size_t)nstrips * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
         hipMemcpyAsync(d_len, strip_len, (size_t)nstrips * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        return fail(oip_fail(ctx, OIP_E_DEVICE, "%s: copying the strip tables failed", fn));
-    launch(OipTiffStreams{scratch, d_off, d_len, d_got, d_status});
+        return oip_fail(ctx, OIP_E_DEVICE, "%s: copying the strip tables failed", fn);
+    launch(OipTiffStreams{scratch.p, d_off, d_len, d_got, d_status});
     std::vector<unsigned> got((size_t)nstrips);
     std::vector<int> status((size_t)nstrips);
     if (hipGetLastError() != hipSuccess ||
         hipMemcpyAsync(got.data(), d_got, (size_t)nstrips * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
         hipMemcpyAsync(status.data(), d_status, (size_t)nstrips * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess)
-        return fail(oip_fail(ctx, OIP_E_DEVICE, "%s: decoding failed on the device", fn));
-    (void)hipFree(scratch);
+        return oip_fail(ctx, OIP_E_DEVICE, "%s: decoding failed on the device", fn);
     for (long k = 0; k < nstrips; ++k) {
-        const long nr = rows - k * rows_per_strip < rows_per_strip ? rows - k * rows_per_strip : rows_per_strip;
-        const size_t want = (size_t)nr * rowBytes;
+        const size_t want = (size_t)tiff_strip_span(k, rows, rows_per_strip).nr * rowBytes;
         if (status[(size_t)k] != 0) return oip_fail(ctx, OIP_E_RUNTIME, "corrupt %s stream (%s) in strip %ld", codec, reason(status[(size_t)k]), k);
         if (got[(size_t)k] != want) return oip_fail(ctx, OIP_E_RUNTIME, "strip %ld decodes to %u bytes, %zu expected", k, got[(size_t)k], want);
     }

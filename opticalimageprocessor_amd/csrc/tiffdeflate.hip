@@ -21,12 +21,12 @@
 // differences of the image's rows, made while they are staged: the image is only read), hash and compare the 64 positions of a
 // round, count the literals, rank the symbols by frequency, and place a block's codes by a prefix sum of their bit counts; one
 // lane walks a round's 64 candidates and builds the code lengths.  Nothing of a stream is kept in HBM but its output: the streams
-// land in fixed slots of the stored bound's size and oip_tiffpack.h packs them, as for LZW.
+// land in fixed slots of the stored bound's size and oip_tiffencode.h packs them, as for LZW.
 #include "oip_internal.h"
 #include "oip_deflate.h"
 #include "oip_inflate.h"
 #include "oip_tiffdecode.h"
-#include "oip_tiffpack.h"
+#include "oip_tiffencode.h"
 
 #include <cstdint>
 #include <memory>
@@ -66,9 +66,8 @@ __global__ __launch_bounds__(64) void deflate_decode_kernel(DeflateJob j)
     const long k = j.strip0 + blockIdx.x;
     if (k >= j.nstrips) return;
     const size_t rowBytes = (size_t)j.width * j.spp * 2;
-    const long r0 = k * j.rps;
-    long nr = j.rows - r0;
-    if (nr > j.rps) nr = j.rps;
+    const OipStripSpan span = tiff_strip_span(k, j.rows, j.rps);
+    const long r0 = span.r0, nr = span.nr;
     uint8_t *out = reinterpret_cast<uint8_t *>(j.img) + (size_t)r0 * rowBytes;
     const unsigned cap = (unsigned)((size_t)nr * rowBytes);
     WaveLane lanes;
@@ -80,14 +79,8 @@ __global__ __launch_bounds__(64) void deflate_decode_kernel(DeflateJob j)
     if (threadIdx.x == 0) { j.got[k] = got; j.status[k] = st; }
 }
 
-// four 16-bit adds in one register: the low 15 bits of every field carry on their own, the top bits by xor (as tifflzw.hip)
-__device__ __forceinline__ unsigned long long padd16(unsigned long long a, unsigned long long b)
-{
-    const unsigned long long m = 0x7fff7fff7fff7fffull;
-    return ((a & m) + (b & m)) ^ ((a ^ b) & ~m);
-}
-
-// Predictor 2 undone: a wave per row, 64 pixels a round, an inclusive scan across the lanes plus the carry of the rounds before.
+// Predictor 2 undone: a wave per row, 64 pixels a round, an inclusive scan (padd16, oip_tiffdecode.h) across the lanes plus the carry
+// of the rounds before.
 // FIELDS = 4: a pixel is four samples in one 64-bit word; 1: one sample.  Rows of a stream that failed are left as they are.
 template <int FIELDS>
 __global__ __launch_bounds__(64) void deflate_unpredict_kernel(uint16_t *img, long rows, int width, long rps, const unsigned *got, const int *status)
@@ -95,7 +88,7 @@ __global__ __launch_bounds__(64) void deflate_unpredict_kernel(uint16_t *img, lo
     const long r = blockIdx.x;
     if (r >= rows) return;
     const long k = r / rps;
-    const long nr = rows - k * rps < rps ? rows - k * rps : rps;
+    const long nr = tiff_strip_span(k, rows, rps).nr;
     if (status[k] != 0 || (size_t)got[k] != (size_t)nr * width * FIELDS * 2) return;
     uint16_t *row = img + (size_t)r * width * FIELDS;
     const int lane = threadIdx.x;
@@ -124,7 +117,7 @@ __global__ __launch_bounds__(64) void deflate_unpredict_any_kernel(uint16_t *img
     const long r = blockIdx.x;
     if (r >= rows || (int)threadIdx.x >= spp) return;
     const long k = r / rps;
-    const long nr = rows - k * rps < rps ? rows - k * rps : rps;
+    const long nr = tiff_strip_span(k, rows, rps).nr;
     if (status[k] != 0 || (size_t)got[k] != (size_t)nr * width * spp * 2) return;
     uint16_t *row = img + (size_t)r * width * spp + threadIdx.x;
     unsigned prev = row[0];
@@ -132,8 +125,6 @@ __global__ __launch_bounds__(64) void deflate_unpredict_any_kernel(uint16_t *img
 }
 
 // ---- encode --------------------------------------------------------------------------------------------------------------------
-constexpr long kEncodeStreamsPerLaunch = 32768;
-
 struct WaveLaneEnc : WaveLane {
     __device__ unsigned scan(unsigned v) const                                 // exclusive prefix sum over the 64 lanes
     {
@@ -180,9 +171,8 @@ __global__ __launch_bounds__(64) void deflate_encode_kernel(DeflateEncJob j)
     const long k = j.strip0 + blockIdx.x;
     if (k >= j.nstrips) return;
     const size_t rowSamples = (size_t)j.width * j.spp;
-    const long r0 = k * j.rps;
-    long nr = j.rows - r0;
-    if (nr > j.rps) nr = j.rps;
+    const OipStripSpan span = tiff_strip_span(k, j.rows, j.rps);
+    const long r0 = span.r0, nr = span.nr;
     WaveLaneEnc lanes;
     const PredictorSource src{j.img + (size_t)r0 * rowSamples, (unsigned)rowSamples, (unsigned)j.spp};
     const unsigned n = (unsigned)((size_t)nr * rowSamples * 2);
@@ -192,16 +182,6 @@ __global__ __launch_bounds__(64) void deflate_encode_kernel(DeflateEncJob j)
     if (threadIdx.x == 0) j.len[k] = st == oipdeflate::kOk ? size : 0u;
 }
 
-// device scratch of one call: the output slots of a launch, the stream lengths and offsets
-void deflate_scratch_layout(long nstrips, size_t slot_bytes, size_t *len, size_t *off, size_t *total)
-{
-    const long per = nstrips < kEncodeStreamsPerLaunch ? nstrips : kEncodeStreamsPerLaunch;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    *len = up((size_t)per * slot_bytes);
-    *off = *len + up((size_t)nstrips * sizeof(unsigned));
-    *total = *off + up((size_t)nstrips * sizeof(unsigned long long));
-}
-size_t deflate_slot_bytes(size_t strip) { return (oipdeflate::stored_bound(strip) + 3) / 4 * 4; }
 }  // namespace
 
 // (oip_tiff_decode's refusals and two of its own: the row kernels take a row per workgroup, so fewer than 2^31 rows, and address the
@@ -213,7 +193,7 @@ extern "C" int oip_tiff_deflate_decode_u16(oip_ctx *ctx, const uint8_t *d_file, 
     OIP_CHECK_CTX(ctx);
     if (rows >= ((long)1 << 31)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_decode_u16: 2^31 rows or more");
     if (((uintptr_t)d_img) & 1) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_decode_u16: image not 2-byte aligned");
-    return oip_tiff_decode(ctx, "oip_tiff_deflate_decode_u16", "Deflate", oipinflate::status_text, oipinflate::kMaxStream, 0, d_file, file_bytes, strip_off,
+    return oip_tiff_decode(ctx, "oip_tiff_deflate_decode_u16", kOipTiffDeflate.name, oipinflate::status_text, oipinflate::kMaxStream, 0, d_file, file_bytes, strip_off,
                            strip_len, nstrips, rows, width, spp, rows_per_strip, predictor, d_img, [&](const OipTiffStreams &t) {
         for (long s0 = 0; s0 < nstrips; s0 += kStreamsPerLaunch) {
             const long ns = nstrips - s0 < kStreamsPerLaunch ? nstrips - s0 : kStreamsPerLaunch;
@@ -239,19 +219,12 @@ extern "C" size_t oip_deflate_stream_host(const uint8_t *src, size_t n, uint8_t 
 
 extern "C" size_t oip_tiff_deflate_worst_bytes(long rows, int width, int spp, long rows_per_strip)
 {
-    if (rows <= 0 || width <= 0 || spp <= 0 || rows_per_strip <= 0) return 0;
-    const size_t strip = (size_t)rows_per_strip * width * spp * 2;
-    const size_t nstrips = ((size_t)rows + rows_per_strip - 1) / rows_per_strip;
-    return nstrips * (oipdeflate::stored_bound(strip) + 2);                    // (+ 2: to the next even offset, and the payload's even end)
+    return plan_tiff_encode(kOipTiffDeflate, rows, width, spp, rows_per_strip).worst_bytes;
 }
 
 extern "C" size_t oip_tiff_deflate_scratch_bytes(long rows, int width, int spp, long rows_per_strip)
 {
-    if (rows <= 0 || width <= 0 || spp <= 0 || rows_per_strip <= 0) return 0;
-    const long nstrips = (rows + rows_per_strip - 1) / rows_per_strip;
-    size_t a, b, total;
-    deflate_scratch_layout(nstrips, deflate_slot_bytes((size_t)rows_per_strip * width * spp * 2), &a, &b, &total);
-    return total;
+    return plan_tiff_encode(kOipTiffDeflate, rows, width, spp, rows_per_strip).scratch_bytes;
 }
 
 extern "C" int oip_tiff_deflate_strips_u16(oip_ctx *ctx, const uint16_t *d_img, long rows, int width, int spp, long rows_per_strip,
@@ -259,74 +232,15 @@ extern "C" int oip_tiff_deflate_strips_u16(oip_ctx *ctx, const uint16_t *d_img, 
                                            size_t *payload_bytes, void *d_scratch, size_t scratch_bytes)
 {
     OIP_CHECK_CTX(ctx);
-    if (!d_img || !d_payload || !strip_off || !strip_len || !payload_bytes || rows <= 0 || width <= 0 || (spp != 1 && spp != 4) ||
-        rows_per_strip <= 0)
-        return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_strips_u16: bad argument");
-    if ((((uintptr_t)d_img) & 1)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_strips_u16: image not 2-byte aligned");
-    if ((((uintptr_t)d_payload) & 1)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_strips_u16: payload not 2-byte aligned");
-    const long nstrips = (rows + rows_per_strip - 1) / rows_per_strip;
-    const size_t strip = (size_t)rows_per_strip * width * spp * 2;
-    if (strip > (1u << 30)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_strips_u16: strip larger than 1 GiB");
-    if (payload_cap < oip_tiff_deflate_worst_bytes(rows, width, spp, rows_per_strip))
-        return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_strips_u16: payload buffer too small");
-    const size_t slot_bytes = deflate_slot_bytes(strip);
-    const long per = nstrips < kEncodeStreamsPerLaunch ? nstrips : kEncodeStreamsPerLaunch;
-    size_t o_len, o_off, need;
-    deflate_scratch_layout(nstrips, slot_bytes, &o_len, &o_off, &need);
-    void *own = nullptr;                         // scratch of this call's own when the caller brought none
-    auto release = [&] { if (own) (void)hipFree(own); };
-#define OIP_DEFLATE_HIP(call)                                                                                 \
-    do {                                                                                                      \
-        hipError_t e__ = (call);                                                                              \
-        if (e__ != hipSuccess) {                                                                              \
-            release();                                                                                        \
-            return oip_fail(ctx, OIP_E_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-        }                                                                                                     \
-    } while (0)
-    if (d_scratch) {
-        if (scratch_bytes < need || (((uintptr_t)d_scratch) & 7)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_strips_u16: scratch too small or misaligned");
-    } else {
-        OIP_DEFLATE_HIP(hipMalloc(&own, need));
-        d_scratch = own;
-    }
-    const size_t lds = sizeof(oipdeflate::Shared);
-    static_assert(sizeof(oipdeflate::Shared) <= 80 * 1024, "two workgroups of the encoder per CU");
-    OIP_DEFLATE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_encode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    uint8_t *d_slots = reinterpret_cast<uint8_t *>(d_scratch);
-    unsigned *d_len = reinterpret_cast<unsigned *>((char *)d_scratch + o_len);
-    unsigned long long *d_off = reinterpret_cast<unsigned long long *>((char *)d_scratch + o_off);
-    std::vector<unsigned> len((size_t)nstrips);
-    std::vector<unsigned long long> off((size_t)nstrips);
-    size_t pos = 0;
-    for (long s0 = 0; s0 < nstrips; s0 += per) {
-        const long ns = nstrips - s0 < per ? nstrips - s0 : per;
-        DeflateEncJob j{d_img, rows, width, spp, rows_per_strip, nstrips, s0, d_slots, slot_bytes, d_len};
-        {
-            OipProfScope prof(ctx, "deflate_encode_kernel");
-            hipLaunchKernelGGL(deflate_encode_kernel, dim3((unsigned)ns), dim3(64), lds, ctx->stream, j);
-        }
-        OIP_DEFLATE_HIP(hipGetLastError());
-        OIP_DEFLATE_HIP(hipMemcpyAsync(len.data() + s0, d_len + s0, (size_t)ns * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-        OIP_DEFLATE_HIP(hipStreamSynchronize(ctx->stream));
-        for (long k = s0; k < s0 + ns; ++k) {
-            if (len[(size_t)k] == 0 || len[(size_t)k] > slot_bytes) { release(); return oip_fail(ctx, OIP_E_RUNTIME, "oip_tiff_deflate_strips_u16: strip %ld was not encoded", k); }
-            if (pos & 1) ++pos;                                                  // strips start on even offsets (oip_tiff.hpp)
-            off[(size_t)k] = pos;
-            pos += len[(size_t)k];
-        }
-        const size_t end = (pos + 1) & ~(size_t)1;
-        if (end > payload_cap) { release(); return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_deflate_strips_u16: payload buffer too small"); }
-        OIP_DEFLATE_HIP(hipMemcpyAsync(d_off + s0, off.data() + s0, (size_t)ns * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
-        {
-            OipProfScope prof(ctx, "deflate_pack_kernel");
-            hipLaunchKernelGGL(tiff_pack_kernel, dim3((unsigned)ns), dim3(256), 0, ctx->stream, d_slots, slot_bytes, d_len, d_off, s0, nstrips, d_payload);
-        }
-        OIP_DEFLATE_HIP(hipGetLastError());
-        OIP_DEFLATE_HIP(hipStreamSynchronize(ctx->stream));                      // the slots and off[] are reused by the next launch
-    }
-#undef OIP_DEFLATE_HIP
-    release();
-    for (long k = 0; k < nstrips; ++k) { strip_off[k] = off[(size_t)k]; strip_len[k] = len[(size_t)k]; }
-    *payload_bytes = pos;
-    return OIP_OK;
+    return oip_tiff_encode(ctx, "oip_tiff_deflate_strips_u16", kOipTiffDeflate, d_img, rows, width, spp, rows_per_strip, d_payload, payload_cap, strip_off,
+                           strip_len, payload_bytes, d_scratch, scratch_bytes, [&](long s0, long ns, const OipTiffSlots &t) {
+        const size_t lds = sizeof(oipdeflate::Shared);
+        static_assert(sizeof(oipdeflate::Shared) <= 80 * 1024, "two workgroups of the encoder per CU");
+        // (above the 64 KiB a kernel gets without it; once a call, as before the launches of a call had one driver)
+        if (s0 == 0) OIP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(deflate_encode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        DeflateEncJob j{d_img, rows, width, spp, rows_per_strip, t.nstrips, s0, t.slots, t.slot_bytes, t.len};
+        OipProfScope prof(ctx, kOipTiffDeflate.encode_scope);
+        hipLaunchKernelGGL(deflate_encode_kernel, dim3((unsigned)ns), dim3(64), lds, ctx->stream, j);
+        return (int)OIP_OK;
+    });
 }

@@ -17,11 +17,10 @@
 // Every step is a dependent 8-byte load from a 2 GB region: the kernel is bound by HBM latency, not bandwidth -- ~1 us a
 // byte, 60 ms for any number of strips up to the 32768 a launch takes -- which is still eight times what the host cores did.
 // The encoded strips land in fixed slots (worst case: 1.5 bytes per byte); a second kernel packs them behind one another
-// (even offsets, as the host writer places them; oip_tiffpack.h) so that the payload leaves the device as one block.
+// (even offsets, as the host writer places them; oip_tiffencode.h) so that the payload leaves the device as one block.
 #include "oip_internal.h"
 #include "oip_tiffdecode.h"
-#include "oip_tiffpack.h"
-#include "oip_tiffshared.h"
+#include "oip_tiffencode.h"
 
 #include <cstdint>
 #include <vector>
@@ -29,7 +28,8 @@
 namespace {
 
 constexpr int kSlots = 8192;                     // per-lane table slots (4094 entries at most: load factor < 0.5)
-constexpr long kStripsPerLaunch = 32768;
+static_assert(kOipTiffLzw.table_bytes == kSlots * sizeof(unsigned long long), "the plan's scratch holds a lane's table");
+constexpr long kStripsPerLaunch = 32768;         // of the decoder
 
 struct LzwJob {
     const uint16_t *img;
@@ -120,7 +120,8 @@ __global__ __launch_bounds__(64) void lzw_strips_kernel(LzwJob j)
     s.out = j.slots + (size_t)local * j.slot_bytes;
     s.acc = 0; s.o = 0; s.nbits = 0; s.width = 9; s.next = 258; s.ent = -1; s.gen = 1;
     lzw_put(s, 256u);
-    const long r0 = k * j.rps;
+    const long r0 = k * j.rps;                   // (not tiff_strip_span: the loops want the end row, and from the row count the compiler
+                                                 // makes other instructions than these)
     long r1 = r0 + j.rps;
     if (r1 > j.rows) r1 = j.rows;
     const size_t rowSamples = (size_t)j.width * j.spp;
@@ -200,9 +201,8 @@ __global__ __launch_bounds__(64) void lzw_decode_kernel(LzwDecJob j)
     const uint8_t *in = j.file + j.off[k];
     const unsigned n = (unsigned)j.len[k];
     const size_t rowBytes = (size_t)j.width * j.spp * 2;
-    const long r0 = k * j.rps;
-    long nr = j.rows - r0;
-    if (nr > j.rps) nr = j.rps;
+    const OipStripSpan span = tiff_strip_span(k, j.rows, j.rps);
+    const long r0 = span.r0, nr = span.nr;
     uint8_t *out = reinterpret_cast<uint8_t *>(j.img) + (size_t)r0 * rowBytes;
     const unsigned cap = (unsigned)((size_t)nr * rowBytes);
     int width = 9, next = 258, status = 0;
@@ -252,10 +252,7 @@ __global__ __launch_bounds__(64) void lzw_decode_kernel(LzwDecJob j)
             unsigned long long *row = reinterpret_cast<unsigned long long *>(out + (size_t)r * rowBytes);
             unsigned long long prev = row[0];
             for (int x = 1; x < j.width; ++x) {
-                const unsigned long long d = row[x];
-                // four 16-bit adds in one register: the low 15 bits of every lane carry on their own, the top bits by xor
-                const unsigned long long m = 0x7fff7fff7fff7fffull;
-                prev = ((prev & m) + (d & m)) ^ ((prev ^ d) & ~m);
+                prev = padd16(prev, row[x]);
                 row[x] = prev;
             }
         }
@@ -271,33 +268,12 @@ __global__ __launch_bounds__(64) void lzw_decode_kernel(LzwDecJob j)
 
 extern "C" size_t oip_tiff_lzw_worst_bytes(long rows, int width, int spp, long rows_per_strip)
 {
-    if (rows <= 0 || width <= 0 || spp <= 0 || rows_per_strip <= 0) return 0;
-    const size_t strip = (size_t)rows_per_strip * width * spp * 2;
-    const size_t nstrips = ((size_t)rows + rows_per_strip - 1) / rows_per_strip;
-    return nstrips * (OIPGPU::tiffdetail::lzw_worst(strip) + 2);
-}
-
-// device scratch of one call: the lanes' tables, their output slots, the strip lengths and offsets
-static void lzw_scratch_layout(long nstrips, size_t slot_bytes, size_t *tab, size_t *slots, size_t *len, size_t *off, size_t *total)
-{
-    const long per = nstrips < kStripsPerLaunch ? nstrips : kStripsPerLaunch;
-    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-    *tab = 0;
-    *slots = up((size_t)per * kSlots * sizeof(unsigned long long));
-    *len = *slots + up((size_t)per * slot_bytes);
-    *off = *len + up((size_t)nstrips * sizeof(unsigned));
-    *total = *off + up((size_t)nstrips * sizeof(unsigned long long));
+    return plan_tiff_encode(kOipTiffLzw, rows, width, spp, rows_per_strip).worst_bytes;
 }
 
 extern "C" size_t oip_tiff_lzw_scratch_bytes(long rows, int width, int spp, long rows_per_strip)
 {
-    if (rows <= 0 || width <= 0 || spp <= 0 || rows_per_strip <= 0) return 0;
-    const long nstrips = (rows + rows_per_strip - 1) / rows_per_strip;
-    const size_t strip = (size_t)rows_per_strip * width * spp * 2;
-    const size_t slot_bytes = (OIPGPU::tiffdetail::lzw_worst(strip) + 3) / 4 * 4;
-    size_t a, b, c, d, total;
-    lzw_scratch_layout(nstrips, slot_bytes, &a, &b, &c, &d, &total);
-    return total;
+    return plan_tiff_encode(kOipTiffLzw, rows, width, spp, rows_per_strip).scratch_bytes;
 }
 
 extern "C" int oip_tiff_lzw_strips_u16(oip_ctx *ctx, const uint16_t *d_img, long rows, int width, int spp, long rows_per_strip,
@@ -305,79 +281,21 @@ extern "C" int oip_tiff_lzw_strips_u16(oip_ctx *ctx, const uint16_t *d_img, long
                                        size_t *payload_bytes, void *d_scratch, size_t scratch_bytes)
 {
     OIP_CHECK_CTX(ctx);
-    if (!d_img || !d_payload || !strip_off || !strip_len || !payload_bytes || rows <= 0 || width <= 0 || (spp != 1 && spp != 4) ||
-        rows_per_strip <= 0)
-        return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_lzw_strips_u16: bad argument");
-    if (spp == 4 && (((uintptr_t)d_img) & 7)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_lzw_strips_u16: image not 8-byte aligned");
-    if ((((uintptr_t)d_payload) & 1)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_lzw_strips_u16: payload not 2-byte aligned");
-    const long nstrips = (rows + rows_per_strip - 1) / rows_per_strip;
-    const size_t strip = (size_t)rows_per_strip * width * spp * 2;
-    if (strip > (1u << 30)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_lzw_strips_u16: strip larger than 1 GiB");
-    const size_t slot_bytes = (OIPGPU::tiffdetail::lzw_worst(strip) + 3) / 4 * 4;
-    const long per = nstrips < kStripsPerLaunch ? nstrips : kStripsPerLaunch;
-    size_t o_tab, o_slots, o_len, o_off, need;
-    lzw_scratch_layout(nstrips, slot_bytes, &o_tab, &o_slots, &o_len, &o_off, &need);
-    void *own = nullptr;                         // scratch of this call's own when the caller brought none
-    auto release = [&] { if (own) (void)hipFree(own); };
-#define OIP_LZW_HIP(call)                                                                                     \
-    do {                                                                                                      \
-        hipError_t e__ = (call);                                                                              \
-        if (e__ != hipSuccess) {                                                                              \
-            release();                                                                                        \
-            return oip_fail(ctx, OIP_E_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-        }                                                                                                     \
-    } while (0)
-    if (d_scratch) {
-        if (scratch_bytes < need || (((uintptr_t)d_scratch) & 7)) return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_lzw_strips_u16: scratch too small or misaligned");
-    } else {
-        OIP_LZW_HIP(hipMalloc(&own, need));
-        d_scratch = own;
-    }
-    unsigned long long *d_tab = reinterpret_cast<unsigned long long *>((char *)d_scratch + o_tab);
-    uint8_t *d_slots = reinterpret_cast<uint8_t *>((char *)d_scratch + o_slots);
-    unsigned *d_len = reinterpret_cast<unsigned *>((char *)d_scratch + o_len);
-    unsigned long long *d_off = reinterpret_cast<unsigned long long *>((char *)d_scratch + o_off);
-    std::vector<unsigned> len((size_t)nstrips);
-    std::vector<unsigned long long> off((size_t)nstrips);
-    size_t pos = 0;
-    for (long s0 = 0; s0 < nstrips; s0 += per) {
-        const long ns = nstrips - s0 < per ? nstrips - s0 : per;
+    return oip_tiff_encode(ctx, "oip_tiff_lzw_strips_u16", kOipTiffLzw, d_img, rows, width, spp, rows_per_strip, d_payload, payload_cap, strip_off, strip_len,
+                           payload_bytes, d_scratch, scratch_bytes, [&](long s0, long ns, const OipTiffSlots &t) {
         // Lanes of a wave that take a strip.  A wave steps at the pace of its slowest lane -- the longest probe chain, a code to
         // flush -- so 64 coders in lockstep are slower than 4 (116 -> 86 ms at 25000 strips, 76 -> 45 ms at 2000: the vector ALU
         // idles either way, and more, emptier waves give the memory system more independent chains to overlap).
         const int active = 4;
-        LzwJob j{d_img, rows, width, spp, rows_per_strip, nstrips, s0, d_slots, slot_bytes, d_tab, d_len, active};
+        LzwJob j{d_img, rows, width, spp, rows_per_strip, t.nstrips, s0, t.slots, t.slot_bytes, reinterpret_cast<unsigned long long *>(t.tables), t.len, active};
         // No slot is read before the lane's occupancy bit says it was written in the current generation, so the tables need no
         // initial VALUE -- but memory fresh from hipMalloc is first touched far cheaper by a linear fill than by the kernel's
         // scattered stores (a launch on untouched scratch: 250-350 ms instead of 90-120); tables and output slots alike.
-        if (s0 == 0) OIP_LZW_HIP(hipMemsetAsync(d_scratch, 0, o_len, ctx->stream));
-        {
-            OipProfScope prof(ctx, "lzw_strips_kernel");
-            hipLaunchKernelGGL(lzw_strips_kernel, dim3((unsigned)((ns + active - 1) / active)), dim3(64), (size_t)active * (kSlots / 32) * 4, ctx->stream, j);
-        }
-        OIP_LZW_HIP(hipGetLastError());
-        OIP_LZW_HIP(hipMemcpyAsync(len.data() + s0, d_len + s0, (size_t)ns * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-        OIP_LZW_HIP(hipStreamSynchronize(ctx->stream));
-        for (long k = s0; k < s0 + ns; ++k) {
-            if (pos & 1) ++pos;                                                  // strips start on even offsets (oip_tiff.hpp)
-            off[(size_t)k] = pos;
-            pos += len[(size_t)k];
-        }
-        const size_t end = (pos + 1) & ~(size_t)1;
-        if (end > payload_cap) { release(); return oip_fail(ctx, OIP_E_INVALID, "oip_tiff_lzw_strips_u16: payload buffer too small"); }
-        OIP_LZW_HIP(hipMemcpyAsync(d_off + s0, off.data() + s0, (size_t)ns * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
-        {
-            OipProfScope prof(ctx, "lzw_pack_kernel");
-            hipLaunchKernelGGL(tiff_pack_kernel, dim3((unsigned)ns), dim3(256), 0, ctx->stream, d_slots, slot_bytes, d_len, d_off, s0, nstrips, d_payload);
-        }
-        OIP_LZW_HIP(hipGetLastError());
-        OIP_LZW_HIP(hipStreamSynchronize(ctx->stream));                          // the slots and off[] are reused by the next launch
-    }
-#undef OIP_LZW_HIP
-    release();
-    for (long k = 0; k < nstrips; ++k) { strip_off[k] = off[(size_t)k]; strip_len[k] = len[(size_t)k]; }
-    *payload_bytes = pos;
-    return OIP_OK;
+        if (s0 == 0) OIP_HIP(ctx, hipMemsetAsync(t.tables, 0, t.launch_bytes, ctx->stream));
+        OipProfScope prof(ctx, kOipTiffLzw.encode_scope);
+        hipLaunchKernelGGL(lzw_strips_kernel, dim3((unsigned)((ns + active - 1) / active)), dim3(64), (size_t)active * (kSlots / 32) * 4, ctx->stream, j);
+        return (int)OIP_OK;
+    });
 }
 
 static const char *lzw_reason(int status)
@@ -392,7 +310,7 @@ extern "C" int oip_tiff_lzw_decode_u16(oip_ctx *ctx, const uint8_t *d_file, size
 {
     OIP_CHECK_CTX(ctx);
     const long per = nstrips < kStripsPerLaunch ? nstrips : kStripsPerLaunch;                       // (a lane: 4096 table entries)
-    return oip_tiff_decode(ctx, "oip_tiff_lzw_decode_u16", "LZW", lzw_reason, (uint64_t)1 << 32, per > 0 ? (size_t)per * 4096 * 8 : 0, d_file, file_bytes,
+    return oip_tiff_decode(ctx, "oip_tiff_lzw_decode_u16", kOipTiffLzw.name, lzw_reason, (uint64_t)1 << 32, per > 0 ? (size_t)per * 4096 * 8 : 0, d_file, file_bytes,
                            strip_off, strip_len, nstrips, rows, width, spp, rows_per_strip, predictor, d_img, [&](const OipTiffStreams &t) {
         for (long s0 = 0; s0 < nstrips; s0 += per) {
             const long ns = nstrips - s0 < per ? nstrips - s0 : per;

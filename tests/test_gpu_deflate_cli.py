@@ -1,7 +1,7 @@
 """GPU: the tools on Deflate TIFFs.  `oip quicklook`, `oip overviews` and `oip cog` write for a Deflate strip file and for a Deflate
 tiled file (written here with zlib: tests/_deflate_tiff.py) the bytes they write for the uncompressed TIFF of the same pixels --
 with the streams inflated on the device, and with OIP_TIFF_GPU_DEFLATE=0 on the host's threads.  The device takes a file of at
-least 256 streams of at most 2 MiB (csrc/oip_host.hpp::read_tiff_to_device), so the device files here are strips of one row and
+least 256 streams of at most 2 MiB (csrc/oip_tiffstreams.h::tiff_streams_on_device), so the device files here are strips of one row and
 tiles of 16; files of a few streams go to the host whatever the switch says.  A corrupt tile ends the run with exit code 2 and the
 tile named -- in the words of the route that met it, which is also how these tests know the route."""
 import hashlib

@@ -10,6 +10,7 @@ import torch
 
 import opticalimageprocessor_amd as oip
 import _deflate_write_ref as R
+import _tiff_boundary as B
 
 pytestmark = pytest.mark.gpu
 
@@ -122,3 +123,27 @@ def test_refusals_launch_nothing(ctx):
     assert (payload.cpu().numpy() == PATTERN).all()
     off, ln, total = ctx.tiff_deflate_strips(d_img, rows, width, spp, rps, payload, scratch=scratch)
     assert total > 0 and zlib.decompress(payload[:int(ln[0])].cpu().numpy().tobytes()) == R.strip_bytes(img, spp, rps=rps)[0]
+
+
+@pytest.mark.parametrize("own_scratch", [True, False], ids=["own_scratch", "callers_scratch"])
+def test_strips_across_the_launch_boundary(ctx, own_scratch):
+    """32770 one-row strips: launches of 32768 and 2 (tests/_tiff_boundary.py).  Stream 32767 is odd by the host coder's count, so the
+    second launch's first offset carries the pad byte of the first launch's last stream."""
+    rows = B.rows_named(["zero", "noise16", "const", "small", "noise12"])
+    streams = [oip.deflate_stream_host(B.predict2(r)) for r in rows]
+    for r, z in zip(rows, streams):
+        assert zlib.decompress(z) == B.predict2(r)
+    B.check_two_launches(ctx, ctx.tiff_deflate_strips, ctx.tiff_deflate_worst_bytes, ctx.tiff_deflate_scratch_bytes, rows, B.WIDTH, 1,
+                         B.pattern_of_rows(len(rows)), streams, own_scratch)
+
+
+def test_misaligned_scratch_is_refused(ctx):
+    rows, width, spp, rps = 8, 64, 4, 2
+    d_img = torch.zeros(rows * width * spp, dtype=torch.int16, device="cuda")
+    payload = torch.full((ctx.tiff_deflate_worst_bytes(rows, width, spp, rps),), PATTERN, dtype=torch.uint8, device="cuda")
+    need = ctx.tiff_deflate_scratch_bytes(rows, width, spp, rps)
+    scratch = torch.zeros(need + 8, dtype=torch.uint8, device="cuda")
+    with pytest.raises(ValueError, match="scratch too small or misaligned"):
+        ctx.tiff_deflate_strips(d_img, rows, width, spp, rps, payload, scratch=scratch[4:], scratch_bytes=need)
+    ctx.sync()
+    assert (payload.cpu().numpy() == PATTERN).all()

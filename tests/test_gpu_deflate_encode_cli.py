@@ -2,7 +2,7 @@
 _cog_ref.py and _overview_ref.py describe with zlib streams as tiles; strip products (overviews, denoise, the default action, stitch)
 hold the pixels of their uncompressed runs; a file is the same bytes whoever encoded its streams -- the device (OIP_TIFF_GPU_DEFLATE=2
 sends every layout the device encoder takes there; by default files of fewer than 256 streams or of streams above 512 KiB go to the host's threads,
-csrc/oip_host.hpp), the host (=0) -- and however it was cut into batches and blocks; the tools read back what they wrote; and a run
+csrc/oip_tiffstreams.h), the host (=0) -- and however it was cut into batches and blocks; the tools read back what they wrote; and a run
 without the option writes what it wrote before the option took `deflate`.  The reader is tests/_deflate_write_ref.py (Python's zlib)."""
 import hashlib
 import os

@@ -10,6 +10,7 @@ import torch
 
 import _lzw_cases as L
 import _tiff
+import _tiff_boundary as B
 
 pytestmark = pytest.mark.gpu
 
@@ -333,3 +334,50 @@ def test_device_lzw_on_tiny_strips(ctx, rows, width, spp, rps):
     assert np.array_equal(_device_decode(ctx, want, rows, width, spp, rps, 2), img)
     plain = [_tiff.lzw_encode(img[k:k + rps].astype("<u2").tobytes()) for k in range(0, rows, rps)]
     assert np.array_equal(_device_decode(ctx, plain, rows, width, spp, rps, 1), img)
+
+
+# ---- the driver around the coder: two launches, refusals before anything runs ------------------------------------------------------
+@pytest.mark.parametrize("own_scratch", [True, False], ids=["own_scratch", "callers_scratch"])
+def test_device_lzw_across_the_launch_boundary(ctx, own_scratch):
+    """32770 one-row strips: launches of 32768 and 2 (tests/_tiff_boundary.py).  Strip 32767 is odd, so the second launch's first
+    offset carries the pad byte of the first launch's last strip."""
+    rows = B.rows_named(["zero", "const", "noise16", "small", "ramp"])
+    streams = [_tiff.lzw_encode(B.predict2(r)) for r in rows]
+    B.check_two_launches(ctx, ctx.tiff_lzw_strips, ctx.tiff_lzw_worst_bytes, ctx.tiff_lzw_scratch_bytes, rows, B.WIDTH, 1,
+                         B.pattern_of_rows(len(rows)), streams, own_scratch)
+
+
+def test_device_lzw_refusals_launch_nothing(ctx):
+    """the twin of test_gpu_deflate_encode.py::test_refusals_launch_nothing"""
+    rows, width, spp, rps = 8, 64, 4, 2
+    img = _image("noise12", rows, width, spp, seed=3)
+    d_img = torch.from_numpy(img.view(np.int16)).cuda()
+    worst = ctx.tiff_lzw_worst_bytes(rows, width, spp, rps)
+    payload = torch.full((worst,), B.PATTERN, dtype=torch.uint8, device="cuda")
+    need = ctx.tiff_lzw_scratch_bytes(rows, width, spp, rps)
+    scratch = torch.zeros(need, dtype=torch.uint8, device="cuda")
+    with pytest.raises(ValueError):
+        ctx.tiff_lzw_strips(d_img, rows, width, spp, rps, payload, payload_cap=worst - 1)
+    with pytest.raises(ValueError):
+        ctx.tiff_lzw_strips(d_img, rows, width, spp, rps, payload, scratch=scratch, scratch_bytes=need - 1)
+    with pytest.raises(ValueError):
+        ctx.tiff_lzw_strips(d_img, rows, width, 3, rps, payload)
+    with pytest.raises(ValueError):
+        ctx.tiff_lzw_strips(d_img, rows, 0, spp, rps, payload)
+    assert ctx.tiff_lzw_worst_bytes(rows, 0, spp, rps) == 0 and ctx.tiff_lzw_scratch_bytes(0, width, spp, rps) == 0
+    ctx.sync()
+    assert (payload.cpu().numpy() == B.PATTERN).all()
+    off, ln, total = ctx.tiff_lzw_strips(d_img, rows, width, spp, rps, payload, scratch=scratch)
+    assert total > 0 and _tiff.lzw_decode(payload[:int(ln[0])].cpu().numpy().tobytes()) == _predict(img[:rps], spp)
+
+
+def test_device_lzw_refuses_misaligned_scratch(ctx):
+    rows, width, spp, rps = 8, 64, 4, 2
+    d_img = torch.zeros(rows * width * spp, dtype=torch.int16, device="cuda")
+    payload = torch.full((ctx.tiff_lzw_worst_bytes(rows, width, spp, rps),), B.PATTERN, dtype=torch.uint8, device="cuda")
+    need = ctx.tiff_lzw_scratch_bytes(rows, width, spp, rps)
+    scratch = torch.zeros(need + 8, dtype=torch.uint8, device="cuda")
+    with pytest.raises(ValueError, match="scratch too small or misaligned"):
+        ctx.tiff_lzw_strips(d_img, rows, width, spp, rps, payload, scratch=scratch[4:], scratch_bytes=need)
+    ctx.sync()
+    assert (payload.cpu().numpy() == B.PATTERN).all()
