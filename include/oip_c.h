@@ -1072,6 +1072,71 @@ int oip_tiff_deflate_strips_u16(oip_ctx *ctx, const uint16_t *d_img, long rows, 
  * 0xFFFF0000 or more, or when a pointer is null.  No alignment is asked of either buffer; nothing past either is touched. */
 size_t oip_deflate_stream_host(const uint8_t *src, size_t n, uint8_t *dst, size_t cap);
 
+/* ---- JPEG: the browse image of `oip quicklook --format jpeg` as a JFIF file, its scan encoded on the device (not in the
+ * reference).  Baseline sequential DCT (ITU-T T.81 SOF0) in a JFIF 1.01 wrapper: 8 bits a sample; 1 component (grey) or 3 (Y, Cb,
+ * Cr, 4:4:4: one 8 x 8 block per component per MCU); the four typical Huffman tables of T.81 Annex K.3; a DRI segment with a
+ * restart interval of exactly one MCU row, ceil(w / 8) MCUs, RST0..RST7 cycling between the intervals and none before EOI.  An
+ * interval reads its own 8 image lines and nothing else, so the intervals are independent streams: one wave of the device each
+ * (csrc/jpeg.hip) running the coder the host instantiation runs (csrc/oip_jpeg.h; no libjpeg).  The arithmetic, all of it exact
+ * integers (>> is an arithmetic shift, / truncates; tests/_jpeg_ref.py restates it):
+ *   colour    (3 channels, from interleaved R, G, B bytes; the results lie in 0..255 without a clamp)
+ *               Y  = ( 19595 R + 38470 G +  7471 B +   32768) >> 16
+ *               Cb = (-11058 R - 21710 G + 32768 B + 8421375) >> 16
+ *               Cr = ( 32768 R - 27439 G -  5329 B + 8421375) >> 16
+ *   padding   the image is extended to multiples of 8 by repeating its last column, then its last line.
+ *   DCT       T[k][n] = rint(8192 c_k cos((2n + 1) k pi / 16)), c_0 = sqrt(1/8), c_k = 1/2 otherwise:
+ *               k = 0:  2896  2896  2896  2896  2896  2896  2896  2896      k = 4:  2896 -2896 -2896  2896  2896 -2896 -2896  2896
+ *               k = 1:  4017  3406  2276   799  -799 -2276 -3406 -4017      k = 5:  2276 -4017   799  3406 -3406  -799  4017 -2276
+ *               k = 2:  3784  1567 -1567 -3784 -3784 -1567  1567  3784      k = 6:  1567 -3784  3784 -1567 -1567  3784 -3784  1567
+ *               k = 3:  3406  -799 -4017 -2276  2276  4017   799 -3406      k = 7:   799 -2276  3406 -4017  4017 -3406  2276  -799
+ *             rows of a block, samples s[0..7]:   t[k] = (sum_n T[k][n] (s[n] - 128) + 512) >> 10
+ *             then its columns, t[0..7] of a column:   F[k] = (sum_m T[k][m] t[m] + 32768) >> 16
+ *             (int32 holds it: |row sum| <= 128 * 8 * 4017, |column sum| <= 8 * 4017^2; |DC| <= 1024, |AC| <= 1020)
+ *   tables    the IJG rule on the base tables of Annex K.1 (Y, grey) and K.2 (Cb, Cr):
+ *               scale = Q < 50 ? 5000 / Q : 200 - 2 Q,   q = clamp((base * scale + 50) / 100, 1, 255)
+ *   quantise  sign(F) ((2 |F| + q) / (2 q))
+ *   entropy   T.81 F.1.2: the DC difference against the previous block of the same component, 0 at the start of each interval;
+ *             AC run/size symbols with ZRL and EOB, no EOB when coefficient 63 is not zero; bits MSB first, a 0xFF byte followed
+ *             by 0x00, each interval padded with 1-bits to a byte.
+ *   file      SOI; APP0 "JFIF", version 1.01, no units, density 1 : 1, no thumbnail; one DQT per table in use (8-bit entries,
+ *             table 0 and for 3 channels table 1); SOF0 (components 1..nch, sampling 1 x 1, tables 0, 1, 1); one DHT per table in
+ *             use (DC 0, AC 0 and for 3 channels DC 1, AC 1); DRI; SOS (Ss 0, Se 63, Ah Al 0); the intervals with RST(k mod 8)
+ *             behind interval k but the last; EOI.
+ *   function  the bytes of an interval depend on its own 8 lines, nch and the quality alone: not on the launch, the interval's
+ *             index, the pitch, any alignment, or on whether the host or the device ran the coder.
+ *
+ * oip_jpeg_scan_u8 encodes the scan of d_img (device; h lines of w pixels of nch interleaved bytes, lines pitch_bytes apart; read,
+ * never written; no alignment asked) into d_payload (device): interval k, without its RSTn, at interval_off[k] with
+ * interval_len[k] bytes (host arrays of ceil(h / 8) entries), packed behind one another in order; *payload_bytes ends the last.
+ * All offsets are 64-bit.  A coefficient costs at most 26 bits, doubled by stuffing 416 bytes a block:
+ * oip_jpeg_worst_bytes() = ceil(h / 8) * ceil(w / 8) * nch * 416 is the capacity the caller proves (0 for arguments the scan
+ * refuses).  The coder runs twice -- measuring, then storing every interval at the running sum of the lengths, each store bounded by
+ * the measured length -- so no more than *payload_bytes of the payload is ever written.  d_scratch (8-byte aligned, at least
+ * oip_jpeg_scratch_bytes(): the tables, lengths and offsets, and in its last 40 bytes five uint64 counters, the cycles the waves of
+ * the storing pass spent staging, transforming, counting bits, placing codes and stuffing -- a profile's input
+ * (profiles/jpeg_bench.py), no part of the contract) may be NULL: the call then allocates its own.  OIP_E_INVALID with
+ * nothing launched for a null pointer, w or h outside 1..65535, nch other than 1 or 3, quality outside 1..100, pitch_bytes <
+ * w * nch, payload_cap below the bound, a scratch buffer too small or misaligned.  Synchronises the context's stream. */
+size_t oip_jpeg_worst_bytes(int w, long h, int nch);
+size_t oip_jpeg_scratch_bytes(int w, long h, int nch);
+int oip_jpeg_scan_u8(oip_ctx *ctx, const uint8_t *d_img, long pitch_bytes, int w, long h, int nch, int quality,
+                     uint8_t *d_payload, size_t payload_cap, uint64_t *interval_off, uint64_t *interval_len,
+                     size_t *payload_bytes, void *d_scratch, size_t scratch_bytes);
+
+/* The same coder in its host instantiation, for one interval and without a context: interval `interval` (0 .. ceil(h / 8) - 1) of
+ * the host image img into dst[0, cap).  Returns its size, or 0 when cap is too small (never when cap >= ceil(w / 8) * nch * 416) or
+ * an argument is one the scan refuses.  Nothing past either buffer is touched. */
+size_t oip_jpeg_interval_host(const uint8_t *img, long pitch_bytes, int w, long h, int nch, int quality, long interval,
+                              uint8_t *dst, size_t cap);
+
+/* The JFIF file of a scan, host: the headers above, the intervals of `payload` (host) with their RSTn, EOI.  An existing file is
+ * replaced.  OIP_E_INVALID for a null pointer or geometry and quality the scan refuses, OIP_E_IO (errno in the message) where the
+ * file cannot be written.  No context needed. */
+#define OIP_JPEG_DEF_QUALITY 90   /* of `oip quicklook --format jpeg`: a convention, nothing measured */
+#define OIP_JPEG_MAX_DIM     65535
+int oip_write_jpeg_u8(const char *path, const uint8_t *payload, const uint64_t *interval_off, const uint64_t *interval_len,
+                      int w, long h, int nch, int quality, char *err, int errlen);
+
 /* ---- overviews: reduced-resolution levels of a strip or product (`oip overviews`; not in the reference) ---- */
 #define OIP_OVERVIEW_SUFFIX ".ovr"   /* appended to the whole file name, GDAL's external-overview convention */
 

@@ -39,6 +39,8 @@ from .capi import (  # noqa: F401
     overview_levels,
     deflate_stored_bound,
     deflate_stream_host,
+    jpeg_interval_host,
+    jpeg_worst_bytes,
     pansharpen_geometry,
     polyfit,
     regfix_fill,
@@ -57,6 +59,7 @@ from .capi import (  # noqa: F401
     warp_grid_src_range,
     write_column_list,
     write_rrc_param_file,
+    write_jpeg_u8,
     write_tiff_u8,
     align_mss_src_range,
 )

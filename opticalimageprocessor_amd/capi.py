@@ -92,6 +92,11 @@ _SIGS = {
     "oip_tiff_deflate_scratch_bytes": ([_l, _i, _i, _l], _sz),
     "oip_tiff_deflate_strips_u16": ([_vp, _vp, _l, _i, _i, _l, _vp, _sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_sz), _vp, _sz], _i),
     "oip_deflate_stream_host": ([_vp, _sz, _vp, _sz], _sz),
+    "oip_jpeg_worst_bytes": ([_i, _l, _i], _sz),
+    "oip_jpeg_scratch_bytes": ([_i, _l, _i], _sz),
+    "oip_jpeg_scan_u8": ([_vp, _vp, _l, _i, _l, _i, _i, _vp, _sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_sz), _vp, _sz], _i),
+    "oip_jpeg_interval_host": ([_vp, _l, _i, _l, _i, _i, _l, _vp, _sz], _sz),
+    "oip_write_jpeg_u8": ([_cp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i, _l, _i, _i, _cp, _i], _i),
     "oip_upload_staged": ([_vp, _vp, _vp, _sz, _lp], _i),
     "oip_upload_staged_2d": ([_vp, _vp, _sz, _vp, _sz, _sz, _sz, _lp], _i),
     "oip_download_staged": ([_vp, _vp, _vp, _sz], _i),
@@ -668,6 +673,34 @@ def deflate_stream_host(data, cap: int = None) -> bytes:
     return bytes(dst[:size])
 
 
+def jpeg_worst_bytes(w: int, h: int, nch: int) -> int:
+    """the payload capacity oip_jpeg_scan_u8 asks for: 416 bytes a block (include/oip_c.h); 0 for a geometry it refuses"""
+    return int(load_library().oip_jpeg_worst_bytes(w, h, nch))
+
+
+def jpeg_interval_host(img, quality: int, interval: int, cap: int = None) -> bytes:
+    """interval `interval` of a (h, w) or (h, w, 3) uint8 image by the host instantiation of the JPEG coder (include/oip_c.h:
+    oip_jpeg_interval_host); cap: the room it is given (default: the bound).  b"" where it does not fit or is refused."""
+    a = np.ascontiguousarray(img, dtype=np.uint8)
+    h, w, nch = a.shape[0], a.shape[1], 1 if a.ndim == 2 else a.shape[2]
+    cap = (w + 7) // 8 * nch * 416 if cap is None else cap
+    dst = (C.c_uint8 * max(cap, 1))()
+    size = load_library().oip_jpeg_interval_host(a.ctypes.data, w * nch, w, h, nch, quality, interval, dst, cap)
+    return bytes(dst[:size])
+
+
+def write_jpeg_u8(path: str, payload, interval_off, interval_len, w: int, h: int, nch: int, quality: int) -> None:
+    """the JFIF file of a scan (include/oip_c.h: oip_write_jpeg_u8); payload: host bytes or a uint8 array"""
+    a = np.ascontiguousarray(np.frombuffer(payload, dtype=np.uint8) if isinstance(payload, (bytes, bytearray)) else payload, dtype=np.uint8)
+    n = len(interval_off)
+    off = (C.c_uint64 * n)(*[int(v) for v in interval_off])
+    ln = (C.c_uint64 * n)(*[int(v) for v in interval_len])
+    err = C.create_string_buffer(1024)
+    rc = load_library().oip_write_jpeg_u8(os.fsencode(path), a.ctypes.data, off, ln, w, h, nch, quality, err, 1024)
+    if rc:
+        raise _STATUS_EXC.get(rc, OipError)(err.value.decode())
+
+
 MATCH_RECORD_WORDS = 20
 MATCH_NODATA, MATCH_FLAT, MATCH_EDGE, MATCH_WEAK = 1, 2, 4, 8
 
@@ -1069,6 +1102,27 @@ class Context:
 
     def tiff_deflate_worst_bytes(self, rows, width, spp, rows_per_strip):
         return int(self.lib.oip_tiff_deflate_worst_bytes(rows, width, spp, rows_per_strip))
+
+    def jpeg_scan(self, img, pitch_bytes, w, h, nch, quality, payload, scratch=None, payload_cap=None, scratch_bytes=None, byte_offset=0):
+        """the scan of a baseline JPEG of a device image (uint8, from `byte_offset` on) into `payload` (device, uint8), an interval per
+        row of 8 x 8 blocks (include/oip_c.h: oip_jpeg_scan_u8); returns (offsets, lengths, payload_bytes)"""
+        n = max((h + 7) // 8, 1)
+        off = (C.c_uint64 * n)()
+        ln = (C.c_uint64 * n)()
+        total = C.c_size_t()
+        if payload_cap is None:
+            payload_cap = payload.numel() * payload.element_size()
+        if scratch_bytes is None:
+            scratch_bytes = scratch.numel() * scratch.element_size() if scratch is not None else 0
+        self._ck(self.lib.oip_jpeg_scan_u8(self.h, _ptr(img) + byte_offset if img is not None else None, pitch_bytes, w, h, nch, quality, _ptr(payload), payload_cap, off, ln,
+                                           C.byref(total), _ptr(scratch) if scratch is not None else None, scratch_bytes))
+        return np.array(off[:], dtype=np.uint64), np.array(ln[:], dtype=np.uint64), total.value
+
+    def jpeg_scratch_bytes(self, w, h, nch):
+        return int(self.lib.oip_jpeg_scratch_bytes(w, h, nch))
+
+    def jpeg_worst_bytes(self, w, h, nch):
+        return int(self.lib.oip_jpeg_worst_bytes(w, h, nch))
 
     def tiff_lzw_scratch_bytes(self, rows, width, spp, rows_per_strip):
         return int(self.lib.oip_tiff_lzw_scratch_bytes(rows, width, spp, rows_per_strip))

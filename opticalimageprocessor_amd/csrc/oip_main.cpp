@@ -11,6 +11,7 @@
 //   oip rrc-calib [--pan P.RAW --rrc-pan OUT] [--mss M.RAW --rrc-msb1..4 OUT]   derives the RRC coefficient files the
 //                               actions above read from a strip's per-column statistics, see run_rrc_calib()
 //   oip quicklook IMAGE [-o OUT.TIFF] [--factor 16 ...]   8-bit browse image of a strip or product, see run_quicklook()
+//                 [--format jpeg [--quality 90]]            ... as a baseline JPEG (<stem>.QL.JPG), its scan encoded on the GPU
 //   oip mtfc IMAGE [-o OUT] (--kernel FILE | --mtf-x M --mtf-y M)   MTF-compensation filter of a strip or product, see run_mtfc()
 //   oip despike IMAGE [-o OUT] [--threshold N] [--relative R] [--bad-columns FILE] [--bil]   repair of a raw strip ahead of RRC:
 //                               bad columns interpolated, impulse pixels replaced by a conditional 3 x 3 median, see run_despike();
@@ -233,6 +234,8 @@ void usage()
          "             [--bad-pan OUT] [--bad-mss OUT] the columns without usable statistics (dead detectors), as despike --bad-columns reads them\n"
          "  quicklook  IMAGE.RAW|IMAGE.TIFF: an 8-bit browse image, box-decimated by --factor and contrast-stretched per band\n"
          "             between two percentiles of its valid samples; written to <stem>.QL.TIFF in the working directory:\n"
+         "             [--format tiff|jpeg] (default tiff, uncompressed; jpeg: a baseline JFIF file, <stem>.QL.JPG, its scan encoded on\n"
+         "             the GPU, at most 65535 x 65535 pixels) [--quality Q] (with --format jpeg; 1 <= Q <= 100, default 90)\n"
          "             [-o,--out FILE] [--factor 2|4|8|16|32|64] [--clip-low P] [--clip-high P] [--valid-min N] [--valid-max N]\n"
          "             [--bands A | A,B,C] [--bil] (RAW: the MSS line layout) [--width N] [--line-offset N] [--lines N] [--force]\n"
          "  mtfc       IMAGE.RAW|IMAGE.TIFF: MTF compensation, a fixed-point restoration filter of up to 9 x 9 taps; the output has\n"
@@ -683,16 +686,23 @@ int run_rrc_calib(const std::vector<std::string> &args, int width)
 }
 
 // oip quicklook IMAGE: the browse image of a strip (.RAW, with --bil the MSS line layout) or a product (.TIFF of 1 or 4
-// samples).  IMAGE is the one positional argument of the tool.
+// samples), an uncompressed TIFF or with --format jpeg a baseline JPEG.  IMAGE is the one positional argument of the tool.
 int run_quicklook(const std::vector<std::string> &args, int width)
 {
     Spec sp;
-    sp.valued = {"--out", "--factor", "--clip-low", "--clip-high", "--valid-min", "--valid-max", "--bands", "--width", "--line-offset", "--lines"};
+    sp.valued = {"--out", "--factor", "--clip-low", "--clip-high", "--valid-min", "--valid-max", "--bands", "--width", "--line-offset", "--lines", "--format",
+                 "--quality"};
     sp.flags = {"--bil", "--force"};
     sp.alias = {{"-o", "--out"}};
     std::string image;
     Parsed p = parse_with_image(sp, args, &image);
     QuicklookOptions o;
+    const std::string format = p.str("--format", "tiff");
+    if (format != "tiff" && format != "jpeg") throw cli_error(105, "--format: tiff or jpeg expected");
+    o.jpeg = format == "jpeg";
+    if (p.has("--quality") && !o.jpeg) throw cli_error(107, "--quality requires --format jpeg");
+    o.quality = p.integer("--quality", OIP_JPEG_DEF_QUALITY);
+    if (o.quality < 1 || o.quality > 100) throw cli_error(105, "--quality: 1 <= Q <= 100 expected");
     o.width = p.integer("--width", width);
     o.bil = p.has("--bil");
     o.factor = p.integer("--factor", OIP_QUICKLOOK_DEF_FACTOR);

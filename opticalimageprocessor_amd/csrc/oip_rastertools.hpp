@@ -319,7 +319,9 @@ inline void RunRrcCalib(const std::string &pan, const std::string &mss, const st
 // The products are too large to look at (a stitched PAN strip is ~4.8 GB of 12-bit values in 16-bit samples): one read-only
 // pass box-decimates the image by F x F (oip_decimate_box_u16), and everything behind it works on planes F^2 times smaller --
 // per band a histogram (oip_histogram_u16), percentile limits and an 8-bit table on the host (oip_stretch_limits,
-// oip_stretch_lut_u8), one look-up kernel (oip_apply_lut_u8) and an uncompressed 8-bit TIFF.  Not in the reference.
+// oip_stretch_lut_u8), one look-up kernel (oip_apply_lut_u8) and an uncompressed 8-bit TIFF -- or, with --format jpeg, a JFIF
+// file whose scan is encoded where the 8-bit image lies (oip_jpeg_scan_u8): only the payload and the interval table come back
+// to the host.  Not in the reference.
 struct QuicklookOptions {
     int width = OIP_PIXELS_PER_LINE;        // RAW input: samples per line
     bool bil = false;                       // RAW input: the MSS line layout, 4 bands of width / 4 next to each other
@@ -329,6 +331,8 @@ struct QuicklookOptions {
     std::vector<int> bands;                 // 1-based; empty: 1 for one band, 1,2,3 for four
     long lineOffset = 0, lines = 0;         // lines == 0: to the end of the image
     bool force = false;
+    bool jpeg = false;                      // --format jpeg: <stem>.QL.JPG instead of <stem>.QL.TIFF
+    int quality = OIP_JPEG_DEF_QUALITY;
 };
 
 // what is refused without a device and stated here alone: --factor and --bands, --width with --bil, the output; returns the
@@ -348,8 +352,9 @@ inline std::string QuicklookCheck(const std::string &file, const std::string &ou
         for (int b : o.bands)
             if (b < 1 || b > MSS_BANDS) throw usage_error("--bands: band index out of range (1.." + std::to_string(MSS_BANDS) + ")");
     }
-    // (not FilterOutputPath: a quick look is a .TIFF whatever the input is, and may be named like anything)
-    const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_QUICKLOOK_SUFFIX, ".TIFF") : out;
+    // (not FilterOutputPath: a quick look is a .TIFF -- a .JPG with --format jpeg -- whatever the input is, and may be named like
+    // anything: the name's extension is not inspected)
+    const std::string path = out.empty() ? IMO::BuildOutputFilePath(file, OIP_QUICKLOOK_SUFFIX, o.jpeg ? ".JPG" : ".TIFF") : out;
     GuardOutput(path, {file}, "quicklook", o.force);
     return path;
 }
@@ -377,6 +382,9 @@ inline void RunQuicklook(const std::string &file, const std::string &out, const 
     auto alloc_planes = [&]() {
         ow = (bw + F - 1) / F;
         oh = (nLines + F - 1) / F;
+        if (o.jpeg && (ow > OIP_JPEG_MAX_DIM || oh > OIP_JPEG_MAX_DIM))
+            throw std::invalid_argument("quicklook: a JPEG holds at most " + std::to_string(OIP_JPEG_MAX_DIM) + " x " + std::to_string(OIP_JPEG_MAX_DIM) +
+                                        " pixels and the browse image has " + std::to_string(ow) + " x " + std::to_string(oh) + ": use a larger --factor");
         plane = (size_t)ow * oh;
         planes.alloc(plane * nb);
     };
@@ -428,10 +436,24 @@ inline void RunQuicklook(const std::string &file, const std::string &out, const 
     luts.upload(lut.data(), lut.size());
     DevBuf<uint8_t> img8(plane * nch);
     ck(oip_apply_lut_u8(ctx, chan, ow, ow, oh, nch, luts.p, img8.p));
-    std::vector<uint8_t> host(plane * nch);
-    img8.download(host.data(), host.size());
-    OLOG("Write quick look (%d x %ld, %s) to file '%s' ...", ow, oh, nch == 1 ? "grey" : "RGB", outPath.c_str());
-    write_tiff_u8(outPath, host.data(), ow, oh, nch);
+    if (o.jpeg) {
+        // the scan is encoded where img8 lies; the payload (the capacity is the coder's bound, the bytes written are the file's)
+        // and the interval table come back
+        DevBuf<uint8_t> payload(oip_jpeg_worst_bytes(ow, oh, nch));
+        std::vector<uint64_t> off((size_t)(oh + 7) / 8), len(off.size());
+        size_t bytes = 0;
+        ck(oip_jpeg_scan_u8(ctx, img8.p, (long)ow * nch, ow, oh, nch, o.quality, payload.p, payload.n, off.data(), len.data(), &bytes, nullptr, 0));
+        std::vector<uint8_t> host(bytes);
+        payload.download(host.data(), host.size());
+        OLOG("Write quick look (%d x %ld, %s; JPEG, quality %d) to file '%s' ...", ow, oh, nch == 1 ? "grey" : "RGB", o.quality, outPath.c_str());
+        char err[1024] = "";
+        if (oip_write_jpeg_u8(outPath.c_str(), host.data(), off.data(), len.data(), ow, oh, nch, o.quality, err, sizeof err) != OIP_OK) throw errno_error(err, 0);
+    } else {
+        std::vector<uint8_t> host(plane * nch);
+        img8.download(host.data(), host.size());
+        OLOG("Write quick look (%d x %ld, %s) to file '%s' ...", ow, oh, nch == 1 ? "grey" : "RGB", outPath.c_str());
+        write_tiff_u8(outPath, host.data(), ow, oh, nch);
+    }
     LogThroughput(inBytes, total.tick());
 }
 
